@@ -12,10 +12,17 @@ per-GPU work fixed).  One "step" = one minibatch step of one learner; value = N*
 Inputs are synthetic (seeded uniform uint8 frames tiled into the ring, no emulator) and already
 resident in HBM when the timed region starts.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step (the milliseconds
+of one timed step) and the configuration.  A plain run does only what that line needs: set-up, W warm-up
+steps, the K timed steps.  --full adds everything else to the line, among it:
   roofline     — the step's dominant kernel, timed live with HIP events on the library stream inside the
-                 timed region; algorithmic bytes/flops per launch from DESIGN.md / SURVEY.md §8d.
-  cpu_baseline — the numpy oracle (a restatement: kind "port") timed on this host's cores, rank 0, N=1 only.
+                 timed region; algorithmic bytes/flops per launch from DESIGN.md / SURVEY.md §8d;
+  cpu_baseline — the numpy oracle (a restatement: kind "port") timed on this host's cores, rank 0, N=1 only;
+and per-kernel times, the standalone replay gather at B and at B = 4096, the oracle comparison
+(q_mae_vs_cpu_ref), the other configurations (config_fp16, config_b256, ...) and the host-bound loops
+(tuple_api, agent_loop), all measured after the timed region.
+--dump-outputs DIR writes what the timed path computed in its last step (Q-values of the last minibatch,
+the network's weights and optimizer state, the sampler state) as DIR/<name>.npy, float32 or float64.
 """
 import argparse
 import json
@@ -285,6 +292,36 @@ def fill_ring(mem, seed, num_actions):
     mem.terminals[:] = rng.rand(size) < 0.005
     mem.count, mem.current = size, size // 3
     mem.sync_mirror()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(net, mt, out_dir):
+    """--dump-outputs: what a caller of the timed path holds after its last step, one DIR/<name>.npy per array — the Q-values of
+    the last minibatch (online net on the prestates, target net's max over actions on the poststates), the online and target
+    weights and the RMSProp state per layer (Neon layouts), BatchNorm parameters and running statistics with --batch-norm, and
+    the 625-word sampler state (float64: exact).  About 20 MB at the default shapes."""
+    import numpy as np
+    q, max_q_post = net.last_q()
+    arrays = {"q_online_last_minibatch": q, "max_q_target_last_minibatch": max_q_post,
+              "sampler_state": np.array(mt[:], dtype=np.float64)}
+    layers = ("conv1", "conv2", "conv3", "fc4", "fc5")
+    for which, key in ((0, "online"), (1, "target"), (2, "rmsprop_s")):
+        for name, w in zip(layers, net.get_weights(which)):
+            arrays["%s_%s" % (key, name)] = w
+    if net.batch_norm:
+        for l, name in enumerate(layers[:4]):
+            for which, key in ((0, "online"), (1, "target"), (2, "rmsprop_s")):
+                arrays["%s_bn_%s" % (key, name)] = np.stack(net.get_bn(l, which))
+            for which, key in ((0, "online"), (1, "target")):
+                arrays["%s_bn_running_%s" % (key, name)] = np.stack(net.get_bn(l, which, running=True))
+    arrays = {k: np.asarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, "outputs of %d bytes exceed the %d-byte limit of --dump-outputs" % (total, DUMP_LIMIT_BYTES)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def cpu_baseline(B, A, seed, budget_s):
@@ -914,7 +951,14 @@ def main():
     ap.add_argument("--zero-copy", action="store_true", help="gather from the pinned host ring over PCIe (no HBM mirror)")
     ap.add_argument("--no-fp16-leg", action="store_true", help="skip the BASELINE configs[4] leg (A=6, float16) that the default B=32 fp32 run appends as `config_fp16`")
     ap.add_argument("--no-b256", action="store_true", help="skip the BASELINE configs[2] leg (B=256, A=3) that the default B=32 fp32 run appends as `config_b256`")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: roofline and per-kernel times, standalone gathers, the "
+                         "oracle comparison, the other configurations' legs, host-bound loops and CPU baselines (the --no-* options trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (rank 0)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -1006,48 +1050,52 @@ def main():
     # ---- the standalone replay-gather measurements (getMinibatch()'s kernel at B and at B = 4096) run FIRST: other kernels on
     # other buffers, and they leave the device at its working clocks before the W warm-up steps (a 5-step warm-up straight after
     # the ring upload otherwise starts the timed region on a device that is still ramping: tools/exp/short_run_rate.sh)
+    # A plain run keeps the launches at B as part of its warm-up (a few milliseconds) and reports nothing from them.
     pre = {}
     if rank == 0 and world == 1 and a.datatype == "float32" and not a.batch_norm:
         # a fresh index set per launch, like consecutive getMinibatch() calls (one repeated set would be read from L2 / MALL, not HBM)
         idx = np.array([mem.sample_indexes().copy() for _ in range(256)])
         g_ms = mem.bench_gather(idx, iters=512)
-        pre["replay_gather"] = roofline_entry(14, "replay_gather_u8", g_ms, B, A)
-        pre["replay_gather"]["index_sets"] = 256
-        if not a.profile_run:
+        if a.full:
+            pre["replay_gather"] = roofline_entry(14, "replay_gather_u8", g_ms, B, A)
+            pre["replay_gather"]["index_sets"] = 256
+        if a.full and not a.profile_run:
             try:
                 pre["replay_gather_large"] = gather_large(sd, make_args, fill_ring, A)
             except Exception as e:
                 pre["replay_gather_large"] = {"error": repr(e)[:200]}
             pre["box"] = box_check(pre["replay_gather_large"])
 
-    # ---- warmup (untimed): includes a pass with every kernel bracketed to find the dominant one
+    # ---- warmup (untimed); with --full its last n_prof steps run with every kernel bracketed to find the dominant one
     n_prof = min(60, max(a.warmup // 2, 1)) if a.warmup else 20      # W = 0 still needs a pass to find the dominant kernel
     run(max(a.warmup - n_prof, 3))                                   # at least 3: the first launches also load the code objects
-    net.profile(True, -1)
-    net.profile_reset()
+    if a.full:
+        net.profile(True, -1)
+        net.profile_reset()
     run(n_prof)
-    prof = net.profile_read()
-    net.profile(False)
-    step_kernels = [p for p in prof if p["launches"] > 0]
-    per_step = [p for p in step_kernels if p["launches"] >= n_prof] or step_kernels    # not the one-off prep / gather launches
-    dom = max(per_step, key=lambda p: p["total_ms"])
-    # timed region: the dominant kernel stays bracketed with HIP events, but only every N-th launch — an event pair costs
-    # 2-3 us of queue time, and bracketing every launch took 7 % off the step rate it is supposed to observe
-    # every N-th launch of the dominant kernel is bracketed, launch 0 included, so even the driver's 20-step run has a live
-    # bracket inside the timed region.  Measured on MI355X: an event pair in the dependent launch chain
-    # costs far more than its own 2-3 us (bracketing EVERY launch of a 20-step run: -7 % step rate; every 4th: -2.3 %).
-    # (round 2, after the per-step event record was removed from train_many: even every 16th launch was 0.7 us per step — 74.0 vs 74.8 —
-    #  so every 64th: launch 0 of the timed region is always bracketed, 47 brackets in the default 3 000-step run)
-    every = 64
-    # (round 4, VERDICT r3 weak #7b) ... and in short regions every 5th launch, so that the driver's 20-step form carries FOUR live
-    # brackets instead of one: profile_mode 1 hands the event pair to the launch itself (dispatch-packet timestamps, nothing added
-    # to the queue) — tools/exp/short_region.py A/B: the 20-step rate with every = 5 equals the rate with every = 64 within noise
-    if a.steps <= 320:
-        every = 5
-    every = int(os.environ.get("SDQN_BENCH_PROFILE_EVERY", every))
-    net.set_option("profile_every", every)
-    net.profile(True, dom["id"])
-    net.profile_reset()
+    if a.full:
+        prof = net.profile_read()
+        net.profile(False)
+        step_kernels = [p for p in prof if p["launches"] > 0]
+        per_step = [p for p in step_kernels if p["launches"] >= n_prof] or step_kernels    # not the one-off prep / gather launches
+        dom = max(per_step, key=lambda p: p["total_ms"])
+        # timed region: the dominant kernel stays bracketed with HIP events, but only every N-th launch — an event pair costs
+        # 2-3 us of queue time, and bracketing every launch took 7 % off the step rate it is supposed to observe
+        # every N-th launch of the dominant kernel is bracketed, launch 0 included, so even the driver's 20-step run has a live
+        # bracket inside the timed region.  Measured on MI355X: an event pair in the dependent launch chain
+        # costs far more than its own 2-3 us (bracketing EVERY launch of a 20-step run: -7 % step rate; every 4th: -2.3 %).
+        # (round 2, after the per-step event record was removed from train_many: even every 16th launch was 0.7 us per step — 74.0 vs 74.8 —
+        #  so every 64th: launch 0 of the timed region is always bracketed, 47 brackets in the default 3 000-step run)
+        every = 64
+        # (round 4, VERDICT r3 weak #7b) ... and in short regions every 5th launch, so that the driver's 20-step form carries FOUR live
+        # brackets instead of one: profile_mode 1 hands the event pair to the launch itself (dispatch-packet timestamps, nothing added
+        # to the queue) — tools/exp/short_region.py A/B: the 20-step rate with every = 5 equals the rate with every = 64 within noise
+        if a.steps <= 320:
+            every = 5
+        every = int(os.environ.get("SDQN_BENCH_PROFILE_EVERY", every))
+        net.set_option("profile_every", every)
+        net.profile(True, dom["id"])
+        net.profile_reset()
 
     # ---- timed region: EXACTLY K steps
     barrier()
@@ -1062,18 +1110,21 @@ def main():
         t = torch.tensor([el], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t[0])
+    if a.dump_outputs and rank == 0:
+        dump_outputs(net, mt, a.dump_outputs)
     dp_b256 = None
-    if world > 1 and B == 32 and a.datatype == "float32" and not a.batch_norm and not a.no_b256 and not a.profile_run:
+    if a.full and world > 1 and B == 32 and a.datatype == "float32" and not a.batch_norm and not a.no_b256 and not a.profile_run:
         try:
             dp_b256 = dp_b256_leg(sd, make_args, dist, torch, rank, world, dev, a.seed, a.dry_run_dp)
         except Exception as e:                                         # (a rank that raises here has already left the others' collectives: report)
             dp_b256 = {"error": repr(e)[:300]}
-    live = [p for p in net.profile_read() if p["id"] == dom["id"]][0]
-    live_src = "timed region, every %d%s launch carries start/stop events (kernel-packet timestamps)" % (every, "th" if every > 3 else ("nd" if every == 2 else "rd"))
-    if live["launches"] == 0:                                        # (K = 0)
-        live, live_src = dom, "warm-up pass (no timed launches)"
-    net.profile(False)
-    net.set_option("profile_every", 1)
+    if a.full:
+        live = [p for p in net.profile_read() if p["id"] == dom["id"]][0]
+        live_src = "timed region, every %d%s launch carries start/stop events (kernel-packet timestamps)" % (every, "th" if every > 3 else ("nd" if every == 2 else "rd"))
+        if live["launches"] == 0:                                    # (K = 0)
+            live, live_src = dom, "warm-up pass (no timed launches)"
+        net.profile(False)
+        net.set_option("profile_every", 1)
 
     if rank == 0:
         total_steps = a.steps * world
@@ -1105,60 +1156,61 @@ def main():
                          "allreduce_model": allreduce_model(world, payload),
                          "allreduce_model_all_n": {str(n): allreduce_model(n, payload)["expected_us"] for n in (2, 4, 8)},
                          "devices": [r["bound_device"] for r in dp_rows], "dry_run": bool(a.dry_run_dp), "per_rank": dp_rows}
-        if dp_b256 is not None:
-            out["config_b256"] = dp_b256
-        _ku, _chained = chained_convs({p["name"]: 0 for p in step_kernels})
-        if _chained and dom["id"] == 1:             # B >= 128: conv2 + conv3 forward are one launch under kernel id 1
-            out["roofline"] = roofline_entry("conv23", "conv2_fwd+conv3_fwd (one chained sample-stationary launch)", live["total_ms"] / max(live["launches"], 1), B, A)
-        else:
-            out["roofline"] = roofline_entry(dom["id"], dom["name"], live["total_ms"] / max(live["launches"], 1), B, A)
-        out["roofline"]["measured_in"] = live_src
-        out["roofline"]["launches_bracketed"] = int(live["launches"])
-        if a.datatype == "float32" and not a.batch_norm:
-            out["roofline_step"] = step_roofline(B, A, el / a.steps * 1e3)
-        out["kernels_us"] = chained_convs({p["name"]: round(p["total_ms"] / p["launches"] * 1e3, 2) for p in step_kernels})[0]
-        out["fc_mfma_utilisation"] = fc_mfma_util(B, A)
         if a.batch_norm:
             out["config"]["workload"] += " [--batch_norm]"
-        if world == 1 and a.datatype == "float32" and not a.batch_norm:
-            out.update(pre)                                    # replay_gather, replay_gather_large: measured before the warm-up
-            if not a.profile_run:
-                # (B > 64: three steps — gate flips are 8x as likely per step at B = 256 and an oracle step costs ~1 s there;
-                #  the free-running number is judged against the fp64 yardstick at every size)
-                out["q_mae_vs_cpu_ref"] = q_mae_on_timed_ring(net, mem, B, A, mt, steps=10 if B <= 64 else 3)
-            out["north_star_target"] = north_star_target(out, sd, B, A)
-            if B == 32 and not a.no_fp16_leg and not a.profile_run and not a.zero_copy:
-                try:
-                    out["config_fp16"] = fp16_leg(sd, make_args, a.seed)
-                except Exception as e:                         # never let the side leg break the headline line
-                    out["config_fp16"] = {"error": repr(e)[:300]}
-            if B == 32 and not a.no_b256 and not a.profile_run and not a.zero_copy:
-                try:
-                    out["config_b256"] = b256_leg(sd, make_args, a.seed)
-                except Exception as e:                         # never let the side leg break the headline line
-                    out["config_b256"] = {"error": repr(e)[:300]}
-                if not a.no_fp16_leg:
+        if a.full:
+            if dp_b256 is not None:
+                out["config_b256"] = dp_b256
+            _ku, _chained = chained_convs({p["name"]: 0 for p in step_kernels})
+            if _chained and dom["id"] == 1:             # B >= 128: conv2 + conv3 forward are one launch under kernel id 1
+                out["roofline"] = roofline_entry("conv23", "conv2_fwd+conv3_fwd (one chained sample-stationary launch)", live["total_ms"] / max(live["launches"], 1), B, A)
+            else:
+                out["roofline"] = roofline_entry(dom["id"], dom["name"], live["total_ms"] / max(live["launches"], 1), B, A)
+            out["roofline"]["measured_in"] = live_src
+            out["roofline"]["launches_bracketed"] = int(live["launches"])
+            if a.datatype == "float32" and not a.batch_norm:
+                out["roofline_step"] = step_roofline(B, A, el / a.steps * 1e3)
+            out["kernels_us"] = chained_convs({p["name"]: round(p["total_ms"] / p["launches"] * 1e3, 2) for p in step_kernels})[0]
+            out["fc_mfma_utilisation"] = fc_mfma_util(B, A)
+            if world == 1 and a.datatype == "float32" and not a.batch_norm:
+                out.update(pre)                                    # replay_gather, replay_gather_large: measured before the warm-up
+                if not a.profile_run:
+                    # (B > 64: three steps — gate flips are 8x as likely per step at B = 256 and an oracle step costs ~1 s there;
+                    #  the free-running number is judged against the fp64 yardstick at every size)
+                    out["q_mae_vs_cpu_ref"] = q_mae_on_timed_ring(net, mem, B, A, mt, steps=10 if B <= 64 else 3)
+                out["north_star_target"] = north_star_target(out, sd, B, A)
+                if B == 32 and not a.no_fp16_leg and not a.profile_run and not a.zero_copy:
                     try:
-                        out["config_fp16_b256"] = fp16_b256_leg(sd, make_args, a.seed)
-                    except Exception as e:
-                        out["config_fp16_b256"] = {"error": repr(e)[:300]}
-            if B == 32 and not a.profile_run and not a.zero_copy and not a.no_b256:
-                # the reference's own call pattern and the agent loop: host-side rates, after the timed region
-                for key, fn in (("tuple_api", tuple_api_leg), ("agent_loop", agent_loop_leg)):
+                        out["config_fp16"] = fp16_leg(sd, make_args, a.seed)
+                    except Exception as e:                         # never let the side leg break the headline line
+                        out["config_fp16"] = {"error": repr(e)[:300]}
+                if B == 32 and not a.no_b256 and not a.profile_run and not a.zero_copy:
                     try:
-                        out[key] = fn(sd, make_args, a.seed)
+                        out["config_b256"] = b256_leg(sd, make_args, a.seed)
+                    except Exception as e:                         # never let the side leg break the headline line
+                        out["config_b256"] = {"error": repr(e)[:300]}
+                    if not a.no_fp16_leg:
+                        try:
+                            out["config_fp16_b256"] = fp16_b256_leg(sd, make_args, a.seed)
+                        except Exception as e:
+                            out["config_fp16_b256"] = {"error": repr(e)[:300]}
+                if B == 32 and not a.profile_run and not a.zero_copy and not a.no_b256:
+                    # the reference's own call pattern and the agent loop: host-side rates, after the timed region
+                    for key, fn in (("tuple_api", tuple_api_leg), ("agent_loop", agent_loop_leg)):
+                        try:
+                            out[key] = fn(sd, make_args, a.seed)
+                        except Exception as e:
+                            out[key] = {"error": repr(e)[:300]}
+                if not a.no_cpu_baseline:
+                    out["cpu_baseline"] = cpu_baseline(B, A, a.seed, a.cpu_baseline_seconds)
+                    try:
+                        out["cpu_baseline_reference_getminibatch"] = cpu_reference_getminibatch(B, A, a.seed, 3.0)
                     except Exception as e:
-                        out[key] = {"error": repr(e)[:300]}
-            if not a.no_cpu_baseline:
-                out["cpu_baseline"] = cpu_baseline(B, A, a.seed, a.cpu_baseline_seconds)
-                try:
-                    out["cpu_baseline_reference_getminibatch"] = cpu_reference_getminibatch(B, A, a.seed, 3.0)
-                except Exception as e:
-                    out["cpu_baseline_reference_getminibatch"] = {"value": None, "kind": "reference", "error": repr(e)[:200]}
-                try:
-                    out["cpu_standin_torch"] = cpu_standin_torch(B, A, a.seed, 5.0)
-                except Exception as e:                         # never let the optional row break the bench line
-                    out["cpu_standin_torch"] = {"error": repr(e)[:200]}
+                        out["cpu_baseline_reference_getminibatch"] = {"value": None, "kind": "reference", "error": repr(e)[:200]}
+                    try:
+                        out["cpu_standin_torch"] = cpu_standin_torch(B, A, a.seed, 5.0)
+                    except Exception as e:                         # never let the optional row break the bench line
+                        out["cpu_standin_torch"] = {"error": repr(e)[:200]}
     # The JSON line must be the LAST line of the job's stdout.  RCCL prints a version banner through C stdio, which
     # is block-buffered on a pipe and would otherwise be flushed at process exit — after the JSON, from every rank.
     # So: tear the communicators down, flush C stdio on every rank, barrier, and only then let rank 0 print.

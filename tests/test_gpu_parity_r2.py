@@ -795,7 +795,7 @@ def test_bench_dry_run_dp_two_ranks(sd):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29541", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "30", "--warmup", "10",
-           "--replay-size", "20000", "--no-cpu-baseline", "--dry-run-dp"]
+           "--replay-size", "20000", "--no-cpu-baseline", "--dry-run-dp", "--full"]
     p = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
@@ -830,13 +830,38 @@ def test_bench_driver_form_brackets_the_timed_region(sd):
     """in the driver's short form (--steps 20 --warmup 5) the roofline of the dominant kernel is measured
     by a live HIP-event bracket INSIDE the timed region (launch 0 is bracketed after profile_reset), not replayed from the
     warm-up pass; the parity leg reports explicit checks."""
-    out = _run_bench(["--steps", "20", "--warmup", "5", "--replay-size", "50000", "--no-cpu-baseline"])
+    out = _run_bench(["--steps", "20", "--warmup", "5", "--replay-size", "50000", "--no-cpu-baseline", "--full"])
     r = out["roofline"]
     assert r["measured_in"].startswith("timed region"), r["measured_in"]
     assert r["launches_bracketed"] >= 1 and 0 < r["frac"] <= 1.0
     q = out["q_mae_vs_cpu_ref"]
     assert q["mode"] == "free-running" and set(q["checks"]) and q["pass"] is True, q
     assert q["teacher_forced"]["mae"] < 1e-4
+
+
+def test_bench_plain_run_and_dumped_outputs(sd, tmp_path):
+    """A plain run (no --full) prints the headline line only and times exactly --steps steps; --dump-outputs writes the last step's
+    Q-values, weights, RMSProp state and sampler state as float32 / float64 .npy files within 64 MB, and two runs with the same
+    arguments write the same arrays (identical inputs: seeded ring, weights and sampler)."""
+    import glob, os
+    dumps = []
+    for run in ("a", "b"):
+        d = str(tmp_path / run)
+        out = _run_bench(["--steps", "7", "--warmup", "3", "--replay-size", "20000", "--dump-outputs", d])
+        assert out["steps"] == 7 and out["value"] > 0 and out["ms_per_step"] > 0 and out["higher_is_better"] is True
+        assert abs(out["ms_per_step"] - 1e3 / out["value"]) <= 1e-3 * out["ms_per_step"] + 1e-4
+        assert {"metric", "unit", "dtype"} <= set(out)
+        assert not {"roofline", "kernels_us", "q_mae_vs_cpu_ref", "config_fp16", "config_b256", "cpu_baseline", "replay_gather"} & set(out)
+        files = sorted(glob.glob(os.path.join(d, "*.npy")))
+        arrays = {os.path.basename(f)[:-4]: np.load(f) for f in files}
+        assert {"q_online_last_minibatch", "max_q_target_last_minibatch", "sampler_state", "online_fc4", "rmsprop_s_conv1"} <= set(arrays)
+        assert all(v.dtype in (np.float32, np.float64) for v in arrays.values())
+        assert sum(os.path.getsize(f) for f in files) <= 64 << 20
+        assert arrays["q_online_last_minibatch"].shape == (32, 4) and np.isfinite(arrays["q_online_last_minibatch"]).all()
+        dumps.append(arrays)
+    assert set(dumps[0]) == set(dumps[1])
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
 
 
 # ---- tuning hooks must not change the arithmetic ----------------------------------------------------------------------

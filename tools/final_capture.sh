@@ -4,14 +4,14 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/cap
 mkdir -p $O
 cd $R
-( time timeout 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err ) 2> $O/bench_default.time
-timeout 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_short.json 2>/dev/null
-timeout 200 python bench.py --datatype float16 --no-cpu-baseline --steps 3000 --warmup 300 > $O/bench_fp16.json 2>/dev/null
-timeout 200 python bench.py --datatype float16 --num-actions 6 --no-cpu-baseline --steps 3000 --warmup 300 --replay-size 200000 > $O/bench_fp16_a6.json 2>/dev/null
-timeout 200 python bench.py --batch-size 256 --num-actions 3 --no-cpu-baseline --steps 600 --warmup 100 --replay-size 200000 > $O/bench_b256.json 2>/dev/null
-timeout 200 python bench.py --batch-size 256 --num-actions 6 --no-cpu-baseline --steps 600 --warmup 100 --replay-size 200000 > $O/bench_b256_a6.json 2>/dev/null
-timeout 200 python bench.py --batch-size 256 --num-actions 3 --datatype float16 --no-cpu-baseline --steps 600 --warmup 100 --replay-size 200000 > $O/bench_b256_fp16.json 2>/dev/null
-timeout 200 python bench.py --single-rank-dp --no-cpu-baseline --steps 2000 --warmup 200 --replay-size 200000 > $O/bench_dp1.json 2>/dev/null
+( time timeout 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err ) 2> $O/bench_default.time
+timeout 200 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_short.json 2>/dev/null
+timeout 200 python bench.py --full --datatype float16 --no-cpu-baseline --steps 3000 --warmup 300 > $O/bench_fp16.json 2>/dev/null
+timeout 200 python bench.py --full --datatype float16 --num-actions 6 --no-cpu-baseline --steps 3000 --warmup 300 --replay-size 200000 > $O/bench_fp16_a6.json 2>/dev/null
+timeout 200 python bench.py --full --batch-size 256 --num-actions 3 --no-cpu-baseline --steps 600 --warmup 100 --replay-size 200000 > $O/bench_b256.json 2>/dev/null
+timeout 200 python bench.py --full --batch-size 256 --num-actions 6 --no-cpu-baseline --steps 600 --warmup 100 --replay-size 200000 > $O/bench_b256_a6.json 2>/dev/null
+timeout 200 python bench.py --full --batch-size 256 --num-actions 3 --datatype float16 --no-cpu-baseline --steps 600 --warmup 100 --replay-size 200000 > $O/bench_b256_fp16.json 2>/dev/null
+timeout 200 python bench.py --full --single-rank-dp --no-cpu-baseline --steps 2000 --warmup 200 --replay-size 200000 > $O/bench_dp1.json 2>/dev/null
 # the whole agent loop on the synthetic environment (README table row) and the reference-style tuple-API loop
 timeout 300 python -m simple_dqn_amd.main --replay_size 100000 --random_steps 5000 --train_steps 40000 --test_steps 20000 --epochs 1 --csv_file $O/agent_loop.csv > $O/agent_loop.log 2>&1
 timeout 300 python -m simple_dqn_amd.main --synthetic_frame_pool 0 --replay_size 100000 --random_steps 5000 --train_steps 40000 --test_steps 20000 --epochs 1 > $O/agent_loop_pool0.log 2>&1

@@ -280,6 +280,19 @@ int sdqn_net_set_option(sdqn_net_t h, const char* name, int value);
  * "dq","g","theta","cost_terms"; internal layouts documented in simple_dqn_amd/csrc/problems.h) */
 int sdqn_net_debug_read(sdqn_net_t h, const char* name, float* out, int64_t n);
 
+/* Filter visualisation (the reference's --visualization_file: src/main.py:119-127 -> visualization.py, Neon's DeconvCallback).  For
+ * each of the first F_l = min(K_l, max_fm) maps of conv1 / conv2 / conv3, the state n and output position p (row-major) with the largest
+ * PRE-activation z_l[n, f, p] over the n states — ties go to the smallest n / batch_size, then the smallest p, then the smallest
+ * n % batch_size (batch_size of the net: the reference's batch loop) — and that activation projected back to the input by guided
+ * backpropagation (ReLU-gated transposed convolutions) -> vis float[4][84][84].  States: either ring indexes idx[n] of r (frames
+ * (idx - 3 + j) mod count, getState's index math; the caller uploads edited ring slots first) or host states u8[n][4][84][84] with
+ * r = idx = NULL.  Records, in order conv1, conv2, conv3 (F_1 + F_2 + F_3 entries): rec_state, rec_pos, rec_value; vis_out
+ * float[records][4][84][84] (NULL: the search only); ms_out float[2] nullable: device ms of the search and of the projection launch.
+ * Online fp32 parameters (float16 nets: the same fp32 master weights), enqueued after pending work on the library stream (sync).
+ * SDQN_ERR_ARG for float64 / non-84x84x4 nets, batch_norm nets, max_fm < 1, n < 1 and an n whose tie key overflows 32 bits. */
+int sdqn_net_visualize(sdqn_net_t h, sdqn_replay_t r, const int64_t* idx, const uint8_t* states, int64_t n, int max_fm,
+                       int64_t* rec_state, int32_t* rec_pos, float* rec_value, float* vis_out, float* ms_out);
+
 /* per-kernel device timing (HIP events on the library stream; see option "profile_mode"), for bench.py's roofline leg.
  * kernel < 0 brackets every kernel of the step, otherwise only that kernel id. */
 int sdqn_net_profile(sdqn_net_t h, int enable, int kernel);

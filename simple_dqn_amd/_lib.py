@@ -103,6 +103,7 @@ SIGNATURES = {
     "sdqn_net_set_option": (C.c_int, [_vp, C.c_char_p, C.c_int]),
     "sdqn_net_set_epoch": (C.c_int, [_vp, C.c_int]),
     "sdqn_net_debug_read": (C.c_int, [_vp, C.c_char_p, _f32p, C.c_int64]),
+    "sdqn_net_visualize": (C.c_int, [_vp, _vp, _i64p, _u8p, C.c_int64, C.c_int, _i64p, C.POINTER(C.c_int32), _f32p, _f32p, _f32p]),
     "sdqn_net_profile": (C.c_int, [_vp, C.c_int, C.c_int]),
     "sdqn_net_profile_count": (C.c_int, [C.POINTER(C.c_int)]),
     "sdqn_net_profile_read": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_double), _i64p]),

@@ -384,6 +384,44 @@ class DeepQNetwork:
         self.train_iterations += 1
         return cost.value if want_cost else None
 
+    def visualize(self, states=None, mem=None, indexes=None, max_fm=4, timing=None):
+        """Guided-backpropagation filter visualisation (the reference's --visualization_file; visualization.py, Neon's DeconvCallback).
+        The states are host arrays u8[N,4,84,84] or ring indexes of a ReplayMemory (mem + indexes: getState(i) of each, read on the
+        device).  Returns one dict per conv layer with, for each of its first min(K, max_fm) maps, the winning state ("state": its
+        position in `states` / `indexes`), output position ("pos", row-major), pre-activation value ("value") and the projection
+        ("vis": float32 [F,4,84,84]).  timing: a dict that receives the device ms of the two launches ("search_ms", "project_ms")."""
+        if self._f64 or self.screen_dim != (84, 84) or self.history_length != 4:
+            raise NotImplementedError("filter visualisation is implemented for 84x84x4 float32 / float16 networks")
+        if self.batch_norm:
+            raise NotImplementedError("filter visualisation is not implemented for batch_norm networks")
+        if (states is None) == (mem is None) or (mem is None) != (indexes is None):
+            raise ValueError("give either states or (mem, indexes)")
+        if mem is not None:
+            idx = np.ascontiguousarray(indexes, dtype=np.int64).reshape(-1)
+            n = idx.size
+            mem._check_mirror()                                    # slots edited through the numpy views reach the HBM ring first
+            src = (mem._h, _lib.ptr(idx, C.c_int64), None)
+        else:
+            st = np.ascontiguousarray(states, dtype=np.uint8)
+            assert st.ndim == 4 and st.shape[1:] == (4, 84, 84), st.shape
+            n = st.shape[0]
+            src = (None, None, _lib.ptr(st, C.c_uint8))
+        F = [min(k, int(max_fm)) for k in (32, 64, 64)] if max_fm >= 1 else [0, 0, 0]
+        R = sum(F)
+        rs, rp = np.zeros(max(R, 1), np.int64), np.zeros(max(R, 1), np.int32)
+        rv, vis = np.zeros(max(R, 1), np.float32), np.zeros((max(R, 1), 4, 84, 84), np.float32)
+        ms = np.zeros(2, np.float32)
+        _lib.check(self._lib.sdqn_net_visualize(self._h, src[0], src[1], src[2], int(n), int(max_fm), _lib.ptr(rs, C.c_int64),
+                                                _lib.ptr(rp, C.c_int32), _lib.ptr(rv, C.c_float), _lib.ptr(vis, C.c_float),
+                                                _lib.ptr(ms, C.c_float) if timing is not None else None))
+        if timing is not None:
+            timing["search_ms"], timing["project_ms"] = float(ms[0]), float(ms[1])
+        out, o = [], 0
+        for f in F:
+            out.append({"state": rs[o:o + f].copy(), "pos": rp[o:o + f].copy(), "value": rv[o:o + f].copy(), "vis": vis[o:o + f].copy()})
+            o += f
+        return out
+
     def set_option(self, name, value):
         """Tuning / test hooks of the library (sdqn_net_set_option), e.g. 'keep_gradients' (materialise the fc4 gradient; disables the
         fused fc4 RMSProp), 'fused_launches', 'bt:<kernel id>' (throughput-regime menu), 'nw:<id>', 'tps:<layer>', 's4'.  Retired

@@ -37,6 +37,9 @@ _OPTIONS = {
         ("--exploration_decay_steps", float, 1000000), ("--exploration_rate_test", float, 0.05),
         ("--train_frequency", int, 4), ("--train_repeat", int, 1), ("--target_steps", int, 10000), ("--random_starts", int, 30),
     ],
+    "Visualization": [
+        ("--visualization_filters", int, 4), ("--visualization_file", str, None),
+    ],
     "Main loop": [
         ("--random_steps", int, 50000), ("--train_steps", int, 250000), ("--test_steps", int, 125000), ("--epochs", int, 200),
         ("--start_epoch", int, 0), ("--play_games", int, 0),
@@ -83,11 +86,19 @@ def run(args):
     stats = Statistics(agent, net, mem, env, args)
     if args.load_weights:
         net.load_weights(args.load_weights)
-    if args.play_games:                                              # :112-128 (visualisation out of scope)
+    if args.play_games:                                              # :112-128
         env.setMode('test')
         stats.reset()
         agent.play(args.play_games)
         stats.write(0, "play")
+        if args.visualization_file:                                  # the states of the game just played, straight from the device ring
+            from .visualization import visualize
+            indexes = range(agent.history_length, mem.current - agent.random_starts)
+            if len(indexes) == 0:
+                raise ValueError("no game states to visualise: range(%d, current %d - random_starts %d) is empty (the replay memory must "
+                                 "hold the whole game)" % (agent.history_length, mem.current, agent.random_starts))
+            logger.info("visualising ring indexes %d..%d: %d states of the game played" % (indexes[0], indexes[-1], len(indexes)))
+            visualize(net, mem, args.visualization_filters, args.visualization_file, indexes=indexes)
         return stats
     if args.random_steps:                                            # :130-137
         env.setMode('train')

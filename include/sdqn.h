@@ -234,7 +234,8 @@ int sdqn_net_grad_to_half(sdqn_net_t h, uint16_t* half_out, int64_t n);
 int sdqn_net_grad_from_half(sdqn_net_t h, const uint16_t* half_in, int64_t n);
 /* {overflow flag of the last from-half pass, log2 of the payload scale, clean steps since the scale last moved}; sync */
 int sdqn_net_half_payload_state(sdqn_net_t h, int* flag, int* scale_log2, int* clean_steps);
-/* q-values of the last train step: preq float[B,A] (online, prestates), maxpostq float[B] (sync) */
+/* q-values of the last train step: preq float[B,A] (online, prestates), maxpostq float[B] = the bootstrap value: max_a Q(theta-, post),
+ * or with option "double_dqn" Q(theta-, post)[argmax_a Q(theta, post)] (first maximum on ties) (sync) */
 int sdqn_net_last_q(sdqn_net_t h, float* preq, float* maxpostq);
 int sdqn_net_train_iterations(sdqn_net_t h, int64_t* n);     /* deepqnetwork.py:168 */
 /* float16 mode under data parallel: the gradient is all-reduced as IEEE half with a dynamic power-of-two payload scale
@@ -251,7 +252,12 @@ int sdqn_net_set_epoch(sdqn_net_t h, int epoch);
  *              2 fused with fc4's all-reduce + update overlapped on the second communicator   3 one launch per problem   4 generic path
  *   update:    0 one update launch   1 serial data parallel (local sums, all-reduce, apply)   2 overlapped data parallel   3 grad_only */
 int sdqn_net_step_structure(sdqn_net_t h, int* structure, int* update);
-/* options: "grad_only" (see sdqn_net_apply_update), "keep_gradients" (1: the fc4 gradient is materialised and readable with which=3; 0 (default): on one
+/* option "double_dqn" (0 default / 1, any configuration, switchable between steps): Double DQN targets (van Hasselt, Guez and Silver
+ * 2016): the online net picks each poststate's action, the target net values it (see sdqn_net_last_q).  The online net's forward on
+ * the poststates rides as a third net slot in the step's own forward launches (batch_norm: a forward of its own in front of the step,
+ * inference mode with the running statistics as they stand before the step); without a target net (target_enabled = 0) it is the
+ * standard step.
+ * options: "grad_only" (see sdqn_net_apply_update), "keep_gradients" (1: the fc4 gradient is materialised and readable with which=3; 0 (default): on one
  * GPU RMSProp of fc4 is fused into the wgrad epilogue), "two_streams" (0 default; 1: wgrad kernels overlap the dgrad chain on a side stream), "fused_launches" (1 default:
  * independent backward stages share one grid), "xcd_map" (0 default = only where it wins time: conv1/conv2/fc4 forward; 1: the
  * XCD-contiguous workgroup->tile map for every launch), "dp_overlap" (BEFORE sdqn_dp_init: -1 default = auto — second communicator for

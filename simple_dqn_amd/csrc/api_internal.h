@@ -103,6 +103,9 @@ struct sdqn_net_s {
          *h_d2p = nullptr, *h_d2 = nullptr, *h_d1 = nullptr, *wh[2] = {nullptr, nullptr}, *wht[2] = {nullptr, nullptr};
   float *d3p = nullptr, *d2p = nullptr, *d1 = nullptr, *slab1 = nullptr, *slab2 = nullptr, *slab3 = nullptr;
   float *q = nullptr, *maxq = nullptr, *dq = nullptr, *cost_terms = nullptr, *cost_out = nullptr; double* cost_accum = nullptr;
+  // --double_dqn (option "double_dqn"): the forward launches carry a third net slot (problems.h: wslot); a1..a3, slab4, a4, q (and
+  // h_a1..h_a3) are re-allocated with room for it when the option is first switched on
+  bool double_dqn = false, slots3 = false;
   uint8_t *st_states = nullptr, *st_act = nullptr, *st_term = nullptr; int64_t* st_rew = nullptr; int64_t* d_idx = nullptr;
   int64_t* d_idx_t = nullptr;              // hoist: the NEXT step's indexes (copied from their pinned slot by an extra workgroup of the head launch)
                                            // Built, bit-identical, measured 1.8 % SLOWER (tools/exp/README.md) -> off; set_option "hoist"

@@ -140,7 +140,7 @@ __device__ __forceinline__ void conv_ss_body(const Args& c, float* const smem, K
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   SS_STAMP_INIT;
-  const int z = (int)blockIdx.x / c.G, g = (int)blockIdx.x - z * c.G;
+  const int z = (int)blockIdx.x / c.G, g = (int)blockIdx.x - z * c.G;     // net slot (problems.h: slot 2 = online weights, w[z & 1])
   const int n0 = g * C::NS;
   const int nvalid = c.B - n0 < C::NS ? c.B - n0 : C::NS;               // samples of this workgroup (the last one of an odd batch has one)
 
@@ -159,7 +159,7 @@ __device__ __forceinline__ void conv_ss_body(const Args& c, float* const smem, K
     const float* const isrc = c.in + ((int64_t)z * c.B + n0) * (C::HI * C::WI * C::CI);
     // (global loads in their scalar-base form — global_load_dwordx4 v, v_lane_offset, s[base] — the base moved per piece on the scalar
     //  unit; buffer loads with a scalar offset would do as well, but hipcc waits for them with vmcnt(0) whatever their order)
-    const char* const wsrc = reinterpret_cast<const char*>(c.w[z]);
+    const char* const wsrc = reinterpret_cast<const char*>(c.w[z & 1]);
     auto ldb = [&](const char* base, unsigned voff, int soff) { return *reinterpret_cast<const f32x4*>(base + soff + voff); };
     f32x4 wv[NR][C::WP];                                                 // weight chunks in flight (prologue: four; later one)
     f32x4 r0[C::P0];                                                     // first rows
@@ -279,7 +279,7 @@ __device__ __forceinline__ void conv_ss_body(const Args& c, float* const smem, K
       for (int d = 0; d < NR; ++d) {
         const int pc = CN::rord(d / CN::S) * CN::S + d % CN::S;
 #pragma unroll
-        for (int j = 0; j < CN::WP; ++j) keep.w[d * CN::WP + j] = ldb(reinterpret_cast<const char*>(cn_w[z]), wvo, pc * (CN::CI * NO * 4) + 4096 * j);
+        for (int j = 0; j < CN::WP; ++j) keep.w[d * CN::WP + j] = ldb(reinterpret_cast<const char*>(cn_w[z & 1]), wvo, pc * (CN::CI * NO * 4) + 4096 * j);
       }
     }
     auto round = [&](int pi) {

@@ -100,8 +100,8 @@ __global__ void __launch_bounds__(NT_) conv_ssh_chain_kernel(const Args c) {
   constexpr int IPC = NS * PX1 * 4, IPT = (IPC + NT_ - 1) / NT_;            // 16-byte pieces of the image / per thread
   constexpr int W2P = NO * KK2 / 8 / NT_, W3P = NO * KK3 / 8 / NT_;         // 8, 9 pieces per thread
   static_assert(W2P * NT_ * 8 == NO * KK2 && W3P * NT_ * 8 == NO * KK3, "whole weight pieces per thread");
-  const u32x4* const w2p = reinterpret_cast<const u32x4*>(c.w2[z]);
-  const u32x4* const w3p = reinterpret_cast<const u32x4*>(c.w3[z]);
+  const u32x4* const w2p = reinterpret_cast<const u32x4*>(c.w2[wslot(z)]);
+  const u32x4* const w3p = reinterpret_cast<const u32x4*>(c.w3[wslot(z)]);
   u32x4 w2v[W2P], w3v[W3P];
   if constexpr (C1) {
     // ---- conv1 in front (deepqnetwork.py:83 + the gather and the / 255 of :94-100): per sample, the state's four frames (28 224 contiguous
@@ -113,7 +113,7 @@ __global__ void __launch_bounds__(NT_) conv_ssh_chain_kernel(const Args c) {
     h_t* const cw = rw + 4 * 84 * 84;                                        // W1^T [32][256 + 8]
     auto frames = [&](int sI, u32x4 (&fv)[FPT]) {
       const int nn = n0 + (sI < nvalid ? sI : nvalid - 1);
-      const int64_t fb = c.from_ring ? (c.idx[nn] - 4 + z) * (int64_t)(84 * 84) : ((int64_t)z * c.B + nn) * (int64_t)(4 * 84 * 84);      // problems.h: sbase
+      const int64_t fb = c.from_ring ? (c.idx[nn] - 4 + sslot(z)) * (int64_t)(84 * 84) : ((int64_t)sslot(z) * c.B + nn) * (int64_t)(4 * 84 * 84);      // problems.h: sbase
       const u32x4* const fp = reinterpret_cast<const u32x4*>(c.src + fb);
 #pragma unroll
       for (int j = 0; j < FPT; ++j) { const int it = tid + NT_ * j; fv[j] = fp[it < FPC ? it : FPC - 1]; }
@@ -121,7 +121,7 @@ __global__ void __launch_bounds__(NT_) conv_ssh_chain_kernel(const Args c) {
     u32x4 fv[2][FPT], w1v[2];
     frames(0, fv[0]);
 #pragma unroll
-    for (int j = 0; j < 2; ++j) w1v[j] = reinterpret_cast<const u32x4*>(c.w1[z])[tid + NT_ * j];
+    for (int j = 0; j < 2; ++j) w1v[j] = reinterpret_cast<const u32x4*>(c.w1[wslot(z)])[tid + NT_ * j];
     if constexpr (NS > 1) frames(1, fv[1]);
 #pragma unroll
     for (int j = 0; j < W2P; ++j) w2v[j] = w2p[tid + NT_ * j];

@@ -36,6 +36,7 @@ struct GenericNet {
   virtual hipError_t read_cost_sum(double* sum) = 0;
   virtual hipError_t last_q(void* preq, void* maxpostq, bool host_f64) = 0;
   virtual hipError_t update_target() = 0;                                // deepqnetwork.py:102-105
+  virtual hipError_t set_double_dqn(bool on) = 0;                        // --double_dqn (allocates the online-on-poststates Q on first use)
   virtual size_t state_bytes() const = 0;                                // hist * H * W
 };
 

@@ -158,10 +158,16 @@ __global__ void __launch_bounds__(256) reduce_slabs_kernel(const T* __restrict__
 template <typename T>
 __global__ void head_kernel(const T* __restrict__ q_on, const T* __restrict__ q_tg, const uint8_t* __restrict__ act,
                             const int64_t* __restrict__ rew, const uint8_t* __restrict__ term, T* __restrict__ dq,
-                            T* __restrict__ cost_terms, T* __restrict__ maxq, int N, int A, double discount, double minr, double maxr, T clip) {
+                            T* __restrict__ cost_terms, T* __restrict__ maxq, int N, int A, double discount, double minr, double maxr, T clip,
+                            const T* __restrict__ q_sel) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
   T m = q_tg[(int64_t)n * A];
+  if (q_sel) {                                                                // --double_dqn: target net's Q at the online net's argmax
+    int best = 0; T bv = q_sel[(int64_t)n * A];
+    for (int a = 1; a < A; ++a) { const T v = q_sel[(int64_t)n * A + a]; if (v > bv) { bv = v; best = a; } }   // first maximum
+    m = q_tg[(int64_t)n * A + best];
+  } else
   for (int a = 1; a < A; ++a) { const T v = q_tg[(int64_t)n * A + a]; m = v > m ? v : m; }     // be.max(postq, axis=0) :124
   maxq[n] = m;
   double r = (double)rew[n];
@@ -234,6 +240,7 @@ class GenericNetT : public GenericNet {
   T* col[4] = {nullptr}; T* act[4] = {nullptr}; T* dact[3] = {nullptr};
   T *q = nullptr, *dq = nullptr, *d4 = nullptr, *dcol = nullptr, *cost_terms = nullptr, *cost = nullptr, *maxq = nullptr, *slab = nullptr;
   double* cost_sum = nullptr; int64_t slab_cap = 0;
+  bool double_dqn = false; T* q_sel = nullptr;          // --double_dqn: Q of the online net on the poststates [B][A]
   uint8_t* st_states = nullptr; uint8_t* st_small = nullptr;
   std::vector<void*> allocs; std::vector<uint8_t> small_host;
 
@@ -318,8 +325,10 @@ class GenericNetT : public GenericNet {
   }
 
   // Q(states; W) of n states -> q + z*B*A; leaves cols / activations of this pass in col[] / act[]  (deepqnetwork.py:119-130,178-180)
+  // z = 2 (--double_dqn): the online net on the poststates, Q into q_sel
   hipError_t forward(int z, const uint8_t* states_dev, int n) {
-    const T* Wt = z ? theta_t : theta;
+    const T* Wt = z == 1 ? theta_t : theta;
+    T* qz = z == 2 ? q_sel : q + (int64_t)z * B * A;
     for (int l = 0; l < 4; ++l) {
       const ConvGeom& c = cv[l];
       const int64_t m = mrows(l, n), total = m * c.crs();
@@ -328,14 +337,16 @@ class GenericNetT : public GenericNet {
       if (l < 3) GCHK(gemm(ga(col[l], c.crs(), 1, Wt + off[l], c.K, 1, act[l], (int)m, c.K, c.crs(), 1)));     // cols @ W, Rectlin
       else GCHK(gemm(ga(col[3], c.crs(), 1, Wt + off[3], 1, c.crs(), act[3], n, 512, c.crs(), 1)));            // x @ W4^T, Rectlin
     }
-    return gemm(ga(act[3], 512, 1, Wt + off[4], 1, 512, q + (int64_t)z * B * A, n, A, 512, 0));                // a4 @ W5^T
+    return gemm(ga(act[3], 512, 1, Wt + off[4], 1, 512, qz, n, A, 512, 0));                                  // a4 @ W5^T
   }
 
   hipError_t train_dev(const uint8_t* pre, const uint8_t* post, const uint8_t* actions, const int64_t* rew, const uint8_t* term, int epoch) override {
     GCHK(forward(1, post, B));                                                 // target net on the poststates :119-125
+    const bool dd = double_dqn && theta_t != theta;                            // (no target net: Double DQN is standard DQN)
+    if (dd) GCHK(forward(2, post, B));                                         // --double_dqn: online net on the poststates
     GCHK(forward(0, pre, B));                                                  // online net on the prestates, tensors kept :128-130
     hipLaunchKernelGGL(head_kernel<T>, dim3((B + 63) / 64), dim3(64), 0, st, (const T*)q, (const T*)(q + (int64_t)B * A), actions, rew, term,
-                       dq, cost_terms, maxq, B, A, cfg.discount_rate, cfg.min_reward, cfg.max_reward, (T)cfg.clip_error);
+                       dq, cost_terms, maxq, B, A, cfg.discount_rate, cfg.min_reward, cfg.max_reward, (T)cfg.clip_error, (const T*)(dd ? q_sel : nullptr));
     hipLaunchKernelGGL(cost_kernel<T>, dim3(1), dim3(64), 0, st, (const T*)cost_terms, cost, cost_sum, B);
     // ---- bprop (A8) :162
     GCHK(gemm(ga(dq, 1, A, act[3], 512, 1, g + off[4], A, 512, B)));                                   // gW5 = dq^T @ a4
@@ -419,6 +430,11 @@ class GenericNetT : public GenericNet {
   hipError_t last_q(void* preq, void* maxpostq, bool f64) override {
     if (preq) GCHK(fetch(q, (int64_t)B * A, preq, f64));
     if (maxpostq) GCHK(fetch(maxq, B, maxpostq, f64));
+    return hipSuccess;
+  }
+  hipError_t set_double_dqn(bool on) override {
+    if (on && !q_sel) GCHK(dalloc(&q_sel, (int64_t)B * A));
+    double_dqn = on;
     return hipSuccess;
   }
   hipError_t update_target() override {

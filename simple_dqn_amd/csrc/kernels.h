@@ -30,13 +30,13 @@ struct HeadArgs {
   const uint8_t* st_actions;    // minibatch metadata (staged from the host, or gathered by prep_kernel)
   const int64_t* st_rewards;
   const uint8_t* st_terminals;
-  float* q;                     // [2][B][A] q-values of both nets
+  float* q;                     // [nz][B][A] q-values of the net slots (problems.h: wslot)
   float* maxq;                  // [B]
   float* dq;                    // [B][A] clipped deltas
   float* cost_terms;            // [B]  0.5 * delta^2 (pre-clip)
   double discount, min_reward, max_reward;
   float clip_error;
-  int train;                    // 0: predict only (z = 0)
+  int train;                    // 0: predict only (z = 0); 1: train step; 2: train step with Double DQN targets (--double_dqn)
   // hoist: one extra workgroup copies the NEXT step's sampled indexes from their pinned slot into device memory, so that
   // the target conv1 riding in this step's K_BWD2 launch reads them from HBM (next_B = 0: nothing to copy)
   const int64_t* next_idx_pinned; int64_t* next_idx_dev; int next_B;

@@ -73,7 +73,7 @@ struct StepArgs {
   float* a1;                // [2][B*400][32]
   float* a2;                // [2][B*81][64]
   float* a3;                // [2][B*49][64]
-  float* slab4;             // fc4 fwd split-K slabs [S4][2][B][512]
+  float* slab4;             // fc4 fwd split-K slabs [S4][2][B][512] (+ [S4][B][512] of the third slot: slab4_row)
   float* a4;                // [2][B][512]
   float* d4;                // [B][512]
   float* d3p;               // [B][11][11][64]
@@ -184,9 +184,17 @@ SDQN_HD void split_bf16x3(float w, uint16_t& hi, uint16_t& mid, uint16_t& lo) {
 }
 constexpr int W1P_PLANE = K1 * CRS1;      // elements per plane: [32 maps][256 k]
 
+// Net slots of a forward launch (StepArgs::nz of them): 0 = online net on the prestates, 1 = target net on the poststates and, with
+// --double_dqn, 2 = ONLINE net on the POSTSTATES (the argmax of the Double DQN target).  Slot z takes its weights from theta[wslot(z)]
+// (and the matching wh / wht / w1p / wpt copies), its frames from state slot sslot(z); activations, slabs and Q are indexed by z itself.
+SDQN_HD int wslot(int z) { return z & 1; }
+SDQN_HD int sslot(int z) { return z != 0 ? 1 : 0; }
+// fc4 forward split-K slab of (K-split ks, slot z): [S4][2] for slots 0 / 1 as before, slot 2's S4 slabs after them
+SDQN_HD int64_t slab4_row(const StepArgs& a, int ks, int z) { return z < 2 ? (int64_t)ks * 2 + z : (int64_t)2 * a.S4 + ks; }
 SDQN_HD int64_t sbase(const StepArgs& a, int z, int n) {
   // replay_memory.py:71-72: prestate = screens[i-4:i], poststate = screens[i-3:i+1]
-  return a.from_ring ? (a.idx[n] - C0 + z) * (int64_t)FRAME : ((int64_t)z * a.B + n) * (int64_t)STATE;
+  const int zs = sslot(z);
+  return a.from_ring ? (a.idx[n] - C0 + zs) * (int64_t)FRAME : ((int64_t)zs * a.B + n) * (int64_t)STATE;
 }
 // deepqnetwork.py:100 be.divide(input, 255): correctly-rounded x/255 without a divide — q = x*r, one fma
 // Newton correction (bit-identical to IEEE x/255.0f for all 256 byte values: tests/test_emul.py checks).
@@ -286,7 +294,7 @@ struct Conv1Fwd {   // fused gather + normalise + conv1 + ReLU: replay_memory.py
   // operand descriptors for the engine's fast paths: *_REG = plain row-major [k][x] matrix with row pitch *_LD
   static constexpr bool A_REG = false, A_U8 = true, B_REG = true; static constexpr int A_LD = 0, B_LD = K1;
   SDQN_HD static const float* a_ptr(const StepArgs& a, int z) { (void)z; return (const float*)nullptr; }
-  SDQN_HD static const float* b_ptr(const StepArgs& a, int z) { (void)z; return a.theta[z] + OFF1; }
+  SDQN_HD static const float* b_ptr(const StepArgs& a, int z) { (void)z; return a.theta[wslot(z)] + OFF1; }
 #if defined(__HIPCC__)
   struct Epi {};
   __device__ static void epi_begin(const StepArgs&, int, int, int, Epi&) {}
@@ -302,8 +310,8 @@ struct Conv1Fwd {   // fused gather + normalise + conv1 + ReLU: replay_memory.py
   SDQN_HD static f4 a_load4(const StepArgs& a, int, aoff_t o) { return ld4_u8(a.src + o); }
   SDQN_HD static int b_row(const StepArgs&, int, int k) { return k * K1; }
   SDQN_HD static int b_col(const StepArgs&, int, int n) { return n; }
-  SDQN_HD static float b_load(const StepArgs& a, int z, int o) { return a.theta[z][OFF1 + o]; }
-  SDQN_HD static f4 b_load4(const StepArgs& a, int z, int o) { return ld4(a.theta[z] + OFF1 + o); }
+  SDQN_HD static float b_load(const StepArgs& a, int z, int o) { return a.theta[wslot(z)][OFF1 + o]; }
+  SDQN_HD static f4 b_load4(const StepArgs& a, int z, int o) { return ld4(a.theta[wslot(z)] + OFF1 + o); }
   SDQN_HD static void store(const StepArgs& a, int z, int, int m, int n, float v) {
     a.a1[((int64_t)z * M(a) + m) * K1 + n] = fmaxf(v, 0.0f);
   }
@@ -315,7 +323,7 @@ struct Conv2Fwd {   // deepqnetwork.py:85
   // operand descriptors for the engine's fast paths: *_REG = plain row-major [k][x] matrix with row pitch *_LD
   static constexpr bool A_REG = false, A_U8 = false, B_REG = true; static constexpr int A_LD = 0, B_LD = K2;
   SDQN_HD static const float* a_ptr(const StepArgs& a, int z) { (void)z; return a.a1; }
-  SDQN_HD static const float* b_ptr(const StepArgs& a, int z) { (void)z; return a.theta[z] + OFF2; }
+  SDQN_HD static const float* b_ptr(const StepArgs& a, int z) { (void)z; return a.theta[wslot(z)] + OFF2; }
 #if defined(__HIPCC__)
   struct Epi {};
   __device__ static void epi_begin(const StepArgs&, int, int, int, Epi&) {}
@@ -331,8 +339,8 @@ struct Conv2Fwd {   // deepqnetwork.py:85
   SDQN_HD static f4 a_load4(const StepArgs& a, int, aoff_t o) { return ld4(a.a1 + o); }
   SDQN_HD static int b_row(const StepArgs&, int, int k) { return k * K2; }
   SDQN_HD static int b_col(const StepArgs&, int, int n) { return n; }
-  SDQN_HD static float b_load(const StepArgs& a, int z, int o) { return a.theta[z][OFF2 + o]; }
-  SDQN_HD static f4 b_load4(const StepArgs& a, int z, int o) { return ld4(a.theta[z] + OFF2 + o); }
+  SDQN_HD static float b_load(const StepArgs& a, int z, int o) { return a.theta[wslot(z)][OFF2 + o]; }
+  SDQN_HD static f4 b_load4(const StepArgs& a, int z, int o) { return ld4(a.theta[wslot(z)] + OFF2 + o); }
   SDQN_HD static void store(const StepArgs& a, int z, int, int m, int n, float v) {
     a.a2[((int64_t)z * M(a) + m) * K2 + n] = fmaxf(v, 0.0f);
   }
@@ -344,7 +352,7 @@ struct Conv3Fwd {   // deepqnetwork.py:87
   // operand descriptors for the engine's fast paths: *_REG = plain row-major [k][x] matrix with row pitch *_LD
   static constexpr bool A_REG = false, A_U8 = false, B_REG = true; static constexpr int A_LD = 0, B_LD = K3;
   SDQN_HD static const float* a_ptr(const StepArgs& a, int z) { (void)z; return a.a2; }
-  SDQN_HD static const float* b_ptr(const StepArgs& a, int z) { (void)z; return a.theta[z] + OFF3; }
+  SDQN_HD static const float* b_ptr(const StepArgs& a, int z) { (void)z; return a.theta[wslot(z)] + OFF3; }
 #if defined(__HIPCC__)
   struct Epi {};
   __device__ static void epi_begin(const StepArgs&, int, int, int, Epi&) {}
@@ -360,8 +368,8 @@ struct Conv3Fwd {   // deepqnetwork.py:87
   SDQN_HD static f4 a_load4(const StepArgs& a, int, aoff_t o) { return ld4(a.a2 + o); }
   SDQN_HD static int b_row(const StepArgs&, int, int k) { return k * K3; }
   SDQN_HD static int b_col(const StepArgs&, int, int n) { return n; }
-  SDQN_HD static float b_load(const StepArgs& a, int z, int o) { return a.theta[z][OFF3 + o]; }
-  SDQN_HD static f4 b_load4(const StepArgs& a, int z, int o) { return ld4(a.theta[z] + OFF3 + o); }
+  SDQN_HD static float b_load(const StepArgs& a, int z, int o) { return a.theta[wslot(z)][OFF3 + o]; }
+  SDQN_HD static f4 b_load4(const StepArgs& a, int z, int o) { return ld4(a.theta[wslot(z)] + OFF3 + o); }
   SDQN_HD static void store(const StepArgs& a, int z, int, int m, int n, float v) {
     a.a3[((int64_t)z * M(a) + m) * K3 + n] = fmaxf(v, 0.0f);
   }
@@ -373,7 +381,7 @@ struct Fc4Fwd {     // deepqnetwork.py:89, split-K over S4 slabs; bias-free, ReL
   // operand descriptors for the engine's fast paths: *_REG = plain row-major [k][x] matrix with row pitch *_LD
   static constexpr bool A_REG = false, A_U8 = false, B_REG = true; static constexpr int A_LD = 0, B_LD = NFC;
   SDQN_HD static const float* a_ptr(const StepArgs& a, int z) { (void)z; return a.a3; }
-  SDQN_HD static const float* b_ptr(const StepArgs& a, int z) { (void)z; return a.theta[z] + OFF4; }
+  SDQN_HD static const float* b_ptr(const StepArgs& a, int z) { (void)z; return a.theta[wslot(z)] + OFF4; }
 #if defined(__HIPCC__)
   struct Epi {};
   __device__ static void epi_begin(const StepArgs&, int, int, int, Epi&) {}
@@ -393,10 +401,10 @@ struct Fc4Fwd {     // deepqnetwork.py:89, split-K over S4 slabs; bias-free, ReL
   SDQN_HD static f4 a_load4(const StepArgs& a, int, aoff_t o) { return ld4(a.a3 + o); }
   SDQN_HD static int b_row(const StepArgs&, int, int k) { return k * NFC; }
   SDQN_HD static int b_col(const StepArgs&, int, int n) { return n; }
-  SDQN_HD static float b_load(const StepArgs& a, int z, int o) { return a.theta[z][OFF4 + o]; }
-  SDQN_HD static f4 b_load4(const StepArgs& a, int z, int o) { return ld4(a.theta[z] + OFF4 + o); }
+  SDQN_HD static float b_load(const StepArgs& a, int z, int o) { return a.theta[wslot(z)][OFF4 + o]; }
+  SDQN_HD static f4 b_load4(const StepArgs& a, int z, int o) { return ld4(a.theta[wslot(z)] + OFF4 + o); }
   SDQN_HD static void store(const StepArgs& a, int z, int ks, int m, int n, float v) {
-    a.slab4[(((int64_t)ks * 2 + z) * a.B + m) * NFC + n] = v;
+    a.slab4[(slab4_row(a, ks, z) * a.B + m) * NFC + n] = v;
   }
 };
 

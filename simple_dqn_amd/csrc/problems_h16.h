@@ -32,7 +32,7 @@ struct Conv1FwdH : Conv1Fwd {
   __device__ static half8 a_load8(const StepArgs& a, int, aoff_t o) { return ldh8_u8(a.src + o); }
   __device__ static int b_row(const StepArgs&, int, int k) { return k; }
   __device__ static int b_col(const StepArgs&, int, int n) { return n * CRS1; }
-  __device__ static half8 b_load8(const StepArgs& a, int z, int o) { return ldh8(a.wht[z] + OFF1 + o); }
+  __device__ static half8 b_load8(const StepArgs& a, int z, int o) { return ldh8(a.wht[wslot(z)] + OFF1 + o); }
   __device__ static void store(const StepArgs& a, int z, int, int m, int n, float v) {
     a.h_a1[((int64_t)z * M(a) + m) * K1 + n] = (half_t)fmaxf(v, 0.0f);
   }
@@ -42,7 +42,7 @@ struct Conv2FwdH : Conv2Fwd {
   __device__ static half8 a_load8(const StepArgs& a, int, aoff_t o) { return ldh8(a.h_a1 + o); }
   __device__ static int b_row(const StepArgs&, int, int k) { return k; }
   __device__ static int b_col(const StepArgs&, int, int n) { return n * CRS2; }
-  __device__ static half8 b_load8(const StepArgs& a, int z, int o) { return ldh8(a.wht[z] + OFF2 + o); }
+  __device__ static half8 b_load8(const StepArgs& a, int z, int o) { return ldh8(a.wht[wslot(z)] + OFF2 + o); }
   __device__ static void store(const StepArgs& a, int z, int, int m, int n, float v) {
     a.h_a2[((int64_t)z * M(a) + m) * K2 + n] = (half_t)fmaxf(v, 0.0f);
   }
@@ -52,7 +52,7 @@ struct Conv3FwdH : Conv3Fwd {
   __device__ static half8 a_load8(const StepArgs& a, int, aoff_t o) { return ldh8(a.h_a2 + o); }
   __device__ static int b_row(const StepArgs&, int, int k) { return k; }
   __device__ static int b_col(const StepArgs&, int, int n) { return n * CRS3; }
-  __device__ static half8 b_load8(const StepArgs& a, int z, int o) { return ldh8(a.wht[z] + OFF3 + o); }
+  __device__ static half8 b_load8(const StepArgs& a, int z, int o) { return ldh8(a.wht[wslot(z)] + OFF3 + o); }
   __device__ static void store(const StepArgs& a, int z, int, int m, int n, float v) {
     a.h_a3[((int64_t)z * M(a) + m) * K3 + n] = (half_t)fmaxf(v, 0.0f);
   }
@@ -62,7 +62,7 @@ struct Fc4FwdH : Fc4Fwd {              // slabs stay fp32 (summed + ReLU'd by th
   __device__ static half8 a_load8(const StepArgs& a, int, aoff_t o) { return ldh8(a.h_a3 + o); }
   __device__ static int b_row(const StepArgs&, int, int k) { return k; }
   __device__ static int b_col(const StepArgs&, int, int n) { return n * NIN4; }
-  __device__ static half8 b_load8(const StepArgs& a, int z, int o) { return ldh8(a.wht[z] + OFF4 + o); }
+  __device__ static half8 b_load8(const StepArgs& a, int z, int o) { return ldh8(a.wht[wslot(z)] + OFF4 + o); }
 };
 
 // ---- dgrad: A = half (loss-scaled) deltas, B = half weights in the master layout wh[0] -------------------------------

@@ -51,8 +51,8 @@ struct Fc4FwdWT : Fc4Fwd {
   static constexpr bool PRELOAD = SDQN_PRELOAD != 0;
   __device__ static void preload(const StepArgs& a, unsigned g0, unsigned g1, unsigned g2) { SDQN_TOUCH("s"(a.a3), "s"(a.slab4), "s"(a.theta[0]), "s"(a.theta[1]), "s"(a.B), "s"(a.nz), "s"(a.S4), "s"(a.xcd_map), "s"(g0), "s"(g1), "s"(g2)); }
 
-  __device__ static f4 b_load4(const StepArgs& a, int z, int o) { return NT_W4 ? ld4_nt(a.theta[z] + OFF4 + o) : ld4(a.theta[z] + OFF4 + o); }
-  __device__ static void store(const StepArgs& a, int z, int ks, int m, int n, float v) { wt_store(&a.slab4[(((int64_t)ks * 2 + z) * a.B + m) * NFC + n], v); }
+  __device__ static f4 b_load4(const StepArgs& a, int z, int o) { return NT_W4 ? ld4_nt(a.theta[wslot(z)] + OFF4 + o) : ld4(a.theta[wslot(z)] + OFF4 + o); }
+  __device__ static void store(const StepArgs& a, int z, int ks, int m, int n, float v) { wt_store(&a.slab4[(slab4_row(a, ks, z) * a.B + m) * NFC + n], v); }
 };
 struct Fc4DgradWT : Fc4Dgrad {
   static constexpr bool PRELOAD = SDQN_PRELOAD != 0;
@@ -172,7 +172,7 @@ struct Fc4WgradBT : Fc4WgradWT {
 
 // ---- plane mode of the block-tile engine (bt_tile_xp): where a problem's B operand (always a weight matrix here) lives as bf16 planes ----
 template <class P, int OFF, int K> struct XPF : P {       // forward conv: transposed planes [n][K] of net z
-  __device__ static const unsigned short* bp(const StepArgs& a, int z) { return a.wpt[z] + OFF; }
+  __device__ static const unsigned short* bp(const StepArgs& a, int z) { return a.wpt[wslot(z)] + OFF; }
   __device__ static int bp_col(const StepArgs&, int, int n) { return n * K; }
   __device__ static int bp_row(const StepArgs&, int, int k) { return k; }
 };

@@ -448,6 +448,11 @@ extern "C" int sdqn_net_set_option(sdqn_net_t h, const char* name, int value) {
   ARGCHK(h && name, "NULL argument");
   if (h->gen) {                                   // the generic path has no tuning knobs; the ones that change semantics are refused
     if (!strcmp(name, "dp_overlap") && value < 0) return SDQN_OK;      // (auto: nothing to overlap without a communicator)
+    if (!strcmp(name, "double_dqn")) {
+      ARGCHK(value == 0 || value == 1, "double_dqn must be 0 or 1");
+      GENCHK(h->gen->set_double_dqn(value != 0));
+      return SDQN_OK;
+    }
     if (!strcmp(name, "grad_only") || !strcmp(name, "dp_overlap") || !strcmp(name, "keep_gradients")) {
       ARGCHK(value == 0 || !strcmp(name, "keep_gradients"), "option %s is implemented for the 84x84x4 float32 / float16 configurations", name);
     }
@@ -456,7 +461,26 @@ extern "C" int sdqn_net_set_option(sdqn_net_t h, const char* name, int value) {
   bool retired = !strncmp(name, "rb:", 3) || !strncmp(name, "btx:", 4);            // (switching one of them OFF stays a no-op, as before)
   for (int i = 0; RETIRED_OPTIONS[i]; ++i) retired = retired || !strcmp(name, RETIRED_OPTIONS[i]);
   if (retired) { if (value) RETIRED_OPTION_REFUSED(name); return SDQN_OK; }
-  if (!strcmp(name, "keep_gradients")) h->keep_grads = value != 0;
+  if (!strcmp(name, "double_dqn")) {                      // Double DQN targets (van Hasselt et al. 2016): sdqn.h
+    ARGCHK(value == 0 || value == 1, "double_dqn must be 0 or 1");
+    if (value && !h->slots3) {                             // room for the third net slot (the two-slot buffers are freed with the network)
+      { int rc_ = join_comm(h); if (rc_) return rc_; } HIPCHK(hipStreamSynchronize(g_stream));
+      const size_t B = (size_t)h->B;
+      float** f32[5] = {&h->a1, &h->a2, &h->a3, &h->a4, &h->q};
+      const size_t n32[5] = {B * PIX1 * K1, B * PIX2 * K2, B * PIX3 * K3, B * NFC, B * h->A};
+      for (int i = 0; i < 5; ++i) { int r_ = dalloc(h, (void**)f32[i], 3 * n32[i] * 4); if (r_) return r_; }
+      { int r_ = dalloc(h, (void**)&h->slab4, (size_t)h->S4_cap * 3 * B * NFC * 4); if (r_) return r_; }
+      if (h->h_a1) {
+        half_t** f16[3] = {&h->h_a1, &h->h_a2, &h->h_a3};
+        const size_t n16[3] = {B * PIX1 * K1, B * PIX2 * K2, B * PIX3 * K3};
+        for (int i = 0; i < 3; ++i) { int r_ = dalloc(h, (void**)f16[i], 3 * n16[i] * 2); if (r_) return r_; }
+      }
+      HIPCHK(hipStreamSynchronize(g_stream));
+      h->slots3 = true;
+    }
+    h->double_dqn = value != 0;
+  }
+  else if (!strcmp(name, "keep_gradients")) h->keep_grads = value != 0;
   else if (!strcmp(name, "grad_only")) h->grad_only = value != 0;
   else if (!strcmp(name, "h16_wgrad_mfma")) h->h16_wgrad_mfma = value != 0;
   else if (!strcmp(name, "c1w_in_wgrads")) { if (value < 0 || value > 2) { set_error("bad c1w_in_wgrads (0..2)"); return SDQN_ERR_ARG; } h->c1w_in_wgrads = value; }

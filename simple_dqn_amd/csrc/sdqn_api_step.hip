@@ -75,14 +75,14 @@ int run_forward(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd) {
     // statistics for the online net of a train step (:129), running statistics for the target net (:120) and predict (:180)
     StepArgs f = a; f.bn = 1;
     f.a1 = h->x1; LAUNCH(K_CONV1_FWD, launch_tuned(h, K_CONV1_FWD, f, g_stream)); f.a1 = h->a1;
-    LAUNCH(K_BN, launch_bn_forward(bn_args(h, a, 0, hd.train), g_stream));
+    LAUNCH(K_BN, launch_bn_forward(bn_args(h, a, 0, hd.train != 0), g_stream));
     f.a2 = h->x2; LAUNCH(K_CONV2_FWD, launch_tuned(h, K_CONV2_FWD, f, g_stream)); f.a2 = h->a2;
-    LAUNCH(K_BN, launch_bn_forward(bn_args(h, a, 1, hd.train), g_stream));
+    LAUNCH(K_BN, launch_bn_forward(bn_args(h, a, 1, hd.train != 0), g_stream));
     f.a3 = h->x3; LAUNCH(K_CONV3_FWD, launch_tuned(h, K_CONV3_FWD, f, g_stream)); f.a3 = h->a3;
-    LAUNCH(K_BN, launch_bn_forward(bn_args(h, a, 2, hd.train), g_stream));
+    LAUNCH(K_BN, launch_bn_forward(bn_args(h, a, 2, hd.train != 0), g_stream));
     { int rc = join_comm(h); if (rc) return rc; }
     LAUNCH(K_FC4_FWD, launch_tuned(h, K_FC4_FWD, f, g_stream));
-    LAUNCH(K_BN, launch_bn_forward(bn_args(h, a, 3, hd.train), g_stream));
+    LAUNCH(K_BN, launch_bn_forward(bn_args(h, a, 3, hd.train != 0), g_stream));
     LAUNCH(K_HEAD, launch_head(f, hd, g_stream));
     return SDQN_OK;
   }
@@ -147,8 +147,29 @@ extern "C" int sdqn_net_step_structure(sdqn_net_t h, int* structure, int* update
   *structure = (int)step_structure(h); *update = (int)update_form(h);
   return SDQN_OK;
 }
-int run_train(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd, const PrepArgs* next) {
-  int rc = run_forward(h, a, hd);
+// --double_dqn: Q(theta, poststates), the argmax of the Double DQN target.  Without batch_norm it is the third net slot of the step's
+// own forward launches (nz = 3: online weights, poststates; problems.h wslot / sslot), and the head takes a* from it.  With batch_norm
+// the online slot's training-mode BatchNorm pass updates the running statistics that an inference-mode third slot of the same launch
+// would read, so there it is a forward of its own in front of the step (the predict forward, nz = 1, running statistics as they stand
+// before the step), its state source shifted to the poststates (one frame further in the ring, replay_memory.py:71-72, or the second
+// half of the [2][B][STATE] staging) and its Q-values left in q slot 2.  Without a target net (theta- aliases theta) Double DQN is
+// standard DQN: nothing changes.
+bool ddqn_active(const sdqn_net_s* h) { return h->double_dqn && h->theta_t != h->theta; }
+int run_online_post_bn(sdqn_net_s* h, const StepArgs& a) {
+  StepArgs p = a; p.nz = 1;
+  p.src = a.from_ring ? a.src + FRAME : a.src + (size_t)a.B * STATE;
+  HeadArgs hp = head_args(h, 0); hp.q = h->q + (size_t)2 * a.B * h->A;
+  return run_forward(h, p, hp);
+}
+int run_train(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd0, const PrepArgs* next) {
+  HeadArgs hd = hd0;
+  StepArgs af = a;                         // the forward's arguments (the backward keeps a: its launches know two slots only)
+  if (ddqn_active(h)) {
+    hd.train = 2;
+    if (h->bn) { int rc0 = run_online_post_bn(h, a); if (rc0) return rc0; }
+    else af.nz = 3;
+  }
+  int rc = run_forward(h, af, hd);
   if (rc) return rc;
   // Backward.  Critical path: fc4_dgrad -> conv3_dgrad -> conv2_dgrad -> conv1_wgrad; the other weight gradients only need the delta of
   // their layer and share a launch with the dgrad that is computed from the same delta.

@@ -143,7 +143,7 @@ hipError_t launch_kernel(int id, const StepArgs& a, const LaunchTune& t, hipStre
 // fetches the next step's indexes from their pinned host slot into HBM.
 // QSYS (acting path, round 4): h.q is HOST memory (mapped, pinned) and every Q-value leaves with a system-scope store the moment it is
 // summed, so the host can poll for it instead of paying a D2H copy packet + a stream synchronisation (sdqn_api_act.hip: predict_state).
-template <int AMAX, bool BN, bool HOIST = false, bool QSYS = false>
+template <int AMAX, bool BN, bool HOIST = false, bool QSYS = false, bool DDQN = false>
 __global__ void __launch_bounds__(512) head_kernel(const StepArgs a, const HeadArgs h) {
   SDQN_STAMP(0);
   if constexpr (HOIST) {
@@ -153,8 +153,11 @@ __global__ void __launch_bounds__(512) head_kernel(const StepArgs a, const HeadA
     }
   }
   const int n = blockIdx.x, j = threadIdx.x, lane = j & 63, wave = j >> 6;
-  __shared__ float prod[2 * AMAX][NFC];               // 16 KB (A <= 4) .. 72 KB (A <= 18)
-  __shared__ float sh_q[2][AMAX];
+  // --double_dqn (DDQN): a third net slot, the online net on the poststates, computed here from its fc4 slabs (NZ = 3); with batch_norm its
+  // Q-values were written to q slot 2 by a forward of their own (sdqn_api_step.hip: run_train)
+  constexpr int NZ = (DDQN && !BN) ? 3 : 2;
+  __shared__ float prod[NZ * AMAX][NFC];              // 16 KB (A <= 4) .. 72 KB (A <= 18); 108 KB with the third slot at A = 18
+  __shared__ float sh_q[NZ][AMAX];
   __shared__ float sh_dc;
   __shared__ int sh_act;
   // ---- everything this thread will ever load is issued up front (one memory round trip) ----------------
@@ -162,9 +165,12 @@ __global__ void __launch_bounds__(512) head_kernel(const StepArgs a, const HeadA
   const float* __restrict__ th0 = a.theta[0];
   const float* __restrict__ th1 = a.theta[nz > 1 ? 1 : 0];
   const float* __restrict__ slab = a.slab4;
-  float a4v[2] = {0.0f, 0.0f};
+  float a4v[NZ];
+#pragma unroll
+  for (int z = 0; z < NZ; ++z) a4v[z] = 0.0f;
   const int64_t sstride = (int64_t)2 * a.B * NFC;
-  float t[2][7];
+  const int64_t s2base = (int64_t)2 * a.S4 * a.B * NFC + (int64_t)n * NFC + j;      // slot 2's slabs follow [S4][2] (problems.h: slab4_row)
+  float t[NZ][7];
   if constexpr (BN) {                                // --batch_norm: a4 was activated by the BatchNorm pass (bn_kernels.hip)
 #pragma unroll
     for (int z = 0; z < 2; ++z) a4v[z] = a.a4[((int64_t)(z < nz ? z : 0) * a.B + n) * NFC + j];
@@ -174,6 +180,10 @@ __global__ void __launch_bounds__(512) head_kernel(const StepArgs a, const HeadA
 #pragma unroll
       for (int s = 0; s < 7; ++s)
         t[z][s] = slab[s * sstride + ((int64_t)(z < nz ? z : 0) * a.B + n) * NFC + j];
+    if constexpr (NZ == 3) {
+#pragma unroll
+      for (int s = 0; s < 7; ++s) t[2][s] = slab[s2base + (int64_t)s * a.B * NFC];
+    }
   }
   float w5[2][AMAX];
 #pragma unroll
@@ -189,7 +199,7 @@ __global__ void __launch_bounds__(512) head_kernel(const StepArgs a, const HeadA
   if constexpr (BN) {
   } else if (a.S4 == 7) {
 #pragma unroll
-    for (int z = 0; z < 2; ++z) { float v = 0.0f;
+    for (int z = 0; z < NZ; ++z) { float v = 0.0f;
 #pragma unroll
       for (int s = 0; s < 7; ++s) v += t[z][s];                                                   // fixed order
       a4v[z] = v; }
@@ -198,6 +208,9 @@ __global__ void __launch_bounds__(512) head_kernel(const StepArgs a, const HeadA
     for (int z = 0; z < 2; ++z) { float v = 0.0f;
       if (z < nz) for (int s = 0; s < a.S4; ++s) v += slab[s * sstride + ((int64_t)z * a.B + n) * NFC + j];
       a4v[z] = v; }
+    if constexpr (NZ == 3) { float v = 0.0f;
+      if (nz > 2) for (int s = 0; s < a.S4; ++s) v += slab[s2base + (int64_t)s * a.B * NFC];
+      a4v[2] = v; }
   }
 #ifdef SDQN_TIMING
   asm volatile("" :: "v"(a4v[0]), "v"(a4v[1]), "v"(w5[0][0]));
@@ -208,14 +221,14 @@ __global__ void __launch_bounds__(512) head_kernel(const StepArgs a, const HeadA
   // ONE 6-step butterfly per row).  A chain of __shfl_xor (= ds_bpermute, ~100 cycles each) per action on every wave
   // measured 5400 cycles here.
 #pragma unroll
-  for (int z = 0; z < 2; ++z) {                      // static indices only: w5 / a4v stay in registers
+  for (int z = 0; z < NZ; ++z) {                     // static indices only: w5 / a4v stay in registers
     if (z >= nz) continue;
     const float v = fmaxf(a4v[z], 0.0f);                                                          // Rectlin, :89
     a4v[z] = v;
     if constexpr (!BN) a.a4[((int64_t)z * a.B + n) * NFC + j] = v;
 #pragma unroll
     for (int act = 0; act < AMAX; ++act)
-      if (act < A) prod[z * A + act][j] = w5[z][act] * v;
+      if (act < A) prod[z * A + act][j] = w5[z & 1][act] * v;                                    // (slot 2: the online fc5, problems.h wslot)
   }
   SDQN_STAMP(2);
   __syncthreads();
@@ -238,8 +251,17 @@ __global__ void __launch_bounds__(512) head_kernel(const StepArgs a, const HeadA
   SDQN_STAMP(4);
   if (j == 0) {
     const int act = m_act, term = m_term; const int64_t rew = m_rew;
-    float m = sh_q[1][0];
-    for (int k = 1; k < A; ++k) m = fmaxf(m, sh_q[1][k]);                                       // be.max(postq, axis=0), :124
+    float m;
+    if constexpr (DDQN) {                            // Double DQN: the online net picks the action, the target net values it
+      const float* qs;
+      if constexpr (NZ == 3) qs = sh_q[NZ - 1]; else qs = h.q + ((int64_t)2 * a.B + n) * A;
+      int best = 0; float bv = qs[0];
+      for (int k = 1; k < A; ++k) { const float v = qs[k]; if (v > bv) { bv = v; best = k; } }   // first maximum (numpy argmax)
+      m = sh_q[1][best];
+    } else {
+      m = sh_q[1][0];
+      for (int k = 1; k < A; ++k) m = fmaxf(m, sh_q[1][k]);                                     // be.max(postq, axis=0), :124
+    }
     double rr = (double)rew;                                                                     // np.clip(rewards, ..), :136
     rr = rr < h.min_reward ? h.min_reward : (rr > h.max_reward ? h.max_reward : rr);
     const double y = term ? rr : rr + h.discount * (double)m;                                    // :139-143 (host float math)
@@ -292,10 +314,18 @@ hipError_t set_wave_timing_buffer(unsigned long long* const* p, const unsigned* 
 #endif
 
 hipError_t launch_head(const StepArgs& a, const HeadArgs& h, hipStream_t s, bool q_system_scope) {
+  if (a.nz > 2 && (h.train != 2 || a.bn)) return hipErrorInvalidValue;          // (a third slot needs the Double DQN head's LDS)
   if (q_system_scope && !a.bn && !h.train) {          // acting path: Q-values straight into mapped host memory
     if (a.A <= 4) SDQN_LAUNCH((head_kernel<4, false, false, true>), dim3(a.B), dim3(512), 0, s, a, h);
     else if (a.A <= 8) SDQN_LAUNCH((head_kernel<8, false, false, true>), dim3(a.B), dim3(512), 0, s, a, h);
     else SDQN_LAUNCH((head_kernel<MAX_ACTIONS, false, false, true>), dim3(a.B), dim3(512), 0, s, a, h);
+    return hipGetLastError();
+  }
+  if (h.train == 2) {                                 // --double_dqn train step (separate instantiations: the default ones are unchanged)
+    if (a.bn) SDQN_LAUNCH((head_kernel<MAX_ACTIONS, true, false, false, true>), dim3(a.B), dim3(512), 0, s, a, h);
+    else if (a.A <= 4) SDQN_LAUNCH((head_kernel<4, false, false, false, true>), dim3(a.B), dim3(512), 0, s, a, h);
+    else if (a.A <= 8) SDQN_LAUNCH((head_kernel<8, false, false, false, true>), dim3(a.B), dim3(512), 0, s, a, h);
+    else SDQN_LAUNCH((head_kernel<MAX_ACTIONS, false, false, false, true>), dim3(a.B), dim3(512), 0, s, a, h);
     return hipGetLastError();
   }
   if (a.bn) SDQN_LAUNCH((head_kernel<MAX_ACTIONS, true>), dim3(a.B), dim3(512), 0, s, a, h);     // --batch_norm (not tuned per bucket)

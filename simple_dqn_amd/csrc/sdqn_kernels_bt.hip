@@ -443,10 +443,10 @@ __global__ void __launch_bounds__(256) conv1_h_kernel(const Conv1HArgs c) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int z = blockIdx.x / c.B, n = blockIdx.x - z * c.B;
-  const int64_t fb = c.from_ring ? (c.idx[n] - C0 + z) * (int64_t)FRAME : ((int64_t)z * c.B + n) * (int64_t)STATE;      // problems.h: sbase
+  const int64_t fb = c.from_ring ? (c.idx[n] - C0 + sslot(z)) * (int64_t)FRAME : ((int64_t)sslot(z) * c.B + n) * (int64_t)STATE;      // problems.h: sbase
   // ---- stage: 1764 x 16 bytes of frames (7 per thread, the last partly), 1024 x 16 bytes of weights (4 per thread) -------------------------
   const c1h_u32x4* fp = reinterpret_cast<const c1h_u32x4*>(c.src + fb);
-  const c1h_u32x4* wp = reinterpret_cast<const c1h_u32x4*>(c.wht[z] + OFF1);
+  const c1h_u32x4* wp = reinterpret_cast<const c1h_u32x4*>(c.wht[wslot(z)] + OFF1);
   c1h_u32x4 fv[7], wv[4];
 #pragma unroll
   for (int j = 0; j < 7; ++j) { const int it = tid + 256 * j; fv[j] = fp[it < STATE / 16 ? it : STATE / 16 - 1]; }
@@ -514,9 +514,9 @@ __global__ void __launch_bounds__(256) conv1_hb_kernel(const Conv1HArgs c) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int z = blockIdx.x / c.B, n = blockIdx.x - z * c.B;
-  const int64_t fb = c.from_ring ? (c.idx[n] - C0 + z) * (int64_t)FRAME : ((int64_t)z * c.B + n) * (int64_t)STATE;      // problems.h: sbase
+  const int64_t fb = c.from_ring ? (c.idx[n] - C0 + sslot(z)) * (int64_t)FRAME : ((int64_t)sslot(z) * c.B + n) * (int64_t)STATE;      // problems.h: sbase
   const c1h_u32x4* fp = reinterpret_cast<const c1h_u32x4*>(c.src + fb);
-  const c1h_u32x4* wp = reinterpret_cast<const c1h_u32x4*>(c.wht[z] + OFF1);
+  const c1h_u32x4* wp = reinterpret_cast<const c1h_u32x4*>(c.wht[wslot(z)] + OFF1);
   c1h_u32x4 fv[7], wv[4];
 #pragma unroll
   for (int j = 0; j < 7; ++j) { const int it = tid + 256 * j; fv[j] = fp[it < STATE / 16 ? it : STATE / 16 - 1]; }

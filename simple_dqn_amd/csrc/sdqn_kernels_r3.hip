@@ -149,8 +149,8 @@ __device__ __forceinline__ void conv1_bf16_body(const Conv1Args& c, const int64_
       const uint32_t lo0 = __builtin_amdgcn_readlane((int)(my_idx & 0xFFFFFFFF), n_lo), lo1 = __builtin_amdgcn_readlane((int)(my_idx >> 32), n_lo);
       const uint32_t hi0 = __builtin_amdgcn_readlane((int)(my_idx & 0xFFFFFFFF), n_hi), hi1 = __builtin_amdgcn_readlane((int)(my_idx >> 32), n_hi);
       const int64_t i_lo = (int64_t)(((uint64_t)lo1 << 32) | lo0), i_hi = (int64_t)(((uint64_t)hi1 << 32) | hi0);
-      org = ((n == n_lo ? i_lo : i_hi) - C0 + z) * (int64_t)FRAME;
-    } else org = c.from_ring ? (c.idx[n] - C0 + z) * (int64_t)FRAME : ((int64_t)z * c.B + n) * (int64_t)STATE;       // problems.h: sbase
+      org = ((n == n_lo ? i_lo : i_hi) - C0 + sslot(z)) * (int64_t)FRAME;
+    } else org = c.from_ring ? (c.idx[n] - C0 + sslot(z)) * (int64_t)FRAME : ((int64_t)sslot(z) * c.B + n) * (int64_t)STATE;       // problems.h: sbase
     const uint8_t* src = c.src + org + (int64_t)(p * ST1 + h) * W0 + q * ST1;
 #pragma unroll
     for (int t = 0; t < 16; ++t) raw[t] = *reinterpret_cast<const u32x2*>(src + (t >> 2) * FRAME + 2 * (t & 3) * W0);
@@ -193,7 +193,7 @@ __device__ __forceinline__ void conv1_bf16_body(const Conv1Args& c, const int64_
       *reinterpret_cast<uint4*>(sw + (2 * K1 + n) * W1P_PITCH + k0) = P2.v;
     }
   } else {
-    const uint4* wp = reinterpret_cast<const uint4*>(c.w1p[z]);
+    const uint4* wp = reinterpret_cast<const uint4*>(c.w1p[wslot(z)]);
     static_assert(3 * K1 * (CRS1 / 8) == 12 * 256, "3072 chunks of 8 bf16: 12 per thread");
     uint4 v[12];
 #pragma unroll
@@ -491,7 +491,7 @@ struct Fc4FwdHWT : Fc4FwdH {
   static constexpr bool PRELOAD = SDQN_PRELOAD != 0;
   __device__ static void preload(const StepArgs& a, unsigned g0, unsigned g1, unsigned g2) { SDQN_TOUCH("s"(a.h_a3), "s"(a.slab4), "s"(a.wht[0]), "s"(a.wht[1]), "s"(a.B), "s"(a.nz), "s"(a.S4), "s"(a.xcd_map), "s"(g0), "s"(g1), "s"(g2)); }
 
-  __device__ static void store(const StepArgs& a, int z, int ks, int m, int n, float v) { wt_store(&a.slab4[(((int64_t)ks * 2 + z) * a.B + m) * NFC + n], v); }
+  __device__ static void store(const StepArgs& a, int z, int ks, int m, int n, float v) { wt_store(&a.slab4[(slab4_row(a, ks, z) * a.B + m) * NFC + n], v); }
 };
 struct Fc4DgradHWT : Fc4DgradH {
   static constexpr bool PRELOAD = SDQN_PRELOAD != 0;
@@ -555,7 +555,7 @@ __global__ void __launch_bounds__(640 + 64 * NLW) conv1_bf16_rows2_kernel(const 
   if (c.from_ring) { const int nn = g + Gz * lane; my_idx = c.idx[nn < c.B ? nn : c.B - 1]; }
   // W1's planes: one coalesced copy per workgroup into LDS (all 768 threads, 4 pieces each)
   {
-    const c1p_u32x4* wp = reinterpret_cast<const c1p_u32x4*>(c.w1p[z]);
+    const c1p_u32x4* wp = reinterpret_cast<const c1p_u32x4*>(c.w1p[wslot(z)]);
     constexpr int NPC = 3 * K1 * CRS1 / 8, PPT = (NPC + NT - 1) / NT;
     c1p_u32x4 wv[PPT];
 #pragma unroll
@@ -567,9 +567,9 @@ __global__ void __launch_bounds__(640 + 64 * NLW) conv1_bf16_rows2_kernel(const 
     // ================= staging waves =================
     const int lid = tid - 640;
     auto org_of = [&](int si) -> int64_t {
-      if (!c.from_ring) return ((int64_t)z * c.B + g + (int64_t)si * Gz) * (int64_t)STATE;
+      if (!c.from_ring) return ((int64_t)sslot(z) * c.B + g + (int64_t)si * Gz) * (int64_t)STATE;
       const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)my_idx, si), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(my_idx >> 32), si);
-      return ((int64_t)(((uint64_t)hi << 32) | lo) - C0 + z) * (int64_t)FRAME;
+      return ((int64_t)(((uint64_t)hi << 32) | lo) - C0 + sslot(z)) * (int64_t)FRAME;
     };
     int poff[C1S_LPT], pdst[C1S_LPT];                         // piece j of this thread: byte offset inside a sample's item window / LDS element
 #pragma unroll
@@ -686,7 +686,7 @@ hipError_t launch_kernel_r3(int id, const StepArgs& a, const LaunchTune& t, hipS
       // number of samples where that is possible: Gz = ceil(B / ceil(B / (256 / nz)))
       // (rounds 4-5's other forms — one workgroup per sample with the frames staged, and the 10-wave pipeline without specialised
       //  waves, 15.9 / 14.5 us against 12.4-13.5 at B = 256 — left the tree in round 6: tools/exp/conv1_forms_r5.hip.txt)
-      const int cap = 256 / (a.nz > 1 ? 2 : 1), per = (a.B + cap - 1) / cap;
+      const int cap = 256 / a.nz, per = (a.B + cap - 1) / cap;
       c.wgs_per_net = (a.B + per - 1) / per;
       SDQN_LAUNCH(conv1_bf16_rows2_kernel<4>, dim3(a.nz * c.wgs_per_net), dim3(896), 0, s, c);      // (staging waves 2 / 4 / 6: 14.8 / 13.5 / 13.4 us)
       return hipGetLastError();

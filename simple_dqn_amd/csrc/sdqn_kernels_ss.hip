@@ -25,6 +25,7 @@ typedef ss::Cfg<P2, Q2, K2, 3, 3, 1, P3, Q3, 1, 8, 48, 0> C3S1;
 // does launch `id` (conv2 / conv3 forward) run on this routine?  LaunchTune::bt[id]: 0 = where its workgroups fill the chip, 7 / 8 = always
 static bool ss_takes(int id, const StepArgs& a, const LaunchTune& t) {
   if (a.B < 128 || a.bn || a.h16) return false;
+  if (a.nz == 3 && t.bt[id] == 0 && t.nw_override[id] == 0) return true;    // --double_dqn: the third slot rides in the same launches
   if ((t.bt[id] != 0 && t.bt[id] != 7 && t.bt[id] != 8) || t.nw_override[id] > 0) return false;
   // one workgroup per CU, NS whole samples each: the routine pays when its workgroups fill (nearly) whole rounds of the chip's 256 CUs —
   // B = 128 and 256 with both nets, B = 256 alone (predict) — and loses to the block-tile engine's finer blocks in between (measured,

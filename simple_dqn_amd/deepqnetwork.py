@@ -89,6 +89,10 @@ class DeepQNetwork:
             s3, s2 = [int(x) for x in os.environ["SDQN_F4_SHARE"].split(",")]
             _lib.check(self._lib.sdqn_net_set_option(h, b"f4_share3", s3))
             _lib.check(self._lib.sdqn_net_set_option(h, b"f4_share2", s2))
+        # Double DQN targets (van Hasselt, Guez and Silver 2016): the online net picks the poststate's action, the target net values it
+        self.double_dqn = bool(getattr(args, "double_dqn", False))
+        if self.double_dqn:
+            _lib.check(self._lib.sdqn_net_set_option(h, b"double_dqn", 1))
         self._mt_buf = (C.c_uint32 * _lib.MT_WORDS)()
         self._act_out = C.c_int(); self._act_greedy = self._lib.sdqn_net_act_greedy
         self.train_iterations = 0
@@ -425,10 +429,12 @@ class DeepQNetwork:
     def set_option(self, name, value):
         """Tuning / test hooks of the library (sdqn_net_set_option), e.g. 'keep_gradients' (materialise the fc4 gradient; disables the
         fused fc4 RMSProp), 'fused_launches', 'bt:<kernel id>' (throughput-regime menu), 'nw:<id>', 'tps:<layer>', 's4'.  Retired
-        experiments ('two_streams', ...) are refused by name."""
+        experiments ('two_streams', ...) are refused by name.  'double_dqn' (0 / 1) switches Double DQN targets between steps."""
         _lib.check(self._lib.sdqn_net_set_option(self._h, name.encode(), int(value)))
         if name == "dp_overlap":
             self._dp_overlap_opt = int(value)
+        elif name == "double_dqn":
+            self.double_dqn = bool(value)
 
     def sync(self):
         _lib.check(self._lib.sdqn_net_sync(self._h))

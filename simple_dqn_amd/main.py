@@ -26,6 +26,7 @@ _OPTIONS = {
         ("--optimizer", str, "rmsprop", dict(choices=["rmsprop", "adam", "adadelta"])),
         ("--decay_rate", float, 0.95), ("--clip_error", float, 1), ("--min_reward", float, -1), ("--max_reward", float, 1),
         ("--batch_norm", _flag, False),
+        ("--double_dqn", _flag, False, dict(help="Double DQN targets: the online net picks the poststate's action, the target net values it.")),
     ],
     "Backend": [
         ("--backend", str, "hip", dict(choices=["hip", "gpu", "cpu"])), ("--device_id", int, 0),

@@ -84,8 +84,31 @@ int sdqn_replay_set_state(sdqn_replay_t h, int64_t count, int64_t current);
 int sdqn_replay_upload(sdqn_replay_t h, int64_t first, int64_t n);
 /* the same for the packed metadata only (actions / rewards / terminals edited in place: 16 B per slot instead of 7 KB) */
 int sdqn_replay_upload_meta(sdqn_replay_t h, int64_t first, int64_t n);
-/* replay_memory.py:54-68 on this ring (terminals/count/current of the handle) */
+/* replay_memory.py:54-68 on this ring (terminals/count/current of the handle).  On a prioritized handle: the stratified draw by priority
+ * (below), 2 x batch MT words per call, draws_out = batch; the sample's importance weights stay on the device for the train step */
 int sdqn_replay_sample(sdqn_replay_t h, uint32_t mt[SDQN_MT_WORDS], int64_t* idx_out, int64_t* draws_out);
+
+/* ---- prioritized experience replay (Schaul et al. 2016, proportional) -------------------------------------------------
+ * P(i) = p_i / sum of p_j over the indexes the reference sampler accepts; sample n of a batch of B draws u_n = random.random() and takes
+ * the leaf whose prefix interval holds (n + u_n) S / B.  p_i = (|delta_i| + epsilon)^alpha of the unclipped TD error of the taken
+ * action; (re)written ring slots get p_max, the largest priority ever written (initially 1).  The train step weights the taken action's
+ * row by w_n = (p_n / min_m p_m)^-beta (batch-max normalised).  train_many / train_many_deferred / train_replay, and train_host on the
+ * memory's own minibatch gathered from its last sdqn_replay_sample, train with the weights and write the new priorities back; a foreign
+ * tuple trains unweighted.  Every datatype and geometry.  A sampled action out of range or a non-finite TD error is SDQN_ERR_ARG
+ * from the next synchronising call (these entry points, a train call returning its cost, sdqn_net_sync, sdqn_net_cost_collect). */
+/* switch the handle to prioritized sampling, every priority (and p_max) = 1.0; again: reset.  SDQN_ERR_ARG without the HBM mirror,
+ * alpha < 0, epsilon <= 0, batch > 256 */
+int sdqn_replay_enable_priorities(sdqn_replay_t h, double alpha, double epsilon);
+/* importance-sampling exponent of the following train steps, 0 <= beta <= 1 (default 0.4) */
+int sdqn_replay_set_priority_beta(sdqn_replay_t h, double beta);
+/* raw priorities of slots [first, first + n) (finite, > 0; p_max follows); sync */
+int sdqn_replay_set_priorities(sdqn_replay_t h, int64_t first, int64_t n, const float* values);
+/* the tree's leaves of slots [first, first + n): raw priority x valid (0 for an index the sampler cannot return); sync */
+int sdqn_replay_get_priorities(sdqn_replay_t h, int64_t first, int64_t n, float* out);
+/* p_max; sync */
+int sdqn_replay_get_max_priority(sdqn_replay_t h, float* out);
+/* the last prioritized batch (sdqn_replay_sample or a train step's own sample): indexes [batch] and weights [batch], either nullable; sync */
+int sdqn_replay_last_sample(sdqn_replay_t h, int64_t* idx_out, float* w_out);
 /* replay_memory.py:71-78: HIP gather of (s, a, r, s', terminal) by index into device HBM (async) */
 int sdqn_replay_gather(sdqn_replay_t h, const int64_t* idx_host /*[batch]*/);
 /* replay_memory.py:79: the device minibatch copied into the buffers of sdqn_replay_minibatch_ptrs (sync) */

@@ -57,6 +57,12 @@ SIGNATURES = {
     "sdqn_replay_upload_meta": (C.c_int, [_vp, C.c_int64, C.c_int64]),
     "sdqn_replay_sample": (C.c_int, [_vp, _u32p, _i64p, _i64p]),
     "sdqn_replay_gather": (C.c_int, [_vp, _i64p]),
+    "sdqn_replay_enable_priorities": (C.c_int, [_vp, C.c_double, C.c_double]),
+    "sdqn_replay_set_priority_beta": (C.c_int, [_vp, C.c_double]),
+    "sdqn_replay_set_priorities": (C.c_int, [_vp, C.c_int64, C.c_int64, _f32p]),
+    "sdqn_replay_get_priorities": (C.c_int, [_vp, C.c_int64, C.c_int64, _f32p]),
+    "sdqn_replay_get_max_priority": (C.c_int, [_vp, _f32p]),
+    "sdqn_replay_last_sample": (C.c_int, [_vp, _i64p, _f32p]),
     "sdqn_replay_minibatch_to_host": (C.c_int, [_vp]),
     "sdqn_replay_declare_minibatch_clean": (C.c_int, [_vp]),
     "sdqn_net_step_structure": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -30,6 +30,13 @@ class _Epsilon:
         return self.start - train_step * (self.start - self.end) / self.decay_steps
 
 
+def priority_beta(beta0, beta_steps, train_step):
+    """importance-sampling exponent of prioritized replay, annealed linearly from beta0 to 1 over beta_steps training steps"""
+    if beta_steps <= 0:
+        return 1.0
+    return min(1.0, beta0 + (1.0 - beta0) * train_step / beta_steps)
+
+
 class Agent:
     def __init__(self, environment, replay_memory, deep_q_network, args, fused=True):
         self.env, self.mem, self.net = environment, replay_memory, deep_q_network
@@ -43,6 +50,9 @@ class Agent:
         self.total_train_steps = args.start_epoch * args.train_steps
         self.train_frequency, self.train_repeat, self.target_steps = args.train_frequency, args.train_repeat, args.target_steps
         self.callback = None
+        self._per = getattr(replay_memory, "prioritized", False)
+        if self._per:
+            self._beta0, self._beta_steps = float(args.priority_beta), int(args.priority_beta_steps)
         self.fused = fused and hasattr(self.net, "train_from_memory") and hasattr(self.mem, "_h")
         # one library call per environment transition (state-buffer add [+ ring add] [+ the next acting forward enqueued ahead of its use])
         self._one_call = hasattr(self.net, "act_step") and hasattr(self.buf, "_h")
@@ -97,6 +107,8 @@ class Agent:
 
     # ---- learning ----------------------------------------------------------------------------------------
     def _learn(self, epoch):
+        if self._per:
+            self.mem.set_priority_beta(priority_beta(self._beta0, self._beta_steps, self.total_train_steps))
         if self.fused:
             if hasattr(self.net, "set_epoch"):
                 self.net.set_epoch(epoch)                             # what net.train(minibatch, epoch) would receive

@@ -17,6 +17,7 @@
 #include "kernels.h"
 #include "generic_net.h"
 #include "sampler.h"
+#include "sdqn_per.h"
 
 using namespace sdqn;
 
@@ -39,6 +40,16 @@ extern int g_dev;                 // device the library streams live on (bound b
 #define STREAMCHK() do { int r_ = ensure_stream(); if (r_) return r_; } while (0)
 
 const int NSLOT = 64;     // pinned index slots: kernels read the sampled indexes zero-copy
+// --prioritized_replay (sdqn_per.hip): the device priorities / sum-tree of one replay handle and what the host keeps about them
+struct PerState {
+  PerTree t;                                 // device arrays (t.err: mapped host word)
+  double alpha = 0.6, eps = 1e-6, beta = 0.4;
+  float* newp = nullptr;                     // [B] the head's new priorities (|delta| + eps)^alpha of the last PER step
+  int64_t* sidx = nullptr; float* w = nullptr;   // [B] the last sample's indexes and importance weights
+  std::vector<PerSeg> rw; bool full = true;  // slots (re)written since the last sampling launch / everything
+  std::vector<int64_t> h_sidx;               // host copy of the last sdqn_replay_sample
+  bool sample_live = false, gathered = false;   // ... not trained on yet / ... and the last gather took exactly those indexes
+};
 struct sdqn_replay_s {
   int64_t size = 0; int H = 0, W = 0, hist = 0, B = 0, flags = 0;
   int64_t frame = 0, state = 0;                    // bytes per screen / per state (hist screens); the tuned kernels need 84 x 84 x 4
@@ -63,6 +74,7 @@ struct sdqn_replay_s {
   // arrays equal it trains on the device copy (sdqn_net_train_host)
   uint8_t* mb_snap = nullptr; uint64_t mb_snap_gen = 0;
   uint64_t mb_gather_gen = 0;   // device-minibatch generation the last sdqn_replay_gather left (sdqn_replay_declare_minibatch_on_device(h, UINT64_MAX) names it)
+  PerState* per = nullptr;      // prioritized replay (nullptr: uniform sampling)
 };
 extern std::vector<sdqn_replay_s*> g_replays;      // live handles: sdqn_net_train_host recognises their pinned minibatch buffers
 
@@ -236,6 +248,20 @@ int check_ring_actions(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* idx);
 int train_replay_slot(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* pinned_idx, bool do_prep = true,
                              const int64_t* next_pinned = nullptr, double* zero8 = nullptr);
 int gen_train_replay(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* idx_host);
+// prioritized replay (sdqn_per.hip)
+int per_free(PerState* p);
+void per_mark(sdqn_replay_s* r, int64_t first, int64_t n);
+void per_mark_all(sdqn_replay_s* r);
+int per_check(sdqn_replay_s* r);
+int per_sample_host(sdqn_replay_s* r, uint32_t* mt, int64_t* idx_out, int64_t* draws_out);
+void per_note_gather(sdqn_replay_s* r, const int64_t* idx);
+bool per_owns_minibatch(sdqn_replay_s* r);
+int per_train_many(sdqn_net_s* h, sdqn_replay_s* r, uint32_t* mt, int n_steps, float* mean_cost);
+int per_train_replay(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* idx_host, float* cost_out);
+int per_train_host_step(sdqn_net_s* h, sdqn_replay_s* r, const StepArgs& a, HeadArgs hd);
+void per_gen_arm(sdqn_net_s* h, sdqn_replay_s* r);
+int per_gen_finish(sdqn_net_s* h, sdqn_replay_s* r);
+int per_check_all();
 
 inline bool prof_single_kernel(int kid) { return kid != K_ALLREDUCE && kid != K_BN; }
 #ifdef SDQN_TIMING

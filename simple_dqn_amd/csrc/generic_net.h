@@ -37,6 +37,9 @@ struct GenericNet {
   virtual hipError_t last_q(void* preq, void* maxpostq, bool host_f64) = 0;
   virtual hipError_t update_target() = 0;                                // deepqnetwork.py:102-105
   virtual hipError_t set_double_dqn(bool on) = 0;                        // --double_dqn (allocates the online-on-poststates Q on first use)
+  // --prioritized_replay (sdqn_per.hip): w != nullptr makes the following train steps weight the taken action's row by w[n] and write the
+  // new priority (|delta| + eps)^alpha into newp[n]; nullptr: the standard step
+  virtual void set_per(const float* w, float* newp, double alpha, double eps) = 0;
   virtual size_t state_bytes() const = 0;                                // hist * H * W
 };
 

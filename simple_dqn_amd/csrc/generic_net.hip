@@ -159,7 +159,7 @@ template <typename T>
 __global__ void head_kernel(const T* __restrict__ q_on, const T* __restrict__ q_tg, const uint8_t* __restrict__ act,
                             const int64_t* __restrict__ rew, const uint8_t* __restrict__ term, T* __restrict__ dq,
                             T* __restrict__ cost_terms, T* __restrict__ maxq, int N, int A, double discount, double minr, double maxr, T clip,
-                            const T* __restrict__ q_sel) {
+                            const T* __restrict__ q_sel, const float* __restrict__ per_w, float* __restrict__ per_p, double per_alpha, double per_eps) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
   T m = q_tg[(int64_t)n * A];
@@ -176,12 +176,18 @@ __global__ void head_kernel(const T* __restrict__ q_on, const T* __restrict__ q_
   const T target = (T)y;                                                      // stored into the backend dtype
   const int at = act[n];
   T d = (T)0;
+  const T w = per_w ? (T)per_w[n] : (T)1;                                     // --prioritized_replay: importance weight of the sample
   for (int a = 0; a < A; ++a) {
     T e = (a == at) ? q_on[(int64_t)n * A + a] - target : (T)0;               // deltas = preq - targets: 0 off the taken action
     if (a == at) d = e;
     if (clip != (T)0) e = e < -clip ? -clip : (e > clip ? clip : e);          // :158-159
+    if (per_w && a == at) e = w * e;                                          // clip, then weight
     dq[(int64_t)n * A + a] = e;
   }
+  if (per_w) {
+    cost_terms[n] = w * ((T)0.5 * (d * d));
+    per_p[n] = (float)pow(fabs((double)d) + per_eps, per_alpha);              // unclipped |delta|
+  } else
   cost_terms[n] = (T)0.5 * (d * d);                                           // SumSquared before the clip (A7) :154
 }
 template <typename T>
@@ -346,7 +352,8 @@ class GenericNetT : public GenericNet {
     if (dd) GCHK(forward(2, post, B));                                         // --double_dqn: online net on the poststates
     GCHK(forward(0, pre, B));                                                  // online net on the prestates, tensors kept :128-130
     hipLaunchKernelGGL(head_kernel<T>, dim3((B + 63) / 64), dim3(64), 0, st, (const T*)q, (const T*)(q + (int64_t)B * A), actions, rew, term,
-                       dq, cost_terms, maxq, B, A, cfg.discount_rate, cfg.min_reward, cfg.max_reward, (T)cfg.clip_error, (const T*)(dd ? q_sel : nullptr));
+                       dq, cost_terms, maxq, B, A, cfg.discount_rate, cfg.min_reward, cfg.max_reward, (T)cfg.clip_error, (const T*)(dd ? q_sel : nullptr),
+                       per_w, per_p, per_alpha, per_eps);
     hipLaunchKernelGGL(cost_kernel<T>, dim3(1), dim3(64), 0, st, (const T*)cost_terms, cost, cost_sum, B);
     // ---- bprop (A8) :162
     GCHK(gemm(ga(dq, 1, A, act[3], 512, 1, g + off[4], A, 512, B)));                                   // gW5 = dq^T @ a4
@@ -432,6 +439,8 @@ class GenericNetT : public GenericNet {
     if (maxpostq) GCHK(fetch(maxq, B, maxpostq, f64));
     return hipSuccess;
   }
+  void set_per(const float* w, float* newp, double alpha, double eps) override { per_w = w; per_p = newp; per_alpha = alpha; per_eps = eps; }
+  const float* per_w = nullptr; float* per_p = nullptr; double per_alpha = 0.0, per_eps = 0.0;
   hipError_t set_double_dqn(bool on) override {
     if (on && !q_sel) GCHK(dalloc(&q_sel, (int64_t)B * A));
     double_dqn = on;

@@ -40,6 +40,9 @@ struct HeadArgs {
   // hoist: one extra workgroup copies the NEXT step's sampled indexes from their pinned slot into device memory, so that
   // the target conv1 riding in this step's K_BWD2 launch reads them from HBM (next_B = 0: nothing to copy)
   const int64_t* next_idx_pinned; int64_t* next_idx_dev; int next_B;
+  // --prioritized_replay (sdqn_per.hip): per_w != nullptr selects the PER head — dq = w clip(delta), cost term 0.5 w delta^2, and
+  // per_p[n] = (|delta| + per_eps)^per_alpha, the new priority the next per_step launch writes back
+  const float* per_w; float* per_p; double per_alpha, per_eps;
 };
 
 struct PrepArgs {                // pinned index slot + ring metadata -> device-resident (idx, a, r, t) of this step

@@ -409,7 +409,7 @@ extern "C" int sdqn_net_half_payload_state(sdqn_net_t h, int* flag, int* scale_l
 }
 extern "C" int sdqn_net_sync(sdqn_net_t h) {
   ARGCHK(h, "NULL handle");
-  if (h->gen) { HIPCHK(hipStreamSynchronize(g_stream)); return SDQN_OK; }
+  if (h->gen) { HIPCHK(hipStreamSynchronize(g_stream)); return per_check_all(); }
   int rc = join_comm(h); if (rc) return rc;
   // short waits are polled (a blocking hipStreamSynchronize costs 10-20 us of wake-up latency: 1 % of a 20-step call); anything
   // longer than ~2 ms falls through to the blocking wait
@@ -418,7 +418,7 @@ extern "C" int sdqn_net_sync(sdqn_net_t h) {
       if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
     (void)hipGetLastError(); }
   HIPCHK(hipStreamSynchronize(g_stream));
-  return SDQN_OK;
+  return per_check_all();                  // (a prioritized memory's device flags)
 }
 extern "C" int sdqn_net_last_q(sdqn_net_t h, float* preq, float* maxpostq) {
   ARGCHK(h, "NULL handle");

@@ -15,6 +15,7 @@ int replay_free(sdqn_replay_s* r) {
   for (int i = 0; i < NSLOT; ++i) if (r->slot_ev[i]) hipEventDestroy(r->slot_ev[i]);
   if (r->mb_upload_ev) hipEventDestroy(r->mb_upload_ev);
   free(r->mb_snap);
+  per_free(r->per);
   delete r;
   return SDQN_OK;
 }
@@ -95,6 +96,7 @@ extern "C" int sdqn_replay_add(sdqn_replay_t r, int action, int64_t reward, cons
   }
   if (c + 1 > r->count) r->count = c + 1;                         // :33
   r->current = (c + 1) % r->size;                                 // :34
+  per_mark(r, c, 1);                                              // prioritized: p_max, validity of [c, c + 1 + hist) re-evaluated
   return SDQN_OK;
 }
 extern "C" int sdqn_replay_get_state(sdqn_replay_t r, int64_t* count, int64_t* current) {
@@ -102,7 +104,7 @@ extern "C" int sdqn_replay_get_state(sdqn_replay_t r, int64_t* count, int64_t* c
 }
 extern "C" int sdqn_replay_set_state(sdqn_replay_t r, int64_t count, int64_t current) {
   ARGCHK(r && count >= 0 && count <= r->size && current >= 0 && current < r->size, "bad count/current");
-  r->count = count; r->current = current; return SDQN_OK;
+  r->count = count; r->current = current; per_mark_all(r); return SDQN_OK;
 }
 extern "C" int sdqn_replay_upload(sdqn_replay_t r, int64_t first, int64_t n) {
   ARGCHK(r && first >= 0 && n >= 0 && first + n <= r->size, "bad upload range");
@@ -115,6 +117,7 @@ extern "C" int sdqn_replay_upload(sdqn_replay_t r, int64_t first, int64_t n) {
     HIPCHK(hipMemcpyAsync(r->d_ring + first * FRAME, r->screens + first * FRAME, (size_t)n * FRAME, hipMemcpyHostToDevice, g_stream));
     HIPCHK(hipMemcpyAsync(r->d_meta + first, r->h_meta + first, (size_t)n * sizeof(MetaRec), hipMemcpyHostToDevice, g_stream));
   }
+  per_mark(r, first, n);
   HIPCHK(hipStreamSynchronize(g_stream));
   return SDQN_OK;
 }
@@ -127,11 +130,13 @@ extern "C" int sdqn_replay_upload_meta(sdqn_replay_t r, int64_t first, int64_t n
   }
   if (!(r->flags & SDQN_REPLAY_ZERO_COPY) && n > 0)
     HIPCHK(hipMemcpyAsync(r->d_meta + first, r->h_meta + first, (size_t)n * sizeof(MetaRec), hipMemcpyHostToDevice, g_stream));
+  per_mark(r, first, n);
   HIPCHK(hipStreamSynchronize(g_stream));
   return SDQN_OK;
 }
 extern "C" int sdqn_replay_sample(sdqn_replay_t r, uint32_t* mt, int64_t* idx_out, int64_t* draws_out) {
   ARGCHK(r, "NULL handle");
+  if (r->per) return per_sample_host(r, mt, idx_out, draws_out);        // prioritized: by priority on the device (sdqn_per.hip)
   return sample_checked(mt, r->terminals, r->count, r->current, r->hist, r->B, idx_out, draws_out);
 }
 
@@ -195,6 +200,7 @@ extern "C" int sdqn_replay_gather(sdqn_replay_t r, const int64_t* idx_host) {
   ARGCHK(r && idx_host, "NULL argument");
   for (int i = 0; i < r->B; ++i)
     ARGCHK(idx_host[i] >= r->hist && idx_host[i] < r->count, "index %lld out of range (count %lld)", (long long)idx_host[i], (long long)r->count);
+  per_note_gather(r, idx_host);
   if (!r->tuned_geom) {
     int slot; const int64_t* didx; int rc = replay_push_idx(r, idx_host, &slot, &didx); if (rc) return rc;
     rc = replay_gather_generic(r, didx); if (rc) return rc;

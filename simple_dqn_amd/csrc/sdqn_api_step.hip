@@ -306,7 +306,7 @@ int read_cost(sdqn_net_s* h, float* cost_out) {
   HIPCHK(hipMemcpyAsync(h->h_f, h->cost_out, 4, hipMemcpyDeviceToHost, g_stream));
   HIPCHK(hipStreamSynchronize(g_stream));
   *cost_out = h->h_f[0];
-  return SDQN_OK;
+  return per_check_all();                  // (a prioritized memory's device flags: action out of range, non-finite TD error)
 }
 
 extern "C" int sdqn_net_predict_f64(sdqn_net_t h, const uint8_t* states, double* q_out) {
@@ -384,8 +384,12 @@ extern "C" int sdqn_net_train_host(sdqn_net_t h, const uint8_t* pre, const uint8
   const bool ours = owner != nullptr;
   if (h->gen) {
     ARGCHK(!ours || (size_t)owner->state == h->gen->state_bytes(), "replay geometry differs from the network's");
-    if (reuse) GENCHK(h->gen->train_dev_host_meta(owner->d_pre, owner->d_post, actions, rewards, terminals, h->epoch));
-    else GENCHK(h->gen->train_host(pre, actions, rewards, post, terminals, h->epoch));
+    const bool per = per_owns_minibatch(owner);                 // prioritized memory: weighted step + priority write-back
+    if (per) per_gen_arm(h, owner);
+    const hipError_t ge = reuse ? h->gen->train_dev_host_meta(owner->d_pre, owner->d_post, actions, rewards, terminals, h->epoch)
+                                : h->gen->train_host(pre, actions, rewards, post, terminals, h->epoch);
+    if (per) { int rcp = per_gen_finish(h, owner); if (ge == hipSuccess && rcp) return rcp; }
+    GENCHK(ge);
     h->train_iterations += 1;
     if (cost_out) { double c; GENCHK(h->gen->read_cost(&c)); *cost_out = (float)c; }
     return SDQN_OK;
@@ -433,7 +437,8 @@ extern "C" int sdqn_net_train_host(sdqn_net_t h, const uint8_t* pre, const uint8
   StepArgs a = step_args(h); a.from_ring = 0; a.src = reuse ? owner->d_pre : h->st_states;
   HeadArgs hd = head_args(h, 1);
   if (small_dev) { hd.st_actions = owner->d_act; hd.st_rewards = owner->d_rew; hd.st_terminals = owner->d_term; }
-  int rc = run_train(h, a, hd); if (rc) return rc;
+  // prioritized memory, minibatch gathered from its last sample: weighted step + priority write-back (a foreign tuple: the standard step)
+  int rc = per_owns_minibatch(owner) ? per_train_host_step(h, owner, a, hd) : run_train(h, a, hd); if (rc) return rc;
   if (ours && !reuse) { HIPCHK(hipEventSynchronize(owner->mb_upload_ev)); }
   if (cost_out) return read_cost(h, cost_out);
   return SDQN_OK;
@@ -492,6 +497,7 @@ int gen_train_replay(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* idx_host) {
 extern "C" int sdqn_net_train_replay(sdqn_net_t h, sdqn_replay_t r, const int64_t* idx_host, float* cost_out) {
   ARGCHK(h && r && idx_host, "NULL argument");
   ARGCHK(r->B == h->B, "replay batch_size %d != network batch_size %d", r->B, h->B);
+  if (r->per) return per_train_replay(h, r, idx_host, cost_out);
   if (h->gen) {
     int rc = gen_train_replay(h, r, idx_host); if (rc) return rc;
     if (cost_out) { double c; GENCHK(h->gen->read_cost(&c)); *cost_out = (float)c; }
@@ -508,6 +514,7 @@ extern "C" int sdqn_net_train_replay(sdqn_net_t h, sdqn_replay_t r, const int64_
 extern "C" int sdqn_net_train_many(sdqn_net_t h, sdqn_replay_t r, uint32_t* mt, int n_steps, float* mean_cost) {
   ARGCHK(h && r && mt && n_steps >= 0, "bad arguments");
   ARGCHK(r->B == h->B, "replay batch_size %d != network batch_size %d", r->B, h->B);
+  if (r->per) return per_train_many(h, r, mt, n_steps, mean_cost);
   if (h->gen) {
     std::vector<int64_t> gi((size_t)r->B);
     GENCHK(h->gen->reset_cost_sum());
@@ -579,6 +586,6 @@ extern "C" int sdqn_net_cost_collect(sdqn_net_t h, int64_t ticket, float* mean_c
   ARGCHK(*w != ~0ull, "the cost of ticket %lld was never delivered", (long long)ticket);
   uint64_t bits = *w; double sum; memcpy(&sum, &bits, 8);
   *mean_cost = (float)(sum / h->cost_steps[slot]);
-  return SDQN_OK;
+  return per_check_all();
 }
 extern "C" int sdqn_mt_words(uint64_t* words) { ARGCHK(words, "NULL argument"); *words = mt_words_drawn(); return SDQN_OK; }

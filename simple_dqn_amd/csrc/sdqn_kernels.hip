@@ -143,7 +143,8 @@ hipError_t launch_kernel(int id, const StepArgs& a, const LaunchTune& t, hipStre
 // fetches the next step's indexes from their pinned host slot into HBM.
 // QSYS (acting path, round 4): h.q is HOST memory (mapped, pinned) and every Q-value leaves with a system-scope store the moment it is
 // summed, so the host can poll for it instead of paying a D2H copy packet + a stream synchronisation (sdqn_api_act.hip: predict_state).
-template <int AMAX, bool BN, bool HOIST = false, bool QSYS = false, bool DDQN = false>
+// PER (--prioritized_replay): the taken action's row is weighted by h.per_w[n] and the new priority goes to h.per_p[n]
+template <int AMAX, bool BN, bool HOIST = false, bool QSYS = false, bool DDQN = false, bool PER = false>
 __global__ void __launch_bounds__(512) head_kernel(const StepArgs a, const HeadArgs h) {
   SDQN_STAMP(0);
   if constexpr (HOIST) {
@@ -195,6 +196,8 @@ __global__ void __launch_bounds__(512) head_kernel(const StepArgs a, const HeadA
   // minibatch metadata last: thread 0 only, and nothing above waits behind it
   int m_act = 0, m_term = 0; int64_t m_rew = 0;
   if (h.train && j == 0) { m_act = h.st_actions[n]; m_rew = h.st_rewards[n]; m_term = h.st_terminals[n]; }
+  float m_w = 1.0f;
+  if constexpr (PER) { if (j == 0) m_w = h.per_w[n]; }
   m_act = m_act < A ? m_act : A - 1;                 // memory safety only: the host rejects out-of-range actions before launching
   if constexpr (BN) {
   } else if (a.S4 == 7) {
@@ -266,9 +269,14 @@ __global__ void __launch_bounds__(512) head_kernel(const StepArgs a, const HeadA
     rr = rr < h.min_reward ? h.min_reward : (rr > h.max_reward ? h.max_reward : rr);
     const double y = term ? rr : rr + h.discount * (double)m;                                    // :139-143 (host float math)
     const float d = sh_q[0][act] - (float)y;                                                     // get_errors, :149
-    h.cost_terms[n] = 0.5f * (d * d);                                                            // get_cost summand, :154
     float dc = d;
     if (h.clip_error != 0.0f) dc = fminf(fmaxf(d, -h.clip_error), h.clip_error);                 // :158-159
+    if constexpr (PER) {                             // importance weight on the taken action's row: clip first, then weight
+      h.cost_terms[n] = m_w * (0.5f * (d * d));
+      dc = m_w * dc;
+      h.per_p[n] = (float)pow(fabs((double)d) + h.per_eps, h.per_alpha);                         // unclipped |delta|
+    } else
+    h.cost_terms[n] = 0.5f * (d * d);                                                            // get_cost summand, :154
     h.maxq[n] = m;
     sh_dc = dc; sh_act = act;
   }
@@ -319,6 +327,20 @@ hipError_t launch_head(const StepArgs& a, const HeadArgs& h, hipStream_t s, bool
     if (a.A <= 4) SDQN_LAUNCH((head_kernel<4, false, false, true>), dim3(a.B), dim3(512), 0, s, a, h);
     else if (a.A <= 8) SDQN_LAUNCH((head_kernel<8, false, false, true>), dim3(a.B), dim3(512), 0, s, a, h);
     else SDQN_LAUNCH((head_kernel<MAX_ACTIONS, false, false, true>), dim3(a.B), dim3(512), 0, s, a, h);
+    return hipGetLastError();
+  }
+  if (h.per_w && h.train) {                           // --prioritized_replay train step (its own instantiations, with or without Double DQN)
+    if (h.train == 2) {
+      if (a.bn) SDQN_LAUNCH((head_kernel<MAX_ACTIONS, true, false, false, true, true>), dim3(a.B), dim3(512), 0, s, a, h);
+      else if (a.A <= 4) SDQN_LAUNCH((head_kernel<4, false, false, false, true, true>), dim3(a.B), dim3(512), 0, s, a, h);
+      else if (a.A <= 8) SDQN_LAUNCH((head_kernel<8, false, false, false, true, true>), dim3(a.B), dim3(512), 0, s, a, h);
+      else SDQN_LAUNCH((head_kernel<MAX_ACTIONS, false, false, false, true, true>), dim3(a.B), dim3(512), 0, s, a, h);
+    } else {
+      if (a.bn) SDQN_LAUNCH((head_kernel<MAX_ACTIONS, true, false, false, false, true>), dim3(a.B), dim3(512), 0, s, a, h);
+      else if (a.A <= 4) SDQN_LAUNCH((head_kernel<4, false, false, false, false, true>), dim3(a.B), dim3(512), 0, s, a, h);
+      else if (a.A <= 8) SDQN_LAUNCH((head_kernel<8, false, false, false, false, true>), dim3(a.B), dim3(512), 0, s, a, h);
+      else SDQN_LAUNCH((head_kernel<MAX_ACTIONS, false, false, false, false, true>), dim3(a.B), dim3(512), 0, s, a, h);
+    }
     return hipGetLastError();
   }
   if (h.train == 2) {                                 // --double_dqn train step (separate instantiations: the default ones are unchanged)

@@ -20,7 +20,13 @@ _OPTIONS = {
         ("--synthetic_frame_pool", int, 256, dict(help="Synthetic environment: serve frames from a pool of this many pre-generated frames (0: generate 7 KB of random bytes every step).")),
         ("--screen_width", int, 84), ("--screen_height", int, 84),
     ],
-    "Replay memory": [("--replay_size", int, 1000000), ("--history_length", int, 4)],
+    "Replay memory": [
+        ("--replay_size", int, 1000000), ("--history_length", int, 4),
+        ("--prioritized_replay", _flag, False, dict(help="Prioritized experience replay (proportional): sample by (|TD error| + epsilon)^alpha, importance-weighted loss.")),
+        ("--priority_alpha", float, 0.6), ("--priority_beta", float, 0.4),
+        ("--priority_beta_steps", int, 1000000, dict(help="Training steps over which the importance-sampling exponent anneals from --priority_beta to 1.")),
+        ("--priority_epsilon", float, 1e-6),
+    ],
     "Deep Q-learning network": [
         ("--learning_rate", float, 0.00025), ("--discount_rate", float, 0.99), ("--batch_size", int, 32),
         ("--optimizer", str, "rmsprop", dict(choices=["rmsprop", "adam", "adadelta"])),

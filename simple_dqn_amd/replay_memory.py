@@ -70,6 +70,13 @@ class ReplayMemory:
         self._idx = np.empty(self.batch_size, dtype=np.int64)
         self._mt = (C.c_uint32 * _lib.MT_WORDS)()
         self.last_indexes = None
+        # --prioritized_replay: priorities and their sum-tree live on the device; getMinibatch() samples by priority and the
+        # train step of the minibatch it returns weights the loss and writes the new priorities back
+        self.prioritized = bool(getattr(args, "prioritized_replay", False))
+        if self.prioritized:
+            self._priority_args = (float(args.priority_alpha), float(args.priority_epsilon))
+            _lib.check(self._lib.sdqn_replay_enable_priorities(h, *self._priority_args))
+            self.set_priority_beta(float(args.priority_beta))
         logger.info("Replay memory size: %d" % self.size)
 
     def __del__(self):
@@ -202,6 +209,8 @@ class ReplayMemory:
         """replay_memory.py:54-68 on Python's GLOBAL random stream (shared with agent.py:32,50-51): the generator's state goes in as a
         copy, the library's sampler draws from it, and Python's own generator is advanced by exactly the 32-bit words that were drawn
         (one getrandbits call: Modules/_randommodule.c — rebuilding a 625-tuple for random.setstate cost 40 us per call)."""
+        if self.prioritized:
+            self._check_mirror()                # (the device refreshes validity from the mirror's metadata before it samples)
         st = random.getstate()
         arr = array.array("I", st[1])
         mt = (C.c_uint32 * _lib.MT_WORDS).from_buffer(arr)
@@ -235,6 +244,41 @@ class ReplayMemory:
         raw = self._raw
         return self._lazy_pre, raw["actions"][idx], raw["rewards"][idx], self._lazy_post, raw["terminals"][idx]
 
+    # ---- prioritized replay ------------------------------------------------------------------------------------------
+    def set_priority_beta(self, beta):
+        """importance-sampling exponent of the following train steps (0 <= beta <= 1)"""
+        _lib.check(self._lib.sdqn_replay_set_priority_beta(self._h, float(beta)))
+
+    def priorities(self, first=0, n=None):
+        """the sum-tree's leaves of slots [first, first + n): raw priority x valid (0 where the sampler cannot land)"""
+        n = self.size - first if n is None else n
+        out = np.empty(n, dtype=np.float32)
+        self._check_mirror()
+        _lib.check(self._lib.sdqn_replay_get_priorities(self._h, int(first), int(n), _lib.ptr(out, C.c_float)))
+        return out
+
+    def set_priorities(self, first, values):
+        """raw priorities of slots [first, first + len(values)) (finite, > 0)"""
+        v = np.ascontiguousarray(values, dtype=np.float32).reshape(-1)
+        self._check_mirror()
+        _lib.check(self._lib.sdqn_replay_set_priorities(self._h, int(first), v.size, _lib.ptr(v, C.c_float)))
+
+    @property
+    def max_priority(self):
+        v = C.c_float()
+        _lib.check(self._lib.sdqn_replay_get_max_priority(self._h, C.byref(v)))
+        return v.value
+
+    def last_sample(self):
+        """(indexes, importance weights) of the last prioritized batch"""
+        idx, w = np.empty(self.batch_size, dtype=np.int64), np.empty(self.batch_size, dtype=np.float32)
+        _lib.check(self._lib.sdqn_replay_last_sample(self._h, _lib.ptr(idx, C.c_int64), _lib.ptr(w, C.c_float)))
+        return idx, w
+
+    @property
+    def last_weights(self):
+        return self.last_sample()[1]
+
     def getMinibatch(self):                                        # :50-79
         assert self.count > self.history_length
         return self.gather(self.sample_indexes())
@@ -264,6 +308,8 @@ class ReplayMemory:
             f.readinto(memoryview(self._raw["screens"][:count]).cast("B"))
         _lib.check(self._lib.sdqn_replay_set_state(self._h, int(count), int(current)))
         self.sync_mirror(0, int(count))
+        if self.prioritized:                    # priorities are not part of the checkpoint: all back to 1.0
+            _lib.check(self._lib.sdqn_replay_enable_priorities(self._h, *self._priority_args))
 
     def bench_gather(self, indexes, iters=100):
         """ms per launch of the standalone gather kernel.  `indexes`: one index set [B] (repeated: cache-resident after the first

@@ -61,6 +61,12 @@ int sdqn_mt_randint(uint32_t mt[SDQN_MT_WORDS], int64_t a, int64_t b, int64_t* o
 int sdqn_sample_indices(uint32_t mt[SDQN_MT_WORDS], const uint8_t* terminals, int64_t count,
                         int64_t current, int history_length, int batch,
                         int64_t* idx_out /*[batch]*/, int64_t* draws_out /*nullable*/);
+/* --n_step: the same rejection loop for n-step transitions — index = randint(history_length, count - n), rejected when
+ * the window [index - history_length, index + n - 1] straddles `current` or terminals[index - history_length : index] holds a terminal;
+ * n = 1 is sdqn_sample_indices draw for draw.  count < history_length + n is SDQN_ERR_ARG. */
+#define SDQN_MAX_N_STEP 16
+int sdqn_sample_indices_n(uint32_t mt[SDQN_MT_WORDS], const uint8_t* terminals, int64_t count, int64_t current,
+                          int history_length, int n, int batch, int64_t* idx_out /*[batch]*/, int64_t* draws_out /*nullable*/);
 
 /* ---- replay memory: src/replay_memory.py ---------------------------------- */
 #define SDQN_REPLAY_HBM_MIRROR 1   /* ring master in pinned host DRAM + mirror in HBM (default) */
@@ -87,6 +93,12 @@ int sdqn_replay_upload_meta(sdqn_replay_t h, int64_t first, int64_t n);
 /* replay_memory.py:54-68 on this ring (terminals/count/current of the handle).  On a prioritized handle: the stratified draw by priority
  * (below), 2 x batch MT words per call, draws_out = batch; the sample's importance weights stay on the device for the train step */
 int sdqn_replay_sample(sdqn_replay_t h, uint32_t mt[SDQN_MT_WORDS], int64_t* idx_out, int64_t* draws_out);
+/* --n_step n (1..16): sampling follows sdqn_sample_indices_n, and every gather of this handle (sdqn_replay_gather and the
+ * train paths' own) takes the poststate of sample i from state(i + n - 1) and turns (rewards, terminals)[i .. i + n - 1] into the return
+ * R = sum_k gamma^k clip(r_{i+k}) up to and including the first terminal, and done = "a terminal was met".  sdqn_replay_gather leaves R
+ * (float64 bits) where the rewards go and done where the terminals go.  A train call refuses a memory whose (n, discount, min_reward,
+ * max_reward) differ from the network's (option "n_step" and its configuration).  n = 1: the standard memory. */
+int sdqn_replay_set_n_step(sdqn_replay_t h, int n, double discount, double min_reward, double max_reward);
 
 /* ---- prioritized experience replay (Schaul et al. 2016, proportional) -------------------------------------------------
  * P(i) = p_i / sum of p_j over the indexes the reference sampler accepts; sample n of a batch of B draws u_n = random.random() and takes
@@ -220,6 +232,11 @@ int sdqn_net_debug_act(sdqn_net_t h, sdqn_statebuf_t sb, float* q_out, unsigned 
  * Threading: handles are created, used and destroyed from ONE host thread (no internal locking). */
 int sdqn_net_train_host(sdqn_net_t h, const uint8_t* pre, const uint8_t* actions, const int64_t* rewards,
                         const uint8_t* post, const uint8_t* terminals, float* cost_out);
+/* the same step for an n-step tuple (option "n_step" > 1, which sdqn_net_train_host refuses): returns R [batch] float64 (clipped per
+ * step already: not clipped again) and dones [batch]; target = R if done else R + discount^n max Q'(post).  The lazy-state and
+ * small-array reuse of sdqn_net_train_host apply unchanged (an unedited gather of an n-step memory uploads nothing). */
+int sdqn_net_train_host_returns(sdqn_net_t h, const uint8_t* pre, const uint8_t* actions, const double* returns,
+                                const uint8_t* post, const uint8_t* dones, float* cost_out);
 /* How sdqn_net_train_host has been served on this handle: calls / calls that read the states from the device minibatch in place (no
  * 2 x batch x state H2D) / calls that uploaded nothing at all (small arrays equal to what the gather left on the device).  Any NULL. */
 int sdqn_net_tuple_counters(sdqn_net_t h, int64_t* calls, int64_t* states_in_place, int64_t* nothing_uploaded);
@@ -280,6 +297,10 @@ int sdqn_net_step_structure(sdqn_net_t h, int* structure, int* update);
  * the poststates rides as a third net slot in the step's own forward launches (batch_norm: a forward of its own in front of the step,
  * inference mode with the running statistics as they stand before the step); without a target net (target_enabled = 0) it is the
  * standard step.
+ * option "n_step" (1 default .. 16, any configuration, between steps): n-step returns — the poststate of sample i is
+ * state(i + n - 1) (a run-time frame offset of the forward launches: no added launch), the target R + discount^n max Q' (R only when
+ * an episode ended inside the n steps).  Ring-fed train calls need a replay memory set to the same n (sdqn_replay_set_n_step); tuples
+ * go through sdqn_net_train_host_returns.  sdqn_net_last_q's maxpostq is then the bootstrap value of state(i + n - 1).
  * options: "grad_only" (see sdqn_net_apply_update), "keep_gradients" (1: the fc4 gradient is materialised and readable with which=3; 0 (default): on one
  * GPU RMSProp of fc4 is fused into the wgrad epilogue), "two_streams" (0 default; 1: wgrad kernels overlap the dgrad chain on a side stream), "fused_launches" (1 default:
  * independent backward stages share one grid), "xcd_map" (0 default = only where it wins time: conv1/conv2/fc4 forward; 1: the

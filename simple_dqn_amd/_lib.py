@@ -45,6 +45,7 @@ SIGNATURES = {
     "sdqn_mt_seed": (C.c_int, [_u32p, C.c_uint64]),
     "sdqn_mt_randint": (C.c_int, [_u32p, C.c_int64, C.c_int64, _i64p]),
     "sdqn_sample_indices": (C.c_int, [_u32p, _u8p, C.c_int64, C.c_int64, C.c_int, C.c_int, _i64p, _i64p]),
+    "sdqn_sample_indices_n": (C.c_int, [_u32p, _u8p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, _i64p, _i64p]),
     "sdqn_replay_create": (C.c_int, [C.POINTER(_vp), C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "sdqn_replay_destroy": (C.c_int, [_vp]),
     "sdqn_replay_host_ptrs": (C.c_int, [_vp, C.POINTER(_u8p), C.POINTER(_u8p), C.POINTER(_i64p), C.POINTER(_u8p)]),
@@ -56,6 +57,7 @@ SIGNATURES = {
     "sdqn_replay_upload": (C.c_int, [_vp, C.c_int64, C.c_int64]),
     "sdqn_replay_upload_meta": (C.c_int, [_vp, C.c_int64, C.c_int64]),
     "sdqn_replay_sample": (C.c_int, [_vp, _u32p, _i64p, _i64p]),
+    "sdqn_replay_set_n_step": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.c_double]),
     "sdqn_replay_gather": (C.c_int, [_vp, _i64p]),
     "sdqn_replay_enable_priorities": (C.c_int, [_vp, C.c_double, C.c_double]),
     "sdqn_replay_set_priority_beta": (C.c_int, [_vp, C.c_double]),
@@ -92,6 +94,7 @@ SIGNATURES = {
     "sdqn_net_act_greedy": (C.c_int, [_vp, _vp, C.POINTER(C.c_int), _f32p]),
     "sdqn_net_debug_act": (C.c_int, [_vp, _vp, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]),
     "sdqn_net_train_host": (C.c_int, [_vp, _u8p, _u8p, _i64p, _u8p, _u8p, _f32p]),
+    "sdqn_net_train_host_returns": (C.c_int, [_vp, _u8p, _u8p, _f64p, _u8p, _u8p, _f32p]),
     "sdqn_net_train_replay": (C.c_int, [_vp, _vp, _i64p, _f32p]),
     "sdqn_net_train_many": (C.c_int, [_vp, _vp, _u32p, C.c_int, _f32p]),
     "sdqn_net_train_many_deferred": (C.c_int, [_vp, _vp, _u32p, C.c_int, C.POINTER(C.c_int64)]),

@@ -75,6 +75,7 @@ struct sdqn_replay_s {
   uint8_t* mb_snap = nullptr; uint64_t mb_snap_gen = 0;
   uint64_t mb_gather_gen = 0;   // device-minibatch generation the last sdqn_replay_gather left (sdqn_replay_declare_minibatch_on_device(h, UINT64_MAX) names it)
   PerState* per = nullptr;      // prioritized replay (nullptr: uniform sampling)
+  NStepArgs ns = {1, 0, 0.0, 0.0, 0.0};   // --n_step (sdqn_replay_set_n_step; n = 1: standard transitions)
 };
 extern std::vector<sdqn_replay_s*> g_replays;      // live handles: sdqn_net_train_host recognises their pinned minibatch buffers
 
@@ -118,6 +119,7 @@ struct sdqn_net_s {
   // --double_dqn (option "double_dqn"): the forward launches carry a third net slot (problems.h: wslot); a1..a3, slab4, a4, q (and
   // h_a1..h_a3) are re-allocated with room for it when the option is first switched on
   bool double_dqn = false, slots3 = false;
+  int n_step = 1;                          // --n_step (option "n_step"): poststate frame offset of the ring paths, n-step head
   uint8_t *st_states = nullptr, *st_act = nullptr, *st_term = nullptr; int64_t* st_rew = nullptr; int64_t* d_idx = nullptr;
   int64_t* d_idx_t = nullptr;              // hoist: the NEXT step's indexes (copied from their pinned slot by an extra workgroup of the head launch)
                                            // Built, bit-identical, measured 1.8 % SLOWER (tools/exp/README.md) -> off; set_option "hoist"
@@ -209,7 +211,9 @@ enum UpdateForm { UPD_SINGLE = 0, UPD_DP_SERIAL = 1, UPD_DP_OVERLAP = 2, UPD_GRA
 // ---- functions that cross a file boundary -------------------------------------------------------------------------------
 int ensure_stream();
 int sample_checked(uint32_t* mt, const uint8_t* terminals, int64_t count, int64_t current, int hist,
-                          int batch, int64_t* idx_out, int64_t* draws_out);
+                          int batch, int64_t* idx_out, int64_t* draws_out, int nstep = 1);
+int nstep_match(const sdqn_net_s* h, const sdqn_replay_s* r);       // --n_step: the memory's (n, discount, reward clip) equal the net's
+double nstep_gamma_n(int n, double gamma);                         // gamma^n by repeated multiplication (the n-step loop's g)
 int replay_free(sdqn_replay_s* r);
 int replay_flush_pending(sdqn_replay_s* r);
 int replay_push_idx(sdqn_replay_s* r, const int64_t* idx, int* slot_out, const int64_t** dev);

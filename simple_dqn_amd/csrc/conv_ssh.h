@@ -50,7 +50,7 @@ struct Args {
   int B, G;                 // G = workgroups per net = ceil(B / NS)
   // C1 (conv1 rides in front: the workgroup computes its own a1 from the frames): the replay ring / the staged states, the sampled
   // indexes, W1^T [32 maps][256 k] per net, and where a1 goes for the backward pass
-  const uint8_t* src; const int64_t* idx; const h_t* w1[2]; h_t* a1w; int from_ring;
+  const uint8_t* src; const int64_t* idx; const h_t* w1[2]; h_t* a1w; int from_ring, post_off;     // post_off: StepArgs::post_off
 };
 
 template <int NS> struct Lds {
@@ -113,7 +113,7 @@ __global__ void __launch_bounds__(NT_) conv_ssh_chain_kernel(const Args c) {
     h_t* const cw = rw + 4 * 84 * 84;                                        // W1^T [32][256 + 8]
     auto frames = [&](int sI, u32x4 (&fv)[FPT]) {
       const int nn = n0 + (sI < nvalid ? sI : nvalid - 1);
-      const int64_t fb = c.from_ring ? (c.idx[nn] - 4 + sslot(z)) * (int64_t)(84 * 84) : ((int64_t)sslot(z) * c.B + nn) * (int64_t)(4 * 84 * 84);      // problems.h: sbase
+      const int64_t fb = c.from_ring ? (c.idx[nn] - 4 + soff(c.post_off, z)) * (int64_t)(84 * 84) : ((int64_t)sslot(z) * c.B + nn) * (int64_t)(4 * 84 * 84);      // problems.h: sbase
       const u32x4* const fp = reinterpret_cast<const u32x4*>(c.src + fb);
 #pragma unroll
       for (int j = 0; j < FPT; ++j) { const int it = tid + NT_ * j; fv[j] = fp[it < FPC ? it : FPC - 1]; }

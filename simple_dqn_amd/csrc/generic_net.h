@@ -9,6 +9,7 @@
 #include <stdint.h>
 #include <string>
 #include "../../include/sdqn.h"
+#include "problems.h"          // NStepArgs
 
 namespace sdqn {
 
@@ -40,6 +41,9 @@ struct GenericNet {
   // --prioritized_replay (sdqn_per.hip): w != nullptr makes the following train steps weight the taken action's row by w[n] and write the
   // new priority (|delta| + eps)^alpha into newp[n]; nullptr: the standard step
   virtual void set_per(const float* w, float* newp, double alpha, double eps) = 0;
+  // --n_step: n > 1 makes the train steps read rew as the n-step returns (float64 bits) and term as the done flags, and
+  // bootstrap with gamma_n; n = 1: the standard step
+  virtual void set_nstep(int n, double gamma_n) = 0;
   virtual size_t state_bytes() const = 0;                                // hist * H * W
 };
 
@@ -51,6 +55,7 @@ struct GatherGenericArgs {
   const uint8_t* ring; const void* meta /*MetaRec[]*/; const int64_t* idx /*device*/;
   uint8_t *pre, *post, *actions; int64_t* rewards; uint8_t* terminals;
   int B, hist; int64_t frame;
+  NStepArgs ns;                 // --n_step: poststate = frames idx-hist+n .. idx+n-1; rewards / terminals receive (R, done)
 };
 hipError_t launch_gather_generic(const GatherGenericArgs& g, hipStream_t s);
 

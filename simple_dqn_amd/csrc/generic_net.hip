@@ -159,7 +159,8 @@ template <typename T>
 __global__ void head_kernel(const T* __restrict__ q_on, const T* __restrict__ q_tg, const uint8_t* __restrict__ act,
                             const int64_t* __restrict__ rew, const uint8_t* __restrict__ term, T* __restrict__ dq,
                             T* __restrict__ cost_terms, T* __restrict__ maxq, int N, int A, double discount, double minr, double maxr, T clip,
-                            const T* __restrict__ q_sel, const float* __restrict__ per_w, float* __restrict__ per_p, double per_alpha, double per_eps) {
+                            const T* __restrict__ q_sel, const float* __restrict__ per_w, float* __restrict__ per_p, double per_alpha, double per_eps,
+                            int nstep, double gamma_n) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
   T m = q_tg[(int64_t)n * A];
@@ -170,9 +171,13 @@ __global__ void head_kernel(const T* __restrict__ q_on, const T* __restrict__ q_
   } else
   for (int a = 1; a < A; ++a) { const T v = q_tg[(int64_t)n * A + a]; m = v > m ? v : m; }     // be.max(postq, axis=0) :124
   maxq[n] = m;
-  double r = (double)rew[n];
-  r = r < minr ? minr : (r > maxr ? maxr : r);                                // np.clip(rewards, min_reward, max_reward) :136
-  const double y = term[n] ? r : r + discount * (double)m;                    // :139-143, python float arithmetic
+  double r, gam = discount;
+  if (nstep > 1) { r = __builtin_bit_cast(double, rew[n]); gam = gamma_n; }   // --n_step: the return R (clipped per step), gamma^n
+  else {
+    r = (double)rew[n];
+    r = r < minr ? minr : (r > maxr ? maxr : r);                              // np.clip(rewards, min_reward, max_reward) :136
+  }
+  const double y = term[n] ? r : r + gam * (double)m;                         // :139-143, python float arithmetic
   const T target = (T)y;                                                      // stored into the backend dtype
   const int at = act[n];
   T d = (T)0;
@@ -353,7 +358,7 @@ class GenericNetT : public GenericNet {
     GCHK(forward(0, pre, B));                                                  // online net on the prestates, tensors kept :128-130
     hipLaunchKernelGGL(head_kernel<T>, dim3((B + 63) / 64), dim3(64), 0, st, (const T*)q, (const T*)(q + (int64_t)B * A), actions, rew, term,
                        dq, cost_terms, maxq, B, A, cfg.discount_rate, cfg.min_reward, cfg.max_reward, (T)cfg.clip_error, (const T*)(dd ? q_sel : nullptr),
-                       per_w, per_p, per_alpha, per_eps);
+                       per_w, per_p, per_alpha, per_eps, nstep, gamma_n);
     hipLaunchKernelGGL(cost_kernel<T>, dim3(1), dim3(64), 0, st, (const T*)cost_terms, cost, cost_sum, B);
     // ---- bprop (A8) :162
     GCHK(gemm(ga(dq, 1, A, act[3], 512, 1, g + off[4], A, 512, B)));                                   // gW5 = dq^T @ a4
@@ -441,6 +446,8 @@ class GenericNetT : public GenericNet {
   }
   void set_per(const float* w, float* newp, double alpha, double eps) override { per_w = w; per_p = newp; per_alpha = alpha; per_eps = eps; }
   const float* per_w = nullptr; float* per_p = nullptr; double per_alpha = 0.0, per_eps = 0.0;
+  void set_nstep(int n, double g) override { nstep = n; gamma_n = g; }
+  int nstep = 1; double gamma_n = 0.0;
   hipError_t set_double_dqn(bool on) override {
     if (on && !q_sel) GCHK(dalloc(&q_sel, (int64_t)B * A));
     double_dqn = on;
@@ -464,7 +471,8 @@ GenericNet* make_t(const sdqn_net_cfg& c, hipStream_t s, std::string* err) {
 __global__ void __launch_bounds__(256) gather_generic_kernel(const GatherGenericArgs g) {
   const int k = blockIdx.y, which = blockIdx.x / g.hist, j = blockIdx.x % g.hist;
   const int64_t index = g.idx[k];
-  const uint8_t* src = g.ring + (index - g.hist + j + which) * g.frame;          // pre: frames idx-hist .. idx-1, post: idx-hist+1 .. idx
+  const int po = which ? (g.ns.n > 1 ? g.ns.n : 1) : 0;                          // (problems.h soff)
+  const uint8_t* src = g.ring + (index - g.hist + j + po) * g.frame;             // pre: frames idx-hist .. idx-1, post: idx-hist+n .. idx+n-1
   uint8_t* dst = (which ? g.post : g.pre) + ((int64_t)k * g.hist + j) * g.frame;
   if ((g.frame & 3) == 0 && ((reinterpret_cast<uintptr_t>(g.ring) | reinterpret_cast<uintptr_t>(dst)) & 3) == 0) {
     const uint32_t* s4 = reinterpret_cast<const uint32_t*>(src); uint32_t* d4 = reinterpret_cast<uint32_t*>(dst);
@@ -472,10 +480,8 @@ __global__ void __launch_bounds__(256) gather_generic_kernel(const GatherGeneric
   } else {
     for (int64_t i = threadIdx.x; i < g.frame; i += 256) dst[i] = src[i];
   }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {                                     // replay_memory.py:76-78
-    const MetaRec rec = reinterpret_cast<const MetaRec*>(g.meta)[index];
-    g.actions[k] = rec.action; g.rewards[k] = rec.reward; g.terminals[k] = rec.terminal;
-  }
+  if (blockIdx.x == 0 && threadIdx.x == 0)                                       // replay_memory.py:76-78
+    stage_meta(reinterpret_cast<const MetaRec*>(g.meta), index, g.ns, g.actions, g.rewards, g.terminals, k);
 }
 
 }  // namespace

@@ -43,6 +43,9 @@ struct HeadArgs {
   // --prioritized_replay (sdqn_per.hip): per_w != nullptr selects the PER head — dq = w clip(delta), cost term 0.5 w delta^2, and
   // per_p[n] = (|delta| + per_eps)^per_alpha, the new priority the next per_step launch writes back
   const float* per_w; float* per_p; double per_alpha, per_eps;
+  // --n_step: nstep > 1 selects the n-step head — st_rewards holds the returns R as doubles, st_terminals the done flags,
+  // the target is R (done) or R + gamma_n * max Q' with gamma_n = discount^n by repeated multiplication, no reward clip
+  int nstep; double gamma_n;
 };
 
 struct PrepArgs {                // pinned index slot + ring metadata -> device-resident (idx, a, r, t) of this step
@@ -58,6 +61,7 @@ struct PrepArgs {                // pinned index slot + ring metadata -> device-
   // dependency chain of the whole update launch)
   int idx_in_valid;
   int64_t idx_in[32];
+  NStepArgs ns;                 // --n_step: rewards / terminals receive (R, done) (problems.h stage_meta)
 };
 
 struct UpdateArgs {
@@ -122,6 +126,7 @@ struct GatherArgs {
   int64_t* rewards;
   uint8_t* terminals;
   int B;
+  NStepArgs ns;                 // --n_step: the poststate starts ns.n frames after the prestate; rewards / terminals receive (R, done)
 };
 
 #if defined(__HIPCC__)

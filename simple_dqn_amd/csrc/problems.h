@@ -64,6 +64,32 @@ struct MetaRec {            // device mirror of (rewards, actions, terminals) of
   uint8_t pad[6];
 };
 
+// --n_step: what turns a sampled index i into (action, return R, done) — n MetaRecs of the ring, read in the order of
+// the numpy loop (tests/nstep_oracle.py), in double, one rounding per operation (the library is built with -ffp-contract=off).  n <= 1:
+// off, the staging keeps (action, reward, terminal) of i itself.  The return goes into the int64 reward staging as a double's bits.
+struct NStepArgs { int n, pad_; double gamma, min_reward, max_reward; };
+SDQN_HD void nstep_return(const MetaRec* meta, int64_t i, const NStepArgs& s, double& R, uint8_t& done) {
+  double r = 0.0, g = 1.0; uint8_t d = 0;
+  for (int k = 0; k < s.n; ++k) {
+    const MetaRec rec = meta[i + k];
+    double c = (double)rec.reward;
+    c = c < s.min_reward ? s.min_reward : (c > s.max_reward ? s.max_reward : c);
+    r = r + g * c;
+    if (rec.terminal) { d = 1; break; }
+    g = g * s.gamma;
+  }
+  R = r; done = d;
+}
+// one staging entry (a, r, t) of sample i, standard or n-step
+SDQN_HD void stage_meta(const MetaRec* meta, int64_t i, const NStepArgs& s, uint8_t* act, int64_t* rew, uint8_t* term, int n) {
+  const MetaRec rec = meta[i];
+  act[n] = rec.action;
+  if (s.n > 1) {
+    double R; uint8_t d; nstep_return(meta, i, s, R, d);
+    reinterpret_cast<double*>(rew)[n] = R; term[n] = d;
+  } else { rew[n] = rec.reward; term[n] = rec.terminal; }
+}
+
 struct StepArgs {
   const uint8_t* src;       // ring mirror (from_ring) or staging states [2][B][STATE]
   const int64_t* idx;       // sampled indexes [B] in DEVICE memory (copied from the pinned slot by prep_kernel)
@@ -101,7 +127,8 @@ struct StepArgs {
   float loss_scale, inv_loss_scale;
   int h16;                         // 1: fp16 mode
   int xcd_map;              // XCD-contiguous workgroup->tile map (cuts fabric traffic to ~algorithmic): bit i = problem i of the launch
-  int reserved_[12];        // (keeps the field offsets of the round-1 layout: the scalar-load schedule hipcc derives from them is part of
+  int post_off;             // ring frames from a prestate to its poststate: --n_step (1 = replay_memory.py:71-72; problems.h soff)
+  int reserved_[11];        // (keeps the field offsets of the round-1 layout: the scalar-load schedule hipcc derives from them is part of
                             //  the tuned kernels — a re-packed struct measured 1 % slower; host-only tuning lives in LaunchTune, kernels.h)
   float* __restrict__ theta_w;   // online parameters, writable alias of theta[0]
   float* __restrict__ state;     // RMSProp state
@@ -186,15 +213,17 @@ constexpr int W1P_PLANE = K1 * CRS1;      // elements per plane: [32 maps][256 k
 
 // Net slots of a forward launch (StepArgs::nz of them): 0 = online net on the prestates, 1 = target net on the poststates and, with
 // --double_dqn, 2 = ONLINE net on the POSTSTATES (the argmax of the Double DQN target).  Slot z takes its weights from theta[wslot(z)]
-// (and the matching wh / wht / w1p / wpt copies), its frames from state slot sslot(z); activations, slabs and Q are indexed by z itself.
+// (and the matching wh / wht / w1p / wpt copies), its frames from state slot sslot(z) of the [2][B][STATE] staging or, read from the ring,
+// from soff(post_off, z) frames after the prestate's first frame; activations, slabs and Q are indexed by z itself.
+// --n_step n: the poststate of sample i is state(i + n - 1), n frames after the prestate — StepArgs::post_off = n.
 SDQN_HD int wslot(int z) { return z & 1; }
 SDQN_HD int sslot(int z) { return z != 0 ? 1 : 0; }
+SDQN_HD int soff(int post_off, int z) { return z != 0 ? post_off : 0; }
 // fc4 forward split-K slab of (K-split ks, slot z): [S4][2] for slots 0 / 1 as before, slot 2's S4 slabs after them
 SDQN_HD int64_t slab4_row(const StepArgs& a, int ks, int z) { return z < 2 ? (int64_t)ks * 2 + z : (int64_t)2 * a.S4 + ks; }
 SDQN_HD int64_t sbase(const StepArgs& a, int z, int n) {
-  // replay_memory.py:71-72: prestate = screens[i-4:i], poststate = screens[i-3:i+1]
-  const int zs = sslot(z);
-  return a.from_ring ? (a.idx[n] - C0 + zs) * (int64_t)FRAME : ((int64_t)zs * a.B + n) * (int64_t)STATE;
+  // replay_memory.py:71-72: prestate = screens[i-4:i], poststate = screens[i-3:i+1] (--n_step n: screens[i-4+n:i+n])
+  return a.from_ring ? (a.idx[n] - C0 + soff(a.post_off, z)) * (int64_t)FRAME : ((int64_t)sslot(z) * a.B + n) * (int64_t)STATE;
 }
 // deepqnetwork.py:100 be.divide(input, 255): correctly-rounded x/255 without a divide — q = x*r, one fma
 // Newton correction (bit-identical to IEEE x/255.0f for all 256 byte values: tests/test_emul.py checks).
@@ -415,12 +444,12 @@ template <class P> struct TargetOnly : P {
   SDQN_HD static int nbz(const StepArgs&) { return 1; }
   SDQN_HD static void ksplit(const StepArgs& a, int, int& z, int& ks, int& kb, int& ke) { P::ksplit(a, 1, z, ks, kb, ke); }
 };
-struct Conv1FwdTarget : Conv1Fwd {       // target conv1 of the NEXT step: gathers with StepArgs::idx_t (poststates = screens[i-3 : i+1])
+struct Conv1FwdTarget : Conv1Fwd {       // target conv1 of the NEXT step: gathers with StepArgs::idx_t (poststates = screens[i-4+n : i+n])
   SDQN_HD static int nbz(const StepArgs&) { return 1; }
   SDQN_HD static void ksplit(const StepArgs& a, int, int& z, int& ks, int& kb, int& ke) { Conv1Fwd::ksplit(a, 1, z, ks, kb, ke); }
   SDQN_HD static aoff_t a_row(const StepArgs& a, int, int m) {
     int n = m / PIX1, pix = m - n * PIX1, p = pix / Q1, q = pix - p * Q1;
-    return (a.idx_t[n] - C0 + 1) * (int64_t)FRAME + (int64_t)(p * ST1) * W0 + q * ST1;
+    return (a.idx_t[n] - C0 + soff(a.post_off, 1)) * (int64_t)FRAME + (int64_t)(p * ST1) * W0 + q * ST1;
   }
 };
 struct Fc4FwdTarget : Fc4Fwd {

@@ -85,16 +85,17 @@ struct MT {
   int64_t randint(int64_t a, int64_t b) { return a + (int64_t)randbelow((uint64_t)(b - a + 1)); }
 };
 
-// replay_memory.py:54-68. Returns number of draws consumed.
+// replay_memory.py:54-68. Returns number of draws consumed.  nstep > 1 (--n_step): draws from [hist, count - nstep] and
+// rejects a window [index - hist, index + nstep - 1] that straddles the write pointer; nstep = 1 is the reference's loop, draw for draw.
 inline int64_t sample_indices(uint32_t* mt_state, const uint8_t* terminals, int64_t count, int64_t current,
-                              int hist, int batch, int64_t* out) {
+                              int hist, int batch, int64_t* out, int nstep = 1) {
   MT mt(mt_state);
   int64_t draws = 0;
   for (int n = 0; n < batch; ++n) {
     for (;;) {
-      int64_t index = mt.randint(hist, count - 1);                     // :59
+      int64_t index = mt.randint(hist, count - nstep);                 // :59
       ++draws;
-      if (index >= current && index - hist < current) continue;        // :61
+      if (index + nstep - 1 >= current && index - hist < current) continue;   // :61
       bool any = false;                                                // :65 terminals[index-hist:index].any()
       for (int64_t i = index - hist; i < index; ++i) any |= terminals[i] != 0;
       if (any) continue;

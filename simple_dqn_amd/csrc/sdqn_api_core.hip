@@ -56,25 +56,32 @@ extern "C" int sdqn_mt_randint(uint32_t* mt, int64_t a, int64_t b, int64_t* out)
   MT m(mt); *out = m.randint(a, b); return SDQN_OK;
 }
 int sample_checked(uint32_t* mt, const uint8_t* terminals, int64_t count, int64_t current, int hist,
-                          int batch, int64_t* idx_out, int64_t* draws_out) {
+                          int batch, int64_t* idx_out, int64_t* draws_out, int nstep) {
   ARGCHK(mt && terminals && idx_out, "NULL argument");
   ARGCHK(mt[624] <= 624, "corrupt MT state (position %u)", mt[624]);
-  ARGCHK(count > hist, "replay memory must hold more than history_length frames (count=%lld)", (long long)count);  // :52
+  ARGCHK(nstep >= 1 && nstep <= SDQN_MAX_N_STEP, "n_step %d out of range [1, %d]", nstep, SDQN_MAX_N_STEP);
+  if (nstep == 1) ARGCHK(count > hist, "replay memory must hold more than history_length frames (count=%lld)", (long long)count);  // :52
+  else ARGCHK(count >= hist + nstep, "replay memory holds %lld screens: n_step %d needs at least history_length + n_step = %d",
+              (long long)count, nstep, hist + nstep);
   ARGCHK(batch > 0 && hist > 0 && current >= 0, "bad sampler arguments");
   // guard against a ring with no admissible index (the reference would spin forever)
   bool any_ok = false;
-  for (int64_t i = hist; i < count && !any_ok; ++i) {
-    if (i >= current && i - hist < current) continue;
+  for (int64_t i = hist; i <= count - nstep && !any_ok; ++i) {
+    if (i + nstep - 1 >= current && i - hist < current) continue;
     bool t = false;
     for (int64_t k = i - hist; k < i; ++k) t |= terminals[k] != 0;
     any_ok = !t;
   }
   ARGCHK(any_ok, "no admissible index in the ring (every window straddles the write pointer or a terminal)");
-  int64_t d = sample_indices(mt, terminals, count, current, hist, batch, idx_out);
+  int64_t d = sample_indices(mt, terminals, count, current, hist, batch, idx_out, nstep);
   if (draws_out) *draws_out = d;
   return SDQN_OK;
 }
 extern "C" int sdqn_sample_indices(uint32_t* mt, const uint8_t* terminals, int64_t count, int64_t current,
                                    int hist, int batch, int64_t* idx_out, int64_t* draws_out) {
   return sample_checked(mt, terminals, count, current, hist, batch, idx_out, draws_out);
+}
+extern "C" int sdqn_sample_indices_n(uint32_t* mt, const uint8_t* terminals, int64_t count, int64_t current,
+                                     int hist, int n, int batch, int64_t* idx_out, int64_t* draws_out) {
+  return sample_checked(mt, terminals, count, current, hist, batch, idx_out, draws_out, n);
 }

@@ -446,6 +446,12 @@ extern "C" int sdqn_net_set_epoch(sdqn_net_t h, int epoch) { ARGCHK(h && epoch >
 
 extern "C" int sdqn_net_set_option(sdqn_net_t h, const char* name, int value) {
   ARGCHK(h && name, "NULL argument");
+  if (!strcmp(name, "n_step")) {                          // n-step returns: sdqn.h
+    ARGCHK(value >= 1 && value <= SDQN_MAX_N_STEP, "n_step %d out of range [1, %d]", value, SDQN_MAX_N_STEP);
+    h->n_step = value;
+    if (h->gen) h->gen->set_nstep(value, nstep_gamma_n(value, h->cfg.discount_rate));
+    return SDQN_OK;
+  }
   if (h->gen) {                                   // the generic path has no tuning knobs; the ones that change semantics are refused
     if (!strcmp(name, "dp_overlap") && value < 0) return SDQN_OK;      // (auto: nothing to overlap without a communicator)
     if (!strcmp(name, "double_dqn")) {

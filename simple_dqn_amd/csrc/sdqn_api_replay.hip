@@ -96,7 +96,7 @@ extern "C" int sdqn_replay_add(sdqn_replay_t r, int action, int64_t reward, cons
   }
   if (c + 1 > r->count) r->count = c + 1;                         // :33
   r->current = (c + 1) % r->size;                                 // :34
-  per_mark(r, c, 1);                                              // prioritized: p_max, validity of [c, c + 1 + hist) re-evaluated
+  per_mark(r, c, 1);                                              // prioritized: p_max, validity of [c - n + 1, c + 1 + hist) re-evaluated
   return SDQN_OK;
 }
 extern "C" int sdqn_replay_get_state(sdqn_replay_t r, int64_t* count, int64_t* current) {
@@ -137,7 +137,16 @@ extern "C" int sdqn_replay_upload_meta(sdqn_replay_t r, int64_t first, int64_t n
 extern "C" int sdqn_replay_sample(sdqn_replay_t r, uint32_t* mt, int64_t* idx_out, int64_t* draws_out) {
   ARGCHK(r, "NULL handle");
   if (r->per) return per_sample_host(r, mt, idx_out, draws_out);        // prioritized: by priority on the device (sdqn_per.hip)
-  return sample_checked(mt, r->terminals, r->count, r->current, r->hist, r->B, idx_out, draws_out);
+  return sample_checked(mt, r->terminals, r->count, r->current, r->hist, r->B, idx_out, draws_out, r->ns.n);
+}
+extern "C" int sdqn_replay_set_n_step(sdqn_replay_t r, int n, double discount, double min_reward, double max_reward) {
+  ARGCHK(r, "NULL handle");
+  ARGCHK(n >= 1 && n <= SDQN_MAX_N_STEP, "n_step %d out of range [1, %d]", n, SDQN_MAX_N_STEP);
+  ARGCHK(n < r->size - r->hist, "n_step %d needs a replay memory larger than history_length + n_step (size %lld)", n, (long long)r->size);
+  r->ns.n = n; r->ns.pad_ = 0;
+  r->ns.gamma = n > 1 ? discount : 0.0; r->ns.min_reward = n > 1 ? min_reward : 0.0; r->ns.max_reward = n > 1 ? max_reward : 0.0;
+  per_mark_all(r);                                                     // prioritized: validity follows the n-step rule from the next launch
+  return SDQN_OK;
 }
 
 // take the next pinned index slot (waiting for its previous consumer), fill it, return its device alias
@@ -156,7 +165,7 @@ int replay_push_idx(sdqn_replay_s* r, const int64_t* idx, int* slot_out, const i
   if (r->slot_busy[s]) { HIPCHK(hipEventSynchronize(r->slot_ev[r->slot_cover[s]])); r->slot_busy[s] = false; }
   int64_t* dst = r->h_idx + (size_t)s * r->B;
   for (int i = 0; i < r->B; ++i) {
-    ARGCHK(idx[i] >= r->hist && idx[i] < r->count, "index %lld out of range (count %lld)", (long long)idx[i], (long long)r->count);
+    ARGCHK(idx[i] >= r->hist && idx[i] + r->ns.n - 1 < r->count, "index %lld out of range (count %lld, n_step %d)", (long long)idx[i], (long long)r->count, r->ns.n);
     dst[i] = idx[i];
   }
   *slot_out = s; *dev = r->d_idx_view + (size_t)s * r->B;
@@ -179,12 +188,12 @@ int replay_release_idx_batched(sdqn_replay_s* r, int slot, bool flush) {
 GatherArgs gather_args(sdqn_replay_s* r, const int64_t* didx) {
   r->mb_dev_gen++;                                  // (every launch built from these arguments overwrites the device minibatch)
   GatherArgs g; g.ring = r->d_ring; g.meta = r->d_meta; g.idx = didx; g.pre = r->d_pre; g.post = r->d_post;
-  g.actions = r->d_act; g.rewards = r->d_rew; g.terminals = r->d_term; g.B = r->B; return g;
+  g.actions = r->d_act; g.rewards = r->d_rew; g.terminals = r->d_term; g.B = r->B; g.ns = r->ns; return g;
 }
 int replay_gather_generic(sdqn_replay_s* r, const int64_t* didx) {      // any geometry (generic_net.hip)
   r->mb_dev_gen++;
   GatherGenericArgs g; g.ring = r->d_ring; g.meta = r->d_meta; g.idx = didx; g.pre = r->d_pre; g.post = r->d_post;
-  g.actions = r->d_act; g.rewards = r->d_rew; g.terminals = r->d_term; g.B = r->B; g.hist = r->hist; g.frame = r->frame;
+  g.actions = r->d_act; g.rewards = r->d_rew; g.terminals = r->d_term; g.B = r->B; g.hist = r->hist; g.frame = r->frame; g.ns = r->ns;
   HIPCHK(launch_gather_generic(g, g_stream));
   return SDQN_OK;
 }
@@ -193,13 +202,14 @@ int replay_gather_generic(sdqn_replay_s* r, const int64_t* didx) {      // any g
 static void snapshot_small(sdqn_replay_s* r, const int64_t* idx) {
   const size_t B = (size_t)r->B;
   int64_t* rew = reinterpret_cast<int64_t*>(r->mb_snap); uint8_t* act = r->mb_snap + B * 8; uint8_t* term = act + B;
-  for (size_t i = 0; i < B; ++i) { const MetaRec& m = r->h_meta[idx[i]]; rew[i] = m.reward; act[i] = m.action; term[i] = m.terminal; }
+  for (size_t i = 0; i < B; ++i) stage_meta(r->h_meta, idx[i], r->ns, act, rew, term, (int)i);    // (n-step: R's bits and done, as the device)
   r->mb_snap_gen = r->mb_dev_gen;
 }
 extern "C" int sdqn_replay_gather(sdqn_replay_t r, const int64_t* idx_host) {
   ARGCHK(r && idx_host, "NULL argument");
   for (int i = 0; i < r->B; ++i)
-    ARGCHK(idx_host[i] >= r->hist && idx_host[i] < r->count, "index %lld out of range (count %lld)", (long long)idx_host[i], (long long)r->count);
+    ARGCHK(idx_host[i] >= r->hist && idx_host[i] + r->ns.n - 1 < r->count, "index %lld out of range (count %lld, n_step %d)",
+           (long long)idx_host[i], (long long)r->count, r->ns.n);
   per_note_gather(r, idx_host);
   if (!r->tuned_geom) {
     int slot; const int64_t* didx; int rc = replay_push_idx(r, idx_host, &slot, &didx); if (rc) return rc;

@@ -27,7 +27,18 @@ StepArgs step_args(sdqn_net_s* h) {
   a.theta_w = h->theta; a.state = h->state; a.bsz = (float)h->B;
   a.rho = (float)h->cfg.decay_rate; a.one_minus_rho = (float)(1.0 - h->cfg.decay_rate);
   a.lr = (float)h->cfg.learning_rate; a.eps = (float)h->cfg.epsilon;
+  a.post_off = h->n_step;                  // ring paths: poststate = state(i + n - 1) (problems.h soff)
   return a;
+}
+double nstep_gamma_n(int n, double gamma) { double g = 1.0; for (int k = 0; k < n; ++k) g = g * gamma; return g; }
+int nstep_match(const sdqn_net_s* h, const sdqn_replay_s* r) {
+  const int rn = r->ns.n > 1 ? r->ns.n : 1;
+  if (rn == 1 && h->n_step == 1) return SDQN_OK;
+  ARGCHK(rn == h->n_step, "replay memory n_step %d != network n_step %d", rn, h->n_step);
+  ARGCHK(r->ns.gamma == h->cfg.discount_rate, "replay memory n-step discount %.17g != network discount_rate %.17g", r->ns.gamma, h->cfg.discount_rate);
+  ARGCHK(r->ns.min_reward == h->cfg.min_reward && r->ns.max_reward == h->cfg.max_reward,
+         "replay memory n-step reward clip [%g, %g] != network [%g, %g]", r->ns.min_reward, r->ns.max_reward, h->cfg.min_reward, h->cfg.max_reward);
+  return SDQN_OK;
 }
 HeadArgs head_args(sdqn_net_s* h, int train) {
   HeadArgs hd; memset(&hd, 0, sizeof hd);
@@ -35,6 +46,7 @@ HeadArgs head_args(sdqn_net_s* h, int train) {
   hd.q = h->q; hd.maxq = h->maxq; hd.dq = h->dq; hd.cost_terms = h->cost_terms;
   hd.discount = h->cfg.discount_rate; hd.min_reward = h->cfg.min_reward; hd.max_reward = h->cfg.max_reward;
   hd.clip_error = (float)h->cfg.clip_error; hd.train = train;
+  if (h->n_step > 1) { hd.nstep = h->n_step; hd.gamma_n = nstep_gamma_n(h->n_step, h->cfg.discount_rate); }
   return hd;
 }
 // Overlapped data parallel: the previous step's fc4 all-reduce + update may still be running on g_comm.  Everything
@@ -157,7 +169,7 @@ extern "C" int sdqn_net_step_structure(sdqn_net_t h, int* structure, int* update
 bool ddqn_active(const sdqn_net_s* h) { return h->double_dqn && h->theta_t != h->theta; }
 int run_online_post_bn(sdqn_net_s* h, const StepArgs& a) {
   StepArgs p = a; p.nz = 1;
-  p.src = a.from_ring ? a.src + FRAME : a.src + (size_t)a.B * STATE;
+  p.src = a.from_ring ? a.src + (size_t)soff(a.post_off, 1) * FRAME : a.src + (size_t)a.B * STATE;
   HeadArgs hp = head_args(h, 0); hp.q = h->q + (size_t)2 * a.B * h->A;
   return run_forward(h, p, hp);
 }
@@ -369,8 +381,9 @@ extern "C" int sdqn_net_predict_one(sdqn_net_t h, const uint8_t* state, float* q
   return SDQN_OK;
 }
 
-extern "C" int sdqn_net_train_host(sdqn_net_t h, const uint8_t* pre, const uint8_t* actions, const int64_t* rewards,
-                                   const uint8_t* post, const uint8_t* terminals, float* cost_out) {
+// returns: rewards are the n-step returns R as float64 bits, terminals the done flags (sdqn_net_train_host_returns)
+static int train_host_tuple(sdqn_net_t h, const uint8_t* pre, const uint8_t* actions, const int64_t* rewards,
+                            const uint8_t* post, const uint8_t* terminals, float* cost_out, bool returns) {
   // the one-shot "minibatch buffers are clean" declarations are consumed FIRST: an argument error below must not leave one armed for a
   // later call whose buffers were edited in place
   sdqn_replay_s* owner = nullptr;                               // (handles are created / destroyed / used from ONE host thread: sdqn.h)
@@ -380,8 +393,11 @@ extern "C" int sdqn_net_train_host(sdqn_net_t h, const uint8_t* pre, const uint8
     r->mb_clean_declared = false; r->mb_clean_on_device = false;          // one-shot, whoever it was meant for
   }
   ARGCHK(h && pre && actions && rewards && post && terminals, "NULL argument");
+  if (returns) ARGCHK(h->n_step > 1, "sdqn_net_train_host_returns needs option n_step > 1 (network n_step %d)", h->n_step);
+  else ARGCHK(h->n_step == 1, "network n_step %d: integer rewards are refused, train with returns (sdqn_net_train_host_returns)", h->n_step);
   for (int i = 0; i < h->B; ++i) ARGCHK(actions[i] < h->A, "action %d out of range at %d", (int)actions[i], i);
   const bool ours = owner != nullptr;
+  if (ours) { int rcn = nstep_match(h, owner); if (rcn) return rcn; }
   if (h->gen) {
     ARGCHK(!ours || (size_t)owner->state == h->gen->state_bytes(), "replay geometry differs from the network's");
     const bool per = per_owns_minibatch(owner);                 // prioritized memory: weighted step + priority write-back
@@ -444,6 +460,15 @@ extern "C" int sdqn_net_train_host(sdqn_net_t h, const uint8_t* pre, const uint8
   return SDQN_OK;
 }
 
+extern "C" int sdqn_net_train_host(sdqn_net_t h, const uint8_t* pre, const uint8_t* actions, const int64_t* rewards,
+                                   const uint8_t* post, const uint8_t* terminals, float* cost_out) {
+  return train_host_tuple(h, pre, actions, rewards, post, terminals, cost_out, false);
+}
+extern "C" int sdqn_net_train_host_returns(sdqn_net_t h, const uint8_t* pre, const uint8_t* actions, const double* returns,
+                                           const uint8_t* post, const uint8_t* dones, float* cost_out) {
+  return train_host_tuple(h, pre, actions, reinterpret_cast<const int64_t*>(returns), post, dones, cost_out, true);
+}
+
 extern "C" int sdqn_net_tuple_counters(sdqn_net_t h, int64_t* calls, int64_t* states_in_place, int64_t* nothing_uploaded) {
   ARGCHK(h, "NULL handle");
   if (calls) *calls = h->tuple_calls; if (states_in_place) *states_in_place = h->tuple_states_skipped;
@@ -455,6 +480,7 @@ PrepArgs prep_args(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* pinned_idx) {
   PrepArgs p; memset(&p, 0, sizeof p);
   p.idx_pinned = pinned_idx; p.meta = r->d_meta; p.idx = h->d_idx; p.actions = h->st_act;
   p.rewards = h->st_rew; p.terminals = h->st_term; p.B = h->B;
+  p.ns = r->ns;                                  // (nstep_match: the net's n)
   if (h->B <= 32 && h->prep_inline) {            // the slot's host copy (pinned_idx is its device alias)
     memcpy(p.idx_in, r->h_idx + (pinned_idx - r->d_idx_view), (size_t)h->B * sizeof(int64_t));
     p.idx_in_valid = 1;
@@ -497,6 +523,7 @@ int gen_train_replay(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* idx_host) {
 extern "C" int sdqn_net_train_replay(sdqn_net_t h, sdqn_replay_t r, const int64_t* idx_host, float* cost_out) {
   ARGCHK(h && r && idx_host, "NULL argument");
   ARGCHK(r->B == h->B, "replay batch_size %d != network batch_size %d", r->B, h->B);
+  { int rcn = nstep_match(h, r); if (rcn) return rcn; }
   if (r->per) return per_train_replay(h, r, idx_host, cost_out);
   if (h->gen) {
     int rc = gen_train_replay(h, r, idx_host); if (rc) return rc;
@@ -514,12 +541,13 @@ extern "C" int sdqn_net_train_replay(sdqn_net_t h, sdqn_replay_t r, const int64_
 extern "C" int sdqn_net_train_many(sdqn_net_t h, sdqn_replay_t r, uint32_t* mt, int n_steps, float* mean_cost) {
   ARGCHK(h && r && mt && n_steps >= 0, "bad arguments");
   ARGCHK(r->B == h->B, "replay batch_size %d != network batch_size %d", r->B, h->B);
+  { int rcn = nstep_match(h, r); if (rcn) return rcn; }
   if (r->per) return per_train_many(h, r, mt, n_steps, mean_cost);
   if (h->gen) {
     std::vector<int64_t> gi((size_t)r->B);
     GENCHK(h->gen->reset_cost_sum());
     for (int i = 0; i < n_steps; ++i) {
-      int rc = sample_checked(mt, r->terminals, r->count, r->current, r->hist, r->B, gi.data(), nullptr); if (rc) return rc;
+      int rc = sample_checked(mt, r->terminals, r->count, r->current, r->hist, r->B, gi.data(), nullptr, r->ns.n); if (rc) return rc;
       rc = gen_train_replay(h, r, gi.data()); if (rc) return rc;
     }
     int rc = replay_flush_pending(r); if (rc) return rc;
@@ -532,14 +560,14 @@ extern "C" int sdqn_net_train_many(sdqn_net_t h, sdqn_replay_t r, uint32_t* mt, 
   // sample one step ahead: step i's update launch also performs step i+1's prep (index copy + metadata gather)
   int slot = -1, next_slot = -1; const int64_t *pinned = nullptr, *next_pinned = nullptr;
   if (n_steps > 0) {
-    int rc = sample_checked(mt, r->terminals, r->count, r->current, r->hist, r->B, idx.data(), nullptr); if (rc) return rc;
+    int rc = sample_checked(mt, r->terminals, r->count, r->current, r->hist, r->B, idx.data(), nullptr, r->ns.n); if (rc) return rc;
     rc = check_ring_actions(h, r, idx.data()); if (rc) return rc;
     rc = replay_push_idx(r, idx.data(), &slot, &pinned); if (rc) return rc;
   }
   for (int i = 0; i < n_steps; ++i) {
     next_pinned = nullptr;
     if (i + 1 < n_steps) {
-      int rc = sample_checked(mt, r->terminals, r->count, r->current, r->hist, r->B, idx.data(), nullptr); if (rc) return rc;
+      int rc = sample_checked(mt, r->terminals, r->count, r->current, r->hist, r->B, idx.data(), nullptr, r->ns.n); if (rc) return rc;
       rc = check_ring_actions(h, r, idx.data()); if (rc) return rc;
       rc = replay_push_idx(r, idx.data(), &next_slot, &next_pinned); if (rc) return rc;
     }

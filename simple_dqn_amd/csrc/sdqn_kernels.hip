@@ -144,7 +144,8 @@ hipError_t launch_kernel(int id, const StepArgs& a, const LaunchTune& t, hipStre
 // QSYS (acting path, round 4): h.q is HOST memory (mapped, pinned) and every Q-value leaves with a system-scope store the moment it is
 // summed, so the host can poll for it instead of paying a D2H copy packet + a stream synchronisation (sdqn_api_act.hip: predict_state).
 // PER (--prioritized_replay): the taken action's row is weighted by h.per_w[n] and the new priority goes to h.per_p[n]
-template <int AMAX, bool BN, bool HOIST = false, bool QSYS = false, bool DDQN = false, bool PER = false>
+// NSTEP (--n_step): the staged reward is the n-step return R (a double's bits), the terminal the done flag, the bootstrap factor gamma^n
+template <int AMAX, bool BN, bool HOIST = false, bool QSYS = false, bool DDQN = false, bool PER = false, bool NSTEP = false>
 __global__ void __launch_bounds__(512) head_kernel(const StepArgs a, const HeadArgs h) {
   SDQN_STAMP(0);
   if constexpr (HOIST) {
@@ -265,9 +266,14 @@ __global__ void __launch_bounds__(512) head_kernel(const StepArgs a, const HeadA
       m = sh_q[1][0];
       for (int k = 1; k < A; ++k) m = fmaxf(m, sh_q[1][k]);                                     // be.max(postq, axis=0), :124
     }
-    double rr = (double)rew;                                                                     // np.clip(rewards, ..), :136
-    rr = rr < h.min_reward ? h.min_reward : (rr > h.max_reward ? h.max_reward : rr);
-    const double y = term ? rr : rr + h.discount * (double)m;                                    // :139-143 (host float math)
+    double rr, gam;
+    if constexpr (NSTEP) { rr = __builtin_bit_cast(double, rew); gam = h.gamma_n; }              // R of the n-step loop, clipped per step
+    else {
+      rr = (double)rew;                                                                          // np.clip(rewards, ..), :136
+      rr = rr < h.min_reward ? h.min_reward : (rr > h.max_reward ? h.max_reward : rr);
+      gam = h.discount;
+    }
+    const double y = term ? rr : rr + gam * (double)m;                                           // :139-143 (host float math)
     const float d = sh_q[0][act] - (float)y;                                                     // get_errors, :149
     float dc = d;
     if (h.clip_error != 0.0f) dc = fminf(fmaxf(d, -h.clip_error), h.clip_error);                 // :158-159
@@ -329,6 +335,17 @@ hipError_t launch_head(const StepArgs& a, const HeadArgs& h, hipStream_t s, bool
     else SDQN_LAUNCH((head_kernel<MAX_ACTIONS, false, false, true>), dim3(a.B), dim3(512), 0, s, a, h);
     return hipGetLastError();
   }
+#define SDQN_HEAD_SET(DD, PP, NS) do { \
+    if (a.bn) SDQN_LAUNCH((head_kernel<MAX_ACTIONS, true, false, false, DD, PP, NS>), dim3(a.B), dim3(512), 0, s, a, h); \
+    else if (a.A <= 4) SDQN_LAUNCH((head_kernel<4, false, false, false, DD, PP, NS>), dim3(a.B), dim3(512), 0, s, a, h); \
+    else if (a.A <= 8) SDQN_LAUNCH((head_kernel<8, false, false, false, DD, PP, NS>), dim3(a.B), dim3(512), 0, s, a, h); \
+    else SDQN_LAUNCH((head_kernel<MAX_ACTIONS, false, false, false, DD, PP, NS>), dim3(a.B), dim3(512), 0, s, a, h); } while (0)
+  if (h.nstep > 1 && h.train) {                       // --n_step train step (its own instantiations, composed with Double DQN and PER)
+    if (h.per_w) { if (h.train == 2) SDQN_HEAD_SET(true, true, true); else SDQN_HEAD_SET(false, true, true); }
+    else { if (h.train == 2) SDQN_HEAD_SET(true, false, true); else SDQN_HEAD_SET(false, false, true); }
+    return hipGetLastError();
+  }
+#undef SDQN_HEAD_SET
   if (h.per_w && h.train) {                           // --prioritized_replay train step (its own instantiations, with or without Double DQN)
     if (h.train == 2) {
       if (a.bn) SDQN_LAUNCH((head_kernel<MAX_ACTIONS, true, false, false, true, true>), dim3(a.B), dim3(512), 0, s, a, h);
@@ -451,8 +468,7 @@ __global__ void __launch_bounds__(256) prep_kernel(const PrepArgs p, double* zer
   for (int n = threadIdx.x; n < p.B; n += 256) {
     const int64_t i = p.idx_in_valid ? *reinterpret_cast<const int64_t*>(ka + 8 * (n & 31)) : p.idx_pinned[n];
     p.idx[n] = i;
-    const MetaRec rec = p.meta[i];
-    p.actions[n] = rec.action; p.rewards[n] = rec.reward; p.terminals[n] = rec.terminal;
+    stage_meta(p.meta, i, p.ns, p.actions, p.rewards, p.terminals, n);
   }
 }
 hipError_t launch_prep(const PrepArgs& p, hipStream_t s, double* zero8) {
@@ -476,15 +492,18 @@ __global__ void __launch_bounds__(256) gather_kernel(const GatherArgs g, const I
   const uint4* src = reinterpret_cast<const uint4*>(g.ring + (index - C0) * (int64_t)FRAME);
   uint4* pre = reinterpret_cast<uint4*>(g.pre + (int64_t)n * STATE);
   uint4* post = reinterpret_cast<uint4*>(g.post + (int64_t)n * STATE);
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < (C0 + 1) * V; i += gridDim.x * 256) {
-    const uint4 v = src[i];
-    if (i < C0 * V) pre[i] = v;
-    if (i >= V) post[i - V] = v;
+  if (g.ns.n <= 1) {
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < (C0 + 1) * V; i += gridDim.x * 256) {
+      const uint4 v = src[i];
+      if (i < C0 * V) pre[i] = v;
+      if (i >= V) post[i - V] = v;
+    }
+  } else {                                                         // --n_step n: frames i-4 .. i-1 and i-4+n .. i-1+n (i + n <= count)
+    const int64_t po = (int64_t)g.ns.n * V;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < C0 * V; i += gridDim.x * 256) { pre[i] = src[i]; post[i] = src[po + i]; }
   }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {                       // replay_memory.py:76-78
-    const MetaRec rec = g.meta[index];
-    g.actions[n] = rec.action; g.rewards[n] = rec.reward; g.terminals[n] = rec.terminal;
-  }
+  if (blockIdx.x == 0 && threadIdx.x == 0)                         // replay_memory.py:76-78
+    stage_meta(g.meta, index, g.ns, g.actions, g.rewards, g.terminals, n);
 }
 
 hipError_t launch_gather(const GatherArgs& g, hipStream_t s, const int64_t* host_idx) {

@@ -430,7 +430,7 @@ static hipError_t launch_c1w_h(const StepArgs& a, const LaunchTune& t, hipStream
 // transposed half copy ([32 maps][256 k]) beside it, and all 400 x 32 outputs come from v_mfma_f32_16x16x32_f16 steps whose A fragment
 // is two 8-byte LDS reads (the 8 consecutive kernel columns of a patch row are contiguous in the image) and whose B fragment is one
 // 16-byte read.  25 row tiles of 16 positions over the 4 waves, both 16-map column tiles per A fragment.
-struct Conv1HArgs { const uint8_t* src; const int64_t* idx; const half_t* wht[2]; half_t* h_a1; int B, from_ring; };
+struct Conv1HArgs { const uint8_t* src; const int64_t* idx; const half_t* wht[2]; half_t* h_a1; int B, from_ring, post_off; };
 constexpr int C1F_PITCH = W0 + 4;                    // halves per image row (176 bytes)
 constexpr int C1F_FR = H0 * C1F_PITCH;               // halves per frame
 constexpr int C1F_WPITCH = CRS1 + 8;                 // halves per map row of W1 (528 bytes)
@@ -443,7 +443,7 @@ __global__ void __launch_bounds__(256) conv1_h_kernel(const Conv1HArgs c) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int z = blockIdx.x / c.B, n = blockIdx.x - z * c.B;
-  const int64_t fb = c.from_ring ? (c.idx[n] - C0 + sslot(z)) * (int64_t)FRAME : ((int64_t)sslot(z) * c.B + n) * (int64_t)STATE;      // problems.h: sbase
+  const int64_t fb = c.from_ring ? (c.idx[n] - C0 + soff(c.post_off, z)) * (int64_t)FRAME : ((int64_t)sslot(z) * c.B + n) * (int64_t)STATE;      // problems.h: sbase
   // ---- stage: 1764 x 16 bytes of frames (7 per thread, the last partly), 1024 x 16 bytes of weights (4 per thread) -------------------------
   const c1h_u32x4* fp = reinterpret_cast<const c1h_u32x4*>(c.src + fb);
   const c1h_u32x4* wp = reinterpret_cast<const c1h_u32x4*>(c.wht[wslot(z)] + OFF1);
@@ -514,7 +514,7 @@ __global__ void __launch_bounds__(256) conv1_hb_kernel(const Conv1HArgs c) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int z = blockIdx.x / c.B, n = blockIdx.x - z * c.B;
-  const int64_t fb = c.from_ring ? (c.idx[n] - C0 + sslot(z)) * (int64_t)FRAME : ((int64_t)sslot(z) * c.B + n) * (int64_t)STATE;      // problems.h: sbase
+  const int64_t fb = c.from_ring ? (c.idx[n] - C0 + soff(c.post_off, z)) * (int64_t)FRAME : ((int64_t)sslot(z) * c.B + n) * (int64_t)STATE;      // problems.h: sbase
   const c1h_u32x4* fp = reinterpret_cast<const c1h_u32x4*>(c.src + fb);
   const c1h_u32x4* wp = reinterpret_cast<const c1h_u32x4*>(c.wht[wslot(z)] + OFF1);
   c1h_u32x4 fv[7], wv[4];
@@ -580,7 +580,7 @@ __global__ void __launch_bounds__(256) conv1_hb_kernel(const Conv1HArgs c) {
 }
 
 static hipError_t launch_conv1_h(const StepArgs& a, const LaunchTune& t, hipStream_t s) {
-  Conv1HArgs c; c.src = a.src; c.idx = a.idx; c.wht[0] = a.wht[0]; c.wht[1] = a.wht[1]; c.h_a1 = a.h_a1; c.B = a.B; c.from_ring = a.from_ring;
+  Conv1HArgs c; c.src = a.src; c.idx = a.idx; c.wht[0] = a.wht[0]; c.wht[1] = a.wht[1]; c.h_a1 = a.h_a1; c.B = a.B; c.from_ring = a.from_ring; c.post_off = a.post_off;
   if (t.bt[K_CONV1_FWD] == 1) SDQN_LAUNCH(conv1_h_kernel, dim3(a.nz * a.B), dim3(256), 0, s, c);           // first form (half(b / 255) operands)
   else if (t.bt[K_CONV1_FWD] == 2) SDQN_LAUNCH(conv1_hb_kernel<false>, dim3(a.nz * a.B), dim3(256), 0, s, c);
   else SDQN_LAUNCH(conv1_hb_kernel<true>, dim3(a.nz * a.B), dim3(256), 0, s, c);

@@ -108,6 +108,7 @@ constexpr int W1P_PITCH = CRS1 + 8;
 struct Conv1Args {
   const uint8_t* src; float* a1; const unsigned short* w1p[2]; const int64_t* idx;
   int B, nz, from_ring, tiles_per_net, wgs_per_net, tpw, xcd, pad_;
+  int post_off, pad2_;      // StepArgs::post_off (problems.h soff)
 };
 struct IdxIn { int64_t v[32]; };
 
@@ -149,8 +150,8 @@ __device__ __forceinline__ void conv1_bf16_body(const Conv1Args& c, const int64_
       const uint32_t lo0 = __builtin_amdgcn_readlane((int)(my_idx & 0xFFFFFFFF), n_lo), lo1 = __builtin_amdgcn_readlane((int)(my_idx >> 32), n_lo);
       const uint32_t hi0 = __builtin_amdgcn_readlane((int)(my_idx & 0xFFFFFFFF), n_hi), hi1 = __builtin_amdgcn_readlane((int)(my_idx >> 32), n_hi);
       const int64_t i_lo = (int64_t)(((uint64_t)lo1 << 32) | lo0), i_hi = (int64_t)(((uint64_t)hi1 << 32) | hi0);
-      org = ((n == n_lo ? i_lo : i_hi) - C0 + sslot(z)) * (int64_t)FRAME;
-    } else org = c.from_ring ? (c.idx[n] - C0 + sslot(z)) * (int64_t)FRAME : ((int64_t)sslot(z) * c.B + n) * (int64_t)STATE;       // problems.h: sbase
+      org = ((n == n_lo ? i_lo : i_hi) - C0 + soff(c.post_off, z)) * (int64_t)FRAME;
+    } else org = c.from_ring ? (c.idx[n] - C0 + soff(c.post_off, z)) * (int64_t)FRAME : ((int64_t)sslot(z) * c.B + n) * (int64_t)STATE;       // problems.h: sbase
     const uint8_t* src = c.src + org + (int64_t)(p * ST1 + h) * W0 + q * ST1;
 #pragma unroll
     for (int t = 0; t < 16; ++t) raw[t] = *reinterpret_cast<const u32x2*>(src + (t >> 2) * FRAME + 2 * (t & 3) * W0);
@@ -569,7 +570,7 @@ __global__ void __launch_bounds__(640 + 64 * NLW) conv1_bf16_rows2_kernel(const 
     auto org_of = [&](int si) -> int64_t {
       if (!c.from_ring) return ((int64_t)sslot(z) * c.B + g + (int64_t)si * Gz) * (int64_t)STATE;
       const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)my_idx, si), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(my_idx >> 32), si);
-      return ((int64_t)(((uint64_t)hi << 32) | lo) - C0 + sslot(z)) * (int64_t)FRAME;
+      return ((int64_t)(((uint64_t)hi << 32) | lo) - C0 + soff(c.post_off, z)) * (int64_t)FRAME;
     };
     int poff[C1S_LPT], pdst[C1S_LPT];                         // piece j of this thread: byte offset inside a sample's item window / LDS element
 #pragma unroll
@@ -680,7 +681,8 @@ hipError_t launch_kernel_r3(int id, const StepArgs& a, const LaunchTune& t, hipS
     const int tiles = (a.B * PIX1 + 31) / 32, tpw = a.B >= 128 ? 4 : 1, wgs = (tiles + 4 * tpw - 1) / (4 * tpw);
     Conv1Args c; c.src = a.src; c.a1 = a.a1; c.w1p[0] = a.w1p[0]; c.w1p[1] = a.w1p[1]; c.idx = a.idx;
     c.B = a.B; c.nz = a.nz; c.from_ring = a.from_ring; c.tiles_per_net = tiles; c.wgs_per_net = wgs; c.tpw = tpw; c.xcd = t.r3_xcd & 1; c.pad_ = (t.wt >> 7) & 1;
-    static_assert(sizeof(Conv1Args) == 72, "the index block follows 8-byte aligned at byte 72");
+    c.post_off = a.post_off; c.pad2_ = 0;
+    static_assert(sizeof(Conv1Args) == 80, "the index block follows 8-byte aligned at byte 80");
     if (a.B >= 128 && t.bt[K_CONV1_FWD] >= 0) {           // throughput regime  (option bt:0 = -1: the per-tile kernel, the test reference)
       // round 5: persistent workgroups (one per CU), planes in registers, frames streamed in 4-row items; every workgroup of a net the same
       // number of samples where that is possible: Gz = ceil(B / ceil(B / (256 / nz)))

@@ -87,7 +87,7 @@ hipError_t launch_kernel_ss(int id, const StepArgs& a, const LaunchTune& t, hipS
     ssh::Args c; c.a1 = a.h_a1; c.a2 = a.h_a2; c.a3 = a.h_a3; c.B = a.B; c.G = (a.B + ns - 1) / ns;
     c.w2[0] = a.wht[0] + OFF2; c.w2[1] = a.wht[z1] + OFF2; c.w3[0] = a.wht[0] + OFF3; c.w3[1] = a.wht[z1] + OFF3;
     const bool wt = t.bt[K_CONV2_FWD] != 8, c1 = ssh_c1(a, t);
-    c.src = a.src; c.idx = a.idx; c.from_ring = a.from_ring; c.a1w = a.h_a1; c.w1[0] = a.wht[0] + OFF1; c.w1[1] = a.wht[z1] + OFF1;
+    c.src = a.src; c.idx = a.idx; c.from_ring = a.from_ring; c.post_off = a.post_off; c.a1w = a.h_a1; c.w1[0] = a.wht[0] + OFF1; c.w1[1] = a.wht[z1] + OFF1;
     if (c1) {
       if (ns == 2) return wt ? ssh::launch_chain<2, true, true>(c, a.nz, s) : ssh::launch_chain<2, false, true>(c, a.nz, s);
       return wt ? ssh::launch_chain<1, true, true>(c, a.nz, s) : ssh::launch_chain<1, false, true>(c, a.nz, s);

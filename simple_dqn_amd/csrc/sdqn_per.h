@@ -33,9 +33,10 @@ struct PerRing {               // what the validity rule reads
   const MetaRec* meta;
   int64_t count, current;
   int hist;
+  NStepArgs ns;                // --n_step: ns.n > 1 widens the rule to the window [i - hist, i + n - 1]; the gather's returns
 };
 
-struct PerSeg { int64_t first, end; };       // slots [first, end) were (re)written: raw = p_max, validity of [first, end + hist) re-evaluated
+struct PerSeg { int64_t first, end; };       // slots [first, end) were (re)written: raw = p_max, validity of [first - n + 1, end + hist) re-evaluated
 
 struct PerStepArgs {
   PerTree t; PerRing ring;

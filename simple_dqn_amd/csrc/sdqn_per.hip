@@ -15,8 +15,9 @@
 namespace sdqn {
 
 __device__ inline bool per_valid(const PerRing& r, int64_t i) {
-  if (i < r.hist || i >= r.count) return false;                           // randint(hist, count - 1), :59
-  if (i >= r.current && i - r.hist < r.current) return false;             // :61
+  const int n = r.ns.n > 1 ? r.ns.n : 1;                                  // --n_step: window [i - hist, i + n - 1] (sampler.h)
+  if (i < r.hist || i > r.count - n) return false;                        // randint(hist, count - n), :59
+  if (i + n - 1 >= r.current && i - r.hist < r.current) return false;     // :61
   for (int64_t k = i - r.hist; k < i; ++k) if (r.meta[k].terminal) return false;   // :65
   return true;
 }
@@ -81,16 +82,18 @@ __global__ void __launch_bounds__(256) per_step_kernel(const PerStepArgsU<CAP> a
   __shared__ float sh_red[4];
   __shared__ double sh_S;
   if (p.zero8 && tid == 0) *p.zero8 = 0.0;                    // the cost accumulator of a train_many call (prep_kernel's job)
-  // ---- 1. slots (re)written since the last sampling launch: raw = p_max, then validity of [first, end + hist) re-evaluated
+  // ---- 1. slots (re)written since the last sampling launch: raw = p_max, then validity of [first - back, end + hist) re-evaluated, where
+  // back = n - 1 (--n_step: a write moves `current`, which decides the validity of indexes whose window ends up to n - 1 slots later)
   if (p.nseg > 0) {
+    const int back = p.ring.ns.n > 1 ? p.ring.ns.n - 1 : 0;
     const float pm = *t.pmax;
     for (int s = 0; s < p.nseg; ++s)
       for (int64_t i = p.seg[s].first + tid; i < p.seg[s].end; i += 256) t.raw[i] = pm;
     __syncthreads();
     for (int s = 0; s < p.nseg; ++s) {
-      const int64_t span = p.seg[s].end - p.seg[s].first + p.ring.hist;
+      const int64_t span = p.seg[s].end - p.seg[s].first + p.ring.hist + back;
       for (int64_t k = tid; k < span; k += 256) {
-        int64_t i = p.seg[s].first + k; if (i >= t.size) i -= t.size;
+        int64_t i = p.seg[s].first - back + k; if (i < 0) i += t.size; if (i >= t.size) i -= t.size;
         t.leaf[i] = per_valid(p.ring, i) ? t.raw[i] : 0.0f;
       }
     }
@@ -98,11 +101,13 @@ __global__ void __launch_bounds__(256) per_step_kernel(const PerStepArgsU<CAP> a
     for (int L = 1; L < t.nlev; ++L) {
       const int sh = 6 * L;
       for (int s = 0; s < p.nseg; ++s) {
-        const int64_t f = p.seg[s].first, last = p.seg[s].end + p.ring.hist - 1;
-        const int64_t lo0 = f, hi0 = last < t.size ? last : t.size - 1;
+        const int64_t f = p.seg[s].first - back, last = p.seg[s].end + p.ring.hist - 1;
+        const int64_t lo0 = f < 0 ? 0 : f, hi0 = last < t.size ? last : t.size - 1;
         for (int64_t j = (lo0 >> sh) + wave; j <= (hi0 >> sh); j += 4) per_recompute(t, L, j, lane);
         if (last >= t.size)
           for (int64_t j = wave; j <= ((last - t.size) >> sh); j += 4) per_recompute(t, L, j, lane);
+        if (f < 0)                                                 // (the widened window wrapped below slot 0: its tail at the ring's end)
+          for (int64_t j = ((f + t.size) >> sh) + wave; j <= ((t.size - 1) >> sh); j += 4) per_recompute(t, L, j, lane);
       }
       __syncthreads();
     }
@@ -173,9 +178,8 @@ __global__ void __launch_bounds__(256) per_step_kernel(const PerStepArgsU<CAP> a
     p.sidx[n] = i; p.w[n] = w;
     if (p.idx_out) p.idx_out[n] = i;
     if (p.actions) {
-      const MetaRec rec = p.ring.meta[i];
-      p.actions[n] = rec.action; p.rewards[n] = rec.reward; p.terminals[n] = rec.terminal;
-      if (rec.action >= p.A) per_flag(t, 1);                 // check_ring_actions, on the device
+      stage_meta(p.ring.meta, i, p.ring.ns, p.actions, p.rewards, p.terminals, n);
+      if (p.ring.meta[i].action >= p.A) per_flag(t, 1);       // check_ring_actions, on the device
     }
   }
 }
@@ -227,7 +231,7 @@ hipError_t per_launch_levels(const PerTree& t, hipStream_t s) {
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
 
-static PerRing per_ring(sdqn_replay_s* r) { PerRing g; g.meta = r->d_meta; g.count = r->count; g.current = r->current; g.hist = r->hist; return g; }
+static PerRing per_ring(sdqn_replay_s* r) { PerRing g; g.meta = r->d_meta; g.count = r->count; g.current = r->current; g.hist = r->hist; g.ns = r->ns; return g; }
 
 int per_free(PerState* p) {
   if (!p) return SDQN_OK;
@@ -266,7 +270,7 @@ static int per_begin(sdqn_replay_s* r, PerStepArgs& a, sdqn_net_s* h = nullptr) 
   PerState* p = r->per;
   per_base(r, a);
   int64_t span = 0;
-  for (const PerSeg& s : p->rw) span += s.end - s.first + r->hist;
+  for (const PerSeg& s : p->rw) span += s.end - s.first + r->hist + (r->ns.n > 1 ? r->ns.n - 1 : 0);
   const bool big = p->full || (int)p->rw.size() > PER_SEGS || span > PER_SEG_SPAN || span > r->size;
   if (big) {
     for (const PerSeg& s : p->rw) PER_LAUNCH(per_launch_leaves(p->t, a.ring, s.first, s.end, s.end, g_stream));
@@ -403,7 +407,7 @@ extern "C" int sdqn_replay_last_sample(sdqn_replay_t r, int64_t* idx_out, float*
 // sdqn_replay_sample on a prioritized handle: refresh, sample, weights; indexes to the host
 int per_sample_host(sdqn_replay_s* r, uint32_t* mt, int64_t* idx_out, int64_t* draws_out) {
   ARGCHK(mt && idx_out, "NULL argument");
-  ARGCHK(r->count > r->hist, "replay memory holds %lld screens: at least history_length + 1 = %d needed", (long long)r->count, r->hist + 1);
+  ARGCHK(r->count >= r->hist + r->ns.n, "replay memory holds %lld screens: at least history_length + n_step = %d needed", (long long)r->count, r->hist + r->ns.n);
   PerStepArgs a; int rc = per_begin(r, a); if (rc) return rc;
   std::vector<double> u((size_t)r->B); per_draw(mt, r->B, u.data());
   a.mode = 1;
@@ -458,7 +462,7 @@ int per_train_many(sdqn_net_s* h, sdqn_replay_s* r, uint32_t* mt, int n_steps, f
   if (h->gen) GENCHK(h->gen->reset_cost_sum());
   else if (n_steps == 0) HIPCHK(hipMemsetAsync(h->cost_accum, 0, 8, g_stream));
   if (n_steps > 0) {
-    ARGCHK(r->count > r->hist, "replay memory holds %lld screens: at least history_length + 1 = %d needed", (long long)r->count, r->hist + 1);
+    ARGCHK(r->count >= r->hist + r->ns.n, "replay memory holds %lld screens: at least history_length + n_step = %d needed", (long long)r->count, r->hist + r->ns.n);
     std::vector<double> u((size_t)r->B);
     PerStepArgs a; rc = per_begin(r, a, h); if (rc) return rc;
     per_targets(h, r, a);
@@ -496,7 +500,7 @@ int per_train_replay(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* idx_host, f
   int rc = per_check_geometry(h, r); if (rc) return rc;
   rc = check_ring_actions(h, r, idx_host); if (rc) return rc;
   for (int i = 0; i < r->B; ++i)
-    ARGCHK(idx_host[i] >= r->hist && idx_host[i] < r->count, "index %lld out of range (count %lld)", (long long)idx_host[i], (long long)r->count);
+    ARGCHK(idx_host[i] >= r->hist && idx_host[i] + r->ns.n - 1 < r->count, "index %lld out of range (count %lld, n_step %d)", (long long)idx_host[i], (long long)r->count, r->ns.n);
   PerState* p = r->per;
   PerStepArgs a; rc = per_begin(r, a, h); if (rc) return rc;
   per_targets(h, r, a);

@@ -191,8 +191,7 @@ __device__ __forceinline__ void update_body(const UpdateArgs& u, const int bid, 
     for (int n = t; n < u.next.B; n += 256) {
       const int64_t i = u.next.idx_in_valid ? *reinterpret_cast<const int64_t*>(ka + 8 * (n & 31)) : u.next.idx_pinned[n];
       u.next.idx[n] = i;
-      const MetaRec rec = u.next.meta[i];
-      u.next.actions[n] = rec.action; u.next.rewards[n] = rec.reward; u.next.terminals[n] = rec.terminal;
+      stage_meta(u.next.meta, i, u.next.ns, u.next.actions, u.next.rewards, u.next.terminals, n);
     }
   }
   if (u.mode != 2 && bid == first_dense + (nb > 1 ? 1 : 0)) {             // get_cost: mean over the batch, :154

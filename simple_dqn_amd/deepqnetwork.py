@@ -93,6 +93,10 @@ class DeepQNetwork:
         self.double_dqn = bool(getattr(args, "double_dqn", False))
         if self.double_dqn:
             _lib.check(self._lib.sdqn_net_set_option(h, b"double_dqn", 1))
+        # n-step returns: train() takes (prestates, actions, returns, poststates, dones) and bootstraps with discount^n
+        self.n_step = int(getattr(args, "n_step", 1))
+        if self.n_step != 1:
+            _lib.check(self._lib.sdqn_net_set_option(h, b"n_step", self.n_step))
         self._mt_buf = (C.c_uint32 * _lib.MT_WORDS)()
         self._act_out = C.c_int(); self._act_greedy = self._lib.sdqn_net_act_greedy
         self.train_iterations = 0
@@ -167,7 +171,12 @@ class DeepQNetwork:
         assert ps[0] == as_[0] == rs[0] == qs[0] == ts[0]
         assert ps == self._state_shape
         act = np.ascontiguousarray(actions, dtype=np.uint8)
-        rew = np.ascontiguousarray(rewards, dtype=np.int64)
+        if self.n_step > 1:                                        # --n_step: float64 returns R (already clipped per step), bool dones
+            if np.asarray(rewards).dtype.kind in "iub":
+                raise ValueError("n_step %d: train() takes float64 returns (ReplayMemory.getMinibatch), not integer rewards" % self.n_step)
+            rew = np.ascontiguousarray(rewards, dtype=np.float64)
+        else:
+            rew = np.ascontiguousarray(rewards, dtype=np.int64)
         term = np.ascontiguousarray(terminals).astype(np.uint8)
         cost = C.c_float()
         want = self.callback is not None
@@ -200,8 +209,12 @@ class DeepQNetwork:
             if (m2 is not None and prestates is getattr(m2, "_prestates", None) and poststates is getattr(m2, "_poststates", None)
                     and not getattr(m2, "_mb_pending", True) and not getattr(m2, "_mb_dirty", True)):
                 _lib.check(self._lib.sdqn_replay_declare_minibatch_clean(m2._h))
-        _lib.check(self._lib.sdqn_net_train_host(self._h, pre_p, _lib.ptr(act, C.c_uint8), _lib.ptr(rew, C.c_int64), post_p,
-                                                 _lib.ptr(term, C.c_uint8), C.byref(cost) if want else None))
+        if self.n_step > 1:
+            _lib.check(self._lib.sdqn_net_train_host_returns(self._h, pre_p, _lib.ptr(act, C.c_uint8), _lib.ptr(rew, C.c_double), post_p,
+                                                             _lib.ptr(term, C.c_uint8), C.byref(cost) if want else None))
+        else:
+            _lib.check(self._lib.sdqn_net_train_host(self._h, pre_p, _lib.ptr(act, C.c_uint8), _lib.ptr(rew, C.c_int64), post_p,
+                                                     _lib.ptr(term, C.c_uint8), C.byref(cost) if want else None))
         self.train_iterations += 1                                 # :168
         if self.callback:
             self.callback.on_train(cost.value)                     # :171-172
@@ -429,12 +442,15 @@ class DeepQNetwork:
     def set_option(self, name, value):
         """Tuning / test hooks of the library (sdqn_net_set_option), e.g. 'keep_gradients' (materialise the fc4 gradient; disables the
         fused fc4 RMSProp), 'fused_launches', 'bt:<kernel id>' (throughput-regime menu), 'nw:<id>', 'tps:<layer>', 's4'.  Retired
-        experiments ('two_streams', ...) are refused by name.  'double_dqn' (0 / 1) switches Double DQN targets between steps."""
+        experiments ('two_streams', ...) are refused by name.  'double_dqn' (0 / 1) switches Double DQN targets between steps, 'n_step'
+        (1..16) n-step returns."""
         _lib.check(self._lib.sdqn_net_set_option(self._h, name.encode(), int(value)))
         if name == "dp_overlap":
             self._dp_overlap_opt = int(value)
         elif name == "double_dqn":
             self.double_dqn = bool(value)
+        elif name == "n_step":
+            self.n_step = int(value)
 
     def sync(self):
         _lib.check(self._lib.sdqn_net_sync(self._h))

@@ -26,6 +26,7 @@ _OPTIONS = {
         ("--priority_alpha", float, 0.6), ("--priority_beta", float, 0.4),
         ("--priority_beta_steps", int, 1000000, dict(help="Training steps over which the importance-sampling exponent anneals from --priority_beta to 1.")),
         ("--priority_epsilon", float, 1e-6),
+        ("--n_step", int, 1, dict(help="n-step returns (1..16): bootstrap from the state n steps later, rewards summed with the discount (1: one-step targets).")),
     ],
     "Deep Q-learning network": [
         ("--learning_rate", float, 0.00025), ("--discount_rate", float, 0.99), ("--batch_size", int, 32),

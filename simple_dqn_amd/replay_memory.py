@@ -20,6 +20,23 @@ logger = logging.getLogger(__name__)
 HBM_MIRROR, ZERO_COPY = 1, 2
 
 
+def nstep_returns(rewards, terminals, indexes, n, discount, min_reward, max_reward):
+    """--n_step: R = sum_k discount^k clip(rewards[i + k]) over k < n, stopping after the first terminal, and done = a
+    terminal was met — for every index i, in float64, in the library's operation order (its device gathers produce the same bits)"""
+    idx = np.asarray(indexes, dtype=np.int64)
+    R = np.zeros(idx.shape, dtype=np.float64)
+    g = np.ones(idx.shape, dtype=np.float64)
+    done = np.zeros(idx.shape, dtype=np.bool_)
+    for k in range(n):
+        live = ~done
+        c = np.minimum(np.maximum(np.asarray(rewards[idx + k], dtype=np.float64), min_reward), max_reward)
+        R = np.where(live, R + g * c, R)
+        t = live & np.asarray(terminals[idx + k], dtype=np.bool_)
+        done = done | t
+        g = np.where(live & ~t, g * discount, g)
+    return R, done
+
+
 class ReplayMemory:
     def __init__(self, size, args, flags=HBM_MIRROR):
         self._lib = _lib.load()
@@ -77,6 +94,12 @@ class ReplayMemory:
             self._priority_args = (float(args.priority_alpha), float(args.priority_epsilon))
             _lib.check(self._lib.sdqn_replay_enable_priorities(h, *self._priority_args))
             self.set_priority_beta(float(args.priority_beta))
+        # --n_step: transitions span n steps — the poststate is state(i + n - 1), gather() returns (R, done) in place of
+        # (reward, terminal), and the memory only trains a network set to the same (n, discount_rate, min_reward, max_reward)
+        self.n_step = int(getattr(args, "n_step", 1))
+        self._nstep_args = (float(args.discount_rate), float(args.min_reward), float(args.max_reward)) if self.n_step > 1 else None
+        if self.n_step != 1:
+            _lib.check(self._lib.sdqn_replay_set_n_step(h, self.n_step, *(self._nstep_args or (0.0, 0.0, 0.0))))
         logger.info("Replay memory size: %d" % self.size)
 
     def __del__(self):
@@ -242,6 +265,9 @@ class ReplayMemory:
             self._materialize()
         self.last_indexes = idx.copy()
         raw = self._raw
+        if self.n_step > 1:
+            R, done = nstep_returns(raw["rewards"], raw["terminals"], idx, self.n_step, *self._nstep_args)
+            return self._lazy_pre, raw["actions"][idx], R, self._lazy_post, done
         return self._lazy_pre, raw["actions"][idx], raw["rewards"][idx], self._lazy_post, raw["terminals"][idx]
 
     # ---- prioritized replay ------------------------------------------------------------------------------------------
@@ -280,7 +306,9 @@ class ReplayMemory:
         return self.last_sample()[1]
 
     def getMinibatch(self):                                        # :50-79
-        assert self.count > self.history_length
+        """(prestates, actions, rewards, poststates, terminals); with n_step > 1 (prestates, actions, returns, poststates, dones):
+        returns float64, dones bool (nstep_returns)"""
+        assert self.count >= self.history_length + self.n_step
         return self.gather(self.sample_indexes())
 
     # ---- checkpoint of the ring (additive: the reference never persists its replay memory, README.md:132) -----------

@@ -343,6 +343,49 @@ int sdqn_net_debug_read(sdqn_net_t h, const char* name, float* out, int64_t n);
 int sdqn_net_visualize(sdqn_net_t h, sdqn_replay_t r, const int64_t* idx, const uint8_t* states, int64_t n, int max_fm,
                        int64_t* rec_state, int32_t* rec_pos, float* rec_value, float* vis_out, float* ms_out);
 
+/* ---- device-resident environment: the game "catch" (no reference counterpart; DESIGN.md §18, csrc/env_catch.h) ------------------------
+ * A 12 x 12 court of (H / 12) x (W / 12)-pixel cells: a ball falls one row per step (col += dx, reflecting at the side walls), a paddle
+ * of 3 cells on row 11 moves with actions 0 stay / 1 left / 2 right.  A ball reaching row 11 gives +1 on the paddle, -1 beside it, and a
+ * new ball spawns; every other step gives 0; an episode is balls_per_episode balls.  Frames u8[H][W]: 0 background, 255 ball, 128 paddle.
+ * The environment owns a splitmix64 generator (never Python's random nor the sampler's MT19937).  create / destroy / restart / step /
+ * screen / get_state / set_state / num_actions run on the HOST and need no device. */
+typedef struct sdqn_env_s* sdqn_env_t;
+typedef struct {
+  int32_t row, col, dx;    /* ball: 0..11, 0..11, -1..1 */
+  int32_t paddle;          /* left edge, 0..9 */
+  int32_t balls;           /* landed in this episode */
+  int32_t terminal;        /* 0 / 1 */
+  uint64_t rng;            /* splitmix64 counter */
+} sdqn_env_state;
+/* name = "catch"; H, W >= 12 (else SDQN_ERR_ARG); the generator starts at `seed`, the first episode is started */
+int sdqn_env_create(sdqn_env_t* h, const char* name, int screen_height, int screen_width, uint64_t seed, int balls_per_episode);
+int sdqn_env_destroy(sdqn_env_t e);
+int sdqn_env_restart(sdqn_env_t e);                                  /* new episode: balls 0, paddle 4, a new ball; does not reseed */
+int sdqn_env_num_actions(sdqn_env_t e, int* n);
+int sdqn_env_step(sdqn_env_t e, int action, int* reward, int* terminal);
+int sdqn_env_screen(sdqn_env_t e, uint8_t* screen /*[H][W]*/);       /* the host-rendered frame of the current state */
+int sdqn_env_get_state(sdqn_env_t e, sdqn_env_state* st);
+int sdqn_env_set_state(sdqn_env_t e, const sdqn_env_state* st);      /* SDQN_ERR_ARG for fields out of range */
+/* test hook: the frame of the current state as the render KERNEL produces it (sync) */
+int sdqn_env_render_device(sdqn_env_t e, uint8_t* screen);
+/* sdqn_net_act_step for an environment of the library: steps the game with `action`, then adds the new frame to the state buffer and,
+ * with r, the transition (action, reward, frame, terminal) to the replay memory.  The host renders the frame into the host mirrors, one
+ * launch renders it into the state buffer's device slot and the ring mirror's slot: no frame crosses PCIe.  Everything else is
+ * sdqn_statebuf_add + sdqn_replay_add (+ the speculative acting forward), bit for bit. */
+int sdqn_net_act_step_env(sdqn_net_t h, sdqn_statebuf_t sb, sdqn_replay_t r, sdqn_env_t e, int action, int speculate,
+                          int* reward, int* terminal);
+/* Vectorised evaluation on the device: num_envs (1 .. batch_size) independent copies of e's game (its geometry and balls_per_episode;
+ * e's own state is untouched) played for `steps` steps by the online net, epsilon-greedy.  Copy i: game generator
+ * seeded mix(seed + K (2 i + 1)), acting generator mix(seed + K (2 i + 2)) (K = 0xD1B54A32D192ED03, mix = the splitmix64 finaliser); per
+ * step ONE draw u of the acting generator, exploring when (u >> 11) < ceil(epsilon 2^53) with a second draw % 3 as the action, else the
+ * first maximum of the copy's Q row (NaN rule of sdqn_net_act_greedy).  A terminal step restarts the copy with zeroed history.  Per
+ * step the batched forward of sdqn_net_predict and one kernel are enqueued; one synchronisation at the end.  Outputs [num_envs], any
+ * NULL: steps, summed reward, balls caught, balls missed, episodes finished.  Trace, all four or none: actions / rewards / terminals
+ * [steps][num_envs], q [steps][num_envs][3] (double: exact for every datatype).  Any datatype / geometry sdqn_net_predict serves. */
+int sdqn_env_eval(sdqn_net_t h, sdqn_env_t e, int num_envs, int64_t steps, double epsilon, uint64_t seed,
+                  int64_t* out_steps, int64_t* out_reward, int64_t* out_caught, int64_t* out_missed, int64_t* out_episodes,
+                  uint8_t* actions, int8_t* rewards, uint8_t* terminals, double* q);
+
 /* per-kernel device timing (HIP events on the library stream; see option "profile_mode"), for bench.py's roofline leg.
  * kernel < 0 brackets every kernel of the step, otherwise only that kernel id. */
 int sdqn_net_profile(sdqn_net_t h, int enable, int kernel);

@@ -30,6 +30,12 @@ class NetCfg(C.Structure):
                 ("epsilon", C.c_double), ("beta_1", C.c_double), ("beta_2", C.c_double), ("loss_scale", C.c_double), ("batch_norm", C.c_double)]
 
 
+class EnvState(C.Structure):
+    """sdqn_env_state: the whole state of one game of catch"""
+    _fields_ = [("row", C.c_int32), ("col", C.c_int32), ("dx", C.c_int32), ("paddle", C.c_int32), ("balls", C.c_int32),
+                ("terminal", C.c_int32), ("rng", C.c_uint64)]
+
+
 _u8p, _i64p, _f32p, _u32p = C.POINTER(C.c_uint8), C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_uint32)
 _f64p = C.POINTER(C.c_double)
 _vp = C.c_void_p
@@ -113,6 +119,18 @@ SIGNATURES = {
     "sdqn_net_set_epoch": (C.c_int, [_vp, C.c_int]),
     "sdqn_net_debug_read": (C.c_int, [_vp, C.c_char_p, _f32p, C.c_int64]),
     "sdqn_net_visualize": (C.c_int, [_vp, _vp, _i64p, _u8p, C.c_int64, C.c_int, _i64p, C.POINTER(C.c_int32), _f32p, _f32p, _f32p]),
+    "sdqn_env_create": (C.c_int, [C.POINTER(_vp), C.c_char_p, C.c_int, C.c_int, C.c_uint64, C.c_int]),
+    "sdqn_env_destroy": (C.c_int, [_vp]),
+    "sdqn_env_restart": (C.c_int, [_vp]),
+    "sdqn_env_num_actions": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "sdqn_env_step": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "sdqn_env_screen": (C.c_int, [_vp, _u8p]),
+    "sdqn_env_get_state": (C.c_int, [_vp, C.POINTER(EnvState)]),
+    "sdqn_env_set_state": (C.c_int, [_vp, C.POINTER(EnvState)]),
+    "sdqn_env_render_device": (C.c_int, [_vp, _u8p]),
+    "sdqn_net_act_step_env": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "sdqn_env_eval": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, C.c_double, C.c_uint64, _i64p, _i64p, _i64p, _i64p, _i64p,
+                                _u8p, C.POINTER(C.c_int8), _u8p, _f64p]),
     "sdqn_net_profile": (C.c_int, [_vp, C.c_int, C.c_int]),
     "sdqn_net_profile_count": (C.c_int, [C.POINTER(C.c_int)]),
     "sdqn_net_profile_read": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_double), _i64p]),

@@ -56,6 +56,9 @@ class Agent:
         self.fused = fused and hasattr(self.net, "train_from_memory") and hasattr(self.mem, "_h")
         # one library call per environment transition (state-buffer add [+ ring add] [+ the next acting forward enqueued ahead of its use])
         self._one_call = hasattr(self.net, "act_step") and hasattr(self.buf, "_h")
+        # ... and the environment's step inside it when the game lives in the library (CatchEnvironment): the frame is rendered on the
+        # device, nothing is uploaded.  fused=False keeps the host-driven path (env.act + act_step with the screen)
+        self._env_call = fused and self._one_call and hasattr(self.net, "act_step_env") and hasattr(self.env, "_h")
 
     # ---- acting ------------------------------------------------------------------------------------------
     def _greedy_action(self):
@@ -84,16 +87,23 @@ class Agent:
     def _advance(self, exploration_rate, store=False):
         explore = random.random() < exploration_rate                  # draw order matters: shared global stream
         action = random.randrange(self.num_actions) if explore else self._greedy_action()
-        reward = self.env.act(action)
-        screen, terminal = self.env.getScreen(), self.env.isTerminal()
         ring = store and hasattr(self.mem, "_h")
-        if self._one_call:
-            # the acting forward of the new state is started now when the next step will most likely want it (greedy with probability
-            # 1 - exploration_rate) and the episode goes on; same Q-values as a forward started at the next step
-            self.net.act_step(self.buf, self.mem if ring else None, screen, action, reward, terminal,
-                              speculate=(exploration_rate < 0.5 and not terminal))
+        if self._env_call:
+            # the game steps inside the library too: one call, the frame rendered on the device (the library skips the speculative
+            # forward after a terminal step, as below)
+            reward, terminal = self.net.act_step_env(self.buf, self.mem if ring else None, self.env, action,
+                                                     speculate=(exploration_rate < 0.5))
+            screen = self.env.getScreen()
         else:
-            self.buf.add(screen)
+            reward = self.env.act(action)
+            screen, terminal = self.env.getScreen(), self.env.isTerminal()
+            if self._one_call:
+                # the acting forward of the new state is started now when the next step will most likely want it (greedy with probability
+                # 1 - exploration_rate) and the episode goes on; same Q-values as a forward started at the next step
+                self.net.act_step(self.buf, self.mem if ring else None, screen, action, reward, terminal,
+                                  speculate=(exploration_rate < 0.5 and not terminal))
+            else:
+                self.buf.add(screen)
         if terminal:
             self._fresh_episode()
         if self.callback:

@@ -215,6 +215,8 @@ int sample_checked(uint32_t* mt, const uint8_t* terminals, int64_t count, int64_
 int nstep_match(const sdqn_net_s* h, const sdqn_replay_s* r);       // --n_step: the memory's (n, discount, reward clip) equal the net's
 double nstep_gamma_n(int n, double gamma);                         // gamma^n by repeated multiplication (the n-step loop's g)
 int replay_free(sdqn_replay_s* r);
+int64_t replay_add_meta(sdqn_replay_s* r, int action, int64_t reward, int terminal);
+int replay_add_commit(sdqn_replay_s* r, int64_t c);
 int replay_flush_pending(sdqn_replay_s* r);
 int replay_push_idx(sdqn_replay_s* r, const int64_t* idx, int* slot_out, const int64_t** dev);
 int replay_release_idx(sdqn_replay_s* r, int slot);
@@ -244,6 +246,7 @@ int run_train(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd, const PrepAr
 int read_cost(sdqn_net_s* h, float* cost_out);
 bool act_sum_partials(const float* part, int A, float* q_out);
 const uint8_t* statebuf_window(sdqn_statebuf_s* s);
+int statebuf_advance(sdqn_statebuf_s* s, uint8_t** host_frame, uint8_t** dev_slot);
 int predict_state_enqueue(sdqn_net_s* h, sdqn_statebuf_s* sb);
 bool act_trace();
 int predict_state_collect(sdqn_net_s* h, float* q_out);

@@ -1,0 +1,97 @@
+// env_catch.h — the game "catch" (DESIGN.md §18): ONE definition in plain integer C++, compiled for the host (sdqn_env_* entry points,
+// the host mirrors of the fused act step) and for the device (render and evaluation kernels of sdqn_env.hip), so both run the same
+// text and agree bit for bit by construction.  No floating point, no library state: the environment owns its generator.
+//
+//   court   12 x 12 cells of ch = H / 12 by cw = W / 12 pixels (integer division); pixels outside 12 ch x 12 cw stay 0
+//   state   ball (row, col, dx), paddle left edge p (3 cells wide on row 11, 0 <= p <= 9), balls landed in this episode, terminal flag,
+//           64-bit generator state
+//   act(a)  0 stay, 1 left, 2 right (clamped); then row += 1, col += dx with reflection at the side walls (dx flips).  Ball on row 11:
+//           reward +1 if p <= col <= p + 2 else -1, balls += 1, terminal when balls == balls_per_episode, a new ball spawns at row 0
+//           from ONE draw d: col = d % 12, dx = (d / 12) % 3 - 1.  Every other step: reward 0.
+//   render  u8[H][W]: background 0, ball cell 255, paddle cells 128
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define CATCH_HD __host__ __device__ inline
+#else
+#define CATCH_HD inline
+#endif
+
+namespace sdqn {
+
+constexpr int CATCH_CELLS = 12, CATCH_PADDLE = 3, CATCH_ACTIONS = 3;
+constexpr int CATCH_BALL_PIXEL = 255, CATCH_PADDLE_PIXEL = 128;
+
+struct CatchState {            // == sdqn_env_state (include/sdqn.h), 32 bytes
+  int32_t row, col, dx, paddle, balls, terminal;
+  uint64_t rng;
+};
+
+// splitmix64 (Steele, Lea and Flood 2014): the state is a counter, the output its finalised value
+CATCH_HD uint64_t catch_mix(uint64_t z) {
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+CATCH_HD uint64_t catch_next(uint64_t& s) { s += 0x9E3779B97F4A7C15ull; return catch_mix(s); }
+// generator `stream` (0 the game's, 1 the acting policy's) of copy `e` of a vectorised evaluation seeded with `seed`
+CATCH_HD uint64_t catch_stream_seed(uint64_t seed, uint64_t e, uint64_t stream) {
+  return catch_mix(seed + 0xD1B54A32D192ED03ull * (2 * e + stream + 1));
+}
+
+CATCH_HD void catch_spawn(CatchState& s) {
+  const uint64_t d = catch_next(s.rng);
+  s.row = 0; s.col = (int32_t)(d % CATCH_CELLS); s.dx = (int32_t)((d / CATCH_CELLS) % 3) - 1;
+}
+CATCH_HD void catch_restart(CatchState& s) {      // new episode; the generator goes on (no reseed)
+  s.balls = 0; s.terminal = 0; s.paddle = 4;
+  catch_spawn(s);
+}
+CATCH_HD void catch_init(CatchState& s, uint64_t seed) { s.rng = seed; catch_restart(s); }
+
+CATCH_HD int catch_step(CatchState& s, int action, int balls_per_episode) {
+  if (action == 1 && s.paddle > 0) s.paddle -= 1;
+  if (action == 2 && s.paddle < CATCH_CELLS - CATCH_PADDLE) s.paddle += 1;
+  s.row += 1; s.col += s.dx;
+  if (s.col < 0) { s.col = -s.col; s.dx = -s.dx; }
+  if (s.col > CATCH_CELLS - 1) { s.col = 2 * (CATCH_CELLS - 1) - s.col; s.dx = -s.dx; }
+  if (s.row < CATCH_CELLS - 1) return 0;
+  const int reward = (s.col >= s.paddle && s.col < s.paddle + CATCH_PADDLE) ? 1 : -1;
+  s.balls += 1;
+  if (s.balls >= balls_per_episode) s.terminal = 1;
+  catch_spawn(s);
+  return reward;
+}
+
+// what the renderer needs of a state, small enough to ride in kernel arguments
+struct CatchView { int32_t row, col, paddle; };
+CATCH_HD CatchView catch_view(const CatchState& s) { CatchView v; v.row = s.row; v.col = s.col; v.paddle = s.paddle; return v; }
+// one pixel, as range tests on the cell rectangles (no division: the device calls this per byte); the ball is drawn over the paddle
+CATCH_HD uint8_t catch_pixel(const CatchView& v, int y, int x, int ch, int cw) {
+  if ((unsigned)(y - v.row * ch) < (unsigned)ch && (unsigned)(x - v.col * cw) < (unsigned)cw) return (uint8_t)CATCH_BALL_PIXEL;
+  if ((unsigned)(y - (CATCH_CELLS - 1) * ch) < (unsigned)ch && (unsigned)(x - v.paddle * cw) < (unsigned)(CATCH_PADDLE * cw))
+    return (uint8_t)CATCH_PADDLE_PIXEL;
+  return 0;
+}
+// the whole frame on the host: the same rectangles, filled
+CATCH_HD void catch_fill(uint8_t* out, int W, int y0, int x0, int h, int w, uint8_t value) {
+  for (int y = y0; y < y0 + h; ++y)
+    for (int x = x0; x < x0 + w; ++x) out[y * W + x] = value;
+}
+CATCH_HD void catch_render(const CatchView& v, uint8_t* out, int H, int W) {
+  const int ch = H / CATCH_CELLS, cw = W / CATCH_CELLS;
+  for (int i = 0; i < H * W; ++i) out[i] = 0;
+  catch_fill(out, W, (CATCH_CELLS - 1) * ch, v.paddle * cw, ch, CATCH_PADDLE * cw, (uint8_t)CATCH_PADDLE_PIXEL);
+  catch_fill(out, W, v.row * ch, v.col * cw, ch, cw, (uint8_t)CATCH_BALL_PIXEL);
+}
+
+// epsilon-greedy with the acting generator: one draw u; explore when (u >> 11) < thresh, thresh = ceil(epsilon * 2^53) (the 53-bit
+// uniform (u >> 11) * 2^-53 < epsilon, in integers); only then a second draw picks the action, draw % A
+CATCH_HD int catch_epsilon_greedy(uint64_t& act_rng, uint64_t thresh, int greedy, int A) {
+  const uint64_t u = catch_next(act_rng);
+  if ((u >> 11) < thresh) return (int)(catch_next(act_rng) % (uint64_t)A);
+  return greedy;
+}
+
+}  // namespace sdqn

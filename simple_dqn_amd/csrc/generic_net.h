@@ -23,6 +23,9 @@ struct GenericNet {
   virtual hipError_t get_param(int which, int layer, void* host, bool host_f64) = 0;          // synchronises
   // Q(s; theta) of n <= batch_size states already on the device ([n][hist][H][W] u8); q_host [n][A], synchronises
   virtual hipError_t predict_dev(const uint8_t* states_dev, int n, void* q_host, bool host_f64) = 0;
+  // the same forward enqueued only (no read-back, no synchronisation); q_dev() is where it leaves Q [n][A] in the network's precision
+  virtual hipError_t forward_dev(const uint8_t* states_dev, int n) = 0;
+  virtual const void* q_dev() const = 0;
   virtual hipError_t predict_host(const uint8_t* states_host, int n, void* q_host, bool host_f64) = 0;
   // one train step (deepqnetwork.py:107-172) on a device-resident minibatch; asynchronous on the stream
   virtual hipError_t train_dev(const uint8_t* pre, const uint8_t* post, const uint8_t* act, const int64_t* rew,

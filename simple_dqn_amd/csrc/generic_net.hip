@@ -431,6 +431,11 @@ class GenericNetT : public GenericNet {
     GCHK(forward(0, states_dev, n));
     return fetch(q, (int64_t)n * A, q_host, f64);                              // (n, A): deepqnetwork.py:186 qvalues.T
   }
+  hipError_t forward_dev(const uint8_t* states_dev, int n) override {
+    if (n < 1 || n > B) return hipErrorInvalidValue;
+    return forward(0, states_dev, n);
+  }
+  const void* q_dev() const override { return q; }
   hipError_t predict_host(const uint8_t* states_host, int n, void* q_host, bool f64) override {
     if (n < 1 || n > B) return hipErrorInvalidValue;
     GCHK(hipMemcpyAsync(st_states, states_host, (size_t)n * state_bytes(), hipMemcpyHostToDevice, st));

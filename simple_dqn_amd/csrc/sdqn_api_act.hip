@@ -28,12 +28,13 @@ extern "C" int sdqn_statebuf_destroy(sdqn_statebuf_t s) {
   free(s->host);
   delete s; return SDQN_OK;
 }
-extern "C" int sdqn_statebuf_add(sdqn_statebuf_t s, const uint8_t* screen) {
-  ARGCHK(s && screen, "NULL argument");
+// the bookkeeping of an add without the frame itself: generation bumped, host window shifted, the ring's wrap handled, `pos` advanced.
+// *host_frame = where the new frame goes in the host mirror, *dev_slot = its slot in the device ring (sdqn_statebuf_add uploads it
+// there, sdqn_net_act_step_env has a kernel render it there)
+int statebuf_advance(sdqn_statebuf_s* s, uint8_t** host_frame, uint8_t** dev_slot) {
   const int64_t FRAME = s->frame;
   s->gen += 1;
   memmove(s->host, s->host + FRAME, (size_t)(s->hist - 1) * FRAME);           // state_buffer.py:17
-  memcpy(s->host + (size_t)(s->hist - 1) * FRAME, screen, FRAME);             // :18
   if (s->pos + 1 == SB_SLOTS) {
     // wrap: the newest hist-1 frames move to the front; the sync also retires every staging slot of this lap
     HIPCHK(hipMemcpyAsync(s->d, s->d + (size_t)(SB_SLOTS - (s->hist - 1)) * FRAME, (size_t)(s->hist - 1) * FRAME,
@@ -42,9 +43,18 @@ extern "C" int sdqn_statebuf_add(sdqn_statebuf_t s, const uint8_t* screen) {
     s->pos = s->hist - 2;
   }
   s->pos += 1;
+  *host_frame = s->host + (size_t)(s->hist - 1) * FRAME; *dev_slot = s->d + (size_t)s->pos * FRAME;
+  return SDQN_OK;
+}
+extern "C" int sdqn_statebuf_add(sdqn_statebuf_t s, const uint8_t* screen) {
+  ARGCHK(s && screen, "NULL argument");
+  const int64_t FRAME = s->frame;
+  uint8_t *hf, *dv;
+  int rc = statebuf_advance(s, &hf, &dv); if (rc) return rc;
+  memcpy(hf, screen, FRAME);                                                  // :18
   uint8_t* src = s->stage + (size_t)s->pos * FRAME;
   memcpy(src, screen, FRAME);
-  HIPCHK(hipMemcpyAsync(s->d + (size_t)s->pos * FRAME, src, FRAME, hipMemcpyHostToDevice, g_stream));
+  HIPCHK(hipMemcpyAsync(dv, src, FRAME, hipMemcpyHostToDevice, g_stream));
   return SDQN_OK;
 }
 extern "C" int sdqn_statebuf_reset(sdqn_statebuf_t s) {

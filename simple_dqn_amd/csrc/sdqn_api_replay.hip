@@ -82,22 +82,32 @@ extern "C" int sdqn_replay_minibatch_ptrs(sdqn_replay_t r, uint8_t** pre, uint8_
   return SDQN_OK;
 }
 
-extern "C" int sdqn_replay_add(sdqn_replay_t r, int action, int64_t reward, const uint8_t* screen, int terminal) {
-  ARGCHK(r && screen, "NULL argument");
-  const int64_t FRAME = r->frame;
-  const int64_t c = r->current;                                   // replay_memory.py:29-32
+// ReplayMemory.add in two halves around the frame, shared with sdqn_net_act_step_env (whose frame is rendered on the device):
+// replay_add_meta writes slot `current` of the host arrays (replay_memory.py:29-31) and returns it; replay_add_commit sends the packed
+// metadata to the mirror, advances count / current (:33-34) and records the written slot for a prioritized memory
+int64_t replay_add_meta(sdqn_replay_s* r, int action, int64_t reward, int terminal) {
+  const int64_t c = r->current;
   r->actions[c] = (uint8_t)action; r->rewards[c] = reward; r->terminals[c] = terminal ? 1 : 0;
-  memcpy(r->screens + c * FRAME, screen, FRAME);
   MetaRec& m = r->h_meta[c];
   m.reward = reward; m.action = (uint8_t)action; m.terminal = terminal ? 1 : 0;
-  if (!(r->flags & SDQN_REPLAY_ZERO_COPY)) {
-    HIPCHK(hipMemcpyAsync(r->d_ring + c * FRAME, r->screens + c * FRAME, FRAME, hipMemcpyHostToDevice, g_stream));
-    HIPCHK(hipMemcpyAsync(r->d_meta + c, &m, sizeof(MetaRec), hipMemcpyHostToDevice, g_stream));
-  }
+  return c;
+}
+int replay_add_commit(sdqn_replay_s* r, int64_t c) {
+  if (!(r->flags & SDQN_REPLAY_ZERO_COPY))
+    HIPCHK(hipMemcpyAsync(r->d_meta + c, r->h_meta + c, sizeof(MetaRec), hipMemcpyHostToDevice, g_stream));
   if (c + 1 > r->count) r->count = c + 1;                         // :33
   r->current = (c + 1) % r->size;                                 // :34
   per_mark(r, c, 1);                                              // prioritized: p_max, validity of [c - n + 1, c + 1 + hist) re-evaluated
   return SDQN_OK;
+}
+extern "C" int sdqn_replay_add(sdqn_replay_t r, int action, int64_t reward, const uint8_t* screen, int terminal) {
+  ARGCHK(r && screen, "NULL argument");
+  const int64_t FRAME = r->frame;
+  const int64_t c = replay_add_meta(r, action, reward, terminal);   // replay_memory.py:29-32
+  memcpy(r->screens + c * FRAME, screen, FRAME);
+  if (!(r->flags & SDQN_REPLAY_ZERO_COPY))
+    HIPCHK(hipMemcpyAsync(r->d_ring + c * FRAME, r->screens + c * FRAME, FRAME, hipMemcpyHostToDevice, g_stream));
+  return replay_add_commit(r, c);
 }
 extern "C" int sdqn_replay_get_state(sdqn_replay_t r, int64_t* count, int64_t* current) {
   ARGCHK(r, "NULL handle"); if (count) *count = r->count; if (current) *current = r->current; return SDQN_OK;

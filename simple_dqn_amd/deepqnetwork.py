@@ -99,6 +99,7 @@ class DeepQNetwork:
             _lib.check(self._lib.sdqn_net_set_option(h, b"n_step", self.n_step))
         self._mt_buf = (C.c_uint32 * _lib.MT_WORDS)()
         self._act_out = C.c_int(); self._act_greedy = self._lib.sdqn_net_act_greedy
+        self._env_r, self._env_t = C.c_int(), C.c_int(); self._act_step_env = self._lib.sdqn_net_act_step_env
         self.train_iterations = 0
         self.callback = None
         self.save_weights_prefix = getattr(args, "save_weights_prefix", None)
@@ -261,6 +262,38 @@ class DeepQNetwork:
         rh = mem._h if mem is not None else None
         _lib.check(self._lib.sdqn_net_act_step(self._h, state_buffer._h, rh, _lib.ptr(scr, C.c_uint8), int(action), int(reward),
                                                int(bool(terminal)), int(bool(speculate))))
+
+    def act_step_env(self, state_buffer, mem, env, action, speculate=False):
+        """act_step for an environment that lives in the library (CatchEnvironment): steps the game with `action`, adds the new frame to
+        the state buffer and — with a device-backed replay memory — the transition to the ring.  The frame is rendered by a kernel
+        straight into the device state buffer and the ring's HBM mirror (nothing is uploaded) and by the host into their host copies.
+        Returns (reward, terminal)."""
+        assert env.dims == state_buffer.dims
+        assert mem is None or env.dims == mem.dims
+        r, t = self._env_r, self._env_t
+        _lib.check(self._act_step_env(self._h, state_buffer._h, mem._h if mem is not None else None, env._h, int(action),
+                                      int(bool(speculate)), C.byref(r), C.byref(t)))
+        env._stepped(t.value)
+        return r.value, bool(t.value)
+
+    def evaluate(self, env, num_envs, steps, epsilon=0.05, seed=0, trace=False):
+        """Vectorised evaluation on the device: `num_envs` (<= batch_size) independent copies of `env`'s game (its geometry and
+        balls_per_episode; env itself is not stepped), `steps` steps each, epsilon-greedy on the online net — per step one batched
+        forward and one kernel, no host round trip until the end.  Returns a dict of int64 arrays [num_envs]: steps, reward (summed),
+        caught, missed, episodes; with trace=True also actions / rewards / terminals [steps, num_envs] and q [steps, num_envs, A]
+        (the network's precision; float64 for a float64 network)."""
+        n, steps = int(num_envs), int(steps)
+        out = dict((k, np.zeros(n, dtype=np.int64)) for k in ("steps", "reward", "caught", "missed", "episodes"))
+        tr = [None] * 4
+        if trace:
+            acts, rews = np.zeros((steps, n), np.uint8), np.zeros((steps, n), np.int8)
+            terms, q = np.zeros((steps, n), np.uint8), np.zeros((steps, n, self.num_actions), np.float64)
+            tr = [_lib.ptr(acts, C.c_uint8), _lib.ptr(rews, C.c_int8), _lib.ptr(terms, C.c_uint8), _lib.ptr(q, C.c_double)]
+        _lib.check(self._lib.sdqn_env_eval(self._h, env._h, n, steps, float(epsilon), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                           *([_lib.ptr(out[k], C.c_int64) for k in ("steps", "reward", "caught", "missed", "episodes")] + tr)))
+        if trace:
+            out.update(actions=acts, rewards=rews, terminals=terms.astype(bool), q=q.astype(self._np))     # (float32 -> double -> float32: exact)
+        return out
 
     def load_weights(self, load_path):                             # :188-189
         """Own .npz snapshots, or a Neon pickle (the reference's `model.load_params`, best effort: neon_compat.py)."""

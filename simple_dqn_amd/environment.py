@@ -4,6 +4,8 @@ The reference's ALE / gym wrappers (environment.py:35-144) are emulator I/O and 
 (SURVEY.md §2.1); SyntheticEnvironment offers the same six methods on seeded uint8 frames so the
 Agent loop and the benchmarks run without an emulator.
 """
+import ctypes as C
+
 import numpy as np
 
 
@@ -71,6 +73,83 @@ class SyntheticEnvironment(Environment):
 
     def setMode(self, mode):
         self.mode = mode
+
+
+class CatchEnvironment(Environment):
+    """The game "catch" of the library (include/sdqn.h sdqn_env_*, csrc/env_catch.h): a ball falls through a 12 x 12 court,
+    a 3-cell paddle on the bottom row moves with actions 0 stay / 1 left / 2 right; +1 for a ball caught, -1 for a ball missed, an
+    episode is `balls_per_episode` balls.  Everything here runs on the host; `_h` lets DeepQNetwork.act_step_env / evaluate step and
+    render the game inside the library.  The generator is the environment's own (never Python's `random`)."""
+
+    def __init__(self, args=None, seed=0, balls_per_episode=None, screen_height=84, screen_width=84):
+        from . import _lib
+        self._libmod, self._lib = _lib, _lib.load()
+        h = getattr(args, "screen_height", screen_height)
+        w = getattr(args, "screen_width", screen_width)
+        if balls_per_episode is None:
+            balls_per_episode = getattr(args, "catch_balls", 10)
+        self.dims = (h, w)
+        self.balls_per_episode = int(balls_per_episode)
+        hd = C.c_void_p()
+        _lib.check(self._lib.sdqn_env_create(C.byref(hd), b"catch", h, w, int(seed) & 0xFFFFFFFFFFFFFFFF, self.balls_per_episode))
+        self._h = hd
+        self._screen = np.zeros(self.dims, dtype=np.uint8)
+        self._screen_ok = False
+        self._terminal = False
+        self._r, self._t = C.c_int(), C.c_int()
+        self.mode = "train"
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None and self._lib is not None:
+            self._lib.sdqn_env_destroy(h)
+
+    def numActions(self):
+        n = C.c_int()
+        self._libmod.check(self._lib.sdqn_env_num_actions(self._h, C.byref(n)))
+        return n.value
+
+    def restart(self):
+        self._libmod.check(self._lib.sdqn_env_restart(self._h))
+        self._terminal, self._screen_ok = False, False
+
+    def act(self, action):
+        self._libmod.check(self._lib.sdqn_env_step(self._h, int(action), C.byref(self._r), C.byref(self._t)))
+        self._terminal, self._screen_ok = bool(self._t.value), False
+        return self._r.value
+
+    def _stepped(self, terminal):
+        """the library stepped the game itself (DeepQNetwork.act_step_env)"""
+        self._terminal, self._screen_ok = bool(terminal), False
+
+    def getScreen(self):
+        if not self._screen_ok:
+            self._screen = np.empty(self.dims, dtype=np.uint8)          # (a new array per frame, like an emulator's getScreen)
+            self._libmod.check(self._lib.sdqn_env_screen(self._h, self._libmod.ptr(self._screen, C.c_uint8)))
+            self._screen_ok = True
+        return self._screen
+
+    def isTerminal(self):
+        return self._terminal
+
+    def setMode(self, mode):
+        self.mode = mode
+
+    def get_state(self):
+        st = self._libmod.EnvState()
+        self._libmod.check(self._lib.sdqn_env_get_state(self._h, C.byref(st)))
+        return dict((k, getattr(st, k)) for k, _ in st._fields_)
+
+    def set_state(self, state):
+        st = self._libmod.EnvState(**state)
+        self._libmod.check(self._lib.sdqn_env_set_state(self._h, C.byref(st)))
+        self._terminal, self._screen_ok = bool(st.terminal), False
+
+    def render_device(self):
+        """test hook: the current frame as the render kernel produces it"""
+        out = np.empty(self.dims, dtype=np.uint8)
+        self._libmod.check(self._lib.sdqn_env_render_device(self._h, self._libmod.ptr(out, C.c_uint8)))
+        return out
 
 
 def _to_gray_resized(obs, height, width):

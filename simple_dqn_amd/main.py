@@ -15,9 +15,11 @@ def _flag(text):
 # (flag, type, default[, extra argparse keywords])
 _OPTIONS = {
     "Environment": [
-        ("--environment", str, "synthetic", dict(choices=["synthetic", "ale", "gym"])),
+        ("--environment", str, "synthetic", dict(choices=["synthetic", "ale", "gym", "catch"])),
         ("--num_actions", int, 4, dict(help="Action-set size of the synthetic environment.")),
         ("--synthetic_frame_pool", int, 256, dict(help="Synthetic environment: serve frames from a pool of this many pre-generated frames (0: generate 7 KB of random bytes every step).")),
+        ("--catch_balls", int, 10, dict(help="Catch environment: balls per episode.")),
+        ("--eval_envs", int, 0, dict(help="Catch environment: play the test phase on this many copies of the game at once, on the device (0: Agent.test, one environment).")),
         ("--screen_width", int, 84), ("--screen_height", int, 84),
     ],
     "Replay memory": [
@@ -72,7 +74,7 @@ def build_parser():
 
 
 def run(args):
-    from . import Agent, DeepQNetwork, ReplayMemory, SyntheticEnvironment, _lib, load
+    from . import Agent, CatchEnvironment, DeepQNetwork, ReplayMemory, SyntheticEnvironment, _lib, load
     from .statistics import Statistics
     logger = logging.getLogger()
     logger.setLevel(args.log_level)
@@ -86,6 +88,8 @@ def run(args):
     if args.environment == "gym":
         from .environment import GymEnvironment                    # needs gymnasium (or gym); not part of this image
         env = GymEnvironment(args.game, args)
+    elif args.environment == "catch":                                # the library's own game (--num_actions is ignored: it has 3)
+        env = CatchEnvironment(args, seed=args.random_seed or 0)
     else:
         env = SyntheticEnvironment(args, num_actions=args.num_actions, seed=args.random_seed or 0, frame_pool=args.synthetic_frame_pool)
     mem = ReplayMemory(args.replay_size, args)                       # main.py:103-106
@@ -124,7 +128,13 @@ def run(args):
         if args.test_steps:
             env.setMode('test')
             stats.reset()
-            agent.test(args.test_steps, epoch)
+            if getattr(args, "eval_envs", 0) > 0:                    # vectorised on the device (catch only)
+                if not hasattr(env, "_h"):
+                    raise ValueError("--eval_envs needs --environment catch")
+                stats.record_evaluation(net.evaluate(env, args.eval_envs, -(-args.test_steps // args.eval_envs), args.exploration_rate_test,
+                                                     seed=(args.random_seed or 0) + epoch + 1), args.exploration_rate_test)
+            else:
+                agent.test(args.test_steps, epoch)
             stats.write(epoch + 1, "test")
     stats.close()
     return stats

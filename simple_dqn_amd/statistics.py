@@ -99,6 +99,19 @@ class Statistics:
     def on_step(self, action, reward, terminal, screen, exploration_rate):
         self._tally.step(reward, terminal, exploration_rate)
 
+    def record_evaluation(self, tallies, exploration_rate):
+        """The phase's tally from DeepQNetwork.evaluate (--eval_envs): steps, nr_games and last_exploration_rate are exact.  The device
+        keeps sums, not per-game returns: average_reward is the summed reward of ALL steps divided by the games finished (it includes
+        the open games' rewards; exact when none is open), min_game_reward / max_game_reward are not available and are written as 0."""
+        t = self._tally
+        t.num_steps = int(tallies["steps"].sum())
+        t.num_games = int(tallies["episodes"].sum())
+        t.game_rewards = int(tallies["reward"].sum())
+        t.last_exploration_rate = exploration_rate
+        t.min_game_reward = t.max_game_reward = 0
+        if t.num_games:
+            t.average_reward = float(t.game_rewards) / t.num_games
+
     def on_train(self, cost):
         self._resolve_pending()
         t = self._tally

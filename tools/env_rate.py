@@ -1,0 +1,87 @@
+"""Rates of the catch environment paths, one process, forms alternated, median of 7 rounds:
+  train   Agent.train env-steps/s on catch, fused act step (game stepped and rendered inside the library) vs host-driven (env.act + act_step
+          with the screen), same build, same seeds
+  eval    DeepQNetwork.evaluate env-steps/s at N = 32 and N = 256 (float32, float16) vs Agent.test on the same float32 net
+    python tools/env_rate.py [--rounds 7] [--train_steps 4000] [--eval_steps 400] [--json out.json]"""
+import argparse
+import json
+import os
+import random
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def _args(**kw):
+    from simple_dqn_amd.main import build_parser
+    a = build_parser().parse_args(["--environment", "catch"])
+    a.replay_size, a.exploration_decay_steps, a.target_steps, a.random_seed = 20000, 10000, 500, 1
+    for k, v in kw.items():
+        setattr(a, k, v)
+    return a
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--rounds", type=int, default=7)
+    p.add_argument("--train_steps", type=int, default=4000)
+    p.add_argument("--eval_steps", type=int, default=400)
+    p.add_argument("--json", default=None)
+    o = p.parse_args()
+    import simple_dqn_amd as sd
+    out = {}
+    # ---- train phase: two agents, alternated
+    agents = {}
+    for form in ("fused", "host"):
+        a = _args()
+        random.seed(1)
+        env, mem, net = sd.CatchEnvironment(a, seed=1), sd.ReplayMemory(a.replay_size, a), sd.DeepQNetwork(3, a)
+        ag = sd.Agent(env, mem, net, a)
+        ag._env_call = form == "fused"
+        ag.play_random(2000)
+        ag.train(1000)
+        net.sync()
+        agents[form] = (ag, net)
+    rates = {"fused": [], "host": []}
+    for _ in range(o.rounds):
+        for form in ("fused", "host"):
+            ag, net = agents[form]
+            t0 = time.perf_counter()
+            ag.train(o.train_steps)
+            net.sync()
+            rates[form].append(o.train_steps / (time.perf_counter() - t0))
+    for form in rates:
+        out["train_" + form] = dict(median=statistics.median(rates[form]), min=min(rates[form]), max=max(rates[form]))
+    # ---- evaluation
+    ag, net32 = agents["fused"]
+    t = []
+    for _ in range(o.rounds):
+        t0 = time.perf_counter()
+        ag.test(4000)
+        net32.sync()
+        t.append(4000 / (time.perf_counter() - t0))
+    out["agent_test"] = dict(median=statistics.median(t), min=min(t), max=max(t))
+    for dt in ("float32", "float16"):
+        for n in (32, 256):
+            a = _args(batch_size=n, datatype=dt)
+            net, env = sd.DeepQNetwork(3, a), sd.CatchEnvironment(a, seed=1)
+            net.evaluate(env, n, 20)
+            t = []
+            for r in range(o.rounds):
+                t0 = time.perf_counter()
+                net.evaluate(env, n, o.eval_steps, 0.05, r)
+                dtm = time.perf_counter() - t0
+                t.append(n * o.eval_steps / dtm)
+            med = statistics.median(t)
+            out["evaluate_%s_n%d" % (dt, n)] = dict(median=med, min=min(t), max=max(t), us_per_launch_group=1e6 * n / med)
+    for k, v in out.items():
+        print("%-24s %s" % (k, " ".join("%s %.1f" % kv for kv in v.items())))
+    if o.json:
+        json.dump(out, open(o.json, "w"), indent=1)
+
+
+if __name__ == "__main__":
+    main()

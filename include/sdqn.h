@@ -302,7 +302,7 @@ int sdqn_net_step_structure(sdqn_net_t h, int* structure, int* update);
  * an episode ended inside the n steps).  Ring-fed train calls need a replay memory set to the same n (sdqn_replay_set_n_step); tuples
  * go through sdqn_net_train_host_returns.  sdqn_net_last_q's maxpostq is then the bootstrap value of state(i + n - 1).
  * options: "grad_only" (see sdqn_net_apply_update), "keep_gradients" (1: the fc4 gradient is materialised and readable with which=3; 0 (default): on one
- * GPU RMSProp of fc4 is fused into the wgrad epilogue), "two_streams" (0 default; 1: wgrad kernels overlap the dgrad chain on a side stream), "fused_launches" (1 default:
+ * GPU RMSProp of fc4 is fused into the wgrad epilogue), "fused_launches" (1 default:
  * independent backward stages share one grid), "xcd_map" (0 default = only where it wins time: conv1/conv2/fc4 forward; 1: the
  * XCD-contiguous workgroup->tile map for every launch), "dp_overlap" (BEFORE sdqn_dp_init: -1 default = auto — second communicator for
  * nranks >= 2, activated by sdqn_dp_probe + vote + sdqn_dp_set_overlap; 1 forced on; 0 one all-reduce on the library stream), "dp_sync_replicas" (1 default: sdqn_dp_init broadcasts rank 0's online net,
@@ -312,9 +312,8 @@ int sdqn_net_step_structure(sdqn_net_t h, int* structure, int* update);
  * Round-3 switches of the default fp32 / float16 step, every one bit-identical to its alternative unless noted (tools/exp/README.md has the
  * measurements): "wt" (bit mask, default 511: write-through epilogue stores per launch), "conv1_bf16" / "conv1w_bf16" (1 default: conv1
  * forward / weight gradient on packed-bf16 MFMA with an exact 3-way split; 0: the fp32-MFMA engine — last bits differ), "conv3_c36" (1 default:
- * conv3 forward on 36-deep K-chunks; last bits differ), "r3_xcd" (tile maps of the two conv1 kernels), and three in-launch hand-offs that
- * measured slower than kernel boundaries and default to 0: "f4w_early" (fc4_wgrad inside the fc4_dgrad launch), "fuse_upd" (update(i) +
- * conv1(i+1)), "head_f4d" (head + fc4_dgrad).  A float64 / non-84x84x4 network (generic path) accepts and ignores the tuning options.
+ * conv3 forward on 36-deep K-chunks; last bits differ), "r3_xcd" (tile maps of the two conv1 kernels).  A float64 / non-84x84x4 network
+ * (generic path) accepts and ignores the tuning options.
  * Round 4: "bt" (1 default: batch_size >= 128 runs on the block-tile engine, gemm_engine_bt.h; 0: the latency engine's launch forms),
  * "bt:<kernel id>" (menu entry of that launch: 0 built-in block shape, -1 latency engine / previous kernel, n > 0 other shapes — tuning
  * surface of tools/sweep_bt.py), "tps:<layer>" (K chunks per weight-gradient slab), "act_kernel" (1 default where available — float32, no

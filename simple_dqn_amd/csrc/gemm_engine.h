@@ -48,10 +48,6 @@ template <class P, class = void> struct a_group4 { static constexpr bool value =
 template <class P> struct a_group4<P, decltype((void)P::A_GROUP4)> { static constexpr bool value = P::A_GROUP4; };
 template <class P, class = void> struct uses_f16_wgrad { static constexpr bool value = false; };
 template <class P> struct uses_f16_wgrad<P, decltype((void)P::F16_WGRAD)> { static constexpr bool value = P::F16_WGRAD; };
-// SIGNALS: thread 0 calls P::signal(a, bx, by, bz) right after the barrier that follows the main loops of all waves of the tile
-// (every operand load of the tile has returned by then) — round 3's write-after-read hand-off between fc4_dgrad and fc4_wgrad
-template <class P, class = void> struct signals { static constexpr bool value = false; };
-template <class P> struct signals<P, decltype((void)P::SIGNALS)> { static constexpr bool value = P::SIGNALS; };
 // PRELOAD: P::preload(a) runs first thing in the kernel and touches every argument field the problem will read, so that hipcc issues
 // ALL their scalar loads in one batch behind one wait.  Left alone it fetches each field of the 464-byte by-value StepArgs where it is
 // first used: four or five DEPENDENT round trips to a kernel-argument segment that is cold at every launch (round 3, sdqn_kernels_r3.hip)
@@ -353,7 +349,6 @@ __device__ __forceinline__ void gemm_tile(const StepArgs& a, int bx, int by, int
     }
     __syncthreads();
     SDQN_STAMP(5);
-    if constexpr (signals<P>::value) { if (threadIdx.x == 0) P::signal(a, bx, by, bz); }
     for (int e = threadIdx.x; e < 1024; e += NT) {
       const int ml = e >> 5, nl = e & 31;
       float v = smem[ml * 33 + nl];

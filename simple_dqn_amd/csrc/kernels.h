@@ -1,6 +1,7 @@
 // kernels.h — launch interface between the host orchestration (sdqn_api_*.hip) and the device
 // code (sdqn_kernels.hip).  Kernel ids double as the profiler's slots.
 #pragma once
+#include <cstddef>
 #include <hip/hip_runtime.h>
 #include "problems.h"
 #include "launch.h"
@@ -15,14 +16,12 @@ enum KernelId {
   K_BWD2,      // one launch: conv2_dgrad + conv2_wgrad (both depend on conv3_dgrad only) + a share of fc4_wgrad
   K_BWD1,      // one launch: conv1_wgrad + the last share of fc4_wgrad
   K_BN,        // --batch_norm: one BatchNorm layer, forward ([partial +] apply) or backward (partial + apply)
-  K_F4D_F4W,   // round 3, one launch: fc4_dgrad + fc4_wgrad (+ fused RMSProp of W4) — the wgrad only needs delta4 and a3
-  K_BWD3_CONV, // round 3: bwd3 without the fc4 share (conv3_dgrad + conv3_wgrad)
-  K_UPD_CONV1, // round 3: update(i) + conv1_fwd(i + 1) in one launch
-  K_HEAD_F4D,  // round 3: head + fc4_dgrad in one launch (the dgrad tiles fetch their W4 panels while the head runs)
+  K_RESERVED_20, K_RESERVED_21, K_RESERVED_22, K_RESERVED_23,   // ids of retired round-3 launches: the numbers are public (options bt:/xcd:/nw:<id>, profile_read), nothing launches them
   K_WGRADS,    // round 4 (float16, B >= 128): fc4_wgrad (+ fused RMSProp) || conv3_wgrad || conv2_wgrad in one launch, after the block-tile dgrad chain
   K_ACT,       // round 4: the acting forward (batch of one) as ONE launch (sdqn_act.hip)
   K_COUNT
 };
+static_assert(K_BN == 19 && K_WGRADS == 24 && K_ACT == 25 && K_COUNT == 26, "kernel ids are public numbers");
 const char* kernel_name(int id);
 
 
@@ -37,9 +36,7 @@ struct HeadArgs {
   double discount, min_reward, max_reward;
   float clip_error;
   int train;                    // 0: predict only (z = 0); 1: train step; 2: train step with Double DQN targets (--double_dqn)
-  // hoist: one extra workgroup copies the NEXT step's sampled indexes from their pinned slot into device memory, so that
-  // the target conv1 riding in this step's K_BWD2 launch reads them from HBM (next_B = 0: nothing to copy)
-  const int64_t* next_idx_pinned; int64_t* next_idx_dev; int next_B;
+  int reserved_[6];             // (a retired option's fields: every later field keeps its offset, see StepArgs::reserved_)
   // --prioritized_replay (sdqn_per.hip): per_w != nullptr selects the PER head — dq = w clip(delta), cost term 0.5 w delta^2, and
   // per_p[n] = (|delta| + per_eps)^per_alpha, the new priority the next per_step launch writes back
   const float* per_w; float* per_p; double per_alpha, per_eps;
@@ -88,15 +85,22 @@ struct UpdateArgs {
   half_t* wh;                   // fp16 mode: half copies of theta refreshed by the update (master layout / transposed)
   half_t* wht;
   unsigned short* w1p;          // conv1's three bf16 planes of the ONLINE net, rewritten with W1 (nullptr: not maintained)
-  unsigned short* wpm;          // round 4: bf16 planes of conv2 / conv3 / fc4 weights, master layout (nullptr: not maintained — B < 128)
-  unsigned short* wpt;          //          ... conv2 / conv3 transposed ([n][K])
+  int reserved_[4];             // (retired options' fields: every other field keeps its offset — update_kernel preloads them by name)
   int wt;                       // 1: the new parameters / optimizer state leave with write-through (sc1) stores
-  unsigned* w1_ctr;             // fused update + conv1 launch only: counts the W1 blocks whose write-through stores are out (monotonic across launches)
+  int reserved2_[3];
   int64_t bn_first;             // --batch_norm: element offset of the [beta|gamma] block (bn_update_kernel); BN_PARAMS elements
   const int* ovf_flag;          // fp16 data parallel (update_kernel<true>): != 0 -> the all-reduced half gradient overflowed, leave theta / state untouched
   int64_t* ovf_count;           //   ... and count the skipped step
   int ovf_dynamic;              //   1: block 0 also moves the payload scale (state[1]) — halve on overflow, double after 200 clean steps
 };
+
+// The kernel-argument layouts are part of the tuned kernels (StepArgs::reserved_, problems.h): frozen where a retired field became reserved bytes
+static_assert(sizeof(HeadArgs) == 160 && offsetof(HeadArgs, train) == 84 && offsetof(HeadArgs, per_w) == 112 && offsetof(HeadArgs, per_eps) == 136 &&
+              offsetof(HeadArgs, nstep) == 144 && offsetof(HeadArgs, gamma_n) == 152, "HeadArgs layout");
+static_assert(sizeof(PrepArgs) == 344 && offsetof(PrepArgs, idx_in_valid) == 52 && offsetof(PrepArgs, idx_in) == 56 && offsetof(PrepArgs, ns) == 312, "PrepArgs layout");
+static_assert(sizeof(UpdateArgs) == 616 && offsetof(UpdateArgs, next) == 128 && offsetof(UpdateArgs, next) + offsetof(PrepArgs, idx_in) == 184 &&
+              offsetof(UpdateArgs, bsz) == 472 && offsetof(UpdateArgs, w1p) == 544 && offsetof(UpdateArgs, wt) == 568 && offsetof(UpdateArgs, bn_first) == 584 &&
+              offsetof(UpdateArgs, ovf_flag) == 592 && offsetof(UpdateArgs, ovf_count) == 600 && offsetof(UpdateArgs, ovf_dynamic) == 608, "UpdateArgs layout");
 
 struct BnArgs {                  // one BatchNorm layer (bn_kernels.hip); activations NHWC: rows x C, C contiguous
   int layer;                    // 0..3 = after conv1, conv2, conv3, fc4
@@ -155,7 +159,8 @@ struct LaunchTune {
   int r3_xcd;               // round-3 kernels' XCD-contiguous tile maps: bit 0 conv1_fwd (bf16), bit 1 conv1_wgrad (bf16)
   int wt;                   // write-through (sc1) epilogue stores per launch: 1 conv2_fwd, 2 conv3_fwd, 4 fc4_fwd, 8 fc4_dgrad, 16 bwd3, 32 bwd2, 64 conv1_wgrad, 128 conv1_fwd
   int bt[K_COUNT];          // B >= 128, float32: block-tile engine (sdqn_kernels_bt.hip) per kernel id; 0 = built-in block shape, n > 0 = menu entry, < 0 = latency engine
-  int r3;                   // round-3 launch variants (sdqn_kernels_r3.hip); bit 0: this K_FC4_DGRAD launch also carries the fc4_wgrad tiles; bit 1: conv3_fwd on 36-deep K-chunks; bit 2: conv1_fwd on packed-bf16 MFMA
+  int r3;                   // round-3 launch variants (sdqn_kernels_r3.hip); bit 1: conv3_fwd on 36-deep K-chunks; bit 2: conv1_fwd on packed-bf16 MFMA; bit 3: conv1_wgrad on packed-bf16 MFMA;
+                            // bits 4 / 5 (float16, B >= 128): conv1_wgrad rides in the K_WGRADS launch / its workgroups first (sdqn_kernels_bt.hip); bit 0 is unused
 };
 hipError_t launch_kernel(int id, const StepArgs& a, const LaunchTune& t, hipStream_t s);     // the GEMM-shaped stages (single or multi-problem launches)
 hipError_t launch_head(const StepArgs& a, const HeadArgs& h, hipStream_t s, bool q_system_scope = false);   // q_system_scope: h.q is mapped host memory (acting path)
@@ -187,6 +192,5 @@ struct ActArgs {
 hipError_t launch_act(const ActArgs& a, bool q_system_scope, hipStream_t s);
 hipError_t launch_w1_planes(const float* theta, unsigned short* w1p, hipStream_t s);   // conv1's three bf16 weight planes of one net (problems.h: split_bf16x3)
 hipError_t launch_refresh16(const float* theta, half_t* wh, half_t* wht, hipStream_t s);   // fp16 mode: rebuild both half copies
-hipError_t launch_refresh_planes(const float* theta, unsigned short* wpm, unsigned short* wpt, hipStream_t s);   // plane mode: rebuild the bf16 planes of conv2 / conv3 (both layouts) and fc4 (master; wpm may be nullptr: target net)
 
 }  // namespace sdqn

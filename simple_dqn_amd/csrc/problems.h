@@ -19,6 +19,7 @@
 //   d3p [n][11][11][64]  conv3-output delta, zero-padded by 2 (full correlation for dgrad); d3 = dense copy
 //   d2p [n][11][11][64]  conv2-output delta, zero-padded by 1 (stride-2 parity decomposition); d2 = dense copy
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #include <math.h>
 
@@ -136,29 +137,16 @@ struct StepArgs {
   // --batch_norm (deepqnetwork.py:26,83-89): launch_kernel picks the *Raw forward problems (linear output without the
   // Rectlin: the BatchNorm + Rectlin pass of bn_kernels.hip follows) and the head variant that reads an activated a4
   int bn;
-  const int64_t* idx_t;     // hoist option only (Conv1FwdTarget): the NEXT step's indexes, whose target conv1 rides in this step's K_BWD2
-  // ---- round 3 (appended: every earlier field keeps its offset) ----
-  // fc4_wgrad + fused RMSProp riding in the fc4_dgrad launch (sdqn_kernels_r3.hip): the dgrad tile of W4 row block j publishes
-  // "my reads of W4 rows [32 j, 32 j + 32) are done" as f4d_flags[16 j] = f4d_epoch; an fc4_wgrad tile of the same row block
-  // waits for it before its in-place RMSProp store (a write-after-read hand-off: no data crosses, so no cache visibility issue)
-  unsigned* f4d_flags;      // [NIN4 / 32][16] one word per row block, 64 B apart; [NIN4 / 32 * 16] = sticky time-out word
-  unsigned f4d_epoch;       // step number (monotonic, never 0): flags never need a reset
-  int r3_pad_;
+  int reserved2_[6];        // (fields of retired round-3 options: every later field keeps its offset, like reserved_ above)
   // conv1 forward on packed-bf16 MFMA (sdqn_kernels_r3.hip): W1 of the online [0] / target [1] net as THREE bf16 planes whose sum is
   // the fp32 weight exactly, each [32 output maps][256 k] with k contiguous — written by whoever writes W1 (update kernel, set_weights,
   // target sync)
   const unsigned short* w1p[2];
-  // ---- round 4 (appended): bf16 planes of the conv2 / conv3 / fc4 weights for the block-tile engine's plane mode (gemm_engine_bt.h:
-  // bt_tile_xp).  Three planes whose sum is the fp32 weight exactly (split_bf16x3), plane stride XP_PLANE elements, written by whoever
-  // writes the weights (update kernel, fc4_wgrad's fused RMSProp epilogue, set_weights, target sync, DP broadcast):
-  //   wpm    : online net, MASTER layout (same element index as theta): the k-contiguous B operand of the dgrads
-  //   wpt[z] : per net, every layer TRANSPOSED ([n][K], k contiguous: the fp16 mode's wht indexing): the B operand of conv2 / conv3 forward
-  const unsigned short* wpm;
-  const unsigned short* wpt[2];
-  int xp;                   // 0: fp32 MFMA everywhere; 9 / 6: plane mode with 9 / 6 exact partial products per fp32 product
-  int xp_pad_;
+  int reserved3_[8];        // (a retired round-4 option's fields: sizeof(StepArgs) stays what the kernels were tuned with)
 };
-constexpr int XP_PLANE = OFF5;            // elements per weight plane (conv1 .. fc4; fc5 is not a GEMM stage of the engine)
+
+static_assert(sizeof(StepArgs) == 496 && offsetof(StepArgs, post_off) == 336 && offsetof(StepArgs, theta_w) == 384 && offsetof(StepArgs, bn) == 420 &&
+              offsetof(StepArgs, w1p) == 448, "StepArgs layout: part of the tuned kernels (reserved_)");
 
 // A9 + A10 in Neon's operation order (the library is built with -ffp-contract=off: one rounding per op)
 // grad / be.bsz (A9), exactly: for a power-of-two divisor (B = 32, 256, ...; R*B under data parallel) the quotient
@@ -213,7 +201,7 @@ constexpr int W1P_PLANE = K1 * CRS1;      // elements per plane: [32 maps][256 k
 
 // Net slots of a forward launch (StepArgs::nz of them): 0 = online net on the prestates, 1 = target net on the poststates and, with
 // --double_dqn, 2 = ONLINE net on the POSTSTATES (the argmax of the Double DQN target).  Slot z takes its weights from theta[wslot(z)]
-// (and the matching wh / wht / w1p / wpt copies), its frames from state slot sslot(z) of the [2][B][STATE] staging or, read from the ring,
+// (and the matching wh / wht / w1p copies), its frames from state slot sslot(z) of the [2][B][STATE] staging or, read from the ring,
 // from soff(post_off, z) frames after the prestate's first frame; activations, slabs and Q are indexed by z itself.
 // --n_step n: the poststate of sample i is state(i + n - 1), n frames after the prestate — StepArgs::post_off = n.
 SDQN_HD int wslot(int z) { return z & 1; }
@@ -444,14 +432,6 @@ template <class P> struct TargetOnly : P {
   SDQN_HD static int nbz(const StepArgs&) { return 1; }
   SDQN_HD static void ksplit(const StepArgs& a, int, int& z, int& ks, int& kb, int& ke) { P::ksplit(a, 1, z, ks, kb, ke); }
 };
-struct Conv1FwdTarget : Conv1Fwd {       // target conv1 of the NEXT step: gathers with StepArgs::idx_t (poststates = screens[i-4+n : i+n])
-  SDQN_HD static int nbz(const StepArgs&) { return 1; }
-  SDQN_HD static void ksplit(const StepArgs& a, int, int& z, int& ks, int& kb, int& ke) { Conv1Fwd::ksplit(a, 1, z, ks, kb, ke); }
-  SDQN_HD static aoff_t a_row(const StepArgs& a, int, int m) {
-    int n = m / PIX1, pix = m - n * PIX1, p = pix / Q1, q = pix - p * Q1;
-    return (a.idx_t[n] - C0 + soff(a.post_off, 1)) * (int64_t)FRAME + (int64_t)(p * ST1) * W0 + q * ST1;
-  }
-};
 struct Fc4FwdTarget : Fc4Fwd {
   SDQN_HD static int nbz(const StepArgs& a) { return a.S4; }
   SDQN_HD static void ksplit(const StepArgs& a, int bz, int& z, int& ks, int& kb, int& ke) { Fc4Fwd::ksplit(a, bz + a.S4, z, ks, kb, ke); }
@@ -549,37 +529,6 @@ struct Fc4Wgrad {   // gW4 = delta4 . a3^T (sum over batch, A8) in the W4i layou
   }
 #endif
 };
-
-#if defined(__HIPCC__)
-// fc4_dgrad + fc4_wgrad in ONE launch (round 3).  At B <= 32 the dgrad has a single M tile, so W4i rows [32 j, 32 j + 32)
-// are read by exactly ONE workgroup (dgrad tile j) — and rewritten in place by the 16 fc4_wgrad tiles (j, 0..15) when RMSProp
-// is fused into their epilogue.  Tile j publishes the end of its reads, the writers wait for it: the 25.7 MB read-modify-write
-// stream of W4 + its optimizer state then runs on the 158 CUs the 98 dgrad workgroups leave idle instead of lengthening bwd3.
-struct Fc4DgradSig : Fc4Dgrad {
-  static constexpr bool SIGNALS = true;
-  // called by thread 0 after the workgroup barrier that follows every wave's main loop (all operand loads have returned)
-  __device__ static void signal(const StepArgs& a, int bx, int by, int bz) {
-    (void)bx; (void)bz;
-    __hip_atomic_store(a.f4d_flags + by * 16, a.f4d_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-};
-struct Fc4WgradWait : Fc4Wgrad {
-  __device__ static void store16(const StepArgs& a, int z, int ks, int m0, int n0, int lane, int M, int N, const float* v, Epi& e) {
-    if (a.fuse_rms) {                                  // (materialised gradient: written to g, nothing to wait for)
-      const unsigned* f = a.f4d_flags + (m0 >> 5) * 16;
-      int spins = 0;                                   // wave-uniform loop: every lane reads the same word
-      while (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != a.f4d_epoch) {
-        __builtin_amdgcn_s_sleep(2);
-        if (++spins > 4000000) {                       // ~ seconds: the producer tile never ran -> report, never hang
-          __hip_atomic_store(a.f4d_flags + (NIN4 / 32) * 16, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          break;
-        }
-      }
-    }
-    Fc4Wgrad::store16(a, z, ks, m0, n0, lane, M, N, v, e);
-  }
-};
-#endif
 
 struct Conv3Dgrad { // delta2 = full-correlation(d3p, W3) * 1[a2 > 0], written into the padded d2p
   static constexpr bool A_K = true, B_K = true;     // operand contiguous along k (-> LDS transpose) or along m/n

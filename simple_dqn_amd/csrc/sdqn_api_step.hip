@@ -100,7 +100,7 @@ int run_forward(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd) {
   }
   // XCD-contiguous tile map where it wins time (tools/sweep_xcd.py, tools/ab_options.py): conv1_fwd +0.5 %, conv2_fwd
   // +0.2 %, fc4_fwd +0.6 % of the step rate; slower for conv3_fwd, fc4_dgrad and every backward launch
-  StepArgs fm = a; fm.xcd_map = 1; fm.idx_t = nullptr;
+  StepArgs fm = a; fm.xcd_map = 1;
   LAUNCH(K_CONV1_FWD, launch_tuned(h, K_CONV1_FWD, fm, g_stream, (h->conv1_bf16 && h->nw_override[K_CONV1_FWD] == 0) ? 4 : 0));
   { StepArgs f2 = fm; if (h->B >= 128) f2.xcd_map = a.xcd_map;          // block-tile routines (B >= 128): conv2_fwd 28.8 / 8.8 us round-robin, 28.9 / 9.0 on the map (fp32 / float16)
     LAUNCH(K_CONV2_FWD, launch_tuned(h, K_CONV2_FWD, f2, g_stream)); }
@@ -229,7 +229,7 @@ int run_train(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd0, const PrepA
     LAUNCH(K_CONV2_DGRAD, launch_tuned(h, K_CONV2_DGRAD, a, g_stream));
     // round 6: conv1's weight gradient (c1w_h_kernel's K-slab workgroups) as a fourth block range of the weight-gradient launch — delta1 is
     // complete by then — where that kernel applies (packed-fp16 weight gradients, slabs of whole 80-position chunks) and nothing asks for
-    // another form (bt:18 / bt:22 = 0; option c1w_in_wgrads: 0 = off, 1 = its workgroups last (built-in), 2 = first)
+    // another form (bt:18 / bt:24 = 0; option c1w_in_wgrads: 0 = off, 1 = its workgroups last (built-in), 2 = first)
     const int merge = (h->c1w_in_wgrads && h->h16_wgrad_mfma && (h->tps1 * 32) % 80 == 0 && h->bt[K_BWD1] == 0 && h->bt[K_WGRADS] == 0 &&
                        h->nw_override[K_CONV1_WGRAD] == 0) ? (h->c1w_in_wgrads == 2 ? 48 : 16) : 0;
     LAUNCH(K_WGRADS, launch_tuned(h, K_WGRADS, w, g_stream, merge));

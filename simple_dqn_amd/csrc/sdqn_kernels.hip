@@ -16,8 +16,8 @@ static const char* k_names[K_COUNT] = {
   "fc4_dgrad", "fc4_wgrad", "conv3_dgrad", "conv3_wgrad", "conv2_dgrad", "conv2_wgrad",
   "conv1_wgrad", "update(reduce+fc5wgrad+rmsprop)", "rccl_allreduce", "replay_gather_u8", "prep(idx+meta)",
   "bwd3(conv3_dgrad+conv3_wgrad+fc4_wgrad)", "bwd2(conv2_dgrad+conv2_wgrad+fc4_wgrad)", "bwd1(conv1_wgrad+fc4_wgrad)",
-  "batchnorm(layer fwd/bwd)", "fc4_dgrad+fc4_wgrad(+rmsprop W4)", "bwd3(conv3_dgrad+conv3_wgrad)", "update(i)+conv1_fwd(i+1)",
-  "head+fc4_dgrad", "wgrads(fc4+conv3+conv2)", "act(conv1..fc5, one state)"};
+  "batchnorm(layer fwd/bwd)", "reserved", "reserved", "reserved", "reserved",
+  "wgrads(fc4+conv3+conv2)", "act(conv1..fc5, one state)"};
 const char* kernel_name(int id) { return (id >= 0 && id < K_COUNT) ? k_names[id] : "?"; }
 LaunchEvents& launch_events() { static thread_local LaunchEvents le; return le; }
 
@@ -33,9 +33,9 @@ static hipError_t launch_nw(int nw, const StepArgs& a, hipStream_t s) {
 }
 
 // Waves per workgroup = how many 32-deep K-chunks run concurrently on one output tile (gemm_engine.h).
-// Everything that is NOT the default fp32 step lives in sdqn_kernels_ext.hip (fp16 mode, option "hoist", the register-blocked
-// experiments): hipcc's schedule of the default kernels depends on what else is instantiated in their translation unit
-// (measured: -1 % step rate when the new variants shared this file), so this file stays what round 1 tuned.
+// The fp16 mode's problems live in sdqn_kernels_ext.hip: hipcc's schedule of the default kernels depends on what else is
+// instantiated in their translation unit (measured: -1 % step rate when the new variants shared this file), so this file stays
+// what round 1 tuned.
 hipError_t launch_kernel_ext(int id, const StepArgs& a, const LaunchTune& t, hipStream_t s, bool* handled);
 
 hipError_t launch_kernel_r3(int id, const StepArgs& a, const LaunchTune& t, hipStream_t s, bool* handled);
@@ -139,21 +139,13 @@ hipError_t launch_kernel(int id, const StepArgs& a, const LaunchTune& t, hipStre
 // AMAX = compile-time bound on num_actions (4 / 8 / 18): every load below is unconditional with a clamped index and
 // a select — a conditional load costs hipcc a branch, a scalar pointer re-load and a wait EACH (36 of them measured
 // ~3000 cycles here), and the LDS footprint follows the bucket.
-// HOIST (option "hoist" only; compiled out of the default kernel — even this one branch was measurable): one extra workgroup
-// fetches the next step's indexes from their pinned host slot into HBM.
 // QSYS (acting path, round 4): h.q is HOST memory (mapped, pinned) and every Q-value leaves with a system-scope store the moment it is
 // summed, so the host can poll for it instead of paying a D2H copy packet + a stream synchronisation (sdqn_api_act.hip: predict_state).
 // PER (--prioritized_replay): the taken action's row is weighted by h.per_w[n] and the new priority goes to h.per_p[n]
 // NSTEP (--n_step): the staged reward is the n-step return R (a double's bits), the terminal the done flag, the bootstrap factor gamma^n
-template <int AMAX, bool BN, bool HOIST = false, bool QSYS = false, bool DDQN = false, bool PER = false, bool NSTEP = false>
+template <int AMAX, bool BN, bool QSYS, bool DDQN, bool PER, bool NSTEP>
 __global__ void __launch_bounds__(512) head_kernel(const StepArgs a, const HeadArgs h) {
   SDQN_STAMP(0);
-  if constexpr (HOIST) {
-    if ((int)blockIdx.x >= a.B) {
-      for (int k = threadIdx.x; k < h.next_B; k += 512) h.next_idx_dev[k] = h.next_idx_pinned[k];
-      return;
-    }
-  }
   const int n = blockIdx.x, j = threadIdx.x, lane = j & 63, wave = j >> 6;
   // --double_dqn (DDQN): a third net slot, the online net on the poststates, computed here from its fc4 slabs (NZ = 3); with batch_norm its
   // Q-values were written to q slot 2 by a forward of their own (sdqn_api_step.hip: run_train)
@@ -327,50 +319,27 @@ hipError_t set_wave_timing_buffer(unsigned long long* const* p, const unsigned* 
 }
 #endif
 
+// The head of one (QSYS, DDQN, PER, NSTEP) combination for a bucket: 0 / 1 / 2 = A <= 4 / <= 8 / <= MAX_ACTIONS, 3 = --batch_norm (not tuned
+// per bucket; never on the acting path).  launch_head names the combinations that exist: the set of instantiations is part of this file's tuning.
+typedef void (*HeadKernel)(const StepArgs, const HeadArgs);
+template <bool QSYS, bool DDQN, bool PER, bool NSTEP>
+static HeadKernel head_for(int bucket) {
+  if constexpr (!QSYS) { if (bucket == 3) return head_kernel<MAX_ACTIONS, true, false, DDQN, PER, NSTEP>; }
+  return bucket == 0 ? head_kernel<4, false, QSYS, DDQN, PER, NSTEP> : bucket == 1 ? head_kernel<8, false, QSYS, DDQN, PER, NSTEP>
+                                                                                   : head_kernel<MAX_ACTIONS, false, QSYS, DDQN, PER, NSTEP>;
+}
+
 hipError_t launch_head(const StepArgs& a, const HeadArgs& h, hipStream_t s, bool q_system_scope) {
   if (a.nz > 2 && (h.train != 2 || a.bn)) return hipErrorInvalidValue;          // (a third slot needs the Double DQN head's LDS)
-  if (q_system_scope && !a.bn && !h.train) {          // acting path: Q-values straight into mapped host memory
-    if (a.A <= 4) SDQN_LAUNCH((head_kernel<4, false, false, true>), dim3(a.B), dim3(512), 0, s, a, h);
-    else if (a.A <= 8) SDQN_LAUNCH((head_kernel<8, false, false, true>), dim3(a.B), dim3(512), 0, s, a, h);
-    else SDQN_LAUNCH((head_kernel<MAX_ACTIONS, false, false, true>), dim3(a.B), dim3(512), 0, s, a, h);
-    return hipGetLastError();
-  }
-#define SDQN_HEAD_SET(DD, PP, NS) do { \
-    if (a.bn) SDQN_LAUNCH((head_kernel<MAX_ACTIONS, true, false, false, DD, PP, NS>), dim3(a.B), dim3(512), 0, s, a, h); \
-    else if (a.A <= 4) SDQN_LAUNCH((head_kernel<4, false, false, false, DD, PP, NS>), dim3(a.B), dim3(512), 0, s, a, h); \
-    else if (a.A <= 8) SDQN_LAUNCH((head_kernel<8, false, false, false, DD, PP, NS>), dim3(a.B), dim3(512), 0, s, a, h); \
-    else SDQN_LAUNCH((head_kernel<MAX_ACTIONS, false, false, false, DD, PP, NS>), dim3(a.B), dim3(512), 0, s, a, h); } while (0)
-  if (h.nstep > 1 && h.train) {                       // --n_step train step (its own instantiations, composed with Double DQN and PER)
-    if (h.per_w) { if (h.train == 2) SDQN_HEAD_SET(true, true, true); else SDQN_HEAD_SET(false, true, true); }
-    else { if (h.train == 2) SDQN_HEAD_SET(true, false, true); else SDQN_HEAD_SET(false, false, true); }
-    return hipGetLastError();
-  }
-#undef SDQN_HEAD_SET
-  if (h.per_w && h.train) {                           // --prioritized_replay train step (its own instantiations, with or without Double DQN)
-    if (h.train == 2) {
-      if (a.bn) SDQN_LAUNCH((head_kernel<MAX_ACTIONS, true, false, false, true, true>), dim3(a.B), dim3(512), 0, s, a, h);
-      else if (a.A <= 4) SDQN_LAUNCH((head_kernel<4, false, false, false, true, true>), dim3(a.B), dim3(512), 0, s, a, h);
-      else if (a.A <= 8) SDQN_LAUNCH((head_kernel<8, false, false, false, true, true>), dim3(a.B), dim3(512), 0, s, a, h);
-      else SDQN_LAUNCH((head_kernel<MAX_ACTIONS, false, false, false, true, true>), dim3(a.B), dim3(512), 0, s, a, h);
-    } else {
-      if (a.bn) SDQN_LAUNCH((head_kernel<MAX_ACTIONS, true, false, false, false, true>), dim3(a.B), dim3(512), 0, s, a, h);
-      else if (a.A <= 4) SDQN_LAUNCH((head_kernel<4, false, false, false, false, true>), dim3(a.B), dim3(512), 0, s, a, h);
-      else if (a.A <= 8) SDQN_LAUNCH((head_kernel<8, false, false, false, false, true>), dim3(a.B), dim3(512), 0, s, a, h);
-      else SDQN_LAUNCH((head_kernel<MAX_ACTIONS, false, false, false, false, true>), dim3(a.B), dim3(512), 0, s, a, h);
-    }
-    return hipGetLastError();
-  }
-  if (h.train == 2) {                                 // --double_dqn train step (separate instantiations: the default ones are unchanged)
-    if (a.bn) SDQN_LAUNCH((head_kernel<MAX_ACTIONS, true, false, false, true>), dim3(a.B), dim3(512), 0, s, a, h);
-    else if (a.A <= 4) SDQN_LAUNCH((head_kernel<4, false, false, false, true>), dim3(a.B), dim3(512), 0, s, a, h);
-    else if (a.A <= 8) SDQN_LAUNCH((head_kernel<8, false, false, false, true>), dim3(a.B), dim3(512), 0, s, a, h);
-    else SDQN_LAUNCH((head_kernel<MAX_ACTIONS, false, false, false, true>), dim3(a.B), dim3(512), 0, s, a, h);
-    return hipGetLastError();
-  }
-  if (a.bn) SDQN_LAUNCH((head_kernel<MAX_ACTIONS, true>), dim3(a.B), dim3(512), 0, s, a, h);     // --batch_norm (not tuned per bucket)
-  else if (a.A <= 4) SDQN_LAUNCH((head_kernel<4, false>), dim3(a.B), dim3(512), 0, s, a, h);
-  else if (a.A <= 8) SDQN_LAUNCH((head_kernel<8, false>), dim3(a.B), dim3(512), 0, s, a, h);
-  else SDQN_LAUNCH((head_kernel<MAX_ACTIONS, false>), dim3(a.B), dim3(512), 0, s, a, h);
+  const int bucket = a.bn ? 3 : (a.A <= 4 ? 0 : (a.A <= 8 ? 1 : 2));
+  const bool qsys = q_system_scope && !a.bn && !h.train;                         // acting path: Q-values straight into mapped host memory
+  const bool ddqn = h.train == 2, per = h.per_w && h.train, nstep = h.nstep > 1 && h.train;   // --double_dqn, --prioritized_replay, --n_step train steps
+  static HeadKernel (*const select[9])(int) = {           // [nstep][per][ddqn], then the acting head
+    head_for<false, false, false, false>, head_for<false, true, false, false>, head_for<false, false, true, false>, head_for<false, true, true, false>,
+    head_for<false, false, false, true>, head_for<false, true, false, true>, head_for<false, false, true, true>, head_for<false, true, true, true>,
+    head_for<true, false, false, false>};
+  const HeadKernel k = select[qsys ? 8 : (nstep ? 4 : 0) + (per ? 2 : 0) + (ddqn ? 1 : 0)](bucket);
+  SDQN_LAUNCH(k, dim3(a.B), dim3(512), 0, s, a, h);
   return hipGetLastError();
 }
 

@@ -706,11 +706,6 @@ static hipError_t launch_c1w_bt2(const StepArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-// ---- plane mode (StepArgs::xp = 9 / 6): conv2 / conv3 forward, the three dgrads on packed-bf16 MFMA with weight planes ------------------
-// EXPERIMENTS BUILD ONLY.  Exact (9 partial products) it ran the B = 256 step in 262.7 us against 224.5 on fp32 MFMA, with 6 products in
-// 244.9 (one box, alternating runs; tools/exp/README.md): the launches are latency- not MFMA-bound there and the split costs VALU time.
-hipError_t launch_refresh_planes(const float*, unsigned short*, unsigned short*, hipStream_t) { return hipErrorInvalidValue; }   // (never called: no planes)
-
 // ---- float16 mode, B >= 128: forward / dgrad launches on the half block-tile routine (menu per kernel id like the fp32 one) ---------------
 #define BTH(P, BM, BN, WM, WN, D) BtCfgH<P, BM, BN, WM, WN, D>
 #define BTH128_CASE(N, P, BM, BN, WM, WN) case N: return launch_bt_h<BtCfgH<P, BM, BN, WM, WN, 2, 128> >(a, s)      /* 128-deep chunks */
@@ -739,7 +734,7 @@ hipError_t launch_kernel_bt(int id, const StepArgs& a, const LaunchTune& t, hipS
   if (a.B < 128) {                         // below the throughput regime: float16's exact-byte conv1 kernels
     // forward: one workgroup per (net, sample) pays from 2 x 48 workgroups up (fused-loop steps/s against the latency engine's tiles:
     // B = 32 18 490 vs 18 755, 48 14 833 vs 14 527, 64 13 943 vs 13 370, 100 11 198 vs 10 453); menu entry 7 = always, 6 = never
-    if (a.h16 && id == K_CONV1_FWD && (t.bt[id] == 7 || (t.bt[id] == 0 && a.B >= 48)) && t.nw_override[id] == 0 && a.idx_t == nullptr) { *handled = true; return launch_conv1_h(a, t, s); }
+    if (a.h16 && id == K_CONV1_FWD && (t.bt[id] == 7 || (t.bt[id] == 0 && a.B >= 48)) && t.nw_override[id] == 0) { *handled = true; return launch_conv1_h(a, t, s); }
     if (a.h16 == 2 && id == K_BWD1 && t.bt[id] == 7 && a.f4w_count == 0) {
       const hipError_t e1 = launch_c1w_h(a, t, s);
       if (e1 == hipErrorInvalidValue) return hipSuccess;
@@ -762,7 +757,7 @@ hipError_t launch_kernel_bt(int id, const StepArgs& a, const LaunchTune& t, hipS
       if (t.bt[id] == 2) return launch_bt_multi<BtCfgHW<Fc4WgradH, 64, 64, 2, 2, 3>, BtCfgHW<Conv3WgradH, 64, 64, 2, 2, 3>, BtCfgHW<Conv2WgradH, 64, 64, 2, 2, 3>>(a, true, true, true, s);
       return launch_bt_multi<HF4W, HC3W, HC2W>(a, true, true, true, s);
     }
-    if (id == K_CONV1_FWD && t.bt[id] >= 0 && t.bt[id] <= 2 && t.nw_override[id] == 0 && a.idx_t == nullptr) {   // one workgroup per (net, sample)
+    if (id == K_CONV1_FWD && t.bt[id] >= 0 && t.bt[id] <= 2 && t.nw_override[id] == 0) {   // one workgroup per (net, sample)
       *handled = true;
       return launch_conv1_h(a, t, s);
     }

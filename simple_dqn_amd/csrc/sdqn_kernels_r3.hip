@@ -4,13 +4,7 @@
 //   K_CONV1_FWD with LaunchTune::r3 bit 2: conv1_bf16_kernel below (bytes x 3-way bf16 split of W1 on packed-bf16 MFMA).
 //   K_BWD1 with LaunchTune::r3 bit 3 (no fc4 share in the launch): conv1_wgrad_bf16_kernel (bytes x on-the-fly 3-way bf16 split of delta1).
 //   K_CONV3_FWD with LaunchTune::r3 bit 1 (B < 128): gemm36_kernel below.
-//   K_FC4_DGRAD with LaunchTune::r3 bit 0 (B <= 32): ONE launch of 1024-thread workgroups =
-//       98 x Staged<Fc4DgradSig> tiles (16 waves each, K = 512 split over the waves)          block ids 0..97   (dispatched first)
-//     + 98 x 16 Fc4WgradWait tiles (one 32x32 tile of gW4 per wave, K = B, fused RMSProp)      block ids 98..195
-//   Same tiles, same K split, same epilogues as the separate launches -> bit-identical results; what changes is WHEN the
-//   25.7 MB read-modify-write of W4 and its RMSProp state runs: beside the latency-bound dgrad (98 of 256 CUs busy) instead of
-//   inside bwd3.  The in-place update is ordered behind the dgrad's reads of the same W4 rows by one flag word per row block
-//   (problems.h: Fc4DgradSig / Fc4WgradWait) — a write-after-read hand-off, no data crosses between the workgroups.
+//   Any id with LaunchTune::wt bits: the default launch forms with the write-through (sc1) epilogues of problems_wt.h.
 #include "gemm_engine.h"
 #include "problems_h16.h"
 #include "kernels.h"
@@ -28,7 +22,7 @@ namespace sdqn {
 //   step 16, 17 : k = kc + 32 + 2 h + (t - 16)             (one 8-byte load)
 // Same fixed-order LDS combine over the 16 waves and the same epilogue as gemm_tile.  Only the partition of the K sum changes, so
 // values differ from the 32-deep routine in the last bits (both are fp32 fmaf chains); every caller of conv3_fwd uses THIS routine
-// (train, predict, predict_one), the hoisted / batch-norm / tuning-hook variants keep the old one consistently on both nets.
+// (train, predict, predict_one), the batch-norm / tuning-hook variants keep the old one consistently on both nets.
 template <class P>
 __global__ void __launch_bounds__(1024) gemm36_kernel(const StepArgs a) {
   if constexpr (has_preload<P>::value) P::preload(a, gridDim.x, gridDim.y, gridDim.z);
@@ -108,7 +102,7 @@ constexpr int W1P_PITCH = CRS1 + 8;
 struct Conv1Args {
   const uint8_t* src; float* a1; const unsigned short* w1p[2]; const int64_t* idx;
   int B, nz, from_ring, tiles_per_net, wgs_per_net, tpw, xcd, pad_;
-  int post_off, pad2_;      // StepArgs::post_off (problems.h soff)
+  int post_off, reserved_;  // StepArgs::post_off (problems.h soff)
 };
 struct IdxIn { int64_t v[32]; };
 
@@ -118,14 +112,8 @@ __device__ __forceinline__ float div255(float s) {        // s / 255 to within a
   return fmaf(fmaf(-q, 255.0f, s), r, q);
 }
 
-// FUSED: the body runs inside the "update + next step's conv1" launch (upd_conv1_kernel below).  Target-net workgroups come first in
-// block order and need nothing from the update; ONLINE workgroups take W1 straight from theta — written by the update blocks of the
-// same launch with write-through stores — after those 64 blocks have counted themselves in (one relaxed poll by one lane, sc1 loads,
-// no fence), and split it into the three LDS planes themselves (the same split_bf16x3 as the global planes: same bits).
-struct FusedW1 { const float* theta; unsigned* ctr; unsigned target; unsigned* timeout; };
-
-template <bool IDX_IN, bool FUSED>
-__device__ __forceinline__ void conv1_bf16_body(const Conv1Args& c, const int64_t my_idx, const int cb, unsigned short* sw, const FusedW1& fw) {
+template <bool IDX_IN>
+__device__ __forceinline__ void conv1_bf16_body(const Conv1Args& c, const int64_t my_idx, const int cb, unsigned short* sw) {
   const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
   {   // every argument field in flight NOW, one wait: left alone hipcc fetches each field where it is first used (five dependent scalar trips)
     const uint8_t* f0 = c.src; float* f1 = c.a1; const unsigned short *f2 = c.w1p[0], *f3 = c.w1p[1]; const int64_t* f4 = c.idx;
@@ -134,7 +122,7 @@ __device__ __forceinline__ void conv1_bf16_body(const Conv1Args& c, const int64_
   }
   // (XCD-contiguous map inside each net: neighbouring tiles share frames and halo rows)
   const int zi = cb / c.wgs_per_net, wg = c.xcd ? xcd_tile_id(cb - zi * c.wgs_per_net, c.wgs_per_net) : cb - zi * c.wgs_per_net;
-  const int z = FUSED ? 1 - zi : zi;                                                         // 0 online, 1 target (nz = 1: online only); FUSED: target first
+  const int z = zi;                                                                          // 0 online, 1 target (nz = 1: online only)
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int M = c.B * PIX1, tiles_per_net = c.tiles_per_net, tpw = c.tpw;
   typedef uint32_t u32x2 __attribute__((ext_vector_type(2), aligned(4)));
@@ -163,37 +151,7 @@ __device__ __forceinline__ void conv1_bf16_body(const Conv1Args& c, const int64_
 #endif
   if (tile0 < tiles_per_net) load_tile(tile0, raw);                                          // in flight under the plane fill below
   SDQN_STAMP(1);
-  if (FUSED && z == 0) {
-    if (threadIdx.x == 0) {                                   // the 64 W1 blocks of THIS launch have published (bounded: never a hung GPU)
-      int spins = 0;
-      while ((int)(__hip_atomic_load(fw.ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - fw.target) < 0) {
-        __builtin_amdgcn_s_sleep(8);
-        if (++spins > 2000000) { __hip_atomic_store(fw.timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
-      }
-    }
-    __syncthreads();
-    // thread (n = t & 31, k-block = t >> 5 (+ 8 per pass)) takes 8 consecutive k of ONE map: 32 coalesced sc1 dword loads in flight
-    // (W1i is [(c,r,s)][map]: a k-row is 128 contiguous bytes over the 32 lanes), then ONE 16-byte LDS store per plane and pass
-    // (a float4-per-thread split needs 96 two-byte LDS stores per thread with 4-way bank conflicts: measured 2.6 us per workgroup)
-    const uint32_t* th = reinterpret_cast<const uint32_t*>(fw.theta + OFF1);
-    const int n = threadIdx.x & 31;
-    uint32_t wv[4][8];
-#pragma unroll
-    for (int ps = 0; ps < 4; ++ps)
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        wv[ps][j] = __hip_atomic_load(th + (8 * ((threadIdx.x >> 5) + 8 * ps) + j) * K1 + n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // sc1: past L1
-#pragma unroll
-    for (int ps = 0; ps < 4; ++ps) {
-      const int k0 = 8 * ((threadIdx.x >> 5) + 8 * ps);
-      union { uint16_t h[8]; uint4 v; } P0, P1, P2;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) split_bf16x3(__uint_as_float(wv[ps][j]), P0.h[j], P1.h[j], P2.h[j]);
-      *reinterpret_cast<uint4*>(sw + n * W1P_PITCH + k0) = P0.v;
-      *reinterpret_cast<uint4*>(sw + (K1 + n) * W1P_PITCH + k0) = P1.v;
-      *reinterpret_cast<uint4*>(sw + (2 * K1 + n) * W1P_PITCH + k0) = P2.v;
-    }
-  } else {
+  {   // this net's three weight planes -> LDS
     const uint4* wp = reinterpret_cast<const uint4*>(c.w1p[wslot(z)]);
     static_assert(3 * K1 * (CRS1 / 8) == 12 * 256, "3072 chunks of 8 bf16: 12 per thread");
     uint4 v[12];
@@ -290,8 +248,7 @@ __global__ void __launch_bounds__(256) conv1_bf16_kernel(const Conv1Args c, cons
     my_idx = *reinterpret_cast<const int64_t*>(ka + sizeof(Conv1Args) + 8 * (threadIdx.x & 31));
   }
   (void)ix;
-  const FusedW1 fw = {nullptr, nullptr, 0u, nullptr};
-  conv1_bf16_body<IDX_IN, false>(c, my_idx, (int)blockIdx.x, sw, fw);
+  conv1_bf16_body<IDX_IN>(c, my_idx, (int)blockIdx.x, sw);
 }
 
 // ---- conv1 forward for B >= 128, round 5: persistent workgroups, W1's planes in REGISTERS, the frames streamed through LDS in row chunks ----
@@ -681,8 +638,8 @@ hipError_t launch_kernel_r3(int id, const StepArgs& a, const LaunchTune& t, hipS
     const int tiles = (a.B * PIX1 + 31) / 32, tpw = a.B >= 128 ? 4 : 1, wgs = (tiles + 4 * tpw - 1) / (4 * tpw);
     Conv1Args c; c.src = a.src; c.a1 = a.a1; c.w1p[0] = a.w1p[0]; c.w1p[1] = a.w1p[1]; c.idx = a.idx;
     c.B = a.B; c.nz = a.nz; c.from_ring = a.from_ring; c.tiles_per_net = tiles; c.wgs_per_net = wgs; c.tpw = tpw; c.xcd = t.r3_xcd & 1; c.pad_ = (t.wt >> 7) & 1;
-    c.post_off = a.post_off; c.pad2_ = 0;
-    static_assert(sizeof(Conv1Args) == 80, "the index block follows 8-byte aligned at byte 80");
+    c.post_off = a.post_off; c.reserved_ = 0;
+    static_assert(sizeof(Conv1Args) == 80 && offsetof(Conv1Args, post_off) == 72, "the index block follows 8-byte aligned at byte 80");
     if (a.B >= 128 && t.bt[K_CONV1_FWD] >= 0) {           // throughput regime  (option bt:0 = -1: the per-tile kernel, the test reference)
       // round 5: persistent workgroups (one per CU), planes in registers, frames streamed in 4-row items; every workgroup of a net the same
       // number of samples where that is possible: Gz = ceil(B / ceil(B / (256 / nz)))
@@ -731,7 +688,7 @@ hipError_t launch_kernel_r3(int id, const StepArgs& a, const LaunchTune& t, hipS
   if (a.B <= 32 && !a.h16 && !a.bn && t.wt && !(id >= 0 && id < 12 && t.nw_override[id] > 0)) {       // write-through epilogues: the default launch forms with the *WT problems
     if (id == K_CONV2_FWD && (t.wt & 1) && !(t.r3 & 16)) return launch_gemm<Conv2FwdWT, 16>(a, s);
     if (id == K_FC4_FWD && (t.wt & 4)) return launch_gemm<Staged<Fc4FwdWT>, 14>(a, s);
-    if (id == K_FC4_DGRAD && (t.wt & 8) && !(t.r3 & 1)) return launch_gemm<Staged<Fc4DgradWT>, 16>(a, s);
+    if (id == K_FC4_DGRAD && (t.wt & 8)) return launch_gemm<Staged<Fc4DgradWT>, 16>(a, s);
     if (id == K_BWD3 && (t.wt & 16) && a.f4w_count > 0) return launch_multi<512, Staged<Conv3DgradWT>, 8, Conv3WgradWT, 8, Fc4WgradWT, 1>(a, true, true, s);
     if (id == K_BWD2 && (t.wt & 32) && a.f4w_count == 0) return launch_multi<512, NoProblem, 2, Conv2DgradWT, 8, Conv2WgradWT, 8>(a, true, true, s);
   }

@@ -62,7 +62,7 @@ static bool ssh_dgrad_takes(const StepArgs& a, const LaunchTune& t) {
 // float16: conv1 rides in FRONT of the forward chain (the workgroup computes its own samples' a1 from the frames: conv_ssh.h, C1) wherever the
 // chain runs and nothing asks for a conv1 launch of its own (bt:0 = 0, no nw override): then K_CONV1_FWD launches nothing
 static bool ssh_c1(const StepArgs& a, const LaunchTune& t) {
-  return ssh_takes(a, t) && t.bt[K_CONV1_FWD] == 0 && t.nw_override[K_CONV1_FWD] == 0 && a.idx_t == nullptr && a.src != nullptr;
+  return ssh_takes(a, t) && t.bt[K_CONV1_FWD] == 0 && t.nw_override[K_CONV1_FWD] == 0 && a.src != nullptr;
 }
 
 hipError_t launch_kernel_ss(int id, const StepArgs& a, const LaunchTune& t, hipStream_t s, bool* handled) {

@@ -1,15 +1,11 @@
 // update_body.h — the optimizer pass (split-K slab reduction + fc5 wgrad + RMSProp / Adam / Adadelta, deepqnetwork.py:165) as a
-// device function, so that both the plain update launch (sdqn_kernels.hip) and round 3's fused "update + next step's conv1" launch
-// (sdqn_kernels_r3.hip) run the very same code.
+// device function: the body of update_kernel (sdqn_kernels.hip).
 #pragma once
 #include <cstddef>
 #include "kernels.h"
 
 namespace sdqn {
 
-// FUSED (round 3, update + next step's conv1 in one launch): W1's new values leave with write-through (sc1) 16-byte stores, so the
-// conv1 workgroups of the SAME launch can read them with sc1 loads once the W1 blocks have signalled (no fence anywhere)
-template <bool FUSED = false>
 __device__ inline void opt_apply4(float* __restrict__ theta, float* __restrict__ st1, float* __restrict__ st2,
                                   int64_t e, const float4& gs, const UpdateArgs& u, const float4* pre = nullptr) {
   // pre: theta[e] and state[e] already fetched by the caller (issued together with the slab loads: one memory round trip less)
@@ -19,11 +15,7 @@ __device__ inline void opt_apply4(float* __restrict__ theta, float* __restrict__
   if (u.opt != 0) b = *reinterpret_cast<float4*>(st2 + e);
   w.x = opt_apply(w.x, a.x, b.x, gs.x, u); w.y = opt_apply(w.y, a.y, b.y, gs.y, u);
   w.z = opt_apply(w.z, a.z, b.z, gs.z, u); w.w = opt_apply(w.w, a.w, b.w, gs.w, u);
-  if (FUSED && e < OFF2) {
-    typedef unsigned int u4_t __attribute__((ext_vector_type(4)));
-    u4_t v; v.x = __float_as_uint(w.x); v.y = __float_as_uint(w.y); v.z = __float_as_uint(w.z); v.w = __float_as_uint(w.w);
-    __builtin_amdgcn_raw_buffer_store_b128(v, __builtin_amdgcn_make_buffer_rsrc((void*)theta, 0, NW1 * 4, 0x00020000), (int)(e * 4), 0, 16);
-  } else if (u.wt) {                                  // write-through (nothing left to flush at the kernel boundary: sdqn_kernels_r3.hip)
+  if (u.wt) {                                  // write-through (nothing left to flush at the kernel boundary: sdqn_kernels_r3.hip)
     typedef unsigned int u4_t __attribute__((ext_vector_type(4)));
     u4_t v; v.x = __float_as_uint(w.x); v.y = __float_as_uint(w.y); v.z = __float_as_uint(w.z); v.w = __float_as_uint(w.w);
     constexpr int FLAT_BYTES = (OFF5 + MAX_ACTIONS * NFC) * 4;                // (wave-uniform descriptors: base of the flat buffer + per-lane offset)
@@ -31,7 +23,6 @@ __device__ inline void opt_apply4(float* __restrict__ theta, float* __restrict__
     v.x = __float_as_uint(a.x); v.y = __float_as_uint(a.y); v.z = __float_as_uint(a.z); v.w = __float_as_uint(a.w);
     __builtin_amdgcn_raw_buffer_store_b128(v, __builtin_amdgcn_make_buffer_rsrc((void*)st1, 0, FLAT_BYTES, 0x00020000), (int)(e * 4), 0, 16);
   } else { *reinterpret_cast<float4*>(theta + e) = w; *reinterpret_cast<float4*>(st1 + e) = a; }
-  if (FUSED && e < OFF2) *reinterpret_cast<float4*>(st1 + e) = a;
   if (u.opt != 0) *reinterpret_cast<float4*>(st2 + e) = b;
   if (u.w1p && e < OFF2) {                        // conv1's bf16 planes follow W1 (e = k * 32 + n: 4 consecutive maps of one k)
     const int k = (int)(e >> 5), n = (int)(e & 31);
@@ -64,7 +55,7 @@ constexpr int FC5_BLOCKS_PER_ACTION = NFC / 4 / 32;   // 4 workgroups of 32 floa
 
 // OVF (fp16 data parallel only; compiled out of the default kernel): a half overflow in the all-reduced gradient skips the
 // whole apply step on every rank
-template <bool OVF, bool FUSED = false>
+template <bool OVF>
 __device__ __forceinline__ void update_body(const UpdateArgs& u, const int bid, const int nblocks, float4 (*part)[32], float* cost_sh) {
   const int t = threadIdx.x;
 #ifdef SDQN_TIMING
@@ -127,12 +118,7 @@ __device__ __forceinline__ void update_body(const UpdateArgs& u, const int bid, 
         *reinterpret_cast<float4*>(u.g + e) = gs;
       }
     }
-    if (applies) opt_apply4<FUSED>(u.theta, u.state, u.state2, e, gs, u, pre);
-    if (FUSED && bid < NW1 / 128) {                 // this block held 128 floats of W1: its write-through stores are out -> count it in
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (t == 0) __hip_atomic_fetch_add(u.w1_ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if (applies) opt_apply4(u.theta, u.state, u.state2, e, gs, u, pre);
     return;
   }
   const int fc5_blocks = u.A * FC5_BLOCKS_PER_ACTION;
@@ -172,7 +158,7 @@ __device__ __forceinline__ void update_body(const UpdateArgs& u, const int bid, 
         *reinterpret_cast<float4*>(u.g + e) = gs;
       }
     }
-    if (sg == 0 && u.mode != 1 && !skip_apply) opt_apply4<FUSED>(u.theta, u.state, u.state2, e, gs, u);
+    if (sg == 0 && u.mode != 1 && !skip_apply) opt_apply4(u.theta, u.state, u.state2, e, gs, u);
     return;
   }
   // fc4: g written by fc4_wgrad (or all-reduced), elementwise; skipped when fused into fc4_wgrad's epilogue
@@ -182,11 +168,11 @@ __device__ __forceinline__ void update_body(const UpdateArgs& u, const int bid, 
     for (int64_t i4 = CONV_F4 + (int64_t)(bid - first_dense) * 256 + t; i4 < OFF5 / 4; i4 += (int64_t)nb * 256) {
       const int64_t e = i4 * 4;
       const float4 gs = *reinterpret_cast<const float4*>(u.g + e);
-      if (u.mode != 1 && !skip_apply) opt_apply4<FUSED>(u.theta, u.state, u.state2, e, gs, u);
+      if (u.mode != 1 && !skip_apply) opt_apply4(u.theta, u.state, u.state2, e, gs, u);
     }
   }
   if (u.next.B > 0 && bid == first_dense) {             // next step's prep rides along (every reader of idx is done)
-    // (UpdateArgs is the first kernel parameter of both launches that run this body: its offset in the argument segment is 0)
+    // (UpdateArgs is the first kernel parameter of update_kernel: its offset in the argument segment is 0)
     const char* ka = (const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(UpdateArgs, next) + offsetof(PrepArgs, idx_in);
     for (int n = t; n < u.next.B; n += 256) {
       const int64_t i = u.next.idx_in_valid ? *reinterpret_cast<const int64_t*>(ka + 8 * (n & 31)) : u.next.idx_pinned[n];

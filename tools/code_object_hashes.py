@@ -2,7 +2,9 @@
 defines: `python tools/code_object_hashes.py simple_dqn_amd/libsdqn_hip.so [> file]`.  Two builds whose outputs are equal run the same
 kernels bit for bit — the check behind a refactoring that is supposed to move host code only.
 `--kernels` lists one line per kernel instead (sha256 of the function's own machine code): when a refactoring also REMOVES kernels that
-nothing can launch any more, every surviving kernel must keep its line (`--compare old.txt new.txt` says which lines differ)."""
+nothing can launch any more, every surviving kernel must keep its line (`--compare old.txt new.txt` says which lines differ).  A kernel
+whose template parameter list changed has a new mangled name: `--compare old.txt new.txt map.txt` reads `old_name new_name` lines and
+compares such a kernel with its old self, so a rename is neither a removal nor an addition."""
 import hashlib
 import os
 import struct
@@ -57,13 +59,20 @@ if __name__ == "__main__":
     if sys.argv[1] == "--compare":
         old = dict(l.split()[::-1] for l in open(sys.argv[2]) if l.strip())
         new = dict(l.split()[::-1] for l in open(sys.argv[3]) if l.strip())
+        renames = dict(l.split() for l in open(sys.argv[4]) if l.strip()) if len(sys.argv) > 4 else {}
+        missing = sorted(k for k, v in renames.items() if k not in old or v not in new)
+        for k in missing:
+            print("map entry without its kernels:", k, "->", renames[k])
+        old = {renames.get(k, k): h for k, h in old.items()}
+        if renames:
+            print("renamed %d (compared under their new names)" % len(renames))
         changed = sorted(k for k in new if k in old and old[k] != new[k])
         print("kernels: %d before, %d after; removed %d, added %d, CHANGED %d" % (len(old), len(new), len(set(old) - set(new)), len(set(new) - set(old)), len(changed)))
         for k in changed:
             print("changed:", k)
         for k in sorted(set(new) - set(old)):
             print("added:", k)
-        sys.exit(1 if changed else 0)
+        sys.exit(1 if changed or missing else 0)
     if sys.argv[1] == "--kernels":
         for r in code_objects(sys.argv[2], True):
             for k, h in sorted(r[3].items()):

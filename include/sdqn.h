@@ -67,6 +67,14 @@ int sdqn_sample_indices(uint32_t mt[SDQN_MT_WORDS], const uint8_t* terminals, in
 #define SDQN_MAX_N_STEP 16
 int sdqn_sample_indices_n(uint32_t mt[SDQN_MT_WORDS], const uint8_t* terminals, int64_t count, int64_t current,
                           int history_length, int n, int batch, int64_t* idx_out /*[batch]*/, int64_t* draws_out /*nullable*/);
+/* --train_envs: the rule for a LANED ring — `lanes` rings of lane_len slots side by side (lane e = slots
+ * [e lane_len, (e + 1) lane_len)) that share one fill f and one write position p.  span = f - n - history_length + 1 valid local
+ * positions per lane; per attempt ONE draw r = randint(0, lanes span - 1), lane r / span, local l = history_length + r % span,
+ * index lane lane_len + l; rejected when l + n - 1 >= p && l - history_length < p (the window straddles the write position) or
+ * terminals[index - history_length : index] holds a terminal.  A window never crosses a lane edge.  SDQN_ERR_ARG for lanes < 1,
+ * lane_len < history_length + n + 2, f > lane_len, p >= lane_len, span <= 0 and lanes without an admissible index. */
+int sdqn_sample_indices_lanes(uint32_t mt[SDQN_MT_WORDS], const uint8_t* terminals, int lanes, int64_t lane_len, int64_t fill, int64_t pos,
+                              int history_length, int n, int batch, int64_t* idx_out /*[batch]*/, int64_t* draws_out /*nullable*/);
 
 /* ---- replay memory: src/replay_memory.py ---------------------------------- */
 #define SDQN_REPLAY_HBM_MIRROR 1   /* ring master in pinned host DRAM + mirror in HBM (default) */
@@ -99,6 +107,14 @@ int sdqn_replay_sample(sdqn_replay_t h, uint32_t mt[SDQN_MT_WORDS], int64_t* idx
  * (float64 bits) where the rewards go and done where the terminals go.  A train call refuses a memory whose (n, discount, min_reward,
  * max_reward) differ from the network's (option "n_step" and its configuration).  n = 1: the standard memory. */
 int sdqn_replay_set_n_step(sdqn_replay_t h, int n, double discount, double min_reward, double max_reward);
+/* --train_envs: cut the ring into `lanes` rings of L = size / lanes slots that sdqn_env_collect fills in lockstep, one
+ * episode stream per lane.  Only on an empty memory with the HBM mirror that is not prioritized; lanes must divide size and
+ * L >= history_length + n_step + 2 (else SDQN_ERR_ARG).  From then on sampling follows sdqn_sample_indices_lanes; sdqn_replay_add,
+ * sdqn_net_act_step*, sdqn_replay_set_state and sdqn_replay_enable_priorities are SDQN_ERR_ARG; sdqn_replay_get_state reports
+ * count = lanes x fill and current = the lanes' write position.  sdqn_replay_get_lanes: (lanes, L, fill, position), lanes = 0 for a
+ * memory without lanes (any pointer may be NULL). */
+int sdqn_replay_set_lanes(sdqn_replay_t h, int lanes);
+int sdqn_replay_get_lanes(sdqn_replay_t h, int* lanes, int64_t* lane_len, int64_t* fill, int64_t* pos);
 
 /* ---- prioritized experience replay (Schaul et al. 2016, proportional) -------------------------------------------------
  * P(i) = p_i / sum of p_j over the indexes the reference sampler accepts; sample n of a batch of B draws u_n = random.random() and takes
@@ -384,6 +400,19 @@ int sdqn_net_act_step_env(sdqn_net_t h, sdqn_statebuf_t sb, sdqn_replay_t r, sdq
 int sdqn_env_eval(sdqn_net_t h, sdqn_env_t e, int num_envs, int64_t steps, double epsilon, uint64_t seed,
                   int64_t* out_steps, int64_t* out_reward, int64_t* out_caught, int64_t* out_missed, int64_t* out_episodes,
                   uint8_t* actions, int8_t* rewards, uint8_t* terminals, double* q);
+/* --train_envs: collect experience the way sdqn_env_eval plays.  `locksteps` locksteps of num_envs copies of e's game;
+ * every lockstep is the forward of sdqn_net_predict on the copies' states (skipped while epsilon >= 1, where no Q row is read) and ONE
+ * kernel that picks the actions, steps and renders the games and writes the num_envs transitions into slot `position` of each lane of the
+ * laned memory r (sdqn_replay_set_lanes(r, num_envs)): frame and (action, reward, terminal) into the HBM mirror, then two strided
+ * device-to-host copies into the pinned master, which stays a true copy.  Nothing goes host to device; the call waits once, at its end,
+ * advances the memory's fill / position and unpacks actions / rewards / terminals.  The copies live on the net handle between calls:
+ * seed >= 0 seeds them as sdqn_env_eval does (their first frames are no transitions), seed < 0 continues the stream of the last call
+ * (SDQN_ERR_ARG if there is none for num_envs).  Lockstep t of the call plays with epsilon = clamp(epsilon_start + t epsilon_step, 0, 1).
+ * The frame stored with a terminal transition is the restarted game's first frame.  Outputs and trace as sdqn_env_eval ([locksteps]
+ * rows; q is 0 where the forward was skipped); the tallies are the copies' running sums since they were seeded. */
+int sdqn_env_collect(sdqn_net_t h, sdqn_env_t e, sdqn_replay_t r, int num_envs, int64_t locksteps, double epsilon_start, double epsilon_step,
+                     int64_t seed, int64_t* out_steps, int64_t* out_reward, int64_t* out_caught, int64_t* out_missed, int64_t* out_episodes,
+                     uint8_t* actions, int8_t* rewards, uint8_t* terminals, double* q);
 
 /* per-kernel device timing (HIP events on the library stream; see option "profile_mode"), for bench.py's roofline leg.
  * kernel < 0 brackets every kernel of the step, otherwise only that kernel id. */

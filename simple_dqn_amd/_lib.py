@@ -52,6 +52,7 @@ SIGNATURES = {
     "sdqn_mt_randint": (C.c_int, [_u32p, C.c_int64, C.c_int64, _i64p]),
     "sdqn_sample_indices": (C.c_int, [_u32p, _u8p, C.c_int64, C.c_int64, C.c_int, C.c_int, _i64p, _i64p]),
     "sdqn_sample_indices_n": (C.c_int, [_u32p, _u8p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, _i64p, _i64p]),
+    "sdqn_sample_indices_lanes": (C.c_int, [_u32p, _u8p, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, _i64p, _i64p]),
     "sdqn_replay_create": (C.c_int, [C.POINTER(_vp), C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "sdqn_replay_destroy": (C.c_int, [_vp]),
     "sdqn_replay_host_ptrs": (C.c_int, [_vp, C.POINTER(_u8p), C.POINTER(_u8p), C.POINTER(_i64p), C.POINTER(_u8p)]),
@@ -64,6 +65,8 @@ SIGNATURES = {
     "sdqn_replay_upload_meta": (C.c_int, [_vp, C.c_int64, C.c_int64]),
     "sdqn_replay_sample": (C.c_int, [_vp, _u32p, _i64p, _i64p]),
     "sdqn_replay_set_n_step": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.c_double]),
+    "sdqn_replay_set_lanes": (C.c_int, [_vp, C.c_int]),
+    "sdqn_replay_get_lanes": (C.c_int, [_vp, C.POINTER(C.c_int), _i64p, _i64p, _i64p]),
     "sdqn_replay_gather": (C.c_int, [_vp, _i64p]),
     "sdqn_replay_enable_priorities": (C.c_int, [_vp, C.c_double, C.c_double]),
     "sdqn_replay_set_priority_beta": (C.c_int, [_vp, C.c_double]),
@@ -131,6 +134,8 @@ SIGNATURES = {
     "sdqn_net_act_step_env": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "sdqn_env_eval": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, C.c_double, C.c_uint64, _i64p, _i64p, _i64p, _i64p, _i64p,
                                 _u8p, C.POINTER(C.c_int8), _u8p, _f64p]),
+    "sdqn_env_collect": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int64, C.c_double, C.c_double, C.c_int64, _i64p, _i64p, _i64p, _i64p, _i64p,
+                                   _u8p, C.POINTER(C.c_int8), _u8p, _f64p]),
     "sdqn_net_profile": (C.c_int, [_vp, C.c_int, C.c_int]),
     "sdqn_net_profile_count": (C.c_int, [C.POINTER(C.c_int)]),
     "sdqn_net_profile_read": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_double), _i64p]),

@@ -59,6 +59,17 @@ class Agent:
         # ... and the environment's step inside it when the game lives in the library (CatchEnvironment): the frame is rendered on the
         # device, nothing is uploaded.  fused=False keeps the host-driven path (env.act + act_step with the screen)
         self._env_call = fused and self._one_call and hasattr(self.net, "act_step_env") and hasattr(self.env, "_h")
+        # --train_envs N: the random and train phases run N copies of the game in lockstep on the device
+        # (play_random_vectorised / train_vectorised); the replay memory becomes N lanes, one episode stream each
+        self.train_envs = int(getattr(args, "train_envs", 0) or 0)
+        if self.train_envs:
+            if not (hasattr(self.net, "collect") and hasattr(self.env, "_h") and hasattr(self.mem, "set_lanes")):
+                raise ValueError("--train_envs needs --environment catch and the device-backed replay memory")
+            if self.mem.lanes[0] != self.train_envs:
+                self.mem.set_lanes(self.train_envs)
+            self._vec_seed = int(getattr(args, "random_seed", 0) or 0)      # None until the copies have been seeded with it
+            self._vec_due = 0
+            self._vec_tally = self._vec_base = None
 
     # ---- acting ------------------------------------------------------------------------------------------
     def _greedy_action(self):
@@ -150,6 +161,42 @@ class Agent:
             if self.mem.count > self.mem.batch_size and i % self.train_frequency == 0:
                 self._learn(epoch)
             self.total_train_steps += 1
+
+    # ---- --train_envs: vectorised collection ---------------------------------------------------------------
+    def _collect(self, locksteps, exploration_rate):
+        seed, self._vec_seed = self._vec_seed, None
+        self._vec_tally = self.net.collect(self.env, self.mem, self.train_envs, locksteps, exploration_rate, seed=seed)
+        if self._vec_base is None:
+            self._vec_base = dict((k, np.zeros_like(v)) for k, v in self._vec_tally.items())
+        self._vec_rate = exploration_rate
+
+    def vectorised_tallies(self):
+        """(tallies of the copies since the last call of this method, last exploration rate): what Statistics.record_evaluation takes"""
+        now = self._vec_tally
+        delta = dict((k, now[k] - self._vec_base[k]) for k in now)
+        self._vec_base = now
+        return delta, self._vec_rate
+
+    def play_random_vectorised(self, random_steps):
+        """ceil(random_steps / train_envs) locksteps of uniform-random play in ONE library call (no forward runs).  --random_starts has
+        no meaning here: catch spawns its balls at random and a restart is the game's own."""
+        self._collect(-(-int(random_steps) // self.train_envs), 1.0)
+
+    def train_vectorised(self, train_steps, epoch=0):
+        """ceil(train_steps / train_envs) locksteps: all copies act with the exploration rate of total_train_steps, the lockstep's
+        transitions are collected, one train call (train_repeat steps) is due per train_frequency environment steps, the target net
+        is refreshed whenever total_train_steps crosses a multiple of target_steps (and at step 0), total_train_steps += train_envs."""
+        N = self.train_envs
+        for _ in range(-(-int(train_steps) // N)):
+            self._collect(1, self._epsilon.at(self.total_train_steps))
+            if self.target_steps and self.total_train_steps % self.target_steps < N:
+                self.net.update_target_network()
+            self._vec_due += N
+            while self._vec_due >= self.train_frequency:
+                if self.mem.can_sample():
+                    self._learn(epoch)
+                self._vec_due -= self.train_frequency
+            self.total_train_steps += N
 
     def test(self, test_steps, epoch=0):
         self._fresh_episode()

@@ -76,7 +76,18 @@ struct sdqn_replay_s {
   uint64_t mb_gather_gen = 0;   // device-minibatch generation the last sdqn_replay_gather left (sdqn_replay_declare_minibatch_on_device(h, UINT64_MAX) names it)
   PerState* per = nullptr;      // prioritized replay (nullptr: uniform sampling)
   NStepArgs ns = {1, 0, 0.0, 0.0, 0.0};   // --n_step (sdqn_replay_set_n_step; n = 1: standard transitions)
+  // --train_envs (sdqn_replay_set_lanes): lanes > 0 splits the ring into `lanes` rings of lane_len slots that advance
+  // together — one fill and one write position for all; count / current stay 0 and every path that reads them asks the helpers below
+  int lanes = 0; int64_t lane_len = 0, lane_fill = 0, lane_pos = 0;
 };
+// index i can be the current frame of a sampled transition: its prestate and its n steps lie in filled slots (of ONE lane)
+inline bool replay_idx_ok(const sdqn_replay_s* r, int64_t i) {
+  if (!r->lanes) return i >= r->hist && i + r->ns.n - 1 < r->count;
+  if (i < 0 || i >= r->size) return false;
+  const int64_t l = i % r->lane_len;
+  return l >= r->hist && l + r->ns.n - 1 < r->lane_fill;
+}
+inline int64_t replay_filled(const sdqn_replay_s* r) { return r->lanes ? r->lanes * r->lane_fill : r->count; }
 extern std::vector<sdqn_replay_s*> g_replays;      // live handles: sdqn_net_train_host recognises their pinned minibatch buffers
 
 struct Id128 { char b[128]; };   // ncclUniqueId is passed BY VALUE to ncclCommInitRank
@@ -186,6 +197,9 @@ struct sdqn_net_s {
   bool dp_overlap = false;        // the overlapped form is active
   int dp_probe_result = -1;       // -1 not probed, 0 timed out / failed, 1 ok (sdqn_dp_probe)
   int wt_kid = -1; unsigned long long* wt_words = nullptr;     // timing build: per-wave stamps around launches of this id (pinned: {buffer, null, blocks})
+  // --train_envs (sdqn_env_collect): the copies' records and the two state-window buffers stay here between calls, so a
+  // training run is one continuous stream of games
+  uint8_t* col_win = nullptr; void* col_recs = nullptr; int col_N = 0; int64_t col_t = 0; size_t col_state = 0;
   std::vector<void*> allocs;
 };
 #define GENCHK(x) do { hipError_t ge_ = (x); if (ge_ != hipSuccess) { set_error("%s -> %s", #x, hipGetErrorString(ge_)); return ge_ == hipErrorInvalidValue ? SDQN_ERR_ARG : SDQN_ERR_HIP; } } while (0)
@@ -210,6 +224,9 @@ enum UpdateForm { UPD_SINGLE = 0, UPD_DP_SERIAL = 1, UPD_DP_OVERLAP = 2, UPD_GRA
 int ensure_stream();
 int sample_checked(uint32_t* mt, const uint8_t* terminals, int64_t count, int64_t current, int hist,
                           int batch, int64_t* idx_out, int64_t* draws_out, int nstep = 1);
+int sample_checked_lanes(uint32_t* mt, const uint8_t* terminals, int lanes, int64_t lane_len, int64_t fill, int64_t pos, int hist,
+                         int batch, int64_t* idx_out, int64_t* draws_out, int nstep);
+int replay_sample_uniform(sdqn_replay_s* r, uint32_t* mt, int64_t* idx_out, int64_t* draws_out);   // the ring's own rule: lanes or not
 int nstep_match(const sdqn_net_s* h, const sdqn_replay_s* r);       // --n_step: the memory's (n, discount, reward clip) equal the net's
 double nstep_gamma_n(int n, double gamma);                         // gamma^n by repeated multiplication (the n-step loop's g)
 int replay_free(sdqn_replay_s* r);

@@ -19,9 +19,10 @@ enum KernelId {
   K_RESERVED_20, K_RESERVED_21, K_RESERVED_22, K_RESERVED_23,   // ids of retired round-3 launches: the numbers are public (options bt:/xcd:/nw:<id>, profile_read), nothing launches them
   K_WGRADS,    // round 4 (float16, B >= 128): fc4_wgrad (+ fused RMSProp) || conv3_wgrad || conv2_wgrad in one launch, after the block-tile dgrad chain
   K_ACT,       // round 4: the acting forward (batch of one) as ONE launch (sdqn_act.hip)
+  K_COLLECT,   // --train_envs: one lockstep of N games of catch written into the laned ring (sdqn_env.hip; not a launch of the train step)
   K_COUNT
 };
-static_assert(K_BN == 19 && K_WGRADS == 24 && K_ACT == 25 && K_COUNT == 26, "kernel ids are public numbers");
+static_assert(K_BN == 19 && K_WGRADS == 24 && K_ACT == 25 && K_COLLECT == 26 && K_COUNT == 27, "kernel ids are public numbers");
 const char* kernel_name(int id);
 
 

@@ -106,4 +106,30 @@ inline int64_t sample_indices(uint32_t* mt_state, const uint8_t* terminals, int6
   return draws;
 }
 
+// A laned ring (--train_envs): `lanes` rings of `lane_len` slots side by side, lane e = slots [e lane_len, (e + 1) lane_len),
+// all with the same fill f and write position p.  One draw per attempt over the lanes' valid local positions together:
+// r = randint(0, lanes span - 1) with span = f - nstep - hist + 1, lane r / span, local l = hist + r % span; rejected when the window
+// straddles p (the rule above, on local positions) or its prestate holds a terminal.  l >= hist and l + nstep - 1 < f keep every window
+// inside its lane.  The caller guarantees span > 0.
+inline int64_t sample_indices_lanes(uint32_t* mt_state, const uint8_t* terminals, int lanes, int64_t lane_len, int64_t fill, int64_t pos,
+                                    int hist, int batch, int64_t* out, int nstep = 1) {
+  MT mt(mt_state);
+  const int64_t span = fill - nstep - hist + 1;
+  int64_t draws = 0;
+  for (int n = 0; n < batch; ++n) {
+    for (;;) {
+      const int64_t r = mt.randint(0, lanes * span - 1);
+      ++draws;
+      const int64_t lane = r / span, l = hist + r % span, index = lane * lane_len + l;
+      if (l + nstep - 1 >= pos && l - hist < pos) continue;
+      bool any = false;
+      for (int64_t i = index - hist; i < index; ++i) any |= terminals[i] != 0;
+      if (any) continue;
+      out[n] = index;
+      break;
+    }
+  }
+  return draws;
+}
+
 }  // namespace sdqn

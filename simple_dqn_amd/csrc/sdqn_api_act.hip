@@ -183,6 +183,7 @@ extern "C" int sdqn_net_act_step(sdqn_net_t h, sdqn_statebuf_t sb, sdqn_replay_t
   ARGCHK(h && sb && screen, "NULL argument");
   ARGCHK(!r || r->frame == (int64_t)sb->frame, "the replay memory's screens (%lld bytes) and the state buffer's (%lld) differ: one screen pointer feeds both",
          (long long)(r ? r->frame : 0), (long long)sb->frame);             // (replay_memory.py:28's assert: sdqn_replay_add copies r->frame bytes)
+  ARGCHK(!r || !r->lanes, "a laned replay memory (sdqn_replay_set_lanes) is written by sdqn_env_collect only");
   int rc = sdqn_statebuf_add(sb, screen); if (rc) return rc;
   if (r) { rc = sdqn_replay_add(r, action, reward, screen, terminal); if (rc) return rc; }
   if (speculate && !h->gen && (size_t)sb->hist * sb->frame == (size_t)STATE) return predict_state_enqueue(h, sb);

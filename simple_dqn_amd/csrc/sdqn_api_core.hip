@@ -77,6 +77,35 @@ int sample_checked(uint32_t* mt, const uint8_t* terminals, int64_t count, int64_
   if (draws_out) *draws_out = d;
   return SDQN_OK;
 }
+int sample_checked_lanes(uint32_t* mt, const uint8_t* terminals, int lanes, int64_t lane_len, int64_t fill, int64_t pos, int hist,
+                         int batch, int64_t* idx_out, int64_t* draws_out, int nstep) {
+  ARGCHK(mt && terminals && idx_out, "NULL argument");
+  ARGCHK(mt[624] <= 624, "corrupt MT state (position %u)", mt[624]);
+  ARGCHK(nstep >= 1 && nstep <= SDQN_MAX_N_STEP, "n_step %d out of range [1, %d]", nstep, SDQN_MAX_N_STEP);
+  ARGCHK(batch > 0 && hist > 0, "bad sampler arguments");
+  ARGCHK(lanes >= 1 && lane_len >= hist + nstep + 2 && lanes <= (int64_t)0x7FFFFFFF / lane_len,
+         "bad lanes (%d lanes of %lld slots: a lane needs at least history_length + n_step + 2 = %d)", lanes, (long long)lane_len, hist + nstep + 2);
+  ARGCHK(fill >= 0 && fill <= lane_len && pos >= 0 && pos < lane_len, "bad lane fill %lld / position %lld (lane length %lld)",
+         (long long)fill, (long long)pos, (long long)lane_len);
+  const int64_t span = fill - nstep - hist + 1;
+  ARGCHK(span > 0, "every lane holds %lld screens: at least history_length + n_step = %d needed", (long long)fill, hist + nstep);
+  bool any_ok = false;                                                  // (as sample_checked: never spin on a ring without an admissible index)
+  for (int e = 0; e < lanes && !any_ok; ++e)
+    for (int64_t l = hist; l < hist + span && !any_ok; ++l) {
+      if (l + nstep - 1 >= pos && l - hist < pos) continue;
+      bool t = false;
+      for (int64_t k = e * lane_len + l - hist; k < e * lane_len + l; ++k) t |= terminals[k] != 0;
+      any_ok = !t;
+    }
+  ARGCHK(any_ok, "no admissible index in the lanes (every window straddles the write position or a terminal)");
+  int64_t d = sample_indices_lanes(mt, terminals, lanes, lane_len, fill, pos, hist, batch, idx_out, nstep);
+  if (draws_out) *draws_out = d;
+  return SDQN_OK;
+}
+extern "C" int sdqn_sample_indices_lanes(uint32_t* mt, const uint8_t* terminals, int lanes, int64_t lane_len, int64_t fill, int64_t pos,
+                                         int hist, int n, int batch, int64_t* idx_out, int64_t* draws_out) {
+  return sample_checked_lanes(mt, terminals, lanes, lane_len, fill, pos, hist, batch, idx_out, draws_out, n);
+}
 extern "C" int sdqn_sample_indices(uint32_t* mt, const uint8_t* terminals, int64_t count, int64_t current,
                                    int hist, int batch, int64_t* idx_out, int64_t* draws_out) {
   return sample_checked(mt, terminals, count, current, hist, batch, idx_out, draws_out);

@@ -102,6 +102,7 @@ int replay_add_commit(sdqn_replay_s* r, int64_t c) {
 }
 extern "C" int sdqn_replay_add(sdqn_replay_t r, int action, int64_t reward, const uint8_t* screen, int terminal) {
   ARGCHK(r && screen, "NULL argument");
+  ARGCHK(!r->lanes, "a laned replay memory (sdqn_replay_set_lanes) is written by sdqn_env_collect only");
   const int64_t FRAME = r->frame;
   const int64_t c = replay_add_meta(r, action, reward, terminal);   // replay_memory.py:29-32
   memcpy(r->screens + c * FRAME, screen, FRAME);
@@ -110,10 +111,13 @@ extern "C" int sdqn_replay_add(sdqn_replay_t r, int action, int64_t reward, cons
   return replay_add_commit(r, c);
 }
 extern "C" int sdqn_replay_get_state(sdqn_replay_t r, int64_t* count, int64_t* current) {
-  ARGCHK(r, "NULL handle"); if (count) *count = r->count; if (current) *current = r->current; return SDQN_OK;
+  ARGCHK(r, "NULL handle");
+  if (count) *count = replay_filled(r); if (current) *current = r->lanes ? r->lane_pos : r->current;      // (laned: N f and p)
+  return SDQN_OK;
 }
 extern "C" int sdqn_replay_set_state(sdqn_replay_t r, int64_t count, int64_t current) {
   ARGCHK(r && count >= 0 && count <= r->size && current >= 0 && current < r->size, "bad count/current");
+  ARGCHK(!r->lanes, "count / current of a laned replay memory (sdqn_replay_set_lanes) follow its locksteps and cannot be set");
   r->count = count; r->current = current; per_mark_all(r); return SDQN_OK;
 }
 extern "C" int sdqn_replay_upload(sdqn_replay_t r, int64_t first, int64_t n) {
@@ -147,12 +151,35 @@ extern "C" int sdqn_replay_upload_meta(sdqn_replay_t r, int64_t first, int64_t n
 extern "C" int sdqn_replay_sample(sdqn_replay_t r, uint32_t* mt, int64_t* idx_out, int64_t* draws_out) {
   ARGCHK(r, "NULL handle");
   if (r->per) return per_sample_host(r, mt, idx_out, draws_out);        // prioritized: by priority on the device (sdqn_per.hip)
+  return replay_sample_uniform(r, mt, idx_out, draws_out);
+}
+int replay_sample_uniform(sdqn_replay_s* r, uint32_t* mt, int64_t* idx_out, int64_t* draws_out) {
+  if (r->lanes) return sample_checked_lanes(mt, r->terminals, r->lanes, r->lane_len, r->lane_fill, r->lane_pos, r->hist, r->B, idx_out, draws_out, r->ns.n);
   return sample_checked(mt, r->terminals, r->count, r->current, r->hist, r->B, idx_out, draws_out, r->ns.n);
+}
+// --train_envs: N episode streams cannot share one ring slot by slot (a state is `hist` CONSECUTIVE slots), so the ring
+// is cut into N lanes of L = size / N slots, each a ring of its own; the lanes advance in lockstep and share fill and write position.
+extern "C" int sdqn_replay_set_lanes(sdqn_replay_t r, int lanes) {
+  ARGCHK(r, "NULL handle");
+  ARGCHK(!r->per, "a prioritized replay memory cannot be laned: the sum-tree refresh takes 4 slot ranges per launch, a lockstep writes one per lane (DESIGN.md 19)");
+  ARGCHK(!(r->flags & SDQN_REPLAY_ZERO_COPY), "lanes need the HBM mirror (SDQN_REPLAY_HBM_MIRROR): the collect kernel writes it");
+  ARGCHK(r->count == 0 && r->current == 0 && r->lane_fill == 0, "lanes can only be set on an empty replay memory");
+  ARGCHK(lanes >= 1 && r->size % lanes == 0, "%d lanes do not divide the replay memory's %lld slots", lanes, (long long)r->size);
+  ARGCHK(r->size / lanes >= r->hist + r->ns.n + 2, "lanes of %lld slots: at least history_length + n_step + 2 = %d needed",
+         (long long)(r->size / lanes), r->hist + r->ns.n + 2);
+  r->lanes = lanes; r->lane_len = r->size / lanes; r->lane_fill = r->lane_pos = 0;
+  return SDQN_OK;
+}
+extern "C" int sdqn_replay_get_lanes(sdqn_replay_t r, int* lanes, int64_t* lane_len, int64_t* fill, int64_t* pos) {
+  ARGCHK(r, "NULL handle");
+  if (lanes) *lanes = r->lanes; if (lane_len) *lane_len = r->lane_len; if (fill) *fill = r->lane_fill; if (pos) *pos = r->lane_pos;
+  return SDQN_OK;
 }
 extern "C" int sdqn_replay_set_n_step(sdqn_replay_t r, int n, double discount, double min_reward, double max_reward) {
   ARGCHK(r, "NULL handle");
   ARGCHK(n >= 1 && n <= SDQN_MAX_N_STEP, "n_step %d out of range [1, %d]", n, SDQN_MAX_N_STEP);
   ARGCHK(n < r->size - r->hist, "n_step %d needs a replay memory larger than history_length + n_step (size %lld)", n, (long long)r->size);
+  ARGCHK(!r->lanes || r->lane_len >= r->hist + n + 2, "n_step %d: lanes of %lld slots hold fewer than history_length + n_step + 2", n, (long long)r->lane_len);
   r->ns.n = n; r->ns.pad_ = 0;
   r->ns.gamma = n > 1 ? discount : 0.0; r->ns.min_reward = n > 1 ? min_reward : 0.0; r->ns.max_reward = n > 1 ? max_reward : 0.0;
   per_mark_all(r);                                                     // prioritized: validity follows the n-step rule from the next launch
@@ -175,7 +202,7 @@ int replay_push_idx(sdqn_replay_s* r, const int64_t* idx, int* slot_out, const i
   if (r->slot_busy[s]) { HIPCHK(hipEventSynchronize(r->slot_ev[r->slot_cover[s]])); r->slot_busy[s] = false; }
   int64_t* dst = r->h_idx + (size_t)s * r->B;
   for (int i = 0; i < r->B; ++i) {
-    ARGCHK(idx[i] >= r->hist && idx[i] + r->ns.n - 1 < r->count, "index %lld out of range (count %lld, n_step %d)", (long long)idx[i], (long long)r->count, r->ns.n);
+    ARGCHK(replay_idx_ok(r, idx[i]), "index %lld out of range (count %lld, n_step %d)", (long long)idx[i], (long long)replay_filled(r), r->ns.n);
     dst[i] = idx[i];
   }
   *slot_out = s; *dev = r->d_idx_view + (size_t)s * r->B;
@@ -218,8 +245,8 @@ static void snapshot_small(sdqn_replay_s* r, const int64_t* idx) {
 extern "C" int sdqn_replay_gather(sdqn_replay_t r, const int64_t* idx_host) {
   ARGCHK(r && idx_host, "NULL argument");
   for (int i = 0; i < r->B; ++i)
-    ARGCHK(idx_host[i] >= r->hist && idx_host[i] + r->ns.n - 1 < r->count, "index %lld out of range (count %lld, n_step %d)",
-           (long long)idx_host[i], (long long)r->count, r->ns.n);
+    ARGCHK(replay_idx_ok(r, idx_host[i]), "index %lld out of range (count %lld, n_step %d)",
+           (long long)idx_host[i], (long long)replay_filled(r), r->ns.n);
   per_note_gather(r, idx_host);
   if (!r->tuned_geom) {
     int slot; const int64_t* didx; int rc = replay_push_idx(r, idx_host, &slot, &didx); if (rc) return rc;
@@ -295,7 +322,7 @@ extern "C" int sdqn_replay_bench_gather_sets(sdqn_replay_t r, const int64_t* idx
   ARGCHK(r->tuned_geom, "bench_gather_sets times the 84x84x4 kernel");
   const int B = r->B;
   for (int64_t i = 0; i < (int64_t)nsets * B; ++i)
-    ARGCHK(idx_host[i] >= r->hist && idx_host[i] < r->count, "index %lld out of range (count %lld)", (long long)idx_host[i], (long long)r->count);
+    ARGCHK(replay_idx_ok(r, idx_host[i]), "index %lld out of range (count %lld)", (long long)idx_host[i], (long long)replay_filled(r));
   int64_t* d = nullptr;
   HIPCHK(hipMalloc((void**)&d, (size_t)nsets * B * sizeof(int64_t)));
   HIPCHK(hipMemcpy(d, idx_host, (size_t)nsets * B * sizeof(int64_t), hipMemcpyHostToDevice));

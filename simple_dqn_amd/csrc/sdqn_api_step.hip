@@ -547,7 +547,7 @@ extern "C" int sdqn_net_train_many(sdqn_net_t h, sdqn_replay_t r, uint32_t* mt, 
     std::vector<int64_t> gi((size_t)r->B);
     GENCHK(h->gen->reset_cost_sum());
     for (int i = 0; i < n_steps; ++i) {
-      int rc = sample_checked(mt, r->terminals, r->count, r->current, r->hist, r->B, gi.data(), nullptr, r->ns.n); if (rc) return rc;
+      int rc = replay_sample_uniform(r, mt, gi.data(), nullptr); if (rc) return rc;
       rc = gen_train_replay(h, r, gi.data()); if (rc) return rc;
     }
     int rc = replay_flush_pending(r); if (rc) return rc;
@@ -560,14 +560,14 @@ extern "C" int sdqn_net_train_many(sdqn_net_t h, sdqn_replay_t r, uint32_t* mt, 
   // sample one step ahead: step i's update launch also performs step i+1's prep (index copy + metadata gather)
   int slot = -1, next_slot = -1; const int64_t *pinned = nullptr, *next_pinned = nullptr;
   if (n_steps > 0) {
-    int rc = sample_checked(mt, r->terminals, r->count, r->current, r->hist, r->B, idx.data(), nullptr, r->ns.n); if (rc) return rc;
+    int rc = replay_sample_uniform(r, mt, idx.data(), nullptr); if (rc) return rc;
     rc = check_ring_actions(h, r, idx.data()); if (rc) return rc;
     rc = replay_push_idx(r, idx.data(), &slot, &pinned); if (rc) return rc;
   }
   for (int i = 0; i < n_steps; ++i) {
     next_pinned = nullptr;
     if (i + 1 < n_steps) {
-      int rc = sample_checked(mt, r->terminals, r->count, r->current, r->hist, r->B, idx.data(), nullptr, r->ns.n); if (rc) return rc;
+      int rc = replay_sample_uniform(r, mt, idx.data(), nullptr); if (rc) return rc;
       rc = check_ring_actions(h, r, idx.data()); if (rc) return rc;
       rc = replay_push_idx(r, idx.data(), &next_slot, &next_pinned); if (rc) return rc;
     }

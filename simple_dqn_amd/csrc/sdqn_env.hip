@@ -64,10 +64,16 @@ struct EvalArgs {
   int64_t t;                   // step number (row of the trace)
   uint8_t* tr_act; int8_t* tr_rew; uint8_t* tr_term; double* tr_q;    // [steps][N] ([A]) or all nullptr
 };
+// --train_envs: where a lockstep's transitions go — slot e lane_len + pos of the ring mirror and of its metadata
+struct CollectArgs { uint8_t* ring; MetaRec* meta; int64_t lane_len, pos; };
 // One workgroup per copy.  Thread 0: first-maximum argmax (NaN rule of sdqn_net_act_greedy), epsilon-greedy, game step, tallies, restart;
 // the view of the new frame reaches the others through LDS; all threads: shift the window into the other buffer and render the new frame
-// (restart: zeroed history in front of the first frame, as StateBuffer.reset), 16 bytes per load / store.
-__global__ void __launch_bounds__(ENV_THREADS) catch_eval_kernel(const EvalArgs a) {
+// (restart: zeroed history in front of the first frame, as StateBuffer.reset), 16 bytes per load / store.  COLLECT: the transition is
+// also a replay-memory add — the rendered frame goes to the copy's ring slot as well, (action, reward, terminal) to its MetaRec (at a
+// terminal the stored frame is the restarted game's first: no valid sample reads it); a.q == nullptr: no Q row was computed (epsilon
+// >= 1, every step explores).  The launch that seeds the copies (a.init) is no transition and writes no slot.
+template <bool COLLECT>
+__device__ __forceinline__ void catch_lockstep(const EvalArgs& a, const CollectArgs& c) {
   __shared__ int sh[4];
   const int e = blockIdx.x, tid = threadIdx.x;
   if (tid == 0) {
@@ -81,7 +87,7 @@ __global__ void __launch_bounds__(ENV_THREADS) catch_eval_kernel(const EvalArgs 
     } else {
       int best = 0; double qb = 0.0;
       for (int k = 0; k < a.A; ++k) {
-        const double qk = a.q_f64 ? reinterpret_cast<const double*>(a.q)[(size_t)e * a.A + k] : (double)reinterpret_cast<const float*>(a.q)[(size_t)e * a.A + k];
+        const double qk = !a.q ? 0.0 : a.q_f64 ? reinterpret_cast<const double*>(a.q)[(size_t)e * a.A + k] : (double)reinterpret_cast<const float*>(a.q)[(size_t)e * a.A + k];
         if (k == 0 || qk > qb || (qk != qk && qb == qb)) { best = k; qb = qk; }
         if (a.tr_q) a.tr_q[((size_t)a.t * a.N + e) * a.A + k] = qk;
       }
@@ -90,6 +96,11 @@ __global__ void __launch_bounds__(ENV_THREADS) catch_eval_kernel(const EvalArgs 
       const int terminal = r.s.terminal;
       r.steps += 1; r.reward += reward; r.caught += reward > 0; r.missed += reward < 0;
       if (a.tr_act) { const size_t o = (size_t)a.t * a.N + e; a.tr_act[o] = (uint8_t)action; a.tr_rew[o] = (int8_t)reward; a.tr_term[o] = (uint8_t)terminal; }
+      if (COLLECT) {
+        MetaRec m; m.reward = reward; m.action = (uint8_t)action; m.terminal = (uint8_t)terminal;
+        for (int k = 0; k < 6; ++k) m.pad[k] = 0;
+        c.meta[(int64_t)e * c.lane_len + c.pos] = m;
+      }
       if (terminal) { r.episodes += 1; catch_restart(r.s); restart = 1; }
     }
     a.envs[e] = r;
@@ -101,16 +112,31 @@ __global__ void __launch_bounds__(ENV_THREADS) catch_eval_kernel(const EvalArgs 
   const int frame = a.H * a.W, ch = a.H / CATCH_CELLS, cw = a.W / CATCH_CELLS;
   const size_t state = (size_t)a.hist * frame;
   const uint8_t* src = a.src + (size_t)e * state; uint8_t* dst = a.dst + (size_t)e * state;
-  if ((frame & 15) == 0 && aligned16(a.src) && aligned16(a.dst)) {
+  uint8_t* slot = (COLLECT && !a.init) ? c.ring + ((int64_t)e * c.lane_len + c.pos) * frame : nullptr;
+  if ((frame & 15) == 0 && aligned16(a.src) && aligned16(a.dst) && (!COLLECT || aligned16(c.ring))) {
     const int n16 = frame / 16, keep = (a.hist - 1) * n16;
     const uint4* s16 = reinterpret_cast<const uint4*>(src) + n16; uint4* d16 = reinterpret_cast<uint4*>(dst);
     for (int i = tid; i < keep; i += ENV_THREADS) d16[i] = restart ? make_uint4(0, 0, 0, 0) : s16[i];
-    for (int i = tid; i < n16; i += ENV_THREADS) d16[keep + i] = render_chunk(v, i * 16, a.W, ch, cw);
+    for (int i = tid; i < n16; i += ENV_THREADS) {
+      const uint4 px = render_chunk(v, i * 16, a.W, ch, cw);
+      d16[keep + i] = px;
+      if (COLLECT && slot) reinterpret_cast<uint4*>(slot)[i] = px;
+    }
   } else {
     const int keep = (a.hist - 1) * frame;
     for (int i = tid; i < keep; i += ENV_THREADS) dst[i] = restart ? (uint8_t)0 : src[frame + i];
-    for (int i = tid; i < frame; i += ENV_THREADS) dst[keep + i] = catch_pixel(v, i / a.W, i % a.W, ch, cw);
+    for (int i = tid; i < frame; i += ENV_THREADS) {
+      const uint8_t px = catch_pixel(v, i / a.W, i % a.W, ch, cw);
+      dst[keep + i] = px;
+      if (COLLECT && slot) slot[i] = px;
+    }
   }
+}
+__global__ void __launch_bounds__(ENV_THREADS) catch_eval_kernel(const EvalArgs a) { catch_lockstep<false>(a, CollectArgs()); }
+__global__ void __launch_bounds__(ENV_THREADS) catch_collect_kernel(const EvalArgs a, const CollectArgs c) { catch_lockstep<true>(a, c); }
+static hipError_t launch_collect(const EvalArgs& a, const CollectArgs& c, hipStream_t s) {
+  SDQN_LAUNCH(catch_collect_kernel, dim3(a.N), dim3(ENV_THREADS), 0, s, a, c);
+  return hipGetLastError();
 }
 
 // ---- environment handle: host only, no device needed ------------------------------------------------------------------------------
@@ -175,6 +201,7 @@ extern "C" int sdqn_net_act_step_env(sdqn_net_t h, sdqn_statebuf_t sb, sdqn_repl
                                      int* reward, int* terminal) {
   ARGCHK(h && sb && e, "NULL argument");
   ARGCHK(action >= 0 && action < CATCH_ACTIONS, "action %d out of range [0, %d)", action, CATCH_ACTIONS);
+  ARGCHK(!r || !r->lanes, "a laned replay memory (sdqn_replay_set_lanes) is written by sdqn_env_collect only");
   const int64_t FRAME = (int64_t)e->H * e->W;
   ARGCHK(sb->frame == FRAME, "the state buffer's screens (%lld bytes) and the environment's (%lld) differ", (long long)sb->frame, (long long)FRAME);
   ARGCHK(!r || r->frame == FRAME, "the replay memory's screens (%lld bytes) and the environment's (%lld) differ", (long long)(r ? r->frame : 0), (long long)FRAME);
@@ -257,6 +284,113 @@ extern "C" int sdqn_env_eval(sdqn_net_t h, sdqn_env_t e, int N, int64_t steps, d
   const int rc = body();
   if (rc && g_stream) hipStreamSynchronize(g_stream);
   hipFree(win); hipFree(recs); hipFree(tr); hipFree(trq);
+  if (rc) return rc;
+  for (int i = 0; i < N; ++i) {
+    if (out_steps) out_steps[i] = hrec[i].steps; if (out_reward) out_reward[i] = hrec[i].reward;
+    if (out_caught) out_caught[i] = hrec[i].caught; if (out_missed) out_missed[i] = hrec[i].missed;
+    if (out_episodes) out_episodes[i] = hrec[i].episodes;
+  }
+  return SDQN_OK;
+}
+
+// --train_envs: `locksteps` locksteps of num_envs copies of the game, each lockstep num_envs transitions written into the
+// laned ring r by ONE launch of catch_collect_kernel behind the forward of sdqn_net_predict (no forward while epsilon >= 1: no Q row is
+// read).  The copies' records and the two window buffers live on the net handle: seed >= 0 seeds the copies as sdqn_env_eval does and
+// renders their first frames, seed < 0 goes on where the last call stopped.  Lockstep t of the call plays with
+// epsilon = clamp(epsilon_start + t epsilon_step, 0, 1).  Per lockstep two strided device-to-host copies bring the num_envs frames and
+// MetaRecs into the pinned master, which stays a true copy of the mirror; nothing goes host to device and nothing waits until the single
+// synchronisation at the end, after which actions / rewards / terminals are unpacked.  Tallies: the copies' running sums since they were seeded.
+extern "C" int sdqn_env_collect(sdqn_net_t h, sdqn_env_t e, sdqn_replay_t r, int N, int64_t locksteps, double epsilon_start, double epsilon_step,
+                                int64_t seed, int64_t* out_steps, int64_t* out_reward, int64_t* out_caught, int64_t* out_missed,
+                                int64_t* out_episodes, uint8_t* tr_actions, int8_t* tr_rewards, uint8_t* tr_terminals, double* tr_q) {
+  ARGCHK(h && e && r, "NULL argument");
+  const int hist = h->gen ? h->cfg.history_length : C0, H = h->gen ? h->cfg.screen_height : H0, W = h->gen ? h->cfg.screen_width : W0;
+  ARGCHK(e->H == H && e->W == W, "the environment's screen (%d x %d) and the network's (%d x %d) differ", e->H, e->W, H, W);
+  ARGCHK(r->H == H && r->W == W && r->hist == hist, "the replay memory's geometry (%d x %d, history %d) and the network's (%d x %d, %d) differ", r->H, r->W, r->hist, H, W, hist);
+  ARGCHK(h->A == CATCH_ACTIONS, "the network has %d actions, catch has %d", h->A, CATCH_ACTIONS);
+  ARGCHK(N >= 1 && N <= h->B, "num_envs %d out of range [1, batch_size %d]", N, h->B);
+  ARGCHK(r->lanes == N, "the replay memory has %d lanes, num_envs is %d (sdqn_replay_set_lanes)", r->lanes, N);
+  ARGCHK(locksteps >= 0, "locksteps %lld < 0", (long long)locksteps);
+  ARGCHK(epsilon_start >= 0.0 && epsilon_start <= 1.0, "epsilon %g out of range [0, 1]", epsilon_start);
+  const bool trace = tr_actions || tr_rewards || tr_terminals || tr_q;
+  ARGCHK(!trace || (tr_actions && tr_rewards && tr_terminals && tr_q), "the trace buffers come together: all four or none");
+  const size_t state = (size_t)hist * H * W, half = (size_t)h->B * state;      // (rows N .. batch_size - 1 stay zero: the forward runs the full batch)
+  ARGCHK(seed >= 0 || (h->col_recs && h->col_N == N && h->col_state == state), "nothing to resume: the copies were never seeded for %d environments", N);
+  STREAMCHK();
+  if (!h->col_win) {
+    int rc = dalloc(h, (void**)&h->col_win, 2 * half + SRC_PAD); if (rc) return rc;
+    rc = dalloc(h, &h->col_recs, (size_t)h->B * sizeof(EvalRec)); if (rc) return rc;
+  }
+  EvalRec* recs = static_cast<EvalRec*>(h->col_recs);
+  const size_t tn = trace ? (size_t)locksteps * N : 0;
+  const int64_t FRAME = r->frame, L = r->lane_len;
+  uint8_t* tr = nullptr; double* trq = nullptr;
+  std::vector<EvalRec> hrec((size_t)N);
+  int64_t p = r->lane_pos, f = r->lane_fill, launched = 0;
+  auto body = [&]() -> int {
+    if (tn) { HIPCHK(hipMalloc((void**)&tr, 3 * tn)); HIPCHK(hipMalloc((void**)&trq, tn * h->A * sizeof(double))); }
+    EvalArgs a; memset(&a, 0, sizeof a);
+    a.q_f64 = (h->gen && h->gen->is_f64()) ? 1 : 0;
+    a.A = h->A; a.N = N; a.hist = hist; a.H = H; a.W = W; a.bpe = e->bpe; a.envs = recs;
+    CollectArgs c; c.ring = r->d_ring; c.meta = r->d_meta; c.lane_len = L; c.pos = p;
+    if (tn) { a.tr_act = tr; a.tr_rew = reinterpret_cast<int8_t*>(tr + tn); a.tr_term = tr + 2 * tn; a.tr_q = trq; }
+    if (seed >= 0) {
+      HIPCHK(hipMemsetAsync(h->col_win, 0, 2 * half + SRC_PAD, g_stream));
+      a.seed = (uint64_t)seed; a.init = 1; a.src = h->col_win + half; a.dst = h->col_win;
+      hipLaunchKernelGGL(catch_collect_kernel, dim3(N), dim3(ENV_THREADS), 0, g_stream, a, c);
+      HIPCHK(hipGetLastError());
+      a.init = 0; h->col_t = 0; h->col_N = N; h->col_state = state;
+    }
+    for (int64_t t = 0; t < locksteps; ++t) {
+      const int64_t T = h->col_t;
+      const uint8_t* cur = h->col_win + (size_t)(T & 1) * half;
+      double eps = epsilon_start + (double)t * epsilon_step;
+      eps = eps < 0.0 ? 0.0 : (eps > 1.0 ? 1.0 : eps);
+      a.q = nullptr;
+      if (eps < 1.0) {
+        if (h->gen) GENCHK(h->gen->forward_dev(cur, N));
+        else {
+          StepArgs fa = step_args(h); fa.nz = 1; fa.from_ring = 0; fa.src = cur;     // what sdqn_net_predict launches
+          int rc = run_forward(h, fa, head_args(h, 0)); if (rc) return rc;
+        }
+        a.q = h->gen ? h->gen->q_dev() : (const void*)h->q;
+      }
+      a.thresh = (uint64_t)ceil(ldexp(eps, 53));
+      a.t = t; a.src = cur; a.dst = h->col_win + (size_t)((T + 1) & 1) * half;
+      c.pos = p;
+      LAUNCH(K_COLLECT, launch_collect(a, c, g_stream));
+      h->col_t = T + 1;
+      // the lockstep's N slots, one per lane, L slots apart: one strided copy of the frames and one of the MetaRecs
+      HIPCHK(hipMemcpy2DAsync(r->screens + p * FRAME, (size_t)L * FRAME, r->d_ring + p * FRAME, (size_t)L * FRAME, (size_t)FRAME, (size_t)N,
+                              hipMemcpyDeviceToHost, g_stream));
+      HIPCHK(hipMemcpy2DAsync(r->h_meta + p, (size_t)L * sizeof(MetaRec), r->d_meta + p, (size_t)L * sizeof(MetaRec), sizeof(MetaRec), (size_t)N,
+                              hipMemcpyDeviceToHost, g_stream));
+      p = (p + 1) % L; if (f < L) ++f;
+      ++launched;
+    }
+    HIPCHK(hipMemcpyAsync(hrec.data(), recs, (size_t)N * sizeof(EvalRec), hipMemcpyDeviceToHost, g_stream));
+    if (tn) {
+      HIPCHK(hipMemcpyAsync(tr_actions, a.tr_act, tn, hipMemcpyDeviceToHost, g_stream));
+      HIPCHK(hipMemcpyAsync(tr_rewards, a.tr_rew, tn, hipMemcpyDeviceToHost, g_stream));
+      HIPCHK(hipMemcpyAsync(tr_terminals, a.tr_term, tn, hipMemcpyDeviceToHost, g_stream));
+      HIPCHK(hipMemcpyAsync(tr_q, trq, tn * h->A * sizeof(double), hipMemcpyDeviceToHost, g_stream));
+    }
+    HIPCHK(hipStreamSynchronize(g_stream));
+    return SDQN_OK;
+  };
+  const int rc = body();
+  if (rc && g_stream) hipStreamSynchronize(g_stream);
+  hipFree(tr); hipFree(trq);
+  // the positions written, newest last (a failed call: whatever reached the master is unpacked too, fill and position follow the launches made)
+  const int64_t touched = launched < L ? launched : L;
+  for (int64_t k = 0; k < touched; ++k) {
+    const int64_t q = ((p - 1 - k) % L + L) % L;
+    for (int en = 0; en < N; ++en) {
+      const int64_t sl = (int64_t)en * L + q; const MetaRec& m = r->h_meta[sl];
+      r->actions[sl] = m.action; r->rewards[sl] = m.reward; r->terminals[sl] = m.terminal;
+    }
+  }
+  r->lane_pos = p; r->lane_fill = f;
   if (rc) return rc;
   for (int i = 0; i < N; ++i) {
     if (out_steps) out_steps[i] = hrec[i].steps; if (out_reward) out_reward[i] = hrec[i].reward;

@@ -314,6 +314,7 @@ static int per_flush(sdqn_replay_s* r) {
 extern "C" int sdqn_replay_enable_priorities(sdqn_replay_t r, double alpha, double epsilon) {
   ARGCHK(r, "NULL handle");
   ARGCHK(!(r->flags & SDQN_REPLAY_ZERO_COPY), "prioritized replay needs the HBM mirror (SDQN_REPLAY_HBM_MIRROR)");
+  ARGCHK(!r->lanes, "a laned replay memory (sdqn_replay_set_lanes) cannot be prioritized: the sum-tree refresh takes 4 slot ranges per launch, a lockstep writes one per lane");
   ARGCHK(alpha >= 0.0 && alpha <= 1e6, "priority alpha %g must be >= 0", alpha);
   ARGCHK(epsilon > 0.0 && epsilon <= 1e30, "priority epsilon %g must be > 0", epsilon);
   ARGCHK(r->B <= PER_MAX_B, "prioritized replay supports batch sizes up to %d (got %d)", PER_MAX_B, r->B);

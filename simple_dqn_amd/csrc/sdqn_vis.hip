@@ -337,6 +337,7 @@ extern "C" int sdqn_net_visualize(sdqn_net_t h, sdqn_replay_t r, const int64_t* 
   ARGCHK(nbatch <= (int64_t)0xFFFFFFFF / (PIX1 * bsz), "%lld states overflow the 32-bit tie key at batch_size %lld", (long long)n, (long long)bsz);
   if (r) {
     ARGCHK(r->tuned_geom, "the replay memory is not 84x84 with history_length 4");
+    ARGCHK(!r->lanes, "filter visualisation reads getState's index math, which a laned replay memory (sdqn_replay_set_lanes) does not have");
     ARGCHK(r->count > 0, "the replay memory is empty");
     for (int64_t i = 0; i < n; ++i)
       ARGCHK(idx[i] >= 0 && idx[i] < r->count, "index %lld out of range (count %lld)", (long long)idx[i], (long long)r->count);

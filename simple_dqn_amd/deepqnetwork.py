@@ -295,6 +295,28 @@ class DeepQNetwork:
             out.update(actions=acts, rewards=rews, terminals=terms.astype(bool), q=q.astype(self._np))     # (float32 -> double -> float32: exact)
         return out
 
+    def collect(self, env, mem, num_envs, locksteps, epsilon=1.0, epsilon_step=0.0, seed=None, trace=False):
+        """--train_envs: `locksteps` locksteps of `num_envs` copies of `env`'s game, every lockstep's num_envs transitions
+        written into the laned memory `mem` (mem.set_lanes(num_envs)) by one kernel behind the batched forward (no forward while
+        epsilon >= 1); no frame goes host to device, one wait at the end.  The copies live on this network between calls: an integer
+        `seed` seeds them as evaluate() does, seed=None goes on where the last call stopped.  Lockstep t of the call plays with
+        epsilon + t epsilon_step, clamped to [0, 1].  Returns the copies' running tallies since they were seeded, as evaluate()
+        (with trace=True also actions / rewards / terminals [locksteps, num_envs] and q [locksteps, num_envs, A])."""
+        n, steps = int(num_envs), int(locksteps)
+        mem._check_mirror()                                        # (slots edited through the numpy views reach the mirror first)
+        out = dict((k, np.zeros(n, dtype=np.int64)) for k in ("steps", "reward", "caught", "missed", "episodes"))
+        tr = [None] * 4
+        if trace:
+            acts, rews = np.zeros((steps, n), np.uint8), np.zeros((steps, n), np.int8)
+            terms, q = np.zeros((steps, n), np.uint8), np.zeros((steps, n, self.num_actions), np.float64)
+            tr = [_lib.ptr(acts, C.c_uint8), _lib.ptr(rews, C.c_int8), _lib.ptr(terms, C.c_uint8), _lib.ptr(q, C.c_double)]
+        _lib.check(self._lib.sdqn_env_collect(self._h, env._h, mem._h, n, steps, float(epsilon), float(epsilon_step),
+                                              -1 if seed is None else int(seed) & 0x7FFFFFFFFFFFFFFF,
+                                              *([_lib.ptr(out[k], C.c_int64) for k in ("steps", "reward", "caught", "missed", "episodes")] + tr)))
+        if trace:
+            out.update(actions=acts, rewards=rews, terminals=terms.astype(bool), q=q.astype(self._np))
+        return out
+
     def load_weights(self, load_path):                             # :188-189
         """Own .npz snapshots, or a Neon pickle (the reference's `model.load_params`, best effort: neon_compat.py)."""
         if not str(load_path).endswith(".npz"):

@@ -20,6 +20,7 @@ _OPTIONS = {
         ("--synthetic_frame_pool", int, 256, dict(help="Synthetic environment: serve frames from a pool of this many pre-generated frames (0: generate 7 KB of random bytes every step).")),
         ("--catch_balls", int, 10, dict(help="Catch environment: balls per episode.")),
         ("--eval_envs", int, 0, dict(help="Catch environment: play the test phase on this many copies of the game at once, on the device (0: Agent.test, one environment).")),
+        ("--train_envs", int, 0, dict(help="Catch environment: collect experience from this many copies of the game at once, on the device; the replay memory becomes that many lanes (0: Agent.train, one environment).")),
         ("--screen_width", int, 84), ("--screen_height", int, 84),
     ],
     "Replay memory": [
@@ -73,7 +74,31 @@ def build_parser():
     return parser
 
 
+def check_train_envs(args):
+    """--train_envs N: what it cannot be combined with, refused before anything touches the device"""
+    n = int(getattr(args, "train_envs", 0) or 0)
+    if n < 0:
+        raise ValueError("--train_envs %d: must be >= 0" % n)
+    if n == 0:
+        return 0
+    if args.environment != "catch":
+        raise ValueError("--train_envs needs --environment catch (got %s): only the library's own game runs on the device" % args.environment)
+    if n > args.batch_size:
+        raise ValueError("--train_envs %d exceeds --batch_size %d: the copies' states are one batch of the acting forward" % (n, args.batch_size))
+    if getattr(args, "prioritized_replay", False):
+        raise ValueError("--train_envs cannot be combined with --prioritized_replay: the sum-tree refresh takes 4 slot ranges per "
+                         "launch, a lockstep writes one per lane")
+    if args.replay_size % n:
+        raise ValueError("--train_envs %d does not divide --replay_size %d: the ring is cut into equal lanes" % (n, args.replay_size))
+    need = args.history_length + int(getattr(args, "n_step", 1)) + 2
+    if args.replay_size // n < need:
+        raise ValueError("--train_envs %d: lanes of --replay_size / train_envs = %d slots, at least history_length + n_step + 2 = %d needed"
+                         % (n, args.replay_size // n, need))
+    return n
+
+
 def run(args):
+    train_envs = check_train_envs(args)
     from . import Agent, CatchEnvironment, DeepQNetwork, ReplayMemory, SyntheticEnvironment, _lib, load
     from .statistics import Statistics
     logger = logging.getLogger()
@@ -115,13 +140,21 @@ def run(args):
     if args.random_steps:                                            # :130-137
         env.setMode('train')
         stats.reset()
-        agent.play_random(args.random_steps)
+        if train_envs:
+            agent.play_random_vectorised(args.random_steps)
+            stats.record_evaluation(*agent.vectorised_tallies())
+        else:
+            agent.play_random(args.random_steps)
         stats.write(0, "random")
     for epoch in range(args.start_epoch, args.epochs):               # :140-162
         if args.train_steps:
             env.setMode('train')
             stats.reset()
-            agent.train(args.train_steps, epoch)
+            if train_envs:
+                agent.train_vectorised(args.train_steps, epoch)
+                stats.record_evaluation(*agent.vectorised_tallies())
+            else:
+                agent.train(args.train_steps, epoch)
             stats.write(epoch + 1, "train")
             if args.save_weights_prefix:
                 net.save_weights(args.save_weights_prefix + "_%d.npz" % (epoch + 1))

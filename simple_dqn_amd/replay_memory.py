@@ -107,6 +107,25 @@ class ReplayMemory:
         if h is not None and self._lib is not None:
             self._lib.sdqn_replay_destroy(h)
 
+    # ---- --train_envs ---------------------------------------------------------------------------------
+    def set_lanes(self, lanes):
+        """Cut the (empty) ring into `lanes` rings of size / lanes slots, one episode stream each, filled in lockstep by
+        DeepQNetwork.collect.  From then on add() and the count / current setters raise, count reads lanes x fill and current the
+        lanes' write position; sampling draws over all lanes and never crosses a lane edge.  A prioritized memory is refused."""
+        _lib.check(self._lib.sdqn_replay_set_lanes(self._h, int(lanes)))
+
+    @property
+    def lanes(self):
+        """(lanes, lane length, fill, write position) — (0, 0, 0, 0) for a memory without lanes"""
+        n, L, f, p = C.c_int(), C.c_int64(), C.c_int64(), C.c_int64()
+        _lib.check(self._lib.sdqn_replay_get_lanes(self._h, C.byref(n), C.byref(L), C.byref(f), C.byref(p)))
+        return n.value, L.value, f.value, p.value
+
+    def can_sample(self):
+        """a minibatch can be drawn: more than batch_size transitions, and every lane of a laned memory holds history_length + n_step"""
+        n, _, f, _ = self.lanes
+        return self.count > self.batch_size and (not n or f >= self.history_length + self.n_step)
+
     # replay_memory.py:21-22: the preallocated minibatch buffers as attributes.  Reading them fetches the last gather's states first
     # (getMinibatch() itself no longer waits for that copy: _lazy.py); the same arrays every time, aliased like the reference's
     # (the attributes ARE what getMinibatch() returns, like the reference's `return self.prestates, ..., self.poststates, ...`:
@@ -309,6 +328,7 @@ class ReplayMemory:
         """(prestates, actions, rewards, poststates, terminals); with n_step > 1 (prestates, actions, returns, poststates, dones):
         returns float64, dones bool (nstep_returns)"""
         assert self.count >= self.history_length + self.n_step
+        assert not self.lanes[0] or self.lanes[2] >= self.history_length + self.n_step
         return self.gather(self.sample_indexes())
 
     # ---- checkpoint of the ring (additive: the reference never persists its replay memory, README.md:132) -----------
@@ -317,6 +337,8 @@ class ReplayMemory:
     def save(self, path):
         """Raw dump of the filled part of the ring (header + actions, rewards, terminals, screens), streamed straight
         from the pinned master copy: 7 GB at 1 M frames, no extra host copy."""
+        if self.lanes[0]:
+            raise NotImplementedError("checkpoints of a laned replay memory (--train_envs) are not implemented")
         count, current = self._state()
         with open(path, "wb") as f:
             f.write(self._MAGIC)
@@ -326,6 +348,8 @@ class ReplayMemory:
 
     def load(self, path):
         """Restores a ring written by save() into THIS memory (same size and geometry) and refreshes the HBM mirror."""
+        if self.lanes[0]:
+            raise NotImplementedError("checkpoints of a laned replay memory (--train_envs) are not implemented")
         with open(path, "rb") as f:
             assert f.read(len(self._MAGIC)) == self._MAGIC, "not a replay-memory checkpoint"
             size, count, current, h, w, hist = np.fromfile(f, dtype=np.int64, count=6)

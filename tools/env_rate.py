@@ -2,7 +2,9 @@
   train   Agent.train env-steps/s on catch, fused act step (game stepped and rendered inside the library) vs host-driven (env.act + act_step
           with the screen), same build, same seeds
   eval    DeepQNetwork.evaluate env-steps/s at N = 32 and N = 256 (float32, float16) vs Agent.test on the same float32 net
-    python tools/env_rate.py [--rounds 7] [--train_steps 4000] [--eval_steps 400] [--json out.json]"""
+    python tools/env_rate.py [--rounds 7] [--train_steps 4000] [--eval_steps 400] [--json out.json]
+  --train_envs    instead: train-phase env-steps/s of Agent.train_vectorised — 32 copies (float32, float16), 8 copies, 256
+          copies at batch_size 256 — against the fused single-environment Agent.train, all alternated in the same process"""
 import argparse
 import json
 import os
@@ -24,15 +26,57 @@ def _args(**kw):
     return a
 
 
+def train_envs_rates(o):
+    import simple_dqn_amd as sd
+    forms = {"single_fused": dict(train_envs=0), "envs32_float32": dict(train_envs=32), "envs8_float32": dict(train_envs=8),
+             "envs256_b256_float32": dict(train_envs=256, batch_size=256, replay_size=20480), "envs32_float16": dict(train_envs=32, datatype="float16")}
+    agents = {}
+    for name, kw in forms.items():
+        a = _args(**kw)
+        random.seed(1)
+        env, mem, net = sd.CatchEnvironment(a, seed=1), sd.ReplayMemory(a.replay_size, a), sd.DeepQNetwork(3, a)
+        ag = sd.Agent(env, mem, net, a)
+        if a.train_envs:
+            ag.play_random_vectorised(2000); ag.train_vectorised(1024)
+        else:
+            ag.play_random(2000); ag.train(1000)
+        net.sync()
+        agents[name] = (ag, net, a.train_envs)
+    rates = dict((k, []) for k in forms)
+    for _ in range(o.rounds):
+        for name, (ag, net, n) in agents.items():
+            steps = o.train_steps * (4 if n else 1)
+            steps = -(-steps // n) * n if n else steps
+            t0 = time.perf_counter()
+            ag.train_vectorised(steps) if n else ag.train(steps)
+            net.sync()
+            rates[name].append(steps / (time.perf_counter() - t0))
+    out = {}
+    for name, r in rates.items():
+        out["train_" + name] = dict(median=statistics.median(r), min=min(r), max=max(r))
+    base = out["train_single_fused"]["median"]
+    for name in forms:
+        out["train_" + name]["x_single"] = out["train_" + name]["median"] / base
+    return out
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--rounds", type=int, default=7)
     p.add_argument("--train_steps", type=int, default=4000)
     p.add_argument("--eval_steps", type=int, default=400)
     p.add_argument("--json", default=None)
+    p.add_argument("--train_envs", action="store_true")
     o = p.parse_args()
     import simple_dqn_amd as sd
     out = {}
+    if o.train_envs:
+        out = train_envs_rates(o)
+        for k, v in out.items():
+            print("%-32s %s" % (k, " ".join("%s %.2f" % kv for kv in v.items())))
+        if o.json:
+            json.dump(out, open(o.json, "w"), indent=1)
+        return
     # ---- train phase: two agents, alternated
     agents = {}
     for form in ("fused", "host"):

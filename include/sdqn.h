@@ -372,7 +372,23 @@ typedef struct {
   int32_t terminal;        /* 0 / 1 */
   uint64_t rng;            /* splitmix64 counter */
 } sdqn_env_state;
-/* name = "catch"; H, W >= 12 (else SDQN_ERR_ARG); the generator starts at `seed`, the first episode is started */
+/* The game "breakout" (csrc/env_breakout.h), on the same court with the same paddle and actions: three rows of bricks
+ * (rows 1..3, pixel 64) that stay destroyed, a ball that moves diagonally (dx, dy in {-1, +1}), reflects at the side walls and the top
+ * wall, turns back from a brick it breaks (reward +1, the only reward) and from the paddle (whose left / right cell also sets dx);
+ * a ball that passes the paddle is lost, a new one spawns on row 4, an episode is balls_per_episode lost balls; the last brick
+ * broken sets all 36 again. */
+typedef struct {
+  int32_t row, col, dx, dy;  /* ball: 0..10, 0..11, -1 / +1, -1 / +1; never in a brick cell */
+  int32_t paddle;            /* left edge, 0..9 */
+  int32_t balls;             /* lost in this episode */
+  int32_t terminal;          /* 0 / 1 */
+  int32_t pad;               /* 0 */
+  uint64_t bricks;           /* bit 12 (r - 1) + c: a brick at row r in {1, 2, 3}, column c; bits 36..63 are 0 */
+  uint64_t rng;              /* splitmix64 counter */
+} sdqn_env_state_breakout;
+/* name = "catch" or "breakout"; H, W >= 12 (else SDQN_ERR_ARG); the generator starts at `seed`, the first episode is started.  Every
+ * sdqn_env_* call below serves both games; the tallies `caught` / `missed` of sdqn_env_eval / sdqn_env_collect count bricks broken /
+ * balls lost on breakout. */
 int sdqn_env_create(sdqn_env_t* h, const char* name, int screen_height, int screen_width, uint64_t seed, int balls_per_episode);
 int sdqn_env_destroy(sdqn_env_t e);
 int sdqn_env_restart(sdqn_env_t e);                                  /* new episode: balls 0, paddle 4, a new ball; does not reseed */
@@ -380,7 +396,10 @@ int sdqn_env_num_actions(sdqn_env_t e, int* n);
 int sdqn_env_step(sdqn_env_t e, int action, int* reward, int* terminal);
 int sdqn_env_screen(sdqn_env_t e, uint8_t* screen /*[H][W]*/);       /* the host-rendered frame of the current state */
 int sdqn_env_get_state(sdqn_env_t e, sdqn_env_state* st);
-int sdqn_env_set_state(sdqn_env_t e, const sdqn_env_state* st);      /* SDQN_ERR_ARG for fields out of range */
+int sdqn_env_set_state(sdqn_env_t e, const sdqn_env_state* st);      /* SDQN_ERR_ARG for fields out of range; both: SDQN_ERR_ARG on a breakout handle */
+int sdqn_env_get_state_breakout(sdqn_env_t e, sdqn_env_state_breakout* st);
+int sdqn_env_set_state_breakout(sdqn_env_t e, const sdqn_env_state_breakout* st);   /* SDQN_ERR_ARG for fields out of range; both: SDQN_ERR_ARG on a catch handle */
+int sdqn_env_name(sdqn_env_t e, const char** name);                  /* "catch" / "breakout": a static string */
 /* test hook: the frame of the current state as the render KERNEL produces it (sync) */
 int sdqn_env_render_device(sdqn_env_t e, uint8_t* screen);
 /* sdqn_net_act_step for an environment of the library: steps the game with `action`, then adds the new frame to the state buffer and,

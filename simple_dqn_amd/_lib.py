@@ -36,6 +36,12 @@ class EnvState(C.Structure):
                 ("terminal", C.c_int32), ("rng", C.c_uint64)]
 
 
+class EnvStateBreakout(C.Structure):
+    """sdqn_env_state_breakout: the whole state of one game of breakout"""
+    _fields_ = [("row", C.c_int32), ("col", C.c_int32), ("dx", C.c_int32), ("dy", C.c_int32), ("paddle", C.c_int32), ("balls", C.c_int32),
+                ("terminal", C.c_int32), ("pad", C.c_int32), ("bricks", C.c_uint64), ("rng", C.c_uint64)]
+
+
 _u8p, _i64p, _f32p, _u32p = C.POINTER(C.c_uint8), C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_uint32)
 _f64p = C.POINTER(C.c_double)
 _vp = C.c_void_p
@@ -130,6 +136,9 @@ SIGNATURES = {
     "sdqn_env_screen": (C.c_int, [_vp, _u8p]),
     "sdqn_env_get_state": (C.c_int, [_vp, C.POINTER(EnvState)]),
     "sdqn_env_set_state": (C.c_int, [_vp, C.POINTER(EnvState)]),
+    "sdqn_env_get_state_breakout": (C.c_int, [_vp, C.POINTER(EnvStateBreakout)]),
+    "sdqn_env_set_state_breakout": (C.c_int, [_vp, C.POINTER(EnvStateBreakout)]),
+    "sdqn_env_name": (C.c_int, [_vp, C.POINTER(C.c_char_p)]),
     "sdqn_env_render_device": (C.c_int, [_vp, _u8p]),
     "sdqn_net_act_step_env": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "sdqn_env_eval": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, C.c_double, C.c_uint64, _i64p, _i64p, _i64p, _i64p, _i64p,

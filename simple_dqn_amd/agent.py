@@ -56,7 +56,7 @@ class Agent:
         self.fused = fused and hasattr(self.net, "train_from_memory") and hasattr(self.mem, "_h")
         # one library call per environment transition (state-buffer add [+ ring add] [+ the next acting forward enqueued ahead of its use])
         self._one_call = hasattr(self.net, "act_step") and hasattr(self.buf, "_h")
-        # ... and the environment's step inside it when the game lives in the library (CatchEnvironment): the frame is rendered on the
+        # ... and the environment's step inside it when the game lives in the library (CatchEnvironment, BreakoutEnvironment): the frame is rendered on the
         # device, nothing is uploaded.  fused=False keeps the host-driven path (env.act + act_step with the screen)
         self._env_call = fused and self._one_call and hasattr(self.net, "act_step_env") and hasattr(self.env, "_h")
         # --train_envs N: the random and train phases run N copies of the game in lockstep on the device
@@ -64,7 +64,7 @@ class Agent:
         self.train_envs = int(getattr(args, "train_envs", 0) or 0)
         if self.train_envs:
             if not (hasattr(self.net, "collect") and hasattr(self.env, "_h") and hasattr(self.mem, "set_lanes")):
-                raise ValueError("--train_envs needs --environment catch and the device-backed replay memory")
+                raise ValueError("--train_envs needs --environment catch or breakout and the device-backed replay memory")
             if self.mem.lanes[0] != self.train_envs:
                 self.mem.set_lanes(self.train_envs)
             self._vec_seed = int(getattr(args, "random_seed", 0) or 0)      # None until the copies have been seeded with it
@@ -179,7 +179,7 @@ class Agent:
 
     def play_random_vectorised(self, random_steps):
         """ceil(random_steps / train_envs) locksteps of uniform-random play in ONE library call (no forward runs).  --random_starts has
-        no meaning here: catch spawns its balls at random and a restart is the game's own."""
+        no meaning here: the library's games spawn their balls at random and a restart is the game's own."""
         self._collect(-(-int(random_steps) // self.train_envs), 1.0)
 
     def train_vectorised(self, train_steps, epoch=0):

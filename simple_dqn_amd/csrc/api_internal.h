@@ -199,7 +199,7 @@ struct sdqn_net_s {
   int wt_kid = -1; unsigned long long* wt_words = nullptr;     // timing build: per-wave stamps around launches of this id (pinned: {buffer, null, blocks})
   // --train_envs (sdqn_env_collect): the copies' records and the two state-window buffers stay here between calls, so a
   // training run is one continuous stream of games
-  uint8_t* col_win = nullptr; void* col_recs = nullptr; int col_N = 0; int64_t col_t = 0; size_t col_state = 0;
+  uint8_t* col_win = nullptr; void* col_recs = nullptr; int col_N = 0; int64_t col_t = 0; size_t col_state = 0; int col_game = 0;    // (col_game: which game the copies play)
   std::vector<void*> allocs;
 };
 #define GENCHK(x) do { hipError_t ge_ = (x); if (ge_ != hipSuccess) { set_error("%s -> %s", #x, hipGetErrorString(ge_)); return ge_ == hipErrorInvalidValue ? SDQN_ERR_ARG : SDQN_ERR_HIP; } } while (0)

@@ -94,4 +94,30 @@ CATCH_HD int catch_epsilon_greedy(uint64_t& act_rng, uint64_t thresh, int greedy
   return greedy;
 }
 
+// the game as the generic device code of sdqn_env.hip sees it: state, view, rules, renderer and tallies of one game
+struct CatchCursor { int32_t y, x; };              // where a renderer stands; made once per 16-byte chunk, then walked byte by byte
+struct CatchGame {
+  typedef CatchState State;
+  typedef CatchView View;
+  typedef CatchCursor Cursor;
+  static constexpr int ACTIONS = CATCH_ACTIONS, CELLS = CATCH_CELLS, VIEW_WORDS = 3;
+  static constexpr const char* NAME = "catch";
+  CATCH_HD static void init(State& s, uint64_t seed) { catch_init(s, seed); }
+  CATCH_HD static void restart(State& s) { catch_restart(s); }
+  CATCH_HD static int step(State& s, int action, int bpe, int& lost) {          // caught = reward > 0, missed = reward < 0
+    const int reward = catch_step(s, action, bpe); lost = reward < 0; return reward;
+  }
+  CATCH_HD static View view(const State& s) { return catch_view(s); }
+  CATCH_HD static bool valid(const State& s) {
+    return s.row >= 0 && s.row < CATCH_CELLS && s.col >= 0 && s.col < CATCH_CELLS && s.dx >= -1 && s.dx <= 1 && s.paddle >= 0 &&
+           s.paddle <= CATCH_CELLS - CATCH_PADDLE && s.balls >= 0 && (s.terminal == 0 || s.terminal == 1);
+  }
+  CATCH_HD static void render(const View& v, uint8_t* out, int H, int W) { catch_render(v, out, H, W); }
+  CATCH_HD static void pack(const View& v, int* w) { w[0] = v.row; w[1] = v.col; w[2] = v.paddle; }
+  CATCH_HD static View unpack(const int* w) { View v; v.row = w[0]; v.col = w[1]; v.paddle = w[2]; return v; }
+  CATCH_HD static Cursor cursor(int y, int x, int, int) { Cursor c; c.y = y; c.x = x; return c; }
+  CATCH_HD static void advance(Cursor& c, int W, int, int) { if (++c.x == W) { c.x = 0; ++c.y; } }
+  CATCH_HD static uint8_t pixel(const View& v, const Cursor& c, int ch, int cw) { return catch_pixel(v, c.y, c.x, ch, cw); }
+};
+
 }  // namespace sdqn

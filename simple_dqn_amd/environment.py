@@ -75,11 +75,13 @@ class SyntheticEnvironment(Environment):
         self.mode = mode
 
 
-class CatchEnvironment(Environment):
-    """The game "catch" of the library (include/sdqn.h sdqn_env_*, csrc/env_catch.h): a ball falls through a 12 x 12 court,
-    a 3-cell paddle on the bottom row moves with actions 0 stay / 1 left / 2 right; +1 for a ball caught, -1 for a ball missed, an
-    episode is `balls_per_episode` balls.  Everything here runs on the host; `_h` lets DeepQNetwork.act_step_env / evaluate step and
-    render the game inside the library.  The generator is the environment's own (never Python's `random`)."""
+class LibraryEnvironment(Environment):
+    """A game that lives in the library (include/sdqn.h sdqn_env_*): everything here runs on the host; `_h` lets
+    DeepQNetwork.act_step_env / evaluate / collect step and render the game inside the library.  The generator is the environment's own
+    (never Python's `random`).  A subclass names its game, its state struct and state calls, and its balls-per-episode option."""
+    game = None                                                      # name given to sdqn_env_create
+    balls_option, balls_default = None, 10                           # the command line's balls-per-episode flag of this game
+    _state_struct, _get_state, _set_state = None, None, None
 
     def __init__(self, args=None, seed=0, balls_per_episode=None, screen_height=84, screen_width=84):
         from . import _lib
@@ -87,11 +89,11 @@ class CatchEnvironment(Environment):
         h = getattr(args, "screen_height", screen_height)
         w = getattr(args, "screen_width", screen_width)
         if balls_per_episode is None:
-            balls_per_episode = getattr(args, "catch_balls", 10)
+            balls_per_episode = getattr(args, self.balls_option, self.balls_default)
         self.dims = (h, w)
         self.balls_per_episode = int(balls_per_episode)
         hd = C.c_void_p()
-        _lib.check(self._lib.sdqn_env_create(C.byref(hd), b"catch", h, w, int(seed) & 0xFFFFFFFFFFFFFFFF, self.balls_per_episode))
+        _lib.check(self._lib.sdqn_env_create(C.byref(hd), self.game.encode(), h, w, int(seed) & 0xFFFFFFFFFFFFFFFF, self.balls_per_episode))
         self._h = hd
         self._screen = np.zeros(self.dims, dtype=np.uint8)
         self._screen_ok = False
@@ -103,6 +105,12 @@ class CatchEnvironment(Environment):
         h, self._h = getattr(self, "_h", None), None
         if h is not None and self._lib is not None:
             self._lib.sdqn_env_destroy(h)
+
+    def name(self):
+        """the game's name as the library reports it"""
+        n = C.c_char_p()
+        self._libmod.check(self._lib.sdqn_env_name(self._h, C.byref(n)))
+        return n.value.decode()
 
     def numActions(self):
         n = C.c_int()
@@ -136,13 +144,13 @@ class CatchEnvironment(Environment):
         self.mode = mode
 
     def get_state(self):
-        st = self._libmod.EnvState()
-        self._libmod.check(self._lib.sdqn_env_get_state(self._h, C.byref(st)))
+        st = getattr(self._libmod, self._state_struct)()
+        self._libmod.check(getattr(self._lib, self._get_state)(self._h, C.byref(st)))
         return dict((k, getattr(st, k)) for k, _ in st._fields_)
 
     def set_state(self, state):
-        st = self._libmod.EnvState(**state)
-        self._libmod.check(self._lib.sdqn_env_set_state(self._h, C.byref(st)))
+        st = getattr(self._libmod, self._state_struct)(**state)
+        self._libmod.check(getattr(self._lib, self._set_state)(self._h, C.byref(st)))
         self._terminal, self._screen_ok = bool(st.terminal), False
 
     def render_device(self):
@@ -150,6 +158,27 @@ class CatchEnvironment(Environment):
         out = np.empty(self.dims, dtype=np.uint8)
         self._libmod.check(self._lib.sdqn_env_render_device(self._h, self._libmod.ptr(out, C.c_uint8)))
         return out
+
+
+class CatchEnvironment(LibraryEnvironment):
+    """The game "catch" of the library (csrc/env_catch.h): a ball falls through a 12 x 12 court, a 3-cell paddle on the
+    bottom row moves with actions 0 stay / 1 left / 2 right; +1 for a ball caught, -1 for a ball missed, an episode is
+    `balls_per_episode` balls."""
+    game = "catch"
+    balls_option, balls_default = "catch_balls", 10
+    _state_struct, _get_state, _set_state = "EnvState", "sdqn_env_get_state", "sdqn_env_set_state"
+
+
+class BreakoutEnvironment(LibraryEnvironment):
+    """The game "breakout" of the library (csrc/env_breakout.h): the court, paddle and actions of catch, three rows of
+    bricks that stay destroyed, a ball that moves diagonally and turns back from walls, bricks and the paddle; +1 for a brick broken
+    and nothing else, an episode is `balls_per_episode` lost balls."""
+    game = "breakout"
+    balls_option, balls_default = "breakout_balls", 3
+    _state_struct, _get_state, _set_state = "EnvStateBreakout", "sdqn_env_get_state_breakout", "sdqn_env_set_state_breakout"
+
+
+LIBRARY_GAMES = {"catch": CatchEnvironment, "breakout": BreakoutEnvironment}     # --environment values that live in the library
 
 
 def _to_gray_resized(obs, height, width):

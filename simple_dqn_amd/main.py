@@ -15,12 +15,13 @@ def _flag(text):
 # (flag, type, default[, extra argparse keywords])
 _OPTIONS = {
     "Environment": [
-        ("--environment", str, "synthetic", dict(choices=["synthetic", "ale", "gym", "catch"])),
+        ("--environment", str, "synthetic", dict(choices=["synthetic", "ale", "gym", "catch", "breakout"])),
         ("--num_actions", int, 4, dict(help="Action-set size of the synthetic environment.")),
         ("--synthetic_frame_pool", int, 256, dict(help="Synthetic environment: serve frames from a pool of this many pre-generated frames (0: generate 7 KB of random bytes every step).")),
         ("--catch_balls", int, 10, dict(help="Catch environment: balls per episode.")),
-        ("--eval_envs", int, 0, dict(help="Catch environment: play the test phase on this many copies of the game at once, on the device (0: Agent.test, one environment).")),
-        ("--train_envs", int, 0, dict(help="Catch environment: collect experience from this many copies of the game at once, on the device; the replay memory becomes that many lanes (0: Agent.train, one environment).")),
+        ("--breakout_balls", int, 3, dict(help="Breakout environment: lost balls per episode.")),
+        ("--eval_envs", int, 0, dict(help="Catch / breakout environment: play the test phase on this many copies of the game at once, on the device (0: Agent.test, one environment).")),
+        ("--train_envs", int, 0, dict(help="Catch / breakout environment: collect experience from this many copies of the game at once, on the device; the replay memory becomes that many lanes (0: Agent.train, one environment).")),
         ("--screen_width", int, 84), ("--screen_height", int, 84),
     ],
     "Replay memory": [
@@ -81,8 +82,9 @@ def check_train_envs(args):
         raise ValueError("--train_envs %d: must be >= 0" % n)
     if n == 0:
         return 0
-    if args.environment != "catch":
-        raise ValueError("--train_envs needs --environment catch (got %s): only the library's own game runs on the device" % args.environment)
+    from .environment import LIBRARY_GAMES
+    if args.environment not in LIBRARY_GAMES:
+        raise ValueError("--train_envs needs --environment catch or breakout (got %s): only the library's own games run on the device" % args.environment)
     if n > args.batch_size:
         raise ValueError("--train_envs %d exceeds --batch_size %d: the copies' states are one batch of the acting forward" % (n, args.batch_size))
     if getattr(args, "prioritized_replay", False):
@@ -99,7 +101,8 @@ def check_train_envs(args):
 
 def run(args):
     train_envs = check_train_envs(args)
-    from . import Agent, CatchEnvironment, DeepQNetwork, ReplayMemory, SyntheticEnvironment, _lib, load
+    from . import Agent, DeepQNetwork, ReplayMemory, SyntheticEnvironment, _lib, load
+    from .environment import LIBRARY_GAMES
     from .statistics import Statistics
     logger = logging.getLogger()
     logger.setLevel(args.log_level)
@@ -113,8 +116,8 @@ def run(args):
     if args.environment == "gym":
         from .environment import GymEnvironment                    # needs gymnasium (or gym); not part of this image
         env = GymEnvironment(args.game, args)
-    elif args.environment == "catch":                                # the library's own game (--num_actions is ignored: it has 3)
-        env = CatchEnvironment(args, seed=args.random_seed or 0)
+    elif args.environment in LIBRARY_GAMES:                          # the library's own games (--num_actions is ignored: they have 3)
+        env = LIBRARY_GAMES[args.environment](args, seed=args.random_seed or 0)
     else:
         env = SyntheticEnvironment(args, num_actions=args.num_actions, seed=args.random_seed or 0, frame_pool=args.synthetic_frame_pool)
     mem = ReplayMemory(args.replay_size, args)                       # main.py:103-106
@@ -161,9 +164,9 @@ def run(args):
         if args.test_steps:
             env.setMode('test')
             stats.reset()
-            if getattr(args, "eval_envs", 0) > 0:                    # vectorised on the device (catch only)
+            if getattr(args, "eval_envs", 0) > 0:                    # vectorised on the device (the library's games only)
                 if not hasattr(env, "_h"):
-                    raise ValueError("--eval_envs needs --environment catch")
+                    raise ValueError("--eval_envs needs --environment catch or breakout")
                 stats.record_evaluation(net.evaluate(env, args.eval_envs, -(-args.test_steps // args.eval_envs), args.exploration_rate_test,
                                                      seed=(args.random_seed or 0) + epoch + 1), args.exploration_rate_test)
             else:

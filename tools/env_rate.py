@@ -3,6 +3,8 @@
           with the screen), same build, same seeds
   eval    DeepQNetwork.evaluate env-steps/s at N = 32 and N = 256 (float32, float16) vs Agent.test on the same float32 net
     python tools/env_rate.py [--rounds 7] [--train_steps 4000] [--eval_steps 400] [--json out.json]
+  --environment catch|breakout   the library game the rates are taken on (default catch); `--environment both` instead
+          alternates the two games in one process: DeepQNetwork.evaluate at N = 32 and the --train_envs 32 train phase, float32
   --train_envs    instead: train-phase env-steps/s of Agent.train_vectorised — 32 copies (float32, float16), 8 copies, 256
           copies at batch_size 256 — against the fused single-environment Agent.train, all alternated in the same process"""
 import argparse
@@ -17,9 +19,17 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+GAME = "catch"                             # --environment
+
+
+def _env(sd, a, seed=1, game=None):
+    from simple_dqn_amd.environment import LIBRARY_GAMES
+    return LIBRARY_GAMES[game or GAME](a, seed=seed)
+
+
 def _args(**kw):
     from simple_dqn_amd.main import build_parser
-    a = build_parser().parse_args(["--environment", "catch"])
+    a = build_parser().parse_args(["--environment", GAME])
     a.replay_size, a.exploration_decay_steps, a.target_steps, a.random_seed = 20000, 10000, 500, 1
     for k, v in kw.items():
         setattr(a, k, v)
@@ -34,7 +44,7 @@ def train_envs_rates(o):
     for name, kw in forms.items():
         a = _args(**kw)
         random.seed(1)
-        env, mem, net = sd.CatchEnvironment(a, seed=1), sd.ReplayMemory(a.replay_size, a), sd.DeepQNetwork(3, a)
+        env, mem, net = _env(sd, a), sd.ReplayMemory(a.replay_size, a), sd.DeepQNetwork(3, a)
         ag = sd.Agent(env, mem, net, a)
         if a.train_envs:
             ag.play_random_vectorised(2000); ag.train_vectorised(1024)
@@ -60,8 +70,44 @@ def train_envs_rates(o):
     return out
 
 
+def both_games_rates(o):
+    """evaluate (N = 32) and the --train_envs 32 train phase on catch and on breakout, alternated in one process, float32"""
+    import simple_dqn_amd as sd
+    games = ("catch", "breakout")
+    ev, tr = {}, {}
+    for g in games:
+        a = _args(batch_size=32, environment=g)
+        net, env = sd.DeepQNetwork(3, a), _env(sd, a, game=g)
+        net.evaluate(env, 32, 20)
+        ev[g] = (net, env)
+        a = _args(train_envs=32, environment=g)
+        random.seed(1)
+        env, mem, net = _env(sd, a, game=g), sd.ReplayMemory(a.replay_size, a), sd.DeepQNetwork(3, a)
+        ag = sd.Agent(env, mem, net, a)
+        ag.play_random_vectorised(2000); ag.train_vectorised(1024)
+        net.sync()
+        tr[g] = (ag, net)
+    rates = dict(("%s_%s" % (k, g), []) for k in ("evaluate_n32", "train_envs32") for g in games)
+    for r in range(o.rounds):
+        for g in games:
+            net, env = ev[g]
+            t0 = time.perf_counter()
+            net.evaluate(env, 32, o.eval_steps, 0.05, r)
+            rates["evaluate_n32_" + g].append(32 * o.eval_steps / (time.perf_counter() - t0))
+        for g in games:
+            ag, net = tr[g]
+            steps = o.train_steps * 4
+            t0 = time.perf_counter()
+            ag.train_vectorised(steps)
+            net.sync()
+            rates["train_envs32_" + g].append(steps / (time.perf_counter() - t0))
+    return dict((k, dict(median=statistics.median(v), min=min(v), max=max(v))) for k, v in rates.items())
+
+
 def main():
+    global GAME
     p = argparse.ArgumentParser()
+    p.add_argument("--environment", default="catch", choices=["catch", "breakout", "both"])
     p.add_argument("--rounds", type=int, default=7)
     p.add_argument("--train_steps", type=int, default=4000)
     p.add_argument("--eval_steps", type=int, default=400)
@@ -70,6 +116,14 @@ def main():
     o = p.parse_args()
     import simple_dqn_amd as sd
     out = {}
+    if o.environment == "both":
+        out = both_games_rates(o)
+        for k, v in out.items():
+            print("%-32s %s" % (k, " ".join("%s %.1f" % kv for kv in v.items())))
+        if o.json:
+            json.dump(out, open(o.json, "w"), indent=1)
+        return
+    GAME = o.environment
     if o.train_envs:
         out = train_envs_rates(o)
         for k, v in out.items():
@@ -82,7 +136,7 @@ def main():
     for form in ("fused", "host"):
         a = _args()
         random.seed(1)
-        env, mem, net = sd.CatchEnvironment(a, seed=1), sd.ReplayMemory(a.replay_size, a), sd.DeepQNetwork(3, a)
+        env, mem, net = _env(sd, a), sd.ReplayMemory(a.replay_size, a), sd.DeepQNetwork(3, a)
         ag = sd.Agent(env, mem, net, a)
         ag._env_call = form == "fused"
         ag.play_random(2000)
@@ -111,7 +165,7 @@ def main():
     for dt in ("float32", "float16"):
         for n in (32, 256):
             a = _args(batch_size=n, datatype=dt)
-            net, env = sd.DeepQNetwork(3, a), sd.CatchEnvironment(a, seed=1)
+            net, env = sd.DeepQNetwork(3, a), _env(sd, a)
             net.evaluate(env, n, 20)
             t = []
             for r in range(o.rounds):

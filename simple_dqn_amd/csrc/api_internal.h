@@ -172,7 +172,7 @@ struct sdqn_net_s {
   const int64_t* host_idx_cur = nullptr;   // ring paths: host copy of the indexes of the step being enqueued (valid during run_train only)
   int r3_xcd = 2;                          // XCD-contiguous tile maps of the round-3 kernels: bit 0 conv1_fwd (bf16), bit 1 conv1_wgrad (bf16)
   bool prep_inline = true;                 // B <= 32: the next step's indexes ride in the update launch's kernel arguments (no PCIe read in its prep block)
-  int wt = 511;                            // write-through epilogue stores, bit per launch (kernels.h: LaunchTune::wt; bit 8 = the update kernel)
+  int wt = WT_ALL;                         // write-through epilogue stores, bit per launch (kernels.h: WriteThrough)
   int conv1w_bf16 = 1;                 // round 3: conv1_wgrad on packed-bf16 MFMA (bytes x on-the-fly bf16 split of delta1)
   bool conv3_c36 = true;                   // round 3: conv3_fwd on 36-deep K-chunks (one chunk per wave; sdqn_kernels_r3.hip)
   bool fused_launches = true;              // independent backward stages share one launch (K_BWD3, K_BWD2)
@@ -252,13 +252,19 @@ StepArgs step_args(sdqn_net_s* h);
 HeadArgs head_args(sdqn_net_s* h, int train);
 int join_comm(sdqn_net_s* h);
 BnArgs bn_args(sdqn_net_s* h, const StepArgs& a, int layer, int train);
-hipError_t launch_tuned(sdqn_net_s* h, int id, StepArgs a, hipStream_t s, int r3 = 0);
+hipError_t launch_tuned(sdqn_net_s* h, int id, StepArgs a, hipStream_t s, int variant = 0);    // variant: LaunchVariant bits
 int run_forward(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd);
 UpdateArgs make_update_args(sdqn_net_s* h, const StepArgs& a);
 StepStructure step_structure(const sdqn_net_s* h);
 UpdateForm update_form(const sdqn_net_s* h);
 int run_train(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd, const PrepArgs* next = nullptr);
-int read_cost(sdqn_net_s* h, float* cost_out);
+int read_cost(sdqn_net_s* h, float* cost_out);                      // either path; ends with per_check_all
+int read_mean_cost(sdqn_net_s* h, int n_steps, float* mean_cost);
+int predict_forward_tuned(sdqn_net_s* h, const uint8_t* states, const HeadArgs& hd, int B = 0);   // B = 0: the net's batch
+int predict_forward(sdqn_net_s* h, const uint8_t* states, int rows, const void** q, int* q_f64);
+StepArgs ring_step_args(sdqn_net_s* h, const sdqn_replay_s* r);
+int run_ring_step(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* host_idx, const HeadArgs& hd, const PrepArgs* next = nullptr);
+int check_replay_geometry(const sdqn_net_s* h, const sdqn_replay_s* r);
 bool act_sum_partials(const float* part, int A, float* q_out);
 const uint8_t* statebuf_window(sdqn_statebuf_s* s);
 int statebuf_advance(sdqn_statebuf_s* s, uint8_t** host_frame, uint8_t** dev_slot);
@@ -267,9 +273,6 @@ bool act_trace();
 int predict_state_collect(sdqn_net_s* h, float* q_out);
 PrepArgs prep_args(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* pinned_idx);
 int check_ring_actions(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* idx);
-int train_replay_slot(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* pinned_idx, bool do_prep = true,
-                             const int64_t* next_pinned = nullptr, double* zero8 = nullptr);
-int gen_train_replay(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* idx_host);
 // prioritized replay (sdqn_per.hip)
 int per_free(PerState* p);
 void per_mark(sdqn_replay_s* r, int64_t first, int64_t n);

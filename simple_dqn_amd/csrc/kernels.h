@@ -153,15 +153,28 @@ __device__ inline float opt_apply(float w, float& s1, float& s2, float gsum, con
 }
 #endif
 
+// LaunchTune::variant — the launch variants the step's orchestration asks for (sdqn_api_step.hip decides, launch_kernel's translation
+// units test); bit 0 is unused
+enum LaunchVariant {
+  LV_CONV3_C36 = 2,           // conv3_fwd on 36-deep K-chunks (sdqn_kernels_r3.hip)
+  LV_CONV1_FWD_BF16 = 4,      // conv1_fwd on packed-bf16 MFMA (sdqn_kernels_r3.hip)
+  LV_CONV1_WGRAD_BF16 = 8,    // conv1_wgrad on packed-bf16 MFMA (sdqn_kernels_r3.hip)
+  LV_C1W_IN_WGRADS = 16,      // float16, B >= 128: conv1_wgrad rides in the K_WGRADS launch and K_BWD1 launches nothing (sdqn_kernels_bt.hip)
+  LV_C1W_FIRST = 32,          // ... with its workgroups first in the block-id order
+};
+// LaunchTune::wt / option "wt" — write-through (sc1) epilogue stores, one bit per launch (WT_UPDATE reaches its kernel as UpdateArgs::wt)
+enum WriteThrough {
+  WT_CONV2_FWD = 1, WT_CONV3_FWD = 2, WT_FC4_FWD = 4, WT_FC4_DGRAD = 8, WT_BWD3 = 16, WT_BWD2 = 32, WT_CONV1_WGRAD = 64, WT_CONV1_FWD = 128,
+  WT_UPDATE = 256, WT_ALL = 511
+};
 // host-side launch choices that never reach a kernel (kept out of StepArgs: kernel-argument bytes are not free)
 struct LaunchTune {
   int nw_override[12];      // tuning hook: waves per tile for kernel id i (0 = built-in choice)
   const int64_t* host_idx;  // ring paths, B <= 32: this step's sampled indexes in HOST memory (they ride in the kernel arguments of conv1_bf16_kernel)
   int r3_xcd;               // round-3 kernels' XCD-contiguous tile maps: bit 0 conv1_fwd (bf16), bit 1 conv1_wgrad (bf16)
-  int wt;                   // write-through (sc1) epilogue stores per launch: 1 conv2_fwd, 2 conv3_fwd, 4 fc4_fwd, 8 fc4_dgrad, 16 bwd3, 32 bwd2, 64 conv1_wgrad, 128 conv1_fwd
+  int wt;                   // WriteThrough bits
   int bt[K_COUNT];          // B >= 128, float32: block-tile engine (sdqn_kernels_bt.hip) per kernel id; 0 = built-in block shape, n > 0 = menu entry, < 0 = latency engine
-  int r3;                   // round-3 launch variants (sdqn_kernels_r3.hip); bit 1: conv3_fwd on 36-deep K-chunks; bit 2: conv1_fwd on packed-bf16 MFMA; bit 3: conv1_wgrad on packed-bf16 MFMA;
-                            // bits 4 / 5 (float16, B >= 128): conv1_wgrad rides in the K_WGRADS launch / its workgroups first (sdqn_kernels_bt.hip); bit 0 is unused
+  int variant;              // LaunchVariant bits
 };
 hipError_t launch_kernel(int id, const StepArgs& a, const LaunchTune& t, hipStream_t s);     // the GEMM-shaped stages (single or multi-problem launches)
 hipError_t launch_head(const StepArgs& a, const HeadArgs& h, hipStream_t s, bool q_system_scope = false);   // q_system_scope: h.q is mapped host memory (acting path)

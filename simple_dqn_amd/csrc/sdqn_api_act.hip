@@ -101,12 +101,11 @@ int predict_state_enqueue(sdqn_net_s* h, sdqn_statebuf_s* sb) {
     h->spec_pending = true; h->spec_sb = sb; h->spec_gen = sb->gen;
     return SDQN_OK;
   }
-  StepArgs a = step_args(h); a.B = 1; a.nz = 1; a.from_ring = 0; a.src = statebuf_window(sb);   // batch of one, read in place
   HeadArgs hd = head_args(h, 0);
   const bool direct = !h->bn;                                    // (--batch_norm: the plain head + a copy, as before)
   if (direct) hd.q = h->q_host_dev + h->q_slot * Q_SLOT_FLOATS;
   h->head_q_system = direct;
-  const int rc = run_forward(h, a, hd);
+  const int rc = predict_forward_tuned(h, statebuf_window(sb), hd, 1);      // batch of one, read in place
   h->head_q_system = false;
   if (rc) return rc;
   if (!direct) HIPCHK(hipMemcpyAsync(h->q_host + h->q_slot * Q_SLOT_FLOATS, h->q, (size_t)h->A * 4, hipMemcpyDeviceToHost, g_stream));

@@ -506,7 +506,7 @@ extern "C" int sdqn_net_set_option(sdqn_net_t h, const char* name, int value) {
   }
   else if (!strcmp(name, "fused_launches")) h->fused_launches = value != 0;
   else if (!strcmp(name, "conv1_bf16")) h->conv1_bf16 = value != 0;     // 0: conv1_fwd on the fp32-MFMA engine (round-2 kernel)
-  else if (!strcmp(name, "wt")) h->wt = value;
+  else if (!strcmp(name, "wt")) h->wt = value;                       // WriteThrough bits (kernels.h)
   else if (!strcmp(name, "prep_inline")) h->prep_inline = value != 0;
   else if (!strcmp(name, "r3_xcd")) h->r3_xcd = value;
   else if (!strcmp(name, "conv1w_bf16")) h->conv1w_bf16 = value;   // 0: conv1_wgrad on the fp32-MFMA engine (round-2 kernel)
@@ -594,15 +594,15 @@ extern "C" int sdqn_debug_time_kernel(sdqn_net_t h, sdqn_replay_t r, const int64
   HIPCHK(hipMemset(d, 0, (size_t)max_blocks * 64));
   int slot; const int64_t* pinned; int rc = replay_push_idx(r, idx_host, &slot, &pinned); if (rc) return rc;
   PrepArgs p = prep_args(h, r, pinned); HIPCHK(launch_prep(p, g_stream));
-  StepArgs a = step_args(h); a.from_ring = 1; a.src = r->d_ring; a.idx = h->d_idx;
+  StepArgs a = ring_step_args(h, r);
   HIPCHK(hipStreamSynchronize(g_stream));
   HIPCHK(set_timing_buffer(d));
   // kernel ids >= 100: round-3 variants — 100 conv1 on bf16 MFMA (warm: third launch on the same indexes), 101 the same, ONE launch
   // (frames never touched before: HBM + TLB cold, what a train step sees), 102 conv3_fwd on 36-deep chunks
   for (int rep = 0; rep < (kernel == 101 ? 1 : 3); ++rep) {                         // last launch's stamps survive
     if (kernel == K_HEAD) { HeadArgs hd = head_args(h, 1); HIPCHK(launch_head(a, hd, g_stream)); }
-    else if (kernel == 100 || kernel == 101) { h->host_idx_cur = idx_host; const hipError_t le = launch_tuned(h, K_CONV1_FWD, a, g_stream, 4); h->host_idx_cur = nullptr; HIPCHK(le); }
-    else if (kernel == 102) HIPCHK(launch_tuned(h, K_CONV3_FWD, a, g_stream, 2));
+    else if (kernel == 100 || kernel == 101) { h->host_idx_cur = idx_host; const hipError_t le = launch_tuned(h, K_CONV1_FWD, a, g_stream, LV_CONV1_FWD_BF16); h->host_idx_cur = nullptr; HIPCHK(le); }
+    else if (kernel == 102) HIPCHK(launch_tuned(h, K_CONV3_FWD, a, g_stream, LV_CONV3_C36));
     else if (kernel == 104) { UpdateArgs u = make_update_args(h, a); u.mode = 0; u.bsz = (float)h->B; u.skip_fc4 = 1; HIPCHK(launch_update(u, g_stream)); }
     else HIPCHK(launch_tuned(h, kernel, a, g_stream));
   }

@@ -72,12 +72,12 @@ BnArgs bn_args(sdqn_net_s* h, const StepArgs& a, int layer, int train) {
 }
 // tuning hook: per-launch XCD map mask override (sdqn_net_set_option "xcd:<id>", value = mask + 1; 0 = built-in)
 #define XCD_TUNE(ARGS, KID) do { if (h->xcd_mask[KID] > 0) (ARGS).xcd_map = h->xcd_mask[KID] - 1; } while (0)
-hipError_t launch_tuned(sdqn_net_s* h, int id, StepArgs a, hipStream_t s, int r3) {
+hipError_t launch_tuned(sdqn_net_s* h, int id, StepArgs a, hipStream_t s, int variant) {
   XCD_TUNE(a, id);
   LaunchTune t;
   for (int i = 0; i < 12; ++i) t.nw_override[i] = h->nw_override[i];
   for (int i = 0; i < K_COUNT; ++i) t.bt[i] = h->bt_on ? h->bt[i] : -1;
-  t.r3 = r3; t.host_idx = h->host_idx_cur; t.r3_xcd = h->r3_xcd; t.wt = h->wt;
+  t.variant = variant; t.host_idx = h->host_idx_cur; t.r3_xcd = h->r3_xcd; t.wt = h->wt;
   return launch_kernel(id, a, t, s);
 }
 int run_forward(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd) {
@@ -101,11 +101,11 @@ int run_forward(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd) {
   // XCD-contiguous tile map where it wins time (tools/sweep_xcd.py, tools/ab_options.py): conv1_fwd +0.5 %, conv2_fwd
   // +0.2 %, fc4_fwd +0.6 % of the step rate; slower for conv3_fwd, fc4_dgrad and every backward launch
   StepArgs fm = a; fm.xcd_map = 1;
-  LAUNCH(K_CONV1_FWD, launch_tuned(h, K_CONV1_FWD, fm, g_stream, (h->conv1_bf16 && h->nw_override[K_CONV1_FWD] == 0) ? 4 : 0));
+  LAUNCH(K_CONV1_FWD, launch_tuned(h, K_CONV1_FWD, fm, g_stream, (h->conv1_bf16 && h->nw_override[K_CONV1_FWD] == 0) ? LV_CONV1_FWD_BF16 : 0));
   { StepArgs f2 = fm; if (h->B >= 128) f2.xcd_map = a.xcd_map;          // block-tile routines (B >= 128): conv2_fwd 28.8 / 8.8 us round-robin, 28.9 / 9.0 on the map (fp32 / float16)
     LAUNCH(K_CONV2_FWD, launch_tuned(h, K_CONV2_FWD, f2, g_stream)); }
   { StepArgs f3 = fm; f3.xcd_map = a.xcd_map;
-    const int c36 = (h->conv3_c36 && h->nw_override[K_CONV3_FWD] == 0) ? 2 : 0;
+    const int c36 = (h->conv3_c36 && h->nw_override[K_CONV3_FWD] == 0) ? LV_CONV3_C36 : 0;
     LAUNCH(K_CONV3_FWD, launch_tuned(h, K_CONV3_FWD, f3, g_stream, c36)); }
   { int rc = join_comm(h); if (rc) return rc; }                // conv1..3 of this step overlap the previous step's fc4 all-reduce
   LAUNCH(K_FC4_FWD, launch_tuned(h, K_FC4_FWD, fm, g_stream));
@@ -124,7 +124,7 @@ UpdateArgs make_update_args(sdqn_net_s* h, const StepArgs& a) {
   u.opt = h->cfg.optimizer; u.state2 = h->state2;
   if (h->cfg.datatype == 1) { u.wh = h->wh[0]; u.wht = h->wht[0]; }
   u.w1p = h->w1p[0];
-  u.wt = (h->wt >> 8) & 1;
+  u.wt = (h->wt & WT_UPDATE) ? 1 : 0;
   u.bn_first = h->bn ? h->NPW : 0;
   if (u.opt == 1) {            // Neon Adam [neon-recalled]: t = epoch + 1, l = lr*sqrt(1-b2^t)/(1-b1^t), math in Python floats
     const double b1 = h->cfg.beta_1, b2 = h->cfg.beta_2, t = (double)h->epoch + 1.0;
@@ -217,7 +217,7 @@ int run_train(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd0, const PrepA
     BN_BWD(1);
     LAUNCH(K_BWD2, launch_tuned(h, K_BWD2, b2, g_stream));
     BN_BWD(0);
-    LAUNCH(K_BWD1, launch_tuned(h, K_BWD1, b1, g_stream, c1w ? 8 : 0));
+    LAUNCH(K_BWD1, launch_tuned(h, K_BWD1, b1, g_stream, c1w ? LV_CONV1_WGRAD_BF16 : 0));
   } else if (st == STEP_H16_BT) {
     // round 4, float16 at B >= 128: the two dgrads run on the half block-tile routine as launches of their own (15.6 / 18.1 -> ~7 / 8 us:
     // operands leave L2 once per workgroup), and every weight gradient that does not need delta1 shares ONE launch behind them (it packs
@@ -231,7 +231,7 @@ int run_train(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd0, const PrepA
     // complete by then — where that kernel applies (packed-fp16 weight gradients, slabs of whole 80-position chunks) and nothing asks for
     // another form (bt:18 / bt:24 = 0; option c1w_in_wgrads: 0 = off, 1 = its workgroups last (built-in), 2 = first)
     const int merge = (h->c1w_in_wgrads && h->h16_wgrad_mfma && (h->tps1 * 32) % 80 == 0 && h->bt[K_BWD1] == 0 && h->bt[K_WGRADS] == 0 &&
-                       h->nw_override[K_CONV1_WGRAD] == 0) ? (h->c1w_in_wgrads == 2 ? 48 : 16) : 0;
+                       h->nw_override[K_CONV1_WGRAD] == 0) ? (LV_C1W_IN_WGRADS | (h->c1w_in_wgrads == 2 ? LV_C1W_FIRST : 0)) : 0;
     LAUNCH(K_WGRADS, launch_tuned(h, K_WGRADS, w, g_stream, merge));
     LAUNCH(K_BWD1, launch_tuned(h, K_BWD1, b1, g_stream, merge));
   } else if (st == STEP_FUSED) {
@@ -255,7 +255,7 @@ int run_train(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd0, const PrepA
     // conv1_wgrad on the XCD-contiguous tile map: the 8 m-tiles of a K-slab read the same frames, so a slab's tiles belong on ONE XCD's L2
     // (L2 <-> fabric traffic of the launch 15.8 -> 4.0 MB = 1.4x algorithmic, rocprofv3 PMC; step rate -0.1 %: the re-reads were MALL hits)
     b1.xcd_map |= 2;
-    LAUNCH(K_BWD1, launch_tuned(h, K_BWD1, b1, g_stream, (c1w && b1.f4w_count == 0) ? 8 : 0));
+    LAUNCH(K_BWD1, launch_tuned(h, K_BWD1, b1, g_stream, (c1w && b1.f4w_count == 0) ? LV_CONV1_WGRAD_BF16 : 0));
   } else {
     // fc4_wgrad may update W4 in place (fused RMSProp): it must not start before fc4_dgrad has read W4 — same stream, after it
     LAUNCH(K_FC4_WGRAD, launch_tuned(h, K_FC4_WGRAD, a, g_stream));            // needs d4, a3
@@ -265,7 +265,7 @@ int run_train(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd0, const PrepA
     LAUNCH(K_CONV2_WGRAD, launch_tuned(h, K_CONV2_WGRAD, a, g_stream));        // needs d2p, a1
     LAUNCH(K_CONV2_DGRAD, launch_tuned(h, K_CONV2_DGRAD, a, g_stream));
     BN_BWD(0);
-    LAUNCH(K_CONV1_WGRAD, launch_tuned(h, K_CONV1_WGRAD, a, g_stream, c1w ? 8 : 0));
+    LAUNCH(K_CONV1_WGRAD, launch_tuned(h, K_CONV1_WGRAD, a, g_stream, c1w ? LV_CONV1_WGRAD_BF16 : 0));
   }
   UpdateArgs u = make_update_args(h, a);
   if (next) u.next = *next;                 // (memset above left next.B = 0 otherwise)
@@ -314,11 +314,38 @@ int run_train(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd0, const PrepA
   h->spec_pending = false;                 // the online parameters move: a forward enqueued before this step no longer is "predict now"
   return SDQN_OK;
 }
-int read_cost(sdqn_net_s* h, float* cost_out) {
-  HIPCHK(hipMemcpyAsync(h->h_f, h->cost_out, 4, hipMemcpyDeviceToHost, g_stream));
+// small read-backs: `bytes` of device memory into the pinned scratch h->h_f, waited for
+static int fetch_small(sdqn_net_s* h, const void* src, size_t bytes) {
+  HIPCHK(hipMemcpyAsync(h->h_f, src, bytes, hipMemcpyDeviceToHost, g_stream));
   HIPCHK(hipStreamSynchronize(g_stream));
-  *cost_out = h->h_f[0];
-  return per_check_all();                  // (a prioritized memory's device flags: action out of range, non-finite TD error)
+  return SDQN_OK;
+}
+// The last step's cost / the mean over the n_steps steps since the cost sum was cleared.  Both wait for the stream, so both end with what
+// every synchronising net call reports: the prioritized memories' device flags (action out of range, non-finite TD error).
+int read_cost(sdqn_net_s* h, float* cost_out) {
+  if (h->gen) { double c; GENCHK(h->gen->read_cost(&c)); *cost_out = (float)c; }
+  else { int rc = fetch_small(h, h->cost_out, 4); if (rc) return rc; *cost_out = h->h_f[0]; }
+  return per_check_all();
+}
+int read_mean_cost(sdqn_net_s* h, int n_steps, float* mean_cost) {
+  double sum;
+  if (h->gen) GENCHK(h->gen->read_cost_sum(&sum));
+  else { int rc = fetch_small(h, h->cost_accum, 8); if (rc) return rc; memcpy(&sum, h->h_f, 8); }
+  *mean_cost = n_steps ? (float)(sum / n_steps) : 0.0f;
+  return per_check_all();
+}
+// The predict forward (what sdqn_net_predict launches) on states already on the device, tuned path: the net's full batch, or B states.
+int predict_forward_tuned(sdqn_net_s* h, const uint8_t* states, const HeadArgs& hd, int B) {
+  StepArgs a = step_args(h); a.nz = 1; a.from_ring = 0; a.src = states;
+  if (B) a.B = B;
+  return run_forward(h, a, hd);
+}
+// ... on either path: `rows` states are wanted (the tuned forward runs its full batch, the generic one these rows); *q: where the Q-values
+// [rows][A] will lie, *q_f64: as doubles (a float64 network)
+int predict_forward(sdqn_net_s* h, const uint8_t* states, int rows, const void** q, int* q_f64) {
+  if (h->gen) { GENCHK(h->gen->forward_dev(states, rows)); *q = h->gen->q_dev(); *q_f64 = h->gen->is_f64() ? 1 : 0; return SDQN_OK; }
+  *q = h->q; *q_f64 = 0;
+  return predict_forward_tuned(h, states, head_args(h, 0));
 }
 
 extern "C" int sdqn_net_predict_f64(sdqn_net_t h, const uint8_t* states, double* q_out) {
@@ -333,11 +360,8 @@ extern "C" int sdqn_net_predict(sdqn_net_t h, const uint8_t* states, float* q_ou
   ARGCHK(h && states && q_out, "NULL argument");
   if (h->gen) { GENCHK(h->gen->predict_host(states, h->B, q_out, false)); return SDQN_OK; }
   HIPCHK(hipMemcpyAsync(h->st_states, states, (size_t)h->B * STATE, hipMemcpyHostToDevice, g_stream));
-  StepArgs a = step_args(h); a.nz = 1; a.from_ring = 0; a.src = h->st_states;
-  HeadArgs hd = head_args(h, 0);
-  int rc = run_forward(h, a, hd); if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(h->h_f, h->q, (size_t)h->B * h->A * 4, hipMemcpyDeviceToHost, g_stream));
-  HIPCHK(hipStreamSynchronize(g_stream));
+  int rc = predict_forward_tuned(h, h->st_states, head_args(h, 0)); if (rc) return rc;
+  rc = fetch_small(h, h->q, (size_t)h->B * h->A * 4); if (rc) return rc;
   memcpy(q_out, h->h_f, (size_t)h->B * h->A * 4);                             // (B, A): deepqnetwork.py:186 qvalues.T
   return SDQN_OK;
 }
@@ -366,17 +390,13 @@ extern "C" int sdqn_net_predict_one(sdqn_net_t h, const uint8_t* state, float* q
     aa.q = h->act_q; aa.A = h->A; aa.seq = h->act_seq++;
     HIPCHK(hipMemsetAsync(h->act_q, 0xFF, (size_t)Q_SLOT_FLOATS * 4, g_stream));          // (an abandoned launch leaves NaNs, checked below)
     LAUNCH(K_ACT, launch_act(aa, false, g_stream));
-    HIPCHK(hipMemcpyAsync(h->h_f, h->act_q, (size_t)Q_SLOT_FLOATS * 4, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
+    { int rcf = fetch_small(h, h->act_q, (size_t)Q_SLOT_FLOATS * 4); if (rcf) return rcf; }
     if (act_sum_partials(h->h_f, h->A, q_out)) return SDQN_OK;
     h->act_on = false; h->act_fallbacks += 1;
     fprintf(stderr, "simple_dqn_amd: the one-launch acting forward did not complete; using the five-launch forward from now on\n");
   }
-  StepArgs a = step_args(h); a.B = 1; a.nz = 1; a.from_ring = 0; a.src = h->st_states;   // same buffers, batch of one
-  HeadArgs hd = head_args(h, 0);
-  int rc = run_forward(h, a, hd); if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(h->h_f, h->q, (size_t)h->A * 4, hipMemcpyDeviceToHost, g_stream));
-  HIPCHK(hipStreamSynchronize(g_stream));
+  int rc = predict_forward_tuned(h, h->st_states, head_args(h, 0), 1); if (rc) return rc;   // same buffers, batch of one
+  rc = fetch_small(h, h->q, (size_t)h->A * 4); if (rc) return rc;
   memcpy(q_out, h->h_f, (size_t)h->A * 4);
   return SDQN_OK;
 }
@@ -397,9 +417,8 @@ static int train_host_tuple(sdqn_net_t h, const uint8_t* pre, const uint8_t* act
   else ARGCHK(h->n_step == 1, "network n_step %d: integer rewards are refused, train with returns (sdqn_net_train_host_returns)", h->n_step);
   for (int i = 0; i < h->B; ++i) ARGCHK(actions[i] < h->A, "action %d out of range at %d", (int)actions[i], i);
   const bool ours = owner != nullptr;
-  if (ours) { int rcn = nstep_match(h, owner); if (rcn) return rcn; }
+  if (ours) { int rcn = nstep_match(h, owner); if (rcn) return rcn; rcn = check_replay_geometry(h, owner); if (rcn) return rcn; }
   if (h->gen) {
-    ARGCHK(!ours || (size_t)owner->state == h->gen->state_bytes(), "replay geometry differs from the network's");
     const bool per = per_owns_minibatch(owner);                 // prioritized memory: weighted step + priority write-back
     if (per) per_gen_arm(h, owner);
     const hipError_t ge = reuse ? h->gen->train_dev_host_meta(owner->d_pre, owner->d_post, actions, rewards, terminals, h->epoch)
@@ -407,8 +426,7 @@ static int train_host_tuple(sdqn_net_t h, const uint8_t* pre, const uint8_t* act
     if (per) { int rcp = per_gen_finish(h, owner); if (ge == hipSuccess && rcp) return rcp; }
     GENCHK(ge);
     h->train_iterations += 1;
-    if (cost_out) { double c; GENCHK(h->gen->read_cost(&c)); *cost_out = (float)c; }
-    return SDQN_OK;
+    return cost_out ? read_cost(h, cost_out) : SDQN_OK;
   }
   const size_t sb = (size_t)h->B * STATE, small = (size_t)h->B * 10;
   // No stream synchronisation (round 1 paid a full PCIe + sync bubble per step here): the caller's arrays are free to
@@ -425,7 +443,6 @@ static int train_host_tuple(sdqn_net_t h, const uint8_t* pre, const uint8_t* act
   // enqueue time); when the caller passes back exactly those values — what getMinibatch() returned, untouched — the step reads the
   // device copy and the call uploads nothing at all (no 10 B x batch H2D, no staging slot, no event: ~6 us of a ~75 us iteration).
   // Any difference (a caller that clips rewards, edits an action, ...) takes the upload below, as before.
-  ARGCHK(!ours || owner->tuned_geom, "replay geometry differs from the network's");
   const size_t nb = (size_t)h->B;
   const bool small_dev = reuse && owner->mb_snap && owner->mb_snap_gen == owner->mb_dev_gen &&
                          !memcmp(owner->mb_snap, rewards, nb * 8) && !memcmp(owner->mb_snap + nb * 8, actions, nb) &&
@@ -456,8 +473,7 @@ static int train_host_tuple(sdqn_net_t h, const uint8_t* pre, const uint8_t* act
   // prioritized memory, minibatch gathered from its last sample: weighted step + priority write-back (a foreign tuple: the standard step)
   int rc = per_owns_minibatch(owner) ? per_train_host_step(h, owner, a, hd) : run_train(h, a, hd); if (rc) return rc;
   if (ours && !reuse) { HIPCHK(hipEventSynchronize(owner->mb_upload_ev)); }
-  if (cost_out) return read_cost(h, cost_out);
-  return SDQN_OK;
+  return cost_out ? read_cost(h, cost_out) : SDQN_OK;
 }
 
 extern "C" int sdqn_net_train_host(sdqn_net_t h, const uint8_t* pre, const uint8_t* actions, const int64_t* rewards,
@@ -495,23 +511,28 @@ int check_ring_actions(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* idx) {
            "ring slot %lld holds action %d but the network has %d actions", (long long)idx[i], (int)r->actions[idx[i]], h->A);
   return SDQN_OK;
 }
-// do_prep: launch the standalone prep for THIS step; next_pinned: fold the NEXT step's prep into the update
-int train_replay_slot(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* pinned_idx, bool do_prep,
-                             const int64_t* next_pinned, double* zero8) {
-  if (do_prep) { PrepArgs p = prep_args(h, r, pinned_idx); LAUNCH(K_PREP, launch_prep(p, g_stream, zero8)); }
+// A step that reads its states from the ring, its indexes in h->d_idx: the arguments, and the step.  host_idx: the host copy of those
+// indexes (conv1's tiles take them from the kernel arguments: launch_tuned), nullptr when they were sampled on the device (conv1 reads HBM)
+StepArgs ring_step_args(sdqn_net_s* h, const sdqn_replay_s* r) {
   StepArgs a = step_args(h); a.from_ring = 1; a.src = r->d_ring; a.idx = h->d_idx;
-  HeadArgs hd = head_args(h, 1);
-  // the slot's HOST address (pinned_idx is its device alias): conv1's tiles take their indexes from the kernel arguments
-  h->host_idx_cur = r->h_idx + (pinned_idx - r->d_idx_view);
-  int rc;
-  if (next_pinned) { PrepArgs np = prep_args(h, r, next_pinned); rc = run_train(h, a, hd, &np); }
-  else rc = run_train(h, a, hd, nullptr);
+  return a;
+}
+int run_ring_step(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* host_idx, const HeadArgs& hd, const PrepArgs* next) {
+  h->host_idx_cur = host_idx;
+  const int rc = run_train(h, ring_step_args(h, r), hd, next);
   h->host_idx_cur = nullptr;
   return rc;
 }
+// do_prep: launch the standalone prep for THIS step; next_pinned: fold the NEXT step's prep into the update
+static int train_replay_slot(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* pinned_idx, bool do_prep = true,
+                             const int64_t* next_pinned = nullptr, double* zero8 = nullptr) {
+  if (do_prep) { PrepArgs p = prep_args(h, r, pinned_idx); LAUNCH(K_PREP, launch_prep(p, g_stream, zero8)); }
+  const int64_t* host_idx = r->h_idx + (pinned_idx - r->d_idx_view);      // the slot's HOST address (pinned_idx is its device alias)
+  PrepArgs np; if (next_pinned) np = prep_args(h, r, next_pinned);
+  return run_ring_step(h, r, host_idx, head_args(h, 1), next_pinned ? &np : nullptr);
+}
 // float64 / other geometries: sample on the host, gather on the device into the replay handle's minibatch buffers, train from there
-int gen_train_replay(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* idx_host) {
-  ARGCHK((size_t)r->state == h->gen->state_bytes(), "replay geometry (%dx%d, history %d) differs from the network's", r->H, r->W, r->hist);
+static int gen_train_replay(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* idx_host) {
   int slot; const int64_t* didx; int rc = check_ring_actions(h, r, idx_host); if (rc) return rc;
   rc = replay_push_idx(r, idx_host, &slot, &didx); if (rc) return rc;
   rc = replay_gather_generic(r, didx); if (rc) return rc;
@@ -520,68 +541,64 @@ int gen_train_replay(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* idx_host) {
   h->train_iterations += 1;
   return SDQN_OK;
 }
+// does this replay memory's geometry fit this network?  (tuned path: 84 x 84 x 4; generic path: the configured state size)
+int check_replay_geometry(const sdqn_net_s* h, const sdqn_replay_s* r) {
+  const int64_t want = h->gen ? (int64_t)h->gen->state_bytes() : (int64_t)STATE;
+  ARGCHK(h->gen ? r->state == want : r->tuned_geom, "replay geometry (%dx%d, history %d: %lld bytes per state) differs from the network's (%lld bytes per state)",
+         r->H, r->W, r->hist, (long long)r->state, (long long)want);
+  return SDQN_OK;
+}
+// what the entry points that train from a replay memory ask first: its batch size, n-step settings and geometry are the network's
+static int check_replay_fits(const sdqn_net_s* h, const sdqn_replay_s* r) {
+  ARGCHK(r->B == h->B, "replay batch_size %d != network batch_size %d", r->B, h->B);
+  const int rc = nstep_match(h, r);
+  return rc ? rc : check_replay_geometry(h, r);
+}
 extern "C" int sdqn_net_train_replay(sdqn_net_t h, sdqn_replay_t r, const int64_t* idx_host, float* cost_out) {
   ARGCHK(h && r && idx_host, "NULL argument");
-  ARGCHK(r->B == h->B, "replay batch_size %d != network batch_size %d", r->B, h->B);
-  { int rcn = nstep_match(h, r); if (rcn) return rcn; }
+  int rc = check_replay_fits(h, r); if (rc) return rc;
   if (r->per) return per_train_replay(h, r, idx_host, cost_out);
-  if (h->gen) {
-    int rc = gen_train_replay(h, r, idx_host); if (rc) return rc;
-    if (cost_out) { double c; GENCHK(h->gen->read_cost(&c)); *cost_out = (float)c; }
-    return SDQN_OK;
+  if (h->gen) rc = gen_train_replay(h, r, idx_host);
+  else {
+    int slot; const int64_t* didx; rc = check_ring_actions(h, r, idx_host); if (rc) return rc;
+    rc = replay_push_idx(r, idx_host, &slot, &didx); if (rc) return rc;
+    rc = train_replay_slot(h, r, didx); if (rc) return rc;
+    rc = replay_release_idx_batched(r, slot, false);
   }
-  ARGCHK(r->tuned_geom, "replay geometry (%dx%d, history %d) differs from the network's (84x84, 4)", r->H, r->W, r->hist);
-  int slot; const int64_t* didx; int rc = check_ring_actions(h, r, idx_host); if (rc) return rc;
-  rc = replay_push_idx(r, idx_host, &slot, &didx); if (rc) return rc;
-  rc = train_replay_slot(h, r, didx); if (rc) return rc;
-  rc = replay_release_idx_batched(r, slot, false); if (rc) return rc;
-  if (cost_out) return read_cost(h, cost_out);
-  return SDQN_OK;
+  if (rc) return rc;
+  return cost_out ? read_cost(h, cost_out) : SDQN_OK;
 }
 extern "C" int sdqn_net_train_many(sdqn_net_t h, sdqn_replay_t r, uint32_t* mt, int n_steps, float* mean_cost) {
   ARGCHK(h && r && mt && n_steps >= 0, "bad arguments");
-  ARGCHK(r->B == h->B, "replay batch_size %d != network batch_size %d", r->B, h->B);
-  { int rcn = nstep_match(h, r); if (rcn) return rcn; }
+  int rc = check_replay_fits(h, r); if (rc) return rc;
+  if (h->gen) GENCHK(h->gen->reset_cost_sum());                                     // the cost sum of this call's steps
+  else if (n_steps == 0) HIPCHK(hipMemsetAsync(h->cost_accum, 0, 8, g_stream));     // (otherwise the first step's prep launch clears it)
   if (r->per) return per_train_many(h, r, mt, n_steps, mean_cost);
-  if (h->gen) {
-    std::vector<int64_t> gi((size_t)r->B);
-    GENCHK(h->gen->reset_cost_sum());
-    for (int i = 0; i < n_steps; ++i) {
-      int rc = replay_sample_uniform(r, mt, gi.data(), nullptr); if (rc) return rc;
-      rc = gen_train_replay(h, r, gi.data()); if (rc) return rc;
-    }
-    int rc = replay_flush_pending(r); if (rc) return rc;
-    if (mean_cost) { double sum; GENCHK(h->gen->read_cost_sum(&sum)); *mean_cost = n_steps ? (float)(sum / n_steps) : 0.0f; }
-    return SDQN_OK;
-  }
-  ARGCHK(r->tuned_geom, "replay geometry (%dx%d, history %d) differs from the network's (84x84, 4)", r->H, r->W, r->hist);
   std::vector<int64_t> idx((size_t)r->B);
-  if (n_steps == 0) HIPCHK(hipMemsetAsync(h->cost_accum, 0, 8, g_stream));       // (otherwise the first step's prep launch clears it)
+  if (h->gen) {
+    for (int i = 0; i < n_steps; ++i) {
+      rc = replay_sample_uniform(r, mt, idx.data(), nullptr); if (rc) return rc;
+      rc = gen_train_replay(h, r, idx.data()); if (rc) return rc;
+    }
+    rc = replay_flush_pending(r); if (rc) return rc;
+    return mean_cost ? read_mean_cost(h, n_steps, mean_cost) : SDQN_OK;
+  }
   // sample one step ahead: step i's update launch also performs step i+1's prep (index copy + metadata gather)
   int slot = -1, next_slot = -1; const int64_t *pinned = nullptr, *next_pinned = nullptr;
-  if (n_steps > 0) {
+  auto sample = [&](int* sl, const int64_t** pin) -> int {
     int rc = replay_sample_uniform(r, mt, idx.data(), nullptr); if (rc) return rc;
     rc = check_ring_actions(h, r, idx.data()); if (rc) return rc;
-    rc = replay_push_idx(r, idx.data(), &slot, &pinned); if (rc) return rc;
-  }
+    return replay_push_idx(r, idx.data(), sl, pin);
+  };
+  if (n_steps > 0) { rc = sample(&slot, &pinned); if (rc) return rc; }
   for (int i = 0; i < n_steps; ++i) {
     next_pinned = nullptr;
-    if (i + 1 < n_steps) {
-      int rc = replay_sample_uniform(r, mt, idx.data(), nullptr); if (rc) return rc;
-      rc = check_ring_actions(h, r, idx.data()); if (rc) return rc;
-      rc = replay_push_idx(r, idx.data(), &next_slot, &next_pinned); if (rc) return rc;
-    }
-    int rc = train_replay_slot(h, r, pinned, /*do_prep=*/i == 0, next_pinned, i == 0 ? h->cost_accum : nullptr); if (rc) return rc;
-    rc = replay_release_idx_batched(r, slot, false);
-    if (rc) return rc;
+    if (i + 1 < n_steps) { rc = sample(&next_slot, &next_pinned); if (rc) return rc; }
+    rc = train_replay_slot(h, r, pinned, /*do_prep=*/i == 0, next_pinned, i == 0 ? h->cost_accum : nullptr); if (rc) return rc;
+    rc = replay_release_idx_batched(r, slot, false); if (rc) return rc;
     slot = next_slot; pinned = next_pinned;
   }
-  if (mean_cost) {
-    HIPCHK(hipMemcpyAsync(h->h_f, h->cost_accum, 8, hipMemcpyDeviceToHost, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-    *mean_cost = n_steps ? (float)(*(double*)h->h_f / n_steps) : 0.0f;
-  }
-  return SDQN_OK;
+  return mean_cost ? read_mean_cost(h, n_steps, mean_cost) : SDQN_OK;
 }
 // ---- train_many without waiting for the cost (agent.py:108-114 + deepqnetwork.py:168-172 when the callback can take the cost later) ----------
 // The mean cost of the call's steps is copied into a pinned ring slot by the stream itself; sdqn_net_cost_collect polls the slot (bounded).

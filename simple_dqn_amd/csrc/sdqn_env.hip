@@ -303,71 +303,103 @@ extern "C" int sdqn_net_act_step_env(sdqn_net_t h, sdqn_statebuf_t sb, sdqn_repl
   return GAME_CALL(e, act_step_env, h, sb, r, e, action, speculate, reward, terminal);
 }
 
-// N independent copies of the game played by the online net, epsilon-greedy, entirely on the device: per step the batched forward of
-// sdqn_net_predict (the generic path's forward for float64 / other geometries) on the [batch][hist][H][W] window buffer, then ONE launch
-// of the game's eval kernel; two window buffers alternate (read one, write the other).  Nothing returns to the host inside the loop; one
-// stream synchronisation at the end.  The environment handle gives the geometry and balls_per_episode; its own state is not touched.
+// ---- the game loops (sdqn_env_eval, sdqn_env_collect): N copies of the game played by the online net, epsilon-greedy, entirely on the
+// device.  Per lockstep the predict forward (predict_forward) on the [batch][hist][H][W] window buffer, then ONE launch of the game's
+// kernel; two window buffers alternate (read one, write the other).  Nothing returns to the host inside a loop; one stream synchronisation
+// at the end.  Shared: what follows.  Per loop: seeding or resuming, whose buffers the copies live in, ring copies, epsilon schedule.
+struct EnvOut {                // the callers' output arrays: five tallies [N] (each optional), the trace [locksteps][N] ([A]) (all four or none)
+  int64_t *steps, *reward, *caught, *missed, *episodes;
+  uint8_t* tr_actions; int8_t* tr_rewards; uint8_t* tr_terminals; double* tr_q;
+  bool trace() const { return tr_actions || tr_rewards || tr_terminals || tr_q; }
+};
+struct EnvGeom { int hist, H, W; size_t state, half; };      // the network's state geometry; half: one window buffer (rows N .. batch_size - 1 stay zero: the forward runs the full batch)
 template <class G>
-static int env_eval(sdqn_net_t h, sdqn_env_t e, int N, int64_t steps, double epsilon, uint64_t seed,
-                    int64_t* out_steps, int64_t* out_reward, int64_t* out_caught, int64_t* out_missed, int64_t* out_episodes,
-                    uint8_t* tr_actions, int8_t* tr_rewards, uint8_t* tr_terminals, double* tr_q) {
-  typedef EvalRec<G> Rec;
-  const int hist = h->gen ? h->cfg.history_length : C0, H = h->gen ? h->cfg.screen_height : H0, W = h->gen ? h->cfg.screen_width : W0;
-  ARGCHK(e->H == H && e->W == W, "the environment's screen (%d x %d) and the network's (%d x %d) differ", e->H, e->W, H, W);
+static int env_check(sdqn_net_t h, sdqn_env_t e, int N, double epsilon, const EnvOut& o, EnvGeom& g) {
+  g.hist = h->gen ? h->cfg.history_length : C0; g.H = h->gen ? h->cfg.screen_height : H0; g.W = h->gen ? h->cfg.screen_width : W0;
+  g.state = (size_t)g.hist * g.H * g.W; g.half = (size_t)h->B * g.state;
+  ARGCHK(e->H == g.H && e->W == g.W, "the environment's screen (%d x %d) and the network's (%d x %d) differ", e->H, e->W, g.H, g.W);
   ARGCHK(h->A == G::ACTIONS, "the network has %d actions, %s has %d", h->A, G::NAME, G::ACTIONS);
   ARGCHK(N >= 1 && N <= h->B, "num_envs %d out of range [1, batch_size %d]", N, h->B);
-  ARGCHK(steps >= 1, "steps %lld < 1", (long long)steps);
   ARGCHK(epsilon >= 0.0 && epsilon <= 1.0, "epsilon %g out of range [0, 1]", epsilon);
-  const bool trace = tr_actions || tr_rewards || tr_terminals || tr_q;
-  ARGCHK(!trace || (tr_actions && tr_rewards && tr_terminals && tr_q), "the trace buffers come together: all four or none");
+  ARGCHK(!o.trace() || (o.tr_actions && o.tr_rewards && o.tr_terminals && o.tr_q), "the trace buffers come together: all four or none");
+  return SDQN_OK;
+}
+struct DevMem {                // device memory of one call
+  void* p = nullptr; ~DevMem() { hipFree(p); }
+  int alloc(size_t bytes) { HIPCHK(hipMalloc(&p, bytes)); return SDQN_OK; }
+};
+// the trace of one call: device buffers for `rows` locksteps of N copies (none when the caller wants no trace), wired into the launch
+// arguments, read back into the caller's arrays behind the loop
+struct EnvTrace {
+  DevMem small, q; size_t tn = 0, qbytes = 0;
+  int begin(const EnvOut& o, int64_t rows, int N, int A, EvalArgs& a) {
+    tn = o.trace() ? (size_t)rows * N : 0; qbytes = tn * A * sizeof(double);
+    if (!tn) return SDQN_OK;
+    int rc = small.alloc(3 * tn); if (rc) return rc;
+    rc = q.alloc(qbytes); if (rc) return rc;
+    a.tr_act = static_cast<uint8_t*>(small.p); a.tr_rew = reinterpret_cast<int8_t*>(a.tr_act + tn); a.tr_term = a.tr_act + 2 * tn; a.tr_q = static_cast<double*>(q.p);
+    return SDQN_OK;
+  }
+  int read_back(const EnvOut& o, const EvalArgs& a) {
+    if (!tn) return SDQN_OK;
+    HIPCHK(hipMemcpyAsync(o.tr_actions, a.tr_act, tn, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipMemcpyAsync(o.tr_rewards, a.tr_rew, tn, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipMemcpyAsync(o.tr_terminals, a.tr_term, tn, hipMemcpyDeviceToHost, g_stream));
+    HIPCHK(hipMemcpyAsync(o.tr_q, a.tr_q, qbytes, hipMemcpyDeviceToHost, g_stream));
+    return SDQN_OK;
+  }
+};
+static EvalArgs env_args(sdqn_net_t h, sdqn_env_t e, int N, const EnvGeom& g, void* recs) {
+  EvalArgs a; memset(&a, 0, sizeof a);
+  a.A = h->A; a.N = N; a.hist = g.hist; a.H = g.H; a.W = g.W; a.bpe = e->bpe; a.envs = recs;
+  return a;
+}
+// the host copy of the records -> the callers' tallies
+template <class G>
+static void env_tallies(const std::vector<EvalRec<G> >& hrec, const EnvOut& o) {
+  for (size_t i = 0; i < hrec.size(); ++i) {
+    if (o.steps) o.steps[i] = hrec[i].steps; if (o.reward) o.reward[i] = hrec[i].reward;
+    if (o.caught) o.caught[i] = hrec[i].caught; if (o.missed) o.missed[i] = hrec[i].missed;
+    if (o.episodes) o.episodes[i] = hrec[i].episodes;
+  }
+}
+
+// sdqn_env_eval: the copies live in buffers of this call, seeded from `seed`; one epsilon.  The environment handle gives the geometry and
+// balls_per_episode; its own state is not touched.
+template <class G>
+static int env_eval(sdqn_net_t h, sdqn_env_t e, int N, int64_t steps, double epsilon, uint64_t seed, const EnvOut& o) {
+  typedef EvalRec<G> Rec;
+  EnvGeom g; int rc = env_check<G>(h, e, N, epsilon, o, g); if (rc) return rc;
+  ARGCHK(steps >= 1, "steps %lld < 1", (long long)steps);
   STREAMCHK();
-  const size_t state = (size_t)hist * H * W, half = (size_t)h->B * state;      // (rows N .. batch_size - 1 stay zero: the forward runs the full batch)
-  const size_t tn = trace ? (size_t)steps * N : 0;
-  uint8_t* win = nullptr; Rec* recs = nullptr; uint8_t* tr = nullptr; double* trq = nullptr;
+  DevMem win_mem, recs; EnvTrace tr;
   std::vector<Rec> hrec((size_t)N);
   auto body = [&]() -> int {
-    HIPCHK(hipMalloc((void**)&win, 2 * half + SRC_PAD));
-    HIPCHK(hipMemsetAsync(win, 0, 2 * half + SRC_PAD, g_stream));
-    HIPCHK(hipMalloc((void**)&recs, (size_t)N * sizeof(Rec)));
-    HIPCHK(hipMemsetAsync(recs, 0, (size_t)N * sizeof(Rec), g_stream));
-    if (trace) { HIPCHK(hipMalloc((void**)&tr, 3 * tn)); HIPCHK(hipMalloc((void**)&trq, tn * h->A * sizeof(double))); }
-    EvalArgs a; memset(&a, 0, sizeof a);
-    a.q = h->gen ? h->gen->q_dev() : (const void*)h->q; a.q_f64 = (h->gen && h->gen->is_f64()) ? 1 : 0;
-    a.A = h->A; a.N = N; a.hist = hist; a.H = H; a.W = W; a.bpe = e->bpe; a.envs = recs; a.seed = seed;
-    a.thresh = (uint64_t)ceil(ldexp(epsilon, 53));
-    if (trace) { a.tr_act = tr; a.tr_rew = reinterpret_cast<int8_t*>(tr + tn); a.tr_term = tr + 2 * tn; a.tr_q = trq; }
-    a.init = 1; a.src = win + half; a.dst = win;
+    int rc = win_mem.alloc(2 * g.half + SRC_PAD); if (rc) return rc;
+    uint8_t* win = static_cast<uint8_t*>(win_mem.p);
+    HIPCHK(hipMemsetAsync(win, 0, 2 * g.half + SRC_PAD, g_stream));
+    rc = recs.alloc((size_t)N * sizeof(Rec)); if (rc) return rc;
+    HIPCHK(hipMemsetAsync(recs.p, 0, (size_t)N * sizeof(Rec), g_stream));
+    EvalArgs a = env_args(h, e, N, g, recs.p);
+    rc = tr.begin(o, steps, N, h->A, a); if (rc) return rc;
+    a.seed = seed; a.thresh = (uint64_t)ceil(ldexp(epsilon, 53));
+    a.init = 1; a.src = win + g.half; a.dst = win;
     HIPCHK(Kernels<G>::eval(a, g_stream));
     a.init = 0;
     for (int64_t t = 0; t < steps; ++t) {
-      const uint8_t* cur = win + (size_t)(t & 1) * half;
-      if (h->gen) GENCHK(h->gen->forward_dev(cur, N));
-      else {
-        StepArgs fa = step_args(h); fa.nz = 1; fa.from_ring = 0; fa.src = cur;     // what sdqn_net_predict launches
-        int rc = run_forward(h, fa, head_args(h, 0)); if (rc) return rc;
-      }
-      a.t = t; a.src = cur; a.dst = win + (size_t)((t + 1) & 1) * half;
+      const uint8_t* cur = win + (size_t)(t & 1) * g.half;
+      rc = predict_forward(h, cur, N, &a.q, &a.q_f64); if (rc) return rc;
+      a.t = t; a.src = cur; a.dst = win + (size_t)((t + 1) & 1) * g.half;
       HIPCHK(Kernels<G>::eval(a, g_stream));
     }
-    HIPCHK(hipMemcpyAsync(hrec.data(), recs, (size_t)N * sizeof(Rec), hipMemcpyDeviceToHost, g_stream));
-    if (trace) {
-      HIPCHK(hipMemcpyAsync(tr_actions, a.tr_act, tn, hipMemcpyDeviceToHost, g_stream));
-      HIPCHK(hipMemcpyAsync(tr_rewards, a.tr_rew, tn, hipMemcpyDeviceToHost, g_stream));
-      HIPCHK(hipMemcpyAsync(tr_terminals, a.tr_term, tn, hipMemcpyDeviceToHost, g_stream));
-      HIPCHK(hipMemcpyAsync(tr_q, trq, tn * h->A * sizeof(double), hipMemcpyDeviceToHost, g_stream));
-    }
+    HIPCHK(hipMemcpyAsync(hrec.data(), recs.p, (size_t)N * sizeof(Rec), hipMemcpyDeviceToHost, g_stream));
+    rc = tr.read_back(o, a); if (rc) return rc;
     HIPCHK(hipStreamSynchronize(g_stream));
     return SDQN_OK;
   };
-  const int rc = body();
-  if (rc && g_stream) hipStreamSynchronize(g_stream);
-  hipFree(win); hipFree(recs); hipFree(tr); hipFree(trq);
-  if (rc) return rc;
-  for (int i = 0; i < N; ++i) {
-    if (out_steps) out_steps[i] = hrec[i].steps; if (out_reward) out_reward[i] = hrec[i].reward;
-    if (out_caught) out_caught[i] = hrec[i].caught; if (out_missed) out_missed[i] = hrec[i].missed;
-    if (out_episodes) out_episodes[i] = hrec[i].episodes;
-  }
+  rc = body();
+  if (rc) { if (g_stream) hipStreamSynchronize(g_stream); return rc; }
+  env_tallies<G>(hrec, o);
   return SDQN_OK;
 }
 
@@ -375,12 +407,12 @@ extern "C" int sdqn_env_eval(sdqn_net_t h, sdqn_env_t e, int N, int64_t steps, d
                              int64_t* out_steps, int64_t* out_reward, int64_t* out_caught, int64_t* out_missed, int64_t* out_episodes,
                              uint8_t* tr_actions, int8_t* tr_rewards, uint8_t* tr_terminals, double* tr_q) {
   ARGCHK(h && e, "NULL argument");
-  return GAME_CALL(e, env_eval, h, e, N, steps, epsilon, seed, out_steps, out_reward, out_caught, out_missed, out_episodes,
-                   tr_actions, tr_rewards, tr_terminals, tr_q);
+  const EnvOut o = {out_steps, out_reward, out_caught, out_missed, out_episodes, tr_actions, tr_rewards, tr_terminals, tr_q};
+  return GAME_CALL(e, env_eval, h, e, N, steps, epsilon, seed, o);
 }
 
 // --train_envs: `locksteps` locksteps of num_envs copies of the game, each lockstep num_envs transitions written into the
-// laned ring r by ONE launch of the game's collect kernel behind the forward of sdqn_net_predict (no forward while epsilon >= 1: no Q row is
+// laned ring r by ONE launch of the game's collect kernel behind the predict forward (no forward while epsilon >= 1: no Q row is
 // read).  The copies' records and the two window buffers live on the net handle: seed >= 0 seeds the copies as sdqn_env_eval does and
 // renders their first frames, seed < 0 goes on where the last call stopped.  Lockstep t of the call plays with
 // epsilon = clamp(epsilon_start + t epsilon_step, 0, 1).  Per lockstep two strided device-to-host copies bring the num_envs frames and
@@ -388,62 +420,42 @@ extern "C" int sdqn_env_eval(sdqn_net_t h, sdqn_env_t e, int N, int64_t steps, d
 // synchronisation at the end, after which actions / rewards / terminals are unpacked.  Tallies: the copies' running sums since they were seeded.
 template <class G>
 static int env_collect(sdqn_net_t h, sdqn_env_t e, sdqn_replay_t r, int N, int64_t locksteps, double epsilon_start, double epsilon_step,
-                       int64_t seed, int64_t* out_steps, int64_t* out_reward, int64_t* out_caught, int64_t* out_missed,
-                       int64_t* out_episodes, uint8_t* tr_actions, int8_t* tr_rewards, uint8_t* tr_terminals, double* tr_q) {
+                       int64_t seed, const EnvOut& o) {
   typedef EvalRec<G> Rec;
-  const int hist = h->gen ? h->cfg.history_length : C0, H = h->gen ? h->cfg.screen_height : H0, W = h->gen ? h->cfg.screen_width : W0;
-  ARGCHK(e->H == H && e->W == W, "the environment's screen (%d x %d) and the network's (%d x %d) differ", e->H, e->W, H, W);
-  ARGCHK(r->H == H && r->W == W && r->hist == hist, "the replay memory's geometry (%d x %d, history %d) and the network's (%d x %d, %d) differ", r->H, r->W, r->hist, H, W, hist);
-  ARGCHK(h->A == G::ACTIONS, "the network has %d actions, %s has %d", h->A, G::NAME, G::ACTIONS);
-  ARGCHK(N >= 1 && N <= h->B, "num_envs %d out of range [1, batch_size %d]", N, h->B);
+  EnvGeom g; int rc = env_check<G>(h, e, N, epsilon_start, o, g); if (rc) return rc;
+  ARGCHK(r->H == g.H && r->W == g.W && r->hist == g.hist, "the replay memory's geometry (%d x %d, history %d) and the network's (%d x %d, %d) differ", r->H, r->W, r->hist, g.H, g.W, g.hist);
   ARGCHK(r->lanes == N, "the replay memory has %d lanes, num_envs is %d (sdqn_replay_set_lanes)", r->lanes, N);
   ARGCHK(locksteps >= 0, "locksteps %lld < 0", (long long)locksteps);
-  ARGCHK(epsilon_start >= 0.0 && epsilon_start <= 1.0, "epsilon %g out of range [0, 1]", epsilon_start);
-  const bool trace = tr_actions || tr_rewards || tr_terminals || tr_q;
-  ARGCHK(!trace || (tr_actions && tr_rewards && tr_terminals && tr_q), "the trace buffers come together: all four or none");
-  const size_t state = (size_t)hist * H * W, half = (size_t)h->B * state;      // (rows N .. batch_size - 1 stay zero: the forward runs the full batch)
-  ARGCHK(seed >= 0 || (h->col_recs && h->col_N == N && h->col_state == state && h->col_game == e->game),
+  ARGCHK(seed >= 0 || (h->col_recs && h->col_N == N && h->col_state == g.state && h->col_game == e->game),
          "nothing to resume: the copies were never seeded for %d environments of %s", N, G::NAME);
   STREAMCHK();
   if (!h->col_win) {
-    int rc = dalloc(h, (void**)&h->col_win, 2 * half + SRC_PAD); if (rc) return rc;
+    rc = dalloc(h, (void**)&h->col_win, 2 * g.half + SRC_PAD); if (rc) return rc;
     rc = dalloc(h, &h->col_recs, (size_t)h->B * std::max(sizeof(EvalRec<CatchGame>), sizeof(EvalRec<BreakoutGame>))); if (rc) return rc;    // (either game's records)
   }
-  Rec* recs = static_cast<Rec*>(h->col_recs);
-  const size_t tn = trace ? (size_t)locksteps * N : 0;
   const int64_t FRAME = r->frame, L = r->lane_len;
-  uint8_t* tr = nullptr; double* trq = nullptr;
+  EnvTrace tr;
   std::vector<Rec> hrec((size_t)N);
   int64_t p = r->lane_pos, f = r->lane_fill, launched = 0;
   auto body = [&]() -> int {
-    if (tn) { HIPCHK(hipMalloc((void**)&tr, 3 * tn)); HIPCHK(hipMalloc((void**)&trq, tn * h->A * sizeof(double))); }
-    EvalArgs a; memset(&a, 0, sizeof a);
-    a.q_f64 = (h->gen && h->gen->is_f64()) ? 1 : 0;
-    a.A = h->A; a.N = N; a.hist = hist; a.H = H; a.W = W; a.bpe = e->bpe; a.envs = recs;
+    EvalArgs a = env_args(h, e, N, g, h->col_recs);
+    int rc = tr.begin(o, locksteps, N, h->A, a); if (rc) return rc;
     CollectArgs c; c.ring = r->d_ring; c.meta = r->d_meta; c.lane_len = L; c.pos = p;
-    if (tn) { a.tr_act = tr; a.tr_rew = reinterpret_cast<int8_t*>(tr + tn); a.tr_term = tr + 2 * tn; a.tr_q = trq; }
     if (seed >= 0) {
-      HIPCHK(hipMemsetAsync(h->col_win, 0, 2 * half + SRC_PAD, g_stream));
-      a.seed = (uint64_t)seed; a.init = 1; a.src = h->col_win + half; a.dst = h->col_win;
+      HIPCHK(hipMemsetAsync(h->col_win, 0, 2 * g.half + SRC_PAD, g_stream));
+      a.seed = (uint64_t)seed; a.init = 1; a.src = h->col_win + g.half; a.dst = h->col_win;
       HIPCHK(Kernels<G>::collect(a, c, g_stream, false));
-      a.init = 0; h->col_t = 0; h->col_N = N; h->col_state = state; h->col_game = e->game;
+      a.init = 0; h->col_t = 0; h->col_N = N; h->col_state = g.state; h->col_game = e->game;
     }
     for (int64_t t = 0; t < locksteps; ++t) {
       const int64_t T = h->col_t;
-      const uint8_t* cur = h->col_win + (size_t)(T & 1) * half;
+      const uint8_t* cur = h->col_win + (size_t)(T & 1) * g.half;
       double eps = epsilon_start + (double)t * epsilon_step;
       eps = eps < 0.0 ? 0.0 : (eps > 1.0 ? 1.0 : eps);
       a.q = nullptr;
-      if (eps < 1.0) {
-        if (h->gen) GENCHK(h->gen->forward_dev(cur, N));
-        else {
-          StepArgs fa = step_args(h); fa.nz = 1; fa.from_ring = 0; fa.src = cur;     // what sdqn_net_predict launches
-          int rc = run_forward(h, fa, head_args(h, 0)); if (rc) return rc;
-        }
-        a.q = h->gen ? h->gen->q_dev() : (const void*)h->q;
-      }
+      if (eps < 1.0) { rc = predict_forward(h, cur, N, &a.q, &a.q_f64); if (rc) return rc; }
       a.thresh = (uint64_t)ceil(ldexp(eps, 53));
-      a.t = t; a.src = cur; a.dst = h->col_win + (size_t)((T + 1) & 1) * half;
+      a.t = t; a.src = cur; a.dst = h->col_win + (size_t)((T + 1) & 1) * g.half;
       c.pos = p;
       LAUNCH(K_COLLECT, Kernels<G>::collect(a, c, g_stream, true));
       h->col_t = T + 1;
@@ -455,19 +467,13 @@ static int env_collect(sdqn_net_t h, sdqn_env_t e, sdqn_replay_t r, int N, int64
       p = (p + 1) % L; if (f < L) ++f;
       ++launched;
     }
-    HIPCHK(hipMemcpyAsync(hrec.data(), recs, (size_t)N * sizeof(Rec), hipMemcpyDeviceToHost, g_stream));
-    if (tn) {
-      HIPCHK(hipMemcpyAsync(tr_actions, a.tr_act, tn, hipMemcpyDeviceToHost, g_stream));
-      HIPCHK(hipMemcpyAsync(tr_rewards, a.tr_rew, tn, hipMemcpyDeviceToHost, g_stream));
-      HIPCHK(hipMemcpyAsync(tr_terminals, a.tr_term, tn, hipMemcpyDeviceToHost, g_stream));
-      HIPCHK(hipMemcpyAsync(tr_q, trq, tn * h->A * sizeof(double), hipMemcpyDeviceToHost, g_stream));
-    }
+    HIPCHK(hipMemcpyAsync(hrec.data(), h->col_recs, (size_t)N * sizeof(Rec), hipMemcpyDeviceToHost, g_stream));
+    rc = tr.read_back(o, a); if (rc) return rc;
     HIPCHK(hipStreamSynchronize(g_stream));
     return SDQN_OK;
   };
-  const int rc = body();
+  rc = body();
   if (rc && g_stream) hipStreamSynchronize(g_stream);
-  hipFree(tr); hipFree(trq);
   // the positions written, newest last (a failed call: whatever reached the master is unpacked too, fill and position follow the launches made)
   const int64_t touched = launched < L ? launched : L;
   for (int64_t k = 0; k < touched; ++k) {
@@ -479,17 +485,13 @@ static int env_collect(sdqn_net_t h, sdqn_env_t e, sdqn_replay_t r, int N, int64
   }
   r->lane_pos = p; r->lane_fill = f;
   if (rc) return rc;
-  for (int i = 0; i < N; ++i) {
-    if (out_steps) out_steps[i] = hrec[i].steps; if (out_reward) out_reward[i] = hrec[i].reward;
-    if (out_caught) out_caught[i] = hrec[i].caught; if (out_missed) out_missed[i] = hrec[i].missed;
-    if (out_episodes) out_episodes[i] = hrec[i].episodes;
-  }
+  env_tallies<G>(hrec, o);
   return SDQN_OK;
 }
 extern "C" int sdqn_env_collect(sdqn_net_t h, sdqn_env_t e, sdqn_replay_t r, int N, int64_t locksteps, double epsilon_start, double epsilon_step,
                                 int64_t seed, int64_t* out_steps, int64_t* out_reward, int64_t* out_caught, int64_t* out_missed,
                                 int64_t* out_episodes, uint8_t* tr_actions, int8_t* tr_rewards, uint8_t* tr_terminals, double* tr_q) {
   ARGCHK(h && e && r, "NULL argument");
-  return GAME_CALL(e, env_collect, h, e, r, N, locksteps, epsilon_start, epsilon_step, seed, out_steps, out_reward, out_caught, out_missed,
-                   out_episodes, tr_actions, tr_rewards, tr_terminals, tr_q);
+  const EnvOut o = {out_steps, out_reward, out_caught, out_missed, out_episodes, tr_actions, tr_rewards, tr_terminals, tr_q};
+  return GAME_CALL(e, env_collect, h, e, r, N, locksteps, epsilon_start, epsilon_step, seed, o);
 }

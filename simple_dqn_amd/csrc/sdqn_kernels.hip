@@ -50,7 +50,7 @@ hipError_t launch_kernel(int id, const StepArgs& a, const LaunchTune& t, hipStre
     e = launch_kernel_bt(id, a, t, s, &handled);        // (B < 128: float16's conv1 kernels on request only)
     if (handled) return e;
   }
-  if (t.r3 || t.wt) {          // round-3 launch variants live in their own translation unit (same reason as sdqn_kernels_ext.hip)
+  if (t.variant || t.wt) {          // round-3 launch variants live in their own translation unit (same reason as sdqn_kernels_ext.hip)
     bool handled = false;
     const hipError_t e = launch_kernel_r3(id, a, t, s, &handled);
     if (handled) return e;

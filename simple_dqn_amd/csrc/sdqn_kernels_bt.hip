@@ -750,9 +750,9 @@ hipError_t launch_kernel_bt(int id, const StepArgs& a, const LaunchTune& t, hipS
       typedef BtCfgHW<Conv3WgradH, 64, 64, 2, 2, 2> HC3W;
       typedef BtCfgHW<Conv2WgradH, 64, 64, 2, 2, 2> HC2W;
       *handled = true;
-      // r3 bit 4 (the step orchestration's decision, sdqn_api_step.hip): conv1's weight gradient rides in this launch and K_BWD1 launches nothing;
-      // bit 5: its workgroups first in the block-id order
-      if (t.r3 & 16) return launch_bt_multi_c1w<HF4W, HC3W, HC2W>(a, (t.r3 & 32) ? 1 : 0, s);
+      // LV_C1W_IN_WGRADS (the step orchestration's decision, sdqn_api_step.hip): conv1's weight gradient rides in this launch and K_BWD1 launches nothing;
+      // LV_C1W_FIRST: its workgroups first in the block-id order
+      if (t.variant & LV_C1W_IN_WGRADS) return launch_bt_multi_c1w<HF4W, HC3W, HC2W>(a, (t.variant & LV_C1W_FIRST) ? 1 : 0, s);
       if (t.bt[id] == 1) return launch_bt_multi<BtCfgHW<Fc4WgradH, 64, 64, 2, 2, 4>, BtCfgHW<Conv3WgradH, 64, 64, 2, 2, 4>, BtCfgHW<Conv2WgradH, 64, 64, 2, 2, 4>>(a, true, true, true, s);
       if (t.bt[id] == 2) return launch_bt_multi<BtCfgHW<Fc4WgradH, 64, 64, 2, 2, 3>, BtCfgHW<Conv3WgradH, 64, 64, 2, 2, 3>, BtCfgHW<Conv2WgradH, 64, 64, 2, 2, 3>>(a, true, true, true, s);
       return launch_bt_multi<HF4W, HC3W, HC2W>(a, true, true, true, s);
@@ -761,7 +761,7 @@ hipError_t launch_kernel_bt(int id, const StepArgs& a, const LaunchTune& t, hipS
       *handled = true;
       return launch_conv1_h(a, t, s);
     }
-    if (id == K_BWD1 && (t.r3 & 16)) { *handled = true; return hipSuccess; }      // (rode in the weight-gradient launch)
+    if (id == K_BWD1 && (t.variant & LV_C1W_IN_WGRADS)) { *handled = true; return hipSuccess; }      // (rode in the weight-gradient launch)
     if (id == K_BWD1 && a.h16 == 2 && a.f4w_count == 0) {    // conv1's weight gradient: all 256 x 32 outputs of a K slab per workgroup, A from the bytes
       // (the generic half routine with A from the bytes — BtCfgHW<Conv1WgradH, 256, 32, 4, 1> — fetches 8-byte patch-row pieces straight
       //  from memory: 16 divergent loads per thread and chunk, 18.9 us at B = 256, no better than the wave-tile routine's 18.7)

@@ -105,8 +105,8 @@ hipError_t launch_kernel_ss(int id, const StepArgs& a, const LaunchTune& t, hipS
 #ifdef SDQN_TIMING
   if (const char* e = getenv("SDQN_SS_DBG")) c2.dbg = c3.dbg = atoi(e);
 #endif
-  c2.in = a.a1; c2.out = a.a2; c2.w[0] = a.theta[0] + OFF2; c2.w[1] = a.theta[a.nz > 1 ? 1 : 0] + OFF2; c2.wt = t.wt & 1;
-  c3.in = a.a2; c3.out = a.a3; c3.w[0] = a.theta[0] + OFF3; c3.w[1] = a.theta[a.nz > 1 ? 1 : 0] + OFF3; c3.wt = (t.wt >> 1) & 1;
+  c2.in = a.a1; c2.out = a.a2; c2.w[0] = a.theta[0] + OFF2; c2.w[1] = a.theta[a.nz > 1 ? 1 : 0] + OFF2; c2.wt = (t.wt & WT_CONV2_FWD) ? 1 : 0;
+  c3.in = a.a2; c3.out = a.a3; c3.w[0] = a.theta[0] + OFF3; c3.w[1] = a.theta[a.nz > 1 ? 1 : 0] + OFF3; c3.wt = (t.wt & WT_CONV3_FWD) ? 1 : 0;
   if (chain) {
     ss::ChainArgs cc; cc.l1 = c2; cc.l2 = c3;
     return ns == 2 ? ss::launch_chain<C2S2, C3S2>(cc, a.nz, s) : ss::launch_chain<C2S1, C3S1>(cc, a.nz, s);

@@ -439,11 +439,6 @@ static void per_targets(sdqn_net_s* h, sdqn_replay_s* r, PerStepArgs& a) {
   if (h->gen) { a.idx_out = nullptr; a.actions = r->d_act; a.rewards = r->d_rew; a.terminals = r->d_term; }
   else { a.idx_out = h->d_idx; a.actions = h->st_act; a.rewards = h->st_rew; a.terminals = h->st_term; }
 }
-static int per_check_geometry(sdqn_net_s* h, sdqn_replay_s* r) {
-  if (h->gen) ARGCHK((size_t)r->state == h->gen->state_bytes(), "replay geometry (%dx%d, history %d) differs from the network's", r->H, r->W, r->hist);
-  else ARGCHK(r->tuned_geom, "replay geometry (%dx%d, history %d) differs from the network's (84x84, 4)", r->H, r->W, r->hist);
-  return SDQN_OK;
-}
 // generic path: gather the sampled minibatch and run one weighted step on it
 static int per_gen_step(sdqn_net_s* h, sdqn_replay_s* r) {
   PerState* p = r->per;
@@ -455,51 +450,35 @@ static int per_gen_step(sdqn_net_s* h, sdqn_replay_s* r) {
   h->train_iterations += 1;
   return SDQN_OK;
 }
-
+// one step on the minibatch the last sampling launch left (host_idx: run_ring_step)
+static int per_train_step(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* host_idx) {
+  return h->gen ? per_gen_step(h, r) : run_ring_step(h, r, host_idx, per_head(h, r->per));
+}
+// (sdqn_net_train_many / sdqn_net_train_replay have checked batch size, n-step settings and geometry; the former has cleared the cost sum)
 // n steps: [refresh + sample 0] | step 0 | [write-back 0 + sample 1] | step 1 | ... | step n-1 | [write-back n-1]
 int per_train_many(sdqn_net_s* h, sdqn_replay_s* r, uint32_t* mt, int n_steps, float* mean_cost) {
-  int rc = per_check_geometry(h, r); if (rc) return rc;
   PerState* p = r->per;
-  if (h->gen) GENCHK(h->gen->reset_cost_sum());
-  else if (n_steps == 0) HIPCHK(hipMemsetAsync(h->cost_accum, 0, 8, g_stream));
   if (n_steps > 0) {
     ARGCHK(r->count >= r->hist + r->ns.n, "replay memory holds %lld screens: at least history_length + n_step = %d needed", (long long)r->count, r->hist + r->ns.n);
     std::vector<double> u((size_t)r->B);
-    PerStepArgs a; rc = per_begin(r, a, h); if (rc) return rc;
+    PerStepArgs a; int rc = per_begin(r, a, h); if (rc) return rc;
     per_targets(h, r, a);
     PerStepArgs s0 = a; s0.mode = 1; s0.zero8 = h->gen ? nullptr : h->cost_accum;
     per_draw(mt, r->B, u.data());
     LAUNCH(K_PREP, per_launch_step(s0, u.data(), g_stream));
     for (int i = 0; i < n_steps; ++i) {
-      if (h->gen) { rc = per_gen_step(h, r); if (rc) return rc; }
-      else {
-        StepArgs sa = step_args(h); sa.from_ring = 1; sa.src = r->d_ring; sa.idx = h->d_idx;
-        h->host_idx_cur = nullptr;                                     // conv1 reads the device-sampled indexes from HBM
-        rc = run_train(h, sa, per_head(h, p), nullptr); if (rc) return rc;
-      }
+      rc = per_train_step(h, r, nullptr); if (rc) return rc;
       PerStepArgs wb = per_writeback(a, p);
       if (i + 1 < n_steps) { wb.mode = 1; per_draw(mt, r->B, u.data()); }
       LAUNCH(K_PREP, per_launch_step(wb, u.data(), g_stream));
     }
     p->sample_live = p->gathered = false;
   }
-  if (mean_cost) {
-    if (h->gen) {
-      double sum; GENCHK(h->gen->read_cost_sum(&sum));
-      rc = per_check(r); if (rc) return rc;
-      *mean_cost = n_steps ? (float)(sum / n_steps) : 0.0f;
-      return SDQN_OK;
-    }
-    HIPCHK(hipMemcpyAsync(h->h_f, h->cost_accum, 8, hipMemcpyDeviceToHost, g_stream));
-    rc = per_sync_check(r); if (rc) return rc;
-    *mean_cost = n_steps ? (float)(*(double*)h->h_f / n_steps) : 0.0f;
-  }
-  return SDQN_OK;
+  return mean_cost ? read_mean_cost(h, n_steps, mean_cost) : SDQN_OK;
 }
 // given indexes (sdqn_net_train_replay): weights from their raw priorities, then the step, then the write-back
 int per_train_replay(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* idx_host, float* cost_out) {
-  int rc = per_check_geometry(h, r); if (rc) return rc;
-  rc = check_ring_actions(h, r, idx_host); if (rc) return rc;
+  int rc = check_ring_actions(h, r, idx_host); if (rc) return rc;
   for (int i = 0; i < r->B; ++i)
     ARGCHK(idx_host[i] >= r->hist && idx_host[i] + r->ns.n - 1 < r->count, "index %lld out of range (count %lld, n_step %d)", (long long)idx_host[i], (long long)r->count, r->ns.n);
   PerState* p = r->per;
@@ -507,20 +486,10 @@ int per_train_replay(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* idx_host, f
   per_targets(h, r, a);
   PerStepArgs s0 = a; s0.mode = 2;
   LAUNCH(K_PREP, per_launch_step(s0, reinterpret_cast<const double*>(idx_host), g_stream));
-  if (h->gen) { rc = per_gen_step(h, r); if (rc) return rc; }
-  else {
-    StepArgs sa = step_args(h); sa.from_ring = 1; sa.src = r->d_ring; sa.idx = h->d_idx;
-    h->host_idx_cur = idx_host;
-    rc = run_train(h, sa, per_head(h, p), nullptr);
-    h->host_idx_cur = nullptr;
-    if (rc) return rc;
-  }
+  rc = per_train_step(h, r, idx_host); if (rc) return rc;
   LAUNCH(K_PREP, per_launch_step(per_writeback(a, p), nullptr, g_stream));
   p->sample_live = p->gathered = false;
-  if (cost_out) {
-    if (h->gen) { double c; GENCHK(h->gen->read_cost(&c)); *cost_out = (float)c; }
-    else { rc = read_cost(h, cost_out); if (rc) return rc; }
-  }
+  if (cost_out) { rc = read_cost(h, cost_out); if (rc) return rc; }
   return per_sync_check(r);
 }
 // sdqn_net_train_host on the memory's own device minibatch, gathered from its last prioritized sample: the weights of that sample.  The

@@ -276,6 +276,20 @@ class DeepQNetwork:
         env._stepped(t.value)
         return r.value, bool(t.value)
 
+    def _play(self, fn, head, n, steps, trace):
+        """evaluate() / collect(): library call fn(*head, <five tally arrays [n]>, <four trace arrays or NULLs>) -> the dict both return."""
+        tallies = ("steps", "reward", "caught", "missed", "episodes")
+        out = dict((k, np.zeros(n, dtype=np.int64)) for k in tallies)
+        tr = [None] * 4
+        if trace:
+            acts, rews = np.zeros((steps, n), np.uint8), np.zeros((steps, n), np.int8)
+            terms, q = np.zeros((steps, n), np.uint8), np.zeros((steps, n, self.num_actions), np.float64)
+            tr = [_lib.ptr(acts, C.c_uint8), _lib.ptr(rews, C.c_int8), _lib.ptr(terms, C.c_uint8), _lib.ptr(q, C.c_double)]
+        _lib.check(fn(*(list(head) + [_lib.ptr(out[k], C.c_int64) for k in tallies] + tr)))
+        if trace:
+            out.update(actions=acts, rewards=rews, terminals=terms.astype(bool), q=q.astype(self._np))     # (float32 -> double -> float32: exact)
+        return out
+
     def evaluate(self, env, num_envs, steps, epsilon=0.05, seed=0, trace=False):
         """Vectorised evaluation on the device: `num_envs` (<= batch_size) independent copies of `env`'s game (its geometry and
         balls_per_episode; env itself is not stepped), `steps` steps each, epsilon-greedy on the online net — per step one batched
@@ -283,17 +297,8 @@ class DeepQNetwork:
         caught, missed, episodes; with trace=True also actions / rewards / terminals [steps, num_envs] and q [steps, num_envs, A]
         (the network's precision; float64 for a float64 network)."""
         n, steps = int(num_envs), int(steps)
-        out = dict((k, np.zeros(n, dtype=np.int64)) for k in ("steps", "reward", "caught", "missed", "episodes"))
-        tr = [None] * 4
-        if trace:
-            acts, rews = np.zeros((steps, n), np.uint8), np.zeros((steps, n), np.int8)
-            terms, q = np.zeros((steps, n), np.uint8), np.zeros((steps, n, self.num_actions), np.float64)
-            tr = [_lib.ptr(acts, C.c_uint8), _lib.ptr(rews, C.c_int8), _lib.ptr(terms, C.c_uint8), _lib.ptr(q, C.c_double)]
-        _lib.check(self._lib.sdqn_env_eval(self._h, env._h, n, steps, float(epsilon), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                           *([_lib.ptr(out[k], C.c_int64) for k in ("steps", "reward", "caught", "missed", "episodes")] + tr)))
-        if trace:
-            out.update(actions=acts, rewards=rews, terminals=terms.astype(bool), q=q.astype(self._np))     # (float32 -> double -> float32: exact)
-        return out
+        head = (self._h, env._h, n, steps, float(epsilon), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        return self._play(self._lib.sdqn_env_eval, head, n, steps, trace)
 
     def collect(self, env, mem, num_envs, locksteps, epsilon=1.0, epsilon_step=0.0, seed=None, trace=False):
         """--train_envs: `locksteps` locksteps of `num_envs` copies of `env`'s game, every lockstep's num_envs transitions
@@ -304,18 +309,8 @@ class DeepQNetwork:
         (with trace=True also actions / rewards / terminals [locksteps, num_envs] and q [locksteps, num_envs, A])."""
         n, steps = int(num_envs), int(locksteps)
         mem._check_mirror()                                        # (slots edited through the numpy views reach the mirror first)
-        out = dict((k, np.zeros(n, dtype=np.int64)) for k in ("steps", "reward", "caught", "missed", "episodes"))
-        tr = [None] * 4
-        if trace:
-            acts, rews = np.zeros((steps, n), np.uint8), np.zeros((steps, n), np.int8)
-            terms, q = np.zeros((steps, n), np.uint8), np.zeros((steps, n, self.num_actions), np.float64)
-            tr = [_lib.ptr(acts, C.c_uint8), _lib.ptr(rews, C.c_int8), _lib.ptr(terms, C.c_uint8), _lib.ptr(q, C.c_double)]
-        _lib.check(self._lib.sdqn_env_collect(self._h, env._h, mem._h, n, steps, float(epsilon), float(epsilon_step),
-                                              -1 if seed is None else int(seed) & 0x7FFFFFFFFFFFFFFF,
-                                              *([_lib.ptr(out[k], C.c_int64) for k in ("steps", "reward", "caught", "missed", "episodes")] + tr)))
-        if trace:
-            out.update(actions=acts, rewards=rews, terminals=terms.astype(bool), q=q.astype(self._np))
-        return out
+        head = (self._h, env._h, mem._h, n, steps, float(epsilon), float(epsilon_step), -1 if seed is None else int(seed) & 0x7FFFFFFFFFFFFFFF)
+        return self._play(self._lib.sdqn_env_collect, head, n, steps, trace)
 
     def load_weights(self, load_path):                             # :188-189
         """Own .npz snapshots, or a Neon pickle (the reference's `model.load_params`, best effort: neon_compat.py)."""

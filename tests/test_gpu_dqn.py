@@ -258,6 +258,46 @@ def test_train_replay_equals_train_host(sd):
         assert np.array_equal(n1.get_layer(i), n2.get_layer(i)), i
 
 
+def test_uniform_train_many_launch_sequence_and_generic_mean_cost(sd):
+    """train_from_memory(mem, 5) on the uniform path, one call.  Tuned (float32, B = 32): step 0's prep is the only standalone one — every
+    later step's rides in the update launch before it — and each step is the ten launches of the fused structure; nothing else is
+    launched.  Generic (float64, B = 8): the call's mean cost is the mean of the five single-step costs of a twin trained index by index."""
+    A, size = 4, 2000
+    args = make_args(batch_size=32)
+    mem = sd.ReplayMemory(size, args)
+    synthetic_fill(mem, 3, num_actions=A)
+    mem.sync_mirror()
+    net, _ = _pair(sd, A, 32, 31)
+    net.profile(True, -1); net.profile_reset()
+    random.seed(9)
+    net.train_from_memory(mem, 5)
+    counts = {p["name"].split("(")[0]: p["launches"] for p in net.profile_read() if p["launches"] > 0}
+    net.profile(False)
+    print("launches of one train_from_memory(mem, 5):", counts)
+    want = dict((k, 5) for k in ("conv1_fwd", "conv2_fwd", "conv3_fwd", "fc4_fwd", "head", "fc4_dgrad", "bwd3", "bwd2", "bwd1", "update"))
+    want["prep"] = 1
+    assert counts == want
+
+    args8 = make_args(batch_size=8, datatype="float64")
+    mem8 = sd.ReplayMemory(size, args8)
+    synthetic_fill(mem8, 3, num_actions=A)
+    mem8.sync_mirror()
+    ws, wt = xavier_weights(A, 31, np.float64), xavier_weights(A, 32, np.float64)
+    nets = []
+    for _ in range(2):
+        n = sd.DeepQNetwork(A, args8)
+        n.set_weights(wt, 1); n.set_weights(ws, 0)
+        nets.append(n)
+    assert nets[0].step_structure()[0] == "generic"
+    random.seed(9)
+    mean = nets[0].train_from_memory(mem8, 5, want_cost=True)
+    random.seed(9)
+    costs = [nets[1].train_indexes(mem8, mem8.sample_indexes(), want_cost=True) for _ in range(5)]
+    print("mean cost %r, single-step costs %r" % (mean, costs))
+    assert np.isfinite(mean)
+    assert abs(mean - np.mean(costs)) < 1e-6 * max(1.0, abs(np.mean(costs)))      # (test_gpu_generic.py's cost tolerance)
+
+
 def test_fused_and_unfused_paths_bit_identical(sd):
     """fc4 RMSProp fused into the wgrad epilogue, the multi-problem backward launches and the XCD-contiguous placement must give
     bit-identical weights to the plain one-launch-per-problem, materialised-gradient path; the step structures retired in round 5

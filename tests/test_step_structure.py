@@ -28,7 +28,7 @@ def sd():
 def test_every_reachable_combination_takes_the_tabulated_structure(sd):
     from simple_dqn_amd.deepqnetwork import dp_unique_id
     seen = set()
-    for B, datatype, bn, dp, fused in itertools.product((32, 256), ("float32", "float16"), (False, True), ("none", "serial", "overlap", "grad_only"), (1, 0)):
+    for B, datatype, bn, dp, fused in itertools.product((32, 33, 127, 128, 256, 257, 512), ("float32", "float16"), (False, True), ("none", "serial", "overlap", "grad_only"), (1, 0)):
         if bn and datatype == "float16":
             continue                                             # refused at creation (--batch_norm with float16)
         net = sd.DeepQNetwork(3, make_args(batch_size=B, datatype=datatype, batch_norm=bn))

@@ -27,7 +27,7 @@ def _net(sd, A, seed, B=32):
     return net
 
 
-@pytest.mark.parametrize("A", [3, 4, 6, 18])
+@pytest.mark.parametrize("A", [1, 3, 4, 6, 7, 8, 9, 17, 18])
 def test_one_launch_forward_matches_the_oracle_and_the_five_launch_forward(sd, A):
     net = _net(sd, A, 500 + A)
     orc = OracleDQN(A, batch_size=1, weights=xavier_weights(A, 500 + A))

@@ -175,6 +175,7 @@ struct sdqn_net_s {
   int wt = WT_ALL;                         // write-through epilogue stores, bit per launch (kernels.h: WriteThrough)
   int conv1w_bf16 = 1;                 // round 3: conv1_wgrad on packed-bf16 MFMA (bytes x on-the-fly bf16 split of delta1)
   bool conv3_c36 = true;                   // round 3: conv3_fwd on 36-deep K-chunks (one chunk per wave; sdqn_kernels_r3.hip)
+  bool arg_preload = true;                 // the B < 128 fp32 step kernels take their hot arguments from the leading block (gemm_engine.h: Lead); 0: from the struct
   bool fused_launches = true;              // independent backward stages share one launch (K_BWD3, K_BWD2)
   // profiler
   bool prof_on = false; int prof_filter = -1;

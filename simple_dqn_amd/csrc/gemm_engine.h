@@ -55,6 +55,47 @@ template <class P, class = void> struct has_preload { static constexpr bool valu
 template <class P> struct has_preload<P, decltype((void)P::PRELOAD)> { static constexpr bool value = P::PRELOAD; };
 template <class P, class = void> struct has_preload_multi { static constexpr bool value = false; };
 template <class P> struct has_preload_multi<P, decltype((void)P::PRELOAD_MULTI)> { static constexpr bool value = P::PRELOAD_MULTI; };
+// LEAD: the launch's hot arguments a second time, as LEADING scalar / pointer kernel parameters in front of the by-value StepArgs.  gfx950's
+// command processor can place the first 14 argument dwords in user SGPRs at wave launch (-mllvm -amdgpu-kernarg-preload-count, csrc/Makefile;
+// a by-value struct is never preloaded), so a wave forms the addresses of its first vector loads without the scalar round trip to the cold
+// kernel-argument segment that P::preload batches.  The block is 16 dwords (the struct keeps its 64-byte phase): five operand pointers the
+// problem names (SDQN_LEAD_FIELDS), B, two launch scalars and a control word; the last two dwords are padding.  With the control word's
+// LEAD_ON bit clear (option arg_preload = 0) the kernel takes the same values from the struct behind P::preload, as before: same bits.
+// What each kernel packs (host) and unpacks (device) — one row per pack / unpack pair:
+//   kernel                   p[0..4]                          B slot            s0                        s1            ctl
+//   gemm_kernel, gemm36      SDQN_LEAD_FIELDS of the problem  B                 gx | gy << 16 | gz << 24   field X       lead_ctl
+//   gemm_multi_kernel        SDQN_LEAD_FIELDS of problem 1    B                 n[0] | n[1] << 16          field X       lead_ctl
+//   head_kernel              theta[0], theta[1], slab4, a4, d4  B               A                         -             lead_ctl
+//   conv1_bf16_kernel        src, a1, w1p[0], w1p[1], idx     B                 tiles_per_net             wgs_per_net   xcd | pad_ << 1 | from_ring << 2 | tpw << 4 | LEAD_ON | post_off << 16
+//   conv1_wgrad_bf16_kernel  src, d1, slab1, idx, -           B                 tps1                      Kt            xcd | pad_ << 1 | from_ring << 2 | LEAD_ON | grid z << 16
+//   update_kernel            theta, state, slab[0..2]         ns[0] | ns[1] << 16  ns[2]                  A | mode << 8 | only_fc4 << 12   LEAD_ON
+// lead_ctl = xcd_map [0, 8) | LEAD_ON | nz [12, 16) | S4 [16, 24).  Every host pack clears LEAD_ON when a value does not fit its bits or B >= 128.
+struct Lead { const void* p[5]; int B, s0, s1, ctl, r0, r1; };
+static_assert(sizeof(Lead) == 64, "leading block: 16 dwords");
+constexpr int LEAD_ON = 256;                 // ctl: xcd_map [0, 8) | LEAD_ON | nz [12, 16) | S4 [16, 24)
+#define SDQN_LEAD_PARAMS const void* lp0, const void* lp1, const void* lp2, const void* lp3, const void* lp4, int lB, int ls0, int ls1, int lctl, int lr0, int lr1
+#define SDQN_LEAD_ARGS(L) (L).p[0], (L).p[1], (L).p[2], (L).p[3], (L).p[4], (L).B, (L).s0, (L).s1, (L).ctl, (L).r0, (L).r1
+template <class T> struct lead_noref { typedef T type; };
+template <class T> struct lead_noref<T&> { typedef T type; };
+#define SDQN_LEAD_SET_(f, v) a.f = (typename lead_noref<decltype(a.f)>::type)(v)
+// the five pointer fields of StepArgs a problem (or a whole multi-problem launch) wants in SGPRs at wave launch; X = one more int field
+#define SDQN_LEAD_FIELDS(f0, f1, f2, f3, f4, X) \
+  static void lead_pack(const StepArgs& a, Lead& l) { l.p[0] = a.f0; l.p[1] = a.f1; l.p[2] = a.f2; l.p[3] = a.f3; l.p[4] = a.f4; l.s1 = a.X; } \
+  __device__ static void lead_apply(StepArgs& a, const void* q0, const void* q1, const void* q2, const void* q3, const void* q4, int x) { \
+    SDQN_LEAD_SET_(f0, q0); SDQN_LEAD_SET_(f1, q1); SDQN_LEAD_SET_(f2, q2); SDQN_LEAD_SET_(f3, q3); SDQN_LEAD_SET_(f4, q4); a.X = x; }
+template <class P, class = void> struct has_lead { static constexpr bool value = false; };
+template <class P> struct has_lead<P, decltype((void)P::LEAD)> { static constexpr bool value = P::LEAD; };
+template <class P, class = void> struct has_lead_multi { static constexpr bool value = false; };
+template <class P> struct has_lead_multi<P, decltype((void)P::LEAD_MULTI)> { static constexpr bool value = P::LEAD_MULTI; };
+inline int lead_grid(const dim3& g) { return (int)(g.x | g.y << 16 | g.z << 24); }          // s0 of a single-problem launch: gx [0, 16) | gy [16, 24) | gz [24, 31)
+inline bool lead_grid_fits(const dim3& g) { return g.x < 65536u && g.y < 256u && g.z < 128u; }
+// (the block is for the latency regime, B < 128; a field that does not fit its bits clears LEAD_ON too: the kernel then reads the struct)
+inline int lead_ctl(const StepArgs& a, bool on) {
+  const bool fits = a.B < 128 && a.xcd_map >= 0 && a.xcd_map < 256 && a.nz >= 0 && a.nz < 16 && a.S4 >= 0 && a.S4 < 256;
+  return (a.xcd_map & 255) | (on && fits ? LEAD_ON : 0) | ((a.nz & 15) << 12) | ((a.S4 & 255) << 16);
+}
+__device__ __forceinline__ void lead_scalars(StepArgs& a, int B, int ctl) { a.B = B; a.xcd_map = ctl & 255; a.nz = (ctl >> 12) & 15; a.S4 = (ctl >> 16) & 255; }
+#define SDQN_LEAD_FWD lp0, lp1, lp2, lp3, lp4, lB, ls0, ls1, lctl, lr0, lr1
 template <class P, class = void> struct uses_f16_mfma { static constexpr bool value = false; };
 template <class P> struct uses_f16_mfma<P, decltype((void)P::F16_MFMA)> { static constexpr bool value = P::F16_MFMA; };
 
@@ -573,15 +614,34 @@ template <class P> constexpr int tile_n() { return 32; }
 
 // (xcd_tile_id / xcd_tile_id_range, the XCD-aware workgroup -> tile maps: problems.h — host + device, tests/emul executes them)
 
+// a single-problem launch's arguments: a = the struct patched from the leading block and the tile grid from s0 (LEAD_ON), or the struct
+// behind P::preload and the launch grid
+template <class P>
+__device__ __forceinline__ void lead_take(StepArgs& a, int& gx, int& gy, int& gz, const StepArgs& a_, SDQN_LEAD_PARAMS) {
+  (void)lr0; (void)lr1;
+  if (lctl & LEAD_ON) { lead_scalars(a, lB, lctl); P::lead_apply(a, lp0, lp1, lp2, lp3, lp4, ls1); gx = ls0 & 0xFFFF; gy = (ls0 >> 16) & 255; gz = ls0 >> 24; }
+  else { if constexpr (has_preload<P>::value) P::preload(a_, gridDim.x, gridDim.y, gridDim.z); gx = gridDim.x; gy = gridDim.y; gz = gridDim.z; }
+}
 template <class P, int NW>
-__global__ void __launch_bounds__(NW * 64) gemm_kernel(const StepArgs a) {
-  __shared__ float smem[tile_lds_any<P, NW>()];
-  if constexpr (has_preload<P>::value) P::preload(a, gridDim.x, gridDim.y, gridDim.z);
-  const int gx = gridDim.x, gy = gridDim.y;
+__device__ __forceinline__ void gemm_kernel_body(const StepArgs& a, int gx, int gy, int gz, float* smem) {
   const int lin = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-  const int t = (a.xcd_map & 1) ? xcd_tile_id(lin, gx * gy * gridDim.z) : lin;
+  const int t = (a.xcd_map & 1) ? xcd_tile_id(lin, gx * gy * gz) : lin;
   const int bz = t / (gx * gy), r = t - bz * (gx * gy);
   run_tile<P, NW, NW * 64>(a, r % gx, r / gx, bz, smem);
+}
+template <class P, int NW>
+__global__ void __launch_bounds__(NW * 64) gemm_kernel(SDQN_LEAD_PARAMS, const StepArgs a_) {
+  __shared__ float smem[tile_lds_any<P, NW>()];
+  (void)lr0; (void)lr1;
+  if constexpr (has_lead<P>::value) {
+    StepArgs a = a_;
+    int gx, gy, gz;
+    lead_take<P>(a, gx, gy, gz, a_, SDQN_LEAD_FWD);
+    gemm_kernel_body<P, NW>(a, gx, gy, gz, smem);
+  } else {
+    if constexpr (has_preload<P>::value) P::preload(a_, gridDim.x, gridDim.y, gridDim.z);
+    gemm_kernel_body<P, NW>(a_, gridDim.x, gridDim.y, gridDim.z, smem);
+  }
 }
 
 // ---- several independent problems in ONE launch -------------------------------------------------------
@@ -611,18 +671,38 @@ __device__ __forceinline__ void multi_dispatch(const StepArgs& a, const MultiDim
 }
 
 template <int NT, class P0, int NW0, class P1, int NW1, class P2, int NW2>
-__global__ void __launch_bounds__(NT) gemm_multi_kernel(const StepArgs a, const MultiDims d) {
-  // (a one-tile-per-wave problem needs one region per wave of the workgroup)
-  constexpr int L0 = tile_lds_any<P0, NW0>() * (NW0 == 1 ? NT / 64 : 1), L1 = tile_lds_any<P1, NW1>() * (NW1 == 1 ? NT / 64 : 1),
-                L2 = tile_lds_any<P2, NW2>() * (NW2 == 1 ? NT / 64 : 1);
-  constexpr int L = L0 > L1 ? (L0 > L2 ? L0 : L2) : (L1 > L2 ? L1 : L2);
-  __shared__ float smem[L];
-  if constexpr (has_preload_multi<P1>::value) P1::preload_multi(a, d);      // (one statement for the whole launch: every field of all its problems)
+__device__ __forceinline__ void gemm_multi_body(const StepArgs& a, const MultiDims& d, float* smem) {
   const int b = blockIdx.x;                               // problem choice is workgroup-uniform; XCD-contiguous runs per problem
   const int xm = a.xcd_map;                               // bit i: problem i of the launch uses the XCD-contiguous map
   if (b < d.n[0]) multi_dispatch<P0, NW0, NT>(a, d, 0, (xm & 1) ? xcd_tile_id_range(b, 0, d.n[0]) : b, smem);
   else if (b < d.n[0] + d.n[1]) multi_dispatch<P1, NW1, NT>(a, d, 1, (xm & 2) ? xcd_tile_id_range(b, d.n[0], d.n[1]) : b - d.n[0], smem);
   else multi_dispatch<P2, NW2, NT>(a, d, 2, (xm & 4) ? xcd_tile_id_range(b, d.n[0] + d.n[1], d.n[2]) : b - d.n[0] - d.n[1], smem);
+}
+template <int NT, class P0, int NW0, class P1, int NW1, class P2, int NW2>
+__global__ void __launch_bounds__(NT) gemm_multi_kernel(SDQN_LEAD_PARAMS, const StepArgs a_, const MultiDims d_) {
+  // (a one-tile-per-wave problem needs one region per wave of the workgroup)
+  constexpr int L0 = tile_lds_any<P0, NW0>() * (NW0 == 1 ? NT / 64 : 1), L1 = tile_lds_any<P1, NW1>() * (NW1 == 1 ? NT / 64 : 1),
+                L2 = tile_lds_any<P2, NW2>() * (NW2 == 1 ? NT / 64 : 1);
+  constexpr int L = L0 > L1 ? (L0 > L2 ? L0 : L2) : (L1 > L2 ? L1 : L2);
+  __shared__ float smem[L];
+  (void)lr0; (void)lr1;
+  if constexpr (has_lead_multi<P1>::value) {
+    // leading block of a multi-problem launch: s0 = workgroups of problem 0 | problem 1 << 16; the tile grids follow from B
+    StepArgs a = a_; MultiDims d = d_;
+    if (lctl & LEAD_ON) {
+      lead_scalars(a, lB, lctl); P1::lead_apply(a, lp0, lp1, lp2, lp3, lp4, ls1);
+      d.n[0] = ls0 & 0xFFFF; d.n[1] = (int)((unsigned)ls0 >> 16);
+      // (multi_fill's formulas.  d.n[2] stays the struct's: its one reader is xcd_tile_id_range in problem 2's branch of gemm_multi_body — the
+      //  choice of the problem compares b with n[0] and n[0] + n[1] only — and problem 2's workgroups wait for their own scalars anyway)
+      d.gx[0] = (P0::M(a) + tile_m<P0>() - 1) / tile_m<P0>(); d.gy[0] = (P0::N(a) + tile_n<P0>() - 1) / tile_n<P0>();
+      d.gx[1] = (P1::M(a) + tile_m<P1>() - 1) / tile_m<P1>(); d.gy[1] = (P1::N(a) + tile_n<P1>() - 1) / tile_n<P1>();
+      d.gx[2] = (P2::M(a) + tile_m<P2>() - 1) / tile_m<P2>(); d.gy[2] = (P2::N(a) + tile_n<P2>() - 1) / tile_n<P2>();
+    } else { if constexpr (has_preload_multi<P1>::value) P1::preload_multi(a_, d_); }
+    gemm_multi_body<NT, P0, NW0, P1, NW1, P2, NW2>(a, d, smem);
+  } else {
+    if constexpr (has_preload_multi<P1>::value) P1::preload_multi(a_, d_);      // (one statement for the whole launch: every field of all its problems)
+    gemm_multi_body<NT, P0, NW0, P1, NW1, P2, NW2>(a_, d_, smem);
+  }
 }
 
 struct NoProblem {            // placeholder third problem for two-problem launches (never dispatched: n[2] = 0)
@@ -650,7 +730,12 @@ struct NoProblem {            // placeholder third problem for two-problem launc
 template <class P, int NW>
 inline hipError_t launch_gemm(const StepArgs& a, hipStream_t stream) {
   dim3 grid((P::M(a) + tile_m<P>() - 1) / tile_m<P>(), (P::N(a) + tile_n<P>() - 1) / tile_n<P>(), P::nbz(a));
-  SDQN_LAUNCH((gemm_kernel<P, NW>), grid, dim3(NW * 64), 0, stream, a);
+  Lead l; memset(&l, 0, sizeof l);
+  if constexpr (has_lead<P>::value) {                       // (the tile grid rides packed in one dword: a larger grid reads the struct)
+    P::lead_pack(a, l); l.B = a.B; l.s0 = lead_grid(grid);
+    l.ctl = lead_ctl(a, a.arg_preload && lead_grid_fits(grid));
+  }
+  SDQN_LAUNCH((gemm_kernel<P, NW>), grid, dim3(NW * 64), 0, stream, SDQN_LEAD_ARGS(l), a);
   return hipGetLastError();
 }
 
@@ -668,7 +753,12 @@ inline hipError_t launch_multi(const StepArgs& a, bool has1, bool has2, hipStrea
   if (has1) multi_fill<NT, P1, NW1>(a, d, 1);
   if (has2) multi_fill<NT, P2, NW2>(a, d, 2);
   if (d.n[0] + d.n[1] + d.n[2] == 0) return hipSuccess;
-  SDQN_LAUNCH((gemm_multi_kernel<NT, P0, NW0, P1, NW1, P2, NW2>), dim3(d.n[0] + d.n[1] + d.n[2]), dim3(NT), 0, stream, a, d);
+  Lead l; memset(&l, 0, sizeof l);
+  if constexpr (has_lead_multi<P1>::value) {
+    P1::lead_pack(a, l); l.B = a.B; l.s0 = (int)((unsigned)d.n[0] | (unsigned)d.n[1] << 16);
+    l.ctl = lead_ctl(a, a.arg_preload && has1 && has2 && d.n[0] < 65536 && d.n[1] < 65536);
+  }
+  SDQN_LAUNCH((gemm_multi_kernel<NT, P0, NW0, P1, NW1, P2, NW2>), dim3(d.n[0] + d.n[1] + d.n[2]), dim3(NT), 0, stream, SDQN_LEAD_ARGS(l), a, d);
   return hipGetLastError();
 }
 

@@ -86,7 +86,8 @@ struct UpdateArgs {
   half_t* wh;                   // fp16 mode: half copies of theta refreshed by the update (master layout / transposed)
   half_t* wht;
   unsigned short* w1p;          // conv1's three bf16 planes of the ONLINE net, rewritten with W1 (nullptr: not maintained)
-  int reserved_[4];             // (retired options' fields: every other field keeps its offset — update_kernel preloads them by name)
+  int arg_preload;              // 1: update_kernel's leading parameter block is live (gemm_engine.h: Lead), 0: it reads this struct
+  int reserved_[3];             // (retired options' fields: every other field keeps its offset — update_kernel preloads them by name)
   int wt;                       // 1: the new parameters / optimizer state leave with write-through (sc1) stores
   int reserved2_[3];
   int64_t bn_first;             // --batch_norm: element offset of the [beta|gamma] block (bn_update_kernel); BN_PARAMS elements

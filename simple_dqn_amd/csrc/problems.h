@@ -129,7 +129,8 @@ struct StepArgs {
   int h16;                         // 1: fp16 mode
   int xcd_map;              // XCD-contiguous workgroup->tile map (cuts fabric traffic to ~algorithmic): bit i = problem i of the launch
   int post_off;             // ring frames from a prestate to its poststate: --n_step (1 = replay_memory.py:71-72; problems.h soff)
-  int reserved_[11];        // (keeps the field offsets of the round-1 layout: the scalar-load schedule hipcc derives from them is part of
+  int arg_preload;          // 1: the launch's leading argument block is live (gemm_engine.h: Lead; option "arg_preload"), 0: kernels read the struct
+  int reserved_[10];        // (keeps the field offsets of the round-1 layout: the scalar-load schedule hipcc derives from them is part of
                             //  the tuned kernels — a re-packed struct measured 1 % slower; host-only tuning lives in LaunchTune, kernels.h)
   float* __restrict__ theta_w;   // online parameters, writable alias of theta[0]
   float* __restrict__ state;     // RMSProp state

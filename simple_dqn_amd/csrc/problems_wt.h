@@ -33,12 +33,20 @@ __device__ __forceinline__ void wt_store(float* p, float v) { __hip_atomic_store
 #endif
 struct Conv2FwdWT : Conv2Fwd {
   static constexpr bool PRELOAD = SDQN_PRELOAD != 0;
+  static constexpr bool LEAD = true;
+  SDQN_LEAD_FIELDS(a1, theta[0], theta[1], a2, a3, A)
+  // (constant indexes: the kernel works on a copy of StepArgs patched from its leading block, which must stay in registers)
+  __device__ static const float* b_ptr(const StepArgs& a, int z) { return (wslot(z) ? a.theta[1] : a.theta[0]) + OFF2; }
   __device__ static void preload(const StepArgs& a, unsigned g0, unsigned g1, unsigned g2) { SDQN_TOUCH("s"(a.a1), "s"(a.a2), "s"(a.theta[0]), "s"(a.theta[1]), "s"(a.B), "s"(a.nz), "s"(a.xcd_map), "s"(g0), "s"(g1), "s"(g2)); }
 
   __device__ static void store(const StepArgs& a, int z, int, int m, int n, float v) { wt_store(&a.a2[((int64_t)z * M(a) + m) * K2 + n], fmaxf(v, 0.0f)); }
 };
 struct Conv3FwdWT : Conv3Fwd {
   static constexpr bool PRELOAD = SDQN_PRELOAD != 0;
+  static constexpr bool LEAD = true;
+  SDQN_LEAD_FIELDS(a2, theta[0], theta[1], a3, a1, A)
+  // (constant indexes: the kernel works on a copy of StepArgs patched from its leading block, which must stay in registers)
+  __device__ static const float* b_ptr(const StepArgs& a, int z) { return (wslot(z) ? a.theta[1] : a.theta[0]) + OFF3; }
   __device__ static void preload(const StepArgs& a, unsigned g0, unsigned g1, unsigned g2) { SDQN_TOUCH("s"(a.a2), "s"(a.a3), "s"(a.theta[0]), "s"(a.theta[1]), "s"(a.B), "s"(a.nz), "s"(a.xcd_map), "s"(g0), "s"(g1), "s"(g2)); }
 
   __device__ static void store(const StepArgs& a, int z, int, int m, int n, float v) { wt_store(&a.a3[((int64_t)z * M(a) + m) * K3 + n], fmaxf(v, 0.0f)); }
@@ -49,6 +57,10 @@ __device__ __forceinline__ f4 ld4_nt(const float* p) {          // streamed-once
 }
 struct Fc4FwdWT : Fc4Fwd {
   static constexpr bool PRELOAD = SDQN_PRELOAD != 0;
+  static constexpr bool LEAD = true;
+  SDQN_LEAD_FIELDS(a3, theta[0], theta[1], slab4, a4, A)
+  // (constant indexes: the kernel works on a copy of StepArgs patched from its leading block, which must stay in registers)
+  __device__ static const float* b_ptr(const StepArgs& a, int z) { return (wslot(z) ? a.theta[1] : a.theta[0]) + OFF4; }
   __device__ static void preload(const StepArgs& a, unsigned g0, unsigned g1, unsigned g2) { SDQN_TOUCH("s"(a.a3), "s"(a.slab4), "s"(a.theta[0]), "s"(a.theta[1]), "s"(a.B), "s"(a.nz), "s"(a.S4), "s"(a.xcd_map), "s"(g0), "s"(g1), "s"(g2)); }
 
   __device__ static f4 b_load4(const StepArgs& a, int z, int o) { return NT_W4 ? ld4_nt(a.theta[wslot(z)] + OFF4 + o) : ld4(a.theta[wslot(z)] + OFF4 + o); }
@@ -56,6 +68,8 @@ struct Fc4FwdWT : Fc4Fwd {
 };
 struct Fc4DgradWT : Fc4Dgrad {
   static constexpr bool PRELOAD = SDQN_PRELOAD != 0;
+  static constexpr bool LEAD = true;
+  SDQN_LEAD_FIELDS(d4, theta[0], a3, d3p, d3, A)
   __device__ static void preload(const StepArgs& a, unsigned g0, unsigned g1, unsigned g2) { SDQN_TOUCH("s"(a.d4), "s"(a.theta[0]), "s"(a.a3), "s"(a.d3p), "s"(a.d3), "s"(a.B), "s"(a.xcd_map), "s"(g0), "s"(g1), "s"(g2)); }
 
   __device__ static f4 b_load4(const StepArgs& a, int, int o) { return NT_W4 ? ld4_nt(a.theta[0] + OFF4 + o) : ld4(a.theta[0] + OFF4 + o); }
@@ -87,6 +101,8 @@ struct Conv3DgradWT : Conv3Dgrad {
 };
 struct Conv3WgradWT : Conv3Wgrad {
   static constexpr bool PRELOAD = SDQN_PRELOAD != 0;
+  static constexpr bool LEAD_MULTI = true;      // bwd3: conv3_dgrad's and conv3_wgrad's operands, fc4_wgrad's A; the rest behind the first loads
+  SDQN_LEAD_FIELDS(d3p, theta[0], a2, d3, a3, tps3)
   SDQN_PRELOAD_MULTI_DEF
   __device__ static void preload(const StepArgs& a, unsigned g0, unsigned g1, unsigned g2) { SDQN_TOUCH("s"(a.a2), "s"(a.d3), "s"(a.slab3), "s"(a.tps3), "s"(a.B), "s"(g0), "s"(g1), "s"(g2)); }
 
@@ -94,6 +110,8 @@ struct Conv3WgradWT : Conv3Wgrad {
 };
 struct Conv2DgradWT : Conv2Dgrad {
   static constexpr bool PRELOAD = SDQN_PRELOAD != 0;
+  static constexpr bool LEAD_MULTI = true;      // bwd2: conv2_dgrad's and conv2_wgrad's operands and conv2_dgrad's output
+  SDQN_LEAD_FIELDS(d2p, theta[0], a1, d2, d1, tps2)
   SDQN_PRELOAD_MULTI_DEF
   __device__ static void preload(const StepArgs& a, unsigned g0, unsigned g1, unsigned g2) { SDQN_TOUCH("s"(a.d2p), "s"(a.theta[0]), "s"(a.a1), "s"(a.d1), "s"(a.B), "s"(g0), "s"(g1), "s"(g2)); }
 

@@ -505,6 +505,7 @@ extern "C" int sdqn_net_set_option(sdqn_net_t h, const char* name, int value) {
     HIPCHK(hipMemcpy(h->ovf_flag, st0, 16, hipMemcpyHostToDevice));
   }
   else if (!strcmp(name, "fused_launches")) h->fused_launches = value != 0;
+  else if (!strcmp(name, "arg_preload")) h->arg_preload = value != 0;   // 0: the step kernels read their hot arguments from the by-value struct (A/B runs)
   else if (!strcmp(name, "conv1_bf16")) h->conv1_bf16 = value != 0;     // 0: conv1_fwd on the fp32-MFMA engine (round-2 kernel)
   else if (!strcmp(name, "wt")) h->wt = value;                       // WriteThrough bits (kernels.h)
   else if (!strcmp(name, "prep_inline")) h->prep_inline = value != 0;

@@ -15,6 +15,7 @@ StepArgs step_args(sdqn_net_s* h) {
   a.S4 = h->S4; a.tps1 = h->tps1; a.tps2 = h->tps2; a.tps3 = h->tps3;
 
   a.xcd_map = h->xcd_map ? 7 : 0;
+  a.arg_preload = h->arg_preload ? 1 : 0;
   if (h->cfg.datatype == 1) {
     a.h16 = h->h16_wgrad_mfma ? 2 : 1; a.h_a1 = h->h_a1; a.h_a2 = h->h_a2; a.h_a3 = h->h_a3; a.h_d4 = h->h_d4; a.h_d3p = h->h_d3p; a.h_d3 = h->h_d3;
     a.h_d2p = h->h_d2p; a.h_d2 = h->h_d2; a.h_d1 = h->h_d1; a.wh[0] = h->wh[0]; a.wh[1] = h->wh[1]; a.wht[0] = h->wht[0]; a.wht[1] = h->wht[1];
@@ -114,6 +115,7 @@ int run_forward(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd) {
 }
 UpdateArgs make_update_args(sdqn_net_s* h, const StepArgs& a) {
   UpdateArgs u; memset(&u, 0, sizeof u);
+  u.arg_preload = a.arg_preload;
   u.theta = h->theta; u.state = h->state; u.g = h->g;
   u.slab[0] = h->slab1; u.slab[1] = h->slab2; u.slab[2] = h->slab3; u.ns[0] = h->ns1; u.ns[1] = h->ns2; u.ns[2] = h->ns3;
   u.dq = h->dq; u.a4 = h->a4; u.cost_terms = h->cost_terms; u.cost_out = h->cost_out; u.cost_accum = h->cost_accum;

@@ -144,7 +144,14 @@ hipError_t launch_kernel(int id, const StepArgs& a, const LaunchTune& t, hipStre
 // PER (--prioritized_replay): the taken action's row is weighted by h.per_w[n] and the new priority goes to h.per_p[n]
 // NSTEP (--n_step): the staged reward is the n-step return R (a double's bits), the terminal the done flag, the bootstrap factor gamma^n
 template <int AMAX, bool BN, bool QSYS, bool DDQN, bool PER, bool NSTEP>
-__global__ void __launch_bounds__(512) head_kernel(const StepArgs a, const HeadArgs h) {
+__global__ void __launch_bounds__(512) head_kernel(SDQN_LEAD_PARAMS, const StepArgs a_, const HeadArgs h) {
+  // leading block (gemm_engine.h: Lead): p = {theta[0], theta[1], slab4, a4, d4}, s0 = A — all this kernel's first loads need
+  StepArgs a = a_;
+  (void)ls1; (void)lr0; (void)lr1;
+  if (lctl & LEAD_ON) {
+    lead_scalars(a, lB, lctl); a.A = ls0;
+    a.theta[0] = (const float*)lp0; a.theta[1] = (const float*)lp1; a.slab4 = (float*)lp2; a.a4 = (float*)lp3; a.d4 = (float*)lp4;
+  }
   SDQN_STAMP(0);
   const int n = blockIdx.x, j = threadIdx.x, lane = j & 63, wave = j >> 6;
   // --double_dqn (DDQN): a third net slot, the online net on the poststates, computed here from its fc4 slabs (NZ = 3); with batch_norm its
@@ -157,7 +164,7 @@ __global__ void __launch_bounds__(512) head_kernel(const StepArgs a, const HeadA
   // ---- everything this thread will ever load is issued up front (one memory round trip) ----------------
   const int nz = a.nz, A = a.A;
   const float* __restrict__ th0 = a.theta[0];
-  const float* __restrict__ th1 = a.theta[nz > 1 ? 1 : 0];
+  const float* __restrict__ th1 = nz > 1 ? a.theta[1] : a.theta[0];
   const float* __restrict__ slab = a.slab4;
   float a4v[NZ];
 #pragma unroll
@@ -321,7 +328,7 @@ hipError_t set_wave_timing_buffer(unsigned long long* const* p, const unsigned* 
 
 // The head of one (QSYS, DDQN, PER, NSTEP) combination for a bucket: 0 / 1 / 2 = A <= 4 / <= 8 / <= MAX_ACTIONS, 3 = --batch_norm (not tuned
 // per bucket; never on the acting path).  launch_head names the combinations that exist: the set of instantiations is part of this file's tuning.
-typedef void (*HeadKernel)(const StepArgs, const HeadArgs);
+typedef void (*HeadKernel)(SDQN_LEAD_PARAMS, const StepArgs, const HeadArgs);
 template <bool QSYS, bool DDQN, bool PER, bool NSTEP>
 static HeadKernel head_for(int bucket) {
   if constexpr (!QSYS) { if (bucket == 3) return head_kernel<MAX_ACTIONS, true, false, DDQN, PER, NSTEP>; }
@@ -339,14 +346,25 @@ hipError_t launch_head(const StepArgs& a, const HeadArgs& h, hipStream_t s, bool
     head_for<false, false, false, true>, head_for<false, true, false, true>, head_for<false, false, true, true>, head_for<false, true, true, true>,
     head_for<true, false, false, false>};
   const HeadKernel k = select[qsys ? 8 : (nstep ? 4 : 0) + (per ? 2 : 0) + (ddqn ? 1 : 0)](bucket);
-  SDQN_LAUNCH(k, dim3(a.B), dim3(512), 0, s, a, h);
+  Lead l; memset(&l, 0, sizeof l);
+  l.p[0] = a.theta[0]; l.p[1] = a.theta[1]; l.p[2] = a.slab4; l.p[3] = a.a4; l.p[4] = a.d4; l.B = a.B; l.s0 = a.A; l.ctl = lead_ctl(a, a.arg_preload != 0);
+  SDQN_LAUNCH(k, dim3(a.B), dim3(512), 0, s, SDQN_LEAD_ARGS(l), a, h);
   return hipGetLastError();
 }
 
 template <bool OVF>
-__global__ void __launch_bounds__(256) update_kernel(const UpdateArgs u) {
+__global__ void __launch_bounds__(256) update_kernel(SDQN_LEAD_PARAMS, const UpdateArgs u) {
   __shared__ float4 part[8][32];
   __shared__ float cost_sh[4096];
+  // leading block (gemm_engine.h: Lead): p = {theta, state, slab[0..2]}, B slot = ns[0] | ns[1] << 16, s0 = ns[2], s1 = A | mode << 8 |
+  // only_fc4 << 12 — the conv-parameter workgroups issue their loads without a trip to the argument segment; the rest follows behind them
+  (void)lr0; (void)lr1;
+  UpdHot hot;
+  const int L = upd_layer((int)blockIdx.x);
+  if ((lctl & LEAD_ON) && (int)blockIdx.x < CONV_BLOCKS) {      // (fc5 / fc4 / prep / cost workgroups read many more fields: they keep the one batched fetch)
+    hot = UpdHot{(float*)lp0, (float*)lp1, (const float*)(L == 0 ? lp2 : (L == 1 ? lp3 : lp4)), L == 0 ? (lB & 0xFFFF) : (L == 1 ? (int)((unsigned)lB >> 16) : ls0),
+                 (ls1 >> 8) & 15, (ls1 >> 12) & 1, ls1 & 255};
+  } else {
 #ifndef SDQN_NO_UPDATE_PRELOAD
   // every argument field in flight at once (one wait): left alone hipcc fetches the fields of the by-value UpdateArgs where each is first
   // used — seven dependent round trips to a cold kernel-argument segment before the first vector load of this latency-bound launch
@@ -355,15 +373,22 @@ __global__ void __launch_bounds__(256) update_kernel(const UpdateArgs u) {
                "s"(u.next.terminals), "s"(u.ns[0]), "s"(u.ns[1]), "s"(u.ns[2]), "s"(u.B), "s"(u.A), "s"(u.mode), "s"(u.skip_fc4), "s"(u.next.B),
                "s"(u.next.idx_in_valid), "s"(u.bsz), "s"(u.rho), "s"(u.one_minus_rho), "s"(u.lr));
 #endif
-  update_body<OVF>(u, (int)blockIdx.x, (int)gridDim.x, part, cost_sh);
+    hot = UpdHot{u.theta, u.state, u.slab[L], u.ns[L], u.mode, u.only_fc4, u.A};
+  }
+  update_body<OVF>(u, hot, (int)sizeof(Lead), (int)blockIdx.x, (int)gridDim.x, part, cost_sh);
 }
 
 hipError_t launch_update(const UpdateArgs& u, hipStream_t s) {
   int dense = 2;                                                   // hosts the ride-along prep and the cost mean
   if (!u.skip_fc4) { dense = (NW4 / 4 + 255) / 256; if (dense > 1792) dense = 1792; }
   const dim3 grid(CONV_BLOCKS + u.A * FC5_BLOCKS_PER_ACTION + dense);
-  if (u.ovf_flag) SDQN_LAUNCH(update_kernel<true>, grid, dim3(256), 0, s, u);
-  else SDQN_LAUNCH(update_kernel<false>, grid, dim3(256), 0, s, u);
+  Lead l; memset(&l, 0, sizeof l);
+  l.p[0] = u.theta; l.p[1] = u.state; l.p[2] = u.slab[0]; l.p[3] = u.slab[1]; l.p[4] = u.slab[2];
+  l.B = (int)((unsigned)u.ns[0] | (unsigned)u.ns[1] << 16); l.s0 = u.ns[2]; l.s1 = u.A | u.mode << 8 | (u.only_fc4 ? 1 << 12 : 0);
+  const bool fits = u.ns[0] >= 0 && u.ns[0] < 65536 && u.ns[1] >= 0 && u.ns[1] < 65536 && u.A >= 0 && u.A < 256 && u.mode >= 0 && u.mode < 16 && u.ns[2] >= 0;      // (only_fc4 travels as one bit: any non-zero value)
+  l.ctl = u.arg_preload && u.B < 128 && fits ? LEAD_ON : 0;
+  if (u.ovf_flag) SDQN_LAUNCH(update_kernel<true>, grid, dim3(256), 0, s, SDQN_LEAD_ARGS(l), u);
+  else SDQN_LAUNCH(update_kernel<false>, grid, dim3(256), 0, s, SDQN_LEAD_ARGS(l), u);
   return hipGetLastError();
 }
 

@@ -24,13 +24,10 @@ namespace sdqn {
 // values differ from the 32-deep routine in the last bits (both are fp32 fmaf chains); every caller of conv3_fwd uses THIS routine
 // (train, predict, predict_one), the batch-norm / tuning-hook variants keep the old one consistently on both nets.
 template <class P>
-__global__ void __launch_bounds__(1024) gemm36_kernel(const StepArgs a) {
-  if constexpr (has_preload<P>::value) P::preload(a, gridDim.x, gridDim.y, gridDim.z);
+__device__ __forceinline__ void gemm36_body(const StepArgs& a, const int gx, const int gy, const int gz, float* smem) {
   static_assert(P::A_K && !P::B_K && P::B_REG, "36-deep routine: k-contiguous A (own-row loads), row-major B");
-  __shared__ float smem[16 * PANEL];
-  const int gx = gridDim.x, gy = gridDim.y;
   const int lin = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-  const int tl = (a.xcd_map & 1) ? xcd_tile_id(lin, gx * gy * gridDim.z) : lin;
+  const int tl = (a.xcd_map & 1) ? xcd_tile_id(lin, gx * gy * gz) : lin;
   const int bz = tl / (gx * gy), rr = tl - bz * (gx * gy);
   const int bx = rr % gx, by = rr / gx;
   const int lane = threadIdx.x & 63;
@@ -74,6 +71,20 @@ __global__ void __launch_bounds__(1024) gemm36_kernel(const StepArgs a) {
 #pragma unroll
     for (int w = 1; w < 16; ++w) v += smem[w * PANEL + ml * 33 + nl];           // fixed order
     if (m0 + ml < M && n0 + nl < N) P::store(a, z, ks, m0 + ml, n0 + nl, v);
+  }
+}
+template <class P>
+__global__ void __launch_bounds__(1024) gemm36_kernel(SDQN_LEAD_PARAMS, const StepArgs a_) {
+  __shared__ float smem[16 * PANEL];
+  (void)lr0; (void)lr1;
+  if constexpr (has_lead<P>::value) {                     // (gemm_engine.h: Lead)
+    StepArgs a = a_;
+    int gx, gy, gz;
+    lead_take<P>(a, gx, gy, gz, a_, SDQN_LEAD_FWD);
+    gemm36_body<P>(a, gx, gy, gz, smem);
+  } else {
+    if constexpr (has_preload<P>::value) P::preload(a_, gridDim.x, gridDim.y, gridDim.z);
+    gemm36_body<P>(a_, gridDim.x, gridDim.y, gridDim.z, smem);
   }
 }
 
@@ -152,15 +163,16 @@ __device__ __forceinline__ void conv1_bf16_body(const Conv1Args& c, const int64_
   if (tile0 < tiles_per_net) load_tile(tile0, raw);                                          // in flight under the plane fill below
   SDQN_STAMP(1);
   {   // this net's three weight planes -> LDS
-    const uint4* wp = reinterpret_cast<const uint4*>(c.w1p[wslot(z)]);
+    typedef uint32_t pl4 __attribute__((ext_vector_type(4)));                                // (a native vector: the array below stays in registers)
+    const pl4* wp = reinterpret_cast<const pl4*>(wslot(z) ? c.w1p[1] : c.w1p[0]);           // (constant indexes: c is a patched copy)
     static_assert(3 * K1 * (CRS1 / 8) == 12 * 256, "3072 chunks of 8 bf16: 12 per thread");
-    uint4 v[12];
+    pl4 v[12];
 #pragma unroll
     for (int u = 0; u < 12; ++u) v[u] = wp[threadIdx.x + 256 * u];                           // all 12 loads in flight before the first LDS store
 #pragma unroll
     for (int u = 0; u < 12; ++u) {
       const int cc = threadIdx.x + 256 * u, row = cc >> 5, col = cc & 31;
-      *reinterpret_cast<uint4*>(sw + row * W1P_PITCH + col * 8) = v[u];
+      *reinterpret_cast<pl4*>(sw + row * W1P_PITCH + col * 8) = v[u];
     }
   }
   SDQN_STAMP(2);
@@ -239,15 +251,23 @@ __device__ __forceinline__ void conv1_bf16_body(const Conv1Args& c, const int64_
   SDQN_STAMP(6);
 }
 
+// Leading block (gemm_engine.h: Lead): p = {src, a1, w1p[0], w1p[1], idx}, s0 = tiles_per_net, s1 = wgs_per_net,
+// ctl = xcd | pad_ << 1 | from_ring << 2 | tpw << 4 | LEAD_ON | post_off << 16.  LEAD_ON clear: the struct, as before.
 template <bool IDX_IN>
-__global__ void __launch_bounds__(256) conv1_bf16_kernel(const Conv1Args c, const IdxIn ix) {
+__global__ void __launch_bounds__(256) conv1_bf16_kernel(SDQN_LEAD_PARAMS, const Conv1Args c_, const IdxIn ix) {
   __shared__ __attribute__((aligned(16))) unsigned short sw[3 * K1 * W1P_PITCH];          // 50 688 B
   int64_t my_idx = 0;
   if constexpr (IDX_IN) {                                   // issued first: needs nothing but the argument-segment pointer
     const char* ka = (const char*)__builtin_amdgcn_kernarg_segment_ptr();
-    my_idx = *reinterpret_cast<const int64_t*>(ka + sizeof(Conv1Args) + 8 * (threadIdx.x & 31));
+    my_idx = *reinterpret_cast<const int64_t*>(ka + sizeof(Lead) + sizeof(Conv1Args) + 8 * (threadIdx.x & 31));
   }
-  (void)ix;
+  (void)ix; (void)lr0; (void)lr1;
+  Conv1Args c = c_;
+  if (lctl & LEAD_ON) {
+    c.src = (const uint8_t*)lp0; c.a1 = (float*)lp1; c.w1p[0] = (const unsigned short*)lp2; c.w1p[1] = (const unsigned short*)lp3; c.idx = (const int64_t*)lp4;
+    c.B = lB; c.tiles_per_net = ls0; c.wgs_per_net = ls1; c.xcd = lctl & 1; c.pad_ = (lctl >> 1) & 1; c.from_ring = (lctl >> 2) & 1;
+    c.tpw = (lctl >> 4) & 15; c.post_off = (int)((unsigned)lctl >> 16);
+  }
   conv1_bf16_body<IDX_IN>(c, my_idx, (int)blockIdx.x, sw);
 }
 
@@ -293,16 +313,26 @@ static_assert(P1 % 4 == 0 && (4 * Q1) % 16 == 0 && C1R_SEG % 16 == 0 && (4 * ST1
 // (bytes 0, 4, 8, 12: the engine's A_GROUP4 trick); the groups' (sample, y, x) are wave-uniform per half-wave: scalar index math.
 struct C1wArgs { const uint8_t* src; const float* d1; float* slab1; const int64_t* idx; int B, from_ring, tps1, Kt, xcd, pad_; };
 
+// Leading block (gemm_engine.h: Lead — scalar / pointer parameters in front of the struct, preloaded into SGPRs at wave launch):
+// p = {src, d1, slab1, idx, unused}, s0 = tps1, s1 = Kt, ctl = xcd | pad_ << 1 | from_ring << 2 | LEAD_ON | grid z << 16.  LEAD_ON clear: the struct, as before.
 template <bool IDX_IN>
-__global__ void __launch_bounds__(1024) conv1_wgrad_bf16_kernel(const C1wArgs c, const IdxIn ix) {
+__global__ void __launch_bounds__(1024) conv1_wgrad_bf16_kernel(SDQN_LEAD_PARAMS, const C1wArgs c_, const IdxIn ix) {
   __shared__ float smem[16 * PANEL];
   const int lane = threadIdx.x & 63, i = lane & 31, h = lane >> 5;
   int64_t my_idx = 0;
   if constexpr (IDX_IN) {
     const char* ka = (const char*)__builtin_amdgcn_kernarg_segment_ptr();
-    my_idx = *reinterpret_cast<const int64_t*>(ka + sizeof(C1wArgs) + 8 * i);
+    my_idx = *reinterpret_cast<const int64_t*>(ka + sizeof(Lead) + sizeof(C1wArgs) + 8 * i);
   }
-  (void)ix;
+  (void)ix; (void)lp4; (void)lr0; (void)lr1;
+  C1wArgs c = c_;
+  int gxw = CRS1 / 32, gzw;                             // the launch grid (x: 8 row tiles, z: K slabs) without a trip to the hidden arguments
+  if (!(lctl & LEAD_ON)) { gxw = (int)gridDim.x; gzw = (int)gridDim.z; }
+  else {
+    gzw = (int)((unsigned)lctl >> 16);
+    c.src = (const uint8_t*)lp0; c.d1 = (const float*)lp1; c.slab1 = (float*)lp2; c.idx = (const int64_t*)lp3;
+    c.B = lB; c.tps1 = ls0; c.Kt = ls1; c.xcd = lctl & 1; c.pad_ = (lctl >> 1) & 1; c.from_ring = (lctl >> 2) & 1;
+  }
   {
     const uint8_t* f0 = c.src; const float* f1 = c.d1; float* f2 = c.slab1; const int64_t* f4 = c.idx;
     int g0 = c.B, g1 = c.from_ring, g2 = c.tps1, g3 = c.Kt;
@@ -311,8 +341,8 @@ __global__ void __launch_bounds__(1024) conv1_wgrad_bf16_kernel(const C1wArgs c,
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   // XCD-contiguous tile map (gemm_engine.h: xcd_tile_id): the 8 row tiles of a K slab read the same frames and deltas, so a slab belongs on
   // ONE XCD's L2 (workgroup b runs on XCD b % 8: without the map a slab's 8 tiles land on 8 different L2s, 5.6x the algorithmic traffic)
-  const int lin = (int)(blockIdx.x + gridDim.x * blockIdx.z);
-  const int tl = c.xcd ? xcd_tile_id(lin, (int)(gridDim.x * gridDim.z)) : lin;
+  const int lin = (int)blockIdx.x + gxw * (int)blockIdx.z;
+  const int tl = c.xcd ? xcd_tile_id(lin, gxw * gzw) : lin;
   const int bx = tl & 7, ks = tl >> 3;
   const int m = 32 * bx + i;
   const int colm = (m >> 6) * FRAME + ((m >> 3) & 7) * W0 + (m & 7);                         // problems.h: col1
@@ -639,7 +669,10 @@ hipError_t launch_kernel_r3(int id, const StepArgs& a, const LaunchTune& t, hipS
     Conv1Args c; c.src = a.src; c.a1 = a.a1; c.w1p[0] = a.w1p[0]; c.w1p[1] = a.w1p[1]; c.idx = a.idx;
     c.B = a.B; c.nz = a.nz; c.from_ring = a.from_ring; c.tiles_per_net = tiles; c.wgs_per_net = wgs; c.tpw = tpw; c.xcd = t.r3_xcd & 1; c.pad_ = (t.wt & WT_CONV1_FWD) ? 1 : 0;
     c.post_off = a.post_off; c.reserved_ = 0;
-    static_assert(sizeof(Conv1Args) == 80 && offsetof(Conv1Args, post_off) == 72, "the index block follows 8-byte aligned at byte 80");
+    static_assert(sizeof(Conv1Args) == 80 && offsetof(Conv1Args, post_off) == 72, "the index block follows 8-byte aligned at byte 64 + 80");
+    Lead l; memset(&l, 0, sizeof l);
+    l.p[0] = c.src; l.p[1] = c.a1; l.p[2] = c.w1p[0]; l.p[3] = c.w1p[1]; l.p[4] = c.idx; l.B = c.B; l.s0 = tiles; l.s1 = wgs;
+    l.ctl = c.xcd | c.pad_ << 1 | (c.from_ring ? 4 : 0) | (tpw & 15) << 4 | (a.arg_preload && a.B < 128 && tpw >= 0 && tpw < 16 && c.xcd < 2 && c.pad_ < 2 && c.post_off >= 0 && c.post_off < 32768 ? LEAD_ON : 0) | (int)((unsigned)c.post_off << 16);
     if (a.B >= 128 && t.bt[K_CONV1_FWD] >= 0) {           // throughput regime  (option bt:0 = -1: the per-tile kernel, the test reference)
       // round 5: persistent workgroups (one per CU), planes in registers, frames streamed in 4-row items; every workgroup of a net the same
       // number of samples where that is possible: Gz = ceil(B / ceil(B / (256 / nz)))
@@ -654,22 +687,25 @@ hipError_t launch_kernel_r3(int id, const StepArgs& a, const LaunchTune& t, hipS
     if (t.host_idx && a.from_ring && a.B <= 32) {
       memset(ix.v, 0, sizeof ix.v);
       memcpy(ix.v, t.host_idx, (size_t)a.B * sizeof(int64_t));
-      SDQN_LAUNCH(conv1_bf16_kernel<true>, dim3(a.nz * wgs), dim3(256), 0, s, c, ix);
+      SDQN_LAUNCH(conv1_bf16_kernel<true>, dim3(a.nz * wgs), dim3(256), 0, s, SDQN_LEAD_ARGS(l), c, ix);
     } else {
       memset(ix.v, 0, sizeof ix.v);
-      SDQN_LAUNCH(conv1_bf16_kernel<false>, dim3(a.nz * wgs), dim3(256), 0, s, c, ix);
+      SDQN_LAUNCH(conv1_bf16_kernel<false>, dim3(a.nz * wgs), dim3(256), 0, s, SDQN_LEAD_ARGS(l), c, ix);
     }
     return hipGetLastError();
   }
   if ((id == K_BWD1 || id == K_CONV1_WGRAD) && (t.variant & LV_CONV1_WGRAD_BF16) && (id == K_CONV1_WGRAD || a.f4w_count == 0) && !a.h16 && !a.bn) {
     C1wArgs c; c.src = a.src; c.d1 = a.d1; c.slab1 = a.slab1; c.idx = a.idx; c.B = a.B; c.from_ring = a.from_ring; c.tps1 = a.tps1; c.Kt = a.B * PIX1; c.xcd = (t.r3_xcd >> 1) & 1; c.pad_ = (t.wt & WT_CONV1_WGRAD) ? 1 : 0;
-    static_assert(sizeof(C1wArgs) == 56, "the index block follows at byte 56 of the argument segment");
+    static_assert(sizeof(C1wArgs) == 56, "the index block follows at byte 64 + 56 of the argument segment");
     const dim3 grid(CRS1 / 32, 1, Conv1Wgrad::nbz(a));
     IdxIn ix; memset(ix.v, 0, sizeof ix.v);
+    Lead l; memset(&l, 0, sizeof l);
+    l.p[0] = c.src; l.p[1] = c.d1; l.p[2] = c.slab1; l.p[3] = c.idx; l.B = c.B; l.s0 = c.tps1; l.s1 = c.Kt;
+    l.ctl = c.xcd | c.pad_ << 1 | (c.from_ring ? 4 : 0) | (a.arg_preload && a.B < 128 && grid.z < 32768u ? LEAD_ON : 0) | (int)(grid.z << 16);
     if (t.host_idx && a.from_ring && a.B <= 32) {
       memcpy(ix.v, t.host_idx, (size_t)a.B * sizeof(int64_t));
-      SDQN_LAUNCH(conv1_wgrad_bf16_kernel<true>, grid, dim3(1024), 0, s, c, ix);
-    } else SDQN_LAUNCH(conv1_wgrad_bf16_kernel<false>, grid, dim3(1024), 0, s, c, ix);
+      SDQN_LAUNCH(conv1_wgrad_bf16_kernel<true>, grid, dim3(1024), 0, s, SDQN_LEAD_ARGS(l), c, ix);
+    } else SDQN_LAUNCH(conv1_wgrad_bf16_kernel<false>, grid, dim3(1024), 0, s, SDQN_LEAD_ARGS(l), c, ix);
     return hipGetLastError();
   }
   // conv2 / conv3 forward with ONE workgroup per 32 x 64 output block (N = 64 = two 32-wide tiles): the register-blocked routine with
@@ -705,8 +741,11 @@ hipError_t launch_kernel_r3(int id, const StepArgs& a, const LaunchTune& t, hipS
   if (id == K_CONV3_FWD && (t.variant & LV_CONV3_C36) && a.B < 128 && !a.h16 && !a.bn) {
     static_assert(CRS3 == 16 * 36, "conv3's K is 16 chunks of 36");
     const dim3 grid((Conv3Fwd::M(a) + 31) / 32, (Conv3Fwd::N(a) + 31) / 32, Conv3Fwd::nbz(a));
-    if ((t.wt & WT_CONV3_FWD) && a.B <= 32) SDQN_LAUNCH((gemm36_kernel<Conv3FwdWT>), grid, dim3(1024), 0, s, a);
-    else SDQN_LAUNCH((gemm36_kernel<Conv3Fwd>), grid, dim3(1024), 0, s, a);
+    Lead l; memset(&l, 0, sizeof l);
+    if ((t.wt & WT_CONV3_FWD) && a.B <= 32) {
+      Conv3FwdWT::lead_pack(a, l); l.B = a.B; l.s0 = lead_grid(grid); l.ctl = lead_ctl(a, a.arg_preload && lead_grid_fits(grid));
+      SDQN_LAUNCH((gemm36_kernel<Conv3FwdWT>), grid, dim3(1024), 0, s, SDQN_LEAD_ARGS(l), a);
+    } else SDQN_LAUNCH((gemm36_kernel<Conv3Fwd>), grid, dim3(1024), 0, s, SDQN_LEAD_ARGS(l), a);
     return hipGetLastError();
   }
   *handled = false;

@@ -55,8 +55,14 @@ constexpr int FC5_BLOCKS_PER_ACTION = NFC / 4 / 32;   // 4 workgroups of 32 floa
 
 // OVF (fp16 data parallel only; compiled out of the default kernel): a half overflow in the all-reduced gradient skips the
 // whole apply step on every rank
+// UpdHot: what a conv-parameter workgroup (608 of the launch's ~630) needs before its first vector loads — from update_kernel's leading
+// parameter block (preloaded into SGPRs at wave launch) or, option arg_preload = 0, copied from the struct.  arg_off: bytes of kernel
+// parameters in front of UpdateArgs.
+// (slab / ns: those of the conv layer this workgroup's 128 floats belong to — upd_layer; picked by the kernel from plain values)
+struct UpdHot { float* theta; float* state; const float* slab; int ns, mode, only_fc4, A; };
+__device__ __forceinline__ int upd_layer(int bid) { const int64_t e = (int64_t)bid * 128; return e < OFF2 ? 0 : (e < OFF3 ? 1 : 2); }
 template <bool OVF>
-__device__ __forceinline__ void update_body(const UpdateArgs& u, const int bid, const int nblocks, float4 (*part)[32], float* cost_sh) {
+__device__ __forceinline__ void update_body(const UpdateArgs& u, const UpdHot& hot, const int arg_off, const int bid, const int nblocks, float4 (*part)[32], float* cost_sh) {
   const int t = threadIdx.x;
 #ifdef SDQN_TIMING
   SDQN_STAMP(0);
@@ -71,22 +77,22 @@ __device__ __forceinline__ void update_body(const UpdateArgs& u, const int bid, 
       else if (u.ovf_dynamic && ++st[2] >= 200) { st[2] = 0; if (st[1] < 15) st[1] += 1; }
     }
   }
-  if (u.only_fc4 && bid < CONV_BLOCKS + u.A * FC5_BLOCKS_PER_ACTION) return;
+  if (hot.only_fc4 && bid < CONV_BLOCKS + hot.A * FC5_BLOCKS_PER_ACTION) return;
   if (bid < CONV_BLOCKS) {
     const int c4 = t & 31, sg = t >> 5;
     const int64_t e = ((int64_t)bid * 32 + c4) * 4;
     float4 gs = make_float4(0.f, 0.f, 0.f, 0.f);
     float4 pre[2] = {gs, gs};
-    const bool applies = sg == 0 && u.mode != 1 && !skip_apply;
-    if (applies) { pre[0] = *reinterpret_cast<const float4*>(u.theta + e); pre[1] = *reinterpret_cast<const float4*>(u.state + e); }
-    if (u.mode == 2) {
+    const bool applies = sg == 0 && hot.mode != 1 && !skip_apply;
+    if (applies) { pre[0] = *reinterpret_cast<const float4*>(hot.theta + e); pre[1] = *reinterpret_cast<const float4*>(hot.state + e); }
+    if (hot.mode == 2) {
       if (sg == 0) gs = *reinterpret_cast<const float4*>(u.g + e);
     } else {
       const int L = e < OFF2 ? 0 : (e < OFF3 ? 1 : 2);                       // uniform per workgroup (128-float groups)
       const int64_t off = e - (L == 0 ? OFF1 : (L == 1 ? OFF2 : OFF3));
       const int64_t nw = L == 0 ? NW1 : (L == 1 ? NW2 : NW3);
-      const float* sp = u.slab[L] + off;
-      const int ns = u.ns[L];
+      const float* sp = hot.slab + off;
+      const int ns = hot.ns;
       // slabs sg, sg + 8, sg + 16, ... in increasing order (the order IS the result: fixed).  Four loads are issued together whatever ns
       // (clamped index + select instead of a data-dependent loop: a 25-slab reduction was three dependent memory round trips for seven
       // of the eight slab groups)
@@ -118,10 +124,10 @@ __device__ __forceinline__ void update_body(const UpdateArgs& u, const int bid, 
         *reinterpret_cast<float4*>(u.g + e) = gs;
       }
     }
-    if (applies) opt_apply4(u.theta, u.state, u.state2, e, gs, u, pre);
+    if (applies) opt_apply4(hot.theta, hot.state, u.state2, e, gs, u, pre);
     return;
   }
-  const int fc5_blocks = u.A * FC5_BLOCKS_PER_ACTION;
+  const int fc5_blocks = hot.A * FC5_BLOCKS_PER_ACTION;
   if (bid < CONV_BLOCKS + fc5_blocks) {
     // fc5 wgrad (delta . a4^T, A x 512) + its update: the batch plays the role of the slabs — 8 sample groups
     // per workgroup, fixed-order LDS combine (deterministic)
@@ -172,8 +178,7 @@ __device__ __forceinline__ void update_body(const UpdateArgs& u, const int bid, 
     }
   }
   if (u.next.B > 0 && bid == first_dense) {             // next step's prep rides along (every reader of idx is done)
-    // (UpdateArgs is the first kernel parameter of update_kernel: its offset in the argument segment is 0)
-    const char* ka = (const char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(UpdateArgs, next) + offsetof(PrepArgs, idx_in);
+    const char* ka = (const char*)__builtin_amdgcn_kernarg_segment_ptr() + arg_off + offsetof(UpdateArgs, next) + offsetof(PrepArgs, idx_in);
     for (int n = t; n < u.next.B; n += 256) {
       const int64_t i = u.next.idx_in_valid ? *reinterpret_cast<const int64_t*>(ka + 8 * (n & 31)) : u.next.idx_pinned[n];
       u.next.idx[n] = i;

@@ -273,6 +273,18 @@ int sdqn_net_cost_collect(sdqn_net_t h, int64_t ticket, float* mean_cost);
 int sdqn_mt_words(uint64_t* words);
 /* DeepQNetwork.update_target_network, deepqnetwork.py:102-105 */
 int sdqn_net_update_target(sdqn_net_t h);
+/* Soft (Polyak) target updates, --target_tau (no reference counterpart).  sdqn_net_soft_update performs ONE blend now,
+ * on the library stream:  theta-[e] <- theta-[e] + tau_f * (theta[e] - theta-[e])  with tau_f = (float)tau (the network's precision on
+ * the generic path: double for float64), subtraction, product and sum each rounded once, never contracted — numpy reproduces it bit
+ * for bit.  It covers everything sdqn_net_update_target copies (with batch_norm: beta / gamma and the running statistics) and leaves
+ * the target's derived weight copies what sdqn_net_set_weights(which = 1) would have made them.  tau = 1 is sdqn_net_update_target;
+ * tau outside (0, 1] or not finite is SDQN_ERR_ARG; without a target net nothing is launched.
+ * sdqn_net_set_target_tau sets the per-step mode: 0 (default) off; tau in (0, 1]: every train step of this net that applies an update
+ * — whatever its entry point, sdqn_net_apply_update included, a "grad_only" step excluded — is followed by one such blend, enqueued
+ * right behind the step's update launch (+1 launch per step; profile row 27). */
+int sdqn_net_soft_update(sdqn_net_t h, double tau);
+int sdqn_net_set_target_tau(sdqn_net_t h, double tau);
+int sdqn_net_get_target_tau(sdqn_net_t h, double* tau);
 int sdqn_net_sync(sdqn_net_t h);
 /* The two halves of a data-parallel step without a communicator (the arithmetic every rank performs
  * around the all-reduce).  With option "grad_only" = 1 a train step ends after the local gradient SUMS are in the flat

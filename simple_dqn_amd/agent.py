@@ -49,6 +49,9 @@ class Agent:
         self.exploration_rate_test = args.exploration_rate_test
         self.total_train_steps = args.start_epoch * args.train_steps
         self.train_frequency, self.train_repeat, self.target_steps = args.train_frequency, args.train_repeat, args.target_steps
+        # --target_tau > 0: the library blends the target net after every train step; the loops below only make the
+        # reference's very first copy (agent.py:105 at total_train_steps == 0), so that training starts from theta- = theta
+        self.target_tau = float(getattr(args, "target_tau", 0.0) or 0.0)
         self.callback = None
         self._per = getattr(replay_memory, "prioritized", False)
         if self._per:
@@ -156,7 +159,10 @@ class Agent:
     def train(self, train_steps, epoch=0):
         for i in range(train_steps):
             self._advance_and_store(self._epsilon.at(self.total_train_steps))
-            if self.target_steps and i % self.target_steps == 0:      # also fires at i == 0 of every call (agent.py:105)
+            if self.target_tau > 0:
+                if self.target_steps and self.total_train_steps == 0:
+                    self.net.update_target_network()
+            elif self.target_steps and i % self.target_steps == 0:    # also fires at i == 0 of every call (agent.py:105)
                 self.net.update_target_network()
             if self.mem.count > self.mem.batch_size and i % self.train_frequency == 0:
                 self._learn(epoch)
@@ -189,7 +195,10 @@ class Agent:
         N = self.train_envs
         for _ in range(-(-int(train_steps) // N)):
             self._collect(1, self._epsilon.at(self.total_train_steps))
-            if self.target_steps and self.total_train_steps % self.target_steps < N:
+            if self.target_tau > 0:
+                if self.target_steps and self.total_train_steps == 0:
+                    self.net.update_target_network()
+            elif self.target_steps and self.total_train_steps % self.target_steps < N:
                 self.net.update_target_network()
             self._vec_due += N
             while self._vec_due >= self.train_frequency:

@@ -131,6 +131,7 @@ struct sdqn_net_s {
   // h_a1..h_a3) are re-allocated with room for it when the option is first switched on
   bool double_dqn = false, slots3 = false;
   int n_step = 1;                          // --n_step (option "n_step"): poststate frame offset of the ring paths, n-step head
+  double target_tau = 0.0;                 // --target_tau (sdqn_net_set_target_tau): > 0: every train step is followed by one soft target update
   uint8_t *st_states = nullptr, *st_act = nullptr, *st_term = nullptr; int64_t* st_rew = nullptr; int64_t* d_idx = nullptr;
   float* h_f = nullptr;                    // pinned scratch for small read-backs
   // acting path (round 4): the head kernel of a predict_state forward writes its Q-values straight into mapped host memory (q_host; q_host_dev
@@ -246,6 +247,9 @@ float* which_buf(sdqn_net_s* h, int which);
 bool bn_layer_span(sdqn_net_s* h, int which, int layer, float** base, int64_t* n);
 int gen_set(sdqn_net_s* h, int which, int layer, const void* w, int64_t n, bool f64);
 int gen_get(sdqn_net_s* h, int which, int layer, void* w, int64_t n, bool f64);
+int target_blend(sdqn_net_s* h, double tau);                       // one soft target update now (tau in (0, 1]; the caller has joined g_comm)
+int step_blend(sdqn_net_s* h);                                     // what every applied train step ends with: the blend of --target_tau, or nothing
+int gen_step_done(sdqn_net_s* h);                                  // generic path: a train step was enqueued (counter + step_blend)
 int prof_collect(sdqn_net_s* h);
 int prof_event(sdqn_net_s* h, hipEvent_t* e);
 hipError_t dp_allreduce(sdqn_net_s* h, void* buf, size_t count, int dtype, void* comm, hipStream_t s);

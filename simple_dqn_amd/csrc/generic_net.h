@@ -40,6 +40,10 @@ struct GenericNet {
   virtual hipError_t read_cost_sum(double* sum) = 0;
   virtual hipError_t last_q(void* preq, void* maxpostq, bool host_f64) = 0;
   virtual hipError_t update_target() = 0;                                // deepqnetwork.py:102-105
+  // --target_tau: theta- <- theta- + tau (theta - theta-) in the network's precision, three rounded operations; one
+  // launch, none without a target net
+  virtual hipError_t soft_update(double tau) = 0;
+  virtual bool has_target() const = 0;
   virtual hipError_t set_double_dqn(bool on) = 0;                        // --double_dqn (allocates the online-on-poststates Q on first use)
   // --prioritized_replay (sdqn_per.hip): w != nullptr makes the following train steps weight the taken action's row by w[n] and write the
   // new priority (|delta| + eps)^alpha into newp[n]; nullptr: the standard step

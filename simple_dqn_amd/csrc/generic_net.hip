@@ -14,6 +14,7 @@
 // plain 64 x 64 LDS-tiled FMA GEMM, ~40 launches per step.
 #include "generic_net.h"
 #include "problems.h"          // MetaRec
+#include "launch.h"            // SDQN_LAUNCH: the soft target update has a profile row
 #include <vector>
 #include <algorithm>
 #include <math.h>
@@ -233,6 +234,14 @@ __global__ void __launch_bounds__(256) update_kernel(const OptArgs<T> u) {
     }
     u.s1[i] = a; u.w[i] = w;
   }
+}
+
+// ---- --target_tau: theta- <- theta- + tau (theta - theta-), every operation rounded once (never an FMA) ------------------------------
+__device__ inline float blend_t(float w, float wt, float tau) { return __fadd_rn(wt, __fmul_rn(tau, __fsub_rn(w, wt))); }
+__device__ inline double blend_t(double w, double wt, double tau) { return __dadd_rn(wt, __dmul_rn(tau, __dsub_rn(w, wt))); }
+template <typename T>
+__global__ void __launch_bounds__(256) soft_update_kernel(const T* __restrict__ w, T* __restrict__ wt, int64_t n, T tau) {
+  for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) wt[i] = blend_t(w[i], wt[i], tau);
 }
 
 inline unsigned grid_for(int64_t n) { int64_t b = (n + 255) / 256; return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b)); }
@@ -461,6 +470,12 @@ class GenericNetT : public GenericNet {
   hipError_t update_target() override {
     if (theta_t != theta) return hipMemcpyAsync(theta_t, theta, (size_t)NP * sizeof(T), hipMemcpyDeviceToDevice, st);
     return hipSuccess;
+  }
+  bool has_target() const override { return theta_t != theta; }
+  hipError_t soft_update(double tau) override {
+    if (theta_t == theta) return hipSuccess;
+    SDQN_LAUNCH(soft_update_kernel<T>, dim3(grid_for(NP)), dim3(256), 0, st, (const T*)theta, theta_t, NP, (T)tau);
+    return hipGetLastError();
   }
 };
 

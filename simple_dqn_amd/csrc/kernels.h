@@ -20,9 +20,10 @@ enum KernelId {
   K_WGRADS,    // round 4 (float16, B >= 128): fc4_wgrad (+ fused RMSProp) || conv3_wgrad || conv2_wgrad in one launch, after the block-tile dgrad chain
   K_ACT,       // round 4: the acting forward (batch of one) as ONE launch (sdqn_act.hip)
   K_COLLECT,   // --train_envs: one lockstep of N games of catch written into the laned ring (sdqn_env.hip; not a launch of the train step)
+  K_TARGET,    // --target_tau: the soft target update, one launch behind the step's update launch (sdqn_target.hip / generic_net.hip)
   K_COUNT
 };
-static_assert(K_BN == 19 && K_WGRADS == 24 && K_ACT == 25 && K_COLLECT == 26 && K_COUNT == 27, "kernel ids are public numbers");
+static_assert(K_BN == 19 && K_WGRADS == 24 && K_ACT == 25 && K_COLLECT == 26 && K_TARGET == 27 && K_COUNT == 28, "kernel ids are public numbers");
 const char* kernel_name(int id);
 
 
@@ -207,5 +208,17 @@ struct ActArgs {
 hipError_t launch_act(const ActArgs& a, bool q_system_scope, hipStream_t s);
 hipError_t launch_w1_planes(const float* theta, unsigned short* w1p, hipStream_t s);   // conv1's three bf16 weight planes of one net (problems.h: split_bf16x3)
 hipError_t launch_refresh16(const float* theta, half_t* wh, half_t* wht, hipStream_t s);   // fp16 mode: rebuild both half copies
+// ---- --target_tau: theta- <- theta- + tau (theta - theta-) and the target's derived weight copies, ONE launch (sdqn_target.hip) -------
+struct TargetBlendArgs {
+  const float* theta;         // online parameters (read only)
+  float* theta_t;             // target parameters, blended in place
+  int64_t NP;                 // values per flat buffer (weights [+ BatchNorm parameters and running statistics])
+  float tau;
+  half_t* wh; half_t* wht;    // float16 nets: the TARGET net's half copies (master layout / transposed), else nullptr
+  unsigned short* w1p;        // float32 nets: the TARGET net's three bf16 planes of W1, else nullptr
+  int tiles;                  // (filled in by launch_target_blend) leading workgroups that take a 64 x 32 tile each
+  int64_t flat_first;         // (filled in by launch_target_blend) first element of the element-wise part
+};
+hipError_t launch_target_blend(TargetBlendArgs a, hipStream_t s);
 
 }  // namespace sdqn

@@ -319,7 +319,9 @@ int prof_event(sdqn_net_s* h, hipEvent_t* e) {
 
 extern "C" int sdqn_net_profile(sdqn_net_t h, int enable, int kernel) {
   ARGCHK(h && kernel < K_COUNT, "bad arguments");
-  if (h->gen) return SDQN_OK; h->prof_on = enable != 0; h->prof_filter = kernel; return SDQN_OK;
+  // the generic path's launches are not bracketed; its one row is the soft target update's (K_TARGET)
+  if (h->gen) { h->prof_on = enable != 0 && (kernel < 0 || kernel == K_TARGET); h->prof_filter = K_TARGET; return SDQN_OK; }
+  h->prof_on = enable != 0; h->prof_filter = kernel; return SDQN_OK;
 }
 extern "C" int sdqn_net_profile_count(int* n) { ARGCHK(n, "NULL"); *n = K_COUNT; return SDQN_OK; }
 extern "C" int sdqn_net_profile_read(sdqn_net_t h, int kernel, const char** name, double* total_ms, int64_t* launches) {
@@ -337,10 +339,8 @@ extern "C" int sdqn_net_profile_reset(sdqn_net_t h) {
 
 // RCCL all-reduce on behalf of LAUNCH_ON: a failure keeps RCCL's own message (h->nccl_rc / sdqn_last_error) and is
 // reported as SDQN_ERR_RCCL by the macro instead of an anonymous hipErrorUnknown
-extern "C" int sdqn_net_update_target(sdqn_net_t h) {
-  ARGCHK(h, "NULL handle");
-  if (h->gen) { GENCHK(h->gen->update_target()); return SDQN_OK; }
-  { int rc = join_comm(h); if (rc) return rc; }
+// theta- = theta and the target's derived copies, as copies on the library stream (tuned path; the caller has joined g_comm)
+static int target_copy(sdqn_net_s* h) {
   if (h->theta_t != h->theta) {
     HIPCHK(hipMemcpyAsync(h->theta_t, h->theta, (size_t)h->NP * 4, hipMemcpyDeviceToDevice, g_stream));   // deepqnetwork.py:102-105
     if (h->w1p[0] && h->w1p[1] != h->w1p[0])
@@ -352,6 +352,57 @@ extern "C" int sdqn_net_update_target(sdqn_net_t h) {
   }
   return SDQN_OK;
 }
+extern "C" int sdqn_net_update_target(sdqn_net_t h) {
+  ARGCHK(h, "NULL handle");
+  if (h->gen) { GENCHK(h->gen->update_target()); return SDQN_OK; }
+  { int rc = join_comm(h); if (rc) return rc; }
+  return target_copy(h);
+}
+// ---- --target_tau: soft (Polyak) target updates -----------------------------------------------------------------------
+// theta- <- theta- + tau (theta - theta-) for the whole flat buffer (BatchNorm parameters and running statistics included: what a hard
+// update copies, a soft update blends) and the target's derived copies, ONE launch on the library stream (sdqn_target.hip; generic
+// path: generic_net.hip).  tau = 1 is the hard update's copies (d + theta- need not equal theta in floating point).  Without a target
+// net nothing is launched.
+static bool tau_in_range(double tau) { return tau > 0.0 && tau <= 1.0; }     // (false for a NaN)
+int target_blend(sdqn_net_s* h, double tau) {
+  if (h->gen) {
+    if (!h->gen->has_target()) return SDQN_OK;
+    if (tau == 1.0) { GENCHK(h->gen->update_target()); return SDQN_OK; }
+    LAUNCH(K_TARGET, h->gen->soft_update(tau));
+    return SDQN_OK;
+  }
+  if (h->theta_t == h->theta) return SDQN_OK;
+  if (tau == 1.0) return target_copy(h);
+  TargetBlendArgs a; memset(&a, 0, sizeof a);
+  a.theta = h->theta; a.theta_t = h->theta_t; a.NP = h->NP; a.tau = (float)tau;
+  if (h->cfg.datatype == 1) { a.wh = h->wh[1]; a.wht = h->wht[1]; }
+  else a.w1p = h->w1p[1];
+  LAUNCH(K_TARGET, launch_target_blend(a, g_stream));
+  return SDQN_OK;
+}
+// Per-step mode: called by whatever has just enqueued the optimizer pass of a train step (run_train, sdqn_net_apply_update, the generic
+// path's three entry points), never by a grad_only step.  Everything that reads theta- (the next step's target forward) is a later launch
+// on the library stream; the one writer of theta that may still be running elsewhere — the overlapped data-parallel fc4 update on g_comm
+// — is joined first.
+int step_blend(sdqn_net_s* h) {
+  if (!(h->target_tau > 0.0)) return SDQN_OK;
+  if (!h->gen) { int rc = join_comm(h); if (rc) return rc; }
+  return target_blend(h, h->target_tau);
+}
+int gen_step_done(sdqn_net_s* h) { h->train_iterations += 1; return step_blend(h); }
+extern "C" int sdqn_net_soft_update(sdqn_net_t h, double tau) {
+  ARGCHK(h, "NULL handle");
+  ARGCHK(tau_in_range(tau), "soft target update: tau %g outside (0, 1]", tau);
+  if (!h->gen) { int rc = join_comm(h); if (rc) return rc; }
+  return target_blend(h, tau);
+}
+extern "C" int sdqn_net_set_target_tau(sdqn_net_t h, double tau) {
+  ARGCHK(h, "NULL handle");
+  ARGCHK(tau == 0.0 || tau_in_range(tau), "target_tau %g outside [0, 1]", tau);
+  h->target_tau = tau;
+  return SDQN_OK;
+}
+extern "C" int sdqn_net_get_target_tau(sdqn_net_t h, double* tau) { ARGCHK(h && tau, "NULL argument"); *tau = h->target_tau; return SDQN_OK; }
 // The second half of a data-parallel step without a communicator: the gradient sums currently in the flat buffer g
 // (written by a grad_only step and/or sdqn_net_set_weights(which = 3)) are applied with divisor bsz — exactly what every
 // rank does after the all-reduce with bsz = nranks * batch_size (A9: grad / be.bsz, deepqnetwork.py:165).
@@ -369,7 +420,7 @@ extern "C" int sdqn_net_apply_update(sdqn_net_t h, double bsz) {
   }
   LAUNCH(K_UPDATE, launch_update(u, g_stream));
   if (h->bn) LAUNCH(K_BN, launch_bn_update(u, g_stream));
-  return SDQN_OK;
+  return step_blend(h);
 }
 // float16 data parallel without a communicator: the two passes that bracket ncclAllReduce(ncclFloat16) in run_train, callable
 // on their own so that the exchange can be done by the caller (tests: gloo across two processes sharing one GPU).

@@ -314,7 +314,7 @@ int run_train(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd0, const PrepA
   }
   h->train_iterations += 1;                                                   // deepqnetwork.py:168
   h->spec_pending = false;                 // the online parameters move: a forward enqueued before this step no longer is "predict now"
-  return SDQN_OK;
+  return update_form(h) == UPD_GRAD_ONLY ? SDQN_OK : step_blend(h);      // --target_tau: one blend behind every APPLIED step
 }
 // small read-backs: `bytes` of device memory into the pinned scratch h->h_f, waited for
 static int fetch_small(sdqn_net_s* h, const void* src, size_t bytes) {
@@ -427,7 +427,7 @@ static int train_host_tuple(sdqn_net_t h, const uint8_t* pre, const uint8_t* act
                                 : h->gen->train_host(pre, actions, rewards, post, terminals, h->epoch);
     if (per) { int rcp = per_gen_finish(h, owner); if (ge == hipSuccess && rcp) return rcp; }
     GENCHK(ge);
-    h->train_iterations += 1;
+    { int rcb = gen_step_done(h); if (rcb) return rcb; }
     return cost_out ? read_cost(h, cost_out) : SDQN_OK;
   }
   const size_t sb = (size_t)h->B * STATE, small = (size_t)h->B * 10;
@@ -540,8 +540,7 @@ static int gen_train_replay(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* idx_
   rc = replay_gather_generic(r, didx); if (rc) return rc;
   rc = replay_release_idx_batched(r, slot, false); if (rc) return rc;
   GENCHK(h->gen->train_dev(r->d_pre, r->d_post, r->d_act, r->d_rew, r->d_term, h->epoch));
-  h->train_iterations += 1;
-  return SDQN_OK;
+  return gen_step_done(h);
 }
 // does this replay memory's geometry fit this network?  (tuned path: 84 x 84 x 4; generic path: the configured state size)
 int check_replay_geometry(const sdqn_net_s* h, const sdqn_replay_s* r) {

@@ -447,8 +447,7 @@ static int per_gen_step(sdqn_net_s* h, sdqn_replay_s* r) {
   const hipError_t e = h->gen->train_dev(r->d_pre, r->d_post, r->d_act, r->d_rew, r->d_term, h->epoch);
   h->gen->set_per(nullptr, nullptr, 0.0, 0.0);
   GENCHK(e);
-  h->train_iterations += 1;
-  return SDQN_OK;
+  return gen_step_done(h);
 }
 // one step on the minibatch the last sampling launch left (host_idx: run_ring_step)
 static int per_train_step(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* host_idx) {

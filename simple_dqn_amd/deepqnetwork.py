@@ -97,6 +97,10 @@ class DeepQNetwork:
         self.n_step = int(getattr(args, "n_step", 1))
         if self.n_step != 1:
             _lib.check(self._lib.sdqn_net_set_option(h, b"n_step", self.n_step))
+        # soft (Polyak) target updates: > 0 makes the library blend the target toward the online net after every train step
+        self.target_tau = float(getattr(args, "target_tau", 0.0) or 0.0)
+        if self.target_tau:
+            self.set_target_tau(self.target_tau)
         self._mt_buf = (C.c_uint32 * _lib.MT_WORDS)()
         self._act_out = C.c_int(); self._act_greedy = self._lib.sdqn_net_act_greedy
         self._env_r, self._env_t = C.c_int(), C.c_int(); self._act_step_env = self._lib.sdqn_net_act_step_env
@@ -159,6 +163,20 @@ class DeepQNetwork:
     # ---- reference API ----------------------------------------------------------------------------
     def update_target_network(self):                               # :102-105
         _lib.check(self._lib.sdqn_net_update_target(self._h))
+
+    def soft_update_target_network(self, tau):
+        """One soft target update now: theta- <- theta- + tau (theta - theta-), tau in (0, 1] (1: update_target_network)."""
+        _lib.check(self._lib.sdqn_net_soft_update(self._h, float(tau)))
+
+    def set_target_tau(self, tau):
+        """--target_tau: tau in (0, 1] makes every train step of this net end with one soft target update inside the library; 0: off."""
+        _lib.check(self._lib.sdqn_net_set_target_tau(self._h, float(tau)))
+        self.target_tau = float(tau)
+
+    def get_target_tau(self):
+        t = C.c_double()
+        _lib.check(self._lib.sdqn_net_get_target_tau(self._h, C.byref(t)))
+        return t.value
 
     def train(self, minibatch, epoch=0):                           # :107-172
         prestates, actions, rewards, poststates, terminals = minibatch

@@ -38,6 +38,7 @@ _OPTIONS = {
         ("--decay_rate", float, 0.95), ("--clip_error", float, 1), ("--min_reward", float, -1), ("--max_reward", float, 1),
         ("--batch_norm", _flag, False),
         ("--double_dqn", _flag, False, dict(help="Double DQN targets: the online net picks the poststate's action, the target net values it.")),
+        ("--target_tau", float, 0.0, dict(help="Soft target updates: after every train step the target net moves by this fraction toward the online net (0: hard copy every --target_steps steps).")),
     ],
     "Backend": [
         ("--backend", str, "hip", dict(choices=["hip", "gpu", "cpu"])), ("--device_id", int, 0),
@@ -99,8 +100,19 @@ def check_train_envs(args):
     return n
 
 
+def check_target_tau(args):
+    """--target_tau: its range and what it needs, refused before anything touches the device"""
+    tau = float(getattr(args, "target_tau", 0.0) or 0.0)
+    if not 0.0 <= tau <= 1.0:                                        # (a NaN fails both comparisons)
+        raise ValueError("--target_tau %g: must be in [0, 1]" % tau)
+    if tau > 0 and not args.target_steps:
+        raise ValueError("--target_tau %g needs a target network, and --target_steps 0 switches it off" % tau)
+    return tau
+
+
 def run(args):
     train_envs = check_train_envs(args)
+    check_target_tau(args)
     from . import Agent, DeepQNetwork, ReplayMemory, SyntheticEnvironment, _lib, load
     from .environment import LIBRARY_GAMES
     from .statistics import Statistics

@@ -1,29 +1,15 @@
-// kernels.h — launch interface between the host orchestration (sdqn_api_*.hip) and the device
-// code (sdqn_kernels.hip).  Kernel ids double as the profiler's slots.
+// kernels.h — launch interface between the host orchestration (sdqn_api_*.hip) and the device code: the argument structs of every launch,
+// launch_kernel (resolve the route of a GEMM-shaped stage, then run its executor) and the single-purpose launchers.  Kernel ids (launch_route.h)
+// double as the profiler's slots.
 #pragma once
 #include <cstddef>
 #include <hip/hip_runtime.h>
 #include "problems.h"
 #include "launch.h"
+#include "launch_route.h"
 
 namespace sdqn {
 
-enum KernelId {
-  K_CONV1_FWD = 0, K_CONV2_FWD, K_CONV3_FWD, K_FC4_FWD, K_HEAD,
-  K_FC4_DGRAD, K_FC4_WGRAD, K_CONV3_DGRAD, K_CONV3_WGRAD, K_CONV2_DGRAD, K_CONV2_WGRAD,
-  K_CONV1_WGRAD, K_UPDATE, K_ALLREDUCE, K_GATHER, K_PREP,
-  K_BWD3,      // one launch: conv3_dgrad + conv3_wgrad + fc4_wgrad (all depend on fc4_dgrad only)
-  K_BWD2,      // one launch: conv2_dgrad + conv2_wgrad (both depend on conv3_dgrad only) + a share of fc4_wgrad
-  K_BWD1,      // one launch: conv1_wgrad + the last share of fc4_wgrad
-  K_BN,        // --batch_norm: one BatchNorm layer, forward ([partial +] apply) or backward (partial + apply)
-  K_RESERVED_20, K_RESERVED_21, K_RESERVED_22, K_RESERVED_23,   // ids of retired round-3 launches: the numbers are public (options bt:/xcd:/nw:<id>, profile_read), nothing launches them
-  K_WGRADS,    // round 4 (float16, B >= 128): fc4_wgrad (+ fused RMSProp) || conv3_wgrad || conv2_wgrad in one launch, after the block-tile dgrad chain
-  K_ACT,       // round 4: the acting forward (batch of one) as ONE launch (sdqn_act.hip)
-  K_COLLECT,   // --train_envs: one lockstep of N games of catch written into the laned ring (sdqn_env.hip; not a launch of the train step)
-  K_TARGET,    // --target_tau: the soft target update, one launch behind the step's update launch (sdqn_target.hip / generic_net.hip)
-  K_COUNT
-};
-static_assert(K_BN == 19 && K_WGRADS == 24 && K_ACT == 25 && K_COLLECT == 26 && K_TARGET == 27 && K_COUNT == 28, "kernel ids are public numbers");
 const char* kernel_name(int id);
 
 
@@ -155,29 +141,16 @@ __device__ inline float opt_apply(float w, float& s1, float& s2, float gsum, con
 }
 #endif
 
-// LaunchTune::variant — the launch variants the step's orchestration asks for (sdqn_api_step.hip decides, launch_kernel's translation
-// units test); bit 0 is unused
-enum LaunchVariant {
-  LV_CONV3_C36 = 2,           // conv3_fwd on 36-deep K-chunks (sdqn_kernels_r3.hip)
-  LV_CONV1_FWD_BF16 = 4,      // conv1_fwd on packed-bf16 MFMA (sdqn_kernels_r3.hip)
-  LV_CONV1_WGRAD_BF16 = 8,    // conv1_wgrad on packed-bf16 MFMA (sdqn_kernels_r3.hip)
-  LV_C1W_IN_WGRADS = 16,      // float16, B >= 128: conv1_wgrad rides in the K_WGRADS launch and K_BWD1 launches nothing (sdqn_kernels_bt.hip)
-  LV_C1W_FIRST = 32,          // ... with its workgroups first in the block-id order
-};
-// LaunchTune::wt / option "wt" — write-through (sc1) epilogue stores, one bit per launch (WT_UPDATE reaches its kernel as UpdateArgs::wt)
-enum WriteThrough {
-  WT_CONV2_FWD = 1, WT_CONV3_FWD = 2, WT_FC4_FWD = 4, WT_FC4_DGRAD = 8, WT_BWD3 = 16, WT_BWD2 = 32, WT_CONV1_WGRAD = 64, WT_CONV1_FWD = 128,
-  WT_UPDATE = 256, WT_ALL = 511
-};
-// host-side launch choices that never reach a kernel (kept out of StepArgs: kernel-argument bytes are not free)
-struct LaunchTune {
-  int nw_override[12];      // tuning hook: waves per tile for kernel id i (0 = built-in choice)
-  const int64_t* host_idx;  // ring paths, B <= 32: this step's sampled indexes in HOST memory (they ride in the kernel arguments of conv1_bf16_kernel)
-  int r3_xcd;               // round-3 kernels' XCD-contiguous tile maps: bit 0 conv1_fwd (bf16), bit 1 conv1_wgrad (bf16)
-  int wt;                   // WriteThrough bits
-  int bt[K_COUNT];          // B >= 128, float32: block-tile engine (sdqn_kernels_bt.hip) per kernel id; 0 = built-in block shape, n > 0 = menu entry, < 0 = latency engine
-  int variant;              // LaunchVariant bits
-};
+// Which kernel a stage runs is resolve_route's answer (launch_route.h); launch_kernel resolves once and hands the Route to the executor of the
+// translation unit that owns the launch form.  An id that rides in another id's launch (Route::unit == U_NONE) launches nothing.
+inline RouteKey route_key(const StepArgs& a, const LaunchTune& t) {
+  return RouteKey{a.B, a.nz, a.h16, a.bn, a.f4w_count, a.from_ring, a.tps1, a.src != nullptr, a.w1p[0] && a.w1p[a.nz > 1 ? 1 : 0], t.host_idx != nullptr};
+}
+hipError_t launch_lat(const Route& r, int id, const StepArgs& a, const LaunchTune& t, hipStream_t s);      // sdqn_kernels.hip: float32 on the latency engine
+hipError_t launch_ext(const Route& r, int id, const StepArgs& a, const LaunchTune& t, hipStream_t s);      // sdqn_kernels_ext.hip: float16 on the latency engine
+hipError_t launch_r3(const Route& r, int id, const StepArgs& a, const LaunchTune& t, hipStream_t s);       // sdqn_kernels_r3.hip: bf16 conv1 kernels, write-through forms, conv3 on 36-deep chunks
+hipError_t launch_bt(const Route& r, int id, const StepArgs& a, const LaunchTune& t, hipStream_t s);       // sdqn_kernels_bt.hip: block tiles and the hand-written kernels beside them
+hipError_t launch_ss(const Route& r, int id, const StepArgs& a, const LaunchTune& t, hipStream_t s);       // sdqn_kernels_ss.hip: sample-stationary convolution chains
 hipError_t launch_kernel(int id, const StepArgs& a, const LaunchTune& t, hipStream_t s);     // the GEMM-shaped stages (single or multi-problem launches)
 hipError_t launch_head(const StepArgs& a, const HeadArgs& h, hipStream_t s, bool q_system_scope = false);   // q_system_scope: h.q is mapped host memory (acting path)
 hipError_t launch_update(const UpdateArgs& u, hipStream_t s);

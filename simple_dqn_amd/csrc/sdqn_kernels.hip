@@ -1,4 +1,6 @@
 // sdqn_kernels.hip — device code of the DQN train step for gfx950 (MI355X / CDNA4).
+//   * launch_kernel : resolves a stage's route (launch_route.h) and calls the executor of the unit that launches it
+//   * launch_lat    : this file's executor — float32 on the latency engine (batch-norm raw outputs, nw overrides, throughput regime, default)
 //   * gemm_kernel<P> instantiations (gemm_engine.h / problems.h): conv1..3, fc4, all dgrad/wgrad
 //   * head_kernel   : fc4 slab reduce + ReLU, fc5 of both nets, max_a Q', TD target, delta, cost term,
 //                     clip, fc5 dgrad            (deepqnetwork.py:120-159 without any host round trip)
@@ -32,104 +34,101 @@ static hipError_t launch_nw(int nw, const StepArgs& a, hipStream_t s) {
   }
 }
 
-// Waves per workgroup = how many 32-deep K-chunks run concurrently on one output tile (gemm_engine.h).
-// The fp16 mode's problems live in sdqn_kernels_ext.hip: hipcc's schedule of the default kernels depends on what else is
-// instantiated in their translation unit (measured: -1 % step rate when the new variants shared this file), so this file stays
-// what round 1 tuned.
-hipError_t launch_kernel_ext(int id, const StepArgs& a, const LaunchTune& t, hipStream_t s, bool* handled);
-
-hipError_t launch_kernel_r3(int id, const StepArgs& a, const LaunchTune& t, hipStream_t s, bool* handled);
-hipError_t launch_kernel_bt(int id, const StepArgs& a, const LaunchTune& t, hipStream_t s, bool* handled);
-hipError_t launch_kernel_ss(int id, const StepArgs& a, const LaunchTune& t, hipStream_t s, bool* handled);
-
+// One GEMM-shaped stage of the step: resolve its route (launch_route.h holds every predicate), then the executor of the unit that owns the
+// launch form builds the arguments and launches.  Each family of launch variants is a translation unit of its own: hipcc's schedule of the
+// default kernels depends on what else is instantiated beside them (measured: -1 % step rate when the float16 variants shared this file),
+// so this file's set of instantiations stays what round 1 tuned.
 hipError_t launch_kernel(int id, const StepArgs& a, const LaunchTune& t, hipStream_t s) {
-  if (a.B >= 128 || a.h16) {   // throughput regime (and float16 at any batch size): the sample-stationary convolution chains (round 6;
-    bool handled = false;      // sdqn_kernels_ss.hip), then — B >= 128 — the block-tile engine (round 4; sdqn_kernels_bt.hip) take what they implement
-    hipError_t e = launch_kernel_ss(id, a, t, s, &handled);
-    if (handled) return e;
-    e = launch_kernel_bt(id, a, t, s, &handled);        // (B < 128: float16's conv1 kernels on request only)
-    if (handled) return e;
+  const Route r = resolve_route(id, route_key(a, t), t);
+  switch (r.unit) {
+    case U_NONE: return hipSuccess;          // rides in the launch of r.rides_in
+    case U_SS: return launch_ss(r, id, a, t, s);
+    case U_BT: return launch_bt(r, id, a, t, s);
+    case U_R3: return launch_r3(r, id, a, t, s);
+    case U_EXT: return launch_ext(r, id, a, t, s);
+    case U_LAT: return launch_lat(r, id, a, t, s);
   }
-  if (t.variant || t.wt) {          // round-3 launch variants live in their own translation unit (same reason as sdqn_kernels_ext.hip)
-    bool handled = false;
-    const hipError_t e = launch_kernel_r3(id, a, t, s, &handled);
-    if (handled) return e;
-  }
-  if (a.h16) {
-    bool handled = false;
-    const hipError_t e = launch_kernel_ext(id, a, t, s, &handled);
-    if (handled) return e;
-  }
-  if (a.bn) {                  // --batch_norm forward: raw linear outputs (same tilings as the default problems)
-    switch (id) {
-      case K_CONV1_FWD: return launch_gemm<Conv1FwdRaw, 8>(a, s);
-      case K_CONV2_FWD: return a.B >= 128 ? launch_gemm<Staged<Conv2FwdRaw>, 8>(a, s) : launch_gemm<Conv2FwdRaw, 16>(a, s);
-      case K_CONV3_FWD: return a.B >= 128 ? launch_gemm<Staged<Conv3FwdRaw>, 8>(a, s) : launch_gemm<Staged<Conv3FwdRaw>, 9>(a, s);
-      default: break;
+  return hipErrorInvalidValue;
+}
+
+// float32 on the latency engine.  Waves per workgroup = how many 32-deep K-chunks run concurrently on one output tile (gemm_engine.h).
+hipError_t launch_lat(const Route& r, int id, const StepArgs& a, const LaunchTune&, hipStream_t s) {
+  switch (r.form) {
+    case LAT_BN: case LAT_BN_B128: {         // --batch_norm forward: raw linear outputs (same tilings as the default problems)
+      const bool b128 = r.form == LAT_BN_B128;
+      switch (id) {
+        case K_CONV1_FWD: return launch_gemm<Conv1FwdRaw, 8>(a, s);
+        case K_CONV2_FWD: return b128 ? launch_gemm<Staged<Conv2FwdRaw>, 8>(a, s) : launch_gemm<Conv2FwdRaw, 16>(a, s);
+        case K_CONV3_FWD: return b128 ? launch_gemm<Staged<Conv3FwdRaw>, 8>(a, s) : launch_gemm<Staged<Conv3FwdRaw>, 9>(a, s);
+        default: return hipErrorInvalidValue;
+      }
     }
-  }
-  if (id >= 0 && id < 12 && t.nw_override[id] > 0) {          // tuning hook (sdqn_net_set_option "nw:<id>")
-    const int nw = t.nw_override[id];
-    switch (id) {
-      case K_CONV1_FWD: return launch_nw<Conv1Fwd>(nw, a, s);
-      case K_CONV2_FWD: return launch_nw<Conv2Fwd>(nw, a, s);
-      case K_CONV3_FWD: if (nw == 9) return launch_gemm<Staged<Conv3Fwd>, 9>(a, s); return launch_nw<Conv3Fwd>(nw, a, s);    // 9 = round 1's choice
-      case K_FC4_FWD: return launch_nw<Fc4Fwd>(nw, a, s);
-      case K_FC4_DGRAD: return launch_nw<Fc4Dgrad>(nw, a, s);
-      case K_CONV3_DGRAD: return launch_nw<Conv3Dgrad>(nw, a, s);
-      case K_CONV3_WGRAD: return launch_nw<Conv3Wgrad>(nw, a, s);
-      case K_CONV2_DGRAD: return launch_nw<Conv2Dgrad>(nw, a, s);
-      case K_CONV2_WGRAD: return launch_nw<Conv2Wgrad>(nw, a, s);
-      case K_CONV1_WGRAD: return launch_nw<Conv1Wgrad>(nw, a, s);
-      default: break;
+    case LAT_NW2: case LAT_NW4: case LAT_NW8: case LAT_NW9: case LAT_NW16: {      // tuning hook (sdqn_net_set_option "nw:<id>")
+      const int nw = r.form == LAT_NW2 ? 2 : r.form == LAT_NW4 ? 4 : r.form == LAT_NW8 ? 8 : r.form == LAT_NW9 ? 9 : 16;
+      switch (id) {
+        case K_CONV1_FWD: return launch_nw<Conv1Fwd>(nw, a, s);
+        case K_CONV2_FWD: return launch_nw<Conv2Fwd>(nw, a, s);
+        case K_CONV3_FWD: if (nw == 9) return launch_gemm<Staged<Conv3Fwd>, 9>(a, s); return launch_nw<Conv3Fwd>(nw, a, s);    // 9 = round 1's choice
+        case K_FC4_FWD: return launch_nw<Fc4Fwd>(nw, a, s);
+        case K_FC4_DGRAD: return launch_nw<Fc4Dgrad>(nw, a, s);
+        case K_CONV3_DGRAD: return launch_nw<Conv3Dgrad>(nw, a, s);
+        case K_CONV3_WGRAD: return launch_nw<Conv3Wgrad>(nw, a, s);
+        case K_CONV2_DGRAD: return launch_nw<Conv2Dgrad>(nw, a, s);
+        case K_CONV2_WGRAD: return launch_nw<Conv2Wgrad>(nw, a, s);
+        case K_CONV1_WGRAD: return launch_nw<Conv1Wgrad>(nw, a, s);
+        default: return hipErrorInvalidValue;
+      }
     }
-  }
-  if (a.B >= 128) {            // throughput regime (thousands of tiles per launch): tools/sweep_nw.py at B = 256
-    switch (id) {
-      case K_CONV1_FWD: return launch_gemm<Conv1Fwd, 8>(a, s);
-      case K_CONV2_FWD: return launch_gemm<Staged<Conv2Fwd>, 8>(a, s);
-      case K_CONV3_FWD: return launch_gemm<Staged<Conv3Fwd>, 8>(a, s);
-      case K_FC4_FWD: return launch_gemm<Staged<Fc4Fwd>, 8>(a, s);
-      case K_FC4_DGRAD: return launch_gemm<Staged<Fc4Dgrad>, 4>(a, s);
-      case K_CONV3_DGRAD: return launch_gemm<Staged<Conv3Dgrad>, 8>(a, s);
-      case K_CONV2_DGRAD: return launch_gemm<Staged<Conv2Dgrad>, 8>(a, s);
-      case K_BWD3:
-        if (a.f4w_count > 0) return launch_multi<512, Fc4Wgrad, 8, Staged<Conv3Dgrad>, 8, Conv3Wgrad, 8>(a, true, true, s);
-        return launch_multi<512, NoProblem, 2, Staged<Conv3Dgrad>, 8, Conv3Wgrad, 8>(a, true, true, s);
-      case K_BWD2: return launch_multi<512, NoProblem, 2, Staged<Conv2Dgrad>, 8, Conv2Wgrad, 8>(a, true, true, s);
-      default: break;
+    case LAT_THROUGHPUT: case LAT_THROUGHPUT_F4W:      // B >= 128 (thousands of tiles per launch): tools/sweep_nw.py at B = 256
+      switch (id) {
+        case K_CONV1_FWD: return launch_gemm<Conv1Fwd, 8>(a, s);
+        case K_CONV2_FWD: return launch_gemm<Staged<Conv2Fwd>, 8>(a, s);
+        case K_CONV3_FWD: return launch_gemm<Staged<Conv3Fwd>, 8>(a, s);
+        case K_FC4_FWD: return launch_gemm<Staged<Fc4Fwd>, 8>(a, s);
+        case K_FC4_DGRAD: return launch_gemm<Staged<Fc4Dgrad>, 4>(a, s);
+        case K_CONV3_DGRAD: return launch_gemm<Staged<Conv3Dgrad>, 8>(a, s);
+        case K_CONV2_DGRAD: return launch_gemm<Staged<Conv2Dgrad>, 8>(a, s);
+        case K_BWD3:
+          if (r.form == LAT_THROUGHPUT_F4W) return launch_multi<512, Fc4Wgrad, 8, Staged<Conv3Dgrad>, 8, Conv3Wgrad, 8>(a, true, true, s);
+          return launch_multi<512, NoProblem, 2, Staged<Conv3Dgrad>, 8, Conv3Wgrad, 8>(a, true, true, s);
+        case K_BWD2: return launch_multi<512, NoProblem, 2, Staged<Conv2Dgrad>, 8, Conv2Wgrad, 8>(a, true, true, s);
+        default: return hipErrorInvalidValue;
+      }
+    case LAT_DEFAULT: case LAT_DEFAULT_F4W: case LAT_DEFAULT_B32_F4W: case LAT_F4W_NW1: case LAT_F4W_NW2: case LAT_F4W_NW4: case LAT_F4W_NW8: {
+      const bool f4w = r.form == LAT_DEFAULT_F4W, b32 = r.form == LAT_DEFAULT_B32_F4W;
+      switch (id) {
+        case K_CONV1_FWD: return launch_gemm<Conv1Fwd, 8>(a, s);        // K = 256  -> 8 chunks
+        case K_CONV2_FWD: return launch_gemm<Conv2Fwd, 16>(a, s);       // K = 512  -> 16 chunks
+        case K_CONV3_FWD: return launch_gemm<Conv3Fwd, 16>(a, s);       // K = 576 -> 18 chunks over 16 waves (staged, 9 waves x 2 chunks: -0.4 %)
+        case K_FC4_FWD: return launch_gemm<Staged<Fc4Fwd>, 14>(a, s);   // K = 3136 -> 98 chunks = S4(7) x 14; rows 12.5 KB apart: staged
+        case K_FC4_DGRAD: return launch_gemm<Staged<Fc4Dgrad>, 16>(a, s);   // K = 512; rows 2 KB apart: staged
+        case K_FC4_WGRAD:                                               // K = B
+          if (r.form == LAT_F4W_NW1) return launch_gemm<Fc4Wgrad, 1>(a, s);
+          if (r.form == LAT_F4W_NW2) return launch_gemm<Fc4Wgrad, 2>(a, s);
+          if (r.form == LAT_F4W_NW4) return launch_gemm<Fc4Wgrad, 4>(a, s);
+          return launch_gemm<Fc4Wgrad, 8>(a, s);
+        case K_CONV3_DGRAD: return launch_gemm<Staged<Conv3Dgrad>, 8>(a, s);   // K = 576 (same split as inside K_BWD3: bit-identical)
+        case K_CONV3_WGRAD: return launch_gemm<Conv3Wgrad, 8>(a, s);    // K = B*49 split over slabs
+        case K_CONV2_DGRAD: return launch_gemm<Conv2Dgrad, 8>(a, s);    // K = 256 per parity class
+        case K_CONV2_WGRAD: return launch_gemm<Conv2Wgrad, 8>(a, s);
+        case K_CONV1_WGRAD: return launch_gemm<Conv1Wgrad, 16>(a, s);
+        // multi-problem launches.  512-thread workgroups (8 waves): at <= 90 VGPRs two of them are resident per CU,
+        // so every tile of the launch is resident at once and the problems' latency chains overlap.  Fc4Wgrad is the
+        // first problem so its memory-bound read-modify-write stream starts earliest (one tile per wave at B <= 32).
+        case K_BWD3:
+          // (problem order = dispatch order: the long conv3 tiles first, the streaming fc4 tiles fill in behind them: +1 % step rate)
+          if (b32) return launch_multi<512, Staged<Conv3Dgrad>, 8, Conv3Wgrad, 8, Fc4Wgrad, 1>(a, true, true, s);
+          if (f4w) return launch_multi<512, Fc4Wgrad, 8, Staged<Conv3Dgrad>, 8, Conv3Wgrad, 8>(a, true, true, s);
+          return launch_multi<512, NoProblem, 2, Staged<Conv3Dgrad>, 8, Conv3Wgrad, 8>(a, true, true, s);
+        case K_BWD2:
+          if (b32) return launch_multi<512, Fc4Wgrad, 1, Conv2Dgrad, 8, Conv2Wgrad, 8>(a, true, true, s);
+          return launch_multi<512, NoProblem, 2, Conv2Dgrad, 8, Conv2Wgrad, 8>(a, true, true, s);
+        case K_BWD1:
+          if (b32) return launch_multi<1024, Fc4Wgrad, 1, Conv1Wgrad, 16, NoProblem, 2>(a, true, false, s);
+          return launch_multi<1024, NoProblem, 2, Conv1Wgrad, 16, NoProblem, 2>(a, true, false, s);
+        default: return hipErrorInvalidValue;
+      }
     }
-  }
-  switch (id) {
-    case K_CONV1_FWD: return launch_gemm<Conv1Fwd, 8>(a, s);        // K = 256  -> 8 chunks
-    case K_CONV2_FWD: return launch_gemm<Conv2Fwd, 16>(a, s);       // K = 512  -> 16 chunks
-    case K_CONV3_FWD: return launch_gemm<Conv3Fwd, 16>(a, s);       // K = 576 -> 18 chunks over 16 waves (staged, 9 waves x 2 chunks: -0.4 %)
-    case K_FC4_FWD: return launch_gemm<Staged<Fc4Fwd>, 14>(a, s);   // K = 3136 -> 98 chunks = S4(7) x 14; rows 12.5 KB apart: staged
-    case K_FC4_DGRAD: return launch_gemm<Staged<Fc4Dgrad>, 16>(a, s);   // K = 512; rows 2 KB apart: staged
-    case K_FC4_WGRAD:                                               // K = B
-      if (a.B <= 32) return launch_gemm<Fc4Wgrad, 1>(a, s);
-      if (a.B <= 64) return launch_gemm<Fc4Wgrad, 2>(a, s);
-      if (a.B <= 128) return launch_gemm<Fc4Wgrad, 4>(a, s);
-      return launch_gemm<Fc4Wgrad, 8>(a, s);
-    case K_CONV3_DGRAD: return launch_gemm<Staged<Conv3Dgrad>, 8>(a, s);   // K = 576 (same split as inside K_BWD3: bit-identical)
-    case K_CONV3_WGRAD: return launch_gemm<Conv3Wgrad, 8>(a, s);    // K = B*49 split over slabs
-    case K_CONV2_DGRAD: return launch_gemm<Conv2Dgrad, 8>(a, s);    // K = 256 per parity class
-    case K_CONV2_WGRAD: return launch_gemm<Conv2Wgrad, 8>(a, s);
-    case K_CONV1_WGRAD: return launch_gemm<Conv1Wgrad, 16>(a, s);
-    // multi-problem launches.  512-thread workgroups (8 waves): at <= 90 VGPRs two of them are resident per CU,
-    // so every tile of the launch is resident at once and the problems' latency chains overlap.  Fc4Wgrad is the
-    // first problem so its memory-bound read-modify-write stream starts earliest (one tile per wave at B <= 32).
-    case K_BWD3:
-      // (problem order = dispatch order: the long conv3 tiles first, the streaming fc4 tiles fill in behind them: +1 % step rate)
-      if (a.B <= 32 && a.f4w_count > 0) return launch_multi<512, Staged<Conv3Dgrad>, 8, Conv3Wgrad, 8, Fc4Wgrad, 1>(a, true, true, s);
-      if (a.f4w_count > 0) return launch_multi<512, Fc4Wgrad, 8, Staged<Conv3Dgrad>, 8, Conv3Wgrad, 8>(a, true, true, s);
-      return launch_multi<512, NoProblem, 2, Staged<Conv3Dgrad>, 8, Conv3Wgrad, 8>(a, true, true, s);
-    case K_BWD2:
-      if (a.B <= 32 && a.f4w_count > 0) return launch_multi<512, Fc4Wgrad, 1, Conv2Dgrad, 8, Conv2Wgrad, 8>(a, true, true, s);
-      return launch_multi<512, NoProblem, 2, Conv2Dgrad, 8, Conv2Wgrad, 8>(a, true, true, s);
-    case K_BWD1:
-      if (a.B <= 32 && a.f4w_count > 0) return launch_multi<1024, Fc4Wgrad, 1, Conv1Wgrad, 16, NoProblem, 2>(a, true, false, s);
-      return launch_multi<1024, NoProblem, 2, Conv1Wgrad, 16, NoProblem, 2>(a, true, false, s);
     default: return hipErrorInvalidValue;
   }
 }

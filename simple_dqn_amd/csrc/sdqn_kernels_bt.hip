@@ -1,13 +1,14 @@
-// sdqn_kernels_bt.hip — the throughput regime (B >= 128, float32) on the block-tile engine (gemm_engine_bt.h): own translation unit,
-// like every other family of launch variants (hipcc's schedule of a kernel depends on what is instantiated beside it).
+// sdqn_kernels_bt.hip — executor of the BT_* launch forms (launch_route.h): the block-tile engine (gemm_engine_bt.h) of the throughput
+// regime (B >= 128) and the hand-written conv1 kernels beside it.  Own translation unit, like every other family of launch variants (hipcc's
+// schedule of a kernel depends on what is instantiated beside it).
 //
-//   forward   conv2 / conv3 / fc4          one launch each (conv1 stays on its packed-bf16 kernel, sdqn_kernels_r3.hip)
-//   backward  fc4_dgrad                    one launch
-//             bwd3 = fc4_wgrad (+ fused RMSProp of W4) || conv3_dgrad || conv3_wgrad          one multi-problem launch
-//             bwd2 = conv2_dgrad (4 stride-parity classes) || conv2_wgrad                     one multi-problem launch
-//   and every backward problem as a launch of its own (fused_launches = 0 / two_streams): the same block shapes, so fused and
-//   unfused steps stay bit-identical.
-// LaunchTune::bt[id]: 0 = the built-in block shape, n > 0 = menu entry n (tools/sweep_bt.py), < 0 = this launch on the latency engine.
+//   float32   BT_SINGLE_MENU*  conv2 / conv3 / fc4 forward, fc4_dgrad, and every backward problem as a launch of its own (unfused steps: the
+//                              same block shapes as the fused launches, so fused and unfused steps stay bit-identical)
+//             BT_FUSED_MENU*   bwd3 = fc4_wgrad (+ fused RMSProp of W4) || conv3_dgrad || conv3_wgrad, bwd2 = conv2_dgrad || conv2_wgrad
+//             BT_C1W_*         conv1's weight gradient (conv1 forward stays on its packed-bf16 kernel, sdqn_kernels_r3.hip)
+//   float16   BT_H_MENU*       forward / dgrad launches, BT_WGRADS* the weight gradients behind them, BT_CONV1_H_* / BT_C1W_H_* conv1
+// *_MENU0 + n is menu entry n of LaunchTune::bt[id] (tools/sweep_bt.py; entry 0 = the built-in block shape); which (id, entry) pairs exist
+// is tabulated beside the RouteForm enum, and DESIGN.md 12 prints what each entry means per id, regime and datatype.
 #include <stdlib.h>
 #include "gemm_engine_bt.h"
 #include "problems_wt.h"
@@ -128,7 +129,7 @@ static hipError_t launch_fused(int id, int menu, const StepArgs& a, hipStream_t 
 //     (kernel rows r = 0..3 / 4..7, column s = lane & 7); double-buffered LDS stages, the next chunk's loads in flight under the MFMAs.
 struct C1wBtArgs { const uint8_t* src; const float* d1; float* slab1; const int64_t* idx; int B, from_ring, tps1, Kt; };
 typedef __bf16 c1w_bf16x8 __attribute__((ext_vector_type(8)));
-constexpr int C1W_CH = 80;                          // output positions per chunk: 4 output rows of one sample, 5 MFMA steps of 16
+constexpr int C1W_CH = route::C1W_CHUNK;                          // output positions per chunk: 4 output rows of one sample, 5 MFMA steps of 16
 constexpr int C1W_REG = 20 * W0;                    // bytes of one frame's staged rows (pixel rows 4 y0 .. 4 y0 + 19): 1680
 constexpr int C1W_DPITCH = 3 * K1 + 8;              // ushorts per k row of the delta planes: [plane][32 maps] + pad (208 bytes)
 constexpr int C1W_STAGE = C0 * C1W_REG + C1W_CH * C1W_DPITCH * 2;      // bytes per LDS stage: 6720 + 16640
@@ -237,8 +238,7 @@ __global__ void __launch_bounds__(256) c1w_bt_kernel(const C1wBtArgs c) {
 }
 
 static hipError_t launch_c1w_bt(const StepArgs& a, hipStream_t s) {
-  // slabs of whole 80-position chunks only (tps1 a multiple of 5: 160 positions); other slab sizes stay on the latency engine's kernel
-  if ((a.tps1 * 32) % C1W_CH != 0) return hipErrorInvalidValue;
+  // (slabs of whole 80-position chunks only — tps1 a multiple of 5: 160 positions — resolve_route keeps other slab sizes on the latency engine's kernel)
   C1wBtArgs c; c.src = a.src; c.d1 = a.d1; c.slab1 = a.slab1; c.idx = a.idx; c.B = a.B; c.from_ring = a.from_ring; c.tps1 = a.tps1; c.Kt = a.B * PIX1;
   SDQN_LAUNCH(c1w_bt_kernel, dim3(Conv1Wgrad::nbz(a)), dim3(256), 0, s, c);
   return hipGetLastError();
@@ -414,11 +414,10 @@ static hipError_t launch_bt_multi_c1w(const StepArgs& a, int c1_first, hipStream
   return hipGetLastError();
 }
 
-static hipError_t launch_c1w_h(const StepArgs& a, const LaunchTune& t, hipStream_t s) {
-  if ((a.tps1 * 32) % C1W_CH != 0) return hipErrorInvalidValue;       // slabs of whole 80-position chunks only
+static hipError_t launch_c1w_h(const StepArgs& a, bool exact, hipStream_t s) {      // (slabs of whole 80-position chunks only: launch_route.h)
   C1wHArgs c; c.src = a.src; c.d1 = a.h_d1; c.slab1 = a.slab1; c.idx = a.idx; c.B = a.B; c.from_ring = a.from_ring; c.tps1 = a.tps1; c.Kt = a.B * PIX1;
   c.inv_loss_scale = a.inv_loss_scale;
-  if (t.bt[K_BWD1] == 1) SDQN_LAUNCH(c1w_h_kernel<false>, dim3(Conv1Wgrad::nbz(a)), dim3(256), 0, s, c);        // first form (half(b / 255) operands)
+  if (!exact) SDQN_LAUNCH(c1w_h_kernel<false>, dim3(Conv1Wgrad::nbz(a)), dim3(256), 0, s, c);        // first form (half(b / 255) operands)
   else SDQN_LAUNCH(c1w_h_kernel<true>, dim3(Conv1Wgrad::nbz(a)), dim3(256), 0, s, c);
   return hipGetLastError();
 }
@@ -579,10 +578,10 @@ __global__ void __launch_bounds__(256) conv1_hb_kernel(const Conv1HArgs c) {
   }
 }
 
-static hipError_t launch_conv1_h(const StepArgs& a, const LaunchTune& t, hipStream_t s) {
+static hipError_t launch_conv1_h(const StepArgs& a, RouteForm form, hipStream_t s) {
   Conv1HArgs c; c.src = a.src; c.idx = a.idx; c.wht[0] = a.wht[0]; c.wht[1] = a.wht[1]; c.h_a1 = a.h_a1; c.B = a.B; c.from_ring = a.from_ring; c.post_off = a.post_off;
-  if (t.bt[K_CONV1_FWD] == 1) SDQN_LAUNCH(conv1_h_kernel, dim3(a.nz * a.B), dim3(256), 0, s, c);           // first form (half(b / 255) operands)
-  else if (t.bt[K_CONV1_FWD] == 2) SDQN_LAUNCH(conv1_hb_kernel<false>, dim3(a.nz * a.B), dim3(256), 0, s, c);
+  if (form == BT_CONV1_H_DIV255) SDQN_LAUNCH(conv1_h_kernel, dim3(a.nz * a.B), dim3(256), 0, s, c);           // first form (half(b / 255) operands)
+  else if (form == BT_CONV1_H_EXACT_WB) SDQN_LAUNCH(conv1_hb_kernel<false>, dim3(a.nz * a.B), dim3(256), 0, s, c);
   else SDQN_LAUNCH(conv1_hb_kernel<true>, dim3(a.nz * a.B), dim3(256), 0, s, c);
   return hipGetLastError();
 }
@@ -700,7 +699,6 @@ __global__ void __launch_bounds__(256) c1w_bt2_kernel(const C1wBtArgs c) {
 }
 
 static hipError_t launch_c1w_bt2(const StepArgs& a, hipStream_t s) {
-  if ((a.tps1 * 32) % C1W_CH != 0) return hipErrorInvalidValue;
   C1wBtArgs c; c.src = a.src; c.d1 = a.d1; c.slab1 = a.slab1; c.idx = a.idx; c.B = a.B; c.from_ring = a.from_ring; c.tps1 = a.tps1; c.Kt = a.B * PIX1;
   SDQN_LAUNCH(c1w_bt2_kernel, dim3(Conv1Wgrad::nbz(a)), dim3(256), 0, s, c);
   return hipGetLastError();
@@ -712,7 +710,9 @@ static hipError_t launch_c1w_bt2(const StepArgs& a, hipStream_t s) {
 #define BTH_CASE(N, P, BM, BN, WM, WN, D) case N: return launch_bt_h<BTH(P, BM, BN, WM, WN, D)>(a, s)
 static hipError_t launch_single_h(int id, int menu, const StepArgs& a, hipStream_t s) {
   switch (id) {
-    // (conv1 forward gathers bytes and converts per lane: 19.4 us here against 17.7 on the register-blocked routine -> only on request)
+    // (conv1 forward gathers bytes and converts per lane: 19.4 us here against 17.7 on the register-blocked routine.  resolve_route never sends
+    //  K_CONV1_FWD here — bt_h_menu has no row for it, launch_conv1_h's kernels took entries 1 / 2 — the two instantiations stay so that this
+    //  file's code object stays what was measured: without them every surviving kernel is unchanged, the object's layout is not)
     case K_CONV1_FWD: switch (menu) { BTH_CASE(1, Conv1FwdH, 128, 32, 4, 1, 2); BTH_CASE(2, Conv1FwdH, 256, 32, 4, 1, 2); default: break; } break;
     case K_CONV2_FWD: switch (menu) { BTH_CASE(0, Conv2FwdH, 64, 64, 2, 2, 2); BTH_CASE(6, Conv2FwdH, 64, 64, 2, 2, 2); BTH128_CASE(3, Conv2FwdH, 64, 64, 2, 2); BTH_CASE(1, Conv2FwdH, 128, 64, 2, 2, 2); BTH_CASE(2, Conv2FwdH, 64, 64, 2, 2, 3); default: break; } break;
     case K_CONV3_FWD: switch (menu) { BTH_CASE(0, Conv3FwdH, 64, 64, 2, 2, 2); BTH_CASE(6, Conv3FwdH, 64, 64, 2, 2, 2); BTH128_CASE(3, Conv3FwdH, 64, 64, 2, 2); BTH_CASE(1, Conv3FwdH, 128, 64, 2, 2, 2); BTH_CASE(2, Conv3FwdH, 64, 64, 2, 2, 3); default: break; } break;
@@ -725,75 +725,33 @@ static hipError_t launch_single_h(int id, int menu, const StepArgs& a, hipStream
   return hipErrorInvalidValue;
 }
 
-// every K range of the launch must be whole chunks for the x-contiguous loaders' zero fill to be the only tail handling — it is
-// (the loaders mask any k >= kend), so the routine takes every B >= 128; what it does not take: fp16 mode, batch-norm (raw outputs)
-hipError_t launch_kernel_bt(int id, const StepArgs& a, const LaunchTune& t, hipStream_t s, bool* handled) {
-  *handled = false;
-  if (a.bn) return hipSuccess;
-  if (id < 0 || id >= K_COUNT || t.bt[id] < 0) return hipSuccess;
-  if (a.B < 128) {                         // below the throughput regime: float16's exact-byte conv1 kernels
-    // forward: one workgroup per (net, sample) pays from 2 x 48 workgroups up (fused-loop steps/s against the latency engine's tiles:
-    // B = 32 18 490 vs 18 755, 48 14 833 vs 14 527, 64 13 943 vs 13 370, 100 11 198 vs 10 453); menu entry 7 = always, 6 = never
-    if (a.h16 && id == K_CONV1_FWD && (t.bt[id] == 7 || (t.bt[id] == 0 && a.B >= 48)) && t.nw_override[id] == 0) { *handled = true; return launch_conv1_h(a, t, s); }
-    if (a.h16 == 2 && id == K_BWD1 && t.bt[id] == 7 && a.f4w_count == 0) {
-      const hipError_t e1 = launch_c1w_h(a, t, s);
-      if (e1 == hipErrorInvalidValue) return hipSuccess;
-      *handled = true;
-      return e1;
-    }
-    return hipSuccess;
+// executor of the BT_* launch forms (launch_route.h).  (Every K range of a block-tile launch is handled by the loaders' zero fill — they mask any
+// k >= kend — so the routine takes every B >= 128.)
+hipError_t launch_bt(const Route& r, int id, const StepArgs& a, const LaunchTune&, hipStream_t s) {
+  // float16 K_WGRADS = fc4_wgrad (+ fused RMSProp) || conv3_wgrad || conv2_wgrad: k-major half panels, transpose reads
+  // (2 chunks of loads in flight per thread: 20.5 us at B = 256 against 22.4 / 22.0 with 3 / 4 — the launch is not load-latency bound)
+  typedef BtCfgHW<Fc4WgradH, 64, 64, 2, 2, 2> HF4W;
+  typedef BtCfgHW<Conv3WgradH, 64, 64, 2, 2, 2> HC3W;
+  typedef BtCfgHW<Conv2WgradH, 64, 64, 2, 2, 2> HC2W;
+  switch (r.form) {
+    case BT_CONV1_H_DIV255: case BT_CONV1_H_EXACT: case BT_CONV1_H_EXACT_WB: return launch_conv1_h(a, r.form, s);      // one workgroup per (net, sample)
+    // conv1's weight gradient: all 256 x 32 outputs of a K slab per workgroup, A from the bytes
+    // (the generic half routine with A from the bytes — BtCfgHW<Conv1WgradH, 256, 32, 4, 1> — fetches 8-byte patch-row pieces straight
+    //  from memory: 16 divergent loads per thread and chunk, 18.9 us at B = 256, no better than the wave-tile routine's 18.7)
+    case BT_C1W_H_DIV255: case BT_C1W_H_EXACT: return launch_c1w_h(a, r.form == BT_C1W_H_EXACT, s);
+    // conv1's weight gradient rides in the weight-gradient launch (K_BWD1 launches nothing), its workgroups last / first in the block-id order
+    case BT_WGRADS_C1W_LAST: case BT_WGRADS_C1W_FIRST: return launch_bt_multi_c1w<HF4W, HC3W, HC2W>(a, r.form == BT_WGRADS_C1W_FIRST ? 1 : 0, s);
+    case BT_WGRADS_D4: return launch_bt_multi<BtCfgHW<Fc4WgradH, 64, 64, 2, 2, 4>, BtCfgHW<Conv3WgradH, 64, 64, 2, 2, 4>, BtCfgHW<Conv2WgradH, 64, 64, 2, 2, 4>>(a, true, true, true, s);
+    case BT_WGRADS_D3: return launch_bt_multi<BtCfgHW<Fc4WgradH, 64, 64, 2, 2, 3>, BtCfgHW<Conv3WgradH, 64, 64, 2, 2, 3>, BtCfgHW<Conv2WgradH, 64, 64, 2, 2, 3>>(a, true, true, true, s);
+    case BT_WGRADS: return launch_bt_multi<HF4W, HC3W, HC2W>(a, true, true, true, s);
+    case BT_C1W_BYTES: return launch_c1w_bt(a, s);       // float32 conv1_wgrad, bytes x three bf16 planes of delta1: fragments from single-byte / two-byte LDS reads
+    case BT_C1W_TR: return launch_c1w_bt2(a, s);         //   ... from transpose reads (the built-in form)
+    default: break;
   }
-  if (a.h16) {                             // float16 mode: forward launches, dgrads, and the weight gradients behind them
-    if (id == K_WGRADS && a.h16 == 2) {    // fc4_wgrad (+ fused RMSProp) || conv3_wgrad || conv2_wgrad: k-major half panels, transpose reads
-      // (2 chunks of loads in flight per thread: 20.5 us at B = 256 against 22.4 / 22.0 with 3 / 4 — the launch is not load-latency bound)
-      typedef BtCfgHW<Fc4WgradH, 64, 64, 2, 2, 2> HF4W;
-      typedef BtCfgHW<Conv3WgradH, 64, 64, 2, 2, 2> HC3W;
-      typedef BtCfgHW<Conv2WgradH, 64, 64, 2, 2, 2> HC2W;
-      *handled = true;
-      // LV_C1W_IN_WGRADS (the step orchestration's decision, sdqn_api_step.hip): conv1's weight gradient rides in this launch and K_BWD1 launches nothing;
-      // LV_C1W_FIRST: its workgroups first in the block-id order
-      if (t.variant & LV_C1W_IN_WGRADS) return launch_bt_multi_c1w<HF4W, HC3W, HC2W>(a, (t.variant & LV_C1W_FIRST) ? 1 : 0, s);
-      if (t.bt[id] == 1) return launch_bt_multi<BtCfgHW<Fc4WgradH, 64, 64, 2, 2, 4>, BtCfgHW<Conv3WgradH, 64, 64, 2, 2, 4>, BtCfgHW<Conv2WgradH, 64, 64, 2, 2, 4>>(a, true, true, true, s);
-      if (t.bt[id] == 2) return launch_bt_multi<BtCfgHW<Fc4WgradH, 64, 64, 2, 2, 3>, BtCfgHW<Conv3WgradH, 64, 64, 2, 2, 3>, BtCfgHW<Conv2WgradH, 64, 64, 2, 2, 3>>(a, true, true, true, s);
-      return launch_bt_multi<HF4W, HC3W, HC2W>(a, true, true, true, s);
-    }
-    if (id == K_CONV1_FWD && t.bt[id] >= 0 && t.bt[id] <= 2 && t.nw_override[id] == 0) {   // one workgroup per (net, sample)
-      *handled = true;
-      return launch_conv1_h(a, t, s);
-    }
-    if (id == K_BWD1 && (t.variant & LV_C1W_IN_WGRADS)) { *handled = true; return hipSuccess; }      // (rode in the weight-gradient launch)
-    if (id == K_BWD1 && a.h16 == 2 && a.f4w_count == 0) {    // conv1's weight gradient: all 256 x 32 outputs of a K slab per workgroup, A from the bytes
-      // (the generic half routine with A from the bytes — BtCfgHW<Conv1WgradH, 256, 32, 4, 1> — fetches 8-byte patch-row pieces straight
-      //  from memory: 16 divergent loads per thread and chunk, 18.9 us at B = 256, no better than the wave-tile routine's 18.7)
-      const hipError_t e1 = launch_c1w_h(a, t, s);
-      if (e1 == hipErrorInvalidValue) return hipSuccess;
-      *handled = true;
-      return e1;
-    }
-    if (id >= 12 || t.nw_override[id] > 0) return hipSuccess;
-    const hipError_t eh = launch_single_h(id, t.bt[id], a, s);
-    if (eh == hipErrorInvalidValue) return hipSuccess;
-    *handled = true;
-    return eh;
-  }
-  // fc4 forward has 64 blocks of 64 x 64 per K slab and measured slower here than on the latency engine (21.0 vs 18.1 us at B = 256 with 7
-  // slabs and unconditional ring loads): block-tile only on request (menu entry > 0).  fc4_dgrad (196 blocks) moved here in round 4's second
-  // session: 12.4 us against 14.4 once its gating activations are fetched before the K loop (17.0 with the dependent loads in the epilogue)
-  if (id == K_FC4_FWD && t.bt[id] == 0) return hipSuccess;
-  if (id < 12 && t.nw_override[id] > 0) return hipSuccess;      // explicit latency-engine tuning hooks win
-  hipError_t e = hipErrorInvalidValue;
-  if ((id == K_BWD1 && a.f4w_count == 0) || id == K_CONV1_WGRAD) {             // conv1's weight gradient: bytes x three bf16 planes of delta1
-    e = t.bt[id] == 1 ? launch_c1w_bt(a, s) : launch_c1w_bt2(a, s);      // (menu 1: the first form, fragments from single-byte / two-byte LDS reads)
-    if (e == hipErrorInvalidValue) return hipSuccess;
-    *handled = true;
-    return e;
-  }
-  if (id == K_BWD3 || id == K_BWD2) e = launch_fused(id, t.bt[id], a, s);
-  else if (id == K_CONV2_FWD || id == K_CONV3_FWD || id == K_FC4_FWD || id == K_FC4_DGRAD || id == K_FC4_WGRAD || id == K_CONV3_DGRAD ||
-           id == K_CONV3_WGRAD || id == K_CONV2_DGRAD || id == K_CONV2_WGRAD) e = launch_single(id, t.bt[id], a, s);
-  if (e == hipErrorInvalidValue) return hipSuccess;       // no such entry: the caller falls through to the latency engine
-  *handled = true;
-  return e;
+  if (r.form >= BT_H_MENU0 && r.form <= BT_H_MENU6) return launch_single_h(id, r.form - BT_H_MENU0, a, s);
+  if (r.form >= BT_FUSED_MENU0 && r.form <= BT_FUSED_MENU7) return launch_fused(id, r.form - BT_FUSED_MENU0, a, s);
+  if (r.form >= BT_SINGLE_MENU0 && r.form <= BT_SINGLE_MENU8) return launch_single(id, r.form - BT_SINGLE_MENU0, a, s);
+  return hipErrorInvalidValue;
 }
 
 #ifdef SDQN_TIMING

@@ -1,10 +1,10 @@
-// sdqn_kernels_r3.hip — round-3 launch variants of the default fp32 step (own translation unit: hipcc's schedule of a kernel
-// depends on what else is instantiated beside it, see sdqn_kernels.hip).
+// sdqn_kernels_r3.hip — executor of the R3_* launch forms (launch_route.h): round-3 launch variants of the default fp32 step (own
+// translation unit: hipcc's schedule of a kernel depends on what else is instantiated beside it, see sdqn_kernels.hip).
 //
-//   K_CONV1_FWD with LV_CONV1_FWD_BF16: conv1_bf16_kernel below (bytes x 3-way bf16 split of W1 on packed-bf16 MFMA).
-//   K_BWD1 with LV_CONV1_WGRAD_BF16 (no fc4 share in the launch): conv1_wgrad_bf16_kernel (bytes x on-the-fly 3-way bf16 split of delta1).
-//   K_CONV3_FWD with LV_CONV3_C36 (B < 128): gemm36_kernel below.
-//   Any id with LaunchTune::wt bits: the default launch forms with the write-through (sc1) epilogues of problems_wt.h.
+//   R3_CONV1_BF16*: conv1_bf16_kernel / conv1_bf16_rows2_kernel below (bytes x 3-way bf16 split of W1 on packed-bf16 MFMA; LV_CONV1_FWD_BF16).
+//   R3_C1W_BF16*:   conv1_wgrad_bf16_kernel (bytes x on-the-fly 3-way bf16 split of delta1; LV_CONV1_WGRAD_BF16, no fc4 share in the launch).
+//   R3_CONV3_C36*:  gemm36_kernel below (LV_CONV3_C36, B < 128).
+//   R3_WT_*:        the default launch forms with the write-through (sc1) epilogues of problems_wt.h (LaunchTune::wt bits).
 #include "gemm_engine.h"
 #include "problems_h16.h"
 #include "kernels.h"
@@ -662,9 +662,10 @@ __global__ void __launch_bounds__(640 + 64 * NLW) conv1_bf16_rows2_kernel(const 
   }
 }
 
-hipError_t launch_kernel_r3(int id, const StepArgs& a, const LaunchTune& t, hipStream_t s, bool* handled) {
-  *handled = true;
-  if (id == K_CONV1_FWD && (t.variant & LV_CONV1_FWD_BF16) && !a.h16 && !a.bn && a.w1p[0] && a.w1p[a.nz > 1 ? 1 : 0]) {
+// executor of the R3_* launch forms (launch_route.h)
+hipError_t launch_r3(const Route& r, int id, const StepArgs& a, const LaunchTune& t, hipStream_t s) {
+  switch (r.form) {
+  case R3_CONV1_BF16_ROWS: case R3_CONV1_BF16_IDX: case R3_CONV1_BF16: {
     const int tiles = (a.B * PIX1 + 31) / 32, tpw = a.B >= 128 ? 4 : 1, wgs = (tiles + 4 * tpw - 1) / (4 * tpw);
     Conv1Args c; c.src = a.src; c.a1 = a.a1; c.w1p[0] = a.w1p[0]; c.w1p[1] = a.w1p[1]; c.idx = a.idx;
     c.B = a.B; c.nz = a.nz; c.from_ring = a.from_ring; c.tiles_per_net = tiles; c.wgs_per_net = wgs; c.tpw = tpw; c.xcd = t.r3_xcd & 1; c.pad_ = (t.wt & WT_CONV1_FWD) ? 1 : 0;
@@ -673,7 +674,7 @@ hipError_t launch_kernel_r3(int id, const StepArgs& a, const LaunchTune& t, hipS
     Lead l; memset(&l, 0, sizeof l);
     l.p[0] = c.src; l.p[1] = c.a1; l.p[2] = c.w1p[0]; l.p[3] = c.w1p[1]; l.p[4] = c.idx; l.B = c.B; l.s0 = tiles; l.s1 = wgs;
     l.ctl = c.xcd | c.pad_ << 1 | (c.from_ring ? 4 : 0) | (tpw & 15) << 4 | (a.arg_preload && a.B < 128 && tpw >= 0 && tpw < 16 && c.xcd < 2 && c.pad_ < 2 && c.post_off >= 0 && c.post_off < 32768 ? LEAD_ON : 0) | (int)((unsigned)c.post_off << 16);
-    if (a.B >= 128 && t.bt[K_CONV1_FWD] >= 0) {           // throughput regime  (option bt:0 = -1: the per-tile kernel, the test reference)
+    if (r.form == R3_CONV1_BF16_ROWS) {                   // throughput regime
       // round 5: persistent workgroups (one per CU), planes in registers, frames streamed in 4-row items; every workgroup of a net the same
       // number of samples where that is possible: Gz = ceil(B / ceil(B / (256 / nz)))
       // (rounds 4-5's other forms — one workgroup per sample with the frames staged, and the 10-wave pipeline without specialised
@@ -684,7 +685,7 @@ hipError_t launch_kernel_r3(int id, const StepArgs& a, const LaunchTune& t, hipS
       return hipGetLastError();
     }
     IdxIn ix;
-    if (t.host_idx && a.from_ring && a.B <= 32) {
+    if (r.form == R3_CONV1_BF16_IDX) {                    // ring step at B <= 32: the host's copy of the indexes rides in the arguments
       memset(ix.v, 0, sizeof ix.v);
       memcpy(ix.v, t.host_idx, (size_t)a.B * sizeof(int64_t));
       SDQN_LAUNCH(conv1_bf16_kernel<true>, dim3(a.nz * wgs), dim3(256), 0, s, SDQN_LEAD_ARGS(l), c, ix);
@@ -694,7 +695,7 @@ hipError_t launch_kernel_r3(int id, const StepArgs& a, const LaunchTune& t, hipS
     }
     return hipGetLastError();
   }
-  if ((id == K_BWD1 || id == K_CONV1_WGRAD) && (t.variant & LV_CONV1_WGRAD_BF16) && (id == K_CONV1_WGRAD || a.f4w_count == 0) && !a.h16 && !a.bn) {
+  case R3_C1W_BF16_IDX: case R3_C1W_BF16: {
     C1wArgs c; c.src = a.src; c.d1 = a.d1; c.slab1 = a.slab1; c.idx = a.idx; c.B = a.B; c.from_ring = a.from_ring; c.tps1 = a.tps1; c.Kt = a.B * PIX1; c.xcd = (t.r3_xcd >> 1) & 1; c.pad_ = (t.wt & WT_CONV1_WGRAD) ? 1 : 0;
     static_assert(sizeof(C1wArgs) == 56, "the index block follows at byte 64 + 56 of the argument segment");
     const dim3 grid(CRS1 / 32, 1, Conv1Wgrad::nbz(a));
@@ -702,54 +703,56 @@ hipError_t launch_kernel_r3(int id, const StepArgs& a, const LaunchTune& t, hipS
     Lead l; memset(&l, 0, sizeof l);
     l.p[0] = c.src; l.p[1] = c.d1; l.p[2] = c.slab1; l.p[3] = c.idx; l.B = c.B; l.s0 = c.tps1; l.s1 = c.Kt;
     l.ctl = c.xcd | c.pad_ << 1 | (c.from_ring ? 4 : 0) | (a.arg_preload && a.B < 128 && grid.z < 32768u ? LEAD_ON : 0) | (int)(grid.z << 16);
-    if (t.host_idx && a.from_ring && a.B <= 32) {
+    if (r.form == R3_C1W_BF16_IDX) {
       memcpy(ix.v, t.host_idx, (size_t)a.B * sizeof(int64_t));
       SDQN_LAUNCH(conv1_wgrad_bf16_kernel<true>, grid, dim3(1024), 0, s, SDQN_LEAD_ARGS(l), c, ix);
     } else SDQN_LAUNCH(conv1_wgrad_bf16_kernel<false>, grid, dim3(1024), 0, s, SDQN_LEAD_ARGS(l), c, ix);
     return hipGetLastError();
   }
-  // conv2 / conv3 forward with ONE workgroup per 32 x 64 output block (N = 64 = two 32-wide tiles): the register-blocked routine with
-  // 1 x 2 accumulators per wave loads the gathered A rows once for both tiles (the gather is the expensive operand: 64 cache lines per
-  // load instruction).  Same k order per accumulator as the unblocked tile: bit-identical.
-  if (a.B <= 32 && a.h16 == 2 && !a.bn && t.wt && !(id >= 0 && id < 12 && t.nw_override[id] > 0)) {      // float16 mode, default launch forms
-    if (id == K_CONV1_FWD && (t.wt & WT_CONV1_FWD)) return launch_gemm<Conv1FwdHWT, 8>(a, s);
-    if (id == K_CONV2_FWD && (t.wt & WT_CONV2_FWD)) return launch_gemm<Conv2FwdHWT, 16>(a, s);
-    if (id == K_CONV3_FWD && (t.wt & WT_CONV3_FWD)) return launch_gemm<Conv3FwdHWT, 16>(a, s);
-    if (id == K_FC4_FWD && (t.wt & WT_FC4_FWD)) return launch_gemm<Fc4FwdHWT, 14>(a, s);
-    if (id == K_FC4_DGRAD && (t.wt & WT_FC4_DGRAD)) return launch_gemm<Fc4DgradHWT, 16>(a, s);
-    // (bwd3 stays on plain stores in this mode: 16 404 vs 16 445 steps/s alone, 16 775 vs 16 809 with the others — tools/exp/README.md)
-    if (id == K_BWD2 && (t.wt & WT_BWD2)) return launch_multi<512, NoProblem, 2, Conv2DgradHWT, 8, Conv2WgradHWWT, 8>(a, true, true, s);
-    if (id == K_BWD1 && (t.wt & WT_CONV1_WGRAD)) return launch_multi<1024, NoProblem, 2, Conv1WgradHWWT, 16, NoProblem, 2>(a, true, false, s);
-  }
-  if (a.B <= 32 && !a.h16 && !a.bn && t.wt && !(id >= 0 && id < 12 && t.nw_override[id] > 0)) {       // write-through epilogues: the default launch forms with the *WT problems
-    if (id == K_CONV2_FWD && (t.wt & WT_CONV2_FWD)) return launch_gemm<Conv2FwdWT, 16>(a, s);
-    if (id == K_FC4_FWD && (t.wt & WT_FC4_FWD)) return launch_gemm<Staged<Fc4FwdWT>, 14>(a, s);
-    if (id == K_FC4_DGRAD && (t.wt & WT_FC4_DGRAD)) return launch_gemm<Staged<Fc4DgradWT>, 16>(a, s);
-    if (id == K_BWD3 && (t.wt & WT_BWD3) && a.f4w_count > 0) return launch_multi<512, Staged<Conv3DgradWT>, 8, Conv3WgradWT, 8, Fc4WgradWT, 1>(a, true, true, s);
-    if (id == K_BWD2 && (t.wt & WT_BWD2) && a.f4w_count == 0) return launch_multi<512, NoProblem, 2, Conv2DgradWT, 8, Conv2WgradWT, 8>(a, true, true, s);
-  }
-  if (a.B >= 128 && !a.h16 && !a.bn && t.wt && !(id >= 0 && id < 12 && t.nw_override[id] > 0)) {
-    // throughput regime: the same launch forms as sdqn_kernels.hip, write-through epilogues
-    if (id == K_CONV2_FWD && (t.wt & WT_CONV2_FWD)) return launch_gemm<Staged<Conv2FwdWT>, 8>(a, s);
-    if (id == K_CONV3_FWD && (t.wt & WT_CONV3_FWD)) return launch_gemm<Staged<Conv3FwdWT>, 8>(a, s);
-    if (id == K_FC4_FWD && (t.wt & WT_FC4_FWD)) return launch_gemm<Staged<Fc4FwdWT>, 8>(a, s);
-    if (id == K_FC4_DGRAD && (t.wt & WT_FC4_DGRAD)) return launch_gemm<Staged<Fc4DgradWT>, 4>(a, s);
-    if (id == K_BWD3 && (t.wt & WT_BWD3) && a.f4w_count > 0) return launch_multi<512, Fc4WgradWT, 8, Staged<Conv3DgradWT>, 8, Conv3WgradWT, 8>(a, true, true, s);
-    if (id == K_BWD2 && (t.wt & WT_BWD2) && a.f4w_count == 0) return launch_multi<512, NoProblem, 2, Staged<Conv2DgradWT>, 8, Conv2WgradWT, 8>(a, true, true, s);
-    if (id == K_BWD1 && (t.wt & WT_CONV1_WGRAD) && a.f4w_count == 0 && !(t.variant & LV_CONV1_WGRAD_BF16)) return launch_multi<1024, NoProblem, 2, Conv1WgradWT, 16, NoProblem, 2>(a, true, false, s);
-  }
-  if (id == K_CONV3_FWD && (t.variant & LV_CONV3_C36) && a.B < 128 && !a.h16 && !a.bn) {
+  case R3_WT_H16_B32:                        // float16 mode, B <= 32: the default launch forms, write-through epilogues
+    switch (id) {
+      case K_CONV1_FWD: return launch_gemm<Conv1FwdHWT, 8>(a, s);
+      case K_CONV2_FWD: return launch_gemm<Conv2FwdHWT, 16>(a, s);
+      case K_CONV3_FWD: return launch_gemm<Conv3FwdHWT, 16>(a, s);
+      case K_FC4_FWD: return launch_gemm<Fc4FwdHWT, 14>(a, s);
+      case K_FC4_DGRAD: return launch_gemm<Fc4DgradHWT, 16>(a, s);
+      // (bwd3 stays on plain stores in this mode: 16 404 vs 16 445 steps/s alone, 16 775 vs 16 809 with the others — tools/exp/README.md)
+      case K_BWD2: return launch_multi<512, NoProblem, 2, Conv2DgradHWT, 8, Conv2WgradHWWT, 8>(a, true, true, s);
+      case K_BWD1: return launch_multi<1024, NoProblem, 2, Conv1WgradHWWT, 16, NoProblem, 2>(a, true, false, s);
+      default: return hipErrorInvalidValue;
+    }
+  case R3_WT_B32:                            // float32, B <= 32: the default launch forms with the *WT problems
+    switch (id) {
+      case K_CONV2_FWD: return launch_gemm<Conv2FwdWT, 16>(a, s);
+      case K_FC4_FWD: return launch_gemm<Staged<Fc4FwdWT>, 14>(a, s);
+      case K_FC4_DGRAD: return launch_gemm<Staged<Fc4DgradWT>, 16>(a, s);
+      case K_BWD3: return launch_multi<512, Staged<Conv3DgradWT>, 8, Conv3WgradWT, 8, Fc4WgradWT, 1>(a, true, true, s);
+      case K_BWD2: return launch_multi<512, NoProblem, 2, Conv2DgradWT, 8, Conv2WgradWT, 8>(a, true, true, s);
+      default: return hipErrorInvalidValue;
+    }
+  case R3_WT_B128:                           // throughput regime: the same launch forms as sdqn_kernels.hip, write-through epilogues
+    switch (id) {
+      case K_CONV2_FWD: return launch_gemm<Staged<Conv2FwdWT>, 8>(a, s);
+      case K_CONV3_FWD: return launch_gemm<Staged<Conv3FwdWT>, 8>(a, s);
+      case K_FC4_FWD: return launch_gemm<Staged<Fc4FwdWT>, 8>(a, s);
+      case K_FC4_DGRAD: return launch_gemm<Staged<Fc4DgradWT>, 4>(a, s);
+      case K_BWD3: return launch_multi<512, Fc4WgradWT, 8, Staged<Conv3DgradWT>, 8, Conv3WgradWT, 8>(a, true, true, s);
+      case K_BWD2: return launch_multi<512, NoProblem, 2, Staged<Conv2DgradWT>, 8, Conv2WgradWT, 8>(a, true, true, s);
+      case K_BWD1: return launch_multi<1024, NoProblem, 2, Conv1WgradWT, 16, NoProblem, 2>(a, true, false, s);
+      default: return hipErrorInvalidValue;
+    }
+  case R3_CONV3_C36_WT: case R3_CONV3_C36: {
     static_assert(CRS3 == 16 * 36, "conv3's K is 16 chunks of 36");
     const dim3 grid((Conv3Fwd::M(a) + 31) / 32, (Conv3Fwd::N(a) + 31) / 32, Conv3Fwd::nbz(a));
     Lead l; memset(&l, 0, sizeof l);
-    if ((t.wt & WT_CONV3_FWD) && a.B <= 32) {
+    if (r.form == R3_CONV3_C36_WT) {
       Conv3FwdWT::lead_pack(a, l); l.B = a.B; l.s0 = lead_grid(grid); l.ctl = lead_ctl(a, a.arg_preload && lead_grid_fits(grid));
       SDQN_LAUNCH((gemm36_kernel<Conv3FwdWT>), grid, dim3(1024), 0, s, SDQN_LEAD_ARGS(l), a);
     } else SDQN_LAUNCH((gemm36_kernel<Conv3Fwd>), grid, dim3(1024), 0, s, SDQN_LEAD_ARGS(l), a);
     return hipGetLastError();
   }
-  *handled = false;
-  return hipSuccess;
+  default: return hipErrorInvalidValue;
+  }
 }
 
 #ifdef SDQN_TIMING

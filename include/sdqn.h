@@ -303,7 +303,8 @@ int sdqn_net_grad_from_half(sdqn_net_t h, const uint16_t* half_in, int64_t n);
 /* {overflow flag of the last from-half pass, log2 of the payload scale, clean steps since the scale last moved}; sync */
 int sdqn_net_half_payload_state(sdqn_net_t h, int* flag, int* scale_log2, int* clean_steps);
 /* q-values of the last train step: preq float[B,A] (online, prestates), maxpostq float[B] = the bootstrap value: max_a Q(theta-, post),
- * or with option "double_dqn" Q(theta-, post)[argmax_a Q(theta, post)] (first maximum on ties) (sync) */
+ * or with option "double_dqn" Q(theta-, post)[argmax_a Q(theta, post)] (first maximum on ties), or with sdqn_net_set_munchausen the soft
+ * value of the poststate (sync) */
 int sdqn_net_last_q(sdqn_net_t h, float* preq, float* maxpostq);
 int sdqn_net_train_iterations(sdqn_net_t h, int64_t* n);     /* deepqnetwork.py:168 */
 /* float16 mode under data parallel: the gradient is all-reduced as IEEE half with a dynamic power-of-two payload scale
@@ -320,6 +321,18 @@ int sdqn_net_set_epoch(sdqn_net_t h, int epoch);
  *              2 fused with fc4's all-reduce + update overlapped on the second communicator   3 one launch per problem   4 generic path
  *   update:    0 one update launch   1 serial data parallel (local sums, all-reduce, apply)   2 overlapped data parallel   3 grad_only */
 int sdqn_net_step_structure(sdqn_net_t h, int* structure, int* update);
+/* Munchausen DQN targets, --munchausen (Vieillard, Pietquin and Geist 2020; no reference counterpart).  With qbar = Q(theta-, .),
+ * pi = softmax(qbar / tau) and lse(q) = max q + tau log sum_a exp((q[a] - max q) / tau) (double, sum in action order), a train step's target is
+ *   y = r_c + alpha clip(qbar(s)[a] - lse(qbar(s)), clip, 0) + (terminal ? 0 : discount lse(qbar(s')))
+ * (with option "n_step": R, the done flag and discount^n in their places; the bonus is that of the first transition and is added on
+ * terminal transitions too).  Everything behind y — TD error, error clip, prioritized-replay weighting and priorities, backward, optimizer
+ * — is unchanged; alpha = 0 is Soft-DQN.  Each step is preceded by ONE more forward, the target net on the prestates (also without a
+ * target net, where theta- aliases theta), and sdqn_net_last_q's maxpostq is the soft value lse(qbar(s')).  on: 0 (default) / 1, any
+ * datatype and geometry, switchable between steps; tau > 0, 0 <= alpha <= 1, clip <= 0 (reference values 0.03, 0.9, -1), checked also
+ * when on = 0.  SDQN_ERR_ARG together with option "double_dqn" (the target has no argmax for the online net to choose) and with batch_norm
+ * (either order: option "double_dqn" is refused on a net whose Munchausen targets are on). */
+int sdqn_net_set_munchausen(sdqn_net_t h, int on, double alpha, double tau, double clip);
+int sdqn_net_get_munchausen(sdqn_net_t h, int* on, double* alpha, double* tau, double* clip);     /* any pointer may be NULL */
 /* option "double_dqn" (0 default / 1, any configuration, switchable between steps): Double DQN targets (van Hasselt, Guez and Silver
  * 2016): the online net picks each poststate's action, the target net values it (see sdqn_net_last_q).  The online net's forward on
  * the poststates rides as a third net slot in the step's own forward launches (batch_norm: a forward of its own in front of the step,

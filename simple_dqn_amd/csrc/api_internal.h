@@ -130,6 +130,9 @@ struct sdqn_net_s {
   // --double_dqn (option "double_dqn"): the forward launches carry a third net slot (problems.h: wslot); a1..a3, slab4, a4, q (and
   // h_a1..h_a3) are re-allocated with room for it when the option is first switched on
   bool double_dqn = false, slots3 = false;
+  // --munchausen (sdqn_net_set_munchausen): Munchausen DQN targets; every train step is preceded by a forward of the target
+  // net on the prestates (q slot 2: the slots3 re-allocation) and ends its forward with the Munchausen head (HeadArgs::train = 3)
+  bool munchausen = false; double mu_alpha = 0.9, mu_tau = 0.03, mu_clip = -1.0;
   int n_step = 1;                          // --n_step (option "n_step"): poststate frame offset of the ring paths, n-step head
   double target_tau = 0.0;                 // --target_tau (sdqn_net_set_target_tau): > 0: every train step is followed by one soft target update
   uint8_t *st_states = nullptr, *st_act = nullptr, *st_term = nullptr; int64_t* st_rew = nullptr; int64_t* d_idx = nullptr;
@@ -247,6 +250,7 @@ float* which_buf(sdqn_net_s* h, int which);
 bool bn_layer_span(sdqn_net_s* h, int which, int layer, float** base, int64_t* n);
 int gen_set(sdqn_net_s* h, int which, int layer, const void* w, int64_t n, bool f64);
 int gen_get(sdqn_net_s* h, int which, int layer, void* w, int64_t n, bool f64);
+int ensure_slots3(sdqn_net_s* h);                                  // room for a third net slot in a1..a4, slab4, q (first use of --double_dqn / --munchausen)
 int target_blend(sdqn_net_s* h, double tau);                       // one soft target update now (tau in (0, 1]; the caller has joined g_comm)
 int step_blend(sdqn_net_s* h);                                     // what every applied train step ends with: the blend of --target_tau, or nothing
 int gen_step_done(sdqn_net_s* h);                                  // generic path: a train step was enqueued (counter + step_blend)

@@ -45,6 +45,9 @@ struct GenericNet {
   virtual hipError_t soft_update(double tau) = 0;
   virtual bool has_target() const = 0;
   virtual hipError_t set_double_dqn(bool on) = 0;                        // --double_dqn (allocates the online-on-poststates Q on first use)
+  // --munchausen: Munchausen DQN targets; one more forward (target net, prestates) and the soft-value branch of the TD head
+  virtual hipError_t set_munchausen(bool on, double alpha, double tau, double clip) = 0;
+  virtual bool munchausen_on() const = 0;
   // --prioritized_replay (sdqn_per.hip): w != nullptr makes the following train steps weight the taken action's row by w[n] and write the
   // new priority (|delta| + eps)^alpha into newp[n]; nullptr: the standard step
   virtual void set_per(const float* w, float* newp, double alpha, double eps) = 0;

@@ -155,17 +155,33 @@ __global__ void __launch_bounds__(256) reduce_slabs_kernel(const T* __restrict__
   }
 }
 
+// --munchausen: lse(q) = v + tau log(sum_a exp((q[a] - v) / tau)), v = max_a q[a]; double, sum in action order
+template <typename T>
+__device__ inline double soft_value(const T* __restrict__ q, int A, double tau) {
+  double v = (double)q[0];
+  for (int a = 1; a < A; ++a) { const double x = (double)q[a]; v = x > v ? x : v; }
+  double s = 0.0;
+  for (int a = 0; a < A; ++a) s += exp(((double)q[a] - v) / tau);
+  return v + tau * log(s);
+}
+
 // ---- TD target, error, cost, clip (deepqnetwork.py:133-159) ----------------------------------------------------------------------
 template <typename T>
 __global__ void head_kernel(const T* __restrict__ q_on, const T* __restrict__ q_tg, const uint8_t* __restrict__ act,
                             const int64_t* __restrict__ rew, const uint8_t* __restrict__ term, T* __restrict__ dq,
                             T* __restrict__ cost_terms, T* __restrict__ maxq, int N, int A, double discount, double minr, double maxr, T clip,
                             const T* __restrict__ q_sel, const float* __restrict__ per_w, float* __restrict__ per_p, double per_alpha, double per_eps,
-                            int nstep, double gamma_n) {
+                            int nstep, double gamma_n, const T* __restrict__ q_mu, double mu_alpha, double mu_tau, double mu_clip) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
   T m = q_tg[(int64_t)n * A];
-  if (q_sel) {                                                                // --double_dqn: target net's Q at the online net's argmax
+  double bonus = 0.0, V = 0.0;
+  if (q_mu) {                                                                 // --munchausen: soft value of s', scaled log-policy bonus of (s, a)
+    V = soft_value(q_tg + (int64_t)n * A, A, mu_tau);
+    const double lp = (double)q_mu[(int64_t)n * A + act[n]] - soft_value(q_mu + (int64_t)n * A, A, mu_tau);     // tau ln pi(a|s) <= 0
+    bonus = mu_alpha * (lp < mu_clip ? mu_clip : (lp > 0.0 ? 0.0 : lp));
+    m = (T)V;
+  } else if (q_sel) {                                                                // --double_dqn: target net's Q at the online net's argmax
     int best = 0; T bv = q_sel[(int64_t)n * A];
     for (int a = 1; a < A; ++a) { const T v = q_sel[(int64_t)n * A + a]; if (v > bv) { bv = v; best = a; } }   // first maximum
     m = q_tg[(int64_t)n * A + best];
@@ -178,7 +194,8 @@ __global__ void head_kernel(const T* __restrict__ q_on, const T* __restrict__ q_
     r = (double)rew[n];
     r = r < minr ? minr : (r > maxr ? maxr : r);                              // np.clip(rewards, min_reward, max_reward) :136
   }
-  const double y = term[n] ? r : r + gam * (double)m;                         // :139-143, python float arithmetic
+  double y = term[n] ? r : r + gam * (double)m;                               // :139-143, python float arithmetic
+  if (q_mu) { const double rm = r + bonus; y = term[n] ? rm : rm + gam * V; }   // y = r_c + m + gamma V, V in double (maxq holds its rounded copy)
   const T target = (T)y;                                                      // stored into the backend dtype
   const int at = act[n];
   T d = (T)0;
@@ -261,6 +278,8 @@ class GenericNetT : public GenericNet {
   T *q = nullptr, *dq = nullptr, *d4 = nullptr, *dcol = nullptr, *cost_terms = nullptr, *cost = nullptr, *maxq = nullptr, *slab = nullptr;
   double* cost_sum = nullptr; int64_t slab_cap = 0;
   bool double_dqn = false; T* q_sel = nullptr;          // --double_dqn: Q of the online net on the poststates [B][A]
+  bool munchausen = false; T* q_mu = nullptr;           // --munchausen: Q of the target net on the prestates [B][A]
+  double mu_alpha = 0.0, mu_tau = 1.0, mu_clip = 0.0;
   uint8_t* st_states = nullptr; uint8_t* st_small = nullptr;
   std::vector<void*> allocs; std::vector<uint8_t> small_host;
 
@@ -345,10 +364,10 @@ class GenericNetT : public GenericNet {
   }
 
   // Q(states; W) of n states -> q + z*B*A; leaves cols / activations of this pass in col[] / act[]  (deepqnetwork.py:119-130,178-180)
-  // z = 2 (--double_dqn): the online net on the poststates, Q into q_sel
+  // z = 2 (--double_dqn): the online net on the poststates, Q into q_sel; z = 3 (--munchausen): the target net on the prestates, Q into q_mu
   hipError_t forward(int z, const uint8_t* states_dev, int n) {
-    const T* Wt = z == 1 ? theta_t : theta;
-    T* qz = z == 2 ? q_sel : q + (int64_t)z * B * A;
+    const T* Wt = (z & 1) ? theta_t : theta;
+    T* qz = z == 2 ? q_sel : (z == 3 ? q_mu : q + (int64_t)z * B * A);
     for (int l = 0; l < 4; ++l) {
       const ConvGeom& c = cv[l];
       const int64_t m = mrows(l, n), total = m * c.crs();
@@ -364,10 +383,11 @@ class GenericNetT : public GenericNet {
     GCHK(forward(1, post, B));                                                 // target net on the poststates :119-125
     const bool dd = double_dqn && theta_t != theta;                            // (no target net: Double DQN is standard DQN)
     if (dd) GCHK(forward(2, post, B));                                         // --double_dqn: online net on the poststates
+    if (munchausen) GCHK(forward(3, pre, B));                                  // --munchausen: target net on the prestates (always, also when theta- aliases theta)
     GCHK(forward(0, pre, B));                                                  // online net on the prestates, tensors kept :128-130
     hipLaunchKernelGGL(head_kernel<T>, dim3((B + 63) / 64), dim3(64), 0, st, (const T*)q, (const T*)(q + (int64_t)B * A), actions, rew, term,
                        dq, cost_terms, maxq, B, A, cfg.discount_rate, cfg.min_reward, cfg.max_reward, (T)cfg.clip_error, (const T*)(dd ? q_sel : nullptr),
-                       per_w, per_p, per_alpha, per_eps, nstep, gamma_n);
+                       per_w, per_p, per_alpha, per_eps, nstep, gamma_n, (const T*)(munchausen ? q_mu : nullptr), mu_alpha, mu_tau, mu_clip);
     hipLaunchKernelGGL(cost_kernel<T>, dim3(1), dim3(64), 0, st, (const T*)cost_terms, cost, cost_sum, B);
     // ---- bprop (A8) :162
     GCHK(gemm(ga(dq, 1, A, act[3], 512, 1, g + off[4], A, 512, B)));                                   // gW5 = dq^T @ a4
@@ -463,10 +483,18 @@ class GenericNetT : public GenericNet {
   void set_nstep(int n, double g) override { nstep = n; gamma_n = g; }
   int nstep = 1; double gamma_n = 0.0;
   hipError_t set_double_dqn(bool on) override {
+    if (on && munchausen) return hipErrorInvalidValue;
     if (on && !q_sel) GCHK(dalloc(&q_sel, (int64_t)B * A));
     double_dqn = on;
     return hipSuccess;
   }
+  hipError_t set_munchausen(bool on, double alpha, double tau, double clip) override {
+    if (on && double_dqn) return hipErrorInvalidValue;
+    if (on && !q_mu) GCHK(dalloc(&q_mu, (int64_t)B * A));
+    munchausen = on; mu_alpha = alpha; mu_tau = tau; mu_clip = clip;
+    return hipSuccess;
+  }
+  bool munchausen_on() const override { return munchausen; }
   hipError_t update_target() override {
     if (theta_t != theta) return hipMemcpyAsync(theta_t, theta, (size_t)NP * sizeof(T), hipMemcpyDeviceToDevice, st);
     return hipSuccess;

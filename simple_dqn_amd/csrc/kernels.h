@@ -23,8 +23,11 @@ struct HeadArgs {
   float* cost_terms;            // [B]  0.5 * delta^2 (pre-clip)
   double discount, min_reward, max_reward;
   float clip_error;
-  int train;                    // 0: predict only (z = 0); 1: train step; 2: train step with Double DQN targets (--double_dqn)
-  int reserved_[6];             // (a retired option's fields: every later field keeps its offset, see StepArgs::reserved_)
+  int train;                    // 0: predict only (z = 0); 1: train step; 2: train step with Double DQN targets (--double_dqn);
+                                // 3: train step with Munchausen targets (--munchausen; sdqn_munchausen.hip)
+  // --munchausen, read when train == 3: bonus scale alpha, softmax temperature tau, lower clip l0 of tau ln pi.  They lie
+  // in the 24 bytes a retired option's fields left: every later field keeps its offset (see StepArgs::reserved_)
+  double mu_alpha, mu_tau, mu_clip;
   // --prioritized_replay (sdqn_per.hip): per_w != nullptr selects the PER head — dq = w clip(delta), cost term 0.5 w delta^2, and
   // per_p[n] = (|delta| + per_eps)^per_alpha, the new priority the next per_step launch writes back
   const float* per_w; float* per_p; double per_alpha, per_eps;
@@ -84,7 +87,8 @@ struct UpdateArgs {
 };
 
 // The kernel-argument layouts are part of the tuned kernels (StepArgs::reserved_, problems.h): frozen where a retired field became reserved bytes
-static_assert(sizeof(HeadArgs) == 160 && offsetof(HeadArgs, train) == 84 && offsetof(HeadArgs, per_w) == 112 && offsetof(HeadArgs, per_eps) == 136 &&
+static_assert(sizeof(HeadArgs) == 160 && offsetof(HeadArgs, train) == 84 && offsetof(HeadArgs, mu_alpha) == 88 && offsetof(HeadArgs, mu_clip) == 104 &&
+              offsetof(HeadArgs, per_w) == 112 && offsetof(HeadArgs, per_eps) == 136 &&
               offsetof(HeadArgs, nstep) == 144 && offsetof(HeadArgs, gamma_n) == 152, "HeadArgs layout");
 static_assert(sizeof(PrepArgs) == 344 && offsetof(PrepArgs, idx_in_valid) == 52 && offsetof(PrepArgs, idx_in) == 56 && offsetof(PrepArgs, ns) == 312, "PrepArgs layout");
 static_assert(sizeof(UpdateArgs) == 616 && offsetof(UpdateArgs, next) == 128 && offsetof(UpdateArgs, next) + offsetof(PrepArgs, idx_in) == 184 &&
@@ -153,6 +157,7 @@ hipError_t launch_bt(const Route& r, int id, const StepArgs& a, const LaunchTune
 hipError_t launch_ss(const Route& r, int id, const StepArgs& a, const LaunchTune& t, hipStream_t s);       // sdqn_kernels_ss.hip: sample-stationary convolution chains
 hipError_t launch_kernel(int id, const StepArgs& a, const LaunchTune& t, hipStream_t s);     // the GEMM-shaped stages (single or multi-problem launches)
 hipError_t launch_head(const StepArgs& a, const HeadArgs& h, hipStream_t s, bool q_system_scope = false);   // q_system_scope: h.q is mapped host memory (acting path)
+hipError_t launch_head_munchausen(const StepArgs& a, const HeadArgs& h, hipStream_t s);     // sdqn_munchausen.hip: what launch_head runs for h.train == 3
 hipError_t launch_update(const UpdateArgs& u, hipStream_t s);
 hipError_t launch_gather(const GatherArgs& g, hipStream_t s, const int64_t* host_idx = nullptr);   // host_idx (B <= 256): indexes inside the kernel arguments
 hipError_t launch_bn_forward(const BnArgs& b, hipStream_t s);      // [partial +] apply

@@ -494,6 +494,49 @@ extern "C" int sdqn_net_train_iterations(sdqn_net_t h, int64_t* n) { ARGCHK(h &&
 
 extern "C" int sdqn_net_set_epoch(sdqn_net_t h, int epoch) { ARGCHK(h && epoch >= 0, "bad epoch"); h->epoch = epoch; return SDQN_OK; }
 
+// room for the third net slot (the two-slot buffers are freed with the network)
+int ensure_slots3(sdqn_net_s* h) {
+  if (h->slots3) return SDQN_OK;
+  { int rc_ = join_comm(h); if (rc_) return rc_; } HIPCHK(hipStreamSynchronize(g_stream));
+  const size_t B = (size_t)h->B;
+  float** f32[5] = {&h->a1, &h->a2, &h->a3, &h->a4, &h->q};
+  const size_t n32[5] = {B * PIX1 * K1, B * PIX2 * K2, B * PIX3 * K3, B * NFC, B * h->A};
+  for (int i = 0; i < 5; ++i) { int r_ = dalloc(h, (void**)f32[i], 3 * n32[i] * 4); if (r_) return r_; }
+  { int r_ = dalloc(h, (void**)&h->slab4, (size_t)h->S4_cap * 3 * B * NFC * 4); if (r_) return r_; }
+  if (h->h_a1) {
+    half_t** f16[3] = {&h->h_a1, &h->h_a2, &h->h_a3};
+    const size_t n16[3] = {B * PIX1 * K1, B * PIX2 * K2, B * PIX3 * K3};
+    for (int i = 0; i < 3; ++i) { int r_ = dalloc(h, (void**)f16[i], 3 * n16[i] * 2); if (r_) return r_; }
+  }
+  HIPCHK(hipStreamSynchronize(g_stream));
+  h->slots3 = true;
+  return SDQN_OK;
+}
+// ---- --munchausen: Munchausen DQN targets (sdqn.h) -------------------------------------------------------------------------
+extern "C" int sdqn_net_set_munchausen(sdqn_net_t h, int on, double alpha, double tau, double clip) {
+  ARGCHK(h, "NULL handle");
+  ARGCHK(on == 0 || on == 1, "munchausen must be 0 or 1");
+  ARGCHK(tau > 0.0 && tau < INFINITY, "munchausen_tau %g: must be > 0", tau);
+  ARGCHK(alpha >= 0.0 && alpha <= 1.0, "munchausen_alpha %g outside [0, 1]", alpha);
+  ARGCHK(clip <= 0.0 && clip > -INFINITY, "munchausen_clip %g: must be <= 0", clip);
+  if (on) {
+    ARGCHK(h->cfg.batch_norm == 0.0, "munchausen cannot be combined with batch_norm: inference-mode statistics for its third forward are not defined");
+    ARGCHK(h->gen || !h->double_dqn, "munchausen cannot be combined with double_dqn: the Munchausen target has no argmax for the online net to choose");
+  }
+  if (h->gen) {
+    const hipError_t ge = h->gen->set_munchausen(on != 0, alpha, tau, clip);
+    ARGCHK(ge != hipErrorInvalidValue, "munchausen cannot be combined with double_dqn: the Munchausen target has no argmax for the online net to choose");
+    GENCHK(ge);
+  } else if (on) { int r_ = ensure_slots3(h); if (r_) return r_; }
+  h->munchausen = on != 0; h->mu_alpha = alpha; h->mu_tau = tau; h->mu_clip = clip;
+  return SDQN_OK;
+}
+extern "C" int sdqn_net_get_munchausen(sdqn_net_t h, int* on, double* alpha, double* tau, double* clip) {
+  ARGCHK(h, "NULL handle");
+  if (on) *on = h->munchausen ? 1 : 0; if (alpha) *alpha = h->mu_alpha; if (tau) *tau = h->mu_tau; if (clip) *clip = h->mu_clip;
+  return SDQN_OK;
+}
+
 extern "C" int sdqn_net_set_option(sdqn_net_t h, const char* name, int value) {
   ARGCHK(h && name, "NULL argument");
   if (!strcmp(name, "n_step")) {                          // n-step returns: sdqn.h
@@ -506,6 +549,7 @@ extern "C" int sdqn_net_set_option(sdqn_net_t h, const char* name, int value) {
     if (!strcmp(name, "dp_overlap") && value < 0) return SDQN_OK;      // (auto: nothing to overlap without a communicator)
     if (!strcmp(name, "double_dqn")) {
       ARGCHK(value == 0 || value == 1, "double_dqn must be 0 or 1");
+      ARGCHK(!(value && h->gen->munchausen_on()), "double_dqn cannot be combined with munchausen: the Munchausen target has no argmax for the online net to choose");
       GENCHK(h->gen->set_double_dqn(value != 0));
       return SDQN_OK;
     }
@@ -519,21 +563,8 @@ extern "C" int sdqn_net_set_option(sdqn_net_t h, const char* name, int value) {
   if (retired) { if (value) RETIRED_OPTION_REFUSED(name); return SDQN_OK; }
   if (!strcmp(name, "double_dqn")) {                      // Double DQN targets (van Hasselt et al. 2016): sdqn.h
     ARGCHK(value == 0 || value == 1, "double_dqn must be 0 or 1");
-    if (value && !h->slots3) {                             // room for the third net slot (the two-slot buffers are freed with the network)
-      { int rc_ = join_comm(h); if (rc_) return rc_; } HIPCHK(hipStreamSynchronize(g_stream));
-      const size_t B = (size_t)h->B;
-      float** f32[5] = {&h->a1, &h->a2, &h->a3, &h->a4, &h->q};
-      const size_t n32[5] = {B * PIX1 * K1, B * PIX2 * K2, B * PIX3 * K3, B * NFC, B * h->A};
-      for (int i = 0; i < 5; ++i) { int r_ = dalloc(h, (void**)f32[i], 3 * n32[i] * 4); if (r_) return r_; }
-      { int r_ = dalloc(h, (void**)&h->slab4, (size_t)h->S4_cap * 3 * B * NFC * 4); if (r_) return r_; }
-      if (h->h_a1) {
-        half_t** f16[3] = {&h->h_a1, &h->h_a2, &h->h_a3};
-        const size_t n16[3] = {B * PIX1 * K1, B * PIX2 * K2, B * PIX3 * K3};
-        for (int i = 0; i < 3; ++i) { int r_ = dalloc(h, (void**)f16[i], 3 * n16[i] * 2); if (r_) return r_; }
-      }
-      HIPCHK(hipStreamSynchronize(g_stream));
-      h->slots3 = true;
-    }
+    ARGCHK(!(value && h->munchausen), "double_dqn cannot be combined with munchausen: the Munchausen target has no argmax for the online net to choose");
+    if (value) { int r_ = ensure_slots3(h); if (r_) return r_; }
     h->double_dqn = value != 0;
   }
   else if (!strcmp(name, "keep_gradients")) h->keep_grads = value != 0;

@@ -164,23 +164,30 @@ extern "C" int sdqn_net_step_structure(sdqn_net_t h, int* structure, int* update
 // --double_dqn: Q(theta, poststates), the argmax of the Double DQN target.  Without batch_norm it is the third net slot of the step's
 // own forward launches (nz = 3: online weights, poststates; problems.h wslot / sslot), and the head takes a* from it.  With batch_norm
 // the online slot's training-mode BatchNorm pass updates the running statistics that an inference-mode third slot of the same launch
-// would read, so there it is a forward of its own in front of the step (the predict forward, nz = 1, running statistics as they stand
-// before the step), its state source shifted to the poststates (one frame further in the ring, replay_memory.py:71-72, or the second
-// half of the [2][B][STATE] staging) and its Q-values left in q slot 2.  Without a target net (theta- aliases theta) Double DQN is
-// standard DQN: nothing changes.
+// would read, so there it is a forward of its own in front of the step (run_extra_forward: online weights, poststates, running
+// statistics as they stand before the step).  Without a target net (theta- aliases theta) Double DQN is standard DQN: nothing changes.
 bool ddqn_active(const sdqn_net_s* h) { return h->double_dqn && h->theta_t != h->theta; }
-int run_online_post_bn(sdqn_net_s* h, const StepArgs& a) {
+// A forward of its own in front of the step: the predict forward (nz = 1) of weight slot `wz` (0 online, 1 target: the net's theta and
+// its wh / wht / w1p copies move to slot-0 position) on state slot `sz` (0 prestates; 1 poststates: post_off frames further in the ring,
+// replay_memory.py:71-72, or the second half of the [2][B][STATE] staging), its Q-values left in q slot 2.  It uses slot 0 of the
+// activation buffers, which the step's own forward overwrites behind it.
+//   --double_dqn with --batch_norm: (0, 1)        --munchausen: (1, 0), qbar of the prestates
+int run_extra_forward(sdqn_net_s* h, const StepArgs& a, int wz, int sz) {
   StepArgs p = a; p.nz = 1;
-  p.src = a.from_ring ? a.src + (size_t)soff(a.post_off, 1) * FRAME : a.src + (size_t)a.B * STATE;
+  if (wz) { p.theta[0] = a.theta[1]; p.wh[0] = a.wh[1]; p.wht[0] = a.wht[1]; p.w1p[0] = a.w1p[1]; }
+  if (sz) p.src = a.from_ring ? a.src + (size_t)soff(a.post_off, 1) * FRAME : a.src + (size_t)a.B * STATE;
   HeadArgs hp = head_args(h, 0); hp.q = h->q + (size_t)2 * a.B * h->A;
   return run_forward(h, p, hp);
 }
 int run_train(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd0, const PrepArgs* next) {
   HeadArgs hd = hd0;
   StepArgs af = a;                         // the forward's arguments (the backward keeps a: its launches know two slots only)
-  if (ddqn_active(h)) {
+  if (h->munchausen) {                     // (refused together with double_dqn / batch_norm: sdqn_net_set_munchausen)
+    hd.train = 3; hd.mu_alpha = h->mu_alpha; hd.mu_tau = h->mu_tau; hd.mu_clip = h->mu_clip;
+    int rc0 = run_extra_forward(h, a, 1, 0); if (rc0) return rc0;
+  } else if (ddqn_active(h)) {
     hd.train = 2;
-    if (h->bn) { int rc0 = run_online_post_bn(h, a); if (rc0) return rc0; }
+    if (h->bn) { int rc0 = run_extra_forward(h, a, 0, 1); if (rc0) return rc0; }
     else af.nz = 3;
   }
   int rc = run_forward(h, af, hd);

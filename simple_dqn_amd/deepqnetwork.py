@@ -101,6 +101,13 @@ class DeepQNetwork:
         self.target_tau = float(getattr(args, "target_tau", 0.0) or 0.0)
         if self.target_tau:
             self.set_target_tau(self.target_tau)
+        # Munchausen DQN targets: soft value of the poststate plus a scaled, clipped log-policy bonus, both from the target net
+        self.munchausen = False
+        self.munchausen_alpha = float(getattr(args, "munchausen_alpha", 0.9))
+        self.munchausen_tau = float(getattr(args, "munchausen_tau", 0.03))
+        self.munchausen_clip = float(getattr(args, "munchausen_clip", -1.0))
+        if bool(getattr(args, "munchausen", False)):
+            self.set_munchausen(True)
         self._mt_buf = (C.c_uint32 * _lib.MT_WORDS)()
         self._act_out = C.c_int(); self._act_greedy = self._lib.sdqn_net_act_greedy
         self._env_r, self._env_t = C.c_int(), C.c_int(); self._act_step_env = self._lib.sdqn_net_act_step_env
@@ -167,6 +174,15 @@ class DeepQNetwork:
     def soft_update_target_network(self, tau):
         """One soft target update now: theta- <- theta- + tau (theta - theta-), tau in (0, 1] (1: update_target_network)."""
         _lib.check(self._lib.sdqn_net_soft_update(self._h, float(tau)))
+
+    def set_munchausen(self, on, alpha=None, tau=None, clip=None):
+        """--munchausen: switch Munchausen DQN targets on or off between steps; alpha / tau / clip left None keep their values
+        (--munchausen_alpha in [0, 1], --munchausen_tau > 0, --munchausen_clip <= 0).  Refused with double_dqn and batch_norm."""
+        alpha = self.munchausen_alpha if alpha is None else float(alpha)
+        tau = self.munchausen_tau if tau is None else float(tau)
+        clip = self.munchausen_clip if clip is None else float(clip)
+        _lib.check(self._lib.sdqn_net_set_munchausen(self._h, 1 if on else 0, alpha, tau, clip))
+        self.munchausen, self.munchausen_alpha, self.munchausen_tau, self.munchausen_clip = bool(on), alpha, tau, clip
 
     def set_target_tau(self, tau):
         """--target_tau: tau in (0, 1] makes every train step of this net end with one soft target update inside the library; 0: off."""

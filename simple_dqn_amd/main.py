@@ -39,6 +39,10 @@ _OPTIONS = {
         ("--batch_norm", _flag, False),
         ("--double_dqn", _flag, False, dict(help="Double DQN targets: the online net picks the poststate's action, the target net values it.")),
         ("--target_tau", float, 0.0, dict(help="Soft target updates: after every train step the target net moves by this fraction toward the online net (0: hard copy every --target_steps steps).")),
+        ("--munchausen", _flag, False, dict(help="Munchausen DQN targets: the target net's soft value of the poststate plus a scaled, clipped log-policy bonus for the action taken (alpha 0: Soft-DQN).")),
+        ("--munchausen_alpha", float, 0.9, dict(help="Munchausen DQN: scale of the log-policy bonus, in [0, 1].")),
+        ("--munchausen_tau", float, 0.03, dict(help="Munchausen DQN: temperature of the target net's softmax policy, > 0.")),
+        ("--munchausen_clip", float, -1.0, dict(help="Munchausen DQN: lower clip of tau * ln pi(a|s), <= 0.")),
     ],
     "Backend": [
         ("--backend", str, "hip", dict(choices=["hip", "gpu", "cpu"])), ("--device_id", int, 0),
@@ -110,9 +114,29 @@ def check_target_tau(args):
     return tau
 
 
+def check_munchausen(args):
+    """--munchausen: the ranges of its three parameters and what it cannot be combined with, refused before anything touches the device"""
+    on = bool(getattr(args, "munchausen", False))
+    tau = float(getattr(args, "munchausen_tau", 0.03))
+    alpha = float(getattr(args, "munchausen_alpha", 0.9))
+    clip = float(getattr(args, "munchausen_clip", -1.0))
+    if not (tau > 0.0 and tau < float("inf")):                       # (a NaN fails the comparison)
+        raise ValueError("--munchausen_tau %g: must be > 0" % tau)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError("--munchausen_alpha %g: must be in [0, 1]" % alpha)
+    if not (clip <= 0.0 and clip > -float("inf")):
+        raise ValueError("--munchausen_clip %g: must be <= 0" % clip)
+    if on and getattr(args, "double_dqn", False):
+        raise ValueError("--munchausen cannot be combined with --double_dqn: the Munchausen target has no argmax for the online net to choose")
+    if on and getattr(args, "batch_norm", False):
+        raise ValueError("--munchausen cannot be combined with --batch_norm: inference-mode statistics for its third forward are not defined")
+    return on
+
+
 def run(args):
     train_envs = check_train_envs(args)
     check_target_tau(args)
+    check_munchausen(args)
     from . import Agent, DeepQNetwork, ReplayMemory, SyntheticEnvironment, _lib, load
     from .environment import LIBRARY_GAMES
     from .statistics import Statistics

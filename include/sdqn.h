@@ -425,6 +425,17 @@ int sdqn_env_set_state(sdqn_env_t e, const sdqn_env_state* st);      /* SDQN_ERR
 int sdqn_env_get_state_breakout(sdqn_env_t e, sdqn_env_state_breakout* st);
 int sdqn_env_set_state_breakout(sdqn_env_t e, const sdqn_env_state_breakout* st);   /* SDQN_ERR_ARG for fields out of range; both: SDQN_ERR_ARG on a catch handle */
 int sdqn_env_name(sdqn_env_t e, const char** name);                  /* "catch" / "breakout": a static string */
+/* Dynamics of the game (csrc/env_dynamics.h), honoured by every call that steps it (sdqn_env_step, sdqn_net_act_step_env,
+ * and the copies of sdqn_env_eval / sdqn_env_collect, which play under the dynamics of the handle they are given).  frame_skip k in 1..8
+ * (default 1): one agent step is up to k game ticks of the same chosen action, the rewards add up, a tick that sets terminal ends it, only
+ * the last state is rendered.  repeat_action_probability p in [0, 1) (default 0; ALE's sticky actions): before every tick one draw u of
+ * the sticky generator (splitmix64; catch_stream_seed(seed, 0, 2) for a handle created with seed, (seed, e, 2) for copy e), and with
+ * (u >> 11) < ceil(p 2^53) the tick executes the action the last tick executed (0 after create and after every restart) instead of the
+ * chosen one; p = 0 draws nothing.  Replay memory, traces and statistics record the chosen action.  Out of range: SDQN_ERR_ARG. */
+int sdqn_env_set_dynamics(sdqn_env_t e, int frame_skip, double repeat_action_probability);
+/* every output optional (NULL); prev_action / sticky_rng complete sdqn_env_get_state*: together they reproduce a game exactly */
+int sdqn_env_get_dynamics(sdqn_env_t e, int* frame_skip, double* repeat_action_probability, int* prev_action, uint64_t* sticky_rng);
+int sdqn_env_set_dynamics_state(sdqn_env_t e, int prev_action, uint64_t sticky_rng);   /* SDQN_ERR_ARG: prev_action not an action */
 /* test hook: the frame of the current state as the render KERNEL produces it (sync) */
 int sdqn_env_render_device(sdqn_env_t e, uint8_t* screen);
 /* sdqn_net_act_step for an environment of the library: steps the game with `action`, then adds the new frame to the state buffer and,

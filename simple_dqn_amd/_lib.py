@@ -144,6 +144,9 @@ SIGNATURES = {
     "sdqn_env_get_state_breakout": (C.c_int, [_vp, C.POINTER(EnvStateBreakout)]),
     "sdqn_env_set_state_breakout": (C.c_int, [_vp, C.POINTER(EnvStateBreakout)]),
     "sdqn_env_name": (C.c_int, [_vp, C.POINTER(C.c_char_p)]),
+    "sdqn_env_set_dynamics": (C.c_int, [_vp, C.c_int, C.c_double]),
+    "sdqn_env_get_dynamics": (C.c_int, [_vp, C.POINTER(C.c_int), _f64p, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
+    "sdqn_env_set_dynamics_state": (C.c_int, [_vp, C.c_int, C.c_uint64]),
     "sdqn_env_render_device": (C.c_int, [_vp, _u8p]),
     "sdqn_net_act_step_env": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "sdqn_env_eval": (C.c_int, [_vp, _vp, C.c_int, C.c_int64, C.c_double, C.c_uint64, _i64p, _i64p, _i64p, _i64p, _i64p,

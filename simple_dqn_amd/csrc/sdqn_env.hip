@@ -3,9 +3,11 @@
 // (sdqn_env_eval) and vectorised collection (sdqn_env_collect).  Everything below is written once against a game trait G (CatchGame,
 // BreakoutGame: state, view, init / restart / step, renderer, action count, tallies) and instantiated per game: three kernels each and
 // one row of the dispatch at the entry points.  The kernels of this feature live here only: the train step's translation units are untouched.
+// Every path that steps a game does so through dynamics_step (env_dynamics.h): frame skip and sticky actions.
 #include "api_internal.h"
 #include "env_catch.h"
 #include "env_breakout.h"
+#include "env_dynamics.h"
 
 enum { GAME_CATCH = 0, GAME_BREAKOUT = 1 };
 struct sdqn_env_s {
@@ -13,6 +15,11 @@ struct sdqn_env_s {
   CatchState cs;                           // the state of the handle's game: the other one is unused
   BreakoutState bs;
   int H = 0, W = 0, bpe = 10;
+  int frame_skip = 1;                      // the dynamics: ticks per agent step, repeat_action_probability p and
+  double p = 0.0;                          // its integer form ceil(p 2^53)
+  uint64_t thresh_p = 0;
+  int32_t prev = 0;                        // the action the last tick executed (0 after create / restart)
+  uint64_t sticky_rng = 0;                 // the sticky generator: catch_stream_seed(seed, 0, 2) at create
   std::vector<uint8_t> frame;              // the host-rendered frame of the state (valid while frame_ok)
   bool frame_ok = false;
   template <class G> typename G::State& st();
@@ -81,10 +88,13 @@ struct EvalRec {               // one copy of the game, resident on the device f
   typename G::State s;
   uint64_t act_rng;
   int64_t steps, reward, caught, missed, episodes;
+  uint64_t sticky_rng;         // the dynamics of the copy (env_dynamics.h): sticky generator, the action its last tick executed
+  int32_t prev, pad_;
 };
 struct EvalArgs {
   const void* q; int q_f64;    // [>= N][A] Q-values of the forward that precedes this launch (float, or double on a float64 network)
   int A, N, hist, H, W, bpe, init;
+  int frame_skip; uint64_t thresh_p;         // the dynamics every copy plays under (env_dynamics.h)
   const uint8_t* src; uint8_t* dst;          // [N][hist][H][W]: the window the forward read / the next step's
   void* envs;                  // EvalRec<G>[N]
   uint64_t seed, thresh;
@@ -93,7 +103,8 @@ struct EvalArgs {
 };
 // --train_envs: where a lockstep's transitions go — slot e lane_len + pos of the ring mirror and of its metadata
 struct CollectArgs { uint8_t* ring; MetaRec* meta; int64_t lane_len, pos; };
-// One workgroup per copy.  Thread 0: first-maximum argmax (NaN rule of sdqn_net_act_greedy), epsilon-greedy, game step, tallies, restart;
+// One workgroup per copy.  Thread 0: first-maximum argmax (NaN rule of sdqn_net_act_greedy), epsilon-greedy, agent step (up to frame_skip
+// game ticks under sticky actions: dynamics_step; trace and MetaRec carry the chosen action and the summed reward), tallies, restart;
 // the view of the new frame reaches the others through LDS; all threads: shift the window into the other buffer and render the new frame
 // (restart: zeroed history in front of the first frame, as StateBuffer.reset), 16 bytes per load / store.  COLLECT: the transition is
 // also a replay-memory add — the rendered frame goes to the copy's ring slot as well, (action, reward, terminal) to its MetaRec (at a
@@ -110,6 +121,7 @@ __device__ __forceinline__ void env_lockstep(const EvalArgs& a, const CollectArg
     if (a.init) {
       G::init(r.s, catch_stream_seed(a.seed, (uint64_t)e, 0));
       r.act_rng = catch_stream_seed(a.seed, (uint64_t)e, 1);
+      r.sticky_rng = catch_stream_seed(a.seed, (uint64_t)e, DYNAMICS_STICKY_STREAM); r.prev = 0; r.pad_ = 0;
       r.steps = r.reward = r.caught = r.missed = r.episodes = 0;
       restart = 1;
     } else {
@@ -120,17 +132,17 @@ __device__ __forceinline__ void env_lockstep(const EvalArgs& a, const CollectArg
         if (a.tr_q) a.tr_q[((size_t)a.t * a.N + e) * a.A + k] = qk;
       }
       const int action = catch_epsilon_greedy(r.act_rng, a.thresh, best, a.A);
-      int lost;
-      const int reward = G::step(r.s, action, a.bpe, lost);
+      int caught, lost;
+      const int reward = dynamics_step<G>(r.s, r.prev, r.sticky_rng, action, a.bpe, a.frame_skip, a.thresh_p, caught, lost);
       const int terminal = r.s.terminal;
-      r.steps += 1; r.reward += reward; r.caught += reward > 0; r.missed += lost;
+      r.steps += 1; r.reward += reward; r.caught += caught; r.missed += lost;
       if (a.tr_act) { const size_t o = (size_t)a.t * a.N + e; a.tr_act[o] = (uint8_t)action; a.tr_rew[o] = (int8_t)reward; a.tr_term[o] = (uint8_t)terminal; }
       if (COLLECT) {
         MetaRec m; m.reward = reward; m.action = (uint8_t)action; m.terminal = (uint8_t)terminal;
         for (int k = 0; k < 6; ++k) m.pad[k] = 0;
         c.meta[(int64_t)e * c.lane_len + c.pos] = m;
       }
-      if (terminal) { r.episodes += 1; G::restart(r.s); restart = 1; }
+      if (terminal) { r.episodes += 1; dynamics_restart<G>(r.s, r.prev); restart = 1; }
     }
     envs[e] = r;
     G::pack(G::view(r.s), sh); sh[G::VIEW_WORDS] = restart;
@@ -191,13 +203,19 @@ template <class G> static const uint8_t* env_frame(sdqn_env_s* e) {
   return e->frame.data();
 }
 template <class G> static int env_init(sdqn_env_s* e, uint64_t seed) { G::init(e->st<G>(), seed); return SDQN_OK; }
-template <class G> static int env_restart(sdqn_env_s* e) { G::restart(e->st<G>()); e->frame_ok = false; return SDQN_OK; }
+template <class G> static int env_restart(sdqn_env_s* e) { dynamics_restart<G>(e->st<G>(), e->prev); e->frame_ok = false; return SDQN_OK; }
+// one agent step of the handle's game under its dynamics: the ONE place the host steps a game (sdqn_env_step, act_step_env)
+template <class G> static int env_advance(sdqn_env_s* e, int action) {
+  int caught, lost;
+  const int r = dynamics_step<G>(e->st<G>(), e->prev, e->sticky_rng, action, e->bpe, e->frame_skip, e->thresh_p, caught, lost);
+  e->frame_ok = false;
+  return r;
+}
 template <class G> static int env_num_actions(int* n) { *n = G::ACTIONS; return SDQN_OK; }
 template <class G> static int env_name(const char** name) { *name = G::NAME; return SDQN_OK; }
 template <class G> static int env_step(sdqn_env_s* e, int action, int* reward, int* terminal) {
   ARGCHK(action >= 0 && action < G::ACTIONS, "action %d out of range [0, %d)", action, G::ACTIONS);
-  int lost;
-  const int r = G::step(e->st<G>(), action, e->bpe, lost); e->frame_ok = false;
+  const int r = env_advance<G>(e, action);
   if (reward) *reward = r; if (terminal) *terminal = e->st<G>().terminal;
   return SDQN_OK;
 }
@@ -211,6 +229,7 @@ extern "C" int sdqn_env_create(sdqn_env_t* out, const char* name, int H, int W, 
   sdqn_env_s* e = new sdqn_env_s();
   e->game = breakout ? GAME_BREAKOUT : GAME_CATCH;
   e->H = H; e->W = W; e->bpe = balls_per_episode; e->frame.assign((size_t)H * W, 0);
+  e->sticky_rng = catch_stream_seed(seed, 0, DYNAMICS_STICKY_STREAM);
   GAME_CALL(e, env_init, e, seed);
   *out = e; return SDQN_OK;
 }
@@ -248,6 +267,30 @@ extern "C" int sdqn_env_set_state_breakout(sdqn_env_t e, const sdqn_env_state_br
          s.row, s.col, s.dx, s.dy, s.paddle, s.balls, s.terminal, s.pad, (unsigned long long)s.bricks);
   e->bs = s; e->frame_ok = false; return SDQN_OK;
 }
+// the dynamics of the handle.  sdqn_env_eval / sdqn_env_collect play their copies under the handle's frame_skip and p;
+// (get_state, get_dynamics) -> (set_state, set_dynamics_state) reproduces a game exactly.
+extern "C" int sdqn_env_set_dynamics(sdqn_env_t e, int frame_skip, double repeat_action_probability) {
+  ARGCHK(e, "NULL handle");
+  ARGCHK(frame_skip >= 1 && frame_skip <= DYNAMICS_MAX_SKIP, "frame_skip %d out of range [1, %d]", frame_skip, DYNAMICS_MAX_SKIP);
+  ARGCHK(repeat_action_probability >= 0.0 && repeat_action_probability < 1.0, "repeat_action_probability %g out of range [0, 1)", repeat_action_probability);   // (a NaN fails both)
+  e->frame_skip = frame_skip; e->p = repeat_action_probability; e->thresh_p = (uint64_t)ceil(ldexp(repeat_action_probability, 53));
+  return SDQN_OK;
+}
+extern "C" int sdqn_env_get_dynamics(sdqn_env_t e, int* frame_skip, double* repeat_action_probability, int* prev_action, uint64_t* sticky_rng) {
+  ARGCHK(e, "NULL handle");
+  if (frame_skip) *frame_skip = e->frame_skip; if (repeat_action_probability) *repeat_action_probability = e->p;
+  if (prev_action) *prev_action = e->prev; if (sticky_rng) *sticky_rng = e->sticky_rng;
+  return SDQN_OK;
+}
+template <class G> static int env_set_dynamics_state(sdqn_env_s* e, int prev_action, uint64_t sticky_rng) {
+  ARGCHK(prev_action >= 0 && prev_action < G::ACTIONS, "prev_action %d out of range [0, %d)", prev_action, G::ACTIONS);
+  e->prev = prev_action; e->sticky_rng = sticky_rng;
+  return SDQN_OK;
+}
+extern "C" int sdqn_env_set_dynamics_state(sdqn_env_t e, int prev_action, uint64_t sticky_rng) {
+  ARGCHK(e, "NULL handle");
+  return GAME_CALL(e, env_set_dynamics_state, e, prev_action, sticky_rng);
+}
 // test hook: the frame of the current state as the KERNEL renders it (device scratch, read back; sync)
 template <class G> static int env_render_device(sdqn_env_s* e, uint8_t* screen) {
   const size_t frame = e->frame.size();
@@ -278,8 +321,7 @@ static int act_step_env(sdqn_net_t h, sdqn_statebuf_t sb, sdqn_replay_t r, sdqn_
   ARGCHK(sb->frame == FRAME, "the state buffer's screens (%lld bytes) and the environment's (%lld) differ", (long long)sb->frame, (long long)FRAME);
   ARGCHK(!r || r->frame == FRAME, "the replay memory's screens (%lld bytes) and the environment's (%lld) differ", (long long)(r ? r->frame : 0), (long long)FRAME);
   typename G::State& st = e->st<G>();
-  int lost;
-  const int rew = G::step(st, action, e->bpe, lost), term = st.terminal;
+  const int rew = env_advance<G>(e, action), term = st.terminal;
   const typename G::View v = G::view(st);
   uint8_t *hf, *dv;
   int rc = statebuf_advance(sb, &hf, &dv); if (rc) return rc;
@@ -352,6 +394,7 @@ struct EnvTrace {
 static EvalArgs env_args(sdqn_net_t h, sdqn_env_t e, int N, const EnvGeom& g, void* recs) {
   EvalArgs a; memset(&a, 0, sizeof a);
   a.A = h->A; a.N = N; a.hist = g.hist; a.H = g.H; a.W = g.W; a.bpe = e->bpe; a.envs = recs;
+  a.frame_skip = e->frame_skip; a.thresh_p = e->thresh_p;
   return a;
 }
 // the host copy of the records -> the callers' tallies
@@ -364,8 +407,8 @@ static void env_tallies(const std::vector<EvalRec<G> >& hrec, const EnvOut& o) {
   }
 }
 
-// sdqn_env_eval: the copies live in buffers of this call, seeded from `seed`; one epsilon.  The environment handle gives the geometry and
-// balls_per_episode; its own state is not touched.
+// sdqn_env_eval: the copies live in buffers of this call, seeded from `seed`; one epsilon.  The environment handle gives the geometry,
+// balls_per_episode and the dynamics (frame_skip, repeat_action_probability); its own state is not touched.
 template <class G>
 static int env_eval(sdqn_net_t h, sdqn_env_t e, int N, int64_t steps, double epsilon, uint64_t seed, const EnvOut& o) {
   typedef EvalRec<G> Rec;

@@ -78,12 +78,15 @@ class SyntheticEnvironment(Environment):
 class LibraryEnvironment(Environment):
     """A game that lives in the library (include/sdqn.h sdqn_env_*): everything here runs on the host; `_h` lets
     DeepQNetwork.act_step_env / evaluate / collect step and render the game inside the library.  The generator is the environment's own
-    (never Python's `random`).  A subclass names its game, its state struct and state calls, and its balls-per-episode option."""
+    (never Python's `random`).  A subclass names its game, its state struct and state calls, and its balls-per-episode option.
+    `args.frame_skip` (1..8, default 1) and `args.repeat_action_probability` (in [0, 1), default 0) are the game's dynamics
+    (DESIGN.md §23): act(), DeepQNetwork.act_step_env and the copies of evaluate / collect all play under them."""
     game = None                                                      # name given to sdqn_env_create
     balls_option, balls_default = None, 10                           # the command line's balls-per-episode flag of this game
     _state_struct, _get_state, _set_state = None, None, None
 
-    def __init__(self, args=None, seed=0, balls_per_episode=None, screen_height=84, screen_width=84):
+    def __init__(self, args=None, seed=0, balls_per_episode=None, screen_height=84, screen_width=84, frame_skip=None,
+                 repeat_action_probability=None):
         from . import _lib
         self._libmod, self._lib = _lib, _lib.load()
         h = getattr(args, "screen_height", screen_height)
@@ -95,6 +98,13 @@ class LibraryEnvironment(Environment):
         hd = C.c_void_p()
         _lib.check(self._lib.sdqn_env_create(C.byref(hd), self.game.encode(), h, w, int(seed) & 0xFFFFFFFFFFFFFFFF, self.balls_per_episode))
         self._h = hd
+        if frame_skip is None:
+            frame_skip = getattr(args, "frame_skip", 1)
+        if repeat_action_probability is None:
+            repeat_action_probability = getattr(args, "repeat_action_probability", 0.0)
+        self.frame_skip, self.repeat_action_probability = int(frame_skip), float(repeat_action_probability)
+        if (self.frame_skip, self.repeat_action_probability) != (1, 0.0):
+            _lib.check(self._lib.sdqn_env_set_dynamics(hd, self.frame_skip, self.repeat_action_probability))
         self._screen = np.zeros(self.dims, dtype=np.uint8)
         self._screen_ok = False
         self._terminal = False
@@ -152,6 +162,16 @@ class LibraryEnvironment(Environment):
         st = getattr(self._libmod, self._state_struct)(**state)
         self._libmod.check(getattr(self._lib, self._set_state)(self._h, C.byref(st)))
         self._terminal, self._screen_ok = bool(st.terminal), False
+
+    def get_dynamics(self):
+        """frame_skip, repeat_action_probability and what get_state() leaves out of an exact copy of the game: the action the last
+        tick executed and the sticky generator"""
+        k, p, prev, rng = C.c_int(), C.c_double(), C.c_int(), C.c_uint64()
+        self._libmod.check(self._lib.sdqn_env_get_dynamics(self._h, C.byref(k), C.byref(p), C.byref(prev), C.byref(rng)))
+        return dict(frame_skip=k.value, repeat_action_probability=p.value, prev_action=prev.value, sticky_rng=rng.value)
+
+    def set_dynamics_state(self, prev_action, sticky_rng):
+        self._libmod.check(self._lib.sdqn_env_set_dynamics_state(self._h, int(prev_action), int(sticky_rng) & 0xFFFFFFFFFFFFFFFF))
 
     def render_device(self):
         """test hook: the current frame as the render kernel produces it"""

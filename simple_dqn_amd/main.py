@@ -22,6 +22,8 @@ _OPTIONS = {
         ("--breakout_balls", int, 3, dict(help="Breakout environment: lost balls per episode.")),
         ("--eval_envs", int, 0, dict(help="Catch / breakout environment: play the test phase on this many copies of the game at once, on the device (0: Agent.test, one environment).")),
         ("--train_envs", int, 0, dict(help="Catch / breakout environment: collect experience from this many copies of the game at once, on the device; the replay memory becomes that many lanes (0: Agent.train, one environment).")),
+        ("--frame_skip", int, 1, dict(help="Catch / breakout environment: game ticks per agent step (1..8); the rewards of the ticks add up.")),
+        ("--repeat_action_probability", float, 0.0, dict(help="Catch / breakout environment: sticky actions; before every game tick the action executed last is repeated with this probability, in [0, 1).")),
         ("--screen_width", int, 84), ("--screen_height", int, 84),
     ],
     "Replay memory": [
@@ -104,6 +106,27 @@ def check_train_envs(args):
     return n
 
 
+def check_dynamics(args):
+    """--frame_skip / --repeat_action_probability: their ranges and the environments that honour them, refused before anything touches
+    the device"""
+    k = getattr(args, "frame_skip", 1)
+    k = 1 if k is None else int(k)
+    p = getattr(args, "repeat_action_probability", 0.0)
+    p = 0.0 if p is None else float(p)
+    if not 1 <= k <= 8:
+        raise ValueError("--frame_skip %d: must be in [1, 8]" % k)
+    if not 0.0 <= p < 1.0:                                           # (a NaN fails both comparisons)
+        raise ValueError("--repeat_action_probability %g: must be in [0, 1)" % p)
+    from .environment import LIBRARY_GAMES
+    if args.environment not in LIBRARY_GAMES:
+        if k != 1:
+            raise ValueError("--frame_skip %d needs --environment catch or breakout (got %s): only the library's own games honour it" % (k, args.environment))
+        if p != 0.0:
+            raise ValueError("--repeat_action_probability %g needs --environment catch or breakout (got %s): only the library's own games honour it"
+                             % (p, args.environment))
+    return k, p
+
+
 def check_target_tau(args):
     """--target_tau: its range and what it needs, refused before anything touches the device"""
     tau = float(getattr(args, "target_tau", 0.0) or 0.0)
@@ -137,6 +160,7 @@ def run(args):
     train_envs = check_train_envs(args)
     check_target_tau(args)
     check_munchausen(args)
+    check_dynamics(args)
     from . import Agent, DeepQNetwork, ReplayMemory, SyntheticEnvironment, _lib, load
     from .environment import LIBRARY_GAMES
     from .statistics import Statistics

@@ -9,6 +9,7 @@
 next to the same figure of the uniformly random policy (evaluate(..., epsilon=1.0), 24 000 steps, same seeds): the baseline the curves
 are read against.  Every evaluation is DeepQNetwork.evaluate on 32 copies, 750 steps each, epsilon 0.05.
     python tools/breakout_curves.py [--steps 200000] [--every 10000] [--seeds 1 2 3] [--configs envs32 single ...] [--out curves.json]
+        [--frame_skip K] [--repeat_action_probability P]     the game's dynamics, passed through to every run and evaluation
 One JSON line per finished run is appended to --out as it completes (a run cut short leaves what was finished), the table is printed at the end.
 Hyper-parameters besides the options above: --replay_size 51200, --exploration_decay_steps 50000 (1 -> 0.1), --target_steps 1000,
 --random_steps 3200, --breakout_balls 3, everything else at the command line's defaults."""
@@ -49,15 +50,15 @@ def bricks_per_ball(net, env, seed, epsilon=0.05):
     return float(out["caught"].sum()) / max(int(out["missed"].sum()), 1)
 
 
-def run(name, seed, steps, every):
+def run(name, seed, steps, every, **dynamics):
     import simple_dqn_amd as sd
-    a = _args(seed, **CONFIGS[name])
+    a = _args(seed, **dict(CONFIGS[name], **dynamics))
     random.seed(seed)
     env = sd.BreakoutEnvironment(a, seed=seed)
     mem, net = sd.ReplayMemory(a.replay_size, a), sd.DeepQNetwork(env.numActions(), a)
     agent = sd.Agent(env, mem, net, a)
     t0 = time.time()
-    rec = dict(config=name, seed=seed, random=bricks_per_ball(net, env, seed, 1.0), untrained=bricks_per_ball(net, env, 1000 + seed), curve=[])
+    rec = dict(config=name, seed=seed, frame_skip=a.frame_skip, repeat_action_probability=a.repeat_action_probability, random=bricks_per_ball(net, env, seed, 1.0), untrained=bricks_per_ball(net, env, 1000 + seed), curve=[])
     if a.train_envs:
         agent.play_random_vectorised(a.random_steps)
     else:
@@ -101,11 +102,15 @@ def main():
     p.add_argument("--seeds", type=int, nargs="+", default=[1, 2, 3])
     p.add_argument("--configs", nargs="+", default=list(CONFIGS), choices=list(CONFIGS))
     p.add_argument("--out", default=None)
+    p.add_argument("--frame_skip", type=int, default=1)
+    p.add_argument("--repeat_action_probability", type=float, default=0.0)
     o = p.parse_args()
+    from simple_dqn_amd.main import check_dynamics
+    check_dynamics(argparse.Namespace(environment="breakout", frame_skip=o.frame_skip, repeat_action_probability=o.repeat_action_probability))
     recs = []
     for name in o.configs:
         for seed in o.seeds:
-            rec = run(name, seed, o.steps, o.every)
+            rec = run(name, seed, o.steps, o.every, frame_skip=o.frame_skip, repeat_action_probability=o.repeat_action_probability)
             recs.append(rec)
             print("%s seed %d: random %.3f untrained %.3f final %.3f (%.0f s)" % (name, seed, rec["random"], rec["untrained"],
                                                                                 rec["curve"][-1][1], rec["seconds"]), flush=True)

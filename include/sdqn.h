@@ -285,6 +285,22 @@ int sdqn_net_update_target(sdqn_net_t h);
 int sdqn_net_soft_update(sdqn_net_t h, double tau);
 int sdqn_net_set_target_tau(sdqn_net_t h, double tau);
 int sdqn_net_get_target_tau(sdqn_net_t h, double* tau);
+/* Global gradient-norm clipping, --clip_grad_norm (no reference counterpart).  max_norm G > 0 switches it on, 0 (default)
+ * off; negative, NaN or infinite is SDQN_ERR_ARG and keeps the previous value.  With g the flat gradient SUM buffer the optimizer reads
+ * (all layers; with batch_norm also the [beta | gamma] block) and bsz the divisor the optimizer uses (batch_size; batch_size x ranks
+ * under data parallel; the argument of sdqn_net_apply_update):
+ *     norm = sqrt(sum_i g_i^2) / bsz  (fp64 accumulation of the stored values: the L2 norm of the mean gradient),
+ *     scale = min(1, G / (norm + 1e-6))  in fp64, rounded once to the network's precision (float; double for float64);
+ * scale < 1: every g_i becomes g_i * scale (one rounded multiply), otherwise — or when norm is not finite — g keeps its bits.  The
+ * optimizer, the BatchNorm parameter update and the --target_tau blend then run as always, on the clipped g.  Two launches between the
+ * gradient's reduction and its application (update form 4: +3 launches per step; a clipped step never runs the overlapped
+ * data-parallel form, and fc4's RMSProp no longer rides its weight-gradient launch).  Every step that applies an update clips,
+ * sdqn_net_apply_update included; a "grad_only" step does not.
+ * sdqn_net_last_grad_norm: norm and the scale as applied (the rounded value) of the last clipped step (sync); SDQN_ERR_STATE before
+ * any such step. */
+int sdqn_net_set_clip_grad_norm(sdqn_net_t h, double max_norm);
+int sdqn_net_get_clip_grad_norm(sdqn_net_t h, double* max_norm);
+int sdqn_net_last_grad_norm(sdqn_net_t h, double* norm, double* scale);
 int sdqn_net_sync(sdqn_net_t h);
 /* The two halves of a data-parallel step without a communicator (the arithmetic every rank performs
  * around the all-reduce).  With option "grad_only" = 1 a train step ends after the local gradient SUMS are in the flat
@@ -319,7 +335,8 @@ int sdqn_net_set_epoch(sdqn_net_t h, int epoch);
  * batch_norm, data-parallel form, option fused_launches) only (tests/test_step_structure.py enumerates the combinations):
  *   structure: 0 fused (fc4_dgrad | bwd3 | bwd2 | bwd1)   1 float16 block-tile (fc4_dgrad | conv3_dgrad | conv2_dgrad | wgrads | bwd1)
  *              2 fused with fc4's all-reduce + update overlapped on the second communicator   3 one launch per problem   4 generic path
- *   update:    0 one update launch   1 serial data parallel (local sums, all-reduce, apply)   2 overlapped data parallel   3 grad_only */
+ *   update:    0 one update launch   1 serial data parallel (local sums, all-reduce, apply)   2 overlapped data parallel   3 grad_only
+ *              4 single GPU with clip_grad_norm (local sums, norm, scale, apply); the generic path reports 4 too when it clips, else 0 */
 int sdqn_net_step_structure(sdqn_net_t h, int* structure, int* update);
 /* Munchausen DQN targets, --munchausen (Vieillard, Pietquin and Geist 2020; no reference counterpart).  With qbar = Q(theta-, .),
  * pi = softmax(qbar / tau) and lse(q) = max q + tau log sum_a exp((q[a] - max q) / tau) (double, sum in action order), a train step's target is

@@ -119,6 +119,9 @@ SIGNATURES = {
     "sdqn_net_soft_update": (C.c_int, [_vp, C.c_double]),
     "sdqn_net_set_target_tau": (C.c_int, [_vp, C.c_double]),
     "sdqn_net_get_target_tau": (C.c_int, [_vp, _f64p]),
+    "sdqn_net_set_clip_grad_norm": (C.c_int, [_vp, C.c_double]),
+    "sdqn_net_get_clip_grad_norm": (C.c_int, [_vp, _f64p]),
+    "sdqn_net_last_grad_norm": (C.c_int, [_vp, _f64p, _f64p]),
     "sdqn_net_set_munchausen": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.c_double]),
     "sdqn_net_get_munchausen": (C.c_int, [_vp, C.POINTER(C.c_int), _f64p, _f64p, _f64p]),
     "sdqn_net_sync": (C.c_int, [_vp]),

@@ -18,6 +18,7 @@
 #include "generic_net.h"
 #include "sampler.h"
 #include "sdqn_per.h"
+#include "sdqn_clip.h"
 
 using namespace sdqn;
 
@@ -135,6 +136,10 @@ struct sdqn_net_s {
   bool munchausen = false; double mu_alpha = 0.9, mu_tau = 0.03, mu_clip = -1.0;
   int n_step = 1;                          // --n_step (option "n_step"): poststate frame offset of the ring paths, n-step head
   double target_tau = 0.0;                 // --target_tau (sdqn_net_set_target_tau): > 0: every train step is followed by one soft target update
+  // --clip_grad_norm (sdqn_net_set_clip_grad_norm): > 0: the flat gradient is scaled to this global L2 norm (of the MEAN
+  // gradient) between its reduction and its application.  clip_buf: [CLIP_GRID] partials | {norm, scale} of the last clipped step,
+  // allocated when the option is first switched on; clip_ran: such a step has been enqueued
+  double clip_grad_norm = 0.0; double* clip_buf = nullptr; bool clip_ran = false;
   uint8_t *st_states = nullptr, *st_act = nullptr, *st_term = nullptr; int64_t* st_rew = nullptr; int64_t* d_idx = nullptr;
   float* h_f = nullptr;                    // pinned scratch for small read-backs
   // acting path (round 4): the head kernel of a predict_state forward writes its Q-values straight into mapped host memory (q_host; q_host_dev
@@ -224,7 +229,7 @@ struct sdqn_statebuf_s {
 
 // which launches a train step is made of / how its optimizer pass runs (sdqn_api_step.hip: step_structure, update_form)
 enum StepStructure { STEP_FUSED = 0, STEP_H16_BT = 1, STEP_DP_OVERLAP = 2, STEP_UNFUSED = 3 };
-enum UpdateForm { UPD_SINGLE = 0, UPD_DP_SERIAL = 1, UPD_DP_OVERLAP = 2, UPD_GRAD_ONLY = 3 };
+enum UpdateForm { UPD_SINGLE = 0, UPD_DP_SERIAL = 1, UPD_DP_OVERLAP = 2, UPD_GRAD_ONLY = 3, UPD_CLIP = 4 };
 // ---- functions that cross a file boundary -------------------------------------------------------------------------------
 int ensure_stream();
 int sample_checked(uint32_t* mt, const uint8_t* terminals, int64_t count, int64_t current, int hist,
@@ -253,7 +258,9 @@ int gen_get(sdqn_net_s* h, int which, int layer, void* w, int64_t n, bool f64);
 int ensure_slots3(sdqn_net_s* h);                                  // room for a third net slot in a1..a4, slab4, q (first use of --double_dqn / --munchausen)
 int target_blend(sdqn_net_s* h, double tau);                       // one soft target update now (tau in (0, 1]; the caller has joined g_comm)
 int step_blend(sdqn_net_s* h);                                     // what every applied train step ends with: the blend of --target_tau, or nothing
-int gen_step_done(sdqn_net_s* h);                                  // generic path: a train step was enqueued (counter + step_blend)
+int gen_step_done(sdqn_net_s* h);                                  // generic path: a train step was enqueued ([clip + deferred update,] counter, step_blend)
+inline bool clip_on(const sdqn_net_s* h) { return h->clip_grad_norm > 0.0; }
+int clip_gradient(sdqn_net_s* h, double bsz);                      // --clip_grad_norm: the two launches on g between update modes 1 and 2 (nothing when off)
 int prof_collect(sdqn_net_s* h);
 int prof_event(sdqn_net_s* h, hipEvent_t* e);
 hipError_t dp_allreduce(sdqn_net_s* h, void* buf, size_t count, int dtype, void* comm, hipStream_t s);
@@ -298,6 +305,10 @@ int per_gen_finish(sdqn_net_s* h, sdqn_replay_s* r);
 int per_check_all();
 
 inline bool prof_single_kernel(int kid) { return kid != K_ALLREDUCE && kid != K_BN; }
+// prof_filter: a kernel id, -1 every launch, PROF_GENERIC_ROWS the rows a generic-path network has (its own launches are not bracketed): the
+// soft target update and the update slot's launches of a clipped step
+constexpr int PROF_GENERIC_ROWS = -2;
+inline bool prof_wants(int filter, int kid) { return filter == -1 || filter == kid || (filter == PROF_GENERIC_ROWS && (kid == K_TARGET || kid == K_UPDATE)); }
 #ifdef SDQN_TIMING
 namespace sdqn { hipError_t set_wave_timing_buffer(unsigned long long* const* p, const unsigned* nb, hipStream_t s); }
 // timing build: sdqn_debug_time_step_waves arms per-wave stamps around ONE launch id of a real train step (h->wt_kid), stream-ordered
@@ -308,7 +319,7 @@ namespace sdqn { hipError_t set_wave_timing_buffer(unsigned long long* const* p,
 #define SDQN_WAVE_TIMING_DISARM(STRM, KID) do {} while (0)
 #endif
 #define LAUNCH_ON(STRM, KID, expr) do { \
-  const bool pf_ = h->prof_on && (h->prof_filter < 0 || h->prof_filter == (KID)) && (h->prof_seen[KID]++ % h->prof_every) == 0; ProfPair pp_; \
+  const bool pf_ = h->prof_on && prof_wants(h->prof_filter, (KID)) && (h->prof_seen[KID]++ % h->prof_every) == 0; ProfPair pp_; \
   const bool px_ = pf_ && h->prof_mode == 1 && prof_single_kernel(KID); \
   if (pf_) { pp_.id = (KID); int r1_ = prof_event(h, &pp_.a); if (r1_) return r1_; r1_ = prof_event(h, &pp_.b); if (r1_) return r1_; \
              if (px_) { sdqn::LaunchEvents& le = sdqn::launch_events(); le.start = pp_.a; le.stop = pp_.b; le.used = false; } \

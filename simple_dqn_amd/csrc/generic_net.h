@@ -54,6 +54,14 @@ struct GenericNet {
   // --n_step: n > 1 makes the train steps read rew as the n-step returns (float64 bits) and term as the done flags, and
   // bootstrap with gamma_n; n = 1: the standard step
   virtual void set_nstep(int n, double gamma_n) = 0;
+  // --clip_grad_norm (sdqn_clip.h): set_clip(true) makes train_dev / train_host / train_dev_host_meta stop behind the
+  // gradient — the caller then enqueues clip_sqnorm, clip_scale (divisor bsz, max norm G) and apply_deferred (the step's optimizer
+  // launch), one launch each; clip_record reads {norm, scale} of the last clip_scale (synchronises)
+  virtual hipError_t set_clip(bool on) = 0;
+  virtual hipError_t clip_sqnorm() = 0;
+  virtual hipError_t clip_scale(double bsz, double max_norm) = 0;
+  virtual hipError_t apply_deferred() = 0;
+  virtual hipError_t clip_record(double* norm_scale) = 0;
   virtual size_t state_bytes() const = 0;                                // hist * H * W
 };
 

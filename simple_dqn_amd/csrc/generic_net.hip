@@ -15,6 +15,7 @@
 #include "generic_net.h"
 #include "problems.h"          // MetaRec
 #include "launch.h"            // SDQN_LAUNCH: the soft target update has a profile row
+#include "sdqn_clip.h"         // --clip_grad_norm: the two clip launches, float / double
 #include <vector>
 #include <algorithm>
 #include <math.h>
@@ -412,8 +413,29 @@ class GenericNetT : public GenericNet {
     u.b1 = (T)cfg.beta_1; u.omb1 = (T)(1.0 - cfg.beta_1); u.b2 = (T)cfg.beta_2; u.omb2 = (T)(1.0 - cfg.beta_2);
     const double tt = (double)epoch + 1.0;
     u.lr_t = (T)(cfg.learning_rate * sqrt(1.0 - pow(cfg.beta_2, tt)) / (1.0 - pow(cfg.beta_1, tt)));
+    if (clip) { deferred = u; has_deferred = true; return hipGetLastError(); }      // --clip_grad_norm: clip_sqnorm, clip_scale, apply_deferred follow
     hipLaunchKernelGGL(update_kernel<T>, dim3(grid_for(NP)), dim3(256), 0, st, u);
     return hipGetLastError();
+  }
+  // --clip_grad_norm: the step's optimizer launch waits in `deferred` while the caller clips g
+  bool clip = false, has_deferred = false; OptArgs<T> deferred; double* clip_buf = nullptr;      // [CLIP_GRID] partials | norm | scale
+  hipError_t set_clip(bool on) override {
+    if (on && !clip_buf) GCHK(dalloc(&clip_buf, CLIP_WORDS));
+    clip = on;
+    return hipSuccess;
+  }
+  hipError_t clip_sqnorm() override { return launch_grad_sqnorm<T>(g, NP, clip_buf, st); }
+  hipError_t clip_scale(double bsz, double max_norm) override { return launch_grad_scale<T>(g, NP, clip_buf, bsz, max_norm, clip_buf + CLIP_GRID, st); }
+  hipError_t apply_deferred() override {
+    if (!has_deferred) return hipErrorInvalidValue;
+    has_deferred = false;
+    SDQN_LAUNCH(update_kernel<T>, dim3(grid_for(NP)), dim3(256), 0, st, deferred);
+    return hipGetLastError();
+  }
+  hipError_t clip_record(double* out) override {
+    if (!clip_buf) return hipErrorInvalidValue;
+    GCHK(hipMemcpyAsync(out, clip_buf + CLIP_GRID, 16, hipMemcpyDeviceToHost, st));
+    return hipStreamSynchronize(st);
   }
   hipError_t upload_meta(const uint8_t* actions, const int64_t* rew, const uint8_t* term) {
     memcpy(small_host.data(), rew, (size_t)B * 8); memcpy(small_host.data() + (size_t)B * 8, actions, B); memcpy(small_host.data() + (size_t)B * 9, term, B);

@@ -247,7 +247,8 @@ extern "C" int sdqn_net_set_weights(sdqn_net_t h, int which, int layer, const fl
   h->spec_pending = false;                 // (parameters may change under a speculative acting forward)
   if (layer >= 5) {
     float* base; int64_t cnt;
-    ARGCHK(which != 3 && bn_layer_span(h, which, layer, &base, &cnt), "no such BatchNorm buffer (which %d, layer %d)", which, layer);
+    // (which = 3: the [beta | gamma] gradient sums, as for the weight layers — what sdqn_net_apply_update then applies)
+    ARGCHK(bn_layer_span(h, which, layer, &base, &cnt), "no such BatchNorm buffer (which %d, layer %d)", which, layer);
     ARGCHK(n == cnt, "layer %d holds %lld values, got %lld", layer, (long long)cnt, (long long)n);
     { int rc_ = join_comm(h); if (rc_) return rc_; } HIPCHK(hipStreamSynchronize(g_stream));
     HIPCHK(hipMemcpy(base, w, (size_t)n * 4, hipMemcpyHostToDevice));
@@ -319,9 +320,10 @@ int prof_event(sdqn_net_s* h, hipEvent_t* e) {
 
 extern "C" int sdqn_net_profile(sdqn_net_t h, int enable, int kernel) {
   ARGCHK(h && kernel < K_COUNT, "bad arguments");
-  // the generic path's launches are not bracketed; its one row is the soft target update's (K_TARGET)
-  if (h->gen) { h->prof_on = enable != 0 && (kernel < 0 || kernel == K_TARGET); h->prof_filter = K_TARGET; return SDQN_OK; }
-  h->prof_on = enable != 0; h->prof_filter = kernel; return SDQN_OK;
+  // the generic path's own launches are not bracketed; its rows are the soft target update's (K_TARGET) and, with --clip_grad_norm, the
+  // update slot's three launches that follow train_dev (gen_step_done)
+  if (h->gen) { h->prof_on = enable != 0 && (kernel < 0 || kernel == K_TARGET || kernel == K_UPDATE); h->prof_filter = kernel < 0 ? PROF_GENERIC_ROWS : kernel; return SDQN_OK; }
+  h->prof_on = enable != 0; h->prof_filter = kernel < 0 ? -1 : kernel; return SDQN_OK;
 }
 extern "C" int sdqn_net_profile_count(int* n) { ARGCHK(n, "NULL"); *n = K_COUNT; return SDQN_OK; }
 extern "C" int sdqn_net_profile_read(sdqn_net_t h, int kernel, const char** name, double* total_ms, int64_t* launches) {
@@ -389,7 +391,40 @@ int step_blend(sdqn_net_s* h) {
   if (!h->gen) { int rc = join_comm(h); if (rc) return rc; }
   return target_blend(h, h->target_tau);
 }
-int gen_step_done(sdqn_net_s* h) { h->train_iterations += 1; return step_blend(h); }
+// generic path: train_dev has enqueued the step.  With --clip_grad_norm it stopped behind the gradient (GenericNet::set_clip): the two
+// clip launches and the deferred optimizer launch follow here, in the profile's update slot
+int gen_step_done(sdqn_net_s* h) {
+  if (clip_on(h)) {
+    LAUNCH(K_UPDATE, h->gen->clip_sqnorm());
+    LAUNCH(K_UPDATE, h->gen->clip_scale((double)h->B, h->clip_grad_norm));
+    LAUNCH(K_UPDATE, h->gen->apply_deferred());
+    h->clip_ran = true;
+  }
+  h->train_iterations += 1;
+  return step_blend(h);
+}
+// ---- --clip_grad_norm: global gradient-norm clipping (sdqn.h) ------------------------------------------------------------
+extern "C" int sdqn_net_set_clip_grad_norm(sdqn_net_t h, double max_norm) {
+  ARGCHK(h, "NULL handle");
+  ARGCHK(max_norm >= 0.0 && max_norm < INFINITY, "clip_grad_norm %g: must be a finite value >= 0 (0 = off)", max_norm);     // (false for a NaN)
+  if (h->gen) GENCHK(h->gen->set_clip(max_norm > 0.0));
+  else if (max_norm > 0.0 && !h->clip_buf) { int r_ = dalloc(h, (void**)&h->clip_buf, (size_t)CLIP_WORDS * 8); if (r_) return r_; }
+  h->clip_grad_norm = max_norm;
+  return SDQN_OK;
+}
+extern "C" int sdqn_net_get_clip_grad_norm(sdqn_net_t h, double* max_norm) { ARGCHK(h && max_norm, "NULL argument"); *max_norm = h->clip_grad_norm; return SDQN_OK; }
+extern "C" int sdqn_net_last_grad_norm(sdqn_net_t h, double* norm, double* scale) {
+  ARGCHK(h, "NULL handle");
+  if (!h->clip_ran) { set_error("no clipped step has run on this network (clip_grad_norm %g)", h->clip_grad_norm); return SDQN_ERR_STATE; }
+  double rec[2];
+  if (h->gen) GENCHK(h->gen->clip_record(rec));
+  else {
+    { int rc_ = join_comm(h); if (rc_) return rc_; } HIPCHK(hipStreamSynchronize(g_stream));
+    HIPCHK(hipMemcpy(rec, h->clip_buf + CLIP_GRID, 16, hipMemcpyDeviceToHost));
+  }
+  if (norm) *norm = rec[0]; if (scale) *scale = rec[1];
+  return SDQN_OK;
+}
 extern "C" int sdqn_net_soft_update(sdqn_net_t h, double tau) {
   ARGCHK(h, "NULL handle");
   ARGCHK(tau_in_range(tau), "soft target update: tau %g outside (0, 1]", tau);
@@ -418,6 +453,7 @@ extern "C" int sdqn_net_apply_update(sdqn_net_t h, double bsz) {
     u.ovf_flag = h->ovf_flag; u.ovf_count = h->ovf_count; u.ovf_dynamic = h->dp_half_scale_log2 < 0 ? 1 : 0;
     h->half_payload_pending = false;
   }
+  { int rcc = clip_gradient(h, bsz); if (rcc) return rcc; }       // --clip_grad_norm: with the caller's divisor
   LAUNCH(K_UPDATE, launch_update(u, g_stream));
   if (h->bn) LAUNCH(K_BN, launch_bn_update(u, g_stream));
   return step_blend(h);

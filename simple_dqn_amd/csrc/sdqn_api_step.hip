@@ -24,7 +24,7 @@ StepArgs step_args(sdqn_net_s* h) {
   }
   a.f4w_first = 0; a.f4w_count = (NIN4 / 32) * (NFC / 32);
   a.w1p[0] = h->w1p[0]; a.w1p[1] = h->w1p[1];
-  a.fuse_rms = (!h->comm && !h->keep_grads && !h->grad_only && h->cfg.optimizer == 0) ? 1 : 0;
+  a.fuse_rms = (!h->comm && !h->keep_grads && !h->grad_only && !clip_on(h) && h->cfg.optimizer == 0) ? 1 : 0;   // (clipping needs ALL of g before any of it is applied)
   a.theta_w = h->theta; a.state = h->state; a.bsz = (float)h->B;
   a.rho = (float)h->cfg.decay_rate; a.one_minus_rho = (float)(1.0 - h->cfg.decay_rate);
   a.lr = (float)h->cfg.learning_rate; a.eps = (float)h->cfg.epsilon;
@@ -143,21 +143,34 @@ UpdateArgs make_update_args(sdqn_net_s* h, const StepArgs& a) {
 //   dp_overlap fused, with ALL of fc4_wgrad in bwd3 and its all-reduce + update on the second communicator's stream
 //   unfused    one launch per problem (option fused_launches = 0; batch_norm inserts its own passes between them)
 StepStructure step_structure(const sdqn_net_s* h) {
-  if (h->comm && h->comm2 && h->dp_overlap && h->fused_launches) return STEP_DP_OVERLAP;
+  // --clip_grad_norm: the overlapped form applies fc4 before the whole gradient's norm exists, so a clipped step runs the serial form
+  if (h->comm && h->comm2 && h->dp_overlap && h->fused_launches && !clip_on(h)) return STEP_DP_OVERLAP;
   if (h->cfg.datatype == 1 && h->B >= 128 && h->bt_on && !h->bn && h->fused_launches && h->bt[K_CONV3_DGRAD] >= 0 && h->bt[K_CONV2_DGRAD] >= 0 &&
       h->nw_override[K_CONV3_DGRAD] == 0 && h->nw_override[K_CONV2_DGRAD] == 0) return STEP_H16_BT;
   return h->fused_launches ? STEP_FUSED : STEP_UNFUSED;
 }
 // how the optimizer pass runs: 0 one update launch (fc4's RMSProp rode in its weight-gradient tiles) | 1 serial data parallel: local sums,
 // one all-reduce of the flat gradient, apply | 2 overlapped data parallel (fc4's part already on its way) | 3 grad_only (local sums, nothing applied)
+// | 4 single GPU with --clip_grad_norm: local sums, the two clip launches, apply (the serial data-parallel form clips inside form 1)
 UpdateForm update_form(const sdqn_net_s* h) {
   if (step_structure(h) == STEP_DP_OVERLAP) return UPD_DP_OVERLAP;
   if (h->comm) return UPD_DP_SERIAL;
-  return h->grad_only ? UPD_GRAD_ONLY : UPD_SINGLE;
+  if (h->grad_only) return UPD_GRAD_ONLY;
+  return clip_on(h) ? UPD_CLIP : UPD_SINGLE;
+}
+// --clip_grad_norm: g holds the complete gradient sums (all layers [+ the BatchNorm beta | gamma block]); bsz is the divisor the
+// optimizer pass behind this will use.  Two launches in the update slot; g is scaled in place, or left bit for bit when nothing is clipped.
+int clip_gradient(sdqn_net_s* h, double bsz) {
+  if (!clip_on(h)) return SDQN_OK;
+  const int64_t n = h->NPW + (h->bn ? BN_PARAMS : 0);
+  LAUNCH(K_UPDATE, launch_grad_sqnorm(h->g, n, h->clip_buf, g_stream));
+  LAUNCH(K_UPDATE, launch_grad_scale(h->g, n, h->clip_buf, bsz, h->clip_grad_norm, h->clip_buf + CLIP_GRID, g_stream));
+  h->clip_ran = true;
+  return SDQN_OK;
 }
 extern "C" int sdqn_net_step_structure(sdqn_net_t h, int* structure, int* update) {
   ARGCHK(h && structure && update, "NULL argument");
-  if (h->gen) { *structure = 4; *update = 0; return SDQN_OK; }
+  if (h->gen) { *structure = 4; *update = clip_on(h) ? (int)UPD_CLIP : 0; return SDQN_OK; }
   *structure = (int)step_structure(h); *update = (int)update_form(h);
   return SDQN_OK;
 }
@@ -305,14 +318,26 @@ int run_train(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd0, const PrepA
       u.ovf_flag = h->ovf_flag; u.ovf_count = h->ovf_count; u.ovf_dynamic = h->dp_half_scale_log2 < 0 ? 1 : 0;
     } else
     LAUNCH(K_ALLREDUCE, dp_allreduce(h, h->g, (size_t)h->NP, /*ncclFloat32*/ 7, h->comm, g_stream));
+    { int rcc = clip_gradient(h, (double)h->B * (double)h->nranks); if (rcc) return rcc; }      // --clip_grad_norm: the all-reduced gradient, every rank alike
     u.mode = 2; u.bsz = (float)h->B * (float)h->nranks;
     if (next) u.next = *next;
     LAUNCH(K_UPDATE, launch_update(u, g_stream));
     if (h->bn) LAUNCH(K_BN, launch_bn_update(u, g_stream));
     break;
   case UPD_GRAD_ONLY:
-    u.mode = 1; u.bsz = (float)h->B;                                            // local sums -> g, nothing applied
+    u.mode = 1; u.bsz = (float)h->B;                                            // local sums -> g, nothing applied (and nothing clipped)
     LAUNCH(K_UPDATE, launch_update(u, g_stream));
+    break;
+  case UPD_CLIP:
+    // --clip_grad_norm on one GPU: what the serial data-parallel form does with the clip where its all-reduce is — local sums -> g, norm,
+    // scale in place, apply (the launch that carries the next step's prep), then the BatchNorm parameters from the same clipped g
+    u.mode = 1; u.bsz = (float)h->B; u.next.B = 0;
+    LAUNCH(K_UPDATE, launch_update(u, g_stream));
+    { int rcc = clip_gradient(h, (double)h->B); if (rcc) return rcc; }
+    u.mode = 2;
+    if (next) u.next = *next;
+    LAUNCH(K_UPDATE, launch_update(u, g_stream));
+    if (h->bn) LAUNCH(K_BN, launch_bn_update(u, g_stream));
     break;
   default:
     u.mode = 0; u.bsz = (float)h->B;

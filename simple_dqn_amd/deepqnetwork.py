@@ -101,6 +101,10 @@ class DeepQNetwork:
         self.target_tau = float(getattr(args, "target_tau", 0.0) or 0.0)
         if self.target_tau:
             self.set_target_tau(self.target_tau)
+        # global gradient-norm clipping: > 0 scales the whole mean gradient to at most this L2 norm before the optimizer
+        self.clip_grad_norm = 0.0
+        if float(getattr(args, "clip_grad_norm", 0.0) or 0.0):
+            self.set_clip_grad_norm(float(args.clip_grad_norm))
         # Munchausen DQN targets: soft value of the poststate plus a scaled, clipped log-policy bonus, both from the target net
         self.munchausen = False
         self.munchausen_alpha = float(getattr(args, "munchausen_alpha", 0.9))
@@ -188,6 +192,19 @@ class DeepQNetwork:
         """--target_tau: tau in (0, 1] makes every train step of this net end with one soft target update inside the library; 0: off."""
         _lib.check(self._lib.sdqn_net_set_target_tau(self._h, float(tau)))
         self.target_tau = float(tau)
+
+    def set_clip_grad_norm(self, max_norm):
+        """--clip_grad_norm: G > 0 clips the gradient of every applied train step to global L2 norm G (of the mean gradient); 0: off.
+        A negative or non-finite value raises and keeps the previous one."""
+        _lib.check(self._lib.sdqn_net_set_clip_grad_norm(self._h, float(max_norm)))
+        self.clip_grad_norm = float(max_norm)
+
+    def last_grad_norm(self):
+        """(norm, scale) of the last clipped step: the pre-clip L2 norm of the mean gradient and the factor that was applied (1.0: nothing
+        was clipped).  Waits for the device; raises SdqnError before any clipped step."""
+        n, sc = C.c_double(), C.c_double()
+        _lib.check(self._lib.sdqn_net_last_grad_norm(self._h, C.byref(n), C.byref(sc)))
+        return n.value, sc.value
 
     def get_target_tau(self):
         t = C.c_double()
@@ -603,7 +620,7 @@ class DeepQNetwork:
         return getattr(self, "_dp_overlap_opt", -1)
 
     STEP_STRUCTURES = ("fused", "h16_block_tile", "dp_overlap", "unfused", "generic")
-    UPDATE_FORMS = ("single", "dp_serial", "dp_overlap", "grad_only")
+    UPDATE_FORMS = ("single", "dp_serial", "dp_overlap", "grad_only", "clip")
 
     def step_structure(self):
         """(launch structure of a train step, form of its optimizer pass) — DESIGN.md 12's table, as the library itself sees this handle."""

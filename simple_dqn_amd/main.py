@@ -41,6 +41,7 @@ _OPTIONS = {
         ("--batch_norm", _flag, False),
         ("--double_dqn", _flag, False, dict(help="Double DQN targets: the online net picks the poststate's action, the target net values it.")),
         ("--target_tau", float, 0.0, dict(help="Soft target updates: after every train step the target net moves by this fraction toward the online net (0: hard copy every --target_steps steps).")),
+        ("--clip_grad_norm", float, 0.0, dict(help="Global gradient-norm clipping: scale the whole (mean) gradient to at most this L2 norm before the optimizer (0: off; Dueling / Rainbow use 10).")),
         ("--munchausen", _flag, False, dict(help="Munchausen DQN targets: the target net's soft value of the poststate plus a scaled, clipped log-policy bonus for the action taken (alpha 0: Soft-DQN).")),
         ("--munchausen_alpha", float, 0.9, dict(help="Munchausen DQN: scale of the log-policy bonus, in [0, 1].")),
         ("--munchausen_tau", float, 0.03, dict(help="Munchausen DQN: temperature of the target net's softmax policy, > 0.")),
@@ -137,6 +138,15 @@ def check_target_tau(args):
     return tau
 
 
+def check_clip_grad_norm(args):
+    """--clip_grad_norm: its range, refused before anything touches the device (it combines with every other option)"""
+    g = getattr(args, "clip_grad_norm", 0.0)
+    g = 0.0 if g is None else float(g)
+    if not 0.0 <= g < float("inf"):                                  # (a NaN fails both comparisons)
+        raise ValueError("--clip_grad_norm %g: must be a finite value >= 0 (0: off)" % g)
+    return g
+
+
 def check_munchausen(args):
     """--munchausen: the ranges of its three parameters and what it cannot be combined with, refused before anything touches the device"""
     on = bool(getattr(args, "munchausen", False))
@@ -160,6 +170,7 @@ def run(args):
     train_envs = check_train_envs(args)
     check_target_tau(args)
     check_munchausen(args)
+    check_clip_grad_norm(args)
     check_dynamics(args)
     from . import Agent, DeepQNetwork, ReplayMemory, SyntheticEnvironment, _lib, load
     from .environment import LIBRARY_GAMES

@@ -428,9 +428,25 @@ typedef struct {
   uint64_t bricks;           /* bit 12 (r - 1) + c: a brick at row r in {1, 2, 3}, column c; bits 36..63 are 0 */
   uint64_t rng;              /* splitmix64 counter */
 } sdqn_env_state_breakout;
-/* name = "catch" or "breakout"; H, W >= 12 (else SDQN_ERR_ARG); the generator starts at `seed`, the first episode is started.  Every
- * sdqn_env_* call below serves both games; the tallies `caught` / `missed` of sdqn_env_eval / sdqn_env_collect count bricks broken /
- * balls lost on breakout. */
+/* The game "freeway" (csrc/env_freeway.h), on the same court: a chicken on column 6 starts on row 11 and moves with actions
+ * 0 stay / 1 up / 2 down; rows 1..10 carry one car each (pixel 128), odd rows driving right, even rows left, wrapping modulo 12, a car of
+ * period p moving one cell every p-th tick.  Reaching row 0 gives +1 (the only reward), puts the chicken back on row 11 and draws new
+ * traffic; a hit (the chicken walks into a car, or a car drives into it) puts it back on row 11 without a reward.  An episode is
+ * balls_per_episode game TICKS (the `balls_per_episode` argument of sdqn_env_create carries the episode length for this game). */
+typedef struct {
+  int32_t row;               /* the chicken: 0..11, never in a car's cell */
+  int32_t ticks;             /* game ticks played in this episode, >= 0 */
+  int32_t crossings;         /* made in this episode, >= 0 */
+  int32_t terminal;          /* 0 / 1 */
+  int32_t pad0, pad1;        /* 0 */
+  uint64_t cars;             /* nibble r - 1: the column (0..11) of the car of row r in 1..10; bits 40..63 are 0 (in all three words) */
+  uint64_t timers;           /* nibble r - 1: ticks until that car moves, 1..period */
+  uint64_t periods;          /* nibble r - 1: 1..5 */
+  uint64_t rng;              /* splitmix64 counter */
+} sdqn_env_state_freeway;
+/* name = "catch", "breakout" or "freeway"; H, W >= 12 (else SDQN_ERR_ARG); the generator starts at `seed`, the first episode is started.
+ * Every sdqn_env_* call below serves all games; the tallies `caught` / `missed` of sdqn_env_eval / sdqn_env_collect count bricks broken /
+ * balls lost on breakout and crossings / hits on freeway. */
 int sdqn_env_create(sdqn_env_t* h, const char* name, int screen_height, int screen_width, uint64_t seed, int balls_per_episode);
 int sdqn_env_destroy(sdqn_env_t e);
 int sdqn_env_restart(sdqn_env_t e);                                  /* new episode: balls 0, paddle 4, a new ball; does not reseed */
@@ -441,7 +457,9 @@ int sdqn_env_get_state(sdqn_env_t e, sdqn_env_state* st);
 int sdqn_env_set_state(sdqn_env_t e, const sdqn_env_state* st);      /* SDQN_ERR_ARG for fields out of range; both: SDQN_ERR_ARG on a breakout handle */
 int sdqn_env_get_state_breakout(sdqn_env_t e, sdqn_env_state_breakout* st);
 int sdqn_env_set_state_breakout(sdqn_env_t e, const sdqn_env_state_breakout* st);   /* SDQN_ERR_ARG for fields out of range; both: SDQN_ERR_ARG on a catch handle */
-int sdqn_env_name(sdqn_env_t e, const char** name);                  /* "catch" / "breakout": a static string */
+int sdqn_env_get_state_freeway(sdqn_env_t e, sdqn_env_state_freeway* st);
+int sdqn_env_set_state_freeway(sdqn_env_t e, const sdqn_env_state_freeway* st);     /* SDQN_ERR_ARG for fields out of range; both: SDQN_ERR_ARG on another game's handle */
+int sdqn_env_name(sdqn_env_t e, const char** name);                  /* "catch" / "breakout" / "freeway": a static string */
 /* Dynamics of the game (csrc/env_dynamics.h), honoured by every call that steps it (sdqn_env_step, sdqn_net_act_step_env,
  * and the copies of sdqn_env_eval / sdqn_env_collect, which play under the dynamics of the handle they are given).  frame_skip k in 1..8
  * (default 1): one agent step is up to k game ticks of the same chosen action, the rewards add up, a tick that sets terminal ends it, only

@@ -14,7 +14,7 @@ from .replay_memory import ReplayMemory  # noqa: F401
 from .deepqnetwork import DeepQNetwork  # noqa: F401
 from .state_buffer import DeviceStateBuffer, StateBuffer  # noqa: F401
 from .agent import Agent  # noqa: F401
-from .environment import BreakoutEnvironment, CatchEnvironment, SyntheticEnvironment  # noqa: F401
+from .environment import BreakoutEnvironment, CatchEnvironment, FreewayEnvironment, SyntheticEnvironment  # noqa: F401
 from .statistics import Statistics  # noqa: F401
 
-__all__ = ["ReplayMemory", "DeepQNetwork", "StateBuffer", "DeviceStateBuffer", "Agent", "SyntheticEnvironment", "CatchEnvironment", "BreakoutEnvironment", "Statistics", "load", "lib_path"]
+__all__ = ["ReplayMemory", "DeepQNetwork", "StateBuffer", "DeviceStateBuffer", "Agent", "SyntheticEnvironment", "CatchEnvironment", "BreakoutEnvironment", "FreewayEnvironment", "Statistics", "load", "lib_path"]

@@ -42,7 +42,13 @@ class EnvStateBreakout(C.Structure):
                 ("terminal", C.c_int32), ("pad", C.c_int32), ("bricks", C.c_uint64), ("rng", C.c_uint64)]
 
 
-_u8p, _i64p, _f32p, _u32p = C.POINTER(C.c_uint8), C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+class EnvStateFreeway(C.Structure):
+    """sdqn_env_state_freeway: the whole state of one game of freeway"""
+    _fields_ = [("row", C.c_int32), ("ticks", C.c_int32), ("crossings", C.c_int32), ("terminal", C.c_int32), ("pad0", C.c_int32),
+                ("pad1", C.c_int32), ("cars", C.c_uint64), ("timers", C.c_uint64), ("periods", C.c_uint64), ("rng", C.c_uint64)]
+
+
+_u8p, _i64p, _f32p, _u32p =C.POINTER(C.c_uint8), C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_uint32)
 _f64p = C.POINTER(C.c_double)
 _vp = C.c_void_p
 
@@ -146,7 +152,9 @@ SIGNATURES = {
     "sdqn_env_set_state": (C.c_int, [_vp, C.POINTER(EnvState)]),
     "sdqn_env_get_state_breakout": (C.c_int, [_vp, C.POINTER(EnvStateBreakout)]),
     "sdqn_env_set_state_breakout": (C.c_int, [_vp, C.POINTER(EnvStateBreakout)]),
-    "sdqn_env_name": (C.c_int, [_vp, C.POINTER(C.c_char_p)]),
+    "sdqn_env_get_state_freeway": (C.c_int, [_vp, C.POINTER(EnvStateFreeway)]),
+    "sdqn_env_set_state_freeway": (C.c_int, [_vp, C.POINTER(EnvStateFreeway)]),
+    "sdqn_env_name":(C.c_int, [_vp, C.POINTER(C.c_char_p)]),
     "sdqn_env_set_dynamics": (C.c_int, [_vp, C.c_int, C.c_double]),
     "sdqn_env_get_dynamics": (C.c_int, [_vp, C.POINTER(C.c_int), _f64p, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]),
     "sdqn_env_set_dynamics_state": (C.c_int, [_vp, C.c_int, C.c_uint64]),

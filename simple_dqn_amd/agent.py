@@ -67,7 +67,7 @@ class Agent:
         self.train_envs = int(getattr(args, "train_envs", 0) or 0)
         if self.train_envs:
             if not (hasattr(self.net, "collect") and hasattr(self.env, "_h") and hasattr(self.mem, "set_lanes")):
-                raise ValueError("--train_envs needs --environment catch or breakout and the device-backed replay memory")
+                raise ValueError("--train_envs needs --environment catch, breakout or freeway and the device-backed replay memory")
             if self.mem.lanes[0] != self.train_envs:
                 self.mem.set_lanes(self.train_envs)
             self._vec_seed = int(getattr(args, "random_seed", 0) or 0)      # None until the copies have been seeded with it

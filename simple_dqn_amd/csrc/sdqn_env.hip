@@ -1,20 +1,22 @@
-// sdqn_env.hip — the device-resident games "catch" (env_catch.h) and "breakout" (env_breakout.h; §20): host entry points of
-// the environment handle, the render kernel of the fused act step (sdqn_net_act_step_env), the vectorised on-device evaluation loop
-// (sdqn_env_eval) and vectorised collection (sdqn_env_collect).  Everything below is written once against a game trait G (CatchGame,
-// BreakoutGame: state, view, init / restart / step, renderer, action count, tallies) and instantiated per game: three kernels each and
-// one row of the dispatch at the entry points.  The kernels of this feature live here only: the train step's translation units are untouched.
+// sdqn_env.hip — the device-resident games "catch" (env_catch.h), "breakout" (env_breakout.h; §20) and "freeway"
+// (env_freeway.h; §25): host entry points of the environment handle, the render kernel of the fused act step (sdqn_net_act_step_env),
+// the vectorised on-device evaluation loop (sdqn_env_eval) and vectorised collection (sdqn_env_collect).  Everything below is written
+// once against a game trait G (CatchGame, BreakoutGame, FreewayGame: state, view, init / restart / step, renderer, action count,
+// tallies) and instantiated per game: three kernels each and one row of the dispatch at the entry points.  The kernels of this feature live here only: the train step's translation units are untouched.
 // Every path that steps a game does so through dynamics_step (env_dynamics.h): frame skip and sticky actions.
 #include "api_internal.h"
 #include "env_catch.h"
 #include "env_breakout.h"
+#include "env_freeway.h"
 #include "env_dynamics.h"
 
-enum { GAME_CATCH = 0, GAME_BREAKOUT = 1 };
+enum { GAME_CATCH = 0, GAME_BREAKOUT = 1, GAME_FREEWAY = 2 };
 struct sdqn_env_s {
   int game = GAME_CATCH;
-  CatchState cs;                           // the state of the handle's game: the other one is unused
+  CatchState cs;                           // the state of the handle's game: the others are unused
   BreakoutState bs;
-  int H = 0, W = 0, bpe = 10;
+  FreewayState fs;
+  int H = 0, W = 0, bpe = 10;              // bpe: balls per episode; freeway: game ticks per episode
   int frame_skip = 1;                      // the dynamics: ticks per agent step, repeat_action_probability p and
   double p = 0.0;                          // its integer form ceil(p 2^53)
   uint64_t thresh_p = 0;
@@ -26,10 +28,13 @@ struct sdqn_env_s {
 };
 template <> inline CatchState& sdqn_env_s::st<CatchGame>() { return cs; }
 template <> inline BreakoutState& sdqn_env_s::st<BreakoutGame>() { return bs; }
+template <> inline FreewayState& sdqn_env_s::st<FreewayGame>() { return fs; }
 static_assert(sizeof(sdqn_env_state) == sizeof(CatchState) && sizeof(CatchState) == 32, "sdqn_env_state is CatchState");
 static_assert(sizeof(sdqn_env_state_breakout) == sizeof(BreakoutState) && sizeof(BreakoutState) == 48, "sdqn_env_state_breakout is BreakoutState");
+static_assert(sizeof(sdqn_env_state_freeway) == sizeof(FreewayState) && sizeof(FreewayState) == 56, "sdqn_env_state_freeway is FreewayState");
 // one row per game: `return GAME_CALL(e, fn, args...)` calls fn<G>(args...) for the handle's game
-#define GAME_CALL(e, fn, ...) ((e)->game == GAME_BREAKOUT ? fn<BreakoutGame>(__VA_ARGS__) : fn<CatchGame>(__VA_ARGS__))
+#define GAME_CALL(e, fn, ...) \
+  ((e)->game == GAME_FREEWAY ? fn<FreewayGame>(__VA_ARGS__) : (e)->game == GAME_BREAKOUT ? fn<BreakoutGame>(__VA_ARGS__) : fn<CatchGame>(__VA_ARGS__))
 
 static const int ENV_THREADS = 512;        // one 21 KB state window = 1323 16-byte chunks: <= 3 per thread
 
@@ -81,6 +86,7 @@ __device__ __forceinline__ void render_frame(const typename G::View& v, uint8_t*
 }
 __global__ void __launch_bounds__(256) catch_render_kernel(CatchView v, uint8_t* dst0, uint8_t* dst1, int H, int W) { render_frame<CatchGame>(v, dst0, dst1, H, W); }
 __global__ void __launch_bounds__(256) breakout_render_kernel(BreakoutView v, uint8_t* dst0, uint8_t* dst1, int H, int W) { render_frame<BreakoutGame>(v, dst0, dst1, H, W); }
+__global__ void __launch_bounds__(256) freeway_render_kernel(FreewayView v, uint8_t* dst0, uint8_t* dst1, int H, int W) { render_frame<FreewayGame>(v, dst0, dst1, H, W); }
 
 // ---- vectorised evaluation ---------------------------------------------------------------------------------------------------
 template <class G>
@@ -173,6 +179,8 @@ __global__ void __launch_bounds__(ENV_THREADS) catch_eval_kernel(const EvalArgs 
 __global__ void __launch_bounds__(ENV_THREADS) catch_collect_kernel(const EvalArgs a, const CollectArgs c) { env_lockstep<CatchGame, true>(a, c); }
 __global__ void __launch_bounds__(ENV_THREADS) breakout_eval_kernel(const EvalArgs a) { env_lockstep<BreakoutGame, false>(a, CollectArgs()); }
 __global__ void __launch_bounds__(ENV_THREADS) breakout_collect_kernel(const EvalArgs a, const CollectArgs c) { env_lockstep<BreakoutGame, true>(a, c); }
+__global__ void __launch_bounds__(ENV_THREADS) freeway_eval_kernel(const EvalArgs a) { env_lockstep<FreewayGame, false>(a, CollectArgs()); }
+__global__ void __launch_bounds__(ENV_THREADS) freeway_collect_kernel(const EvalArgs a, const CollectArgs c) { env_lockstep<FreewayGame, true>(a, c); }
 
 // the three kernels of a game; `timed`: the launch the profile's "catch_collect(lockstep)" row brackets (either game's lockstep)
 template <class G> struct Kernels;
@@ -195,6 +203,7 @@ template <class G> struct Kernels;
   }
 GAME_KERNELS(CatchGame, catch);
 GAME_KERNELS(BreakoutGame, breakout);
+GAME_KERNELS(FreewayGame, freeway);
 #undef GAME_KERNELS
 
 // ---- environment handle: host only, no device needed ------------------------------------------------------------------------------
@@ -222,12 +231,12 @@ template <class G> static int env_step(sdqn_env_s* e, int action, int* reward, i
 template <class G> static int env_screen(sdqn_env_s* e, uint8_t* screen) { memcpy(screen, env_frame<G>(e), e->frame.size()); return SDQN_OK; }
 extern "C" int sdqn_env_create(sdqn_env_t* out, const char* name, int H, int W, uint64_t seed, int balls_per_episode) {
   ARGCHK(out && name, "NULL argument");
-  const bool breakout = strcmp(name, BreakoutGame::NAME) == 0;
-  ARGCHK(breakout || strcmp(name, CatchGame::NAME) == 0, "unknown environment '%s' (known: catch, breakout)", name);
+  const int game = strcmp(name, FreewayGame::NAME) == 0 ? GAME_FREEWAY : strcmp(name, BreakoutGame::NAME) == 0 ? GAME_BREAKOUT : strcmp(name, CatchGame::NAME) == 0 ? GAME_CATCH : -1;
+  ARGCHK(game >= 0, "unknown environment '%s' (known: catch, breakout, freeway)", name);
   ARGCHK(H >= CATCH_CELLS && W >= CATCH_CELLS && H <= 4096 && W <= 4096, "%s needs a screen of at least %d x %d pixels (got %d x %d)", name, CATCH_CELLS, CATCH_CELLS, H, W);
-  ARGCHK(balls_per_episode >= 1, "balls_per_episode %d < 1", balls_per_episode);
+  ARGCHK(balls_per_episode >= 1, "%s %d < 1", game == GAME_FREEWAY ? "episode_ticks" : "balls_per_episode", balls_per_episode);
   sdqn_env_s* e = new sdqn_env_s();
-  e->game = breakout ? GAME_BREAKOUT : GAME_CATCH;
+  e->game = game;
   e->H = H; e->W = W; e->bpe = balls_per_episode; e->frame.assign((size_t)H * W, 0);
   e->sticky_rng = catch_stream_seed(seed, 0, DYNAMICS_STICKY_STREAM);
   GAME_CALL(e, env_init, e, seed);
@@ -242,30 +251,41 @@ extern "C" int sdqn_env_step(sdqn_env_t e, int action, int* reward, int* termina
   return GAME_CALL(e, env_step, e, action, reward, terminal);
 }
 extern "C" int sdqn_env_screen(sdqn_env_t e, uint8_t* screen) { ARGCHK(e && screen, "NULL argument"); return GAME_CALL(e, env_screen, e, screen); }
-extern "C" int sdqn_env_get_state(sdqn_env_t e, sdqn_env_state* st) {
+// the state entry points, one pair per game: SDQN_ERR_ARG on another game's handle; a refused set leaves the state untouched
+static const char* game_name(int game) { return game == GAME_FREEWAY ? FreewayGame::NAME : game == GAME_BREAKOUT ? BreakoutGame::NAME : CatchGame::NAME; }
+template <class G> static int env_get_state(sdqn_env_s* e, int game, void* st, const char* fn) {
   ARGCHK(e && st, "NULL argument");
-  ARGCHK(e->game == GAME_CATCH, "sdqn_env_get_state serves catch; this environment is breakout (sdqn_env_get_state_breakout)");
-  memcpy(st, &e->cs, sizeof e->cs); return SDQN_OK;
+  ARGCHK(e->game == game, "%s serves %s; this environment is %s", fn, G::NAME, game_name(e->game));
+  memcpy(st, &e->st<G>(), sizeof(typename G::State)); return SDQN_OK;
 }
-extern "C" int sdqn_env_set_state(sdqn_env_t e, const sdqn_env_state* st) {
+template <class G> static int env_state_checked(sdqn_env_s* e, int game, const void* st, typename G::State& s, const char* fn) {
   ARGCHK(e && st, "NULL argument");
-  ARGCHK(e->game == GAME_CATCH, "sdqn_env_set_state serves catch; this environment is breakout (sdqn_env_set_state_breakout)");
-  CatchState s; memcpy(&s, st, sizeof s);
+  ARGCHK(e->game == game, "%s serves %s; this environment is %s", fn, G::NAME, game_name(e->game));
+  memcpy(&s, st, sizeof s); return SDQN_OK;
+}
+extern "C" int sdqn_env_get_state(sdqn_env_t e, sdqn_env_state* st) { return env_get_state<CatchGame>(e, GAME_CATCH, st, "sdqn_env_get_state"); }
+extern "C" int sdqn_env_set_state(sdqn_env_t e, const sdqn_env_state* st) {
+  CatchState s; int rc = env_state_checked<CatchGame>(e, GAME_CATCH, st, s, "sdqn_env_set_state"); if (rc) return rc;
   ARGCHK(CatchGame::valid(s), "catch state out of range (row %d col %d dx %d paddle %d balls %d terminal %d)", s.row, s.col, s.dx, s.paddle, s.balls, s.terminal);
   e->cs = s; e->frame_ok = false; return SDQN_OK;
 }
 extern "C" int sdqn_env_get_state_breakout(sdqn_env_t e, sdqn_env_state_breakout* st) {
-  ARGCHK(e && st, "NULL argument");
-  ARGCHK(e->game == GAME_BREAKOUT, "sdqn_env_get_state_breakout serves breakout; this environment is catch (sdqn_env_get_state)");
-  memcpy(st, &e->bs, sizeof e->bs); return SDQN_OK;
+  return env_get_state<BreakoutGame>(e, GAME_BREAKOUT, st, "sdqn_env_get_state_breakout");
 }
 extern "C" int sdqn_env_set_state_breakout(sdqn_env_t e, const sdqn_env_state_breakout* st) {
-  ARGCHK(e && st, "NULL argument");
-  ARGCHK(e->game == GAME_BREAKOUT, "sdqn_env_set_state_breakout serves breakout; this environment is catch (sdqn_env_set_state)");
-  BreakoutState s; memcpy(&s, st, sizeof s);
+  BreakoutState s; int rc = env_state_checked<BreakoutGame>(e, GAME_BREAKOUT, st, s, "sdqn_env_set_state_breakout"); if (rc) return rc;
   ARGCHK(BreakoutGame::valid(s), "breakout state out of range (row %d col %d dx %d dy %d paddle %d balls %d terminal %d pad %d bricks 0x%llx)",
          s.row, s.col, s.dx, s.dy, s.paddle, s.balls, s.terminal, s.pad, (unsigned long long)s.bricks);
   e->bs = s; e->frame_ok = false; return SDQN_OK;
+}
+extern "C" int sdqn_env_get_state_freeway(sdqn_env_t e, sdqn_env_state_freeway* st) {
+  return env_get_state<FreewayGame>(e, GAME_FREEWAY, st, "sdqn_env_get_state_freeway");
+}
+extern "C" int sdqn_env_set_state_freeway(sdqn_env_t e, const sdqn_env_state_freeway* st) {
+  FreewayState s; int rc = env_state_checked<FreewayGame>(e, GAME_FREEWAY, st, s, "sdqn_env_set_state_freeway"); if (rc) return rc;
+  ARGCHK(FreewayGame::valid(s), "freeway state out of range (row %d ticks %d crossings %d terminal %d pad %d %d cars 0x%llx timers 0x%llx periods 0x%llx)",
+         s.row, s.ticks, s.crossings, s.terminal, s.pad0, s.pad1, (unsigned long long)s.cars, (unsigned long long)s.timers, (unsigned long long)s.periods);
+  e->fs = s; e->frame_ok = false; return SDQN_OK;
 }
 // the dynamics of the handle.  sdqn_env_eval / sdqn_env_collect play their copies under the handle's frame_skip and p;
 // (get_state, get_dynamics) -> (set_state, set_dynamics_state) reproduces a game exactly.
@@ -474,7 +494,7 @@ static int env_collect(sdqn_net_t h, sdqn_env_t e, sdqn_replay_t r, int N, int64
   STREAMCHK();
   if (!h->col_win) {
     rc = dalloc(h, (void**)&h->col_win, 2 * g.half + SRC_PAD); if (rc) return rc;
-    rc = dalloc(h, &h->col_recs, (size_t)h->B * std::max(sizeof(EvalRec<CatchGame>), sizeof(EvalRec<BreakoutGame>))); if (rc) return rc;    // (either game's records)
+    rc = dalloc(h, &h->col_recs, (size_t)h->B * std::max(std::max(sizeof(EvalRec<CatchGame>), sizeof(EvalRec<BreakoutGame>)), sizeof(EvalRec<FreewayGame>))); if (rc) return rc;    // (any game's records)
   }
   const int64_t FRAME = r->frame, L = r->lane_len;
   EnvTrace tr;

@@ -78,7 +78,8 @@ class SyntheticEnvironment(Environment):
 class LibraryEnvironment(Environment):
     """A game that lives in the library (include/sdqn.h sdqn_env_*): everything here runs on the host; `_h` lets
     DeepQNetwork.act_step_env / evaluate / collect step and render the game inside the library.  The generator is the environment's own
-    (never Python's `random`).  A subclass names its game, its state struct and state calls, and its balls-per-episode option.
+    (never Python's `random`).  A subclass names its game, its state struct and state calls, and its balls-per-episode option
+    (freeway: its ticks-per-episode option).
     `args.frame_skip` (1..8, default 1) and `args.repeat_action_probability` (in [0, 1), default 0) are the game's dynamics
     (DESIGN.md §23): act(), DeepQNetwork.act_step_env and the copies of evaluate / collect all play under them."""
     game = None                                                      # name given to sdqn_env_create
@@ -198,7 +199,17 @@ class BreakoutEnvironment(LibraryEnvironment):
     _state_struct, _get_state, _set_state = "EnvStateBreakout", "sdqn_env_get_state_breakout", "sdqn_env_set_state_breakout"
 
 
-LIBRARY_GAMES = {"catch": CatchEnvironment, "breakout": BreakoutEnvironment}     # --environment values that live in the library
+class FreewayEnvironment(LibraryEnvironment):
+    """The game "freeway" of the library (csrc/env_freeway.h): a chicken on column 6 of the same court walks from row 11
+    to row 0 with actions 0 stay / 1 up / 2 down through ten rows of traffic, one car per row, each with its own period and direction;
+    +1 for a crossing and nothing else, a hit sends the chicken back to row 11, an episode is `balls_per_episode` game ticks
+    (`--freeway_ticks`, 500: the library's balls-per-episode argument carries the episode length for this game)."""
+    game = "freeway"
+    balls_option, balls_default = "freeway_ticks", 500
+    _state_struct, _get_state, _set_state = "EnvStateFreeway", "sdqn_env_get_state_freeway", "sdqn_env_set_state_freeway"
+
+
+LIBRARY_GAMES = {"catch": CatchEnvironment, "breakout": BreakoutEnvironment, "freeway": FreewayEnvironment}     # --environment values that live in the library
 
 
 def _to_gray_resized(obs, height, width):

@@ -15,15 +15,16 @@ def _flag(text):
 # (flag, type, default[, extra argparse keywords])
 _OPTIONS = {
     "Environment": [
-        ("--environment", str, "synthetic", dict(choices=["synthetic", "ale", "gym", "catch", "breakout"])),
+        ("--environment", str, "synthetic", dict(choices=["synthetic", "ale", "gym", "catch", "breakout", "freeway"])),
         ("--num_actions", int, 4, dict(help="Action-set size of the synthetic environment.")),
         ("--synthetic_frame_pool", int, 256, dict(help="Synthetic environment: serve frames from a pool of this many pre-generated frames (0: generate 7 KB of random bytes every step).")),
         ("--catch_balls", int, 10, dict(help="Catch environment: balls per episode.")),
         ("--breakout_balls", int, 3, dict(help="Breakout environment: lost balls per episode.")),
-        ("--eval_envs", int, 0, dict(help="Catch / breakout environment: play the test phase on this many copies of the game at once, on the device (0: Agent.test, one environment).")),
-        ("--train_envs", int, 0, dict(help="Catch / breakout environment: collect experience from this many copies of the game at once, on the device; the replay memory becomes that many lanes (0: Agent.train, one environment).")),
-        ("--frame_skip", int, 1, dict(help="Catch / breakout environment: game ticks per agent step (1..8); the rewards of the ticks add up.")),
-        ("--repeat_action_probability", float, 0.0, dict(help="Catch / breakout environment: sticky actions; before every game tick the action executed last is repeated with this probability, in [0, 1).")),
+        ("--freeway_ticks", int, 500, dict(help="Freeway environment: game ticks per episode (>= 1).")),
+        ("--eval_envs", int, 0, dict(help="Catch / breakout / freeway environment: play the test phase on this many copies of the game at once, on the device (0: Agent.test, one environment).")),
+        ("--train_envs", int, 0, dict(help="Catch / breakout / freeway environment: collect experience from this many copies of the game at once, on the device; the replay memory becomes that many lanes (0: Agent.train, one environment).")),
+        ("--frame_skip", int, 1, dict(help="Catch / breakout / freeway environment: game ticks per agent step (1..8); the rewards of the ticks add up.")),
+        ("--repeat_action_probability", float, 0.0, dict(help="Catch / breakout / freeway environment: sticky actions; before every game tick the action executed last is repeated with this probability, in [0, 1).")),
         ("--screen_width", int, 84), ("--screen_height", int, 84),
     ],
     "Replay memory": [
@@ -92,7 +93,7 @@ def check_train_envs(args):
         return 0
     from .environment import LIBRARY_GAMES
     if args.environment not in LIBRARY_GAMES:
-        raise ValueError("--train_envs needs --environment catch or breakout (got %s): only the library's own games run on the device" % args.environment)
+        raise ValueError("--train_envs needs --environment catch, breakout or freeway (got %s): only the library's own games run on the device" % args.environment)
     if n > args.batch_size:
         raise ValueError("--train_envs %d exceeds --batch_size %d: the copies' states are one batch of the acting forward" % (n, args.batch_size))
     if getattr(args, "prioritized_replay", False):
@@ -121,11 +122,20 @@ def check_dynamics(args):
     from .environment import LIBRARY_GAMES
     if args.environment not in LIBRARY_GAMES:
         if k != 1:
-            raise ValueError("--frame_skip %d needs --environment catch or breakout (got %s): only the library's own games honour it" % (k, args.environment))
+            raise ValueError("--frame_skip %d needs --environment catch, breakout or freeway (got %s): only the library's own games honour it" % (k, args.environment))
         if p != 0.0:
-            raise ValueError("--repeat_action_probability %g needs --environment catch or breakout (got %s): only the library's own games honour it"
+            raise ValueError("--repeat_action_probability %g needs --environment catch, breakout or freeway (got %s): only the library's own games honour it"
                              % (p, args.environment))
     return k, p
+
+
+def check_freeway_ticks(args):
+    """--freeway_ticks: its range, refused before anything touches the device"""
+    t = getattr(args, "freeway_ticks", 500)
+    t = 500 if t is None else int(t)
+    if t < 1:
+        raise ValueError("--freeway_ticks %d: must be >= 1" % t)
+    return t
 
 
 def check_target_tau(args):
@@ -172,6 +182,7 @@ def run(args):
     check_munchausen(args)
     check_clip_grad_norm(args)
     check_dynamics(args)
+    check_freeway_ticks(args)
     from . import Agent, DeepQNetwork, ReplayMemory, SyntheticEnvironment, _lib, load
     from .environment import LIBRARY_GAMES
     from .statistics import Statistics
@@ -237,7 +248,7 @@ def run(args):
             stats.reset()
             if getattr(args, "eval_envs", 0) > 0:                    # vectorised on the device (the library's games only)
                 if not hasattr(env, "_h"):
-                    raise ValueError("--eval_envs needs --environment catch or breakout")
+                    raise ValueError("--eval_envs needs --environment catch, breakout or freeway")
                 stats.record_evaluation(net.evaluate(env, args.eval_envs, -(-args.test_steps // args.eval_envs), args.exploration_rate_test,
                                                      seed=(args.random_seed or 0) + epoch + 1), args.exploration_rate_test)
             else:

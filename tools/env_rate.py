@@ -3,8 +3,9 @@
           with the screen), same build, same seeds
   eval    DeepQNetwork.evaluate env-steps/s at N = 32 and N = 256 (float32, float16) vs Agent.test on the same float32 net
     python tools/env_rate.py [--rounds 7] [--train_steps 4000] [--eval_steps 400] [--json out.json]
-  --environment catch|breakout   the library game the rates are taken on (default catch); `--environment both` instead
-          alternates the two games in one process: DeepQNetwork.evaluate at N = 32 and the --train_envs 32 train phase, float32
+  --environment catch|breakout|freeway   the library game the rates are taken on (default catch); `--environment both`
+          instead alternates catch and breakout in one process, `--environment all` (§25) all three games: DeepQNetwork.evaluate at
+          N = 32 and the --train_envs 32 train phase, float32
   --train_envs    instead: train-phase env-steps/s of Agent.train_vectorised — 32 copies (float32, float16), 8 copies, 256
           copies at batch_size 256 — against the fused single-environment Agent.train, all alternated in the same process"""
 import argparse
@@ -70,10 +71,9 @@ def train_envs_rates(o):
     return out
 
 
-def both_games_rates(o):
-    """evaluate (N = 32) and the --train_envs 32 train phase on catch and on breakout, alternated in one process, float32"""
+def both_games_rates(o, games=("catch", "breakout")):
+    """evaluate (N = 32) and the --train_envs 32 train phase on each of `games`, alternated in one process, float32"""
     import simple_dqn_amd as sd
-    games = ("catch", "breakout")
     ev, tr = {}, {}
     for g in games:
         a = _args(batch_size=32, environment=g)
@@ -107,7 +107,7 @@ def both_games_rates(o):
 def main():
     global GAME
     p = argparse.ArgumentParser()
-    p.add_argument("--environment", default="catch", choices=["catch", "breakout", "both"])
+    p.add_argument("--environment", default="catch", choices=["catch", "breakout", "freeway", "both", "all"])
     p.add_argument("--rounds", type=int, default=7)
     p.add_argument("--train_steps", type=int, default=4000)
     p.add_argument("--eval_steps", type=int, default=400)
@@ -116,8 +116,8 @@ def main():
     o = p.parse_args()
     import simple_dqn_amd as sd
     out = {}
-    if o.environment == "both":
-        out = both_games_rates(o)
+    if o.environment in ("both", "all"):
+        out = both_games_rates(o, ("catch", "breakout") if o.environment == "both" else ("catch", "breakout", "freeway"))
         for k, v in out.items():
             print("%-32s %s" % (k, " ".join("%s %.1f" % kv for kv in v.items())))
         if o.json:

@@ -230,6 +230,33 @@ struct sdqn_statebuf_s {
 // which launches a train step is made of / how its optimizer pass runs (sdqn_api_step.hip: step_structure, update_form)
 enum StepStructure { STEP_FUSED = 0, STEP_H16_BT = 1, STEP_DP_OVERLAP = 2, STEP_UNFUSED = 3 };
 enum UpdateForm { UPD_SINGLE = 0, UPD_DP_SERIAL = 1, UPD_DP_OVERLAP = 2, UPD_GRAD_ONLY = 3, UPD_CLIP = 4 };
+// What one launch of the step gets on top of the step's arguments: xcd_map = (the step's & xcd_keep) | xcd_bits, the fc4-wgrad tile range that
+// rides in it, the LaunchVariant bits.  The default changes nothing (step_args hands out all F4_TILES tiles).
+constexpr int F4_TILES = (NIN4 / 32) * (NFC / 32);
+struct LaunchPlan { int xcd_keep = ~0, xcd_bits = 0, variant = 0, f4w_first = 0, f4w_count = F4_TILES; };
+// The optimizer tail (run_update_tail): [mode 1: local sums -> g] -> [exchange] -> [clip] -> apply (mode 2, or mode 0 = sums and apply in one
+// launch) -> [BatchNorm parameters].  The next step's prep rides in the last update launch of the sequence.
+enum Exchange { XCH_NONE = 0, XCH_F32, XCH_HALF, XCH_GROUPED };   // all-reduce of g: fp32 | as half (float16 nets) | overlapped form: the conv and fc5 ranges as one group
+struct TailPlan {
+  bool reduce_first = false;
+  Exchange exchange = XCH_NONE;
+  bool clip = false;                       // --clip_grad_norm: the two clip launches in front of the apply launch
+  bool ovf = false;                        // the gradient came through the half payload: the apply launch honours the overflow flag
+  int apply_mode = 0;                      // UpdateArgs::mode of the apply launch: 0 | 2 | -1 nothing is applied (grad_only)
+  double divisor = 0.0;                    // A9's bsz of the apply launch (and of the clip): B x ranks, or sdqn_net_apply_update's argument
+  int skip_fc4 = 0;                        // fc4 is applied elsewhere: in its weight-gradient tiles (fuse_rms) or by the overlapped form's side launch
+};
+// Everything run_train decides, taken once per step from the handle (sdqn_api_step.hip: step_plan; no HIP call, no side effect)
+struct StepPlan {
+  StepStructure structure; UpdateForm update;
+  int fuse_rms;                            // StepArgs::fuse_rms: fc4's RMSProp rides in its weight-gradient tiles
+  int extra_fwd;                           // forward in front of the step (run_extra_forward): 0 none | 1 --munchausen (1, 0) | 2 --double_dqn with --batch_norm (0, 1)
+  int head_train;                          // HeadArgs::train of the step's head: 2 Double DQN, 3 Munchausen, 0: the caller's
+  int nz;                                  // net slots of the step's forward (3: the Double DQN slot rides in it)
+  bool side_fc4;                           // overlapped data parallel: fc4's all-reduce + update on g_comm behind bwd3
+  LaunchPlan launch[K_WGRADS + 1];         // by kernel id
+  TailPlan tail;
+};
 // ---- functions that cross a file boundary -------------------------------------------------------------------------------
 int ensure_stream();
 int sample_checked(uint32_t* mt, const uint8_t* terminals, int64_t count, int64_t current, int hist,
@@ -261,6 +288,8 @@ int step_blend(sdqn_net_s* h);                                     // what every
 int gen_step_done(sdqn_net_s* h);                                  // generic path: a train step was enqueued ([clip + deferred update,] counter, step_blend)
 inline bool clip_on(const sdqn_net_s* h) { return h->clip_grad_norm > 0.0; }
 int clip_gradient(sdqn_net_s* h, double bsz);                      // --clip_grad_norm: the two launches on g between update modes 1 and 2 (nothing when off)
+StepPlan step_plan(const sdqn_net_s* h);
+int run_update_tail(sdqn_net_s* h, UpdateArgs u, const TailPlan& t, const PrepArgs* next = nullptr);
 int prof_collect(sdqn_net_s* h);
 int prof_event(sdqn_net_s* h, hipEvent_t* e);
 hipError_t dp_allreduce(sdqn_net_s* h, void* buf, size_t count, int dtype, void* comm, hipStream_t s);

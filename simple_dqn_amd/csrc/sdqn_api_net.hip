@@ -446,17 +446,12 @@ extern "C" int sdqn_net_apply_update(sdqn_net_t h, double bsz) {
   if (h->gen) { set_error("data parallel (grad_only / apply_update) is implemented for the 84x84x4 float32 / float16 configurations"); return SDQN_ERR_STATE; }
   { int rc = join_comm(h); if (rc) return rc; }
   h->spec_pending = false;
-  StepArgs a = step_args(h);
-  UpdateArgs u = make_update_args(h, a);
-  u.mode = 2; u.bsz = (float)bsz; u.skip_fc4 = 0;
-  if (h->half_payload_pending) {           // the gradient came back through the half payload: same overflow rule as the RCCL path
-    u.ovf_flag = h->ovf_flag; u.ovf_count = h->ovf_count; u.ovf_dynamic = h->dp_half_scale_log2 < 0 ? 1 : 0;
-    h->half_payload_pending = false;
-  }
-  { int rcc = clip_gradient(h, bsz); if (rcc) return rcc; }       // --clip_grad_norm: with the caller's divisor
-  LAUNCH(K_UPDATE, launch_update(u, g_stream));
-  if (h->bn) LAUNCH(K_BN, launch_bn_update(u, g_stream));
-  return step_blend(h);
+  TailPlan t;                              // the step's optimizer tail from "clip" on, with the caller's divisor
+  t.clip = clip_on(h); t.apply_mode = 2; t.divisor = bsz;
+  t.ovf = h->half_payload_pending;         // the gradient came back through the half payload: same overflow rule as the RCCL path
+  h->half_payload_pending = false;
+  const int rc = run_update_tail(h, make_update_args(h, step_args(h)), t);
+  return rc ? rc : step_blend(h);
 }
 // float16 data parallel without a communicator: the two passes that bracket ncclAllReduce(ncclFloat16) in run_train, callable
 // on their own so that the exchange can be done by the caller (tests: gloo across two processes sharing one GPU).

@@ -7,6 +7,9 @@ hipError_t dp_allreduce(sdqn_net_s* h, void* buf, size_t count, int dtype, void*
 }
 
 // ---- the step ---------------------------------------------------------------------------------------------
+// fc4's RMSProp rides in its weight-gradient tiles: only when the step's one update launch applies everything else (clipping and the
+// data-parallel forms need ALL of g before any of it is applied), nobody wants to read the fc4 gradient, and the optimizer is RMSProp
+static int plan_fuse_rms(const sdqn_net_s* h, UpdateForm update) { return (update == UPD_SINGLE && !h->keep_grads && h->cfg.optimizer == 0) ? 1 : 0; }
 StepArgs step_args(sdqn_net_s* h) {
   StepArgs a; memset(&a, 0, sizeof a);
   a.B = h->B; a.A = h->A; a.nz = 2; a.theta[0] = h->theta; a.theta[1] = h->theta_t;
@@ -22,9 +25,9 @@ StepArgs step_args(sdqn_net_s* h) {
     a.wh_w = h->wh[0]; a.wht_w = h->wht[0];
     a.loss_scale = (float)h->cfg.loss_scale; a.inv_loss_scale = (float)(1.0 / h->cfg.loss_scale);
   }
-  a.f4w_first = 0; a.f4w_count = (NIN4 / 32) * (NFC / 32);
+  a.f4w_first = 0; a.f4w_count = F4_TILES;
   a.w1p[0] = h->w1p[0]; a.w1p[1] = h->w1p[1];
-  a.fuse_rms = (!h->comm && !h->keep_grads && !h->grad_only && !clip_on(h) && h->cfg.optimizer == 0) ? 1 : 0;   // (clipping needs ALL of g before any of it is applied)
+  a.fuse_rms = plan_fuse_rms(h, update_form(h));
   a.theta_w = h->theta; a.state = h->state; a.bsz = (float)h->B;
   a.rho = (float)h->cfg.decay_rate; a.one_minus_rho = (float)(1.0 - h->cfg.decay_rate);
   a.lr = (float)h->cfg.learning_rate; a.eps = (float)h->cfg.epsilon;
@@ -81,37 +84,42 @@ hipError_t launch_tuned(sdqn_net_s* h, int id, StepArgs a, hipStream_t s, int va
   t.variant = variant; t.host_idx = h->host_idx_cur; t.r3_xcd = h->r3_xcd; t.wt = h->wt;
   return launch_kernel(id, a, t, s);
 }
-int run_forward(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd) {
-  if (h->bn) {
-    // deepqnetwork.py:83-89 with batch_norm: [Convolution|Linear] -> BatchNorm -> Rectlin.  The GEMM stage writes the raw
-    // linear output (x_l), the BatchNorm pass turns it into the activation the next stage reads; training-mode
-    // statistics for the online net of a train step (:129), running statistics for the target net (:120) and predict (:180)
-    StepArgs f = a; f.bn = 1;
-    f.a1 = h->x1; LAUNCH(K_CONV1_FWD, launch_tuned(h, K_CONV1_FWD, f, g_stream)); f.a1 = h->a1;
-    LAUNCH(K_BN, launch_bn_forward(bn_args(h, a, 0, hd.train != 0), g_stream));
-    f.a2 = h->x2; LAUNCH(K_CONV2_FWD, launch_tuned(h, K_CONV2_FWD, f, g_stream)); f.a2 = h->a2;
-    LAUNCH(K_BN, launch_bn_forward(bn_args(h, a, 1, hd.train != 0), g_stream));
-    f.a3 = h->x3; LAUNCH(K_CONV3_FWD, launch_tuned(h, K_CONV3_FWD, f, g_stream)); f.a3 = h->a3;
-    LAUNCH(K_BN, launch_bn_forward(bn_args(h, a, 2, hd.train != 0), g_stream));
-    { int rc = join_comm(h); if (rc) return rc; }
-    LAUNCH(K_FC4_FWD, launch_tuned(h, K_FC4_FWD, f, g_stream));
-    LAUNCH(K_BN, launch_bn_forward(bn_args(h, a, 3, hd.train != 0), g_stream));
-    LAUNCH(K_HEAD, launch_head(f, hd, g_stream));
-    return SDQN_OK;
-  }
+static StepArgs planned(const StepArgs& a, const LaunchPlan& p) {
+  StepArgs b = a; b.xcd_map = (a.xcd_map & p.xcd_keep) | p.xcd_bits; b.f4w_first = p.f4w_first; b.f4w_count = p.f4w_count;
+  return b;
+}
+#define PLANNED_LAUNCH(KID, ARGS, L) LAUNCH(KID, launch_tuned(h, KID, planned(ARGS, (L)[KID]), g_stream, (L)[KID].variant))
+// the forward's four GEMM launches (l[K_CONV1_FWD .. K_FC4_FWD]); --batch_norm: as the step's arguments have them
+static void plan_forward(const sdqn_net_s* h, LaunchPlan* l) {
+  if (h->bn) return;
   // XCD-contiguous tile map where it wins time (tools/sweep_xcd.py, tools/ab_options.py): conv1_fwd +0.5 %, conv2_fwd
   // +0.2 %, fc4_fwd +0.6 % of the step rate; slower for conv3_fwd, fc4_dgrad and every backward launch
-  StepArgs fm = a; fm.xcd_map = 1;
-  LAUNCH(K_CONV1_FWD, launch_tuned(h, K_CONV1_FWD, fm, g_stream, (h->conv1_bf16 && h->nw_override[K_CONV1_FWD] == 0) ? LV_CONV1_FWD_BF16 : 0));
-  { StepArgs f2 = fm; if (h->B >= 128) f2.xcd_map = a.xcd_map;          // block-tile routines (B >= 128): conv2_fwd 28.8 / 8.8 us round-robin, 28.9 / 9.0 on the map (fp32 / float16)
-    LAUNCH(K_CONV2_FWD, launch_tuned(h, K_CONV2_FWD, f2, g_stream)); }
-  { StepArgs f3 = fm; f3.xcd_map = a.xcd_map;
-    const int c36 = (h->conv3_c36 && h->nw_override[K_CONV3_FWD] == 0) ? LV_CONV3_C36 : 0;
-    LAUNCH(K_CONV3_FWD, launch_tuned(h, K_CONV3_FWD, f3, g_stream, c36)); }
+  l[K_CONV1_FWD].xcd_keep = l[K_FC4_FWD].xcd_keep = 0; l[K_CONV1_FWD].xcd_bits = l[K_FC4_FWD].xcd_bits = 1;
+  if (h->B < 128) { l[K_CONV2_FWD].xcd_keep = 0; l[K_CONV2_FWD].xcd_bits = 1; }   // block-tile routines (B >= 128): conv2_fwd 28.8 / 8.8 us round-robin, 28.9 / 9.0 on the map (fp32 / float16)
+  if (h->conv1_bf16 && h->nw_override[K_CONV1_FWD] == 0) l[K_CONV1_FWD].variant = LV_CONV1_FWD_BF16;
+  if (h->conv3_c36 && h->nw_override[K_CONV3_FWD] == 0) l[K_CONV3_FWD].variant = LV_CONV3_C36;
+}
+// deepqnetwork.py:83-89.  With batch_norm: [Convolution|Linear] -> BatchNorm -> Rectlin.  The GEMM stage writes the raw linear output
+// (x_l), the BatchNorm pass turns it into the activation the next stage reads; training-mode statistics for the online net of a
+// train step (:129), running statistics for the target net (:120) and predict (:180)
+static int forward(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd, const LaunchPlan* l) {
+  StepArgs f = a; f.bn = h->bn ? 1 : 0;
+  float* const raw[3] = {h->x1, h->x2, h->x3}; float* StepArgs::* const out[3] = {&StepArgs::a1, &StepArgs::a2, &StepArgs::a3};
+#define BN_FWD(L) do { if (h->bn) LAUNCH(K_BN, launch_bn_forward(bn_args(h, a, (L), hd.train != 0), g_stream)); } while (0)
+  for (int c = K_CONV1_FWD; c <= K_CONV3_FWD; ++c) {           // (the three ids are the layer numbers)
+    StepArgs fc = f; if (h->bn) fc.*out[c] = raw[c];
+    PLANNED_LAUNCH(c, fc, l);
+    BN_FWD(c);
+  }
   { int rc = join_comm(h); if (rc) return rc; }                // conv1..3 of this step overlap the previous step's fc4 all-reduce
-  LAUNCH(K_FC4_FWD, launch_tuned(h, K_FC4_FWD, fm, g_stream));
-  LAUNCH(K_HEAD, launch_head(a, hd, g_stream, h->head_q_system));
+  PLANNED_LAUNCH(K_FC4_FWD, f, l);
+  BN_FWD(3);
+  LAUNCH(K_HEAD, launch_head(f, hd, g_stream, h->head_q_system));      // (head_q_system: the acting path, never with batch_norm)
   return SDQN_OK;
+}
+int run_forward(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd) {
+  LaunchPlan l[K_FC4_FWD + 1]; plan_forward(h, l);
+  return forward(h, a, hd, l);
 }
 UpdateArgs make_update_args(sdqn_net_s* h, const StepArgs& a) {
   UpdateArgs u; memset(&u, 0, sizeof u);
@@ -152,12 +160,13 @@ StepStructure step_structure(const sdqn_net_s* h) {
 // how the optimizer pass runs: 0 one update launch (fc4's RMSProp rode in its weight-gradient tiles) | 1 serial data parallel: local sums,
 // one all-reduce of the flat gradient, apply | 2 overlapped data parallel (fc4's part already on its way) | 3 grad_only (local sums, nothing applied)
 // | 4 single GPU with --clip_grad_norm: local sums, the two clip launches, apply (the serial data-parallel form clips inside form 1)
-UpdateForm update_form(const sdqn_net_s* h) {
-  if (step_structure(h) == STEP_DP_OVERLAP) return UPD_DP_OVERLAP;
+static UpdateForm update_form_of(const sdqn_net_s* h, StepStructure structure) {
+  if (structure == STEP_DP_OVERLAP) return UPD_DP_OVERLAP;
   if (h->comm) return UPD_DP_SERIAL;
   if (h->grad_only) return UPD_GRAD_ONLY;
   return clip_on(h) ? UPD_CLIP : UPD_SINGLE;
 }
+UpdateForm update_form(const sdqn_net_s* h) { return update_form_of(h, step_structure(h)); }
 // --clip_grad_norm: g holds the complete gradient sums (all layers [+ the BatchNorm beta | gamma block]); bsz is the divisor the
 // optimizer pass behind this will use.  Two launches in the update slot; g is scaled in place, or left bit for bit when nothing is clipped.
 int clip_gradient(sdqn_net_s* h, double bsz) {
@@ -185,168 +194,158 @@ bool ddqn_active(const sdqn_net_s* h) { return h->double_dqn && h->theta_t != h-
 // replay_memory.py:71-72, or the second half of the [2][B][STATE] staging), its Q-values left in q slot 2.  It uses slot 0 of the
 // activation buffers, which the step's own forward overwrites behind it.
 //   --double_dqn with --batch_norm: (0, 1)        --munchausen: (1, 0), qbar of the prestates
-int run_extra_forward(sdqn_net_s* h, const StepArgs& a, int wz, int sz) {
+static int run_extra_forward(sdqn_net_s* h, const StepArgs& a, int wz, int sz, const LaunchPlan* l) {
   StepArgs p = a; p.nz = 1;
   if (wz) { p.theta[0] = a.theta[1]; p.wh[0] = a.wh[1]; p.wht[0] = a.wht[1]; p.w1p[0] = a.w1p[1]; }
   if (sz) p.src = a.from_ring ? a.src + (size_t)soff(a.post_off, 1) * FRAME : a.src + (size_t)a.B * STATE;
   HeadArgs hp = head_args(h, 0); hp.q = h->q + (size_t)2 * a.B * h->A;
-  return run_forward(h, p, hp);
+  return forward(h, p, hp, l);
 }
-int run_train(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd0, const PrepArgs* next) {
-  HeadArgs hd = hd0;
-  StepArgs af = a;                         // the forward's arguments (the backward keeps a: its launches know two slots only)
-  if (h->munchausen) {                     // (refused together with double_dqn / batch_norm: sdqn_net_set_munchausen)
-    hd.train = 3; hd.mu_alpha = h->mu_alpha; hd.mu_tau = h->mu_tau; hd.mu_clip = h->mu_clip;
-    int rc0 = run_extra_forward(h, a, 1, 0); if (rc0) return rc0;
-  } else if (ddqn_active(h)) {
-    hd.train = 2;
-    if (h->bn) { int rc0 = run_extra_forward(h, a, 0, 1); if (rc0) return rc0; }
-    else af.nz = 3;
-  }
-  int rc = run_forward(h, af, hd);
-  if (rc) return rc;
-  // Backward.  Critical path: fc4_dgrad -> conv3_dgrad -> conv2_dgrad -> conv1_wgrad; the other weight gradients only need the delta of
-  // their layer and share a launch with the dgrad that is computed from the same delta.
-  // --batch_norm: the delta arriving at layer l (masked by its Rectlin) first goes back through BatchNorm l, in place
-#define BN_BWD(L) do { if (h->bn) LAUNCH(K_BN, launch_bn_backward(bn_args(h, a, (L), 1), g_stream)); } while (0)
-  BN_BWD(3);
-  const StepStructure st = step_structure(h);
-  // conv1's weight gradient on packed-bf16 MFMA (sdqn_kernels_r3.hip) in every launch structure (same bits); B < 128 only: in the
+// Everything a train step decides, once, from the handle alone: no HIP call, no side effect (api_internal.h: StepPlan)
+StepPlan step_plan(const sdqn_net_s* h) {
+  StepPlan p;
+  p.structure = step_structure(h); p.update = update_form_of(h, p.structure);
+  p.fuse_rms = plan_fuse_rms(h, p.update); p.side_fc4 = p.structure == STEP_DP_OVERLAP;
+  // the forward: --munchausen (refused together with double_dqn / batch_norm: sdqn_net_set_munchausen) | --double_dqn (comment at ddqn_active)
+  p.extra_fwd = h->munchausen ? 1 : (ddqn_active(h) && h->bn) ? 2 : 0;
+  p.head_train = h->munchausen ? 3 : ddqn_active(h) ? 2 : 0;
+  p.nz = (!h->munchausen && ddqn_active(h) && !h->bn) ? 3 : 2;
+  LaunchPlan* l = p.launch;
+  plan_forward(h, l);
+  // The backward.  conv1's weight gradient on packed-bf16 MFMA (sdqn_kernels_r3.hip) in every launch structure (same bits); B < 128 only: in the
   // throughput regime the on-the-fly split of delta1 makes it VALU-bound (3 580 vs 4 063 steps/s at B = 256; option value 2 forces it)
-  const bool c1w = (h->conv1w_bf16 == 2 || (h->conv1w_bf16 == 1 && h->B < 128)) && h->cfg.datatype == 0 && !h->bn && h->nw_override[K_CONV1_WGRAD] == 0;
+  const bool f32 = h->cfg.datatype == 0 && !h->bn;
+  const int c1w = ((h->conv1w_bf16 == 2 || (h->conv1w_bf16 == 1 && h->B < 128)) && f32 && h->nw_override[K_CONV1_WGRAD] == 0) ? LV_CONV1_WGRAD_BF16 : 0;
   // round 4, B >= 128 float32: the backward launches on the XCD-contiguous block / tile maps (the blocks that share a weight panel share an L2):
   // fc4_dgrad 15.1 -> 14.4 us, bwd2 38.9 -> 37.5, bwd3 39.7 -> 39.2; 4 802 -> 4 867 steps/s at B = 256 (placement only: same bits)
-  const bool bt_xcd = h->B >= 128 && h->cfg.datatype == 0 && h->bt_on && !h->bn && h->bt_xcd;
-  { StepArgs fd = a; if (bt_xcd) fd.xcd_map |= 1;
-    LAUNCH(K_FC4_DGRAD, launch_tuned(h, K_FC4_DGRAD, fd, g_stream)); }
-  BN_BWD(2);
-  const int f4_tiles = (NIN4 / 32) * (NFC / 32);
-  if (st == STEP_DP_OVERLAP) {
+  const bool bt_xcd = h->B >= 128 && f32 && h->bt_on && h->bt_xcd;
+  if (bt_xcd) l[K_FC4_DGRAD].xcd_bits = 1;
+  switch (p.structure) {
+  case STEP_DP_OVERLAP:
     // data parallel, overlapped: ALL of fc4_wgrad rides the first backward launch, so the 6.4 MB fc4 gradient is
     // complete two launches before the step ends; its all-reduce and its optimizer update run on g_comm
     // (second communicator) under K_BWD2, K_BWD1, the conv/fc5 all-reduce + update and the next step's conv1..3.
-    StepArgs b3 = a, b2 = a, b1 = a;
-    b3.f4w_first = 0; b3.f4w_count = f4_tiles; b2.f4w_count = b1.f4w_count = 0;
-    LAUNCH(K_BWD3, launch_tuned(h, K_BWD3, b3, g_stream));
-    HIPCHK(hipEventRecord(h->ev_g4, g_stream));
-    HIPCHK(hipStreamWaitEvent(g_comm, h->ev_g4, 0));
-    LAUNCH_ON(g_comm, K_ALLREDUCE, dp_allreduce(h, h->g + OFF4, (size_t)NW4, /*ncclFloat32*/ 7, h->comm2, g_comm));
-    UpdateArgs u4 = make_update_args(h, a);
-    u4.mode = 2; u4.only_fc4 = 1; u4.skip_fc4 = 0; u4.bsz = (float)h->B * (float)h->nranks;
-    LAUNCH_ON(g_comm, K_UPDATE, launch_update(u4, g_comm));
-    HIPCHK(hipEventRecord(h->ev_w4, g_comm));
-    h->w4_pending = true;
-    BN_BWD(1);
-    LAUNCH(K_BWD2, launch_tuned(h, K_BWD2, b2, g_stream));
-    BN_BWD(0);
-    LAUNCH(K_BWD1, launch_tuned(h, K_BWD1, b1, g_stream, c1w ? LV_CONV1_WGRAD_BF16 : 0));
-  } else if (st == STEP_H16_BT) {
+    l[K_BWD2].f4w_count = l[K_BWD1].f4w_count = 0; l[K_BWD1].variant = c1w;
+    break;
+  case STEP_FUSED:
+    // fc4 wgrad (1568 tiles at B <= 32) may be spread over the three backward launches as background traffic (options f4_share3 / f4_share2;
+    // built-in: all of it in bwd3); for B > 32 (K-split workgroups) it all rides in the first one
+    if (h->B <= 32) {
+      const int s3 = h->f4_share[0] * F4_TILES / 100, s2 = h->f4_share[1] * F4_TILES / 100;
+      l[K_BWD3].f4w_count = s3;
+      l[K_BWD2].f4w_first = s3; l[K_BWD2].f4w_count = s2;
+      l[K_BWD1].f4w_first = s3 + s2; l[K_BWD1].f4w_count = F4_TILES - s3 - s2;
+    } else l[K_BWD2].f4w_count = l[K_BWD1].f4w_count = 0;
+    if (bt_xcd) l[K_BWD3].xcd_bits = l[K_BWD2].xcd_bits = 7;
+    // B <= 32: the fc4_wgrad tiles of bwd3 (third problem of the launch) on the XCD-contiguous map — a tile row's 16 tiles share a3's columns
+    // (10.29 -> 10.10 us, 15 315 -> 15 345 steps/s in alternating rate loops; the conv3 problems are slower on it: round-robin as before)
+    if (h->B <= 32 && f32 && h->bt_xcd) l[K_BWD3].xcd_bits |= 4;
+    // conv1_wgrad on the XCD-contiguous tile map: the 8 m-tiles of a K-slab read the same frames, so a slab's tiles belong on ONE XCD's L2
+    // (L2 <-> fabric traffic of the launch 15.8 -> 4.0 MB = 1.4x algorithmic, rocprofv3 PMC; step rate -0.1 %: the re-reads were MALL hits)
+    l[K_BWD1].xcd_bits = 2;
+    l[K_BWD1].variant = l[K_BWD1].f4w_count == 0 ? c1w : 0;
+    break;
+  case STEP_H16_BT:
     // round 4, float16 at B >= 128: the two dgrads run on the half block-tile routine as launches of their own (15.6 / 18.1 -> ~7 / 8 us:
     // operands leave L2 once per workgroup), and every weight gradient that does not need delta1 shares ONE launch behind them (it packs
     // better than the two fused backward launches did) — five launches where there were four, 19 us less (tools/exp/README.md)
-    StepArgs w = a; w.f4w_first = 0; w.f4w_count = f4_tiles;
-    if (h->bt_xcd) w.xcd_map |= 7;          // the weight-gradient launch on XCD-contiguous block maps (the blocks of a K slab share their operand rows): 20.1 -> 17.0 us at B = 256
-    StepArgs b1 = a; b1.f4w_count = 0; b1.xcd_map |= 2;
-    LAUNCH(K_CONV3_DGRAD, launch_tuned(h, K_CONV3_DGRAD, a, g_stream));
-    LAUNCH(K_CONV2_DGRAD, launch_tuned(h, K_CONV2_DGRAD, a, g_stream));
+    if (h->bt_xcd) l[K_WGRADS].xcd_bits = 7;          // the weight-gradient launch on XCD-contiguous block maps (the blocks of a K slab share their operand rows): 20.1 -> 17.0 us at B = 256
+    l[K_BWD1].f4w_count = 0; l[K_BWD1].xcd_bits = 2;
     // round 6: conv1's weight gradient (c1w_h_kernel's K-slab workgroups) as a fourth block range of the weight-gradient launch — delta1 is
     // complete by then — where that kernel applies (packed-fp16 weight gradients, slabs of whole 80-position chunks) and nothing asks for
     // another form (bt:18 / bt:24 = 0; option c1w_in_wgrads: 0 = off, 1 = its workgroups last (built-in), 2 = first)
-    const int merge = (h->c1w_in_wgrads && h->h16_wgrad_mfma && (h->tps1 * 32) % 80 == 0 && h->bt[K_BWD1] == 0 && h->bt[K_WGRADS] == 0 &&
-                       h->nw_override[K_CONV1_WGRAD] == 0) ? (LV_C1W_IN_WGRADS | (h->c1w_in_wgrads == 2 ? LV_C1W_FIRST : 0)) : 0;
-    LAUNCH(K_WGRADS, launch_tuned(h, K_WGRADS, w, g_stream, merge));
-    LAUNCH(K_BWD1, launch_tuned(h, K_BWD1, b1, g_stream, merge));
-  } else if (st == STEP_FUSED) {
-    // fc4 wgrad (1568 tiles at B <= 32) may be spread over the three backward launches as background traffic (options f4_share3 / f4_share2;
-    // built-in: all of it in bwd3); for B > 32 (K-split workgroups) it all rides in the first one
-    StepArgs b3 = a, b2 = a, b1 = a;
-    if (h->B <= 32) {
-      const int s3 = h->f4_share[0] * f4_tiles / 100, s2 = h->f4_share[1] * f4_tiles / 100;
-      b3.f4w_first = 0; b3.f4w_count = s3;
-      b2.f4w_first = s3; b2.f4w_count = s2;
-      b1.f4w_first = s3 + s2; b1.f4w_count = f4_tiles - s3 - s2;
-    } else { b3.f4w_first = 0; b3.f4w_count = f4_tiles; b2.f4w_count = b1.f4w_count = 0; }
-    if (bt_xcd) { b3.xcd_map |= 7; b2.xcd_map |= 7; }
-    // B <= 32: the fc4_wgrad tiles of bwd3 (third problem of the launch) on the XCD-contiguous map — a tile row's 16 tiles share a3's columns
-    // (10.29 -> 10.10 us, 15 315 -> 15 345 steps/s in alternating rate loops; the conv3 problems are slower on it: round-robin as before)
-    if (h->B <= 32 && h->cfg.datatype == 0 && !h->bn && h->bt_xcd) b3.xcd_map |= 4;
-    LAUNCH(K_BWD3, launch_tuned(h, K_BWD3, b3, g_stream));
-    BN_BWD(1);
-    LAUNCH(K_BWD2, launch_tuned(h, K_BWD2, b2, g_stream));
-    BN_BWD(0);
-    // conv1_wgrad on the XCD-contiguous tile map: the 8 m-tiles of a K-slab read the same frames, so a slab's tiles belong on ONE XCD's L2
-    // (L2 <-> fabric traffic of the launch 15.8 -> 4.0 MB = 1.4x algorithmic, rocprofv3 PMC; step rate -0.1 %: the re-reads were MALL hits)
-    b1.xcd_map |= 2;
-    LAUNCH(K_BWD1, launch_tuned(h, K_BWD1, b1, g_stream, (c1w && b1.f4w_count == 0) ? LV_CONV1_WGRAD_BF16 : 0));
-  } else {
-    // fc4_wgrad may update W4 in place (fused RMSProp): it must not start before fc4_dgrad has read W4 — same stream, after it
-    LAUNCH(K_FC4_WGRAD, launch_tuned(h, K_FC4_WGRAD, a, g_stream));            // needs d4, a3
-    LAUNCH(K_CONV3_WGRAD, launch_tuned(h, K_CONV3_WGRAD, a, g_stream));        // needs d3p, a2
-    LAUNCH(K_CONV3_DGRAD, launch_tuned(h, K_CONV3_DGRAD, a, g_stream));
-    BN_BWD(1);
-    LAUNCH(K_CONV2_WGRAD, launch_tuned(h, K_CONV2_WGRAD, a, g_stream));        // needs d2p, a1
-    LAUNCH(K_CONV2_DGRAD, launch_tuned(h, K_CONV2_DGRAD, a, g_stream));
-    BN_BWD(0);
-    LAUNCH(K_CONV1_WGRAD, launch_tuned(h, K_CONV1_WGRAD, a, g_stream, c1w ? LV_CONV1_WGRAD_BF16 : 0));
+    if (h->c1w_in_wgrads && h->h16_wgrad_mfma && (h->tps1 * 32) % 80 == 0 && h->bt[K_BWD1] == 0 && h->bt[K_WGRADS] == 0 && h->nw_override[K_CONV1_WGRAD] == 0)
+      l[K_WGRADS].variant = l[K_BWD1].variant = LV_C1W_IN_WGRADS | (h->c1w_in_wgrads == 2 ? LV_C1W_FIRST : 0);
+    break;
+  case STEP_UNFUSED: l[K_CONV1_WGRAD].variant = c1w; break;
   }
-  UpdateArgs u = make_update_args(h, a);
-  if (next) u.next = *next;                 // (memset above left next.B = 0 otherwise)
-  switch (update_form(h)) {
-  case UPD_DP_OVERLAP:
-    // conv + fc5 gradients (0.3 MB): reduce the slabs, all-reduce the two ranges as one RCCL group on the library
-    // stream (first communicator), apply; the fc4 part is already on its way on g_comm
-    u.mode = 1; u.bsz = (float)h->B; u.next.B = 0; u.skip_fc4 = 1;
+  // The optimizer tail.  single: one launch.  clip: what the serial data-parallel form does without its all-reduce (one rank).  grad_only: that
+  // form stopped after its local sums (nothing applied, nothing clipped).  dp_overlap: the conv + fc5 gradients (0.3 MB) only — fc4's part
+  // is already on its way on g_comm
+  TailPlan& t = p.tail;
+  t.reduce_first = p.update != UPD_SINGLE;
+  if (p.update == UPD_DP_OVERLAP) t.exchange = XCH_GROUPED;
+  // fp16 mode: half payload, fp32 accumulation in the optimizer, overflow -> the step is skipped on all ranks
+  else if (p.update == UPD_DP_SERIAL) t.exchange = (h->cfg.datatype == 1 && h->dp_half && h->gh) ? XCH_HALF : XCH_F32;
+  t.ovf = t.exchange == XCH_HALF;
+  t.clip = clip_on(h) && (p.update == UPD_CLIP || p.update == UPD_DP_SERIAL);      // the all-reduced gradient, every rank alike
+  t.apply_mode = p.update == UPD_SINGLE ? 0 : p.update == UPD_GRAD_ONLY ? -1 : 2;
+  t.divisor = (double)h->B * (double)(h->comm ? h->nranks : 1);
+  t.skip_fc4 = p.side_fc4 ? 1 : p.fuse_rms;
+  return p;
+}
+// the overlapped form's side stream: fc4's gradient is complete behind bwd3 — its all-reduce and its update run on g_comm (second communicator)
+static int side_fc4_update(sdqn_net_s* h, const StepArgs& a, const TailPlan& t) {
+  HIPCHK(hipEventRecord(h->ev_g4, g_stream));
+  HIPCHK(hipStreamWaitEvent(g_comm, h->ev_g4, 0));
+  LAUNCH_ON(g_comm, K_ALLREDUCE, dp_allreduce(h, h->g + OFF4, (size_t)NW4, /*ncclFloat32*/ 7, h->comm2, g_comm));
+  UpdateArgs u4 = make_update_args(h, a);
+  u4.mode = 2; u4.only_fc4 = 1; u4.skip_fc4 = 0; u4.bsz = (float)t.divisor;
+  LAUNCH_ON(g_comm, K_UPDATE, launch_update(u4, g_comm));
+  HIPCHK(hipEventRecord(h->ev_w4, g_comm));
+  h->w4_pending = true;
+  return SDQN_OK;
+}
+// [local sums] -> [exchange] -> [clip] -> apply -> [BatchNorm parameters] (api_internal.h: TailPlan); `next` rides in the last update launch
+int run_update_tail(sdqn_net_s* h, UpdateArgs u, const TailPlan& t, const PrepArgs* next) {
+  u.skip_fc4 = t.skip_fc4; u.next.B = 0;
+  if (t.reduce_first) {
+    u.mode = 1; u.bsz = (float)h->B;
+    if (t.apply_mode < 0 && next) u.next = *next;
     LAUNCH(K_UPDATE, launch_update(u, g_stream));
+  }
+  if (t.apply_mode < 0) return SDQN_OK;
+  switch (t.exchange) {
+  case XCH_GROUPED:
     if (g_rccl.GroupStart && g_rccl.GroupEnd) NCCLCHK(g_rccl.GroupStart());
     LAUNCH(K_ALLREDUCE, dp_allreduce(h, h->g, (size_t)OFF4, 7, h->comm, g_stream));
     LAUNCH(K_ALLREDUCE, dp_allreduce(h, h->g + OFF5, (size_t)(h->NP - OFF5), 7, h->comm, g_stream));
     if (g_rccl.GroupStart && g_rccl.GroupEnd) NCCLCHK(g_rccl.GroupEnd());
-    u.mode = 2; u.bsz = (float)h->B * (float)h->nranks; u.skip_fc4 = 1;
-    if (next) u.next = *next;
-    LAUNCH(K_UPDATE, launch_update(u, g_stream));
-    if (h->bn) LAUNCH(K_BN, launch_bn_update(u, g_stream));
     break;
-  case UPD_DP_SERIAL:
-    // synchronous data parallel: local gradient sums -> one RCCL all-reduce of the flat buffer -> identical RMSProp
-    u.mode = 1; u.bsz = (float)h->B; u.next.B = 0;
-    LAUNCH(K_UPDATE, launch_update(u, g_stream));
-    if (h->cfg.datatype == 1 && h->dp_half && h->gh) {
-      // fp16 mode: half payload, fp32 accumulation in the optimizer, overflow -> the step is skipped on all ranks
-      LAUNCH(K_UPDATE, launch_grad_to_half(h->g, h->gh, h->NP, h->ovf_flag, g_stream));
-      LAUNCH(K_ALLREDUCE, dp_allreduce(h, h->gh, (size_t)h->NP, /*ncclFloat16*/ 6, h->comm, g_stream));
-      LAUNCH(K_UPDATE, launch_grad_from_half(h->gh, h->g, h->NP, h->ovf_flag, g_stream));
-      u.ovf_flag = h->ovf_flag; u.ovf_count = h->ovf_count; u.ovf_dynamic = h->dp_half_scale_log2 < 0 ? 1 : 0;
-    } else
-    LAUNCH(K_ALLREDUCE, dp_allreduce(h, h->g, (size_t)h->NP, /*ncclFloat32*/ 7, h->comm, g_stream));
-    { int rcc = clip_gradient(h, (double)h->B * (double)h->nranks); if (rcc) return rcc; }      // --clip_grad_norm: the all-reduced gradient, every rank alike
-    u.mode = 2; u.bsz = (float)h->B * (float)h->nranks;
-    if (next) u.next = *next;
-    LAUNCH(K_UPDATE, launch_update(u, g_stream));
-    if (h->bn) LAUNCH(K_BN, launch_bn_update(u, g_stream));
+  case XCH_HALF:
+    LAUNCH(K_UPDATE, launch_grad_to_half(h->g, h->gh, h->NP, h->ovf_flag, g_stream));
+    LAUNCH(K_ALLREDUCE, dp_allreduce(h, h->gh, (size_t)h->NP, /*ncclFloat16*/ 6, h->comm, g_stream));
+    LAUNCH(K_UPDATE, launch_grad_from_half(h->gh, h->g, h->NP, h->ovf_flag, g_stream));
     break;
-  case UPD_GRAD_ONLY:
-    u.mode = 1; u.bsz = (float)h->B;                                            // local sums -> g, nothing applied (and nothing clipped)
-    LAUNCH(K_UPDATE, launch_update(u, g_stream));
-    break;
-  case UPD_CLIP:
-    // --clip_grad_norm on one GPU: what the serial data-parallel form does with the clip where its all-reduce is — local sums -> g, norm,
-    // scale in place, apply (the launch that carries the next step's prep), then the BatchNorm parameters from the same clipped g
-    u.mode = 1; u.bsz = (float)h->B; u.next.B = 0;
-    LAUNCH(K_UPDATE, launch_update(u, g_stream));
-    { int rcc = clip_gradient(h, (double)h->B); if (rcc) return rcc; }
-    u.mode = 2;
-    if (next) u.next = *next;
-    LAUNCH(K_UPDATE, launch_update(u, g_stream));
-    if (h->bn) LAUNCH(K_BN, launch_bn_update(u, g_stream));
-    break;
-  default:
-    u.mode = 0; u.bsz = (float)h->B;
-    LAUNCH(K_UPDATE, launch_update(u, g_stream));
-    if (h->bn) LAUNCH(K_BN, launch_bn_update(u, g_stream));
+  case XCH_F32: LAUNCH(K_ALLREDUCE, dp_allreduce(h, h->g, (size_t)h->NP, /*ncclFloat32*/ 7, h->comm, g_stream)); break;
+  case XCH_NONE: break;
   }
+  if (t.ovf) { u.ovf_flag = h->ovf_flag; u.ovf_count = h->ovf_count; u.ovf_dynamic = h->dp_half_scale_log2 < 0 ? 1 : 0; }
+  if (t.clip) { int rc = clip_gradient(h, t.divisor); if (rc) return rc; }
+  u.mode = t.apply_mode; u.bsz = (float)t.divisor;
+  if (next) u.next = *next;
+  LAUNCH(K_UPDATE, launch_update(u, g_stream));
+  if (h->bn) LAUNCH(K_BN, launch_bn_update(u, g_stream));
+  return SDQN_OK;
+}
+// The backward's launches per structure, in order.  Critical path: fc4_dgrad -> conv3_dgrad -> conv2_dgrad -> conv1_wgrad; the other weight
+// gradients only need the delta of their layer and share a launch with the dgrad that is computed from the same delta.  BWD_BN + l
+// (--batch_norm only): the delta arriving at layer l (masked by its Rectlin) first goes back through BatchNorm l, in place.  Unfused:
+// fc4_wgrad may update W4 in place (fused RMSProp), so it must not start before fc4_dgrad has read W4 — same stream, after it; fc4_wgrad
+// needs d4 and a3, conv3_wgrad d3p and a2, conv2_wgrad d2p and a1.
+enum { BWD_END = -1, BWD_SIDE_FC4 = -2, BWD_BN = -8 };
+static const int BWD_SEQ[4][12] = {
+  /* STEP_FUSED      */ {BWD_BN + 3, K_FC4_DGRAD, BWD_BN + 2, K_BWD3, BWD_SIDE_FC4, BWD_BN + 1, K_BWD2, BWD_BN + 0, K_BWD1, BWD_END},
+  /* STEP_H16_BT     */ {K_FC4_DGRAD, K_CONV3_DGRAD, K_CONV2_DGRAD, K_WGRADS, K_BWD1, BWD_END},
+  /* STEP_DP_OVERLAP */ {BWD_BN + 3, K_FC4_DGRAD, BWD_BN + 2, K_BWD3, BWD_SIDE_FC4, BWD_BN + 1, K_BWD2, BWD_BN + 0, K_BWD1, BWD_END},
+  /* STEP_UNFUSED    */ {BWD_BN + 3, K_FC4_DGRAD, BWD_BN + 2, K_FC4_WGRAD, K_CONV3_WGRAD, K_CONV3_DGRAD, BWD_BN + 1, K_CONV2_WGRAD, K_CONV2_DGRAD, BWD_BN + 0, K_CONV1_WGRAD, BWD_END}};
+int run_train(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd0, const PrepArgs* next) {
+  const StepPlan plan = step_plan(h);
+  HeadArgs hd = hd0;
+  if (plan.head_train) hd.train = plan.head_train;
+  if (plan.head_train == 3) { hd.mu_alpha = h->mu_alpha; hd.mu_tau = h->mu_tau; hd.mu_clip = h->mu_clip; }
+  if (plan.extra_fwd) { int rc0 = run_extra_forward(h, a, plan.extra_fwd == 1, plan.extra_fwd == 2, plan.launch); if (rc0) return rc0; }
+  StepArgs af = a; af.nz = plan.nz;        // the forward's arguments (the backward keeps a: its launches know two slots only)
+  int rc = forward(h, af, hd, plan.launch); if (rc) return rc;
+  for (const int* s = BWD_SEQ[plan.structure]; *s != BWD_END; ++s) {
+    if (*s >= 0) PLANNED_LAUNCH(*s, a, plan.launch);
+    else if (*s == BWD_SIDE_FC4) { if (plan.side_fc4) { rc = side_fc4_update(h, a, plan.tail); if (rc) return rc; } }
+    else if (h->bn) LAUNCH(K_BN, launch_bn_backward(bn_args(h, a, *s - BWD_BN, 1), g_stream));
+  }
+  rc = run_update_tail(h, make_update_args(h, a), plan.tail, next); if (rc) return rc;
   h->train_iterations += 1;                                                   // deepqnetwork.py:168
   h->spec_pending = false;                 // the online parameters move: a forward enqueued before this step no longer is "predict now"
-  return update_form(h) == UPD_GRAD_ONLY ? SDQN_OK : step_blend(h);      // --target_tau: one blend behind every APPLIED step
+  return plan.update == UPD_GRAD_ONLY ? SDQN_OK : step_blend(h);      // --target_tau: one blend behind every APPLIED step
 }
 // small read-backs: `bytes` of device memory into the pinned scratch h->h_f, waited for
 static int fetch_small(sdqn_net_s* h, const void* src, size_t bytes) {

@@ -16,6 +16,8 @@
 //     k-slot <-> logical-k assignment is free as long as A and B agree, and with kslot(t, h) = 8*(t>>2) + 4h + (t&3)
 //     a lane's 16 operand values are four 16 B loads of its own row (4 B for the u8 ring);
 //   * the NW partial tiles are summed through LDS in a fixed order (deterministic), then P::store.
+//   * a staged problem whose N leaves most CUs without a 32-wide tile (fc4_dgrad: 98 of them) runs the same scheme on 32 x 16 tiles and
+//     v_mfma_f32_16x16x4_f32 instead (P::N16_WAVES, gemm_tile_n16; maps in n16_map.h).
 //
 // MFMA operand maps (guide §3): lane l holds A[i = l&31][k = l>>5], B[k = l>>5][j = l&31];
 // D register r of lane l is D[i = (r&3) + 8*(r>>2) + 4*(l>>5)][j = l&31].
@@ -23,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include "problems.h"
+#include "n16_map.h"
 #include "launch.h"
 
 namespace sdqn {
@@ -98,6 +101,16 @@ __device__ __forceinline__ void lead_scalars(StepArgs& a, int B, int ctl) { a.B 
 #define SDQN_LEAD_FWD lp0, lp1, lp2, lp3, lp4, lB, ls0, ls1, lctl, lr0, lr1
 template <class P, class = void> struct uses_f16_mfma { static constexpr bool value = false; };
 template <class P> struct uses_f16_mfma<P, decltype((void)P::F16_MFMA)> { static constexpr bool value = P::F16_MFMA; };
+// N16_WAVES: the wave count at which a staged fp32 problem runs on the 32 x 16 tile body (gemm_tile_n16 below) instead of the 32 x 32 one;
+// absent or 0: never.  The choice belongs to (problem, waves per tile): the same problem keeps 32 x 32 tiles in its other launch forms.
+template <class P, class = void> struct n16_waves { static constexpr int value = 0; };
+template <class P> struct n16_waves<P, decltype((void)P::N16_WAVES)> { static constexpr int value = P::N16_WAVES; };
+template <class P, int NW> constexpr bool use_n16() {
+  return NW > 1 && n16_waves<P>::value == NW && stages_lds<P>::value && !uses_f16_wgrad<P>::value && !uses_f16_mfma<P>::value;
+}
+// problems whose epilogue gates the result with a stored activation may offer the two halves of store apart (P::GATED: gate_load, store_gated)
+template <class P, class = void> struct gated_store { static constexpr bool value = false; };
+template <class P> struct gated_store<P, decltype((void)P::GATED)> { static constexpr bool value = P::GATED; };
 
 constexpr int PANEL = 32 * 33;      // one [32 k][32 x] fp32 panel, pitch 33
 
@@ -407,6 +420,124 @@ __device__ __forceinline__ void gemm_tile(const StepArgs& a, int bx, int by, int
   SDQN_WSTAMP_FLUSH;
 }
 
+// ---- 32 x 16 tile body: v_mfma_f32_16x16x4_f32 ----------------------------------------------------------------------------------
+// For staged problems (both operands k-contiguous) whose N leaves most CUs without a 32-wide tile: half the columns per workgroup, twice
+// the workgroups, half the matrix time and half the B panel on every CU.  Same structure as gemm_tile — wave w owns the 32-deep chunks
+// w, w + NW, ..., runs them without a workgroup barrier with the next chunk's loads in flight, and the NW partial tiles are summed through
+// LDS in wave order — on the maps of n16_map.h: a chunk is 8 k-steps x 2 row halves of the 16 x 16 x 4 instruction (32 cycles each, two
+// independent accumulators: the 40-cycle dependent latency never shows), both halves on the same B fragment.  Exact fp32 like the
+// 32 x 32 x 2 form, and the k-slot map feeds every element's fmaf chain the same k in the same order: bit-identical to gemm_tile.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+template <class P, int NW, int NT>
+__device__ __forceinline__ void gemm_tile_n16(const StepArgs& a, int bx, int by, int bz, float* smem) {
+  static_assert(P::A_K && P::B_K && NW > 1, "32 x 16 body: both operands staged, K split over the waves");
+  typedef typename P::aoff_t aoff_t;
+  SDQN_STAMP(0);
+  SDQN_WSTAMP_DECL;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int m0 = bx * n16::TM, n0 = by * n16::TN;
+  int z, ks, kbeg, kend;
+  P::ksplit(a, bz, z, ks, kbeg, kend);
+  if (NW * 64 < NT && wave >= NW) kend = kbeg;          // surplus waves of a wider workgroup: no chunks
+  const int M = P::M(a), N = P::N(a);
+
+  float* pan_a = smem + (wave < NW ? wave : 0) * n16::WAVE_LDS;
+  float* pan_b = pan_a + n16::PANEL_A;
+  aoff_t srow[4]; int scol[2];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { const int m = m0 + n16::ld_x(lane, j); srow[j] = P::a_row(a, z, m < M ? m : M - 1); }
+#pragma unroll
+  for (int j = 0; j < 2; ++j) { const int n = n0 + n16::ld_x(lane, j); scol[j] = P::b_col(a, z, n < N ? n : N - 1); }
+
+  f4 pra[4], prb[2];
+  auto stage_load = [&](int kk) {
+    const aoff_t c = P::a_col(a, z, kk + n16::ld_k(lane));
+#pragma unroll
+    for (int j = 0; j < 4; ++j) pra[j] = P::a_load4(a, z, srow[j] + c);
+    const int r = P::b_row(a, z, kk + n16::ld_k(lane));
+#pragma unroll
+    for (int j = 0; j < 2; ++j) prb[j] = P::b_load4(a, z, r + scol[j]);
+  };
+  int kc = kbeg + (wave < NW ? wave : 0) * 32;            // wave-uniform
+  SDQN_STAMP(1);
+  SDQN_STAMP(2);
+  SDQN_WSTAMP(0);
+  if (kc < kend) stage_load(kc);
+  SDQN_WSTAMP(1);
+  // the epilogue's element of this thread: known now, so a gating activation is fetched behind the operand loads instead of as a
+  // dependent load after the combine (unconditional with clamped indexes: a guarded load costs a branch and a full vmcnt wait)
+  const int el = threadIdx.x & (n16::TM * n16::TN - 1);
+  const int ml = n16::epi_row(el), nl = n16::epi_col(el);
+  const bool mine = threadIdx.x < n16::TM * n16::TN && m0 + ml < M && n0 + nl < N;
+  float gate = 0.0f;
+  if constexpr (gated_store<P>::value) gate = P::gate_load(a, z, m0 + ml < M ? m0 + ml : M - 1, n0 + nl < N ? n0 + nl : N - 1);
+  (void)gate;
+
+  f32x4 acc0 = {0.0f, 0.0f, 0.0f, 0.0f}, acc1 = {0.0f, 0.0f, 0.0f, 0.0f};
+  while (kc < kend) {
+    float fa0[8], fa1[8], fb[8];
+    // registers -> panels: logical k = ld_k + e goes to panel row krow(k) (n16_map.h), columns as loaded
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int x = n16::ld_x(lane, j), k = n16::ld_k(lane);
+      pan_a[n16::pan_off(n16::PA, k, x)] = pra[j].x; pan_a[n16::pan_off(n16::PA, k + 1, x)] = pra[j].y;
+      pan_a[n16::pan_off(n16::PA, k + 2, x)] = pra[j].z; pan_a[n16::pan_off(n16::PA, k + 3, x)] = pra[j].w;
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int x = n16::ld_x(lane, j), k = n16::ld_k(lane);
+      pan_b[n16::pan_off(n16::PB, k, x)] = prb[j].x; pan_b[n16::pan_off(n16::PB, k + 1, x)] = prb[j].y;
+      pan_b[n16::pan_off(n16::PB, k + 2, x)] = prb[j].z; pan_b[n16::pan_off(n16::PB, k + 3, x)] = prb[j].w;
+    }
+    if (kc + NW * 32 < kend) stage_load(kc + NW * 32);     // next chunk's loads fly under this chunk's MFMAs
+    wave_lds_sync();
+#pragma unroll
+    for (int t = 0; t < 8; ++t) { fa0[t] = pan_a[n16::frag_a(lane, t, 0)]; fa1[t] = pan_a[n16::frag_a(lane, t, 1)]; fb[t] = pan_b[n16::frag_b(lane, t)]; }
+    wave_lds_sync();                                       // panel reads issued before the next chunk's stores
+#ifdef SDQN_TIMING
+    asm volatile("" :: "v"(fa0[0]), "v"(fa1[7]));          // A landed (its loads were issued first: in-order return)
+    SDQN_WSTAMP(2);
+    asm volatile("" :: "v"(fb[0]), "v"(fb[7]));            // operands landed
+    SDQN_WSTAMP(3);
+    SDQN_STAMP(3);
+#endif
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+      acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(fa0[t], fb[t], acc0, 0, 0, 0);
+      acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(fa1[t], fb[t], acc1, 0, 0, 0);
+    }
+    kc += NW * 32;
+  }
+
+  // ---- epilogue: NW partial tiles -> LDS (the wave's own panels, done with) -> summed in wave order -> store ----
+#ifdef SDQN_TIMING
+  asm volatile("" :: "v"(acc0[0]), "v"(acc1[3]));
+  SDQN_STAMP(4);
+#endif
+  if (wave < NW) {
+    float* cw = smem + wave * n16::WAVE_LDS;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      cw[n16::comb_off(n16::acc_row(0, lane, r), n16::acc_col(lane))] = acc0[r];
+      cw[n16::comb_off(n16::acc_row(1, lane, r), n16::acc_col(lane))] = acc1[r];
+    }
+  }
+  __syncthreads();
+  SDQN_STAMP(5);
+  static_assert(NT >= n16::TM * n16::TN, "one thread per element of the tile");
+  if (mine) {
+    float v = smem[n16::comb_off(ml, nl)];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) v += smem[w * n16::WAVE_LDS + n16::comb_off(ml, nl)];
+    if constexpr (gated_store<P>::value) P::store_gated(a, z, ks, m0 + ml, n0 + nl, v, gate);
+    else P::store(a, z, ks, m0 + ml, n0 + nl, v);
+  }
+  SDQN_STAMP(6);
+  SDQN_WSTAMP_FLUSH;
+}
+
 // ---- fp16-mode tile body: packed-fp16 MFMA -------------------------------------------------------------------
 // v_mfma_f32_32x32x16_f16: lane (i = l & 31, h = l >> 5) feeds 8 consecutive k (one 16-B load) of row i of A and of
 // column i of B into k-slots 8h..8h+7; both operands of these problems are k-contiguous in memory (NHWC activations /
@@ -599,18 +730,20 @@ __device__ __forceinline__ void gemm_tile_hw(const StepArgs& a, int bx, int by, 
 
 template <class P, int NW, int NT>
 __device__ __forceinline__ void run_tile(const StepArgs& a, int bx, int by, int bz, float* smem) {
-  if constexpr (uses_f16_wgrad<P>::value) gemm_tile_hw<P, NW, NT>(a, bx, by, bz, smem);
+  if constexpr (use_n16<P, NW>()) gemm_tile_n16<P, NW, NT>(a, bx, by, bz, smem);
+  else if constexpr (uses_f16_wgrad<P>::value) gemm_tile_hw<P, NW, NT>(a, bx, by, bz, smem);
   else if constexpr (uses_f16_mfma<P>::value) gemm_tile_h<P, NW, NT>(a, bx, by, bz, smem);
   else gemm_tile<P, NW, NT>(a, bx, by, bz, smem);
 }
 template <class P, int NW>
 constexpr int tile_lds_any() {
-  if constexpr (uses_f16_wgrad<P>::value) return NW * HW_WAVE_LDS;   // staging tiles, reused as combine panels
+  if constexpr (use_n16<P, NW>()) return NW * n16::WAVE_LDS;          // operand panels, reused as combine panels
+  else if constexpr (uses_f16_wgrad<P>::value) return NW * HW_WAVE_LDS;   // staging tiles, reused as combine panels
   else return uses_f16_mfma<P>::value ? NW * PANEL : tile_lds<P, NW>();
 }
-// rows / columns of C one wave-tile covers
+// rows / columns of C one tile covers (NW: waves per tile of the launch form; 0 = a form without a narrow body)
 template <class P> constexpr int tile_m() { return 32; }
-template <class P> constexpr int tile_n() { return 32; }
+template <class P, int NW = 0> constexpr int tile_n() { return use_n16<P, NW>() ? n16::TN : 32; }
 
 // (xcd_tile_id / xcd_tile_id_range, the XCD-aware workgroup -> tile maps: problems.h — host + device, tests/emul executes them)
 
@@ -653,6 +786,7 @@ struct MultiDims { int n[3]; int gx[3], gy[3]; };       // workgroups per proble
 
 template <class P, int NW, int NT>
 __device__ __forceinline__ void multi_dispatch(const StepArgs& a, const MultiDims& d, int which, int local, float* smem) {
+  static_assert(!use_n16<P, NW>(), "multi-problem launches size their tile grids for 32 x 32 tiles");
   if constexpr (NW == 1) {
     // one tile per wave; the launch owns the tile range [a.f4w_first, a.f4w_first + a.f4w_count)
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -729,7 +863,7 @@ struct NoProblem {            // placeholder third problem for two-problem launc
 
 template <class P, int NW>
 inline hipError_t launch_gemm(const StepArgs& a, hipStream_t stream) {
-  dim3 grid((P::M(a) + tile_m<P>() - 1) / tile_m<P>(), (P::N(a) + tile_n<P>() - 1) / tile_n<P>(), P::nbz(a));
+  dim3 grid((P::M(a) + tile_m<P>() - 1) / tile_m<P>(), (P::N(a) + tile_n<P, NW>() - 1) / tile_n<P, NW>(), P::nbz(a));
   Lead l; memset(&l, 0, sizeof l);
   if constexpr (has_lead<P>::value) {                       // (the tile grid rides packed in one dword: a larger grid reads the struct)
     P::lead_pack(a, l); l.B = a.B; l.s0 = lead_grid(grid);

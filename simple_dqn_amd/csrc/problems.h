@@ -444,6 +444,8 @@ struct Fc4Dgrad {   // delta3 = (W4^T delta4) * 1[a3 > 0]  (A5, A8), written str
   typedef int aoff_t;
   // operand descriptors for the engine's fast paths: *_REG = plain row-major [k][x] matrix with row pitch *_LD
   static constexpr bool A_REG = false, A_U8 = false, B_REG = false; static constexpr int A_LD = 0, B_LD = 0;
+  // the staged 16-wave form (B < 128) cuts N = 3136 into 196 tiles of 16 columns instead of 98 of 32: gemm_engine.h, gemm_tile_n16
+  static constexpr int N16_WAVES = 16;
   SDQN_HD static const float* a_ptr(const StepArgs& a, int z) { (void)z; return a.d4; }
   SDQN_HD static const float* b_ptr(const StepArgs& a, int z) { (void)z; return a.theta[0] + OFF4; }
 #if defined(__HIPCC__)
@@ -471,6 +473,8 @@ struct Fc4Dgrad {   // delta3 = (W4^T delta4) * 1[a3 > 0]  (A5, A8), written str
     a.d3[(int64_t)m * NIN4 + n] = dv;                             // dense [(n,pix)][f]: operand of conv3 wgrad
   }
 };
+
+struct Fc4DgradWide : Fc4Dgrad { static constexpr int N16_WAVES = 0; };      // --batch_norm keeps the 32 x 32 tiles at every wave count
 
 struct Fc4Wgrad {   // gW4 = delta4 . a3^T (sum over batch, A8) in the W4i layout; no split (K = B)
   static constexpr bool A_K = false, B_K = false;     // operand contiguous along k (-> LDS transpose) or along m/n

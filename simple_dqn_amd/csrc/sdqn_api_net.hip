@@ -687,7 +687,7 @@ extern "C" int sdqn_net_debug_read(sdqn_net_t h, const char* name, float* out, i
   struct { const char* n; float* p; int64_t len; } tab[] = {
     {"a1", h->a1, (int64_t)2 * B * PIX1 * K1}, {"a2", h->a2, (int64_t)2 * B * PIX2 * K2}, {"a3", h->a3, (int64_t)2 * B * PIX3 * K3},
     {"a4", h->a4, (int64_t)2 * B * NFC}, {"d4", h->d4, (int64_t)B * NFC}, {"d3p", h->d3p, (int64_t)B * PD3 * PD3 * K3},
-    {"d2p", h->d2p, (int64_t)B * PD2 * PD2 * K2}, {"d1", h->d1, (int64_t)B * PIX1 * K1}, {"q", h->q, (int64_t)2 * B * h->A},
+    {"d3", h->d3, (int64_t)B * PIX3 * K3}, {"d2p", h->d2p, (int64_t)B * PD2 * PD2 * K2}, {"d1", h->d1, (int64_t)B * PIX1 * K1}, {"q", h->q, (int64_t)2 * B * h->A},
     {"dq", h->dq, (int64_t)B * h->A}, {"g", h->g, h->NP}, {"theta", h->theta, h->NP}, {"cost_terms", h->cost_terms, B}};
   for (auto& e : tab) if (!strcmp(e.n, name)) {
     ARGCHK(n <= e.len, "buffer %s holds %lld floats", name, (long long)e.len);

@@ -101,7 +101,9 @@ hipError_t launch_lat(const Route& r, int id, const StepArgs& a, const LaunchTun
         case K_CONV2_FWD: return launch_gemm<Conv2Fwd, 16>(a, s);       // K = 512  -> 16 chunks
         case K_CONV3_FWD: return launch_gemm<Conv3Fwd, 16>(a, s);       // K = 576 -> 18 chunks over 16 waves (staged, 9 waves x 2 chunks: -0.4 %)
         case K_FC4_FWD: return launch_gemm<Staged<Fc4Fwd>, 14>(a, s);   // K = 3136 -> 98 chunks = S4(7) x 14; rows 12.5 KB apart: staged
-        case K_FC4_DGRAD: return launch_gemm<Staged<Fc4Dgrad>, 16>(a, s);   // K = 512; rows 2 KB apart: staged
+        case K_FC4_DGRAD:                                               // K = 512; rows 2 KB apart: staged; 196 tiles of 32 x 16
+          if (a.bn) return launch_gemm<Staged<Fc4DgradWide>, 16>(a, s);   // (--batch_norm: the 98 tiles of 32 x 32 it was measured with)
+          return launch_gemm<Staged<Fc4Dgrad>, 16>(a, s);
         case K_FC4_WGRAD:                                               // K = B
           if (r.form == LAT_F4W_NW1) return launch_gemm<Fc4Wgrad, 1>(a, s);
           if (r.form == LAT_F4W_NW2) return launch_gemm<Fc4Wgrad, 2>(a, s);

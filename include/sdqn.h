@@ -350,6 +350,28 @@ int sdqn_net_step_structure(sdqn_net_t h, int* structure, int* update);
  * (either order: option "double_dqn" is refused on a net whose Munchausen targets are on). */
 int sdqn_net_set_munchausen(sdqn_net_t h, int on, double alpha, double tau, double clip);
 int sdqn_net_get_munchausen(sdqn_net_t h, int* on, double* alpha, double* tau, double* clip);     /* any pointer may be NULL */
+/* Bootstrapped DQN, --bootstrap_heads K (Osband, Blundell, Pritzel and Van Roy 2016; no reference counterpart).  The network is
+ * created with num_actions = K x A outputs (<= 18); output row k A + a is Q-head k, action a, and actions in transitions are < A.  A train step
+ * gives every Q-head its own target y_k = r_c + (terminal ? 0 : discount max_a Q_k(theta-, s')[a]) and sets
+ *   dq[k A + a_n] = m_k clip(Q_k(theta, s)[a_n] - y_k) / K,   cost term = (sum_k m_k 0.5 delta_k^2) / K,   maxpostq (sdqn_net_last_q) = mean_k max_a Q_k
+ * (option "n_step": R, the done flag and discount^n in their places).  m_k is the bootstrap mask of the sample's RING SLOT: a pure function
+ * of (seed, slot index, k) that is 1 with probability P (sdqn_bootstrap_mask), all ones for P = 1.  P < 1 therefore needs steps fed from a replay
+ * memory (sdqn_net_train_many, sdqn_net_train_replay); sdqn_net_train_host* are refused by name then.  Acting: the game loops and
+ * sdqn_net_act_greedy follow ONE Q-head per episode while collecting — head sdqn_bootstrap_head_of(seed, K, copy, episode number) — and the
+ * majority vote of the K greedy actions (ties: lowest action) while evaluating.  K = 1 (default) is the network without any of this: no
+ * launch, no argument changes.  K in 1..18 dividing num_actions, P in (0, 1]; K > 1 is SDQN_ERR_ARG together with option "double_dqn",
+ * sdqn_net_set_munchausen, batch_norm and a prioritized replay memory (either order). */
+int sdqn_net_set_bootstrap(sdqn_net_t h, int K, double P, uint64_t seed);
+int sdqn_net_get_bootstrap(sdqn_net_t h, int* K, double* P, uint64_t* seed);     /* any pointer may be NULL */
+/* single-environment acting (sdqn_net_act_greedy): vote = 1 the majority vote (testing), 0 the episode's Q-head of copy 0 (collecting);
+ * new_episode: 1 a fresh episode starts (the episode number advances), 0 not, -1 the episode number returns to 0 */
+int sdqn_net_bootstrap_acting(sdqn_net_t h, int vote, int new_episode);
+/* the two pure functions, host side (no device): out[k] = m_k(index), k < K; *k = the Q-head copy `copy` follows in its episode `episode` */
+int sdqn_bootstrap_mask(uint64_t seed, double P, int K, int64_t index, uint8_t* out);
+int sdqn_bootstrap_head_of(uint64_t seed, int K, int64_t copy, int64_t episode, int* k);
+/* the acting rule on one raw Q row q[K A]: vote = 1 the majority vote, 0 the greedy action of Q-head sdqn_bootstrap_head_of(seed, K, copy, episode)
+ * (first maximum; a NaN counts as one) */
+int sdqn_bootstrap_act(const float* q, int K, int A, int vote, uint64_t seed, int64_t copy, int64_t episode, int* action);
 /* option "double_dqn" (0 default / 1, any configuration, switchable between steps): Double DQN targets (van Hasselt, Guez and Silver
  * 2016): the online net picks each poststate's action, the target net values it (see sdqn_net_last_q).  The online net's forward on
  * the poststates rides as a third net slot in the step's own forward launches (batch_norm: a forward of its own in front of the step,

@@ -53,6 +53,8 @@ class Agent:
         # reference's very first copy (agent.py:105 at total_train_steps == 0), so that training starts from theta- = theta
         self.target_tau = float(getattr(args, "target_tau", 0.0) or 0.0)
         self.callback = None
+        # --bootstrap_heads: the net follows one Q-head per episode while collecting and votes while testing
+        self._boot = getattr(deep_q_network, "bootstrap_heads", 1) > 1
         self._per = getattr(replay_memory, "prioritized", False)
         if self._per:
             self._beta0, self._beta_steps = float(args.priority_beta), int(args.priority_beta_steps)
@@ -86,12 +88,16 @@ class Agent:
             q = self.net.predict_one(self.buf.getState())             # same numbers as predict(padded batch)[0]
         else:
             q = self.net.predict(self.buf.getStateMinibatch())[0]     # the reference's padded minibatch, agent.py:55-58
+        if self._boot:
+            return self.net.acting_action(q)
         assert len(q) == self.num_actions
         return int(np.argmax(q))
 
     def _fresh_episode(self):
         """restart and idle through a random number of no-op frames so episodes do not all start alike (agent.py:29-39)"""
         self.env.restart()
+        if self._boot:
+            self.net.next_episode()
         for _ in range(random.randint(self.history_length, self.random_starts) + 1):
             self.env.act(0)
             if self.env.isTerminal():
@@ -151,12 +157,20 @@ class Agent:
     def _explorationRate(self):
         return self._epsilon.at(self.total_train_steps)
 
+    def _acting_mode(self, test):
+        if self._boot:
+            self.net.set_acting(test)
+
     def play_random(self, random_steps):                              # fill the replay memory with uniform-random play
+        self._acting_mode(False)
         self.env.restart()
+        if self._boot:
+            self.net.next_episode()
         for _ in range(random_steps):
             self._advance_and_store(1)
 
     def train(self, train_steps, epoch=0):
+        self._acting_mode(False)
         for i in range(train_steps):
             self._advance_and_store(self._epsilon.at(self.total_train_steps))
             if self.target_tau > 0:
@@ -208,11 +222,13 @@ class Agent:
             self.total_train_steps += N
 
     def test(self, test_steps, epoch=0):
+        self._acting_mode(True)
         self._fresh_episode()
         for _ in range(test_steps):
             self._advance(self.exploration_rate_test)
 
     def play(self, num_games):
+        self._acting_mode(True)
         self._fresh_episode()
         for _ in range(num_games):
             terminal = False

@@ -10,6 +10,7 @@
 #include <string>
 #include "../../include/sdqn.h"
 #include "problems.h"          // NStepArgs
+#include "bootstrap.h"         // BootArgs
 
 namespace sdqn {
 
@@ -44,6 +45,7 @@ struct GenericNet {
   // launch, none without a target net
   virtual hipError_t soft_update(double tau) = 0;
   virtual bool has_target() const = 0;
+  virtual bool double_dqn_on() const = 0;
   virtual hipError_t set_double_dqn(bool on) = 0;                        // --double_dqn (allocates the online-on-poststates Q on first use)
   // --munchausen: Munchausen DQN targets; one more forward (target net, prestates) and the soft-value branch of the TD head
   virtual hipError_t set_munchausen(bool on, double alpha, double tau, double clip) = 0;
@@ -51,6 +53,10 @@ struct GenericNet {
   // --prioritized_replay (sdqn_per.hip): w != nullptr makes the following train steps weight the taken action's row by w[n] and write the
   // new priority (|delta| + eps)^alpha into newp[n]; nullptr: the standard step
   virtual void set_per(const float* w, float* newp, double alpha, double eps) = 0;
+  // --bootstrap_heads (bootstrap.h): K > 1 arms the K-head branch of the TD head (the net has K x game-A outputs); boot_idx
+  // names the [B] ring indexes of the NEXT step's samples (device-readable; copied on the stream) or, nullptr, none (tuple path, P = 1)
+  virtual void set_bootstrap(int K, uint64_t thresh, uint64_t mask_seed) = 0;
+  virtual hipError_t boot_idx(const int64_t* idx) = 0;
   // --n_step: n > 1 makes the train steps read rew as the n-step returns (float64 bits) and term as the done flags, and
   // bootstrap with gamma_n; n = 1: the standard step
   virtual void set_nstep(int n, double gamma_n) = 0;

@@ -172,9 +172,33 @@ __global__ void head_kernel(const T* __restrict__ q_on, const T* __restrict__ q_
                             const int64_t* __restrict__ rew, const uint8_t* __restrict__ term, T* __restrict__ dq,
                             T* __restrict__ cost_terms, T* __restrict__ maxq, int N, int A, double discount, double minr, double maxr, T clip,
                             const T* __restrict__ q_sel, const float* __restrict__ per_w, float* __restrict__ per_p, double per_alpha, double per_eps,
-                            int nstep, double gamma_n, const T* __restrict__ q_mu, double mu_alpha, double mu_tau, double mu_clip) {
+                            int nstep, double gamma_n, const T* __restrict__ q_mu, double mu_alpha, double mu_tau, double mu_clip, const BootArgs boot) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
+  if (boot.K > 1) {                                                           // --bootstrap_heads: one target per Q-head, masked, all over K
+    const int K = boot.K, GA = boot.A, at = act[n] < GA ? act[n] : GA - 1;
+    double r, gam = discount;
+    if (nstep > 1) { r = __builtin_bit_cast(double, rew[n]); gam = gamma_n; }
+    else { r = (double)rew[n]; r = r < minr ? minr : (r > maxr ? maxr : r); }
+    const int64_t i = boot.idx ? boot.idx[n] : 0;
+    double msum = 0.0; T cost = (T)0;
+    for (int k = 0; k < K; ++k) {
+      const T* qp = q_tg + (int64_t)n * A + k * GA;
+      T m = qp[0];
+      for (int a = 1; a < GA; ++a) { const T v = qp[a]; m = v > m ? v : m; }
+      msum += (double)m;
+      const double y = term[n] ? r : r + gam * (double)m;
+      const T d = q_on[(int64_t)n * A + k * GA + at] - (T)y;
+      T e = d;
+      if (clip != (T)0) e = e < -clip ? -clip : (e > clip ? clip : e);
+      const int live = bootstrap_mask_bit(boot.mask_seed, boot.thresh, i, k);
+      if (live) cost += (T)0.5 * (d * d);
+      for (int a = 0; a < GA; ++a) dq[(int64_t)n * A + k * GA + a] = (live && a == at) ? e / (T)K : (T)0;
+    }
+    cost_terms[n] = cost / (T)K;
+    maxq[n] = (T)(msum / (double)K);
+    return;
+  }
   T m = q_tg[(int64_t)n * A];
   double bonus = 0.0, V = 0.0;
   if (q_mu) {                                                                 // --munchausen: soft value of s', scaled log-policy bonus of (s, a)
@@ -388,7 +412,7 @@ class GenericNetT : public GenericNet {
     GCHK(forward(0, pre, B));                                                  // online net on the prestates, tensors kept :128-130
     hipLaunchKernelGGL(head_kernel<T>, dim3((B + 63) / 64), dim3(64), 0, st, (const T*)q, (const T*)(q + (int64_t)B * A), actions, rew, term,
                        dq, cost_terms, maxq, B, A, cfg.discount_rate, cfg.min_reward, cfg.max_reward, (T)cfg.clip_error, (const T*)(dd ? q_sel : nullptr),
-                       per_w, per_p, per_alpha, per_eps, nstep, gamma_n, (const T*)(munchausen ? q_mu : nullptr), mu_alpha, mu_tau, mu_clip);
+                       per_w, per_p, per_alpha, per_eps, nstep, gamma_n, (const T*)(munchausen ? q_mu : nullptr), mu_alpha, mu_tau, mu_clip, boot);
     hipLaunchKernelGGL(cost_kernel<T>, dim3(1), dim3(64), 0, st, (const T*)cost_terms, cost, cost_sum, B);
     // ---- bprop (A8) :162
     GCHK(gemm(ga(dq, 1, A, act[3], 512, 1, g + off[4], A, 512, B)));                                   // gW5 = dq^T @ a4
@@ -503,7 +527,18 @@ class GenericNetT : public GenericNet {
   void set_per(const float* w, float* newp, double alpha, double eps) override { per_w = w; per_p = newp; per_alpha = alpha; per_eps = eps; }
   const float* per_w = nullptr; float* per_p = nullptr; double per_alpha = 0.0, per_eps = 0.0;
   void set_nstep(int n, double g) override { nstep = n; gamma_n = g; }
+  BootArgs boot = {1, 0, 1ull << 53, 0, nullptr}; int64_t* boot_idx_buf = nullptr;
+  void set_bootstrap(int K, uint64_t thresh, uint64_t mask_seed) override { boot.K = K; boot.A = A / K; boot.thresh = thresh; boot.mask_seed = mask_seed; boot.idx = nullptr; }
+  hipError_t boot_idx(const int64_t* idx) override {
+    boot.idx = nullptr;
+    if (!idx) return hipSuccess;
+    if (!boot_idx_buf) GCHK(dalloc(&boot_idx_buf, (int64_t)B));
+    GCHK(hipMemcpyAsync(boot_idx_buf, idx, (size_t)B * sizeof(int64_t), hipMemcpyDefault, st));
+    boot.idx = boot_idx_buf;
+    return hipSuccess;
+  }
   int nstep = 1; double gamma_n = 0.0;
+  bool double_dqn_on() const override { return double_dqn; }
   hipError_t set_double_dqn(bool on) override {
     if (on && munchausen) return hipErrorInvalidValue;
     if (on && !q_sel) GCHK(dalloc(&q_sel, (int64_t)B * A));

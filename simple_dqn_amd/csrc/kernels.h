@@ -7,6 +7,7 @@
 #include "problems.h"
 #include "launch.h"
 #include "launch_route.h"
+#include "bootstrap.h"
 
 namespace sdqn {
 
@@ -24,7 +25,8 @@ struct HeadArgs {
   double discount, min_reward, max_reward;
   float clip_error;
   int train;                    // 0: predict only (z = 0); 1: train step; 2: train step with Double DQN targets (--double_dqn);
-                                // 3: train step with Munchausen targets (--munchausen; sdqn_munchausen.hip)
+                                // 3: train step with Munchausen targets (--munchausen; sdqn_munchausen.hip);
+                                // 4: train step of a K-head bootstrapped net (--bootstrap_heads; sdqn_bootstrap.hip, its BootArgs beside this struct)
   // --munchausen, read when train == 3: bonus scale alpha, softmax temperature tau, lower clip l0 of tau ln pi.  They lie
   // in the 24 bytes a retired option's fields left: every later field keeps its offset (see StepArgs::reserved_)
   double mu_alpha, mu_tau, mu_clip;
@@ -156,8 +158,14 @@ hipError_t launch_r3(const Route& r, int id, const StepArgs& a, const LaunchTune
 hipError_t launch_bt(const Route& r, int id, const StepArgs& a, const LaunchTune& t, hipStream_t s);       // sdqn_kernels_bt.hip: block tiles and the hand-written kernels beside them
 hipError_t launch_ss(const Route& r, int id, const StepArgs& a, const LaunchTune& t, hipStream_t s);       // sdqn_kernels_ss.hip: sample-stationary convolution chains
 hipError_t launch_kernel(int id, const StepArgs& a, const LaunchTune& t, hipStream_t s);     // the GEMM-shaped stages (single or multi-problem launches)
-hipError_t launch_head(const StepArgs& a, const HeadArgs& h, hipStream_t s, bool q_system_scope = false);   // q_system_scope: h.q is mapped host memory (acting path)
+// q_system_scope: h.q is mapped host memory (acting path); boot: what h.train == 4 (--bootstrap_heads) needs beside the two structs (refused without it)
+hipError_t launch_head(const StepArgs& a, const HeadArgs& h, hipStream_t s, bool q_system_scope = false, const BootArgs* boot = nullptr);
 hipError_t launch_head_munchausen(const StepArgs& a, const HeadArgs& h, hipStream_t s);     // sdqn_munchausen.hip: what launch_head runs for h.train == 3
+hipError_t launch_head_bootstrap(const StepArgs& a, const HeadArgs& h, const BootArgs& b, hipStream_t s);     // sdqn_bootstrap.hip: what launch_head runs for h.train == 4
+// sdqn_bootstrap.hip: [N][K A] Q rows -> [N][A] acting rows (float or double); vote = 0: the slice of Q-head k(e, episodes_e), the int64 episode
+// counter of copy e at recs + e stride + offset; vote = 1: the vote counts
+hipError_t launch_bootstrap_select(const void* q, void* out, bool f64, int N, int K, int A, int vote, uint64_t head_seed,
+                                   const void* recs, size_t stride, size_t offset, hipStream_t s);
 hipError_t launch_update(const UpdateArgs& u, hipStream_t s);
 hipError_t launch_gather(const GatherArgs& g, hipStream_t s, const int64_t* host_idx = nullptr);   // host_idx (B <= 256): indexes inside the kernel arguments
 hipError_t launch_bn_forward(const BnArgs& b, hipStream_t s);      // [partial +] apply

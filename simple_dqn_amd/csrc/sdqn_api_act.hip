@@ -169,6 +169,11 @@ extern "C" int sdqn_net_act_greedy(sdqn_net_t h, sdqn_statebuf_t sb, int* action
   int best = 0;
   for (int k = 1; k < A; ++k) if (q[k] > q[best] || (q[k] != q[k] && q[best] == q[best])) best = k;   // np.argmax: the first maximum, a NaN counts as one
   *action = best;
+  if (h->boot_K > 1) {                     // --bootstrap_heads: the vote while testing, the episode's Q-head (copy 0) while collecting
+    int votes[MAX_ACTIONS]; const int GA = game_actions(h);
+    if (h->boot_vote) *action = bootstrap_vote(q, h->boot_K, GA, votes);
+    else *action = bootstrap_vote(q + bootstrap_head_of(bootstrap_head_seed(h->boot_seed), h->boot_K, 0, (uint64_t)h->boot_episode) * GA, 1, GA, votes);
+  }
   if (q_out) memcpy(q_out, q, (size_t)A * 4);
   return SDQN_OK;
 }

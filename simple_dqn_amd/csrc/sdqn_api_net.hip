@@ -551,6 +551,7 @@ extern "C" int sdqn_net_set_munchausen(sdqn_net_t h, int on, double alpha, doubl
   ARGCHK(alpha >= 0.0 && alpha <= 1.0, "munchausen_alpha %g outside [0, 1]", alpha);
   ARGCHK(clip <= 0.0 && clip > -INFINITY, "munchausen_clip %g: must be <= 0", clip);
   if (on) {
+    ARGCHK(h->boot_K == 1, "munchausen cannot be combined with bootstrap_heads %d", h->boot_K);
     ARGCHK(h->cfg.batch_norm == 0.0, "munchausen cannot be combined with batch_norm: inference-mode statistics for its third forward are not defined");
     ARGCHK(h->gen || !h->double_dqn, "munchausen cannot be combined with double_dqn: the Munchausen target has no argmax for the online net to choose");
   }
@@ -568,8 +569,62 @@ extern "C" int sdqn_net_get_munchausen(sdqn_net_t h, int* on, double* alpha, dou
   return SDQN_OK;
 }
 
+// ---- --bootstrap_heads: Bootstrapped DQN (sdqn.h; bootstrap.h) --------------------------------------------------------------
+static int boot_thresh_of(double P, uint64_t* thresh) {
+  ARGCHK(P > 0.0 && P <= 1.0, "bootstrap_mask_probability %g outside (0, 1]", P);
+  *thresh = (uint64_t)ceil(ldexp(P, 53));
+  return SDQN_OK;
+}
+extern "C" int sdqn_net_set_bootstrap(sdqn_net_t h, int K, double P, uint64_t seed) {
+  ARGCHK(h, "NULL handle");
+  ARGCHK(K >= 1 && K <= MAX_ACTIONS, "bootstrap_heads %d outside [1, %d]", K, MAX_ACTIONS);
+  ARGCHK(h->A % K == 0, "bootstrap_heads %d does not divide the network's %d outputs (create it with bootstrap_heads x num_actions <= %d)", K, h->A, MAX_ACTIONS);
+  uint64_t thresh; { int rc_ = boot_thresh_of(P, &thresh); if (rc_) return rc_; }
+  if (K > 1) {
+    ARGCHK(h->cfg.batch_norm == 0.0, "bootstrap_heads %d cannot be combined with batch_norm", K);
+    const bool dd = h->gen ? h->gen->double_dqn_on() : h->double_dqn, mu = h->gen ? h->gen->munchausen_on() : h->munchausen;
+    ARGCHK(!dd, "bootstrap_heads %d cannot be combined with double_dqn", K);
+    ARGCHK(!mu, "bootstrap_heads %d cannot be combined with munchausen", K);
+  }
+  if (h->gen) h->gen->set_bootstrap(K, thresh, bootstrap_mask_seed(seed));
+  h->boot_K = K; h->boot_P = P; h->boot_seed = seed; h->boot_thresh = thresh; h->boot_episode = 0;
+  return SDQN_OK;
+}
+extern "C" int sdqn_net_get_bootstrap(sdqn_net_t h, int* K, double* P, uint64_t* seed) {
+  ARGCHK(h, "NULL handle");
+  if (K) *K = h->boot_K; if (P) *P = h->boot_P; if (seed) *seed = h->boot_seed;
+  return SDQN_OK;
+}
+extern "C" int sdqn_net_bootstrap_acting(sdqn_net_t h, int vote, int new_episode) {
+  ARGCHK(h, "NULL handle");
+  ARGCHK(vote == 0 || vote == 1, "vote must be 0 or 1");
+  h->boot_vote = vote;
+  if (new_episode < 0) h->boot_episode = 0; else h->boot_episode += new_episode;
+  return SDQN_OK;
+}
+extern "C" int sdqn_bootstrap_mask(uint64_t seed, double P, int K, int64_t index, uint8_t* out) {
+  ARGCHK(out && K >= 1, "bad arguments");
+  uint64_t thresh; { int rc_ = boot_thresh_of(P, &thresh); if (rc_) return rc_; }
+  const uint64_t ms = bootstrap_mask_seed(seed);
+  for (int k = 0; k < K; ++k) out[k] = (uint8_t)bootstrap_mask_bit(ms, thresh, index, k);
+  return SDQN_OK;
+}
+extern "C" int sdqn_bootstrap_head_of(uint64_t seed, int K, int64_t copy, int64_t episode, int* k) {
+  ARGCHK(k && K >= 1 && copy >= 0 && episode >= 0, "bad arguments");
+  *k = bootstrap_head_of(bootstrap_head_seed(seed), K, (uint64_t)copy, (uint64_t)episode);
+  return SDQN_OK;
+}
+extern "C" int sdqn_bootstrap_act(const float* q, int K, int A, int vote, uint64_t seed, int64_t copy, int64_t episode, int* action) {
+  ARGCHK(q && action && K >= 1 && A >= 1 && A <= MAX_ACTIONS && copy >= 0 && episode >= 0, "bad arguments");
+  int votes[MAX_ACTIONS];
+  if (vote) *action = bootstrap_vote(q, K, A, votes);
+  else *action = bootstrap_vote(q + bootstrap_head_of(bootstrap_head_seed(seed), K, (uint64_t)copy, (uint64_t)episode) * A, 1, A, votes);   // (one head's vote: its greedy action)
+  return SDQN_OK;
+}
+
 extern "C" int sdqn_net_set_option(sdqn_net_t h, const char* name, int value) {
   ARGCHK(h && name, "NULL argument");
+  if (!strcmp(name, "double_dqn") && value) ARGCHK(h->boot_K == 1, "double_dqn cannot be combined with bootstrap_heads %d", h->boot_K);
   if (!strcmp(name, "n_step")) {                          // n-step returns: sdqn.h
     ARGCHK(value >= 1 && value <= SDQN_MAX_N_STEP, "n_step %d out of range [1, %d]", value, SDQN_MAX_N_STEP);
     h->n_step = value;
@@ -703,6 +758,7 @@ namespace sdqn { hipError_t set_timing_buffer(unsigned long long* p); }
 // experiment-only build (make timing): run ONE kernel id of the step with phase stamps; returns [blocks][8] cycles
 extern "C" int sdqn_debug_time_kernel(sdqn_net_t h, sdqn_replay_t r, const int64_t* idx_host, int kernel, unsigned long long* out, int max_blocks) {
   ARGCHK(h && r && idx_host && out, "NULL");
+  ARGCHK(kernel != K_HEAD || h->boot_K == 1, "bootstrap_heads %d: this hook launches the standard head, not the step's bootstrap head", h->boot_K);
   unsigned long long* d = nullptr;
   HIPCHK(hipMalloc((void**)&d, (size_t)max_blocks * 64));
   HIPCHK(hipMemset(d, 0, (size_t)max_blocks * 64));

@@ -114,7 +114,8 @@ static int forward(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd, const L
   { int rc = join_comm(h); if (rc) return rc; }                // conv1..3 of this step overlap the previous step's fc4 all-reduce
   PLANNED_LAUNCH(K_FC4_FWD, f, l);
   BN_FWD(3);
-  LAUNCH(K_HEAD, launch_head(f, hd, g_stream, h->head_q_system));      // (head_q_system: the acting path, never with batch_norm)
+  const BootArgs boot = {h->boot_K, game_actions(h), h->boot_thresh, bootstrap_mask_seed(h->boot_seed), a.from_ring ? a.idx : nullptr};   // (read when hd.train == 4)
+  LAUNCH(K_HEAD, launch_head(f, hd, g_stream, h->head_q_system, &boot));      // (head_q_system: the acting path, never with batch_norm)
   return SDQN_OK;
 }
 int run_forward(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd) {
@@ -208,7 +209,8 @@ StepPlan step_plan(const sdqn_net_s* h) {
   p.fuse_rms = plan_fuse_rms(h, p.update); p.side_fc4 = p.structure == STEP_DP_OVERLAP;
   // the forward: --munchausen (refused together with double_dqn / batch_norm: sdqn_net_set_munchausen) | --double_dqn (comment at ddqn_active)
   p.extra_fwd = h->munchausen ? 1 : (ddqn_active(h) && h->bn) ? 2 : 0;
-  p.head_train = h->munchausen ? 3 : ddqn_active(h) ? 2 : 0;
+  // --bootstrap_heads K > 1 (refused together with double_dqn / munchausen / batch_norm: sdqn_net_set_bootstrap): its own head; K = 1: nothing
+  p.head_train = h->boot_K > 1 ? 4 : h->munchausen ? 3 : ddqn_active(h) ? 2 : 0;
   p.nz = (!h->munchausen && ddqn_active(h) && !h->bn) ? 3 : 2;
   LaunchPlan* l = p.launch;
   plan_forward(h, l);
@@ -448,10 +450,15 @@ static int train_host_tuple(sdqn_net_t h, const uint8_t* pre, const uint8_t* act
   ARGCHK(h && pre && actions && rewards && post && terminals, "NULL argument");
   if (returns) ARGCHK(h->n_step > 1, "sdqn_net_train_host_returns needs option n_step > 1 (network n_step %d)", h->n_step);
   else ARGCHK(h->n_step == 1, "network n_step %d: integer rewards are refused, train with returns (sdqn_net_train_host_returns)", h->n_step);
-  for (int i = 0; i < h->B; ++i) ARGCHK(actions[i] < h->A, "action %d out of range at %d", (int)actions[i], i);
+  for (int i = 0; i < h->B; ++i) ARGCHK(actions[i] < game_actions(h), "action %d out of range at %d", (int)actions[i], i);
+  ARGCHK(h->boot_K == 1 || h->boot_P >= 1.0, "%s: bootstrap_mask_probability %g < 1 needs the ring index of every sample — train from the replay memory "
+         "(sdqn_net_train_many / sdqn_net_train_replay); the tuple path serves bootstrap_heads %d with probability 1 only",
+         returns ? "sdqn_net_train_host_returns" : "sdqn_net_train_host", h->boot_P, h->boot_K);
   const bool ours = owner != nullptr;
   if (ours) { int rcn = nstep_match(h, owner); if (rcn) return rcn; rcn = check_replay_geometry(h, owner); if (rcn) return rcn; }
+  ARGCHK(h->boot_K == 1 || !per_owns_minibatch(owner), "bootstrap_heads %d cannot be combined with prioritized_replay", h->boot_K);
   if (h->gen) {
+    if (h->boot_K > 1) GENCHK(h->gen->boot_idx(nullptr));
     const bool per = per_owns_minibatch(owner);                 // prioritized memory: weighted step + priority write-back
     if (per) per_gen_arm(h, owner);
     const hipError_t ge = reuse ? h->gen->train_dev_host_meta(owner->d_pre, owner->d_post, actions, rewards, terminals, h->epoch)
@@ -540,8 +547,8 @@ PrepArgs prep_args(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* pinned_idx) {
 // head kernel (which clamps) and train garbage silently; the tuple API checks the same thing (sdqn_net_train_host)
 int check_ring_actions(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* idx) {
   for (int i = 0; i < r->B; ++i)
-    ARGCHK(idx[i] >= 0 && idx[i] < r->size && r->actions[idx[i]] < h->A,
-           "ring slot %lld holds action %d but the network has %d actions", (long long)idx[i], (int)r->actions[idx[i]], h->A);
+    ARGCHK(idx[i] >= 0 && idx[i] < r->size && r->actions[idx[i]] < game_actions(h),
+           "ring slot %lld holds action %d but the network has %d actions", (long long)idx[i], (int)r->actions[idx[i]], game_actions(h));
   return SDQN_OK;
 }
 // A step that reads its states from the ring, its indexes in h->d_idx: the arguments, and the step.  host_idx: the host copy of those
@@ -569,6 +576,7 @@ static int gen_train_replay(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* idx_
   int slot; const int64_t* didx; int rc = check_ring_actions(h, r, idx_host); if (rc) return rc;
   rc = replay_push_idx(r, idx_host, &slot, &didx); if (rc) return rc;
   rc = replay_gather_generic(r, didx); if (rc) return rc;
+  if (h->boot_K > 1) GENCHK(h->gen->boot_idx(didx));                    // (copied on the stream, in front of the slot's release)
   rc = replay_release_idx_batched(r, slot, false); if (rc) return rc;
   GENCHK(h->gen->train_dev(r->d_pre, r->d_post, r->d_act, r->d_rew, r->d_term, h->epoch));
   return gen_step_done(h);
@@ -583,6 +591,7 @@ int check_replay_geometry(const sdqn_net_s* h, const sdqn_replay_s* r) {
 // what the entry points that train from a replay memory ask first: its batch size, n-step settings and geometry are the network's
 static int check_replay_fits(const sdqn_net_s* h, const sdqn_replay_s* r) {
   ARGCHK(r->B == h->B, "replay batch_size %d != network batch_size %d", r->B, h->B);
+  ARGCHK(h->boot_K == 1 || !r->per, "bootstrap_heads %d cannot be combined with prioritized_replay", h->boot_K);
   const int rc = nstep_match(h, r);
   return rc ? rc : check_replay_geometry(h, r);
 }

@@ -380,7 +380,7 @@ static int env_check(sdqn_net_t h, sdqn_env_t e, int N, double epsilon, const En
   g.hist = h->gen ? h->cfg.history_length : C0; g.H = h->gen ? h->cfg.screen_height : H0; g.W = h->gen ? h->cfg.screen_width : W0;
   g.state = (size_t)g.hist * g.H * g.W; g.half = (size_t)h->B * g.state;
   ARGCHK(e->H == g.H && e->W == g.W, "the environment's screen (%d x %d) and the network's (%d x %d) differ", e->H, e->W, g.H, g.W);
-  ARGCHK(h->A == G::ACTIONS, "the network has %d actions, %s has %d", h->A, G::NAME, G::ACTIONS);
+  ARGCHK(h->A == h->boot_K * G::ACTIONS, "the network has %d actions, %s has %d", game_actions(h), G::NAME, G::ACTIONS);
   ARGCHK(N >= 1 && N <= h->B, "num_envs %d out of range [1, batch_size %d]", N, h->B);
   ARGCHK(epsilon >= 0.0 && epsilon <= 1.0, "epsilon %g out of range [0, 1]", epsilon);
   ARGCHK(!o.trace() || (o.tr_actions && o.tr_rewards && o.tr_terminals && o.tr_q), "the trace buffers come together: all four or none");
@@ -411,9 +411,24 @@ struct EnvTrace {
     return SDQN_OK;
   }
 };
+// --bootstrap_heads K > 1: one launch behind the forward reduces its [N][K A] rows to the [N][A] acting rows the game's
+// kernel reads — the episode's Q-head per copy (collecting; the episode counters are read from the records) or the vote counts (evaluating).
+// K = 1: nothing is launched, the kernel reads the forward's rows.
+template <class G>
+static int env_select(sdqn_net_t h, EvalArgs& a, int vote) {
+  if (h->boot_K == 1) return SDQN_OK;
+  if (!h->boot_q) { int rc = dalloc(h, &h->boot_q, (size_t)h->B * MAX_ACTIONS * sizeof(double)); if (rc) return rc; }
+  // counted like the game kernel it feeds: collect's lockstep under K_COLLECT, eval's not at all
+#define BOOT_SELECT launch_bootstrap_select(a.q, h->boot_q, a.q_f64 != 0, a.N, h->boot_K, a.A, vote, bootstrap_head_seed(h->boot_seed), a.envs, \
+                                            sizeof(EvalRec<G>), offsetof(EvalRec<G>, episodes), g_stream)
+  if (vote) HIPCHK(BOOT_SELECT); else LAUNCH(K_COLLECT, BOOT_SELECT);
+#undef BOOT_SELECT
+  a.q = h->boot_q;
+  return SDQN_OK;
+}
 static EvalArgs env_args(sdqn_net_t h, sdqn_env_t e, int N, const EnvGeom& g, void* recs) {
   EvalArgs a; memset(&a, 0, sizeof a);
-  a.A = h->A; a.N = N; a.hist = g.hist; a.H = g.H; a.W = g.W; a.bpe = e->bpe; a.envs = recs;
+  a.A = game_actions(h); a.N = N; a.hist = g.hist; a.H = g.H; a.W = g.W; a.bpe = e->bpe; a.envs = recs;
   a.frame_skip = e->frame_skip; a.thresh_p = e->thresh_p;
   return a;
 }
@@ -444,7 +459,7 @@ static int env_eval(sdqn_net_t h, sdqn_env_t e, int N, int64_t steps, double eps
     rc = recs.alloc((size_t)N * sizeof(Rec)); if (rc) return rc;
     HIPCHK(hipMemsetAsync(recs.p, 0, (size_t)N * sizeof(Rec), g_stream));
     EvalArgs a = env_args(h, e, N, g, recs.p);
-    rc = tr.begin(o, steps, N, h->A, a); if (rc) return rc;
+    rc = tr.begin(o, steps, N, a.A, a); if (rc) return rc;
     a.seed = seed; a.thresh = (uint64_t)ceil(ldexp(epsilon, 53));
     a.init = 1; a.src = win + g.half; a.dst = win;
     HIPCHK(Kernels<G>::eval(a, g_stream));
@@ -452,6 +467,7 @@ static int env_eval(sdqn_net_t h, sdqn_env_t e, int N, int64_t steps, double eps
     for (int64_t t = 0; t < steps; ++t) {
       const uint8_t* cur = win + (size_t)(t & 1) * g.half;
       rc = predict_forward(h, cur, N, &a.q, &a.q_f64); if (rc) return rc;
+      rc = env_select<G>(h, a, 1); if (rc) return rc;
       a.t = t; a.src = cur; a.dst = win + (size_t)((t + 1) & 1) * g.half;
       HIPCHK(Kernels<G>::eval(a, g_stream));
     }
@@ -502,7 +518,7 @@ static int env_collect(sdqn_net_t h, sdqn_env_t e, sdqn_replay_t r, int N, int64
   int64_t p = r->lane_pos, f = r->lane_fill, launched = 0;
   auto body = [&]() -> int {
     EvalArgs a = env_args(h, e, N, g, h->col_recs);
-    int rc = tr.begin(o, locksteps, N, h->A, a); if (rc) return rc;
+    int rc = tr.begin(o, locksteps, N, a.A, a); if (rc) return rc;
     CollectArgs c; c.ring = r->d_ring; c.meta = r->d_meta; c.lane_len = L; c.pos = p;
     if (seed >= 0) {
       HIPCHK(hipMemsetAsync(h->col_win, 0, 2 * g.half + SRC_PAD, g_stream));
@@ -516,7 +532,7 @@ static int env_collect(sdqn_net_t h, sdqn_env_t e, sdqn_replay_t r, int N, int64
       double eps = epsilon_start + (double)t * epsilon_step;
       eps = eps < 0.0 ? 0.0 : (eps > 1.0 ? 1.0 : eps);
       a.q = nullptr;
-      if (eps < 1.0) { rc = predict_forward(h, cur, N, &a.q, &a.q_f64); if (rc) return rc; }
+      if (eps < 1.0) { rc = predict_forward(h, cur, N, &a.q, &a.q_f64); if (rc) return rc; rc = env_select<G>(h, a, 0); if (rc) return rc; }
       a.thresh = (uint64_t)ceil(ldexp(eps, 53));
       a.t = t; a.src = cur; a.dst = h->col_win + (size_t)((T + 1) & 1) * g.half;
       c.pos = p;

@@ -27,8 +27,35 @@ def layer_shapes(num_actions, history_length=4, screen_height=84, screen_width=8
     return shapes + [(512, c * h * w), (num_actions, 512)]
 
 
+MAX_ACTIONS = 18                                          # outputs of the library's head kernels (csrc/problems.h)
+
+
+def check_bootstrap(args, num_actions=None):
+    """--bootstrap_heads K / --bootstrap_mask_probability P: K >= 1, K x num_actions <= 18 (when num_actions is known),
+    P in (0, 1], and K > 1 with none of --double_dqn, --prioritized_replay, --munchausen, --batch_norm.  Raises ValueError; touches no
+    device.  Returns (K, P)."""
+    K = getattr(args, "bootstrap_heads", 1)
+    K = 1 if K is None else int(K)
+    P = float(getattr(args, "bootstrap_mask_probability", 1.0))
+    if K < 1:
+        raise ValueError("--bootstrap_heads %d: must be >= 1" % K)
+    if not 0.0 < P <= 1.0:                                    # (a NaN fails the comparison)
+        raise ValueError("--bootstrap_mask_probability %g: must be in (0, 1]" % P)
+    if K > 1 and num_actions is not None and K * int(num_actions) > MAX_ACTIONS:      # (K = 1: the library's own range check, as ever)
+        raise ValueError("--bootstrap_heads %d x %d actions = %d outputs: the network has at most %d"
+                         % (K, int(num_actions), K * int(num_actions), MAX_ACTIONS))
+    if K > 1:
+        for flag in ("double_dqn", "prioritized_replay", "munchausen", "batch_norm"):
+            if getattr(args, flag, False):
+                raise ValueError("--bootstrap_heads cannot be combined with --%s (DESIGN.md §27 lists it as a follow-up)" % flag)
+    return K, P
+
+
 class DeepQNetwork:
     def __init__(self, num_actions, args):
+        # Bootstrapped DQN (DESIGN.md §27): K Q-heads over one torso are a library net with K x num_actions outputs, row k A + a = head k, action a
+        self.bootstrap_heads, self.bootstrap_mask_probability = check_bootstrap(args, num_actions)
+        self._net_actions = self.bootstrap_heads * num_actions
         self._lib = _lib.load()
         self.num_actions = num_actions
         self.batch_size = args.batch_size
@@ -50,7 +77,7 @@ class DeepQNetwork:
         # else on the tuned kernels; the choice is the library's, from the configuration alone
         self._f64 = dt == "float64"
         self._np = np.float64 if self._f64 else np.float32
-        self._shapes = layer_shapes(num_actions, self.history_length, *self.screen_dim)
+        self._shapes = layer_shapes(self._net_actions, self.history_length, *self.screen_dim)
         tuned_geom = (self.history_length,) + tuple(self.screen_dim) == (4, 84, 84)
         if not tuned_geom and (dt == "float16" or self.batch_norm):
             raise NotImplementedError("float16 and batch_norm are implemented for 84x84 screens with history_length 4")
@@ -65,7 +92,7 @@ class DeepQNetwork:
         cfg = _lib.NetCfg()
         cfg.batch_size, cfg.history_length = self.batch_size, self.history_length
         cfg.screen_height, cfg.screen_width = self.screen_dim
-        cfg.num_actions = num_actions
+        cfg.num_actions = self._net_actions
         cfg.target_enabled = 1 if getattr(args, "target_steps", 10000) else 0          # :64
         cfg.discount_rate, cfg.clip_error = float(self.discount_rate), float(self.clip_error or 0)
         cfg.min_reward, cfg.max_reward = float(self.min_reward), float(self.max_reward)
@@ -112,6 +139,10 @@ class DeepQNetwork:
         self.munchausen_clip = float(getattr(args, "munchausen_clip", -1.0))
         if bool(getattr(args, "munchausen", False)):
             self.set_munchausen(True)
+        self.bootstrap_seed = int(getattr(args, "random_seed", 0) or 0) & 0xFFFFFFFFFFFFFFFF
+        self._boot_vote, self._boot_episode = False, 0
+        if self.bootstrap_heads > 1:                           # (K = 1: the library is not told anything)
+            _lib.check(self._lib.sdqn_net_set_bootstrap(h, self.bootstrap_heads, self.bootstrap_mask_probability, self.bootstrap_seed))
         self._mt_buf = (C.c_uint32 * _lib.MT_WORDS)()
         self._act_out = C.c_int(); self._act_greedy = self._lib.sdqn_net_act_greedy
         self._env_r, self._env_t = C.c_int(), C.c_int(); self._act_step_env = self._lib.sdqn_net_act_step_env
@@ -187,6 +218,28 @@ class DeepQNetwork:
         clip = self.munchausen_clip if clip is None else float(clip)
         _lib.check(self._lib.sdqn_net_set_munchausen(self._h, 1 if on else 0, alpha, tau, clip))
         self.munchausen, self.munchausen_alpha, self.munchausen_tau, self.munchausen_clip = bool(on), alpha, tau, clip
+
+    # ---- --bootstrap_heads: the acting rule of the single-environment paths (the game loops carry theirs: evaluate votes, collect follows heads)
+    def set_acting(self, test):
+        """test=True: act by the majority vote of the Q-heads; False: follow the Q-head of the current episode.  Nothing with one head."""
+        self._boot_vote = bool(test)
+        if self.bootstrap_heads > 1:
+            _lib.check(self._lib.sdqn_net_bootstrap_acting(self._h, int(self._boot_vote), 0))
+
+    def next_episode(self, reset=False):
+        """a fresh episode starts: the episode number, which picks the Q-head to follow, advances (reset=True: returns to 0)"""
+        self._boot_episode = 0 if reset else self._boot_episode + 1
+        if self.bootstrap_heads > 1:
+            _lib.check(self._lib.sdqn_net_bootstrap_acting(self._h, int(self._boot_vote), -1 if reset else 1))
+
+    def acting_action(self, q_row):
+        """the action of the acting rule on one raw Q row [K A] (what act_greedy returns for the buffered state)"""
+        q = np.ascontiguousarray(q_row, dtype=np.float32).reshape(-1)
+        assert q.size == self._net_actions
+        a = C.c_int()
+        _lib.check(self._lib.sdqn_bootstrap_act(_lib.ptr(q, C.c_float), self.bootstrap_heads, self.num_actions, int(self._boot_vote),
+                                                self.bootstrap_seed, 0, self._boot_episode, C.byref(a)))
+        return a.value
 
     def set_target_tau(self, tau):
         """--target_tau: tau in (0, 1] makes every train step of this net end with one soft target update inside the library; 0: off."""
@@ -274,7 +327,18 @@ class DeepQNetwork:
     def predict(self, states):                                     # :174-186
         assert states.shape == ((self.batch_size, self.history_length,) + self.screen_dim)
         st = np.ascontiguousarray(states, dtype=np.uint8)
-        q = np.empty((self.batch_size, self.num_actions), dtype=self._np)
+        q = self._predict_raw(st)
+        if self.bootstrap_heads == 1:
+            return q
+        return q.reshape(self.batch_size, self.bootstrap_heads, self.num_actions).mean(axis=1, dtype=self._np)     # the head-mean [B][A]
+
+    def predict_heads(self, states):
+        """--bootstrap_heads: the Q-values of every Q-head, [B][K][A] (K = 1: predict() with an axis of one)"""
+        assert states.shape == ((self.batch_size, self.history_length,) + self.screen_dim)
+        return self._predict_raw(np.ascontiguousarray(states, dtype=np.uint8)).reshape(self.batch_size, self.bootstrap_heads, self.num_actions)
+
+    def _predict_raw(self, st):
+        q = np.empty((self.batch_size, self._net_actions), dtype=self._np)
         if self._f64:
             _lib.check(self._lib.sdqn_net_predict_f64(self._h, _lib.ptr(st, C.c_uint8), _lib.ptr(q, C.c_double)))
         else:
@@ -283,17 +347,18 @@ class DeepQNetwork:
 
     def predict_one(self, state):
         """Acting-path fast path: Q-values of one state u8[hist,H,W] -> float32[A]; identical to
-        predict(padded_batch)[0] (agent.py:55-61) without computing the zero rows."""
+        predict(padded_batch)[0] (agent.py:55-61) without computing the zero rows.  --bootstrap_heads K > 1: the raw row [K A]
+        (acting_action turns it into an action)."""
         assert state.shape == (self.history_length,) + self.screen_dim
         st = np.ascontiguousarray(state, dtype=np.uint8)
-        q = np.empty((self.num_actions,), dtype=np.float32)
+        q = np.empty((self._net_actions,), dtype=np.float32)
         _lib.check(self._lib.sdqn_net_predict_one(self._h, _lib.ptr(st, C.c_uint8), _lib.ptr(q, C.c_float)))
         return q
 
     def predict_state(self, state_buffer):
         """Acting path with a DeviceStateBuffer: Q-values float32[A] of the buffered state, read in place from HBM
-        (no state upload; same numbers as predict(state_buffer.getStateMinibatch())[0])."""
-        q = np.empty((self.num_actions,), dtype=np.float32)
+        (no state upload; same numbers as predict(state_buffer.getStateMinibatch())[0]; --bootstrap_heads K > 1: the raw row [K A])."""
+        q = np.empty((self._net_actions,), dtype=np.float32)
         _lib.check(self._lib.sdqn_net_predict_state(self._h, state_buffer._h, _lib.ptr(q, C.c_float)))
         return q
 
@@ -368,7 +433,7 @@ class DeepQNetwork:
         if not str(load_path).endswith(".npz"):
             from .neon_compat import read_neon_pickle
             ws, states, A = read_neon_pickle(load_path)
-            assert A == self.num_actions, "snapshot has %d actions, the network %d" % (A, self.num_actions)
+            assert A == self._net_actions, "snapshot has %d actions, the network %d" % (A, self._net_actions)
             for i in range(5):
                 self.set_layer(i, ws[i], 0)
                 if states is not None and self.optimizer == "rmsprop":
@@ -557,7 +622,7 @@ class DeepQNetwork:
         _lib.check(self._lib.sdqn_net_sync(self._h))
 
     def last_q(self):
-        preq = np.empty((self.batch_size, self.num_actions), dtype=np.float32)
+        preq = np.empty((self.batch_size, self._net_actions), dtype=np.float32)
         mq = np.empty((self.batch_size,), dtype=np.float32)
         _lib.check(self._lib.sdqn_net_last_q(self._h, _lib.ptr(preq, C.c_float), _lib.ptr(mq, C.c_float)))
         return preq, mq

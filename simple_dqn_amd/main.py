@@ -47,6 +47,8 @@ _OPTIONS = {
         ("--munchausen_alpha", float, 0.9, dict(help="Munchausen DQN: scale of the log-policy bonus, in [0, 1].")),
         ("--munchausen_tau", float, 0.03, dict(help="Munchausen DQN: temperature of the target net's softmax policy, > 0.")),
         ("--munchausen_clip", float, -1.0, dict(help="Munchausen DQN: lower clip of tau * ln pi(a|s), <= 0.")),
+        ("--bootstrap_heads", int, 1, dict(help="Bootstrapped DQN: this many Q-heads over one shared torso (heads x actions <= 18); acting follows one head per episode while training, the heads' majority vote while testing (1: off).")),
+        ("--bootstrap_mask_probability", float, 1.0, dict(help="Bootstrapped DQN: probability that a Q-head trains on a transition, in (0, 1]; the mask is a fixed function of the replay slot.")),
     ],
     "Backend": [
         ("--backend", str, "hip", dict(choices=["hip", "gpu", "cpu"])), ("--device_id", int, 0),
@@ -176,8 +178,15 @@ def check_munchausen(args):
     return on
 
 
+def check_bootstrap(args, num_actions=None):
+    """--bootstrap_heads: its ranges and what it cannot be combined with, refused before anything touches the device"""
+    from .deepqnetwork import check_bootstrap as check
+    return check(args, num_actions)
+
+
 def run(args):
     train_envs = check_train_envs(args)
+    check_bootstrap(args)
     check_target_tau(args)
     check_munchausen(args)
     check_clip_grad_norm(args)

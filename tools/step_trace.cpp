@@ -56,7 +56,7 @@ hipError_t launch_kernel(int id, const StepArgs& a, const LaunchTune& t, hipStre
   fprintf(g_out, " v=%d hidx=%d\n", t.variant, t.host_idx != nullptr);
   return hipSuccess;
 }
-hipError_t launch_head(const StepArgs& a, const HeadArgs& h, hipStream_t s, bool q_system_scope) {
+hipError_t launch_head(const StepArgs& a, const HeadArgs& h, hipStream_t s, bool q_system_scope, const BootArgs*) {
   fprintf(g_out, "  %s %2d %-11s", sname(s), K_HEAD, "head"); step_fields(a);
   fprintf(g_out, " train=%d nstep=%d q=%s sys=%d\n", h.train, h.nstep, nm(h.q).c_str(), (int)q_system_scope);
   return hipSuccess;

@@ -350,6 +350,17 @@ int sdqn_net_step_structure(sdqn_net_t h, int* structure, int* update);
  * (either order: option "double_dqn" is refused on a net whose Munchausen targets are on). */
 int sdqn_net_set_munchausen(sdqn_net_t h, int on, double alpha, double tau, double clip);
 int sdqn_net_get_munchausen(sdqn_net_t h, int* on, double* alpha, double* tau, double* clip);     /* any pointer may be NULL */
+/* Advantage-learning targets, --advantage_learning alpha / --persistent_advantage (Bellemare, Ostrovski, Guez, Thomas and Munos 2016; DESIGN.md 28;
+ * no reference counterpart).  With qbar = Q(theta-, .), gap(q, a) = max_k q[k] - q[a] and y_std the standard target of the taken action,
+ *   y_AL  = y_std - alpha gap(qbar(s), a)                                       (persistent = 0; on terminal transitions too)
+ *   y_PAL = terminal ? y_AL : max(y_AL, y_std - alpha gap(qbar(s'), a))         (persistent = 1)
+ * in double from the stored Q-values (with option "n_step": R, the done flag and discount^n inside y_std); everything behind y is the standard
+ * step, and sdqn_net_last_q's maxpostq stays max_a qbar(s')[a].  qbar(s) costs one more forward per train step (the target weights on the
+ * prestates, also without a target network).  alpha in [0, 1); alpha = 0 (default) is off: no launch, no argument changes.  Every datatype and
+ * geometry, switchable between steps.  SDQN_ERR_ARG for persistent = 1 with alpha = 0 or with option "n_step" > 1, and for alpha > 0 together
+ * with option "double_dqn", sdqn_net_set_munchausen, sdqn_net_set_bootstrap K > 1 and batch_norm (either order). */
+int sdqn_net_set_advantage_learning(sdqn_net_t h, double alpha, int persistent);
+int sdqn_net_get_advantage_learning(sdqn_net_t h, double* alpha, int* persistent);     /* any pointer may be NULL */
 /* Bootstrapped DQN, --bootstrap_heads K (Osband, Blundell, Pritzel and Van Roy 2016; no reference counterpart).  The network is
  * created with num_actions = K x A outputs (<= 18); output row k A + a is Q-head k, action a, and actions in transitions are < A.  A train step
  * gives every Q-head its own target y_k = r_c + (terminal ? 0 : discount max_a Q_k(theta-, s')[a]) and sets

@@ -130,6 +130,8 @@ SIGNATURES = {
     "sdqn_net_last_grad_norm": (C.c_int, [_vp, _f64p, _f64p]),
     "sdqn_net_set_munchausen": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double, C.c_double]),
     "sdqn_net_get_munchausen": (C.c_int, [_vp, C.POINTER(C.c_int), _f64p, _f64p, _f64p]),
+    "sdqn_net_set_advantage_learning": (C.c_int, [_vp, C.c_double, C.c_int]),
+    "sdqn_net_get_advantage_learning": (C.c_int, [_vp, _f64p, C.POINTER(C.c_int)]),
     "sdqn_net_set_bootstrap": (C.c_int, [_vp, C.c_int, C.c_double, C.c_uint64]),
     "sdqn_net_get_bootstrap": (C.c_int, [_vp, C.POINTER(C.c_int), _f64p, C.POINTER(C.c_uint64)]),
     "sdqn_net_bootstrap_acting": (C.c_int, [_vp, C.c_int, C.c_int]),

@@ -134,6 +134,9 @@ struct sdqn_net_s {
   // --munchausen (sdqn_net_set_munchausen): Munchausen DQN targets; every train step is preceded by a forward of the target
   // net on the prestates (q slot 2: the slots3 re-allocation) and ends its forward with the Munchausen head (HeadArgs::train = 3)
   bool munchausen = false; double mu_alpha = 0.9, mu_tau = 0.03, mu_clip = -1.0;
+  // --advantage_learning / --persistent_advantage (sdqn_net_set_advantage_learning): al_alpha > 0: the same forward in front
+  // of every train step, and the step's forward ends with the advantage-learning head (HeadArgs::train = 5); 0: off, nothing changes
+  double al_alpha = 0.0; bool al_persistent = false;
   // --bootstrap_heads (sdqn_net_set_bootstrap; bootstrap.h): the net's A outputs are boot_K Q-heads of A / boot_K actions.  boot_K > 1:
   // train steps end their forward with the bootstrap head (HeadArgs::train = 4), the acting paths reduce a Q row to the game's actions.
   // boot_q: [B][A / boot_K] acting rows of the game loops (select launch), allocated on first use.  boot_vote / boot_episode: the single-
@@ -256,8 +259,8 @@ struct TailPlan {
 struct StepPlan {
   StepStructure structure; UpdateForm update;
   int fuse_rms;                            // StepArgs::fuse_rms: fc4's RMSProp rides in its weight-gradient tiles
-  int extra_fwd;                           // forward in front of the step (run_extra_forward): 0 none | 1 --munchausen (1, 0) | 2 --double_dqn with --batch_norm (0, 1)
-  int head_train;                          // HeadArgs::train of the step's head: 2 Double DQN, 3 Munchausen, 4 bootstrapped heads, 0: the caller's
+  int extra_fwd;                           // forward in front of the step (run_extra_forward): 0 none | 1 --munchausen / --advantage_learning (1, 0) | 2 --double_dqn with --batch_norm (0, 1)
+  int head_train;                          // HeadArgs::train of the step's head: 2 Double DQN, 3 Munchausen, 4 bootstrapped heads, 5 advantage learning, 0: the caller's
   int nz;                                  // net slots of the step's forward (3: the Double DQN slot rides in it)
   bool side_fc4;                           // overlapped data parallel: fc4's all-reduce + update on g_comm behind bwd3
   LaunchPlan launch[K_WGRADS + 1];         // by kernel id
@@ -288,7 +291,7 @@ float* which_buf(sdqn_net_s* h, int which);
 bool bn_layer_span(sdqn_net_s* h, int which, int layer, float** base, int64_t* n);
 int gen_set(sdqn_net_s* h, int which, int layer, const void* w, int64_t n, bool f64);
 int gen_get(sdqn_net_s* h, int which, int layer, void* w, int64_t n, bool f64);
-int ensure_slots3(sdqn_net_s* h);                                  // room for a third net slot in a1..a4, slab4, q (first use of --double_dqn / --munchausen)
+int ensure_slots3(sdqn_net_s* h);                                  // room for a third net slot in a1..a4, slab4, q (first use of --double_dqn / --munchausen / --advantage_learning)
 int target_blend(sdqn_net_s* h, double tau);                       // one soft target update now (tau in (0, 1]; the caller has joined g_comm)
 int step_blend(sdqn_net_s* h);                                     // what every applied train step ends with: the blend of --target_tau, or nothing
 int gen_step_done(sdqn_net_s* h);                                  // generic path: a train step was enqueued ([clip + deferred update,] counter, step_blend)

@@ -50,6 +50,10 @@ struct GenericNet {
   // --munchausen: Munchausen DQN targets; one more forward (target net, prestates) and the soft-value branch of the TD head
   virtual hipError_t set_munchausen(bool on, double alpha, double tau, double clip) = 0;
   virtual bool munchausen_on() const = 0;
+  // --advantage_learning / --persistent_advantage: the same extra forward as --munchausen and the AL / PAL branch of the TD head;
+  // refused (hipErrorInvalidValue) with double_dqn, munchausen and bootstrap heads, and they with it
+  virtual hipError_t set_advantage_learning(bool on, double alpha, bool persistent) = 0;
+  virtual bool advantage_learning_on() const = 0;
   // --prioritized_replay (sdqn_per.hip): w != nullptr makes the following train steps weight the taken action's row by w[n] and write the
   // new priority (|delta| + eps)^alpha into newp[n]; nullptr: the standard step
   virtual void set_per(const float* w, float* newp, double alpha, double eps) = 0;

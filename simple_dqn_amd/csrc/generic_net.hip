@@ -172,7 +172,8 @@ __global__ void head_kernel(const T* __restrict__ q_on, const T* __restrict__ q_
                             const int64_t* __restrict__ rew, const uint8_t* __restrict__ term, T* __restrict__ dq,
                             T* __restrict__ cost_terms, T* __restrict__ maxq, int N, int A, double discount, double minr, double maxr, T clip,
                             const T* __restrict__ q_sel, const float* __restrict__ per_w, float* __restrict__ per_p, double per_alpha, double per_eps,
-                            int nstep, double gamma_n, const T* __restrict__ q_mu, double mu_alpha, double mu_tau, double mu_clip, const BootArgs boot) {
+                            int nstep, double gamma_n, const T* __restrict__ q_mu, double mu_alpha, double mu_tau, double mu_clip, const BootArgs boot,
+                            double al_alpha, int al_persistent) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
   if (boot.K > 1) {                                                           // --bootstrap_heads: one target per Q-head, masked, all over K
@@ -201,7 +202,8 @@ __global__ void head_kernel(const T* __restrict__ q_on, const T* __restrict__ q_
   }
   T m = q_tg[(int64_t)n * A];
   double bonus = 0.0, V = 0.0;
-  if (q_mu) {                                                                 // --munchausen: soft value of s', scaled log-policy bonus of (s, a)
+  const bool al = q_mu && al_alpha > 0.0;                                     // --advantage_learning: q_mu is qbar of the prestates, the maximum stays the standard one
+  if (q_mu && !al) {                                                                 // --munchausen: soft value of s', scaled log-policy bonus of (s, a)
     V = soft_value(q_tg + (int64_t)n * A, A, mu_tau);
     const double lp = (double)q_mu[(int64_t)n * A + act[n]] - soft_value(q_mu + (int64_t)n * A, A, mu_tau);     // tau ln pi(a|s) <= 0
     bonus = mu_alpha * (lp < mu_clip ? mu_clip : (lp > 0.0 ? 0.0 : lp));
@@ -220,7 +222,18 @@ __global__ void head_kernel(const T* __restrict__ q_on, const T* __restrict__ q_
     r = r < minr ? minr : (r > maxr ? maxr : r);                              // np.clip(rewards, min_reward, max_reward) :136
   }
   double y = term[n] ? r : r + gam * (double)m;                               // :139-143, python float arithmetic
-  if (q_mu) { const double rm = r + bonus; y = term[n] ? rm : rm + gam * V; }   // y = r_c + m + gamma V, V in double (maxq holds its rounded copy)
+  if (q_mu && !al) { const double rm = r + bonus; y = term[n] ? rm : rm + gam * V; }   // y = r_c + m + gamma V, V in double (maxq holds its rounded copy)
+  if (al) {                                                                   // y_AL = y - alpha gap(qbar(s), a), on terminal transitions too
+    const T* qp = q_mu + (int64_t)n * A;
+    double v = (double)qp[0];
+    for (int a = 1; a < A; ++a) { const double x = (double)qp[a]; v = x > v ? x : v; }
+    const double ystd = y;
+    y = ystd - al_alpha * (v - (double)qp[act[n]]);
+    if (al_persistent && !term[n]) {                                          // PAL: or the gap of repeating a in s', whichever target is larger
+      const double yp = ystd - al_alpha * ((double)m - (double)q_tg[(int64_t)n * A + act[n]]);
+      y = yp > y ? yp : y;
+    }
+  }
   const T target = (T)y;                                                      // stored into the backend dtype
   const int at = act[n];
   T d = (T)0;
@@ -305,6 +318,7 @@ class GenericNetT : public GenericNet {
   bool double_dqn = false; T* q_sel = nullptr;          // --double_dqn: Q of the online net on the poststates [B][A]
   bool munchausen = false; T* q_mu = nullptr;           // --munchausen: Q of the target net on the prestates [B][A]
   double mu_alpha = 0.0, mu_tau = 1.0, mu_clip = 0.0;
+  bool advantage = false, al_persistent = false; double al_alpha = 0.0;      // --advantage_learning: shares forward(3, ..) and q_mu with --munchausen (refused together)
   uint8_t* st_states = nullptr; uint8_t* st_small = nullptr;
   std::vector<void*> allocs; std::vector<uint8_t> small_host;
 
@@ -408,11 +422,12 @@ class GenericNetT : public GenericNet {
     GCHK(forward(1, post, B));                                                 // target net on the poststates :119-125
     const bool dd = double_dqn && theta_t != theta;                            // (no target net: Double DQN is standard DQN)
     if (dd) GCHK(forward(2, post, B));                                         // --double_dqn: online net on the poststates
-    if (munchausen) GCHK(forward(3, pre, B));                                  // --munchausen: target net on the prestates (always, also when theta- aliases theta)
+    if (munchausen || advantage) GCHK(forward(3, pre, B));                     // --munchausen / --advantage_learning: target net on the prestates (always, also when theta- aliases theta)
     GCHK(forward(0, pre, B));                                                  // online net on the prestates, tensors kept :128-130
     hipLaunchKernelGGL(head_kernel<T>, dim3((B + 63) / 64), dim3(64), 0, st, (const T*)q, (const T*)(q + (int64_t)B * A), actions, rew, term,
                        dq, cost_terms, maxq, B, A, cfg.discount_rate, cfg.min_reward, cfg.max_reward, (T)cfg.clip_error, (const T*)(dd ? q_sel : nullptr),
-                       per_w, per_p, per_alpha, per_eps, nstep, gamma_n, (const T*)(munchausen ? q_mu : nullptr), mu_alpha, mu_tau, mu_clip, boot);
+                       per_w, per_p, per_alpha, per_eps, nstep, gamma_n, (const T*)((munchausen || advantage) ? q_mu : nullptr), mu_alpha, mu_tau, mu_clip, boot,
+                       advantage ? al_alpha : 0.0, al_persistent ? 1 : 0);
     hipLaunchKernelGGL(cost_kernel<T>, dim3(1), dim3(64), 0, st, (const T*)cost_terms, cost, cost_sum, B);
     // ---- bprop (A8) :162
     GCHK(gemm(ga(dq, 1, A, act[3], 512, 1, g + off[4], A, 512, B)));                                   // gW5 = dq^T @ a4
@@ -540,18 +555,25 @@ class GenericNetT : public GenericNet {
   int nstep = 1; double gamma_n = 0.0;
   bool double_dqn_on() const override { return double_dqn; }
   hipError_t set_double_dqn(bool on) override {
-    if (on && munchausen) return hipErrorInvalidValue;
+    if (on && (munchausen || advantage)) return hipErrorInvalidValue;
     if (on && !q_sel) GCHK(dalloc(&q_sel, (int64_t)B * A));
     double_dqn = on;
     return hipSuccess;
   }
   hipError_t set_munchausen(bool on, double alpha, double tau, double clip) override {
-    if (on && double_dqn) return hipErrorInvalidValue;
+    if (on && (double_dqn || advantage)) return hipErrorInvalidValue;
     if (on && !q_mu) GCHK(dalloc(&q_mu, (int64_t)B * A));
     munchausen = on; mu_alpha = alpha; mu_tau = tau; mu_clip = clip;
     return hipSuccess;
   }
   bool munchausen_on() const override { return munchausen; }
+  hipError_t set_advantage_learning(bool on, double alpha, bool persistent) override {
+    if (on && (double_dqn || munchausen || boot.K > 1 || !(alpha > 0.0 && alpha < 1.0))) return hipErrorInvalidValue;
+    if (on && !q_mu) GCHK(dalloc(&q_mu, (int64_t)B * A));
+    advantage = on; al_alpha = on ? alpha : 0.0; al_persistent = on && persistent;
+    return hipSuccess;
+  }
+  bool advantage_learning_on() const override { return advantage; }
   hipError_t update_target() override {
     if (theta_t != theta) return hipMemcpyAsync(theta_t, theta, (size_t)NP * sizeof(T), hipMemcpyDeviceToDevice, st);
     return hipSuccess;

@@ -27,9 +27,14 @@ struct HeadArgs {
   int train;                    // 0: predict only (z = 0); 1: train step; 2: train step with Double DQN targets (--double_dqn);
                                 // 3: train step with Munchausen targets (--munchausen; sdqn_munchausen.hip);
                                 // 4: train step of a K-head bootstrapped net (--bootstrap_heads; sdqn_bootstrap.hip, its BootArgs beside this struct)
+                                // 5: train step with advantage-learning targets (--advantage_learning; sdqn_advantage.hip)
   // --munchausen, read when train == 3: bonus scale alpha, softmax temperature tau, lower clip l0 of tau ln pi.  They lie
   // in the 24 bytes a retired option's fields left: every later field keeps its offset (see StepArgs::reserved_)
-  double mu_alpha, mu_tau, mu_clip;
+  // --advantage_learning, read when train == 5: the gap scale alpha in (0, 1) and the persistent (PAL) switch.  The two
+  // options are refused together (sdqn_net_set_advantage_learning), so they share mu_alpha's and mu_tau's bytes: no field moves
+  union { double mu_alpha; double al_alpha; };
+  union { double mu_tau; int al_persistent; };
+  double mu_clip;
   // --prioritized_replay (sdqn_per.hip): per_w != nullptr selects the PER head — dq = w clip(delta), cost term 0.5 w delta^2, and
   // per_p[n] = (|delta| + per_eps)^per_alpha, the new priority the next per_step launch writes back
   const float* per_w; float* per_p; double per_alpha, per_eps;
@@ -90,6 +95,7 @@ struct UpdateArgs {
 
 // The kernel-argument layouts are part of the tuned kernels (StepArgs::reserved_, problems.h): frozen where a retired field became reserved bytes
 static_assert(sizeof(HeadArgs) == 160 && offsetof(HeadArgs, train) == 84 && offsetof(HeadArgs, mu_alpha) == 88 && offsetof(HeadArgs, mu_clip) == 104 &&
+              offsetof(HeadArgs, al_alpha) == offsetof(HeadArgs, mu_alpha) && offsetof(HeadArgs, al_persistent) == offsetof(HeadArgs, mu_tau) &&
               offsetof(HeadArgs, per_w) == 112 && offsetof(HeadArgs, per_eps) == 136 &&
               offsetof(HeadArgs, nstep) == 144 && offsetof(HeadArgs, gamma_n) == 152, "HeadArgs layout");
 static_assert(sizeof(PrepArgs) == 344 && offsetof(PrepArgs, idx_in_valid) == 52 && offsetof(PrepArgs, idx_in) == 56 && offsetof(PrepArgs, ns) == 312, "PrepArgs layout");
@@ -162,6 +168,7 @@ hipError_t launch_kernel(int id, const StepArgs& a, const LaunchTune& t, hipStre
 hipError_t launch_head(const StepArgs& a, const HeadArgs& h, hipStream_t s, bool q_system_scope = false, const BootArgs* boot = nullptr);
 hipError_t launch_head_munchausen(const StepArgs& a, const HeadArgs& h, hipStream_t s);     // sdqn_munchausen.hip: what launch_head runs for h.train == 3
 hipError_t launch_head_bootstrap(const StepArgs& a, const HeadArgs& h, const BootArgs& b, hipStream_t s);     // sdqn_bootstrap.hip: what launch_head runs for h.train == 4
+hipError_t launch_head_advantage(const StepArgs& a, const HeadArgs& h, hipStream_t s);      // sdqn_advantage.hip: what launch_head runs for h.train == 5
 // sdqn_bootstrap.hip: [N][K A] Q rows -> [N][A] acting rows (float or double); vote = 0: the slice of Q-head k(e, episodes_e), the int64 episode
 // counter of copy e at recs + e stride + offset; vote = 1: the vote counts
 hipError_t launch_bootstrap_select(const void* q, void* out, bool f64, int N, int K, int A, int vote, uint64_t head_seed,

@@ -552,6 +552,7 @@ extern "C" int sdqn_net_set_munchausen(sdqn_net_t h, int on, double alpha, doubl
   ARGCHK(clip <= 0.0 && clip > -INFINITY, "munchausen_clip %g: must be <= 0", clip);
   if (on) {
     ARGCHK(h->boot_K == 1, "munchausen cannot be combined with bootstrap_heads %d", h->boot_K);
+    ARGCHK(!(h->al_alpha > 0.0), "munchausen cannot be combined with advantage_learning: both targets want q slot 2 for a head of their own");
     ARGCHK(h->cfg.batch_norm == 0.0, "munchausen cannot be combined with batch_norm: inference-mode statistics for its third forward are not defined");
     ARGCHK(h->gen || !h->double_dqn, "munchausen cannot be combined with double_dqn: the Munchausen target has no argmax for the online net to choose");
   }
@@ -566,6 +567,31 @@ extern "C" int sdqn_net_set_munchausen(sdqn_net_t h, int on, double alpha, doubl
 extern "C" int sdqn_net_get_munchausen(sdqn_net_t h, int* on, double* alpha, double* tau, double* clip) {
   ARGCHK(h, "NULL handle");
   if (on) *on = h->munchausen ? 1 : 0; if (alpha) *alpha = h->mu_alpha; if (tau) *tau = h->mu_tau; if (clip) *clip = h->mu_clip;
+  return SDQN_OK;
+}
+
+// ---- --advantage_learning / --persistent_advantage: action-gap-increasing targets (sdqn.h) ----------------------------------
+extern "C" int sdqn_net_set_advantage_learning(sdqn_net_t h, double alpha, int persistent) {
+  ARGCHK(h, "NULL handle");
+  ARGCHK(alpha >= 0.0 && alpha < 1.0, "advantage_learning %g outside [0, 1)", alpha);                    // (a NaN fails the comparison)
+  ARGCHK(persistent == 0 || persistent == 1, "persistent_advantage must be 0 or 1");
+  ARGCHK(!(persistent && alpha == 0.0), "persistent_advantage needs advantage_learning > 0");
+  if (alpha > 0.0) {
+    const bool dd = h->gen ? h->gen->double_dqn_on() : h->double_dqn, mu = h->gen ? h->gen->munchausen_on() : h->munchausen;
+    ARGCHK(!dd, "advantage_learning cannot be combined with double_dqn: q slot 2 is taken by its third forward");
+    ARGCHK(!mu, "advantage_learning cannot be combined with munchausen: both targets want q slot 2 for a head of their own");
+    ARGCHK(h->boot_K == 1, "advantage_learning cannot be combined with bootstrap_heads %d", h->boot_K);
+    ARGCHK(h->cfg.batch_norm == 0.0, "advantage_learning cannot be combined with batch_norm: inference-mode statistics for its third forward are not defined");
+    ARGCHK(!(persistent && h->n_step > 1), "persistent_advantage cannot be combined with n_step %d: it repeats the action in the NEXT state", h->n_step);
+  }
+  if (h->gen) GENCHK(h->gen->set_advantage_learning(alpha > 0.0, alpha, persistent != 0));
+  else if (alpha > 0.0) { int r_ = ensure_slots3(h); if (r_) return r_; }
+  h->al_alpha = alpha; h->al_persistent = persistent != 0;
+  return SDQN_OK;
+}
+extern "C" int sdqn_net_get_advantage_learning(sdqn_net_t h, double* alpha, int* persistent) {
+  ARGCHK(h, "NULL handle");
+  if (alpha) *alpha = h->al_alpha; if (persistent) *persistent = h->al_persistent ? 1 : 0;
   return SDQN_OK;
 }
 
@@ -585,6 +611,7 @@ extern "C" int sdqn_net_set_bootstrap(sdqn_net_t h, int K, double P, uint64_t se
     const bool dd = h->gen ? h->gen->double_dqn_on() : h->double_dqn, mu = h->gen ? h->gen->munchausen_on() : h->munchausen;
     ARGCHK(!dd, "bootstrap_heads %d cannot be combined with double_dqn", K);
     ARGCHK(!mu, "bootstrap_heads %d cannot be combined with munchausen", K);
+    ARGCHK(!(h->al_alpha > 0.0), "bootstrap_heads %d cannot be combined with advantage_learning", K);
   }
   if (h->gen) h->gen->set_bootstrap(K, thresh, bootstrap_mask_seed(seed));
   h->boot_K = K; h->boot_P = P; h->boot_seed = seed; h->boot_thresh = thresh; h->boot_episode = 0;
@@ -625,8 +652,10 @@ extern "C" int sdqn_bootstrap_act(const float* q, int K, int A, int vote, uint64
 extern "C" int sdqn_net_set_option(sdqn_net_t h, const char* name, int value) {
   ARGCHK(h && name, "NULL argument");
   if (!strcmp(name, "double_dqn") && value) ARGCHK(h->boot_K == 1, "double_dqn cannot be combined with bootstrap_heads %d", h->boot_K);
+  if (!strcmp(name, "double_dqn") && value) ARGCHK(!(h->al_alpha > 0.0), "double_dqn cannot be combined with advantage_learning: q slot 2 is taken by its third forward");
   if (!strcmp(name, "n_step")) {                          // n-step returns: sdqn.h
     ARGCHK(value >= 1 && value <= SDQN_MAX_N_STEP, "n_step %d out of range [1, %d]", value, SDQN_MAX_N_STEP);
+    ARGCHK(!(value > 1 && h->al_persistent), "n_step %d cannot be combined with persistent_advantage: it repeats the action in the NEXT state", value);
     h->n_step = value;
     if (h->gen) h->gen->set_nstep(value, nstep_gamma_n(value, h->cfg.discount_rate));
     return SDQN_OK;

@@ -194,7 +194,7 @@ bool ddqn_active(const sdqn_net_s* h) { return h->double_dqn && h->theta_t != h-
 // its wh / wht / w1p copies move to slot-0 position) on state slot `sz` (0 prestates; 1 poststates: post_off frames further in the ring,
 // replay_memory.py:71-72, or the second half of the [2][B][STATE] staging), its Q-values left in q slot 2.  It uses slot 0 of the
 // activation buffers, which the step's own forward overwrites behind it.
-//   --double_dqn with --batch_norm: (0, 1)        --munchausen: (1, 0), qbar of the prestates
+//   --double_dqn with --batch_norm: (0, 1)        --munchausen / --advantage_learning: (1, 0), qbar of the prestates
 static int run_extra_forward(sdqn_net_s* h, const StepArgs& a, int wz, int sz, const LaunchPlan* l) {
   StepArgs p = a; p.nz = 1;
   if (wz) { p.theta[0] = a.theta[1]; p.wh[0] = a.wh[1]; p.wht[0] = a.wht[1]; p.w1p[0] = a.w1p[1]; }
@@ -208,10 +208,12 @@ StepPlan step_plan(const sdqn_net_s* h) {
   p.structure = step_structure(h); p.update = update_form_of(h, p.structure);
   p.fuse_rms = plan_fuse_rms(h, p.update); p.side_fc4 = p.structure == STEP_DP_OVERLAP;
   // the forward: --munchausen (refused together with double_dqn / batch_norm: sdqn_net_set_munchausen) | --double_dqn (comment at ddqn_active)
-  p.extra_fwd = h->munchausen ? 1 : (ddqn_active(h) && h->bn) ? 2 : 0;
+  // | --advantage_learning (refused together with all of them: sdqn_net_set_advantage_learning; alpha = 0 is off: nothing below changes)
+  const bool al = h->al_alpha > 0.0;
+  p.extra_fwd = (h->munchausen || al) ? 1 : (ddqn_active(h) && h->bn) ? 2 : 0;
   // --bootstrap_heads K > 1 (refused together with double_dqn / munchausen / batch_norm: sdqn_net_set_bootstrap): its own head; K = 1: nothing
-  p.head_train = h->boot_K > 1 ? 4 : h->munchausen ? 3 : ddqn_active(h) ? 2 : 0;
-  p.nz = (!h->munchausen && ddqn_active(h) && !h->bn) ? 3 : 2;
+  p.head_train = h->boot_K > 1 ? 4 : h->munchausen ? 3 : al ? 5 : ddqn_active(h) ? 2 : 0;
+  p.nz = (!h->munchausen && !al && ddqn_active(h) && !h->bn) ? 3 : 2;
   LaunchPlan* l = p.launch;
   plan_forward(h, l);
   // The backward.  conv1's weight gradient on packed-bf16 MFMA (sdqn_kernels_r3.hip) in every launch structure (same bits); B < 128 only: in the
@@ -336,6 +338,7 @@ int run_train(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd0, const PrepA
   HeadArgs hd = hd0;
   if (plan.head_train) hd.train = plan.head_train;
   if (plan.head_train == 3) { hd.mu_alpha = h->mu_alpha; hd.mu_tau = h->mu_tau; hd.mu_clip = h->mu_clip; }
+  if (plan.head_train == 5) { hd.al_alpha = h->al_alpha; hd.al_persistent = h->al_persistent ? 1 : 0; }
   if (plan.extra_fwd) { int rc0 = run_extra_forward(h, a, plan.extra_fwd == 1, plan.extra_fwd == 2, plan.launch); if (rc0) return rc0; }
   StepArgs af = a; af.nz = plan.nz;        // the forward's arguments (the backward keeps a: its launches know two slots only)
   int rc = forward(h, af, hd, plan.launch); if (rc) return rc;

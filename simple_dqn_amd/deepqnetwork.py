@@ -33,7 +33,7 @@ MAX_ACTIONS = 18                                          # outputs of the libra
 def check_bootstrap(args, num_actions=None):
     """--bootstrap_heads K / --bootstrap_mask_probability P: K >= 1, K x num_actions <= 18 (when num_actions is known),
     P in (0, 1], and K > 1 with none of --double_dqn, --prioritized_replay, --munchausen, --batch_norm.  Raises ValueError; touches no
-    device.  Returns (K, P)."""
+    device.  Returns (K, P).  --advantage_learning is refused here too, in check_advantage_learning's words."""
     K = getattr(args, "bootstrap_heads", 1)
     K = 1 if K is None else int(K)
     P = float(getattr(args, "bootstrap_mask_probability", 1.0))
@@ -45,15 +45,44 @@ def check_bootstrap(args, num_actions=None):
         raise ValueError("--bootstrap_heads %d x %d actions = %d outputs: the network has at most %d"
                          % (K, int(num_actions), K * int(num_actions), MAX_ACTIONS))
     if K > 1:
-        for flag in ("double_dqn", "prioritized_replay", "munchausen", "batch_norm"):
+        for flag in ("double_dqn", "prioritized_replay", "munchausen", "batch_norm", "advantage_learning"):
             if getattr(args, flag, False):
                 raise ValueError("--bootstrap_heads cannot be combined with --%s (DESIGN.md §27 lists it as a follow-up)" % flag)
     return K, P
 
 
+def check_advantage_learning(args):
+    """--advantage_learning alpha / --persistent_advantage: alpha in [0, 1) (0: off), the persistent form only with
+    alpha > 0 and one-step targets, and alpha > 0 with none of --double_dqn, --munchausen, --bootstrap_heads K > 1, --batch_norm.  Raises
+    ValueError; touches no device.  Returns (alpha, persistent)."""
+    alpha = getattr(args, "advantage_learning", 0.0)
+    alpha = 0.0 if alpha is None else float(alpha)
+    pal = bool(getattr(args, "persistent_advantage", False))
+    if not 0.0 <= alpha < 1.0:                                # (a NaN fails both comparisons)
+        raise ValueError("--advantage_learning %g: must be in [0, 1) (0: off)" % alpha)
+    if pal and alpha == 0.0:
+        raise ValueError("--persistent_advantage needs --advantage_learning > 0: it is a form of the same gap correction")
+    if alpha == 0.0:
+        return alpha, pal
+    if pal and int(getattr(args, "n_step", 1) or 1) > 1:
+        raise ValueError("--persistent_advantage cannot be combined with --n_step %d (--advantage_learning alone can): it repeats the "
+                         "action in the NEXT state" % int(args.n_step))
+    if getattr(args, "double_dqn", False):
+        raise ValueError("--advantage_learning cannot be combined with --double_dqn: q slot 2 is taken by its third forward (DESIGN.md §28 lists it as a follow-up)")
+    if getattr(args, "munchausen", False):
+        raise ValueError("--advantage_learning cannot be combined with --munchausen: both targets want q slot 2 for a head of their own")
+    K = getattr(args, "bootstrap_heads", 1)
+    if (1 if K is None else int(K)) > 1:
+        raise ValueError("--advantage_learning cannot be combined with --bootstrap_heads %d (DESIGN.md §28 lists it as a follow-up)" % int(K))
+    if getattr(args, "batch_norm", False):
+        raise ValueError("--advantage_learning cannot be combined with --batch_norm: inference-mode statistics for its third forward are not defined")
+    return alpha, pal
+
+
 class DeepQNetwork:
     def __init__(self, num_actions, args):
         # Bootstrapped DQN (DESIGN.md §27): K Q-heads over one torso are a library net with K x num_actions outputs, row k A + a = head k, action a
+        al_alpha, al_persistent = check_advantage_learning(args)
         self.bootstrap_heads, self.bootstrap_mask_probability = check_bootstrap(args, num_actions)
         self._net_actions = self.bootstrap_heads * num_actions
         self._lib = _lib.load()
@@ -139,6 +168,10 @@ class DeepQNetwork:
         self.munchausen_clip = float(getattr(args, "munchausen_clip", -1.0))
         if bool(getattr(args, "munchausen", False)):
             self.set_munchausen(True)
+        # advantage-learning targets: the standard target minus alpha x the target net's action gap of the taken action
+        self.advantage_learning, self.persistent_advantage = 0.0, False
+        if al_alpha > 0.0:                                     # (alpha = 0: the library is not told anything)
+            self.set_advantage_learning(al_alpha, al_persistent)
         self.bootstrap_seed = int(getattr(args, "random_seed", 0) or 0) & 0xFFFFFFFFFFFFFFFF
         self._boot_vote, self._boot_episode = False, 0
         if self.bootstrap_heads > 1:                           # (K = 1: the library is not told anything)
@@ -218,6 +251,15 @@ class DeepQNetwork:
         clip = self.munchausen_clip if clip is None else float(clip)
         _lib.check(self._lib.sdqn_net_set_munchausen(self._h, 1 if on else 0, alpha, tau, clip))
         self.munchausen, self.munchausen_alpha, self.munchausen_tau, self.munchausen_clip = bool(on), alpha, tau, clip
+
+    def set_advantage_learning(self, alpha, persistent=None):
+        """--advantage_learning / --persistent_advantage: set the gap scale alpha in [0, 1) between steps (0 switches the option off, and the
+        persistent form with it); persistent left None keeps its value.  Refused with double_dqn, munchausen, bootstrap_heads > 1 and
+        batch_norm, and the persistent form with n_step > 1."""
+        alpha = float(alpha)
+        persistent = (self.persistent_advantage if persistent is None else bool(persistent)) and alpha != 0.0
+        _lib.check(self._lib.sdqn_net_set_advantage_learning(self._h, alpha, 1 if persistent else 0))
+        self.advantage_learning, self.persistent_advantage = alpha, persistent
 
     # ---- --bootstrap_heads: the acting rule of the single-environment paths (the game loops carry theirs: evaluate votes, collect follows heads)
     def set_acting(self, test):

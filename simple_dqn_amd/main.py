@@ -47,6 +47,8 @@ _OPTIONS = {
         ("--munchausen_alpha", float, 0.9, dict(help="Munchausen DQN: scale of the log-policy bonus, in [0, 1].")),
         ("--munchausen_tau", float, 0.03, dict(help="Munchausen DQN: temperature of the target net's softmax policy, > 0.")),
         ("--munchausen_clip", float, -1.0, dict(help="Munchausen DQN: lower clip of tau * ln pi(a|s), <= 0.")),
+        ("--advantage_learning", float, 0.0, dict(help="Advantage learning (Bellemare et al. 2016): subtract this fraction, in [0, 1), of the target net's action gap max_a Q(s, a) - Q(s, a_taken) from the target (0: off; the paper uses 0.9).")),
+        ("--persistent_advantage", _flag, False, dict(help="Persistent advantage learning: on non-terminal transitions take the larger of the advantage-learning target and the one with the poststate's gap of the same action (needs --advantage_learning > 0).")),
         ("--bootstrap_heads", int, 1, dict(help="Bootstrapped DQN: this many Q-heads over one shared torso (heads x actions <= 18); acting follows one head per episode while training, the heads' majority vote while testing (1: off).")),
         ("--bootstrap_mask_probability", float, 1.0, dict(help="Bootstrapped DQN: probability that a Q-head trains on a transition, in (0, 1]; the mask is a fixed function of the replay slot.")),
     ],
@@ -178,6 +180,13 @@ def check_munchausen(args):
     return on
 
 
+def check_advantage_learning(args):
+    """--advantage_learning / --persistent_advantage: their ranges and what they cannot be combined with, refused before anything touches
+    the device"""
+    from .deepqnetwork import check_advantage_learning as check
+    return check(args)
+
+
 def check_bootstrap(args, num_actions=None):
     """--bootstrap_heads: its ranges and what it cannot be combined with, refused before anything touches the device"""
     from .deepqnetwork import check_bootstrap as check
@@ -189,6 +198,7 @@ def run(args):
     check_bootstrap(args)
     check_target_tau(args)
     check_munchausen(args)
+    check_advantage_learning(args)
     check_clip_grad_norm(args)
     check_dynamics(args)
     check_freeway_ticks(args)

@@ -1,0 +1,44 @@
+"""Cost of --advantage_learning: a standard net, an advantage-learning net (alpha 0.9; --persistent for PAL) and a Munchausen
+net trained alternately in one process with train_from_memory (the fused replay loop of the Agent path) on a synthetic-filled ring, at
+B = 32 and B = 256 in float32 and float16.  The Munchausen net is the yardstick: both options pay the same extra forward.  Prints
+steps/s of the three and the ratios AL / standard and AL / Munchausen per configuration (median of the alternated rounds)."""
+import argparse, json, os, random, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np
+import simple_dqn_amd as sd
+from oracle.replay_numpy import synthetic_fill
+from util import make_args
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--steps", type=int, default=200, help="train steps per timed call")
+ap.add_argument("--rounds", type=int, default=7, help="alternated (standard, advantage, Munchausen) rounds")
+ap.add_argument("--datatype", choices=["float32", "float16"], help="one datatype only")
+ap.add_argument("--batch", type=int, help="one batch size only")
+ap.add_argument("--persistent", action="store_true", help="the advantage-learning net runs the persistent form (PAL)")
+ap.add_argument("--net", choices=["all", "standard", "advantage", "munchausen"], default="all", help="one net only (a kernel trace of each form)")
+a = ap.parse_args()
+KW = {"standard": {}, "advantage": dict(advantage_learning=0.9, persistent_advantage=a.persistent), "munchausen": dict(munchausen=True)}
+for dt in ([a.datatype] if a.datatype else ["float32", "float16"]):
+    for B in ([a.batch] if a.batch else [32, 256]):
+        args = make_args(batch_size=B, datatype=dt)
+        mem = sd.ReplayMemory(20000, args)
+        synthetic_fill(mem, 1, num_actions=4)
+        mem.sync_mirror()
+        nets = {k: sd.DeepQNetwork(4, make_args(batch_size=B, datatype=dt, **kw)) for k, kw in KW.items() if a.net in ("all", k)}
+        rate = {k: [] for k in nets}
+        random.seed(1)
+        for r in range(a.rounds + 1):
+            for k, net in nets.items():
+                net.train_from_memory(mem, 10); net.sync()
+                t0 = time.perf_counter()
+                net.train_from_memory(mem, a.steps); net.sync()
+                if r:                                        # (round 0 warms the code objects and the caches up)
+                    rate[k].append(a.steps / (time.perf_counter() - t0))
+        med = {k: float(np.median(v)) for k, v in rate.items()}
+        rec = {"datatype": dt, "batch_size": B, "persistent": bool(a.persistent)}
+        for k, v in med.items():
+            rec[k + "_steps_per_s"], rec[k + "_us"] = round(v, 1), round(1e6 / v, 2)
+        if a.net == "all":
+            rec["ratio_to_standard"] = round(med["advantage"] / med["standard"], 4)
+            rec["ratio_to_munchausen"] = round(med["advantage"] / med["munchausen"], 4)
+        print(json.dumps(rec), flush=True)

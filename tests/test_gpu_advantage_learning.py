@@ -21,7 +21,7 @@ import per_oracle as P
 from oracle.dqn_numpy import xavier_weights
 from oracle.replay_numpy import synthetic_fill
 from test_gpu_double_dqn import _counts, _minibatch
-from test_gpu_munchausen import CONFIGS, _check_grads, _dt, _layers
+from test_gpu_munchausen import CONFIGS, _cfg, _check_grads, _check_priorities, _dt, _layers
 from test_gpu_nstep import GAMMA, MAXR, MINR, _mems, _per_kw
 from util import make_args
 
@@ -42,7 +42,7 @@ def _kw(pal, alpha=ALPHA):
 
 
 def _oracle(name, ws, wt, pal, cls=AO.AdvantageOracle, A=None, **attrs):
-    A0, B, (hist, H, W), kw, _, _ = CONFIGS[name]
+    A0, B, (hist, H, W), kw, _, _ = _cfg(name)
     half = kw.get("datatype") == "float16"
     o = cls(A or A0, batch_size=B, history_length=hist, screen_height=H, screen_width=W, dtype=np.float32 if half else np.float64, weights=ws,
             half_activations=half)
@@ -54,7 +54,7 @@ def _oracle(name, ws, wt, pal, cls=AO.AdvantageOracle, A=None, **attrs):
 
 
 def _net(sd, name, ws, wt, pal, A=None, **extra):
-    A0, B, geom, kw, _, _ = CONFIGS[name]
+    A0, B, geom, kw, _, _ = _cfg(name)
     al = _kw(pal); al.update(extra)
     net = sd.DeepQNetwork(A or A0, make_args(batch_size=B, history_length=geom[0], screen_height=geom[1], screen_width=geom[2], **kw, **al))
     net.set_weights(wt, 1)
@@ -79,7 +79,7 @@ def _discriminates(o, mb, tol, pal, B):
 
 def _setup(sd, name, seed, mb, pal, **extra):
     """net + oracle from different Xavier draws on which mb discriminates (the seed is walked until it does)"""
-    A, B, geom, kw, tol, _ = CONFIGS[name]
+    A, B, geom, kw, tol, _ = _cfg(name)
     for s in range(seed, seed + 20):
         ws, wt = xavier_weights(A, s, _dt(kw), *geom), xavier_weights(A, s + 100, _dt(kw), *geom)
         o = _oracle(name, ws, wt, pal)
@@ -240,7 +240,7 @@ def _ring_seed(name, mem, om, ws, wt, pal, cls, n):
     inside it is gated by summation order, and its whole delta (it reaches every conv layer) comes or goes with it.  Measured with seed 17:
     step 2 holds such a unit — at one set of weights the library stood 1.4e-7 from the float64 oracle and the float32 oracle 7e-3 from it, at
     weights 1e-8 away the library 7e-3 from the float64 oracle."""
-    B = CONFIGS[name][1]
+    B = _cfg(name)[1]
     for seed in range(17, 37):
         o = _oracle(name, ws, wt, pal, cls, n_step=n)
         random.seed(seed)
@@ -257,16 +257,15 @@ def _ring_seed(name, mem, om, ws, wt, pal, cls, n):
     pytest.fail("no sampling seed with a well-conditioned reference")
 
 
-def _composed(sd, n, per, pal):
+def _composed(sd, n, per, pal, name="fp32_b32"):
     """three teacher-forced steps through train_from_memory on a 600-slot ring with terminals against the combined oracle fed the same
-    indexes: Q(pre), maxq, every gradient; PER: the priorities written back"""
-    name = "fp32_b32"
-    A, B, geom, kw, tol, _ = CONFIGS[name]
-    extra = dict(_kw(pal), **(_per_kw() if per else {}))
-    mem, om = _mems(sd, name, n, size=600, **extra)
-    ws, wt = xavier_weights(A, 71, np.float32, *geom), xavier_weights(A, 171, np.float32, *geom)
-    net = sd.DeepQNetwork(A, make_args(batch_size=B, n_step=n, **extra))
-    net.set_weights(wt, 1); net.set_weights(ws, 0)
+    indexes: Q(pre), maxq, every gradient; PER: the priorities written back.  name: a configuration of CONFIGS that
+    tests/test_gpu_nstep.py's CONFIGS (the ring's) holds too"""
+    A, B, geom, kw, tol, _ = _cfg(name)
+    per_kw = _per_kw() if per else {}
+    mem, om = _mems(sd, name, n, size=600, **dict(_kw(pal), **per_kw))
+    ws, wt = xavier_weights(A, 71, _dt(kw), *geom), xavier_weights(A, 171, _dt(kw), *geom)
+    net = _net(sd, name, ws, wt, pal, n_step=n, **per_kw)
     net.set_option("keep_gradients", 1)
     cls = {(False, False): AO.AdvantageOracle, (True, False): AO.AdvantageOracleNStep,
            (False, True): AO.AdvantageOraclePER, (True, True): AO.AdvantageOraclePERNStep}[(n > 1, per)]
@@ -288,14 +287,14 @@ def _composed(sd, n, per, pal):
         mb = N.gather(om, idx, n, GAMMA, MINR, MAXR) if n > 1 else om.gather(idx)
         seen_done = seen_done or bool(np.asarray(mb[4]).any())
         g, _, _, preq = o.gradients(mb)
-        assert (ALPHA * o.last_gap_pre > 100 * tol).mean() >= 0.5
+        far = 100 * tol
+        if kw.get("datatype") == "float16" and far > float(np.median(ALPHA * o.last_gap_pre)):
+            far = 10 * tol                                       # (_discriminates' fallback: 100 x 3e-3 exceeds the median alpha gap)
+        assert (ALPHA * o.last_gap_pre > far).mean() >= 0.5
         _check_q(net, preq, o.last_post_target_q.max(1), tol)
         _check_grads(net, name, g)
         if per:
-            newp = P.new_priority(o.last_abs_delta, 0.6, 1e-6)
-            pr = mem.priorities()
-            last = {int(i): k for k, i in enumerate(idx)}
-            np.testing.assert_allclose(np.array([pr[i] for i in last]), np.array([newp[k] for k in last.values()]), rtol=1e-4)
+            _check_priorities(mem, idx, o, kw)
         o.optimize(g, B)
     assert seen_done
 

@@ -37,6 +37,11 @@ CASES = [("fp32_b32", 2, 2), ("fp32_b32", 4, 2), ("fp32_b32", 3, 6), ("fp32_b128
          ("fp16_b32", 3, 6), ("fp16_b128", 3, 6), ("f64_b32", 3, 6), ("f32_generic", 2, 2)]
 
 
+def _regime(regime):
+    """a key of REGIMES, or a regime of its form itself (tests/test_gpu_option_head_edges.py passes its own)"""
+    return REGIMES[regime] if isinstance(regime, str) else regime
+
+
 @pytest.fixture(scope="module")
 def sd():
     import simple_dqn_amd
@@ -48,13 +53,13 @@ def _dt(kw):
 
 
 def _args(regime, **extra):
-    B, (hist, H, W), kw = REGIMES[regime][:3]
+    B, (hist, H, W), kw = _regime(regime)[:3]
     return make_args(batch_size=B, history_length=hist, screen_height=H, screen_width=W, **dict(kw, **extra))
 
 
 def _setup(sd, regime, A, K, seed=11, n=1, **extra):
     """(net, oracle, product ring, oracle ring, valid indexes): a full, wrapped 300-slot ring with terminals; different draws for theta / theta-"""
-    B, (hist, H, W), kw = REGIMES[regime][:3]
+    B, (hist, H, W), kw = _regime(regime)[:3]
     args = _args(regime, bootstrap_heads=K, n_step=n, **extra)
     mem, om = sd.ReplayMemory(SIZE, args), ReplayOracle(SIZE, H, W, hist, B)
     for m in (mem, om):
@@ -82,7 +87,7 @@ def _batch(om, valid, B, seed, n=1, must=None):
 
 def _check_grads(net, regime, g):
     """the rules of tests/test_gpu_munchausen.py::_check_grads"""
-    B, _, kw = REGIMES[regime][:3]
+    B, _, kw = _regime(regime)[:3]
     for i in range(5):
         gg, ref = np.asarray(net.get_layer(i, 3), np.float64), np.asarray(g[i], np.float64)
         rel = np.linalg.norm(gg - ref) / max(np.linalg.norm(ref), 1e-300)
@@ -98,7 +103,7 @@ def _check_grads(net, regime, g):
 
 
 def _check_step(net, o, regime, g, cost_ref, preq, cost):
-    tol = max(REGIMES[regime][3], 1e-6)
+    tol = max(_regime(regime)[3], 1e-6)
     K, A = o.heads, o.game_actions
     q, mq = net.last_q()
     scale = max(1.0, float(np.abs(preq).max()))

@@ -35,6 +35,11 @@ ALPHA, TAU, L0 = 0.9, 0.03, -0.05
 MU = dict(munchausen=True, munchausen_alpha=ALPHA, munchausen_tau=TAU, munchausen_clip=L0)
 
 
+def _cfg(name):
+    """a key of CONFIGS, or a configuration of its form itself (tests/test_gpu_option_head_edges.py passes its own)"""
+    return CONFIGS[name] if isinstance(name, str) else name
+
+
 @pytest.fixture(scope="module")
 def sd():
     import simple_dqn_amd
@@ -45,11 +50,12 @@ def _dt(kw):
     return np.float64 if kw.get("datatype") == "float64" else np.float32
 
 
-def _oracle(name, ws, wt, cls=MO.MunchausenOracle, **attrs):
-    A, B, (hist, H, W), kw, _, _ = CONFIGS[name]
-    o = cls(A, batch_size=B, history_length=hist, screen_height=H, screen_width=W, dtype=_dt(kw), weights=ws,
+def _oracle(name, ws, wt, cls=MO.MunchausenOracle, dtype=None, **attrs):
+    """dtype: the oracle's precision where it is not the net's (the float64 oracle of a float32 net)"""
+    A, B, (hist, H, W), kw, _, _ = _cfg(name)
+    o = cls(A, batch_size=B, history_length=hist, screen_height=H, screen_width=W, dtype=dtype or _dt(kw), weights=ws,
             half_activations=kw.get("datatype") == "float16")
-    o.Wt = [w.copy() for w in wt]
+    o.Wt = [np.array(w, dtype=o.dtype) for w in wt]
     o.munchausen_alpha, o.munchausen_tau, o.munchausen_clip = ALPHA, TAU, L0
     for k, v in attrs.items():
         setattr(o, k, v)
@@ -57,7 +63,7 @@ def _oracle(name, ws, wt, cls=MO.MunchausenOracle, **attrs):
 
 
 def _net(sd, name, ws, wt, A=None, **extra):
-    A0, B, geom, kw, _, _ = CONFIGS[name]
+    A0, B, geom, kw, _, _ = _cfg(name)
     mu = dict(MU); mu.update(extra)
     net = sd.DeepQNetwork(A or A0, make_args(batch_size=B, history_length=geom[0], screen_height=geom[1], screen_width=geom[2], **kw, **mu))
     net.set_weights(wt, 1)
@@ -86,7 +92,7 @@ def _discriminates(o, mb, tol):
 
 def _setup(sd, name, seed, mb, **extra):
     """net + oracle from different Xavier draws on which mb discriminates (the seed is walked until it does)"""
-    A, B, geom, kw, tol, _ = CONFIGS[name]
+    A, B, geom, kw, tol, _ = _cfg(name)
     for s in range(seed, seed + 20):
         ws, wt = xavier_weights(A, s, _dt(kw), *geom), xavier_weights(A, s + 100, _dt(kw), *geom)
         o = _oracle(name, ws, wt)
@@ -96,10 +102,10 @@ def _setup(sd, name, seed, mb, **extra):
     pytest.fail("no pair of draws on which the Munchausen targets discriminate")
 
 
-def _check_grads(net, name, g):
+def _check_grads(net, name, g, layers=range(5)):
     """the rules of tests/test_gpu_double_dqn.py::_check_grads (B >= 128 float32: tests/test_gpu_nstep.py's relative norm, for its reason)"""
-    A, B, _, kw, _, _ = CONFIGS[name]
-    for i in range(5):
+    A, B, _, kw, _, _ = _cfg(name)
+    for i in layers:
         gg = np.asarray(net.get_layer(i, 3), np.float64)
         ref = np.asarray(g[i], np.float64)
         rel = np.linalg.norm(gg - ref) / max(np.linalg.norm(ref), 1e-300)
@@ -217,23 +223,35 @@ def test_exact_ties_and_all_terminal(sd, name):
     _check_grads(net, name, g)
 
 
-def _composed(sd, n, per):
+def _check_priorities(mem, idx, o, kw):
+    """the priorities written back for idx (the last occurrence of a slot wins) against those of the oracle's |delta|; float16: the
+    relative 3e-3 tests/test_gpu_per.py::test_one_step holds float16 priorities to at B <= 32"""
+    newp = P.new_priority(o.last_abs_delta, 0.6, 1e-6)
+    pr = mem.priorities()
+    last = {int(i): k for k, i in enumerate(idx)}
+    rt = 3e-3 if kw.get("datatype") == "float16" else 1e-4
+    np.testing.assert_allclose(np.array([pr[i] for i in last]), np.array([newp[k] for k in last.values()]), rtol=rt)
+
+
+def _composed(sd, n, per, name="fp32_b32", dtype=None, seed=17):
     """three teacher-forced steps through train_from_memory on a 600-slot ring with terminals against the combined oracle fed the same
-    indexes: Q(pre), the soft value, every gradient; PER: the priorities written back"""
-    name = "fp32_b32"
-    A, B, geom, kw, tol, _ = CONFIGS[name]
-    extra = dict(MU, **(_per_kw() if per else {}))
-    mem, om = _mems(sd, name, n, size=600, **extra)
-    ws, wt = xavier_weights(A, 71, np.float32, *geom), xavier_weights(A, 171, np.float32, *geom)
-    net = sd.DeepQNetwork(A, make_args(batch_size=B, n_step=n, **extra))
-    net.set_weights(wt, 1); net.set_weights(ws, 0)
+    indexes: Q(pre), the soft value, every gradient; PER: the priorities written back.  name: a configuration of CONFIGS that
+    tests/test_gpu_nstep.py's CONFIGS (the ring's) holds too; dtype: _oracle's; seed: of the sampling"""
+    A, B, geom, kw, tol, _ = _cfg(name)
+    per_kw = _per_kw() if per else {}
+    mem, om = _mems(sd, name, n, size=600, **dict(MU, **per_kw))
+    ws, wt = xavier_weights(A, 71, _dt(kw), *geom), xavier_weights(A, 171, _dt(kw), *geom)
+    net = _net(sd, name, ws, wt, n_step=n, **per_kw)
     net.set_option("keep_gradients", 1)
     cls = {(False, False): MO.MunchausenOracle, (True, False): MO.MunchausenOracleNStep,
            (False, True): MO.MunchausenOraclePER, (True, True): MO.MunchausenOraclePERNStep}[(n > 1, per)]
-    o = _oracle(name, ws, wt, cls, n_step=n)
-    random.seed(17)
+    o = _oracle(name, ws, wt, cls, dtype=dtype, n_step=n)
+    random.seed(seed)
     seen_done = False
     for s in range(3):
+        if o.dtype != net._np:                                   # (tests/test_gpu_advantage_learning.py::_force: both sides hold the same numbers)
+            o.W = [np.asarray(w, net._np).astype(o.dtype) for w in o.W]
+            o.S = [np.asarray(x, net._np).astype(o.dtype) for x in o.S]
         net.set_weights(o.W, 0)
         for i in range(5):
             net.set_layer(i, o.S[i], 2)
@@ -253,10 +271,7 @@ def _composed(sd, n, per):
         _check_q(net, o, preq, tol)
         _check_grads(net, name, g)
         if per:
-            newp = P.new_priority(o.last_abs_delta, 0.6, 1e-6)
-            pr = mem.priorities()
-            last = {int(i): k for k, i in enumerate(idx)}
-            np.testing.assert_allclose(np.array([pr[i] for i in last]), np.array([newp[k] for k in last.values()]), rtol=1e-4)
+            _check_priorities(mem, idx, o, kw)
         o.optimize(g, B)
     assert seen_done
 

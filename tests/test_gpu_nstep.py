@@ -28,6 +28,11 @@ CONFIGS = {
 }
 
 
+def _cfg(name):
+    """a key of CONFIGS, or a configuration of its form itself (tests/test_gpu_option_head_edges.py passes its own)"""
+    return CONFIGS[name] if isinstance(name, str) else name
+
+
 @pytest.fixture(scope="module")
 def sd():
     import simple_dqn_amd
@@ -39,13 +44,13 @@ def _dt(kw):
 
 
 def _args(name, n, **extra):
-    A, B, (hist, H, W), kw, _, _ = CONFIGS[name]
+    A, B, (hist, H, W), kw, _, _ = _cfg(name)
     return make_args(batch_size=B, history_length=hist, screen_height=H, screen_width=W, n_step=n, **kw, **extra)
 
 
 def _mems(sd, name, n, size=600, seed=3, p_term=0.05, **extra):
     """a product memory and an oracle ring with the same content: full, wrapped (current inside), terminals every ~20 slots"""
-    A, B, (hist, H, W), kw, _, _ = CONFIGS[name]
+    A, B, (hist, H, W), kw, _, _ = _cfg(name)
     mem = sd.ReplayMemory(size, _args(name, n, **extra))
     om = ReplayOracle(size, H, W, hist, B)
     for m in (mem, om):
@@ -58,14 +63,14 @@ def _mems(sd, name, n, size=600, seed=3, p_term=0.05, **extra):
 
 
 def _net(sd, name, n, ws, wt, **extra):
-    net = sd.DeepQNetwork(CONFIGS[name][0], _args(name, n, **extra))
+    net = sd.DeepQNetwork(_cfg(name)[0], _args(name, n, **extra))
     net.set_weights(wt, 1)
     net.set_weights(ws, 0)
     return net
 
 
 def _oracle(name, n, ws, wt, cls=None):
-    A, B, (hist, H, W), kw, _, _ = CONFIGS[name]
+    A, B, (hist, H, W), kw, _, _ = _cfg(name)
     if cls is None:
         cls = N.NStepOracleBN if kw.get("batch_norm") else N.NStepOracle
     o = cls(A, batch_size=B, history_length=hist, screen_height=H, screen_width=W, dtype=_dt(kw), weights=ws,
@@ -76,7 +81,7 @@ def _oracle(name, n, ws, wt, cls=None):
 
 
 def _weights(name, s):
-    A, _, geom, kw, _, _ = CONFIGS[name]
+    A, _, geom, kw, _, _ = _cfg(name)
     return xavier_weights(A, s, _dt(kw), *geom), xavier_weights(A, s + 100, _dt(kw), *geom)
 
 
@@ -86,7 +91,7 @@ def _sample(mem, n, seed):
 
 
 def _check_grads(net, name, g):
-    kw = CONFIGS[name][3]
+    kw = _cfg(name)[3]
     for i in range(5):
         gg = np.asarray(net.get_layer(i, 3), np.float64)
         ref = np.asarray(g[i], np.float64)
@@ -94,7 +99,7 @@ def _check_grads(net, name, g):
             assert np.linalg.norm(gg - ref) / max(np.linalg.norm(ref), 1e-300) < 1e-11, i
         elif kw.get("datatype") == "float16":
             assert np.linalg.norm(gg - ref) / max(1e-12, np.linalg.norm(ref)) < 5e-2, i
-        elif CONFIGS[name][1] >= 128:
+        elif _cfg(name)[1] >= 128:
             # float32 B = 256: a Rectlin gate of the throughput routines that lands on the other side of zero moves single elements of
             # the conv gradients far past the element bound, in the standard step as well (tests/test_gpu_double_dqn.py,
             # test_ten_teacher_forced_steps): held to a relative norm instead (conv1 measured 4.7e-3 here; a wrong frame would be O(1))

@@ -383,6 +383,28 @@ int sdqn_bootstrap_head_of(uint64_t seed, int K, int64_t copy, int64_t episode, 
 /* the acting rule on one raw Q row q[K A]: vote = 1 the majority vote, 0 the greedy action of Q-head sdqn_bootstrap_head_of(seed, K, copy, episode)
  * (first maximum; a NaN counts as one) */
 int sdqn_bootstrap_act(const float* q, int K, int A, int vote, uint64_t seed, int64_t copy, int64_t episode, int* action);
+/* Quantile-regression DQN, --quantiles N (Dabney, Rowland, Bellemare and Munos 2018; no reference counterpart).  The network is
+ * created with num_actions = N x A outputs (<= 18); output row j A + a is quantile j of action a at the midpoint tau_j = (2 j + 1) / (2 N),
+ * and actions in transitions are < A.  With m(a) = (sum_j theta_j(theta-, s')[a]) / N and a* its first maximum, a train step sets
+ *   T_j' = r_c + (terminal ? 0 : discount theta_j'(theta-, s')[a*]),   delta_jj' = theta_j(theta, s)[a_n] - T_j',   kappa = clip_error (> 0),
+ *   dq[j A + a_n] = (sum_j' |tau_j - 1[delta_jj' > 0]| clip(delta_jj', -kappa, kappa) / kappa) / N^2,
+ *   cost term = (sum_jj' |tau_j - 1[delta_jj' > 0]| L_kappa(delta_jj') / kappa) / N^2 (L_kappa: the Huber function),   maxpostq (sdqn_net_last_q) = m(a*)
+ * (option "n_step": R, the done flag and discount^n in their places).  The mean over the N^2 pairs divides the paper's loss by N once more,
+ * so one learning rate serves every N.  Acting: the game loops and sdqn_net_act_greedy take the first maximum of the action values
+ * Q(s, a) = (sum_j theta_j(s)[a]) / N, collecting and evaluating alike.  N = 1 (default) is the network without any of this: no launch,
+ * no argument changes.  N in 1..18 dividing num_actions; N > 1 is SDQN_ERR_ARG with clip_error <= 0 and together with option "double_dqn",
+ * sdqn_net_set_munchausen, sdqn_net_set_advantage_learning, sdqn_net_set_bootstrap K > 1, batch_norm and a prioritized replay memory (either order). */
+int sdqn_net_set_quantiles(sdqn_net_t h, int N);
+int sdqn_net_get_quantiles(sdqn_net_t h, int* N);     /* the pointer may be NULL */
+/* what the last train step's head left (N > 1; sync): targets [B][N] = T_j' as stored in the network's precision, dq [B][N A]; widened to
+ * double on every path; either pointer may be NULL */
+int sdqn_net_last_quantile_step(sdqn_net_t h, double* targets, double* dq);
+/* the rule on one sample, host side (no device), from its two stored Q rows q_pre_row / q_post_row [N A]: reward is r_c (n_step: R), gamma the
+ * discount (discount^n); dq_out [N A] and *cost_out receive what the train step's head writes for that sample, bit for bit */
+int sdqn_quantile_loss(int N, int A, double kappa, const float* q_pre_row, const float* q_post_row, int action, double reward, int terminal,
+                       double gamma, float* dq_out, float* cost_out);
+/* the acting rule on one raw Q row q[N A]: the first maximum of the quantile means (a NaN counts as one) */
+int sdqn_quantile_act(const float* q, int N, int A, int* action);
 /* option "double_dqn" (0 default / 1, any configuration, switchable between steps): Double DQN targets (van Hasselt, Guez and Silver
  * 2016): the online net picks each poststate's action, the target net values it (see sdqn_net_last_q).  The online net's forward on
  * the poststates rides as a third net slot in the step's own forward launches (batch_norm: a forward of its own in front of the step,

@@ -55,6 +55,9 @@ class Agent:
         self.callback = None
         # --bootstrap_heads: the net follows one Q-head per episode while collecting and votes while testing
         self._boot = getattr(deep_q_network, "bootstrap_heads", 1) > 1
+        # --quantiles: the net acts on the mean over its quantiles, training and testing alike; like the Q-heads' rule it
+        # turns a raw row of the net into an action (net.acting_action), but it has no mode and no episode bookkeeping
+        self._reduced_acting = self._boot or getattr(deep_q_network, "quantiles", 1) > 1
         self._per = getattr(replay_memory, "prioritized", False)
         if self._per:
             self._beta0, self._beta_steps = float(args.priority_beta), int(args.priority_beta_steps)
@@ -88,7 +91,7 @@ class Agent:
             q = self.net.predict_one(self.buf.getState())             # same numbers as predict(padded batch)[0]
         else:
             q = self.net.predict(self.buf.getStateMinibatch())[0]     # the reference's padded minibatch, agent.py:55-58
-        if self._boot:
+        if self._reduced_acting:
             return self.net.acting_action(q)
         assert len(q) == self.num_actions
         return int(np.argmax(q))

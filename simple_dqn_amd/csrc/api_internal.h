@@ -143,6 +143,11 @@ struct sdqn_net_s {
   // environment acting paths (sdqn_net_act_greedy) — majority vote (testing) or the Q-head of copy 0's episode boot_episode (collecting)
   int boot_K = 1; double boot_P = 1.0; uint64_t boot_seed = 0, boot_thresh = 1ull << 53; void* boot_q = nullptr;
   int boot_vote = 0; int64_t boot_episode = 0;
+  // --quantiles (sdqn_net_set_quantiles; quantile.h): the net's A outputs are quant_N quantiles of A / quant_N actions.  quant_N > 1:
+  // train steps end their forward with the quantile head (HeadArgs::train = 6), the acting paths reduce a Q row to its mean over the
+  // quantiles (the game loops: one launch into boot_q, which the two options — refused together — share).  quant_targets: [B][quant_N]
+  // the last step's targets (tuned path; sdqn_net_debug_read "quantile_targets"), allocated by the setter
+  int quant_N = 1; float* quant_targets = nullptr;
   int n_step = 1;                          // --n_step (option "n_step"): poststate frame offset of the ring paths, n-step head
   double target_tau = 0.0;                 // --target_tau (sdqn_net_set_target_tau): > 0: every train step is followed by one soft target update
   // --clip_grad_norm (sdqn_net_set_clip_grad_norm): > 0: the flat gradient is scaled to this global L2 norm (of the MEAN
@@ -260,7 +265,7 @@ struct StepPlan {
   StepStructure structure; UpdateForm update;
   int fuse_rms;                            // StepArgs::fuse_rms: fc4's RMSProp rides in its weight-gradient tiles
   int extra_fwd;                           // forward in front of the step (run_extra_forward): 0 none | 1 --munchausen / --advantage_learning (1, 0) | 2 --double_dqn with --batch_norm (0, 1)
-  int head_train;                          // HeadArgs::train of the step's head: 2 Double DQN, 3 Munchausen, 4 bootstrapped heads, 5 advantage learning, 0: the caller's
+  int head_train;                          // HeadArgs::train of the step's head: 2 Double DQN, 3 Munchausen, 4 bootstrapped heads, 5 advantage learning, 6 quantiles, 0: the caller's
   int nz;                                  // net slots of the step's forward (3: the Double DQN slot rides in it)
   bool side_fc4;                           // overlapped data parallel: fc4's all-reduce + update on g_comm behind bwd3
   LaunchPlan launch[K_WGRADS + 1];         // by kernel id
@@ -295,7 +300,7 @@ int ensure_slots3(sdqn_net_s* h);                                  // room for a
 int target_blend(sdqn_net_s* h, double tau);                       // one soft target update now (tau in (0, 1]; the caller has joined g_comm)
 int step_blend(sdqn_net_s* h);                                     // what every applied train step ends with: the blend of --target_tau, or nothing
 int gen_step_done(sdqn_net_s* h);                                  // generic path: a train step was enqueued ([clip + deferred update,] counter, step_blend)
-inline int game_actions(const sdqn_net_s* h) { return h->A / h->boot_K; }   // the actions a transition may hold (--bootstrap_heads: A is K times that)
+inline int game_actions(const sdqn_net_s* h) { return h->A / (h->boot_K * h->quant_N); }   // the actions a transition may hold (--bootstrap_heads / --quantiles: A is K / N times that)
 inline bool clip_on(const sdqn_net_s* h) { return h->clip_grad_norm > 0.0; }
 int clip_gradient(sdqn_net_s* h, double bsz);                      // --clip_grad_norm: the two launches on g between update modes 1 and 2 (nothing when off)
 StepPlan step_plan(const sdqn_net_s* h);

@@ -11,6 +11,7 @@
 #include "../../include/sdqn.h"
 #include "problems.h"          // NStepArgs
 #include "bootstrap.h"         // BootArgs
+#include "quantile.h"          // QuantArgs
 
 namespace sdqn {
 
@@ -61,6 +62,9 @@ struct GenericNet {
   // names the [B] ring indexes of the NEXT step's samples (device-readable; copied on the stream) or, nullptr, none (tuple path, P = 1)
   virtual void set_bootstrap(int K, uint64_t thresh, uint64_t mask_seed) = 0;
   virtual hipError_t boot_idx(const int64_t* idx) = 0;
+  // --quantiles (quantile.h): N > 1 arms the quantile branch of the TD head (the net has N x game-A outputs; clip_error is kappa)
+  virtual hipError_t set_quantiles(int N) = 0;
+  virtual hipError_t last_quantile_step(double* targets, double* dq) = 0;      // the last train step's [B][N] targets and [B][A] dq row, as doubles
   // --n_step: n > 1 makes the train steps read rew as the n-step returns (float64 bits) and term as the done flags, and
   // bootstrap with gamma_n; n = 1: the standard step
   virtual void set_nstep(int n, double gamma_n) = 0;

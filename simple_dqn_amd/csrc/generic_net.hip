@@ -173,9 +173,18 @@ __global__ void head_kernel(const T* __restrict__ q_on, const T* __restrict__ q_
                             T* __restrict__ cost_terms, T* __restrict__ maxq, int N, int A, double discount, double minr, double maxr, T clip,
                             const T* __restrict__ q_sel, const float* __restrict__ per_w, float* __restrict__ per_p, double per_alpha, double per_eps,
                             int nstep, double gamma_n, const T* __restrict__ q_mu, double mu_alpha, double mu_tau, double mu_clip, const BootArgs boot,
-                            double al_alpha, int al_persistent) {
+                            double al_alpha, int al_persistent, const QuantArgs quant, T* __restrict__ q_targets) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
+  if (quant.N > 1) {                                                          // --quantiles: quantile.h's rule on this sample's two rows; clip is kappa
+    const int GA = quant.A, at = act[n] < GA ? act[n] : GA - 1;
+    double r, gam = discount;
+    if (nstep > 1) { r = __builtin_bit_cast(double, rew[n]); gam = gamma_n; }
+    else { r = (double)rew[n]; r = r < minr ? minr : (r > maxr ? maxr : r); }
+    cost_terms[n] = quantile_sample<T>(q_on + (int64_t)n * A, q_tg + (int64_t)n * A, quant.N, GA, at, r, term[n], gam, clip, dq + (int64_t)n * A,
+                                         q_targets ? q_targets + (int64_t)n * quant.N : nullptr, maxq + n);
+    return;
+  }
   if (boot.K > 1) {                                                           // --bootstrap_heads: one target per Q-head, masked, all over K
     const int K = boot.K, GA = boot.A, at = act[n] < GA ? act[n] : GA - 1;
     double r, gam = discount;
@@ -427,7 +436,7 @@ class GenericNetT : public GenericNet {
     hipLaunchKernelGGL(head_kernel<T>, dim3((B + 63) / 64), dim3(64), 0, st, (const T*)q, (const T*)(q + (int64_t)B * A), actions, rew, term,
                        dq, cost_terms, maxq, B, A, cfg.discount_rate, cfg.min_reward, cfg.max_reward, (T)cfg.clip_error, (const T*)(dd ? q_sel : nullptr),
                        per_w, per_p, per_alpha, per_eps, nstep, gamma_n, (const T*)((munchausen || advantage) ? q_mu : nullptr), mu_alpha, mu_tau, mu_clip, boot,
-                       advantage ? al_alpha : 0.0, al_persistent ? 1 : 0);
+                       advantage ? al_alpha : 0.0, al_persistent ? 1 : 0, quant, q_targets);
     hipLaunchKernelGGL(cost_kernel<T>, dim3(1), dim3(64), 0, st, (const T*)cost_terms, cost, cost_sum, B);
     // ---- bprop (A8) :162
     GCHK(gemm(ga(dq, 1, A, act[3], 512, 1, g + off[4], A, 512, B)));                                   // gW5 = dq^T @ a4
@@ -544,6 +553,18 @@ class GenericNetT : public GenericNet {
   void set_nstep(int n, double g) override { nstep = n; gamma_n = g; }
   BootArgs boot = {1, 0, 1ull << 53, 0, nullptr}; int64_t* boot_idx_buf = nullptr;
   void set_bootstrap(int K, uint64_t thresh, uint64_t mask_seed) override { boot.K = K; boot.A = A / K; boot.thresh = thresh; boot.mask_seed = mask_seed; boot.idx = nullptr; }
+  QuantArgs quant = {1, 0, nullptr}; T* q_targets = nullptr;          // q_targets: [B][N] the last step's targets in T (quant.targets is the tuned path's float buffer)
+  hipError_t set_quantiles(int N) override {
+    if (N > 1 && !q_targets) GCHK(dalloc(&q_targets, (int64_t)B * A));
+    quant.N = N; quant.A = A / N;
+    return hipSuccess;
+  }
+  hipError_t last_quantile_step(double* targets, double* dq_host) override {
+    if (quant.N < 2 || !q_targets) return hipErrorInvalidValue;
+    if (targets) GCHK(fetch(q_targets, (int64_t)B * quant.N, targets, true));
+    if (dq_host) GCHK(fetch(dq, (int64_t)B * A, dq_host, true));
+    return hipSuccess;
+  }
   hipError_t boot_idx(const int64_t* idx) override {
     boot.idx = nullptr;
     if (!idx) return hipSuccess;
@@ -568,7 +589,7 @@ class GenericNetT : public GenericNet {
   }
   bool munchausen_on() const override { return munchausen; }
   hipError_t set_advantage_learning(bool on, double alpha, bool persistent) override {
-    if (on && (double_dqn || munchausen || boot.K > 1 || !(alpha > 0.0 && alpha < 1.0))) return hipErrorInvalidValue;
+    if (on && (double_dqn || munchausen || boot.K > 1 || quant.N > 1 || !(alpha > 0.0 && alpha < 1.0))) return hipErrorInvalidValue;
     if (on && !q_mu) GCHK(dalloc(&q_mu, (int64_t)B * A));
     advantage = on; al_alpha = on ? alpha : 0.0; al_persistent = on && persistent;
     return hipSuccess;

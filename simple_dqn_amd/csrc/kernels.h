@@ -8,6 +8,7 @@
 #include "launch.h"
 #include "launch_route.h"
 #include "bootstrap.h"
+#include "quantile.h"
 
 namespace sdqn {
 
@@ -28,6 +29,8 @@ struct HeadArgs {
                                 // 3: train step with Munchausen targets (--munchausen; sdqn_munchausen.hip);
                                 // 4: train step of a K-head bootstrapped net (--bootstrap_heads; sdqn_bootstrap.hip, its BootArgs beside this struct)
                                 // 5: train step with advantage-learning targets (--advantage_learning; sdqn_advantage.hip)
+                                // 6: train step of an N-quantile net (--quantiles; sdqn_quantile.hip, its QuantArgs beside this struct;
+                                //    clip_error is the Huber threshold kappa there).  launch_route.h: HEAD_QUANTILE
   // --munchausen, read when train == 3: bonus scale alpha, softmax temperature tau, lower clip l0 of tau ln pi.  They lie
   // in the 24 bytes a retired option's fields left: every later field keeps its offset (see StepArgs::reserved_)
   // --advantage_learning, read when train == 5: the gap scale alpha in (0, 1) and the persistent (PAL) switch.  The two
@@ -164,8 +167,13 @@ hipError_t launch_r3(const Route& r, int id, const StepArgs& a, const LaunchTune
 hipError_t launch_bt(const Route& r, int id, const StepArgs& a, const LaunchTune& t, hipStream_t s);       // sdqn_kernels_bt.hip: block tiles and the hand-written kernels beside them
 hipError_t launch_ss(const Route& r, int id, const StepArgs& a, const LaunchTune& t, hipStream_t s);       // sdqn_kernels_ss.hip: sample-stationary convolution chains
 hipError_t launch_kernel(int id, const StepArgs& a, const LaunchTune& t, hipStream_t s);     // the GEMM-shaped stages (single or multi-problem launches)
-// q_system_scope: h.q is mapped host memory (acting path); boot: what h.train == 4 (--bootstrap_heads) needs beside the two structs (refused without it)
-hipError_t launch_head(const StepArgs& a, const HeadArgs& h, hipStream_t s, bool q_system_scope = false, const BootArgs* boot = nullptr);
+// q_system_scope: h.q is mapped host memory (acting path); boot / quant: what h.train == 4 (--bootstrap_heads) / 6 (--quantiles) needs beside
+// the two structs (refused without it)
+hipError_t launch_head(const StepArgs& a, const HeadArgs& h, hipStream_t s, bool q_system_scope = false, const BootArgs* boot = nullptr,
+                       const QuantArgs* quant = nullptr);
+hipError_t launch_head_quantile(const StepArgs& a, const HeadArgs& h, const QuantArgs& b, hipStream_t s);     // sdqn_quantile.hip: what launch_head runs for h.train == 6
+// sdqn_quantile.hip: [M][N A] Q rows -> [M][A] action values, the mean over the quantiles (float or double)
+hipError_t launch_quantile_mean(const void* q, void* out, bool f64, int M, int N, int A, hipStream_t s);
 hipError_t launch_head_munchausen(const StepArgs& a, const HeadArgs& h, hipStream_t s);     // sdqn_munchausen.hip: what launch_head runs for h.train == 3
 hipError_t launch_head_bootstrap(const StepArgs& a, const HeadArgs& h, const BootArgs& b, hipStream_t s);     // sdqn_bootstrap.hip: what launch_head runs for h.train == 4
 hipError_t launch_head_advantage(const StepArgs& a, const HeadArgs& h, hipStream_t s);      // sdqn_advantage.hip: what launch_head runs for h.train == 5

@@ -24,6 +24,9 @@ enum KernelId {
   K_TARGET,    // --target_tau: the soft target update, one launch behind the step's update launch (sdqn_target.hip / generic_net.hip)
   K_COUNT
 };
+// HeadArgs::train / StepPlan::head_train of a --quantiles N > 1 step: the K_HEAD launch runs quantile_head_kernel (sdqn_quantile.hip; the
+// values 0 .. 5 of the other heads are listed at HeadArgs::train, kernels.h)
+constexpr int HEAD_QUANTILE = 6;
 static_assert(K_BN == 19 && K_WGRADS == 24 && K_ACT == 25 && K_COLLECT == 26 && K_TARGET == 27 && K_COUNT == 28, "kernel ids are public numbers");
 
 // LaunchTune::variant — the launch variants the step's orchestration asks for (sdqn_api_step.hip decides, resolve_route tests); bit 0 is unused

@@ -552,6 +552,7 @@ extern "C" int sdqn_net_set_munchausen(sdqn_net_t h, int on, double alpha, doubl
   ARGCHK(clip <= 0.0 && clip > -INFINITY, "munchausen_clip %g: must be <= 0", clip);
   if (on) {
     ARGCHK(h->boot_K == 1, "munchausen cannot be combined with bootstrap_heads %d", h->boot_K);
+    ARGCHK(h->quant_N == 1, "munchausen cannot be combined with quantiles %d", h->quant_N);
     ARGCHK(!(h->al_alpha > 0.0), "munchausen cannot be combined with advantage_learning: both targets want q slot 2 for a head of their own");
     ARGCHK(h->cfg.batch_norm == 0.0, "munchausen cannot be combined with batch_norm: inference-mode statistics for its third forward are not defined");
     ARGCHK(h->gen || !h->double_dqn, "munchausen cannot be combined with double_dqn: the Munchausen target has no argmax for the online net to choose");
@@ -581,6 +582,7 @@ extern "C" int sdqn_net_set_advantage_learning(sdqn_net_t h, double alpha, int p
     ARGCHK(!dd, "advantage_learning cannot be combined with double_dqn: q slot 2 is taken by its third forward");
     ARGCHK(!mu, "advantage_learning cannot be combined with munchausen: both targets want q slot 2 for a head of their own");
     ARGCHK(h->boot_K == 1, "advantage_learning cannot be combined with bootstrap_heads %d", h->boot_K);
+    ARGCHK(h->quant_N == 1, "advantage_learning cannot be combined with quantiles %d", h->quant_N);
     ARGCHK(h->cfg.batch_norm == 0.0, "advantage_learning cannot be combined with batch_norm: inference-mode statistics for its third forward are not defined");
     ARGCHK(!(persistent && h->n_step > 1), "persistent_advantage cannot be combined with n_step %d: it repeats the action in the NEXT state", h->n_step);
   }
@@ -612,6 +614,7 @@ extern "C" int sdqn_net_set_bootstrap(sdqn_net_t h, int K, double P, uint64_t se
     ARGCHK(!dd, "bootstrap_heads %d cannot be combined with double_dqn", K);
     ARGCHK(!mu, "bootstrap_heads %d cannot be combined with munchausen", K);
     ARGCHK(!(h->al_alpha > 0.0), "bootstrap_heads %d cannot be combined with advantage_learning", K);
+    ARGCHK(h->quant_N == 1, "bootstrap_heads %d cannot be combined with quantiles %d", K, h->quant_N);
   }
   if (h->gen) h->gen->set_bootstrap(K, thresh, bootstrap_mask_seed(seed));
   h->boot_K = K; h->boot_P = P; h->boot_seed = seed; h->boot_thresh = thresh; h->boot_episode = 0;
@@ -649,9 +652,67 @@ extern "C" int sdqn_bootstrap_act(const float* q, int K, int A, int vote, uint64
   return SDQN_OK;
 }
 
+// ---- --quantiles: quantile-regression DQN (sdqn.h; quantile.h) -------------------------------------------------------------
+extern "C" int sdqn_net_set_quantiles(sdqn_net_t h, int N) {
+  ARGCHK(h, "NULL handle");
+  ARGCHK(N >= 1 && N <= MAX_ACTIONS, "quantiles %d outside [1, %d]", N, MAX_ACTIONS);
+  ARGCHK(h->A % N == 0, "quantiles %d does not divide the network's %d outputs (create it with quantiles x num_actions <= %d)", N, h->A, MAX_ACTIONS);
+  if (N > 1) {
+    ARGCHK(h->cfg.clip_error > 0.0, "quantiles %d needs clip_error > 0 (clip_error %g): it is the Huber threshold of the quantile loss", N, h->cfg.clip_error);
+    ARGCHK(h->cfg.batch_norm == 0.0, "quantiles %d cannot be combined with batch_norm", N);
+    const bool dd = h->gen ? h->gen->double_dqn_on() : h->double_dqn, mu = h->gen ? h->gen->munchausen_on() : h->munchausen;
+    ARGCHK(!dd, "quantiles %d cannot be combined with double_dqn", N);
+    ARGCHK(!mu, "quantiles %d cannot be combined with munchausen", N);
+    ARGCHK(!(h->al_alpha > 0.0), "quantiles %d cannot be combined with advantage_learning", N);
+    ARGCHK(h->boot_K == 1, "quantiles %d cannot be combined with bootstrap_heads %d", N, h->boot_K);
+    if (!h->gen && !h->quant_targets) { int r_ = dalloc(h, (void**)&h->quant_targets, (size_t)h->B * MAX_ACTIONS * sizeof(float)); if (r_) return r_; }
+  }
+  if (h->gen) GENCHK(h->gen->set_quantiles(N));
+  h->quant_N = N;
+  return SDQN_OK;
+}
+// what the last train step's quantile head left: its N targets per sample and its dq rows, widened to double (every path; a test's view)
+extern "C" int sdqn_net_last_quantile_step(sdqn_net_t h, double* targets, double* dq) {
+  ARGCHK(h, "NULL handle");
+  ARGCHK(h->quant_N > 1, "the network has no quantiles (sdqn_net_set_quantiles)");
+  if (h->gen) { GENCHK(h->gen->last_quantile_step(targets, dq)); return SDQN_OK; }
+  { int rc_ = join_comm(h); if (rc_) return rc_; }
+  const size_t nt = (size_t)h->B * h->quant_N, nd = (size_t)h->B * h->A;
+  std::vector<float> buf(nt + nd);
+  HIPCHK(hipMemcpyAsync(buf.data(), h->quant_targets, nt * 4, hipMemcpyDeviceToHost, g_stream));
+  HIPCHK(hipMemcpyAsync(buf.data() + nt, h->dq, nd * 4, hipMemcpyDeviceToHost, g_stream));
+  HIPCHK(hipStreamSynchronize(g_stream));
+  if (targets) for (size_t i = 0; i < nt; ++i) targets[i] = (double)buf[i];
+  if (dq) for (size_t i = 0; i < nd; ++i) dq[i] = (double)buf[nt + i];
+  return SDQN_OK;
+}
+extern "C" int sdqn_net_get_quantiles(sdqn_net_t h, int* N) {
+  ARGCHK(h, "NULL handle");
+  if (N) *N = h->quant_N;
+  return SDQN_OK;
+}
+// the host restatement of one sample of the quantile head (no device): quantile.h's quantile_sample on float rows
+extern "C" int sdqn_quantile_loss(int N, int A, double kappa, const float* q_pre_row, const float* q_post_row, int action, double reward, int terminal,
+                                  double gamma, float* dq_out, float* cost_out) {
+  ARGCHK(q_pre_row && q_post_row && dq_out && cost_out, "NULL argument");
+  ARGCHK(N >= 1 && A >= 1 && N * A <= MAX_ACTIONS, "quantiles %d x %d actions outside [1, %d] outputs", N, A, MAX_ACTIONS);
+  ARGCHK(action >= 0 && action < A, "action %d out of range [0, %d)", action, A);
+  ARGCHK(kappa > 0.0, "kappa %g: must be > 0", kappa);
+  float maxq;
+  *cost_out = quantile_sample<float>(q_pre_row, q_post_row, N, A, action, reward, terminal, gamma, (float)kappa, dq_out, nullptr, &maxq);
+  return SDQN_OK;
+}
+// the acting rule on one raw Q row q[N A]: the first maximum of the quantile means (a NaN counts as one)
+extern "C" int sdqn_quantile_act(const float* q, int N, int A, int* action) {
+  ARGCHK(q && action && N >= 1 && A >= 1 && N * A <= MAX_ACTIONS, "bad arguments");
+  *action = quantile_act(q, N, A);
+  return SDQN_OK;
+}
+
 extern "C" int sdqn_net_set_option(sdqn_net_t h, const char* name, int value) {
   ARGCHK(h && name, "NULL argument");
   if (!strcmp(name, "double_dqn") && value) ARGCHK(h->boot_K == 1, "double_dqn cannot be combined with bootstrap_heads %d", h->boot_K);
+  if (!strcmp(name, "double_dqn") && value) ARGCHK(h->quant_N == 1, "double_dqn cannot be combined with quantiles %d", h->quant_N);
   if (!strcmp(name, "double_dqn") && value) ARGCHK(!(h->al_alpha > 0.0), "double_dqn cannot be combined with advantage_learning: q slot 2 is taken by its third forward");
   if (!strcmp(name, "n_step")) {                          // n-step returns: sdqn.h
     ARGCHK(value >= 1 && value <= SDQN_MAX_N_STEP, "n_step %d out of range [1, %d]", value, SDQN_MAX_N_STEP);
@@ -772,7 +833,8 @@ extern "C" int sdqn_net_debug_read(sdqn_net_t h, const char* name, float* out, i
     {"a1", h->a1, (int64_t)2 * B * PIX1 * K1}, {"a2", h->a2, (int64_t)2 * B * PIX2 * K2}, {"a3", h->a3, (int64_t)2 * B * PIX3 * K3},
     {"a4", h->a4, (int64_t)2 * B * NFC}, {"d4", h->d4, (int64_t)B * NFC}, {"d3p", h->d3p, (int64_t)B * PD3 * PD3 * K3},
     {"d3", h->d3, (int64_t)B * PIX3 * K3}, {"d2p", h->d2p, (int64_t)B * PD2 * PD2 * K2}, {"d1", h->d1, (int64_t)B * PIX1 * K1}, {"q", h->q, (int64_t)2 * B * h->A},
-    {"dq", h->dq, (int64_t)B * h->A}, {"g", h->g, h->NP}, {"theta", h->theta, h->NP}, {"cost_terms", h->cost_terms, B}};
+    {"dq", h->dq, (int64_t)B * h->A}, {"g", h->g, h->NP}, {"theta", h->theta, h->NP}, {"cost_terms", h->cost_terms, B},
+    {"quantile_targets", h->quant_targets, h->quant_targets ? (int64_t)B * h->quant_N : 0}};
   for (auto& e : tab) if (!strcmp(e.n, name)) {
     ARGCHK(n <= e.len, "buffer %s holds %lld floats", name, (long long)e.len);
     { int rc_ = join_comm(h); if (rc_) return rc_; } HIPCHK(hipStreamSynchronize(g_stream));
@@ -788,6 +850,7 @@ namespace sdqn { hipError_t set_timing_buffer(unsigned long long* p); }
 extern "C" int sdqn_debug_time_kernel(sdqn_net_t h, sdqn_replay_t r, const int64_t* idx_host, int kernel, unsigned long long* out, int max_blocks) {
   ARGCHK(h && r && idx_host && out, "NULL");
   ARGCHK(kernel != K_HEAD || h->boot_K == 1, "bootstrap_heads %d: this hook launches the standard head, not the step's bootstrap head", h->boot_K);
+  ARGCHK(kernel != K_HEAD || h->quant_N == 1, "quantiles %d: this hook launches the standard head, not the step's quantile head", h->quant_N);
   unsigned long long* d = nullptr;
   HIPCHK(hipMalloc((void**)&d, (size_t)max_blocks * 64));
   HIPCHK(hipMemset(d, 0, (size_t)max_blocks * 64));

@@ -115,7 +115,8 @@ static int forward(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd, const L
   PLANNED_LAUNCH(K_FC4_FWD, f, l);
   BN_FWD(3);
   const BootArgs boot = {h->boot_K, game_actions(h), h->boot_thresh, bootstrap_mask_seed(h->boot_seed), a.from_ring ? a.idx : nullptr};   // (read when hd.train == 4)
-  LAUNCH(K_HEAD, launch_head(f, hd, g_stream, h->head_q_system, &boot));      // (head_q_system: the acting path, never with batch_norm)
+  const QuantArgs quant = {h->quant_N, game_actions(h), h->quant_targets};      // (read when hd.train == 6)
+  LAUNCH(K_HEAD, launch_head(f, hd, g_stream, h->head_q_system, &boot, &quant));      // (head_q_system: the acting path, never with batch_norm)
   return SDQN_OK;
 }
 int run_forward(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd) {
@@ -212,7 +213,8 @@ StepPlan step_plan(const sdqn_net_s* h) {
   const bool al = h->al_alpha > 0.0;
   p.extra_fwd = (h->munchausen || al) ? 1 : (ddqn_active(h) && h->bn) ? 2 : 0;
   // --bootstrap_heads K > 1 (refused together with double_dqn / munchausen / batch_norm: sdqn_net_set_bootstrap): its own head; K = 1: nothing
-  p.head_train = h->boot_K > 1 ? 4 : h->munchausen ? 3 : al ? 5 : ddqn_active(h) ? 2 : 0;
+  // --quantiles N > 1 (refused together with all of them: sdqn_net_set_quantiles): likewise; N = 1: nothing
+  p.head_train = h->quant_N > 1 ? HEAD_QUANTILE : h->boot_K > 1 ? 4 : h->munchausen ? 3 : al ? 5 : ddqn_active(h) ? 2 : 0;
   p.nz = (!h->munchausen && !al && ddqn_active(h) && !h->bn) ? 3 : 2;
   LaunchPlan* l = p.launch;
   plan_forward(h, l);
@@ -460,6 +462,7 @@ static int train_host_tuple(sdqn_net_t h, const uint8_t* pre, const uint8_t* act
   const bool ours = owner != nullptr;
   if (ours) { int rcn = nstep_match(h, owner); if (rcn) return rcn; rcn = check_replay_geometry(h, owner); if (rcn) return rcn; }
   ARGCHK(h->boot_K == 1 || !per_owns_minibatch(owner), "bootstrap_heads %d cannot be combined with prioritized_replay", h->boot_K);
+  ARGCHK(h->quant_N == 1 || !per_owns_minibatch(owner), "quantiles %d cannot be combined with prioritized_replay", h->quant_N);
   if (h->gen) {
     if (h->boot_K > 1) GENCHK(h->gen->boot_idx(nullptr));
     const bool per = per_owns_minibatch(owner);                 // prioritized memory: weighted step + priority write-back
@@ -595,6 +598,7 @@ int check_replay_geometry(const sdqn_net_s* h, const sdqn_replay_s* r) {
 static int check_replay_fits(const sdqn_net_s* h, const sdqn_replay_s* r) {
   ARGCHK(r->B == h->B, "replay batch_size %d != network batch_size %d", r->B, h->B);
   ARGCHK(h->boot_K == 1 || !r->per, "bootstrap_heads %d cannot be combined with prioritized_replay", h->boot_K);
+  ARGCHK(h->quant_N == 1 || !r->per, "quantiles %d cannot be combined with prioritized_replay", h->quant_N);
   const int rc = nstep_match(h, r);
   return rc ? rc : check_replay_geometry(h, r);
 }

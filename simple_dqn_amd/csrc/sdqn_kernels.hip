@@ -337,7 +337,8 @@ static HeadKernel head_for(int bucket) {
                                                                                    : head_kernel<MAX_ACTIONS, false, QSYS, DDQN, PER, NSTEP>;
 }
 
-hipError_t launch_head(const StepArgs& a, const HeadArgs& h, hipStream_t s, bool q_system_scope, const BootArgs* boot) {
+hipError_t launch_head(const StepArgs& a, const HeadArgs& h, hipStream_t s, bool q_system_scope, const BootArgs* boot, const QuantArgs* quant) {
+  if (h.train == HEAD_QUANTILE) return quant ? launch_head_quantile(a, h, *quant, s) : hipErrorInvalidValue;   // --quantiles: a kernel of its own (sdqn_quantile.hip)
   if (h.train == 3) return launch_head_munchausen(a, h, s);                      // --munchausen: a kernel of its own (sdqn_munchausen.hip)
   if (h.train == 4) return boot ? launch_head_bootstrap(a, h, *boot, s) : hipErrorInvalidValue;   // --bootstrap_heads: likewise (sdqn_bootstrap.hip)
   if (h.train == 5) return launch_head_advantage(a, h, s);                       // --advantage_learning: likewise (sdqn_advantage.hip)

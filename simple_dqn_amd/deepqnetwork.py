@@ -51,6 +51,34 @@ def check_bootstrap(args, num_actions=None):
     return K, P
 
 
+def check_quantiles(args, num_actions=None):
+    """--quantiles N: N >= 1, N x num_actions <= 18 (when num_actions is known), and N > 1 with clip_error > 0 (the Huber
+    threshold) and none of --double_dqn, --prioritized_replay, --munchausen, --advantage_learning, --bootstrap_heads > 1, --batch_norm.
+    Raises ValueError; touches no device.  Returns N."""
+    N = getattr(args, "quantiles", 1)
+    N = 1 if N is None else int(N)
+    if N < 1:
+        raise ValueError("--quantiles %d: must be >= 1" % N)
+    if N == 1:
+        return N
+    if num_actions is not None and N * int(num_actions) > MAX_ACTIONS:
+        raise ValueError("--quantiles %d x %d actions = %d outputs: the network has at most %d"
+                         % (N, int(num_actions), N * int(num_actions), MAX_ACTIONS))
+    kappa = getattr(args, "clip_error", 1.0)
+    if not float(kappa or 0.0) > 0.0:
+        raise ValueError("--quantiles %d needs --clip_error > 0 (got %s): it is the Huber threshold of the quantile loss; the pure "
+                         "pinball loss is not offered" % (N, kappa))
+    for flag in ("double_dqn", "prioritized_replay", "munchausen", "batch_norm"):
+        if getattr(args, flag, False):
+            raise ValueError("--quantiles cannot be combined with --%s (DESIGN.md §29 lists it as a follow-up)" % flag)
+    if float(getattr(args, "advantage_learning", 0.0) or 0.0) > 0.0:
+        raise ValueError("--quantiles cannot be combined with --advantage_learning (DESIGN.md §29 lists it as a follow-up)")
+    K = getattr(args, "bootstrap_heads", 1)
+    if (1 if K is None else int(K)) > 1:
+        raise ValueError("--quantiles cannot be combined with --bootstrap_heads %d (DESIGN.md §29 lists it as a follow-up)" % int(K))
+    return N
+
+
 def check_advantage_learning(args):
     """--advantage_learning alpha / --persistent_advantage: alpha in [0, 1) (0: off), the persistent form only with
     alpha > 0 and one-step targets, and alpha > 0 with none of --double_dqn, --munchausen, --bootstrap_heads K > 1, --batch_norm.  Raises
@@ -84,7 +112,9 @@ class DeepQNetwork:
         # Bootstrapped DQN: K Q-heads over one torso are a library net with K x num_actions outputs, row k A + a = head k, action a
         al_alpha, al_persistent = check_advantage_learning(args)
         self.bootstrap_heads, self.bootstrap_mask_probability = check_bootstrap(args, num_actions)
-        self._net_actions = self.bootstrap_heads * num_actions
+        # quantile-regression DQN: N quantiles per action are a library net with N x num_actions outputs, row j A + a = quantile j, action a
+        self.quantiles = check_quantiles(args, num_actions)
+        self._net_actions = self.bootstrap_heads * self.quantiles * num_actions
         self._lib = _lib.load()
         self.num_actions = num_actions
         self.batch_size = args.batch_size
@@ -176,6 +206,8 @@ class DeepQNetwork:
         self._boot_vote, self._boot_episode = False, 0
         if self.bootstrap_heads > 1:                           # (K = 1: the library is not told anything)
             _lib.check(self._lib.sdqn_net_set_bootstrap(h, self.bootstrap_heads, self.bootstrap_mask_probability, self.bootstrap_seed))
+        if self.quantiles > 1:                                 # (N = 1: the library is not told anything)
+            _lib.check(self._lib.sdqn_net_set_quantiles(h, self.quantiles))
         self._mt_buf = (C.c_uint32 * _lib.MT_WORDS)()
         self._act_out = C.c_int(); self._act_greedy = self._lib.sdqn_net_act_greedy
         self._env_r, self._env_t = C.c_int(), C.c_int(); self._act_step_env = self._lib.sdqn_net_act_step_env
@@ -279,6 +311,9 @@ class DeepQNetwork:
         q = np.ascontiguousarray(q_row, dtype=np.float32).reshape(-1)
         assert q.size == self._net_actions
         a = C.c_int()
+        if self.quantiles > 1:                                  # --quantiles: the first maximum of the quantile means
+            _lib.check(self._lib.sdqn_quantile_act(_lib.ptr(q, C.c_float), self.quantiles, self.num_actions, C.byref(a)))
+            return a.value
         _lib.check(self._lib.sdqn_bootstrap_act(_lib.ptr(q, C.c_float), self.bootstrap_heads, self.num_actions, int(self._boot_vote),
                                                 self.bootstrap_seed, 0, self._boot_episode, C.byref(a)))
         return a.value
@@ -370,6 +405,12 @@ class DeepQNetwork:
         assert states.shape == ((self.batch_size, self.history_length,) + self.screen_dim)
         st = np.ascontiguousarray(states, dtype=np.uint8)
         q = self._predict_raw(st)
+        if self.quantiles > 1:                                  # the action values [B][A]: the sum over the quantiles, in order, over N
+            qs = q.reshape(self.batch_size, self.quantiles, self.num_actions)
+            s = np.zeros((self.batch_size, self.num_actions), self._np)
+            for j in range(self.quantiles):
+                s += qs[:, j]
+            return s / self._np(self.quantiles)
         if self.bootstrap_heads == 1:
             return q
         return q.reshape(self.batch_size, self.bootstrap_heads, self.num_actions).mean(axis=1, dtype=self._np)     # the head-mean [B][A]
@@ -378,6 +419,11 @@ class DeepQNetwork:
         """--bootstrap_heads: the Q-values of every Q-head, [B][K][A] (K = 1: predict() with an axis of one)"""
         assert states.shape == ((self.batch_size, self.history_length,) + self.screen_dim)
         return self._predict_raw(np.ascontiguousarray(states, dtype=np.uint8)).reshape(self.batch_size, self.bootstrap_heads, self.num_actions)
+
+    def predict_quantiles(self, states):
+        """--quantiles: the quantile estimates of every action, [B][N][A] (N = 1: predict() with an axis of one)"""
+        assert states.shape == ((self.batch_size, self.history_length,) + self.screen_dim)
+        return self._predict_raw(np.ascontiguousarray(states, dtype=np.uint8)).reshape(self.batch_size, self.quantiles, self.num_actions)
 
     def _predict_raw(self, st):
         q = np.empty((self.batch_size, self._net_actions), dtype=self._np)
@@ -668,6 +714,13 @@ class DeepQNetwork:
         mq = np.empty((self.batch_size,), dtype=np.float32)
         _lib.check(self._lib.sdqn_net_last_q(self._h, _lib.ptr(preq, C.c_float), _lib.ptr(mq, C.c_float)))
         return preq, mq
+
+    def last_quantile_step(self):
+        """--quantiles N > 1: (targets float64[B, N], dq float64[B, N * A]) of the last train step's head, on every path"""
+        t = np.empty((self.batch_size, self.quantiles), np.float64)
+        dq = np.empty((self.batch_size, self._net_actions), np.float64)
+        _lib.check(self._lib.sdqn_net_last_quantile_step(self._h, _lib.ptr(t, C.c_double), _lib.ptr(dq, C.c_double)))
+        return t, dq
 
     def debug_read(self, name, n):
         out = np.empty(int(n), dtype=np.float32)

@@ -1,0 +1,49 @@
+"""Cost of --quantiles: a standard 18-action net and a quantile (A = 3, N = 6) net — the same forward and backward launches,
+only the head differs — trained alternately in one process with train_from_memory on a synthetic-filled ring, float32 at B = 32 and
+B = 256.  Prints steps/s of both and their ratio per batch size (median of the alternated rounds); --out appends the lines to a file."""
+import argparse, json, os, random, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np
+import simple_dqn_amd as sd
+from oracle.replay_numpy import synthetic_fill
+from util import make_args
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=200, help="train steps per timed call")
+    ap.add_argument("--rounds", type=int, default=7, help="alternated (standard, quantile) rounds")
+    ap.add_argument("--batch", type=int, help="one batch size only")
+    ap.add_argument("--net", choices=["both", "standard", "quantile"], default="both", help="one net only (a kernel trace of each form)")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    for B in ([a.batch] if a.batch else [32, 256]):
+        mem = sd.ReplayMemory(20000, make_args(batch_size=B))
+        synthetic_fill(mem, 1, num_actions=3)                    # actions < 3: valid for both nets
+        mem.sync_mirror()
+        make = {"standard": lambda: sd.DeepQNetwork(18, make_args(batch_size=B)),
+                "quantile": lambda: sd.DeepQNetwork(3, make_args(batch_size=B, quantiles=6))}
+        nets = {k: make[k]() for k in make if a.net in ("both", k)}
+        rate = {k: [] for k in nets}
+        random.seed(1)
+        for r in range(a.rounds + 1):
+            for k, net in nets.items():
+                net.train_from_memory(mem, 10); net.sync()
+                t0 = time.perf_counter()
+                net.train_from_memory(mem, a.steps); net.sync()
+                if r:                                            # (round 0 warms the code objects and the caches up)
+                    rate[k].append(a.steps / (time.perf_counter() - t0))
+        out = {"batch_size": B, "rounds": a.rounds}
+        for k in nets:
+            out[k + "_steps_per_s"] = round(float(np.median(rate[k])), 1); out[k + "_us"] = round(1e6 / float(np.median(rate[k])), 2)
+            out[k + "_all"] = [round(x, 1) for x in rate[k]]
+        if len(nets) == 2:
+            out["ratio"] = round(out["quantile_steps_per_s"] / out["standard_steps_per_s"], 4)
+        print(json.dumps(out), flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(json.dumps(out) + "\n")
+
+
+if __name__ == "__main__":
+    main()

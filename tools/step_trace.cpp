@@ -6,6 +6,8 @@
 //   step_trace          the thinned grid (the golden): every launch structure and optimizer tail, the other axes off their default one at a
 //                       time; every distinct line once, numbered, then each step as the numbers of its lines
 //   step_trace --full   the whole cross product, every step written out (12 MB: compare two trees' outputs, or their checksums)
+//   step_trace --quantiles   the steps of a --quantiles 6 net over 3 actions (18 outputs), every datatype-regime cell that has them, written
+//                       out (neither golden holds them: tests/test_quantile.py reads the head's line)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -56,7 +58,7 @@ hipError_t launch_kernel(int id, const StepArgs& a, const LaunchTune& t, hipStre
   fprintf(g_out, " v=%d hidx=%d\n", t.variant, t.host_idx != nullptr);
   return hipSuccess;
 }
-hipError_t launch_head(const StepArgs& a, const HeadArgs& h, hipStream_t s, bool q_system_scope, const BootArgs*) {
+hipError_t launch_head(const StepArgs& a, const HeadArgs& h, hipStream_t s, bool q_system_scope, const BootArgs*, const QuantArgs*) {
   fprintf(g_out, "  %s %2d %-11s", sname(s), K_HEAD, "head"); step_fields(a);
   fprintf(g_out, " train=%d nstep=%d q=%s sys=%d\n", h.train, h.nstep, nm(h.q).c_str(), (int)q_system_scope);
   return hipSuccess;
@@ -122,7 +124,9 @@ enum Opt { O_NONE, O_BT_XCD0, O_C1W0, O_C1W2, O_C1WIN0, O_C1WIN2, O_F4_SHARE, O_
 static const char* O_NAMES[] = {"", " bt_xcd=0", " conv1w_bf16=0", " conv1w_bf16=2", " c1w_in_wgrads=0", " c1w_in_wgrads=2", " f4_share=60,30", " tuple"};
 struct Cfg { int B, dt, fused, dp, clip, tgt, next, adam, keep, opt; };      // dt: 0 float32, 1 float32 + batch_norm, 2 float16
 
+static int g_quantiles = 1;      // --quantiles: every net is a quantile net over 18 / g_quantiles actions
 static bool refused(const Cfg& c) {
+  if (g_quantiles > 1 && (c.dt == 1 || c.tgt != T_STD)) return true;      // sdqn_net_set_quantiles refuses batch_norm, double_dqn and munchausen
   if (c.dp == DP_SERIAL_F32 && c.dt != 2) return true;     // dp_half is a float16 option
   if (c.tgt == T_MUNCH && c.dt == 1) return true;          // sdqn_net_set_munchausen refuses batch_norm
   return false;
@@ -144,6 +148,7 @@ static void fill(sdqn_net_s* h, const Cfg& c) {
     NAMED(h->h_a1); NAMED(h->h_a2); NAMED(h->h_a3); NAMED(h->h_d4); NAMED(h->h_d3p); NAMED(h->h_d3); NAMED(h->h_d2p); NAMED(h->h_d2); NAMED(h->h_d1);
     NAMED(h->wh[0]); NAMED(h->wh[1]); NAMED(h->wht[0]); NAMED(h->wht[1]); NAMED(h->gh); NAMED(h->ovf_flag); NAMED(h->ovf_count);
   }
+  if (g_quantiles > 1) { h->cfg.num_actions = h->A = MAX_ACTIONS; h->quant_N = g_quantiles; h->NPW = OFF5 + (int64_t)h->A * NFC; h->NP = h->NPW; }
   h->ev_g4 = (hipEvent_t)0x4000; h->ev_w4 = (hipEvent_t)0x5000;
   h->fused_launches = c.fused != 0; h->keep_grads = c.keep != 0; h->target_tau = 0.01;      // (every applied step ends with its blend line)
   if (c.clip) h->clip_grad_norm = 10.0;
@@ -245,9 +250,16 @@ int main(int argc, char** argv) {
   setvbuf(stdout, nullptr, _IOFBF, 1 << 20);
   const bool full = argc > 1 && !strcmp(argv[1], "--full");
   char* text = nullptr; size_t text_len = 0;
-  if (!full) g_out = open_memstream(&text, &text_len);
+  const bool quantiles = argc > 1 && !strcmp(argv[1], "--quantiles");
+  if (!full && !quantiles) g_out = open_memstream(&text, &text_len);
   g_rccl.AllReduce = ar_stub; g_rccl.GroupStart = group_start; g_rccl.GroupEnd = group_end;
   for (int i = 0; i < 512; ++i) g_host_idx[i] = 1000 + 37 * i;
+  if (quantiles) {
+    g_quantiles = 6;
+    for (int dt : {0, 2}) for (int B : {32, 128}) for (int clip = 0; clip < 2; ++clip) train(Cfg{B, dt, 1, DP_NONE, clip, T_STD, 0, 0, 0, O_NONE});
+    train(Cfg{32, 0, 1, DP_SERIAL, 0, T_STD, 0, 0, 0, O_NONE});
+    return 0;
+  }
   static const int BS[] = {32, 33, 127, 128, 256};
   for (int dt = 0; dt < 3; ++dt) for (int B : BS) for (int fused = 1; fused >= 0; --fused) for (int dp = 0; dp < DP_COUNT; ++dp) for (int clip = 0; clip < 2; ++clip)
     for (int tgt = 0; tgt < 3; ++tgt) for (int next = 0; next < 2; ++next) for (int adam = 0; adam < 2; ++adam) for (int keep = 0; keep < 2; ++keep) {

@@ -18,6 +18,8 @@
 //   * the NW partial tiles are summed through LDS in a fixed order (deterministic), then P::store.
 //   * a staged problem whose N leaves most CUs without a 32-wide tile (fc4_dgrad: 98 of them) runs the same scheme on 32 x 16 tiles and
 //     v_mfma_f32_16x16x4_f32 instead (P::N16_WAVES, gemm_tile_n16; maps in n16_map.h).
+//   * a direct-operand problem whose 32-row tiles give some CUs two workgroups and the others one (conv2_fwd below B = 128: 324 tiles) runs
+//     on 48 x 32 tiles of the same instruction, one workgroup per CU (P::M48_WAVES, gemm_tile_m48; maps in m48_map.h).
 //
 // MFMA operand maps (guide §3): lane l holds A[i = l&31][k = l>>5], B[k = l>>5][j = l&31];
 // D register r of lane l is D[i = (r&3) + 8*(r>>2) + 4*(l>>5)][j = l&31].
@@ -26,6 +28,7 @@
 #include <string.h>
 #include "problems.h"
 #include "n16_map.h"
+#include "m48_map.h"
 #include "launch.h"
 
 namespace sdqn {
@@ -107,6 +110,13 @@ template <class P, class = void> struct n16_waves { static constexpr int value =
 template <class P> struct n16_waves<P, decltype((void)P::N16_WAVES)> { static constexpr int value = P::N16_WAVES; };
 template <class P, int NW> constexpr bool use_n16() {
   return NW > 1 && n16_waves<P>::value == NW && stages_lds<P>::value && !uses_f16_wgrad<P>::value && !uses_f16_mfma<P>::value;
+}
+// M48_WAVES: the wave count at which a direct-operand fp32 problem (A k-contiguous, B a plain [k][n] matrix) runs on the 48 x 32 tile body
+// (gemm_tile_m48 below) instead of the 32 x 32 one; absent or 0: never.  Like N16_WAVES the choice belongs to (problem, waves per tile).
+template <class P, class = void> struct m48_waves { static constexpr int value = 0; };
+template <class P> struct m48_waves<P, decltype((void)P::M48_WAVES)> { static constexpr int value = P::M48_WAVES; };
+template <class P, int NW> constexpr bool use_m48() {
+  return NW > 1 && m48_waves<P>::value == NW && !stages_lds<P>::value && !uses_f16_wgrad<P>::value && !uses_f16_mfma<P>::value;
 }
 // problems whose epilogue gates the result with a stored activation may offer the two halves of store apart (P::GATED: gate_load, store_gated)
 template <class P, class = void> struct gated_store { static constexpr bool value = false; };
@@ -538,6 +548,127 @@ __device__ __forceinline__ void gemm_tile_n16(const StepArgs& a, int bx, int by,
   SDQN_WSTAMP_FLUSH;
 }
 
+// ---- 48 x 32 tile body: v_mfma_f32_16x16x4_f32 --------------------------------------------------------------------------------------
+// For a direct-operand problem (A k-contiguous, B a plain [k][n] matrix, K a whole number of 32-deep chunks) whose 32-row tiles land two
+// to a CU on part of the chip: 1.5 x the rows per workgroup, two thirds of the workgroups, one per CU.  Wave w owns the 32-deep chunks
+// w, w + NW, ... as in gemm_tile; a chunk is 8 k-steps x 3 row groups x 2 column halves of the 16 x 16 x 4 instruction on six accumulators
+// (m48_map.h).  The k-slot map is n16_map.h's, so every element's fmaf chain takes the same k in the same order as the 32 x 32 body's;
+// the NW partial tiles pass through LDS in two halves of NW / 2 panels with the running sum carried in registers, in wave order:
+// bit-identical to gemm_tile.
+template <class P, int NW, int NT>
+__device__ __forceinline__ void gemm_tile_m48(const StepArgs& a, int bx, int by, int bz, float* smem) {
+  static_assert(P::A_K && !P::B_K && P::B_REG && !P::A_U8, "48 x 32 body: A k-contiguous floats, B a plain [k][n] matrix");
+  static_assert(NW == 2 * m48::HALF_WAVES && NT == NW * 64, "two combine halves of 8 waves, no surplus waves");
+  static_assert(sizeof(typename a_elem<P>::type) == 4 && sizeof(typename b_elem<P>::type) == 4, "fp32 operands");
+  typedef typename P::aoff_t aoff_t;
+  SDQN_STAMP(0);
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int m0 = bx * m48::TM, n0 = by * m48::TN;
+  int z, ks, kbeg, kend;
+  P::ksplit(a, bz, z, ks, kbeg, kend);
+  const int M = P::M(a), N = P::N(a);
+  const float* bbase = P::b_ptr(a, z);
+  // A: loader lane (k4 = l & 7, x = n16::ld_x(l, j)) fetches 16 bytes of row 16 rg + x — the 8 lanes of a k4 run read the 128 contiguous
+  // bytes of one row's chunk — and the wave-private panel turns them into fragments, one row group at a time.  B: lane l owns columns
+  // 16 h + (l & 15) at the k of its slot l >> 4.  (Clamped in bounds: rows past M are computed and not stored.)
+  aoff_t srow[m48::RG][2]; int bcol[m48::CH];
+#pragma unroll
+  for (int rg = 0; rg < m48::RG; ++rg)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) { const int m = m0 + m48::ld_row(lane, rg, j); srow[rg][j] = P::a_row(a, z, m < M ? m : M - 1); }
+#pragma unroll
+  for (int h = 0; h < m48::CH; ++h) { const int n = n0 + m48::frag_col(lane, h); bcol[h] = P::b_col(a, z, n < N ? n : N - 1); }
+  const int klane = m48::kslot_lane(lane >> 4);
+  float* pan = smem + m48::opnd_off(wave);
+
+  f32x4 acc[m48::RG][m48::CH];
+#pragma unroll
+  for (int rg = 0; rg < m48::RG; ++rg)
+#pragma unroll
+    for (int h = 0; h < m48::CH; ++h) acc[rg][h] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  SDQN_STAMP(1);
+  SDQN_STAMP(2);
+  for (int kc = kbeg + wave * 32; kc < kend; kc += NW * 32) {      // wave-uniform
+    f4 pra[m48::RG][2]; float fb[m48::CH][m48::STEPS];
+    const aoff_t c = P::a_col(a, z, kc + n16::ld_k(lane));
+    // (the last row group's two loads are issued behind the first group's panel stores and land under 32 MFMAs: 8 VGPRs less at the peak)
+#pragma unroll
+    for (int rg = 0; rg < m48::RG - 1; ++rg)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) pra[rg][j] = P::a_load4(a, z, srow[rg][j] + c);
+#pragma unroll
+    for (int t = 0; t < m48::STEPS; ++t) {
+      const int r = P::b_row(a, z, kc + m48::kslot_step(t) + klane);
+#pragma unroll
+      for (int h = 0; h < m48::CH; ++h) fb[h][t] = bbase[(uint32_t)(r + bcol[h])];
+    }
+#ifdef SDQN_TIMING
+    asm volatile("" :: "v"(pra[0][0].x), "v"(pra[1][1].w), "v"(fb[0][0]), "v"(fb[1][7]));      // operands landed
+    SDQN_STAMP(3);
+#endif
+    // row group by row group through the one panel: registers -> panel (logical k in row n16::krow(k)) -> fragments -> 16 MFMAs.  An
+    // accumulator pair starts to live when its group begins, which keeps the kernel inside 64 VGPRs; the two column halves alternate,
+    // so a dependent MFMA is 64 cycles behind its predecessor
+#pragma unroll
+    for (int rg = 0; rg < m48::RG; ++rg) {
+      float fa[m48::STEPS];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int x = n16::ld_x(lane, j), k = n16::ld_k(lane);
+        pan[m48::pan_off(k, x)] = pra[rg][j].x; pan[m48::pan_off(k + 1, x)] = pra[rg][j].y;
+        pan[m48::pan_off(k + 2, x)] = pra[rg][j].z; pan[m48::pan_off(k + 3, x)] = pra[rg][j].w;
+      }
+      if (rg == 0) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) pra[m48::RG - 1][j] = P::a_load4(a, z, srow[m48::RG - 1][j] + c);
+      }
+      wave_lds_sync();
+#pragma unroll
+      for (int t = 0; t < m48::STEPS; ++t) fa[t] = pan[m48::frag_a(lane, t)];
+      wave_lds_sync();                                     // panel reads issued before the next group's stores
+#pragma unroll
+      for (int t = 0; t < m48::STEPS; ++t)
+#pragma unroll
+        for (int h = 0; h < m48::CH; ++h) acc[rg][h] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[t], fb[h][t], acc[rg][h], 0, 0, 0);
+    }
+  }
+
+  // ---- epilogue: NW partial tiles -> 8 panels, twice -> running sums in wave order -> P::store (32 consecutive lanes = one row) ----
+#ifdef SDQN_TIMING
+  asm volatile("" :: "v"(acc[0][0][0]), "v"(acc[2][1][3]));
+  SDQN_STAMP(4);
+#endif
+  const int e0 = threadIdx.x, e1 = threadIdx.x + NT;
+  const bool two = e1 < m48::TM * m48::TN;                 // waves 0-7: a second element (wave-uniform)
+  const int o0 = m48::comb_off(m48::epi_row(e0), m48::epi_col(e0)), o1 = two ? m48::comb_off(m48::epi_row(e1), m48::epi_col(e1)) : o0;
+  float v0 = 0.0f, v1 = 0.0f;
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+    if (half) __syncthreads();                             // the first half's panels are read before the second half's stores
+    if (m48::comb_half(wave) == half) {
+      float* cw = smem + m48::comb_panel(wave) * m48::PANEL_C;
+#pragma unroll
+      for (int rg = 0; rg < m48::RG; ++rg)
+#pragma unroll
+        for (int h = 0; h < m48::CH; ++h)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) cw[m48::comb_off(m48::acc_row(rg, lane, r), m48::acc_col(h, lane))] = acc[rg][h][r];
+    }
+    __syncthreads();
+    if (half) SDQN_STAMP(5);
+#pragma unroll
+    for (int w = 0; w < m48::HALF_WAVES; ++w) {
+      const float p0 = smem[w * m48::PANEL_C + o0];
+      v0 = (half == 0 && w == 0) ? p0 : v0 + p0;
+      if (two) { const float p1 = smem[w * m48::PANEL_C + o1]; v1 = (half == 0 && w == 0) ? p1 : v1 + p1; }
+    }
+  }
+  { const int m = m0 + m48::epi_row(e0), n = n0 + m48::epi_col(e0); if (m < M && n < N) P::store(a, z, ks, m, n, v0); }
+  if (two) { const int m = m0 + m48::epi_row(e1), n = n0 + m48::epi_col(e1); if (m < M && n < N) P::store(a, z, ks, m, n, v1); }
+  SDQN_STAMP(6);
+}
+
 // ---- fp16-mode tile body: packed-fp16 MFMA -------------------------------------------------------------------
 // v_mfma_f32_32x32x16_f16: lane (i = l & 31, h = l >> 5) feeds 8 consecutive k (one 16-B load) of row i of A and of
 // column i of B into k-slots 8h..8h+7; both operands of these problems are k-contiguous in memory (NHWC activations /
@@ -731,6 +862,7 @@ __device__ __forceinline__ void gemm_tile_hw(const StepArgs& a, int bx, int by, 
 template <class P, int NW, int NT>
 __device__ __forceinline__ void run_tile(const StepArgs& a, int bx, int by, int bz, float* smem) {
   if constexpr (use_n16<P, NW>()) gemm_tile_n16<P, NW, NT>(a, bx, by, bz, smem);
+  else if constexpr (use_m48<P, NW>()) gemm_tile_m48<P, NW, NT>(a, bx, by, bz, smem);
   else if constexpr (uses_f16_wgrad<P>::value) gemm_tile_hw<P, NW, NT>(a, bx, by, bz, smem);
   else if constexpr (uses_f16_mfma<P>::value) gemm_tile_h<P, NW, NT>(a, bx, by, bz, smem);
   else gemm_tile<P, NW, NT>(a, bx, by, bz, smem);
@@ -738,11 +870,12 @@ __device__ __forceinline__ void run_tile(const StepArgs& a, int bx, int by, int 
 template <class P, int NW>
 constexpr int tile_lds_any() {
   if constexpr (use_n16<P, NW>()) return NW * n16::WAVE_LDS;          // operand panels, reused as combine panels
+  else if constexpr (use_m48<P, NW>()) return m48::LDS_FLOATS;      // the combine panels of one half of the waves + the A panels of the other half
   else if constexpr (uses_f16_wgrad<P>::value) return NW * HW_WAVE_LDS;   // staging tiles, reused as combine panels
   else return uses_f16_mfma<P>::value ? NW * PANEL : tile_lds<P, NW>();
 }
 // rows / columns of C one tile covers (NW: waves per tile of the launch form; 0 = a form without a narrow body)
-template <class P> constexpr int tile_m() { return 32; }
+template <class P, int NW = 0> constexpr int tile_m() { return use_m48<P, NW>() ? m48::TM : 32; }
 template <class P, int NW = 0> constexpr int tile_n() { return use_n16<P, NW>() ? n16::TN : 32; }
 
 // (xcd_tile_id / xcd_tile_id_range, the XCD-aware workgroup -> tile maps: problems.h — host + device, tests/emul executes them)
@@ -786,7 +919,7 @@ struct MultiDims { int n[3]; int gx[3], gy[3]; };       // workgroups per proble
 
 template <class P, int NW, int NT>
 __device__ __forceinline__ void multi_dispatch(const StepArgs& a, const MultiDims& d, int which, int local, float* smem) {
-  static_assert(!use_n16<P, NW>(), "multi-problem launches size their tile grids for 32 x 32 tiles");
+  static_assert(!use_n16<P, NW>() && !use_m48<P, NW>(), "multi-problem launches size their tile grids for 32 x 32 tiles");
   if constexpr (NW == 1) {
     // one tile per wave; the launch owns the tile range [a.f4w_first, a.f4w_first + a.f4w_count)
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -863,7 +996,7 @@ struct NoProblem {            // placeholder third problem for two-problem launc
 
 template <class P, int NW>
 inline hipError_t launch_gemm(const StepArgs& a, hipStream_t stream) {
-  dim3 grid((P::M(a) + tile_m<P>() - 1) / tile_m<P>(), (P::N(a) + tile_n<P, NW>() - 1) / tile_n<P, NW>(), P::nbz(a));
+  dim3 grid((P::M(a) + tile_m<P, NW>() - 1) / tile_m<P, NW>(), (P::N(a) + tile_n<P, NW>() - 1) / tile_n<P, NW>(), P::nbz(a));
   Lead l; memset(&l, 0, sizeof l);
   if constexpr (has_lead<P>::value) {                       // (the tile grid rides packed in one dword: a larger grid reads the struct)
     P::lead_pack(a, l); l.B = a.B; l.s0 = lead_grid(grid);

@@ -337,6 +337,8 @@ struct Conv1Fwd {   // fused gather + normalise + conv1 + ReLU: replay_memory.py
 
 struct Conv2Fwd {   // deepqnetwork.py:85
   static constexpr bool A_K = true, B_K = false;     // operand contiguous along k (-> LDS transpose) or along m/n
+  // the direct 16-wave form (B < 128) cuts M into 48-row tiles — at B = 32, 216 tiles instead of 324, one per CU: gemm_engine.h, gemm_tile_m48
+  static constexpr int M48_WAVES = 16;
   typedef int aoff_t;
   // operand descriptors for the engine's fast paths: *_REG = plain row-major [k][x] matrix with row pitch *_LD
   static constexpr bool A_REG = false, A_U8 = false, B_REG = true; static constexpr int A_LD = 0, B_LD = K2;
@@ -730,7 +732,9 @@ struct Conv1FwdRaw : Conv1Fwd {
   __device__ static void store16(const StepArgs& a, int z, int ks, int m0, int n0, int lane, int M, int N, const float* v, Epi&);
 #endif
 };
+struct Conv2FwdWide : Conv2Fwd { static constexpr int M48_WAVES = 0; };      // the 32 x 32 tiles at every wave count (tuning hook nw:1, the tests' reference)
 struct Conv2FwdRaw : Conv2Fwd {
+  static constexpr int M48_WAVES = 0;                // --batch_norm keeps the 32 x 32 tiles it was measured with
   SDQN_HD static void store(const StepArgs& a, int z, int, int m, int n, float v) { a.a2[((int64_t)z * M(a) + m) * K2 + n] = v; }
 #if defined(__HIPCC__)
   __device__ static void store16(const StepArgs& a, int z, int ks, int m0, int n0, int lane, int M, int N, const float* v, Epi&);

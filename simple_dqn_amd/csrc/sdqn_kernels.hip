@@ -67,7 +67,7 @@ hipError_t launch_lat(const Route& r, int id, const StepArgs& a, const LaunchTun
       const int nw = r.form == LAT_NW2 ? 2 : r.form == LAT_NW4 ? 4 : r.form == LAT_NW8 ? 8 : r.form == LAT_NW9 ? 9 : 16;
       switch (id) {
         case K_CONV1_FWD: return launch_nw<Conv1Fwd>(nw, a, s);
-        case K_CONV2_FWD: return launch_nw<Conv2Fwd>(nw, a, s);
+        case K_CONV2_FWD: return launch_nw<Conv2FwdWide>(nw, a, s);      // (16: the 32 x 32 body that the default 48 x 32 tiles reproduce)
         case K_CONV3_FWD: if (nw == 9) return launch_gemm<Staged<Conv3Fwd>, 9>(a, s); return launch_nw<Conv3Fwd>(nw, a, s);    // 9 = round 1's choice
         case K_FC4_FWD: return launch_nw<Fc4Fwd>(nw, a, s);
         case K_FC4_DGRAD: return launch_nw<Fc4Dgrad>(nw, a, s);

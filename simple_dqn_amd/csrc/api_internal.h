@@ -132,19 +132,19 @@ struct sdqn_net_s {
   // h_a1..h_a3) are re-allocated with room for it when the option is first switched on
   bool double_dqn = false, slots3 = false;
   // --munchausen (sdqn_net_set_munchausen): Munchausen DQN targets; every train step is preceded by a forward of the target
-  // net on the prestates (q slot 2: the slots3 re-allocation) and ends its forward with the Munchausen head (HeadArgs::train = 3)
+  // net on the prestates (q slot 2: the slots3 re-allocation) and ends its forward with the Munchausen head (HEAD_MUNCHAUSEN)
   bool munchausen = false; double mu_alpha = 0.9, mu_tau = 0.03, mu_clip = -1.0;
   // --advantage_learning / --persistent_advantage (sdqn_net_set_advantage_learning): al_alpha > 0: the same forward in front
-  // of every train step, and the step's forward ends with the advantage-learning head (HeadArgs::train = 5); 0: off, nothing changes
+  // of every train step, and the step's forward ends with the advantage-learning head (HEAD_ADVANTAGE); 0: off, nothing changes
   double al_alpha = 0.0; bool al_persistent = false;
   // --bootstrap_heads (sdqn_net_set_bootstrap; bootstrap.h): the net's A outputs are boot_K Q-heads of A / boot_K actions.  boot_K > 1:
-  // train steps end their forward with the bootstrap head (HeadArgs::train = 4), the acting paths reduce a Q row to the game's actions.
+  // train steps end their forward with the bootstrap head (HEAD_BOOTSTRAP), the acting paths reduce a Q row to the game's actions.
   // boot_q: [B][A / boot_K] acting rows of the game loops (select launch), allocated on first use.  boot_vote / boot_episode: the single-
   // environment acting paths (sdqn_net_act_greedy) — majority vote (testing) or the Q-head of copy 0's episode boot_episode (collecting)
   int boot_K = 1; double boot_P = 1.0; uint64_t boot_seed = 0, boot_thresh = 1ull << 53; void* boot_q = nullptr;
   int boot_vote = 0; int64_t boot_episode = 0;
   // --quantiles (sdqn_net_set_quantiles; quantile.h): the net's A outputs are quant_N quantiles of A / quant_N actions.  quant_N > 1:
-  // train steps end their forward with the quantile head (HeadArgs::train = 6), the acting paths reduce a Q row to its mean over the
+  // train steps end their forward with the quantile head (HEAD_QUANTILE), the acting paths reduce a Q row to its mean over the
   // quantiles (the game loops: one launch into boot_q, which the two options — refused together — share).  quant_targets: [B][quant_N]
   // the last step's targets (tuned path; sdqn_net_debug_read "quantile_targets"), allocated by the setter
   int quant_N = 1; float* quant_targets = nullptr;
@@ -265,7 +265,7 @@ struct StepPlan {
   StepStructure structure; UpdateForm update;
   int fuse_rms;                            // StepArgs::fuse_rms: fc4's RMSProp rides in its weight-gradient tiles
   int extra_fwd;                           // forward in front of the step (run_extra_forward): 0 none | 1 --munchausen / --advantage_learning (1, 0) | 2 --double_dqn with --batch_norm (0, 1)
-  int head_train;                          // HeadArgs::train of the step's head: 2 Double DQN, 3 Munchausen, 4 bootstrapped heads, 5 advantage learning, 6 quantiles, 0: the caller's
+  int head_train;                          // HeadArgs::train of the step's head: the HeadMode (launch_route.h) of the option that is on, 0: the caller's
   int nz;                                  // net slots of the step's forward (3: the Double DQN slot rides in it)
   bool side_fc4;                           // overlapped data parallel: fc4's all-reduce + update on g_comm behind bwd3
   LaunchPlan launch[K_WGRADS + 1];         // by kernel id

@@ -25,15 +25,10 @@ struct HeadArgs {
   float* cost_terms;            // [B]  0.5 * delta^2 (pre-clip)
   double discount, min_reward, max_reward;
   float clip_error;
-  int train;                    // 0: predict only (z = 0); 1: train step; 2: train step with Double DQN targets (--double_dqn);
-                                // 3: train step with Munchausen targets (--munchausen; sdqn_munchausen.hip);
-                                // 4: train step of a K-head bootstrapped net (--bootstrap_heads; sdqn_bootstrap.hip, its BootArgs beside this struct)
-                                // 5: train step with advantage-learning targets (--advantage_learning; sdqn_advantage.hip)
-                                // 6: train step of an N-quantile net (--quantiles; sdqn_quantile.hip, its QuantArgs beside this struct;
-                                //    clip_error is the Huber threshold kappa there).  launch_route.h: HEAD_QUANTILE
-  // --munchausen, read when train == 3: bonus scale alpha, softmax temperature tau, lower clip l0 of tau ln pi.  They lie
+  int train;                    // a HeadMode (launch_route.h): HEAD_PREDICT, HEAD_TRAIN, or the train step of an option with a head of its own
+  // --munchausen, read when train == HEAD_MUNCHAUSEN: bonus scale alpha, softmax temperature tau, lower clip l0 of tau ln pi.  They lie
   // in the 24 bytes a retired option's fields left: every later field keeps its offset (see StepArgs::reserved_)
-  // --advantage_learning, read when train == 5: the gap scale alpha in (0, 1) and the persistent (PAL) switch.  The two
+  // --advantage_learning, read when train == HEAD_ADVANTAGE: the gap scale alpha in (0, 1) and the persistent (PAL) switch.  The two
   // options are refused together (sdqn_net_set_advantage_learning), so they share mu_alpha's and mu_tau's bytes: no field moves
   union { double mu_alpha; double al_alpha; };
   union { double mu_tau; int al_persistent; };
@@ -167,16 +162,16 @@ hipError_t launch_r3(const Route& r, int id, const StepArgs& a, const LaunchTune
 hipError_t launch_bt(const Route& r, int id, const StepArgs& a, const LaunchTune& t, hipStream_t s);       // sdqn_kernels_bt.hip: block tiles and the hand-written kernels beside them
 hipError_t launch_ss(const Route& r, int id, const StepArgs& a, const LaunchTune& t, hipStream_t s);       // sdqn_kernels_ss.hip: sample-stationary convolution chains
 hipError_t launch_kernel(int id, const StepArgs& a, const LaunchTune& t, hipStream_t s);     // the GEMM-shaped stages (single or multi-problem launches)
-// q_system_scope: h.q is mapped host memory (acting path); boot / quant: what h.train == 4 (--bootstrap_heads) / 6 (--quantiles) needs beside
+// q_system_scope: h.q is mapped host memory (acting path); boot / quant: what h.train == HEAD_BOOTSTRAP / HEAD_QUANTILE needs beside
 // the two structs (refused without it)
 hipError_t launch_head(const StepArgs& a, const HeadArgs& h, hipStream_t s, bool q_system_scope = false, const BootArgs* boot = nullptr,
                        const QuantArgs* quant = nullptr);
-hipError_t launch_head_quantile(const StepArgs& a, const HeadArgs& h, const QuantArgs& b, hipStream_t s);     // sdqn_quantile.hip: what launch_head runs for h.train == 6
+hipError_t launch_head_quantile(const StepArgs& a, const HeadArgs& h, const QuantArgs& b, hipStream_t s);     // sdqn_quantile.hip: what launch_head runs for HEAD_QUANTILE
 // sdqn_quantile.hip: [M][N A] Q rows -> [M][A] action values, the mean over the quantiles (float or double)
 hipError_t launch_quantile_mean(const void* q, void* out, bool f64, int M, int N, int A, hipStream_t s);
-hipError_t launch_head_munchausen(const StepArgs& a, const HeadArgs& h, hipStream_t s);     // sdqn_munchausen.hip: what launch_head runs for h.train == 3
-hipError_t launch_head_bootstrap(const StepArgs& a, const HeadArgs& h, const BootArgs& b, hipStream_t s);     // sdqn_bootstrap.hip: what launch_head runs for h.train == 4
-hipError_t launch_head_advantage(const StepArgs& a, const HeadArgs& h, hipStream_t s);      // sdqn_advantage.hip: what launch_head runs for h.train == 5
+hipError_t launch_head_munchausen(const StepArgs& a, const HeadArgs& h, hipStream_t s);     // sdqn_munchausen.hip: what launch_head runs for HEAD_MUNCHAUSEN
+hipError_t launch_head_bootstrap(const StepArgs& a, const HeadArgs& h, const BootArgs& b, hipStream_t s);     // sdqn_bootstrap.hip: what launch_head runs for HEAD_BOOTSTRAP
+hipError_t launch_head_advantage(const StepArgs& a, const HeadArgs& h, hipStream_t s);      // sdqn_advantage.hip: what launch_head runs for HEAD_ADVANTAGE
 // sdqn_bootstrap.hip: [N][K A] Q rows -> [N][A] acting rows (float or double); vote = 0: the slice of Q-head k(e, episodes_e), the int64 episode
 // counter of copy e at recs + e stride + offset; vote = 1: the vote counts
 hipError_t launch_bootstrap_select(const void* q, void* out, bool f64, int N, int K, int A, int vote, uint64_t head_seed,

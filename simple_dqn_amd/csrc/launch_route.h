@@ -24,9 +24,18 @@ enum KernelId {
   K_TARGET,    // --target_tau: the soft target update, one launch behind the step's update launch (sdqn_target.hip / generic_net.hip)
   K_COUNT
 };
-// HeadArgs::train / StepPlan::head_train of a --quantiles N > 1 step: the K_HEAD launch runs quantile_head_kernel (sdqn_quantile.hip; the
-// values 0 .. 5 of the other heads are listed at HeadArgs::train, kernels.h)
-constexpr int HEAD_QUANTILE = 6;
+// HeadArgs::train / StepPlan::head_train: what the K_HEAD launch runs.  The numbers are public (tools/step_trace prints them into the goldens)
+enum HeadMode {
+  HEAD_PREDICT = 0,     // predict only (z = 0)
+  HEAD_TRAIN,           // train step
+  HEAD_DOUBLE,          // train step with Double DQN targets (--double_dqn)
+  HEAD_MUNCHAUSEN,      // ... with Munchausen targets (--munchausen; munchausen_head_kernel, sdqn_munchausen.hip)
+  HEAD_BOOTSTRAP,       // train step of a K-head bootstrapped net (--bootstrap_heads; bootstrap_head_kernel, sdqn_bootstrap.hip, its BootArgs beside HeadArgs)
+  HEAD_ADVANTAGE,       // train step with advantage-learning targets (--advantage_learning; advantage_head_kernel, sdqn_advantage.hip)
+  HEAD_QUANTILE         // train step of an N-quantile net (--quantiles N > 1; quantile_head_kernel, sdqn_quantile.hip, its QuantArgs beside HeadArgs;
+                        // HeadArgs::clip_error is the Huber threshold kappa there)
+};
+static_assert(HEAD_TRAIN == 1 && HEAD_DOUBLE == 2 && HEAD_MUNCHAUSEN == 3 && HEAD_BOOTSTRAP == 4 && HEAD_ADVANTAGE == 5 && HEAD_QUANTILE == 6, "head modes are public numbers");
 static_assert(K_BN == 19 && K_WGRADS == 24 && K_ACT == 25 && K_COLLECT == 26 && K_TARGET == 27 && K_COUNT == 28, "kernel ids are public numbers");
 
 // LaunchTune::variant — the launch variants the step's orchestration asks for (sdqn_api_step.hip decides, resolve_route tests); bit 0 is unused

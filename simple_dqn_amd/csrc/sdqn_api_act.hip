@@ -101,7 +101,7 @@ int predict_state_enqueue(sdqn_net_s* h, sdqn_statebuf_s* sb) {
     h->spec_pending = true; h->spec_sb = sb; h->spec_gen = sb->gen;
     return SDQN_OK;
   }
-  HeadArgs hd = head_args(h, 0);
+  HeadArgs hd = head_args(h, HEAD_PREDICT);
   const bool direct = !h->bn;                                    // (--batch_norm: the plain head + a copy, as before)
   if (direct) hd.q = h->q_host_dev + h->q_slot * Q_SLOT_FLOATS;
   h->head_q_system = direct;

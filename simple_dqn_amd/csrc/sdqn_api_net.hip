@@ -862,7 +862,7 @@ extern "C" int sdqn_debug_time_kernel(sdqn_net_t h, sdqn_replay_t r, const int64
   // kernel ids >= 100: round-3 variants — 100 conv1 on bf16 MFMA (warm: third launch on the same indexes), 101 the same, ONE launch
   // (frames never touched before: HBM + TLB cold, what a train step sees), 102 conv3_fwd on 36-deep chunks
   for (int rep = 0; rep < (kernel == 101 ? 1 : 3); ++rep) {                         // last launch's stamps survive
-    if (kernel == K_HEAD) { HeadArgs hd = head_args(h, 1); HIPCHK(launch_head(a, hd, g_stream)); }
+    if (kernel == K_HEAD) { HeadArgs hd = head_args(h, HEAD_TRAIN); HIPCHK(launch_head(a, hd, g_stream)); }
     else if (kernel == 100 || kernel == 101) { h->host_idx_cur = idx_host; const hipError_t le = launch_tuned(h, K_CONV1_FWD, a, g_stream, LV_CONV1_FWD_BF16); h->host_idx_cur = nullptr; HIPCHK(le); }
     else if (kernel == 102) HIPCHK(launch_tuned(h, K_CONV3_FWD, a, g_stream, LV_CONV3_C36));
     else if (kernel == 104) { UpdateArgs u = make_update_args(h, a); u.mode = 0; u.bsz = (float)h->B; u.skip_fc4 = 1; HIPCHK(launch_update(u, g_stream)); }

@@ -114,8 +114,8 @@ static int forward(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd, const L
   { int rc = join_comm(h); if (rc) return rc; }                // conv1..3 of this step overlap the previous step's fc4 all-reduce
   PLANNED_LAUNCH(K_FC4_FWD, f, l);
   BN_FWD(3);
-  const BootArgs boot = {h->boot_K, game_actions(h), h->boot_thresh, bootstrap_mask_seed(h->boot_seed), a.from_ring ? a.idx : nullptr};   // (read when hd.train == 4)
-  const QuantArgs quant = {h->quant_N, game_actions(h), h->quant_targets};      // (read when hd.train == 6)
+  const BootArgs boot = {h->boot_K, game_actions(h), h->boot_thresh, bootstrap_mask_seed(h->boot_seed), a.from_ring ? a.idx : nullptr};   // (read when HEAD_BOOTSTRAP)
+  const QuantArgs quant = {h->quant_N, game_actions(h), h->quant_targets};      // (read when HEAD_QUANTILE)
   LAUNCH(K_HEAD, launch_head(f, hd, g_stream, h->head_q_system, &boot, &quant));      // (head_q_system: the acting path, never with batch_norm)
   return SDQN_OK;
 }
@@ -200,7 +200,7 @@ static int run_extra_forward(sdqn_net_s* h, const StepArgs& a, int wz, int sz, c
   StepArgs p = a; p.nz = 1;
   if (wz) { p.theta[0] = a.theta[1]; p.wh[0] = a.wh[1]; p.wht[0] = a.wht[1]; p.w1p[0] = a.w1p[1]; }
   if (sz) p.src = a.from_ring ? a.src + (size_t)soff(a.post_off, 1) * FRAME : a.src + (size_t)a.B * STATE;
-  HeadArgs hp = head_args(h, 0); hp.q = h->q + (size_t)2 * a.B * h->A;
+  HeadArgs hp = head_args(h, HEAD_PREDICT); hp.q = h->q + (size_t)2 * a.B * h->A;
   return forward(h, p, hp, l);
 }
 // Everything a train step decides, once, from the handle alone: no HIP call, no side effect (api_internal.h: StepPlan)
@@ -214,7 +214,7 @@ StepPlan step_plan(const sdqn_net_s* h) {
   p.extra_fwd = (h->munchausen || al) ? 1 : (ddqn_active(h) && h->bn) ? 2 : 0;
   // --bootstrap_heads K > 1 (refused together with double_dqn / munchausen / batch_norm: sdqn_net_set_bootstrap): its own head; K = 1: nothing
   // --quantiles N > 1 (refused together with all of them: sdqn_net_set_quantiles): likewise; N = 1: nothing
-  p.head_train = h->quant_N > 1 ? HEAD_QUANTILE : h->boot_K > 1 ? 4 : h->munchausen ? 3 : al ? 5 : ddqn_active(h) ? 2 : 0;
+  p.head_train = h->quant_N > 1 ? HEAD_QUANTILE : h->boot_K > 1 ? HEAD_BOOTSTRAP : h->munchausen ? HEAD_MUNCHAUSEN : al ? HEAD_ADVANTAGE : ddqn_active(h) ? HEAD_DOUBLE : 0;
   p.nz = (!h->munchausen && !al && ddqn_active(h) && !h->bn) ? 3 : 2;
   LaunchPlan* l = p.launch;
   plan_forward(h, l);
@@ -339,8 +339,8 @@ int run_train(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd0, const PrepA
   const StepPlan plan = step_plan(h);
   HeadArgs hd = hd0;
   if (plan.head_train) hd.train = plan.head_train;
-  if (plan.head_train == 3) { hd.mu_alpha = h->mu_alpha; hd.mu_tau = h->mu_tau; hd.mu_clip = h->mu_clip; }
-  if (plan.head_train == 5) { hd.al_alpha = h->al_alpha; hd.al_persistent = h->al_persistent ? 1 : 0; }
+  if (plan.head_train == HEAD_MUNCHAUSEN) { hd.mu_alpha = h->mu_alpha; hd.mu_tau = h->mu_tau; hd.mu_clip = h->mu_clip; }
+  if (plan.head_train == HEAD_ADVANTAGE) { hd.al_alpha = h->al_alpha; hd.al_persistent = h->al_persistent ? 1 : 0; }
   if (plan.extra_fwd) { int rc0 = run_extra_forward(h, a, plan.extra_fwd == 1, plan.extra_fwd == 2, plan.launch); if (rc0) return rc0; }
   StepArgs af = a; af.nz = plan.nz;        // the forward's arguments (the backward keeps a: its launches know two slots only)
   int rc = forward(h, af, hd, plan.launch); if (rc) return rc;
@@ -385,7 +385,7 @@ int predict_forward_tuned(sdqn_net_s* h, const uint8_t* states, const HeadArgs& 
 int predict_forward(sdqn_net_s* h, const uint8_t* states, int rows, const void** q, int* q_f64) {
   if (h->gen) { GENCHK(h->gen->forward_dev(states, rows)); *q = h->gen->q_dev(); *q_f64 = h->gen->is_f64() ? 1 : 0; return SDQN_OK; }
   *q = h->q; *q_f64 = 0;
-  return predict_forward_tuned(h, states, head_args(h, 0));
+  return predict_forward_tuned(h, states, head_args(h, HEAD_PREDICT));
 }
 
 extern "C" int sdqn_net_predict_f64(sdqn_net_t h, const uint8_t* states, double* q_out) {
@@ -400,7 +400,7 @@ extern "C" int sdqn_net_predict(sdqn_net_t h, const uint8_t* states, float* q_ou
   ARGCHK(h && states && q_out, "NULL argument");
   if (h->gen) { GENCHK(h->gen->predict_host(states, h->B, q_out, false)); return SDQN_OK; }
   HIPCHK(hipMemcpyAsync(h->st_states, states, (size_t)h->B * STATE, hipMemcpyHostToDevice, g_stream));
-  int rc = predict_forward_tuned(h, h->st_states, head_args(h, 0)); if (rc) return rc;
+  int rc = predict_forward_tuned(h, h->st_states, head_args(h, HEAD_PREDICT)); if (rc) return rc;
   rc = fetch_small(h, h->q, (size_t)h->B * h->A * 4); if (rc) return rc;
   memcpy(q_out, h->h_f, (size_t)h->B * h->A * 4);                             // (B, A): deepqnetwork.py:186 qvalues.T
   return SDQN_OK;
@@ -435,7 +435,7 @@ extern "C" int sdqn_net_predict_one(sdqn_net_t h, const uint8_t* state, float* q
     h->act_on = false; h->act_fallbacks += 1;
     fprintf(stderr, "simple_dqn_amd: the one-launch acting forward did not complete; using the five-launch forward from now on\n");
   }
-  int rc = predict_forward_tuned(h, h->st_states, head_args(h, 0), 1); if (rc) return rc;   // same buffers, batch of one
+  int rc = predict_forward_tuned(h, h->st_states, head_args(h, HEAD_PREDICT), 1); if (rc) return rc;   // same buffers, batch of one
   rc = fetch_small(h, h->q, (size_t)h->A * 4); if (rc) return rc;
   memcpy(q_out, h->h_f, (size_t)h->A * 4);
   return SDQN_OK;
@@ -514,7 +514,7 @@ static int train_host_tuple(sdqn_net_t h, const uint8_t* pre, const uint8_t* act
   }
   h->tuple_calls += 1; h->tuple_states_skipped += reuse ? 1 : 0; h->tuple_small_skipped += small_dev ? 1 : 0;
   StepArgs a = step_args(h); a.from_ring = 0; a.src = reuse ? owner->d_pre : h->st_states;
-  HeadArgs hd = head_args(h, 1);
+  HeadArgs hd = head_args(h, HEAD_TRAIN);
   if (small_dev) { hd.st_actions = owner->d_act; hd.st_rewards = owner->d_rew; hd.st_terminals = owner->d_term; }
   // prioritized memory, minibatch gathered from its last sample: weighted step + priority write-back (a foreign tuple: the standard step)
   int rc = per_owns_minibatch(owner) ? per_train_host_step(h, owner, a, hd) : run_train(h, a, hd); if (rc) return rc;
@@ -575,7 +575,7 @@ static int train_replay_slot(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* pin
   if (do_prep) { PrepArgs p = prep_args(h, r, pinned_idx); LAUNCH(K_PREP, launch_prep(p, g_stream, zero8)); }
   const int64_t* host_idx = r->h_idx + (pinned_idx - r->d_idx_view);      // the slot's HOST address (pinned_idx is its device alias)
   PrepArgs np; if (next_pinned) np = prep_args(h, r, next_pinned);
-  return run_ring_step(h, r, host_idx, head_args(h, 1), next_pinned ? &np : nullptr);
+  return run_ring_step(h, r, host_idx, head_args(h, HEAD_TRAIN), next_pinned ? &np : nullptr);
 }
 // float64 / other geometries: sample on the host, gather on the device into the replay handle's minibatch buffers, train from there
 static int gen_train_replay(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* idx_host) {

@@ -6,94 +6,33 @@
 //     dq[n][k A + a_n] = m_k(i_n) dc_k / K, zero elsewhere;  cost term = (sum_k m_k 0.5 d_k^2) / K, sum in head order
 //     d4     = 1[a4 > 0] sum_k W5[k A + a_n] dq_k  over the rows with m_k = 1, in head order
 //     maxq[n] = (float)((sum_k max_a Q_k(theta-, s')[a]) / K)
-// m_k: bootstrap.h.  One 512-thread workgroup per sample, as head_kernel and munchausen_head_kernel (sdqn_munchausen.hip): the fc4 slab
-// reduce + ReLU and the fc5 of slots 0 / 1 are the same loads, the same prod[][] transpose and the same single butterfly per row, over
-// A' rows, so Q(pre), Q(post), a4 are what the standard head of an A'-action net leaves.  Thread 0 computes the K targets; the dq row
-// replaces the (dead) target-net row in LDS and reaches the other threads with a bit mask of its live rows.  A kernel of its own name in
-// a translation unit of its own: head_kernel's template list and instantiation set stay what they are; K, A, the mask threshold and
+// m_k: bootstrap.h.  The front end over the A' rows and the fc5 dgrad are head_body.h.  Thread 0 computes the K targets; the dq row
+// replaces the (dead) target-net row in LDS and reaches the other threads with a bit mask of its live rows.  K, A, the mask threshold and
 // seed and the index pointer are a third kernel argument (BootArgs), StepArgs and HeadArgs keep their layout.
-// No scratch, no atomics; LDS = head_kernel's for the same bucket (minus one float).
-#include "kernels.h"
+#include "head_body.h"
 
 namespace sdqn {
 namespace {
 
 template <int AMAX, bool NSTEP>
 __global__ void __launch_bounds__(512) bootstrap_head_kernel(const StepArgs a, const HeadArgs h, const BootArgs b) {
-  const int n = blockIdx.x, j = threadIdx.x, lane = j & 63, wave = j >> 6;
+  const int n = blockIdx.x, j = threadIdx.x;
   __shared__ float prod[2 * AMAX][NFC];
   __shared__ float sh_q[2][AMAX];
   __shared__ int sh_rows;
-  const int A = a.A;                                   // K A rows (a train step: nz = 2)
-  const float* __restrict__ th0 = a.theta[0];
-  const float* __restrict__ th1 = a.theta[1];
-  const float* __restrict__ slab = a.slab4;
-  float a4v[2] = {0.0f, 0.0f};
-  const int64_t sstride = (int64_t)2 * a.B * NFC;
-  float t[2][7];
-  if (a.S4 == 7) {                                     // the built-in split: 14 independent loads in flight
-#pragma unroll
-    for (int z = 0; z < 2; ++z)
-#pragma unroll
-      for (int s = 0; s < 7; ++s) t[z][s] = slab[s * sstride + ((int64_t)z * a.B + n) * NFC + j];
-  }
-  float w5[2][AMAX];
-#pragma unroll
-  for (int act = 0; act < AMAX; ++act) {
-    const int ac = act < A ? act : A - 1;
-    w5[0][act] = th0[OFF5 + ac * NFC + j];
-    w5[1][act] = th1[OFF5 + ac * NFC + j];
-  }
+  const int A = a.A;                                   // K A rows
+  HeadFront<AMAX> f;
+  head_front_issue<AMAX>(a, n, j, f);
   int m_act = 0, m_term = 0; int64_t m_rew = 0, m_idx = 0;
   if (j == 0) {
     m_act = h.st_actions[n]; m_rew = h.st_rewards[n]; m_term = h.st_terminals[n];
     if (b.idx) m_idx = b.idx[n];
   }
   m_act = m_act < b.A ? m_act : b.A - 1;               // memory safety only: the host rejects out-of-range actions before launching
-  if (a.S4 == 7) {
-#pragma unroll
-    for (int z = 0; z < 2; ++z) { float v = 0.0f;
-#pragma unroll
-      for (int s = 0; s < 7; ++s) v += t[z][s];                                                   // fixed order
-      a4v[z] = v; }
-  } else {
-#pragma unroll
-    for (int z = 0; z < 2; ++z) { float v = 0.0f;
-      for (int s = 0; s < a.S4; ++s) v += slab[s * sstride + ((int64_t)z * a.B + n) * NFC + j];
-      a4v[z] = v; }
-  }
-#pragma unroll
-  for (int z = 0; z < 2; ++z) {
-    const float v = fmaxf(a4v[z], 0.0f);
-    a4v[z] = v;
-    a.a4[((int64_t)z * a.B + n) * NFC + j] = v;
-#pragma unroll
-    for (int act = 0; act < AMAX; ++act)
-      if (act < A) prod[z * A + act][j] = w5[z][act] * v;
-  }
-  __syncthreads();
-  for (int row = wave; row < 2 * A; row += 8) {
-    float p = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) p += prod[row][lane + 64 * k];                                    // fixed order
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) p += __shfl_xor(p, off, 64);
-    if (lane == 0) {
-      const int z = row / A, act = row - z * A;
-      sh_q[z][act] = p;
-      h.q[((int64_t)z * a.B + n) * A + act] = p;
-    }
-  }
-  __syncthreads();
+  head_front_q<AMAX>(a, h, n, j, f, prod, sh_q);
   if (j == 0) {
-    const int act = m_act, term = m_term, K = b.K, GA = b.A; const int64_t rew = m_rew;
-    double rr, gam;
-    if constexpr (NSTEP) { rr = __builtin_bit_cast(double, rew); gam = h.gamma_n; }
-    else {
-      rr = (double)rew;
-      rr = rr < h.min_reward ? h.min_reward : (rr > h.max_reward ? h.max_reward : rr);
-      gam = h.discount;
-    }
+    const int act = m_act, term = m_term, K = b.K, GA = b.A;
+    double rr, gam; head_reward<NSTEP>(h, m_rew, rr, gam);
     const float fK = (float)K;
     double msum = 0.0; float cost = 0.0f; int rows = 0;
     for (int k = 0; k < K; ++k) {
@@ -103,8 +42,7 @@ __global__ void __launch_bounds__(512) bootstrap_head_kernel(const StepArgs a, c
       msum += (double)m;
       const double y = term ? rr : rr + gam * (double)m;
       const float d = sh_q[0][k * GA + act] - (float)y;
-      float dc = d;
-      if (h.clip_error != 0.0f) dc = fminf(fmaxf(d, -h.clip_error), h.clip_error);
+      const float dc = head_clip(h, d);
       const int live = bootstrap_mask_bit(b.mask_seed, b.thresh, m_idx, k);
       if (live) { cost += 0.5f * (d * d); rows |= 1 << (k * GA + act); }
       for (int c = 0; c < GA; ++c) qp[c] = (live && c == act) ? dc / fK : 0.0f;   // the slice is dead: it becomes the dq row's
@@ -114,14 +52,7 @@ __global__ void __launch_bounds__(512) bootstrap_head_kernel(const StepArgs a, c
     sh_rows = rows;
   }
   __syncthreads();
-  const int rows = sh_rows;
-  // fc5 dgrad: delta4 = W5^T delta * 1[a4 > 0] over the live rows, in head order (W5 rows already in registers)
-  float acc = 0.0f;
-#pragma unroll
-  for (int r = 0; r < AMAX; ++r) if ((rows >> r) & 1) acc += w5[0][r] * sh_q[1][r];
-  const float d4v = a4v[0] > 0.0f ? acc : 0.0f;
-  if (a.h16) a.h_d4[(int64_t)n * NFC + j] = (half_t)(d4v * a.loss_scale);     // fp16 mode: loss-scaled half delta
-  else a.d4[(int64_t)n * NFC + j] = d4v;
+  head_back_rows<AMAX>(a, n, j, f, sh_rows, sh_q[1]);  // over the live rows, in head order
   if (j < A) h.dq[(int64_t)n * A + j] = sh_q[1][j];
 }
 
@@ -157,12 +88,11 @@ __global__ void __launch_bounds__(64) bootstrap_select_kernel(const T* __restric
 
 }  // namespace
 
-// launch_head's branch for HeadArgs::train == 4 (a.nz = 2; a.A = K b.A)
+// launch_head's branch for HEAD_BOOTSTRAP (a.nz = 2; a.A = K b.A)
 hipError_t launch_head_bootstrap(const StepArgs& a, const HeadArgs& h, const BootArgs& b, hipStream_t s) {
-  if (h.train != 4 || a.nz != 2 || a.bn || h.per_w || b.K < 1 || b.A < 1 || a.A != b.K * b.A || a.A > MAX_ACTIONS) return hipErrorInvalidValue;
+  if (h.train != HEAD_BOOTSTRAP || a.nz != 2 || a.bn || h.per_w || b.K < 1 || b.A < 1 || a.A != b.K * b.A || a.A > MAX_ACTIONS) return hipErrorInvalidValue;
   if (!b.idx && b.thresh < (1ull << 53)) return hipErrorInvalidValue;           // masks need the ring index
-  const int bucket = a.A <= 4 ? 0 : (a.A <= 8 ? 1 : 2);
-  const BootstrapHead k = h.nstep > 1 ? head_for<true>(bucket) : head_for<false>(bucket);
+  const BootstrapHead k = h.nstep > 1 ? head_for<true>(head_bucket(a.A)) : head_for<false>(head_bucket(a.A));
   SDQN_LAUNCH(k, dim3(a.B), dim3(512), 0, s, a, h, b);
   return hipGetLastError();
 }

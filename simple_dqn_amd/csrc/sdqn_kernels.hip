@@ -339,13 +339,13 @@ static HeadKernel head_for(int bucket) {
 
 hipError_t launch_head(const StepArgs& a, const HeadArgs& h, hipStream_t s, bool q_system_scope, const BootArgs* boot, const QuantArgs* quant) {
   if (h.train == HEAD_QUANTILE) return quant ? launch_head_quantile(a, h, *quant, s) : hipErrorInvalidValue;   // --quantiles: a kernel of its own (sdqn_quantile.hip)
-  if (h.train == 3) return launch_head_munchausen(a, h, s);                      // --munchausen: a kernel of its own (sdqn_munchausen.hip)
-  if (h.train == 4) return boot ? launch_head_bootstrap(a, h, *boot, s) : hipErrorInvalidValue;   // --bootstrap_heads: likewise (sdqn_bootstrap.hip)
-  if (h.train == 5) return launch_head_advantage(a, h, s);                       // --advantage_learning: likewise (sdqn_advantage.hip)
-  if (a.nz > 2 && (h.train != 2 || a.bn)) return hipErrorInvalidValue;          // (a third slot needs the Double DQN head's LDS)
+  if (h.train == HEAD_MUNCHAUSEN) return launch_head_munchausen(a, h, s);        // --munchausen: a kernel of its own (sdqn_munchausen.hip)
+  if (h.train == HEAD_BOOTSTRAP) return boot ? launch_head_bootstrap(a, h, *boot, s) : hipErrorInvalidValue;   // --bootstrap_heads: likewise (sdqn_bootstrap.hip)
+  if (h.train == HEAD_ADVANTAGE) return launch_head_advantage(a, h, s);          // --advantage_learning: likewise (sdqn_advantage.hip)
+  if (a.nz > 2 && (h.train != HEAD_DOUBLE || a.bn)) return hipErrorInvalidValue;   // (a third slot needs the Double DQN head's LDS)
   const int bucket = a.bn ? 3 : (a.A <= 4 ? 0 : (a.A <= 8 ? 1 : 2));
   const bool qsys = q_system_scope && !a.bn && !h.train;                         // acting path: Q-values straight into mapped host memory
-  const bool ddqn = h.train == 2, per = h.per_w && h.train, nstep = h.nstep > 1 && h.train;   // --double_dqn, --prioritized_replay, --n_step train steps
+  const bool ddqn = h.train == HEAD_DOUBLE, per = h.per_w && h.train, nstep = h.nstep > 1 && h.train;   // --double_dqn, --prioritized_replay, --n_step train steps
   static HeadKernel (*const select[9])(int) = {           // [nstep][per][ddqn], then the acting head
     head_for<false, false, false, false>, head_for<false, true, false, false>, head_for<false, false, true, false>, head_for<false, true, true, false>,
     head_for<false, false, false, true>, head_for<false, true, false, true>, head_for<false, false, true, true>, head_for<false, true, true, true>,

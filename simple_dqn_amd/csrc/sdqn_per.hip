@@ -425,7 +425,7 @@ int per_sample_host(sdqn_replay_s* r, uint32_t* mt, int64_t* idx_out, int64_t* d
 // from HBM.  Generic path (float64, other geometries; generic_net.hip): the same per_step launches, the gather of the sampled indexes,
 // then the generic step with its head in the weighted form (GenericNet::set_per).
 static HeadArgs per_head(sdqn_net_s* h, PerState* p) {
-  HeadArgs hd = head_args(h, 1);
+  HeadArgs hd = head_args(h, HEAD_TRAIN);
   hd.per_w = p->w; hd.per_p = p->newp; hd.per_alpha = p->alpha; hd.per_eps = p->eps;
   return hd;
 }

@@ -8,95 +8,36 @@
 //     dq[n][j A + a_n] = (sum_j' w_jj' clip(d_jj', -kappa, kappa) / kappa) / N^2, the sum in j' order; zero elsewhere
 //     cost term = (sum_jj' w_jj' L_kappa(d_jj') / kappa) / N^2, the sum in double in j-major order
 //     d4     = 1[a4 > 0] sum_j W5[j A + a_n] dq_j, in quantile order
-// One 512-thread workgroup per sample, as head_kernel and bootstrap_head_kernel (sdqn_bootstrap.hip): the fc4 slab reduce + ReLU and the
-// fc5 of slots 0 / 1 are the same loads, the same prod[][] transpose and the same single butterfly per row over A' rows, so Q(pre), Q(post)
-// and a4 are what the standard head of an A'-action net leaves.  Behind them the work is spread, not left to thread 0: thread t < N^2 owns
+// The front end over the A' rows and the fc5 dgrad are head_body.h.  Between them the work is spread, not left to thread 0: thread t < N^2 owns
 // the pair (j, j') = (t / N, t % N) — it restates m(a) and a* from the row in LDS (N A reads; no hand-off, no barrier), then its target and
 // its pair's two terms, which go to the dead prod[][] rows 0 / 1; thread r < A' sums dq row r's N terms in j' order; behind its own share
 // of the fc5 dgrad thread 0 adds the N^2 cost terms up in double, in the j-major order the rule states — a serial tail of every workgroup
 // (36 LDS reads and adds at N = 6, 81 at N = 9, 324 at (A = 1, N = 18)), not overlapped work.  N, A and the targets' read-back buffer are a third kernel argument
-// (QuantArgs); StepArgs and HeadArgs keep their layout.  No scratch, no atomics; LDS = head_kernel's for the same bucket (minus one float).
-#include "kernels.h"
+// (QuantArgs); StepArgs and HeadArgs keep their layout.
+#include "head_body.h"
 
 namespace sdqn {
 namespace {
 
 template <int AMAX, bool NSTEP>
 __global__ void __launch_bounds__(512) quantile_head_kernel(const StepArgs a, const HeadArgs h, const QuantArgs b) {
-  const int n = blockIdx.x, j = threadIdx.x, lane = j & 63, wave = j >> 6;
+  const int n = blockIdx.x, j = threadIdx.x;
   __shared__ float prod[2 * AMAX][NFC];
   __shared__ float sh_q[2][AMAX];
   __shared__ int sh_rows;
-  const int A = a.A;                                   // N A rows (a train step: nz = 2)
+  const int A = a.A;                                   // N A rows
   const int N = b.N, GA = b.A, NN = N * N;
-  const float* __restrict__ th0 = a.theta[0];
-  const float* __restrict__ th1 = a.theta[1];
-  const float* __restrict__ slab = a.slab4;
-  float a4v[2] = {0.0f, 0.0f};
-  const int64_t sstride = (int64_t)2 * a.B * NFC;
-  float t[2][7];
-  if (a.S4 == 7) {                                     // the built-in split: 14 independent loads in flight
-#pragma unroll
-    for (int z = 0; z < 2; ++z)
-#pragma unroll
-      for (int s = 0; s < 7; ++s) t[z][s] = slab[s * sstride + ((int64_t)z * a.B + n) * NFC + j];
-  }
-  float w5[2][AMAX];
-#pragma unroll
-  for (int act = 0; act < AMAX; ++act) {
-    const int ac = act < A ? act : A - 1;
-    w5[0][act] = th0[OFF5 + ac * NFC + j];
-    w5[1][act] = th1[OFF5 + ac * NFC + j];
-  }
+  HeadFront<AMAX> f;
+  head_front_issue<AMAX>(a, n, j, f);
   // minibatch metadata: the pair threads and the row threads only
   int m_act = 0, m_term = 0; int64_t m_rew = 0;
   if (j < NN || j < A) { m_act = h.st_actions[n]; m_rew = h.st_rewards[n]; m_term = h.st_terminals[n]; }
   m_act = m_act < GA ? m_act : GA - 1;                 // memory safety only: the host rejects out-of-range actions before launching
-  if (a.S4 == 7) {
-#pragma unroll
-    for (int z = 0; z < 2; ++z) { float v = 0.0f;
-#pragma unroll
-      for (int s = 0; s < 7; ++s) v += t[z][s];                                                   // fixed order
-      a4v[z] = v; }
-  } else {
-#pragma unroll
-    for (int z = 0; z < 2; ++z) { float v = 0.0f;
-      for (int s = 0; s < a.S4; ++s) v += slab[s * sstride + ((int64_t)z * a.B + n) * NFC + j];
-      a4v[z] = v; }
-  }
-#pragma unroll
-  for (int z = 0; z < 2; ++z) {
-    const float v = fmaxf(a4v[z], 0.0f);
-    a4v[z] = v;
-    a.a4[((int64_t)z * a.B + n) * NFC + j] = v;
-#pragma unroll
-    for (int act = 0; act < AMAX; ++act)
-      if (act < A) prod[z * A + act][j] = w5[z][act] * v;
-  }
-  __syncthreads();
-  for (int row = wave; row < 2 * A; row += 8) {
-    float p = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) p += prod[row][lane + 64 * k];                                    // fixed order
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) p += __shfl_xor(p, off, 64);
-    if (lane == 0) {
-      const int z = row / A, act = row - z * A;
-      sh_q[z][act] = p;
-      h.q[((int64_t)z * a.B + n) * A + act] = p;
-    }
-  }
-  __syncthreads();                                     // prod[][] is dead from here on: rows 0 / 1 take the pairs' gradient / cost terms
+  head_front_q<AMAX>(a, h, n, j, f, prod, sh_q);       // prod[][] is dead from here on: rows 0 / 1 take the pairs' gradient / cost terms
   if (j < NN) {                                        // pair (qj, qp): quantile qj of the online net against target qp
     const int qj = j / N, qp = j - qj * N;
     double mb; const int as = quantile_greedy(sh_q[1], N, GA, &mb);
-    double rr, gam;
-    if constexpr (NSTEP) { rr = __builtin_bit_cast(double, m_rew); gam = h.gamma_n; }
-    else {
-      rr = (double)m_rew;
-      rr = rr < h.min_reward ? h.min_reward : (rr > h.max_reward ? h.max_reward : rr);
-      gam = h.discount;
-    }
+    double rr, gam; head_reward<NSTEP>(h, m_rew, rr, gam);
     const double y = m_term ? rr : rr + gam * (double)sh_q[1][qp * GA + as];
     float g, rho; quantile_pair<float>(sh_q[0][qj * GA + m_act] - (float)y, quantile_tau<float>(qj, N), h.clip_error, &g, &rho);
     prod[0][j] = g; prod[1][j] = rho;
@@ -121,14 +62,7 @@ __global__ void __launch_bounds__(512) quantile_head_kernel(const StepArgs a, co
     h.dq[(int64_t)n * A + j] = v;
   }
   __syncthreads();
-  const int rows = sh_rows;
-  // fc5 dgrad: delta4 = W5^T delta * 1[a4 > 0] over the taken action's N rows, in quantile order (W5 rows already in registers)
-  float acc = 0.0f;
-#pragma unroll
-  for (int r = 0; r < AMAX; ++r) if ((rows >> r) & 1) acc += w5[0][r] * sh_q[1][r];
-  const float d4v = a4v[0] > 0.0f ? acc : 0.0f;
-  if (a.h16) a.h_d4[(int64_t)n * NFC + j] = (half_t)(d4v * a.loss_scale);     // fp16 mode: loss-scaled half delta
-  else a.d4[(int64_t)n * NFC + j] = d4v;
+  head_back_rows<AMAX>(a, n, j, f, sh_rows, sh_q[1]);  // over the taken action's N rows, in quantile order
   if (j == 0) {
     double cost = 0.0;
     for (int p = 0; p < NN; ++p) cost += (double)prod[1][p];                                      // j-major
@@ -154,12 +88,11 @@ __global__ void __launch_bounds__(64) quantile_mean_kernel(const T* __restrict__
 
 }  // namespace
 
-// launch_head's branch for HeadArgs::train == 6 (a.nz = 2; a.A = b.N b.A)
+// launch_head's branch for HEAD_QUANTILE (a.nz = 2; a.A = b.N b.A)
 hipError_t launch_head_quantile(const StepArgs& a, const HeadArgs& h, const QuantArgs& b, hipStream_t s) {
   if (h.train != HEAD_QUANTILE || a.nz != 2 || a.bn || h.per_w || b.N < 2 || b.A < 1 || a.A != b.N * b.A || a.A > MAX_ACTIONS || !(h.clip_error > 0.0f))
     return hipErrorInvalidValue;                       // (N <= 18: at most 324 pair threads; N A <= 18 rows)
-  const int bucket = a.A <= 4 ? 0 : (a.A <= 8 ? 1 : 2);
-  const QuantileHead k = h.nstep > 1 ? head_for<true>(bucket) : head_for<false>(bucket);
+  const QuantileHead k = h.nstep > 1 ? head_for<true>(head_bucket(a.A)) : head_for<false>(head_bucket(a.A));
   SDQN_LAUNCH(k, dim3(a.B), dim3(512), 0, s, a, h, b);
   return hipGetLastError();
 }

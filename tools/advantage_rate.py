@@ -37,7 +37,7 @@ for dt in ([a.datatype] if a.datatype else ["float32", "float16"]):
         med = {k: float(np.median(v)) for k, v in rate.items()}
         rec = {"datatype": dt, "batch_size": B, "persistent": bool(a.persistent)}
         for k, v in med.items():
-            rec[k + "_steps_per_s"], rec[k + "_us"] = round(v, 1), round(1e6 / v, 2)
+            rec[k + "_steps_per_s"], rec[k + "_us"], rec[k + "_all"] = round(v, 1), round(1e6 / v, 2), [round(x, 1) for x in rate[k]]
         if a.net == "all":
             rec["ratio_to_standard"] = round(med["advantage"] / med["standard"], 4)
             rec["ratio_to_munchausen"] = round(med["advantage"] / med["munchausen"], 4)

@@ -37,6 +37,7 @@ def main():
         out = {"batch_size": B}
         for k in nets:
             out[k + "_steps_per_s"] = round(float(np.median(rate[k])), 1); out[k + "_us"] = round(1e6 / float(np.median(rate[k])), 2)
+            out[k + "_all"] = [round(x, 1) for x in rate[k]]
         if len(nets) == 2:
             out["ratio"] = round(out["bootstrap_steps_per_s"] / out["standard_steps_per_s"], 4)
         print(json.dumps(out), flush=True)

@@ -37,4 +37,5 @@ for dt in ([a.datatype] if a.datatype else ["float32", "float16"]):
             continue
         s, d = float(np.median(rate["standard"])), float(np.median(rate["munchausen"]))
         print(json.dumps({"datatype": dt, "batch_size": B, "standard_steps_per_s": round(s, 1), "munchausen_steps_per_s": round(d, 1),
-                          "ratio": round(d / s, 4), "standard_us": round(1e6 / s, 2), "munchausen_us": round(1e6 / d, 2)}), flush=True)
+                          "ratio": round(d / s, 4), "standard_us": round(1e6 / s, 2), "munchausen_us": round(1e6 / d, 2),
+                          "standard_all": [round(x, 1) for x in rate["standard"]], "munchausen_all": [round(x, 1) for x in rate["munchausen"]]}), flush=True)

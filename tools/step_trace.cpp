@@ -188,7 +188,7 @@ static void train(const Cfg& c) {
   if (c.opt == O_TUPLE) { a.from_ring = 0; a.src = h->st_states; }
   else { a.from_ring = 1; a.src = dummy<const uint8_t>("ring"); a.idx = h->d_idx; h->host_idx_cur = g_host_idx; }
   PrepArgs next; memset(&next, 0, sizeof next); next.B = c.B;
-  footer(run_train(h, a, head_args(h, 1), c.next ? &next : nullptr), h);
+  footer(run_train(h, a, head_args(h, HEAD_TRAIN), c.next ? &next : nullptr), h);
   delete h; g_h = nullptr;
 }
 static void predict(const Cfg& c, int B1) {
@@ -196,7 +196,7 @@ static void predict(const Cfg& c, int B1) {
   fill(h, c);
   header(B1 ? "predict_one" : "predict", c);
   h->w4_pending = c.dp == DP_OVERLAP;        // (the previous step's fc4 update may still be running)
-  footer(predict_forward_tuned(h, h->st_states, head_args(h, 0), B1), h);
+  footer(predict_forward_tuned(h, h->st_states, head_args(h, HEAD_PREDICT), B1), h);
   delete h; g_h = nullptr;
 }
 static void apply(const Cfg& c, bool half_pending) {

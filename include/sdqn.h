@@ -405,6 +405,35 @@ int sdqn_quantile_loss(int N, int A, double kappa, const float* q_pre_row, const
                        double gamma, float* dq_out, float* cost_out);
 /* the acting rule on one raw Q row q[N A]: the first maximum of the quantile means (a NaN counts as one) */
 int sdqn_quantile_act(const float* q, int N, int A, int* action);
+/* The dueling architecture, --dueling (Wang, Schaul, Hessel, van Hasselt, Lanctot and de Freitas 2016; no reference counterpart).
+ * The network is created with num_actions = A + 1 outputs (<= 18): output row 0 is V, row 1 + a is Adv_a, and actions in transitions are < A.
+ * The two streams are the halves of fc4's 512 hidden units: V reads units j < 256 only, every Adv_a units j >= 256 only.  fc5's other
+ * entries are exactly +0.0 in the online and the target weights at every point a forward can read them: the setter zeroes them, and so do
+ * sdqn_net_set_weights / _f64 on layer 4 of which 0 / 1 (a caller's non-zero values there are accepted and dropped); the same entries of the
+ * flat gradient are set to +0.0 behind its local sums (and the all-reduce), in front of clip_grad_norm's norm and of the optimizer, which
+ * moves a weight with gradient 0 by exactly 0.  With Q(s, a) = (float)((V + Adv_a) - (sum_b Adv_b) / A) (double, the sum in action order):
+ *   y = r_c + (terminal ? 0 : discount max_a Q(theta-, s', a)),   delta = Q(theta, s, a_n) - (float)y,
+ *   c = the standard head's clipped (and, prioritized replay, weighted) error,   dq[0] = c,   dq[1 + b] = c (1[b = a_n] - 1 / A)
+ * (option "n_step": R, the done flag and discount^n in their places; the cost term and the new priority are the standard head's on delta).
+ * maxpostq (sdqn_net_last_q) = max_a Q(theta-, s', a).  Acting: the game loops and sdqn_net_act_greedy take the first maximum of Q(s, .),
+ * collecting and evaluating alike.  Every train step runs the split optimizer tail (local sums, mask, apply).  on = 0 (default) is the
+ * network without any of this.  on = 1 is SDQN_ERR_ARG together with option "double_dqn", sdqn_net_set_munchausen,
+ * sdqn_net_set_advantage_learning, sdqn_net_set_bootstrap K > 1, sdqn_net_set_quantiles N > 1 and batch_norm (either order). */
+int sdqn_net_set_dueling(sdqn_net_t h, int on);
+int sdqn_net_get_dueling(sdqn_net_t h, int* on);      /* the pointer may be NULL */
+/* what the last train step's head left (dueling on; sync): y [B] and delta [B] as stored in the network's precision, dq [B][A + 1]; widened
+ * to double on every path; any pointer may be NULL */
+int sdqn_net_last_dueling_step(sdqn_net_t h, double* y, double* delta, double* dq);
+/* the rule on one sample, host side (no device), from its two stored rows q_pre_row / q_post_row [A + 1]: reward is r_c (n_step: R), gamma
+ * the discount (discount^n), clip_error 0 = no clip; per != 0: per_weight multiplies the cost term and the clipped error and *priority_out
+ * receives (|delta| + per_eps)^per_alpha.  dq_out [A + 1] and *cost_out receive what the train step's head writes for that sample;
+ * y_out, delta_out, maxq_out, priority_out may be NULL */
+int sdqn_dueling_loss(int A, double clip_error, const float* q_pre_row, const float* q_post_row, int action, double reward, int terminal,
+                      double gamma, int per, double per_weight, double per_alpha, double per_eps, float* dq_out, float* cost_out,
+                      float* y_out, float* delta_out, float* maxq_out, float* priority_out);
+/* the acting rule on one raw row q[A + 1]: the first maximum of Q(s, .) (a NaN Q(a) is never chosen over a number, a NaN Q(0) stays);
+ * q_out (may be NULL) receives the A action values */
+int sdqn_dueling_act(const float* q, int A, int* action, float* q_out);
 /* option "double_dqn" (0 default / 1, any configuration, switchable between steps): Double DQN targets (van Hasselt, Guez and Silver
  * 2016): the online net picks each poststate's action, the target net values it (see sdqn_net_last_q).  The online net's forward on
  * the poststates rides as a third net slot in the step's own forward launches (batch_norm: a forward of its own in front of the step,

@@ -143,6 +143,12 @@ SIGNATURES = {
     "sdqn_net_last_quantile_step": (C.c_int, [_vp, _f64p, _f64p]),
     "sdqn_quantile_loss": (C.c_int, [C.c_int, C.c_int, C.c_double, _f32p, _f32p, C.c_int, C.c_double, C.c_int, C.c_double, _f32p, _f32p]),
     "sdqn_quantile_act": (C.c_int, [_f32p, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "sdqn_net_set_dueling": (C.c_int, [_vp, C.c_int]),
+    "sdqn_net_get_dueling": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "sdqn_net_last_dueling_step": (C.c_int, [_vp, _f64p, _f64p, _f64p]),
+    "sdqn_dueling_loss": (C.c_int, [C.c_int, C.c_double, _f32p, _f32p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double,
+                                    C.c_double, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]),
+    "sdqn_dueling_act": (C.c_int, [_f32p, C.c_int, C.POINTER(C.c_int), _f32p]),
     "sdqn_net_sync": (C.c_int, [_vp]),
     "sdqn_net_apply_update": (C.c_int, [_vp, C.c_double]),
     "sdqn_net_grad_to_half": (C.c_int, [_vp, C.POINTER(C.c_uint16), C.c_int64]),

@@ -57,7 +57,8 @@ class Agent:
         self._boot = getattr(deep_q_network, "bootstrap_heads", 1) > 1
         # --quantiles: the net acts on the mean over its quantiles, training and testing alike; like the Q-heads' rule it
         # turns a raw row of the net into an action (net.acting_action), but it has no mode and no episode bookkeeping
-        self._reduced_acting = self._boot or getattr(deep_q_network, "quantiles", 1) > 1
+        # --dueling: likewise, the first maximum of V + Adv - mean(Adv) over the net's A + 1 outputs
+        self._reduced_acting = self._boot or getattr(deep_q_network, "quantiles", 1) > 1 or bool(getattr(deep_q_network, "dueling", False))
         self._per = getattr(replay_memory, "prioritized", False)
         if self._per:
             self._beta0, self._beta_steps = float(args.priority_beta), int(args.priority_beta_steps)

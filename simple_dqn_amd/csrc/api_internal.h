@@ -148,6 +148,12 @@ struct sdqn_net_s {
   // quantiles (the game loops: one launch into boot_q, which the two options — refused together — share).  quant_targets: [B][quant_N]
   // the last step's targets (tuned path; sdqn_net_debug_read "quantile_targets"), allocated by the setter
   int quant_N = 1; float* quant_targets = nullptr;
+  // --dueling (sdqn_net_set_dueling; dueling.h): the net's A outputs are V and A - 1 advantages over the two halves of fc4's
+  // units; fc5's entries outside the two blocks are +0.0 in theta and theta_t (masked where weights are set) and in g before it is clipped
+  // or applied (TailPlan::mask).  Train steps end their forward with the dueling head (HEAD_DUELING), the acting paths reduce a row to its
+  // A - 1 action values (the game loops: one launch into boot_q).  duel_step: [2][B] the last step's y and delta (tuned path;
+  // sdqn_net_debug_read "dueling_step"), allocated by the setter
+  bool dueling = false; float* duel_step = nullptr;
   int n_step = 1;                          // --n_step (option "n_step"): poststate frame offset of the ring paths, n-step head
   double target_tau = 0.0;                 // --target_tau (sdqn_net_set_target_tau): > 0: every train step is followed by one soft target update
   // --clip_grad_norm (sdqn_net_set_clip_grad_norm): > 0: the flat gradient is scaled to this global L2 norm (of the MEAN
@@ -248,12 +254,13 @@ enum UpdateForm { UPD_SINGLE = 0, UPD_DP_SERIAL = 1, UPD_DP_OVERLAP = 2, UPD_GRA
 // rides in it, the LaunchVariant bits.  The default changes nothing (step_args hands out all F4_TILES tiles).
 constexpr int F4_TILES = (NIN4 / 32) * (NFC / 32);
 struct LaunchPlan { int xcd_keep = ~0, xcd_bits = 0, variant = 0, f4w_first = 0, f4w_count = F4_TILES; };
-// The optimizer tail (run_update_tail): [mode 1: local sums -> g] -> [exchange] -> [clip] -> apply (mode 2, or mode 0 = sums and apply in one
+// The optimizer tail (run_update_tail): [mode 1: local sums -> g] -> [exchange] -> [mask] -> [clip] -> apply (mode 2, or mode 0 = sums and apply in one
 // launch) -> [BatchNorm parameters].  The next step's prep rides in the last update launch of the sequence.
 enum Exchange { XCH_NONE = 0, XCH_F32, XCH_HALF, XCH_GROUPED };   // all-reduce of g: fp32 | as half (float16 nets) | overlapped form: the conv and fc5 ranges as one group
 struct TailPlan {
   bool reduce_first = false;
   Exchange exchange = XCH_NONE;
+  bool mask = false;                       // --dueling: fc5's block mask on g, one launch behind the sums / exchange, in front of the clip
   bool clip = false;                       // --clip_grad_norm: the two clip launches in front of the apply launch
   bool ovf = false;                        // the gradient came through the half payload: the apply launch honours the overflow flag
   int apply_mode = 0;                      // UpdateArgs::mode of the apply launch: 0 | 2 | -1 nothing is applied (grad_only)
@@ -300,7 +307,8 @@ int ensure_slots3(sdqn_net_s* h);                                  // room for a
 int target_blend(sdqn_net_s* h, double tau);                       // one soft target update now (tau in (0, 1]; the caller has joined g_comm)
 int step_blend(sdqn_net_s* h);                                     // what every applied train step ends with: the blend of --target_tau, or nothing
 int gen_step_done(sdqn_net_s* h);                                  // generic path: a train step was enqueued ([clip + deferred update,] counter, step_blend)
-inline int game_actions(const sdqn_net_s* h) { return h->A / (h->boot_K * h->quant_N); }   // the actions a transition may hold (--bootstrap_heads / --quantiles: A is K / N times that)
+// the actions a transition may hold (--bootstrap_heads / --quantiles: A is K / N times that; --dueling: one more, the V row)
+inline int game_actions(const sdqn_net_s* h) { return h->dueling ? h->A - 1 : h->A / (h->boot_K * h->quant_N); }
 inline bool clip_on(const sdqn_net_s* h) { return h->clip_grad_norm > 0.0; }
 int clip_gradient(sdqn_net_s* h, double bsz);                      // --clip_grad_norm: the two launches on g between update modes 1 and 2 (nothing when off)
 StepPlan step_plan(const sdqn_net_s* h);

@@ -12,8 +12,11 @@
 #include "problems.h"          // NStepArgs
 #include "bootstrap.h"         // BootArgs
 #include "quantile.h"          // QuantArgs
+#include "dueling.h"           // DuelArgs
 
 namespace sdqn {
+
+hipError_t launch_dueling_mask(void* w5, bool f64, int rows, int H, hipStream_t s);      // sdqn_dueling.hip (kernels.h)
 
 struct GenericNet {
   virtual ~GenericNet() {}
@@ -65,6 +68,11 @@ struct GenericNet {
   // --quantiles (quantile.h): N > 1 arms the quantile branch of the TD head (the net has N x game-A outputs; clip_error is kappa)
   virtual hipError_t set_quantiles(int N) = 0;
   virtual hipError_t last_quantile_step(double* targets, double* dq) = 0;      // the last train step's [B][N] targets and [B][A] dq row, as doubles
+  // --dueling (dueling.h): arms the dueling branch of the TD head (the net has game-A + 1 outputs) and fc5's block mask on g
+  // in front of the clip / the optimizer; dueling_mask_weights applies the mask to W5 of theta (0) or theta_t (1)
+  virtual hipError_t set_dueling(bool on) = 0;
+  virtual hipError_t dueling_mask_weights(int which) = 0;
+  virtual hipError_t last_dueling_step(double* y, double* delta, double* dq) = 0;
   // --n_step: n > 1 makes the train steps read rew as the n-step returns (float64 bits) and term as the done flags, and
   // bootstrap with gamma_n; n = 1: the standard step
   virtual void set_nstep(int n, double gamma_n) = 0;

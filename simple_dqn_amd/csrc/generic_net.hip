@@ -173,9 +173,20 @@ __global__ void head_kernel(const T* __restrict__ q_on, const T* __restrict__ q_
                             T* __restrict__ cost_terms, T* __restrict__ maxq, int N, int A, double discount, double minr, double maxr, T clip,
                             const T* __restrict__ q_sel, const float* __restrict__ per_w, float* __restrict__ per_p, double per_alpha, double per_eps,
                             int nstep, double gamma_n, const T* __restrict__ q_mu, double mu_alpha, double mu_tau, double mu_clip, const BootArgs boot,
-                            double al_alpha, int al_persistent, const QuantArgs quant, T* __restrict__ q_targets) {
+                            double al_alpha, int al_persistent, const QuantArgs quant, T* __restrict__ q_targets, const DuelArgs duel,
+                            T* __restrict__ duel_step) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
+  if (duel.on) {                                                              // --dueling: dueling.h's rule on this sample's two rows
+    const int GA = duel.A, at = act[n] < GA ? act[n] : GA - 1;
+    double r, gam = discount;
+    if (nstep > 1) { r = __builtin_bit_cast(double, rew[n]); gam = gamma_n; }
+    else { r = (double)rew[n]; r = r < minr ? minr : (r > maxr ? maxr : r); }
+    cost_terms[n] = dueling_sample<T>(q_on + (int64_t)n * A, q_tg + (int64_t)n * A, GA, at, r, term[n], gam, clip, per_w != nullptr,
+                                        per_w ? (T)per_w[n] : (T)1, per_alpha, per_eps, dq + (int64_t)n * A, duel_step ? duel_step + n : nullptr,
+                                        duel_step ? duel_step + N + n : nullptr, maxq + n, per_p ? per_p + n : nullptr);
+    return;
+  }
   if (quant.N > 1) {                                                          // --quantiles: quantile.h's rule on this sample's two rows; clip is kappa
     const int GA = quant.A, at = act[n] < GA ? act[n] : GA - 1;
     double r, gam = discount;
@@ -436,7 +447,7 @@ class GenericNetT : public GenericNet {
     hipLaunchKernelGGL(head_kernel<T>, dim3((B + 63) / 64), dim3(64), 0, st, (const T*)q, (const T*)(q + (int64_t)B * A), actions, rew, term,
                        dq, cost_terms, maxq, B, A, cfg.discount_rate, cfg.min_reward, cfg.max_reward, (T)cfg.clip_error, (const T*)(dd ? q_sel : nullptr),
                        per_w, per_p, per_alpha, per_eps, nstep, gamma_n, (const T*)((munchausen || advantage) ? q_mu : nullptr), mu_alpha, mu_tau, mu_clip, boot,
-                       advantage ? al_alpha : 0.0, al_persistent ? 1 : 0, quant, q_targets);
+                       advantage ? al_alpha : 0.0, al_persistent ? 1 : 0, quant, q_targets, duel, duel_step);
     hipLaunchKernelGGL(cost_kernel<T>, dim3(1), dim3(64), 0, st, (const T*)cost_terms, cost, cost_sum, B);
     // ---- bprop (A8) :162
     GCHK(gemm(ga(dq, 1, A, act[3], 512, 1, g + off[4], A, 512, B)));                                   // gW5 = dq^T @ a4
@@ -455,6 +466,7 @@ class GenericNetT : public GenericNet {
         hipLaunchKernelGGL(col2im_kernel<T>, dim3(grid_for(total)), dim3(256), 0, st, (const T*)dcol, (const T*)act[l - 1], dact[l - 1], total, c);
       }
     }
+    if (duel.on) GCHK(launch_dueling_mask(g + off[4], sizeof(T) == 8, A, 512, st));                  // --dueling: the clip and the optimizer see the masked g
     // ---- optimizer :165
     OptArgs<T> u; u.w = theta; u.s1 = s1; u.s2 = s2; u.g = g; u.n = NP; u.opt = cfg.optimizer;
     u.bsz = (T)B; u.rho = (T)cfg.decay_rate; u.omr = (T)(1.0 - cfg.decay_rate); u.lr = (T)cfg.learning_rate; u.eps = (T)cfg.epsilon;
@@ -565,6 +577,25 @@ class GenericNetT : public GenericNet {
     if (dq_host) GCHK(fetch(dq, (int64_t)B * A, dq_host, true));
     return hipSuccess;
   }
+  DuelArgs duel = {0, 0, nullptr}; T* duel_step = nullptr;            // duel_step: [2][B] the last step's y and delta in T (duel.step is the tuned path's float buffer)
+  hipError_t set_dueling(bool on) override {
+    if (on && (double_dqn || munchausen || advantage || boot.K > 1 || quant.N > 1 || A < 2)) return hipErrorInvalidValue;
+    if (on && !duel_step) GCHK(dalloc(&duel_step, (int64_t)2 * B));
+    duel.on = on ? 1 : 0; duel.A = A - 1;
+    return hipSuccess;
+  }
+  hipError_t dueling_mask_weights(int which) override {
+    T* w = which ? theta_t : theta;
+    if (which && theta_t == theta) return hipSuccess;
+    return launch_dueling_mask(w + off[4], sizeof(T) == 8, A, 512, st);
+  }
+  hipError_t last_dueling_step(double* y, double* delta, double* dq_host) override {
+    if (!duel.on || !duel_step) return hipErrorInvalidValue;
+    if (y) GCHK(fetch(duel_step, B, y, true));
+    if (delta) GCHK(fetch(duel_step + B, B, delta, true));
+    if (dq_host) GCHK(fetch(dq, (int64_t)B * A, dq_host, true));
+    return hipSuccess;
+  }
   hipError_t boot_idx(const int64_t* idx) override {
     boot.idx = nullptr;
     if (!idx) return hipSuccess;
@@ -589,7 +620,7 @@ class GenericNetT : public GenericNet {
   }
   bool munchausen_on() const override { return munchausen; }
   hipError_t set_advantage_learning(bool on, double alpha, bool persistent) override {
-    if (on && (double_dqn || munchausen || boot.K > 1 || quant.N > 1 || !(alpha > 0.0 && alpha < 1.0))) return hipErrorInvalidValue;
+    if (on && (double_dqn || munchausen || boot.K > 1 || quant.N > 1 || duel.on || !(alpha > 0.0 && alpha < 1.0))) return hipErrorInvalidValue;
     if (on && !q_mu) GCHK(dalloc(&q_mu, (int64_t)B * A));
     advantage = on; al_alpha = on ? alpha : 0.0; al_persistent = on && persistent;
     return hipSuccess;

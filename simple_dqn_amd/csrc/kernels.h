@@ -9,6 +9,7 @@
 #include "launch_route.h"
 #include "bootstrap.h"
 #include "quantile.h"
+#include "dueling.h"
 
 namespace sdqn {
 
@@ -162,10 +163,15 @@ hipError_t launch_r3(const Route& r, int id, const StepArgs& a, const LaunchTune
 hipError_t launch_bt(const Route& r, int id, const StepArgs& a, const LaunchTune& t, hipStream_t s);       // sdqn_kernels_bt.hip: block tiles and the hand-written kernels beside them
 hipError_t launch_ss(const Route& r, int id, const StepArgs& a, const LaunchTune& t, hipStream_t s);       // sdqn_kernels_ss.hip: sample-stationary convolution chains
 hipError_t launch_kernel(int id, const StepArgs& a, const LaunchTune& t, hipStream_t s);     // the GEMM-shaped stages (single or multi-problem launches)
-// q_system_scope: h.q is mapped host memory (acting path); boot / quant: what h.train == HEAD_BOOTSTRAP / HEAD_QUANTILE needs beside
-// the two structs (refused without it)
+// q_system_scope: h.q is mapped host memory (acting path); boot / quant / duel: what h.train == HEAD_BOOTSTRAP / HEAD_QUANTILE / HEAD_DUELING
+// needs beside the two structs (refused without it)
 hipError_t launch_head(const StepArgs& a, const HeadArgs& h, hipStream_t s, bool q_system_scope = false, const BootArgs* boot = nullptr,
-                       const QuantArgs* quant = nullptr);
+                       const QuantArgs* quant = nullptr, const DuelArgs* duel = nullptr);
+hipError_t launch_head_dueling(const StepArgs& a, const HeadArgs& h, const DuelArgs& b, hipStream_t s);     // sdqn_dueling.hip: what launch_head runs for HEAD_DUELING
+// sdqn_dueling.hip: fc5's block mask on the [rows][H] fc5 range of a flat vector (float or double): the entries outside the two streams become +0.0
+hipError_t launch_dueling_mask(void* w5, bool f64, int rows, int H, hipStream_t s);
+// sdqn_dueling.hip: [M][A + 1] rows -> [M][A] action values Q = V + Adv - mean(Adv) (float or double)
+hipError_t launch_dueling_q(const void* q, void* out, bool f64, int M, int A, hipStream_t s);
 hipError_t launch_head_quantile(const StepArgs& a, const HeadArgs& h, const QuantArgs& b, hipStream_t s);     // sdqn_quantile.hip: what launch_head runs for HEAD_QUANTILE
 // sdqn_quantile.hip: [M][N A] Q rows -> [M][A] action values, the mean over the quantiles (float or double)
 hipError_t launch_quantile_mean(const void* q, void* out, bool f64, int M, int N, int A, hipStream_t s);

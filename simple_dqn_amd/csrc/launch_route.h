@@ -32,10 +32,11 @@ enum HeadMode {
   HEAD_MUNCHAUSEN,      // ... with Munchausen targets (--munchausen; munchausen_head_kernel, sdqn_munchausen.hip)
   HEAD_BOOTSTRAP,       // train step of a K-head bootstrapped net (--bootstrap_heads; bootstrap_head_kernel, sdqn_bootstrap.hip, its BootArgs beside HeadArgs)
   HEAD_ADVANTAGE,       // train step with advantage-learning targets (--advantage_learning; advantage_head_kernel, sdqn_advantage.hip)
-  HEAD_QUANTILE         // train step of an N-quantile net (--quantiles N > 1; quantile_head_kernel, sdqn_quantile.hip, its QuantArgs beside HeadArgs;
+  HEAD_QUANTILE,        // train step of an N-quantile net (--quantiles N > 1; quantile_head_kernel, sdqn_quantile.hip, its QuantArgs beside HeadArgs;
                         // HeadArgs::clip_error is the Huber threshold kappa there)
+  HEAD_DUELING          // train step of a dueling net (--dueling; dueling_head_kernel, sdqn_dueling.hip, its DuelArgs beside HeadArgs)
 };
-static_assert(HEAD_TRAIN == 1 && HEAD_DOUBLE == 2 && HEAD_MUNCHAUSEN == 3 && HEAD_BOOTSTRAP == 4 && HEAD_ADVANTAGE == 5 && HEAD_QUANTILE == 6, "head modes are public numbers");
+static_assert(HEAD_TRAIN == 1 && HEAD_DOUBLE == 2 && HEAD_MUNCHAUSEN == 3 && HEAD_BOOTSTRAP == 4 && HEAD_ADVANTAGE == 5 && HEAD_QUANTILE == 6 && HEAD_DUELING == 7, "head modes are public numbers");
 static_assert(K_BN == 19 && K_WGRADS == 24 && K_ACT == 25 && K_COLLECT == 26 && K_TARGET == 27 && K_COUNT == 28, "kernel ids are public numbers");
 
 // LaunchTune::variant — the launch variants the step's orchestration asks for (sdqn_api_step.hip decides, resolve_route tests); bit 0 is unused

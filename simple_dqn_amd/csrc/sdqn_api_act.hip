@@ -175,6 +175,7 @@ extern "C" int sdqn_net_act_greedy(sdqn_net_t h, sdqn_statebuf_t sb, int* action
     else *action = bootstrap_vote(q + bootstrap_head_of(bootstrap_head_seed(h->boot_seed), h->boot_K, 0, (uint64_t)h->boot_episode) * GA, 1, GA, votes);
   }
   if (h->quant_N > 1) *action = quantile_act(q, h->quant_N, game_actions(h));     // --quantiles: the first maximum of the quantile means
+  if (h->dueling) *action = dueling_act(q, game_actions(h));                      // --dueling: the first maximum of V + Adv - mean(Adv)
   if (q_out) memcpy(q_out, q, (size_t)A * 4);
   return SDQN_OK;
 }

@@ -216,6 +216,7 @@ int gen_set(sdqn_net_s* h, int which, int layer, const void* w, int64_t n, bool 
   ARGCHK(which != 4 || h->cfg.optimizer != 0, "this optimizer has no second state");
   ARGCHK(n == h->gen->layer_size(layer), "layer %d holds %lld values, got %lld", layer, (long long)h->gen->layer_size(layer), (long long)n);
   GENCHK(h->gen->set_param(which, layer, w, f64));
+  if (h->dueling && layer == 4 && which <= 1) GENCHK(h->gen->dueling_mask_weights(which));      // --dueling: as sdqn_net_set_weights
   return SDQN_OK;
 }
 int gen_get(sdqn_net_s* h, int which, int layer, void* w, int64_t n, bool f64) {
@@ -262,6 +263,10 @@ extern "C" int sdqn_net_set_weights(sdqn_net_t h, int which, int layer, const fl
   for (int64_t r = 0; r < rows; ++r) for (int64_t c = 0; c < cols; ++c) tmp[(size_t)neon_to_internal(layer, r, c)] = w[r * cols + c];
   { int rc_ = join_comm(h); if (rc_) return rc_; } HIPCHK(hipStreamSynchronize(g_stream));
   HIPCHK(hipMemcpy(which_buf(h, which) + off, tmp.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+  if (h->dueling && layer == 4 && which <= 1) {  // --dueling: whatever the caller's W5 holds outside the two streams' blocks becomes +0.0
+    HIPCHK(launch_dueling_mask(which_buf(h, which) + OFF5, false, h->A, NFC, g_stream));
+    HIPCHK(hipStreamSynchronize(g_stream));
+  }
   if (h->cfg.datatype == 1 && which <= 1) {      // fp16 mode: the half copies follow the master weights
     const int zz = (which == 1 && h->theta_t != h->theta) ? 1 : 0;
     HIPCHK(launch_refresh16(zz ? h->theta_t : h->theta, h->wh[zz], h->wht[zz], g_stream));
@@ -447,7 +452,7 @@ extern "C" int sdqn_net_apply_update(sdqn_net_t h, double bsz) {
   { int rc = join_comm(h); if (rc) return rc; }
   h->spec_pending = false;
   TailPlan t;                              // the step's optimizer tail from "clip" on, with the caller's divisor
-  t.clip = clip_on(h); t.apply_mode = 2; t.divisor = bsz;
+  t.mask = h->dueling; t.clip = clip_on(h); t.apply_mode = 2; t.divisor = bsz;
   t.ovf = h->half_payload_pending;         // the gradient came back through the half payload: same overflow rule as the RCCL path
   h->half_payload_pending = false;
   const int rc = run_update_tail(h, make_update_args(h, step_args(h)), t);
@@ -553,6 +558,7 @@ extern "C" int sdqn_net_set_munchausen(sdqn_net_t h, int on, double alpha, doubl
   if (on) {
     ARGCHK(h->boot_K == 1, "munchausen cannot be combined with bootstrap_heads %d", h->boot_K);
     ARGCHK(h->quant_N == 1, "munchausen cannot be combined with quantiles %d", h->quant_N);
+    ARGCHK(!h->dueling, "munchausen cannot be combined with dueling");
     ARGCHK(!(h->al_alpha > 0.0), "munchausen cannot be combined with advantage_learning: both targets want q slot 2 for a head of their own");
     ARGCHK(h->cfg.batch_norm == 0.0, "munchausen cannot be combined with batch_norm: inference-mode statistics for its third forward are not defined");
     ARGCHK(h->gen || !h->double_dqn, "munchausen cannot be combined with double_dqn: the Munchausen target has no argmax for the online net to choose");
@@ -583,6 +589,7 @@ extern "C" int sdqn_net_set_advantage_learning(sdqn_net_t h, double alpha, int p
     ARGCHK(!mu, "advantage_learning cannot be combined with munchausen: both targets want q slot 2 for a head of their own");
     ARGCHK(h->boot_K == 1, "advantage_learning cannot be combined with bootstrap_heads %d", h->boot_K);
     ARGCHK(h->quant_N == 1, "advantage_learning cannot be combined with quantiles %d", h->quant_N);
+    ARGCHK(!h->dueling, "advantage_learning cannot be combined with dueling");
     ARGCHK(h->cfg.batch_norm == 0.0, "advantage_learning cannot be combined with batch_norm: inference-mode statistics for its third forward are not defined");
     ARGCHK(!(persistent && h->n_step > 1), "persistent_advantage cannot be combined with n_step %d: it repeats the action in the NEXT state", h->n_step);
   }
@@ -615,6 +622,7 @@ extern "C" int sdqn_net_set_bootstrap(sdqn_net_t h, int K, double P, uint64_t se
     ARGCHK(!mu, "bootstrap_heads %d cannot be combined with munchausen", K);
     ARGCHK(!(h->al_alpha > 0.0), "bootstrap_heads %d cannot be combined with advantage_learning", K);
     ARGCHK(h->quant_N == 1, "bootstrap_heads %d cannot be combined with quantiles %d", K, h->quant_N);
+    ARGCHK(!h->dueling, "bootstrap_heads %d cannot be combined with dueling", K);
   }
   if (h->gen) h->gen->set_bootstrap(K, thresh, bootstrap_mask_seed(seed));
   h->boot_K = K; h->boot_P = P; h->boot_seed = seed; h->boot_thresh = thresh; h->boot_episode = 0;
@@ -665,6 +673,7 @@ extern "C" int sdqn_net_set_quantiles(sdqn_net_t h, int N) {
     ARGCHK(!mu, "quantiles %d cannot be combined with munchausen", N);
     ARGCHK(!(h->al_alpha > 0.0), "quantiles %d cannot be combined with advantage_learning", N);
     ARGCHK(h->boot_K == 1, "quantiles %d cannot be combined with bootstrap_heads %d", N, h->boot_K);
+    ARGCHK(!h->dueling, "quantiles %d cannot be combined with dueling", N);
     if (!h->gen && !h->quant_targets) { int r_ = dalloc(h, (void**)&h->quant_targets, (size_t)h->B * MAX_ACTIONS * sizeof(float)); if (r_) return r_; }
   }
   if (h->gen) GENCHK(h->gen->set_quantiles(N));
@@ -709,10 +718,79 @@ extern "C" int sdqn_quantile_act(const float* q, int N, int A, int* action) {
   return SDQN_OK;
 }
 
+// ---- --dueling: the dueling architecture (sdqn.h; dueling.h) ----------------------------------------------------------------
+extern "C" int sdqn_net_set_dueling(sdqn_net_t h, int on) {
+  ARGCHK(h, "NULL handle");
+  if (on) {
+    ARGCHK(h->A >= 2, "dueling needs a network with actions + 1 >= 2 outputs, this one has %d", h->A);
+    ARGCHK(h->cfg.batch_norm == 0.0, "dueling cannot be combined with batch_norm");
+    const bool dd = h->gen ? h->gen->double_dqn_on() : h->double_dqn, mu = h->gen ? h->gen->munchausen_on() : h->munchausen;
+    ARGCHK(!dd, "dueling cannot be combined with double_dqn: the shared head body carries no third slot");
+    ARGCHK(!mu, "dueling cannot be combined with munchausen");
+    ARGCHK(!(h->al_alpha > 0.0), "dueling cannot be combined with advantage_learning");
+    ARGCHK(h->boot_K == 1, "dueling cannot be combined with bootstrap_heads %d", h->boot_K);
+    ARGCHK(h->quant_N == 1, "dueling cannot be combined with quantiles %d", h->quant_N);
+    if (!h->gen && !h->duel_step) { int r_ = dalloc(h, (void**)&h->duel_step, (size_t)2 * h->B * sizeof(float)); if (r_) return r_; }
+  }
+  if (h->gen) GENCHK(h->gen->set_dueling(on != 0));
+  h->dueling = on != 0;
+  if (!on) return SDQN_OK;
+  // the weights as they stand (the online net's and the target's) take the block mask now; sdqn_net_set_weights repeats it on whatever it is handed
+  if (h->gen) { GENCHK(h->gen->dueling_mask_weights(0)); GENCHK(h->gen->dueling_mask_weights(1)); return SDQN_OK; }
+  { int rc_ = join_comm(h); if (rc_) return rc_; }
+  h->spec_pending = false;
+  HIPCHK(launch_dueling_mask(h->theta + OFF5, false, h->A, NFC, g_stream));
+  if (h->theta_t != h->theta) HIPCHK(launch_dueling_mask(h->theta_t + OFF5, false, h->A, NFC, g_stream));
+  return SDQN_OK;
+}
+extern "C" int sdqn_net_get_dueling(sdqn_net_t h, int* on) {
+  ARGCHK(h, "NULL handle");
+  if (on) *on = h->dueling ? 1 : 0;
+  return SDQN_OK;
+}
+// what the last train step's dueling head left: y, delta and the dq rows, widened to double (every path; a test's view)
+extern "C" int sdqn_net_last_dueling_step(sdqn_net_t h, double* y, double* delta, double* dq) {
+  ARGCHK(h, "NULL handle");
+  ARGCHK(h->dueling, "the network is not a dueling net (sdqn_net_set_dueling)");
+  if (h->gen) { GENCHK(h->gen->last_dueling_step(y, delta, dq)); return SDQN_OK; }
+  { int rc_ = join_comm(h); if (rc_) return rc_; }
+  const size_t nb = (size_t)h->B, nd = (size_t)h->B * h->A;
+  std::vector<float> buf(2 * nb + nd);
+  HIPCHK(hipMemcpyAsync(buf.data(), h->duel_step, 2 * nb * 4, hipMemcpyDeviceToHost, g_stream));
+  HIPCHK(hipMemcpyAsync(buf.data() + 2 * nb, h->dq, nd * 4, hipMemcpyDeviceToHost, g_stream));
+  HIPCHK(hipStreamSynchronize(g_stream));
+  if (y) for (size_t i = 0; i < nb; ++i) y[i] = (double)buf[i];
+  if (delta) for (size_t i = 0; i < nb; ++i) delta[i] = (double)buf[nb + i];
+  if (dq) for (size_t i = 0; i < nd; ++i) dq[i] = (double)buf[2 * nb + i];
+  return SDQN_OK;
+}
+// the host restatement of one sample of the dueling head (no device): dueling.h's dueling_sample on float rows
+extern "C" int sdqn_dueling_loss(int A, double clip_error, const float* q_pre_row, const float* q_post_row, int action, double reward, int terminal,
+                                 double gamma, int per, double per_weight, double per_alpha, double per_eps, float* dq_out, float* cost_out,
+                                 float* y_out, float* delta_out, float* maxq_out, float* priority_out) {
+  ARGCHK(q_pre_row && q_post_row && dq_out && cost_out, "NULL argument");
+  ARGCHK(A >= 1 && A + 1 <= MAX_ACTIONS, "%d actions + 1 outside [2, %d] outputs", A, MAX_ACTIONS);
+  ARGCHK(action >= 0 && action < A, "action %d out of range [0, %d)", action, A);
+  ARGCHK(clip_error >= 0.0, "clip_error %g: must be >= 0", clip_error);
+  float maxq;
+  *cost_out = dueling_sample<float>(q_pre_row, q_post_row, A, action, reward, terminal, gamma, (float)clip_error, per, (float)per_weight, per_alpha, per_eps,
+                                    dq_out, y_out, delta_out, &maxq, priority_out);
+  if (maxq_out) *maxq_out = maxq;
+  return SDQN_OK;
+}
+// the acting rule on one raw row q[A + 1]: the first maximum of Q = V + Adv - mean(Adv); q_out (may be NULL) receives the A action values
+extern "C" int sdqn_dueling_act(const float* q, int A, int* action, float* q_out) {
+  ARGCHK(q && action && A >= 1 && A + 1 <= MAX_ACTIONS, "bad arguments");
+  *action = dueling_act(q, A);
+  if (q_out) for (int a = 0; a < A; ++a) q_out[a] = dueling_q(q, A, a);
+  return SDQN_OK;
+}
+
 extern "C" int sdqn_net_set_option(sdqn_net_t h, const char* name, int value) {
   ARGCHK(h && name, "NULL argument");
   if (!strcmp(name, "double_dqn") && value) ARGCHK(h->boot_K == 1, "double_dqn cannot be combined with bootstrap_heads %d", h->boot_K);
   if (!strcmp(name, "double_dqn") && value) ARGCHK(h->quant_N == 1, "double_dqn cannot be combined with quantiles %d", h->quant_N);
+  if (!strcmp(name, "double_dqn") && value) ARGCHK(!h->dueling, "double_dqn cannot be combined with dueling: the shared head body carries no third slot");
   if (!strcmp(name, "double_dqn") && value) ARGCHK(!(h->al_alpha > 0.0), "double_dqn cannot be combined with advantage_learning: q slot 2 is taken by its third forward");
   if (!strcmp(name, "n_step")) {                          // n-step returns: sdqn.h
     ARGCHK(value >= 1 && value <= SDQN_MAX_N_STEP, "n_step %d out of range [1, %d]", value, SDQN_MAX_N_STEP);
@@ -834,7 +912,8 @@ extern "C" int sdqn_net_debug_read(sdqn_net_t h, const char* name, float* out, i
     {"a4", h->a4, (int64_t)2 * B * NFC}, {"d4", h->d4, (int64_t)B * NFC}, {"d3p", h->d3p, (int64_t)B * PD3 * PD3 * K3},
     {"d3", h->d3, (int64_t)B * PIX3 * K3}, {"d2p", h->d2p, (int64_t)B * PD2 * PD2 * K2}, {"d1", h->d1, (int64_t)B * PIX1 * K1}, {"q", h->q, (int64_t)2 * B * h->A},
     {"dq", h->dq, (int64_t)B * h->A}, {"g", h->g, h->NP}, {"theta", h->theta, h->NP}, {"cost_terms", h->cost_terms, B},
-    {"quantile_targets", h->quant_targets, h->quant_targets ? (int64_t)B * h->quant_N : 0}};
+    {"quantile_targets", h->quant_targets, h->quant_targets ? (int64_t)B * h->quant_N : 0},
+    {"dueling_step", h->duel_step, h->duel_step ? (int64_t)2 * B : 0}};
   for (auto& e : tab) if (!strcmp(e.n, name)) {
     ARGCHK(n <= e.len, "buffer %s holds %lld floats", name, (long long)e.len);
     { int rc_ = join_comm(h); if (rc_) return rc_; } HIPCHK(hipStreamSynchronize(g_stream));
@@ -851,6 +930,7 @@ extern "C" int sdqn_debug_time_kernel(sdqn_net_t h, sdqn_replay_t r, const int64
   ARGCHK(h && r && idx_host && out, "NULL");
   ARGCHK(kernel != K_HEAD || h->boot_K == 1, "bootstrap_heads %d: this hook launches the standard head, not the step's bootstrap head", h->boot_K);
   ARGCHK(kernel != K_HEAD || h->quant_N == 1, "quantiles %d: this hook launches the standard head, not the step's quantile head", h->quant_N);
+  ARGCHK(kernel != K_HEAD || !h->dueling, "dueling: this hook launches the standard head, not the step's dueling head");
   unsigned long long* d = nullptr;
   HIPCHK(hipMalloc((void**)&d, (size_t)max_blocks * 64));
   HIPCHK(hipMemset(d, 0, (size_t)max_blocks * 64));

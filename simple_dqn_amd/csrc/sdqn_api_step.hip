@@ -116,7 +116,8 @@ static int forward(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd, const L
   BN_FWD(3);
   const BootArgs boot = {h->boot_K, game_actions(h), h->boot_thresh, bootstrap_mask_seed(h->boot_seed), a.from_ring ? a.idx : nullptr};   // (read when HEAD_BOOTSTRAP)
   const QuantArgs quant = {h->quant_N, game_actions(h), h->quant_targets};      // (read when HEAD_QUANTILE)
-  LAUNCH(K_HEAD, launch_head(f, hd, g_stream, h->head_q_system, &boot, &quant));      // (head_q_system: the acting path, never with batch_norm)
+  const DuelArgs duel = {h->dueling ? 1 : 0, game_actions(h), h->duel_step};      // (read when HEAD_DUELING)
+  LAUNCH(K_HEAD, launch_head(f, hd, g_stream, h->head_q_system, &boot, &quant, &duel));      // (head_q_system: the acting path, never with batch_norm)
   return SDQN_OK;
 }
 int run_forward(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd) {
@@ -166,7 +167,8 @@ static UpdateForm update_form_of(const sdqn_net_s* h, StepStructure structure) {
   if (structure == STEP_DP_OVERLAP) return UPD_DP_OVERLAP;
   if (h->comm) return UPD_DP_SERIAL;
   if (h->grad_only) return UPD_GRAD_ONLY;
-  return clip_on(h) ? UPD_CLIP : UPD_SINGLE;
+  // --dueling masks g between its sums and their application: the split tail a clipped step runs, with or without the clip's own launches
+  return (clip_on(h) || h->dueling) ? UPD_CLIP : UPD_SINGLE;
 }
 UpdateForm update_form(const sdqn_net_s* h) { return update_form_of(h, step_structure(h)); }
 // --clip_grad_norm: g holds the complete gradient sums (all layers [+ the BatchNorm beta | gamma block]); bsz is the divisor the
@@ -214,7 +216,8 @@ StepPlan step_plan(const sdqn_net_s* h) {
   p.extra_fwd = (h->munchausen || al) ? 1 : (ddqn_active(h) && h->bn) ? 2 : 0;
   // --bootstrap_heads K > 1 (refused together with double_dqn / munchausen / batch_norm: sdqn_net_set_bootstrap): its own head; K = 1: nothing
   // --quantiles N > 1 (refused together with all of them: sdqn_net_set_quantiles): likewise; N = 1: nothing
-  p.head_train = h->quant_N > 1 ? HEAD_QUANTILE : h->boot_K > 1 ? HEAD_BOOTSTRAP : h->munchausen ? HEAD_MUNCHAUSEN : al ? HEAD_ADVANTAGE : ddqn_active(h) ? HEAD_DOUBLE : 0;
+  // --dueling (refused together with all of them and with double_dqn: sdqn_net_set_dueling): likewise
+  p.head_train = h->dueling ? HEAD_DUELING : h->quant_N > 1 ? HEAD_QUANTILE : h->boot_K > 1 ? HEAD_BOOTSTRAP : h->munchausen ? HEAD_MUNCHAUSEN : al ? HEAD_ADVANTAGE : ddqn_active(h) ? HEAD_DOUBLE : 0;
   p.nz = (!h->munchausen && !al && ddqn_active(h) && !h->bn) ? 3 : 2;
   LaunchPlan* l = p.launch;
   plan_forward(h, l);
@@ -275,6 +278,7 @@ StepPlan step_plan(const sdqn_net_s* h) {
   else if (p.update == UPD_DP_SERIAL) t.exchange = (h->cfg.datatype == 1 && h->dp_half && h->gh) ? XCH_HALF : XCH_F32;
   t.ovf = t.exchange == XCH_HALF;
   t.clip = clip_on(h) && (p.update == UPD_CLIP || p.update == UPD_DP_SERIAL);      // the all-reduced gradient, every rank alike
+  t.mask = h->dueling && p.update != UPD_GRAD_ONLY;                                // likewise, in every applying form (fc5 is never applied on the side stream)
   t.apply_mode = p.update == UPD_SINGLE ? 0 : p.update == UPD_GRAD_ONLY ? -1 : 2;
   t.divisor = (double)h->B * (double)(h->comm ? h->nranks : 1);
   t.skip_fc4 = p.side_fc4 ? 1 : p.fuse_rms;
@@ -292,7 +296,7 @@ static int side_fc4_update(sdqn_net_s* h, const StepArgs& a, const TailPlan& t) 
   h->w4_pending = true;
   return SDQN_OK;
 }
-// [local sums] -> [exchange] -> [clip] -> apply -> [BatchNorm parameters] (api_internal.h: TailPlan); `next` rides in the last update launch
+// [local sums] -> [exchange] -> [mask] -> [clip] -> apply -> [BatchNorm parameters] (api_internal.h: TailPlan); `next` rides in the last update launch
 int run_update_tail(sdqn_net_s* h, UpdateArgs u, const TailPlan& t, const PrepArgs* next) {
   u.skip_fc4 = t.skip_fc4; u.next.B = 0;
   if (t.reduce_first) {
@@ -317,6 +321,7 @@ int run_update_tail(sdqn_net_s* h, UpdateArgs u, const TailPlan& t, const PrepAr
   case XCH_NONE: break;
   }
   if (t.ovf) { u.ovf_flag = h->ovf_flag; u.ovf_count = h->ovf_count; u.ovf_dynamic = h->dp_half_scale_log2 < 0 ? 1 : 0; }
+  if (t.mask) LAUNCH(K_UPDATE, launch_dueling_mask(h->g + OFF5, false, h->A, NFC, g_stream));      // --dueling: the clip measures, the optimizer reads the masked g
   if (t.clip) { int rc = clip_gradient(h, t.divisor); if (rc) return rc; }
   u.mode = t.apply_mode; u.bsz = (float)t.divisor;
   if (next) u.next = *next;

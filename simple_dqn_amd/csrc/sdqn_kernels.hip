@@ -337,7 +337,9 @@ static HeadKernel head_for(int bucket) {
                                                                                    : head_kernel<MAX_ACTIONS, false, QSYS, DDQN, PER, NSTEP>;
 }
 
-hipError_t launch_head(const StepArgs& a, const HeadArgs& h, hipStream_t s, bool q_system_scope, const BootArgs* boot, const QuantArgs* quant) {
+hipError_t launch_head(const StepArgs& a, const HeadArgs& h, hipStream_t s, bool q_system_scope, const BootArgs* boot, const QuantArgs* quant,
+                       const DuelArgs* duel) {
+  if (h.train == HEAD_DUELING) return duel ? launch_head_dueling(a, h, *duel, s) : hipErrorInvalidValue;       // --dueling: a kernel of its own (sdqn_dueling.hip)
   if (h.train == HEAD_QUANTILE) return quant ? launch_head_quantile(a, h, *quant, s) : hipErrorInvalidValue;   // --quantiles: a kernel of its own (sdqn_quantile.hip)
   if (h.train == HEAD_MUNCHAUSEN) return launch_head_munchausen(a, h, s);        // --munchausen: a kernel of its own (sdqn_munchausen.hip)
   if (h.train == HEAD_BOOTSTRAP) return boot ? launch_head_bootstrap(a, h, *boot, s) : hipErrorInvalidValue;   // --bootstrap_heads: likewise (sdqn_bootstrap.hip)

@@ -79,6 +79,30 @@ def check_quantiles(args, num_actions=None):
     return N
 
 
+def check_dueling(args, num_actions=None):
+    """--dueling: num_actions + 1 <= 18 outputs (when num_actions is known) and none of --double_dqn, --munchausen,
+    --advantage_learning, --bootstrap_heads > 1, --quantiles > 1, --batch_norm.  Raises ValueError; touches no device.  Returns the flag."""
+    if not bool(getattr(args, "dueling", False)):
+        return False
+    if num_actions is not None and int(num_actions) + 1 > MAX_ACTIONS:
+        raise ValueError("--dueling with %d actions needs %d outputs (V and one advantage per action): the network has at most %d"
+                         % (int(num_actions), int(num_actions) + 1, MAX_ACTIONS))
+    if num_actions is not None and int(num_actions) < 1:
+        raise ValueError("--dueling needs at least one action, got %d" % int(num_actions))
+    for flag in ("double_dqn", "munchausen", "batch_norm"):
+        if getattr(args, flag, False):
+            raise ValueError("--dueling cannot be combined with --%s (DESIGN.md §32 lists it as a follow-up)" % flag)
+    if float(getattr(args, "advantage_learning", 0.0) or 0.0) > 0.0:
+        raise ValueError("--dueling cannot be combined with --advantage_learning (DESIGN.md §32 lists it as a follow-up)")
+    K = getattr(args, "bootstrap_heads", 1)
+    if (1 if K is None else int(K)) > 1:
+        raise ValueError("--dueling cannot be combined with --bootstrap_heads %d (DESIGN.md §32 lists it as a follow-up)" % int(K))
+    N = getattr(args, "quantiles", 1)
+    if (1 if N is None else int(N)) > 1:
+        raise ValueError("--dueling cannot be combined with --quantiles %d (DESIGN.md §32 lists it as a follow-up)" % int(N))
+    return True
+
+
 def check_advantage_learning(args):
     """--advantage_learning alpha / --persistent_advantage: alpha in [0, 1) (0: off), the persistent form only with
     alpha > 0 and one-step targets, and alpha > 0 with none of --double_dqn, --munchausen, --bootstrap_heads K > 1, --batch_norm.  Raises
@@ -115,6 +139,11 @@ class DeepQNetwork:
         # quantile-regression DQN: N quantiles per action are a library net with N x num_actions outputs, row j A + a = quantile j, action a
         self.quantiles = check_quantiles(args, num_actions)
         self._net_actions = self.bootstrap_heads * self.quantiles * num_actions
+        # the dueling architecture: V and one advantage per action are a library net with num_actions + 1 outputs, row 0 = V,
+        # row 1 + a = Adv_a, over the two halves of fc4's units (fc5 block-sparse: the library holds the other entries at +0.0)
+        self.dueling = check_dueling(args, num_actions)
+        if self.dueling:
+            self._net_actions = num_actions + 1
         self._lib = _lib.load()
         self.num_actions = num_actions
         self.batch_size = args.batch_size
@@ -208,6 +237,8 @@ class DeepQNetwork:
             _lib.check(self._lib.sdqn_net_set_bootstrap(h, self.bootstrap_heads, self.bootstrap_mask_probability, self.bootstrap_seed))
         if self.quantiles > 1:                                 # (N = 1: the library is not told anything)
             _lib.check(self._lib.sdqn_net_set_quantiles(h, self.quantiles))
+        if self.dueling:                                       # (off: the library is not told anything)
+            _lib.check(self._lib.sdqn_net_set_dueling(h, 1))
         self._mt_buf = (C.c_uint32 * _lib.MT_WORDS)()
         self._act_out = C.c_int(); self._act_greedy = self._lib.sdqn_net_act_greedy
         self._env_r, self._env_t = C.c_int(), C.c_int(); self._act_step_env = self._lib.sdqn_net_act_step_env
@@ -261,6 +292,8 @@ class DeepQNetwork:
         _lib.check(self._lib.sdqn_net_set_weights(self._h, (5 + which) if running else which, 5 + l, _lib.ptr(w, C.c_float), w.size))
 
     def set_weights(self, weights, which=0):
+        """--dueling: the entries of W5 (layer 4, which 0 / 1) outside the two streams' blocks — row 0 over units >= 256, rows 1.. over
+        units < 256 — are accepted with any value and zeroed by the library; load_weights goes through here."""
         for i, w in enumerate(weights):
             self.set_layer(i, w, which)
 
@@ -311,6 +344,9 @@ class DeepQNetwork:
         q = np.ascontiguousarray(q_row, dtype=np.float32).reshape(-1)
         assert q.size == self._net_actions
         a = C.c_int()
+        if self.dueling:                                        # --dueling: the first maximum of V + Adv - mean(Adv)
+            _lib.check(self._lib.sdqn_dueling_act(_lib.ptr(q, C.c_float), self.num_actions, C.byref(a), None))
+            return a.value
         if self.quantiles > 1:                                  # --quantiles: the first maximum of the quantile means
             _lib.check(self._lib.sdqn_quantile_act(_lib.ptr(q, C.c_float), self.quantiles, self.num_actions, C.byref(a)))
             return a.value
@@ -405,6 +441,8 @@ class DeepQNetwork:
         assert states.shape == ((self.batch_size, self.history_length,) + self.screen_dim)
         st = np.ascontiguousarray(states, dtype=np.uint8)
         q = self._predict_raw(st)
+        if self.dueling:                                        # Q [B][A] = t((V + Adv_a) - (sum_b Adv_b) / A), in double, the sum in action order
+            return self._dueling_q(q)
         if self.quantiles > 1:                                  # the action values [B][A]: the sum over the quantiles, in order, over N
             qs = q.reshape(self.batch_size, self.quantiles, self.num_actions)
             s = np.zeros((self.batch_size, self.num_actions), self._np)
@@ -424,6 +462,21 @@ class DeepQNetwork:
         """--quantiles: the quantile estimates of every action, [B][N][A] (N = 1: predict() with an axis of one)"""
         assert states.shape == ((self.batch_size, self.history_length,) + self.screen_dim)
         return self._predict_raw(np.ascontiguousarray(states, dtype=np.uint8)).reshape(self.batch_size, self.quantiles, self.num_actions)
+
+    def _dueling_q(self, raw):
+        raw = np.asarray(raw)
+        v, adv = raw[..., 0].astype(np.float64), raw[..., 1:].astype(np.float64)
+        s = np.zeros(v.shape, np.float64)
+        for b in range(self.num_actions):
+            s = s + adv[..., b]
+        return ((v[..., None] + adv) - (s / float(self.num_actions))[..., None]).astype(self._np)
+
+    def predict_streams(self, states):
+        """--dueling: the two streams' outputs (V [B], Adv [B][A]); predict() returns Q = V + Adv - mean(Adv)"""
+        assert self.dueling, "predict_streams needs --dueling"
+        assert states.shape == ((self.batch_size, self.history_length,) + self.screen_dim)
+        raw = self._predict_raw(np.ascontiguousarray(states, dtype=np.uint8))
+        return raw[:, 0].copy(), raw[:, 1:].copy()
 
     def _predict_raw(self, st):
         q = np.empty((self.batch_size, self._net_actions), dtype=self._np)
@@ -721,6 +774,13 @@ class DeepQNetwork:
         dq = np.empty((self.batch_size, self._net_actions), np.float64)
         _lib.check(self._lib.sdqn_net_last_quantile_step(self._h, _lib.ptr(t, C.c_double), _lib.ptr(dq, C.c_double)))
         return t, dq
+
+    def last_dueling_step(self):
+        """--dueling: (y float64[B], delta float64[B], dq float64[B, A + 1]) of the last train step's head, on every path"""
+        y, d = np.empty(self.batch_size, np.float64), np.empty(self.batch_size, np.float64)
+        dq = np.empty((self.batch_size, self._net_actions), np.float64)
+        _lib.check(self._lib.sdqn_net_last_dueling_step(self._h, _lib.ptr(y, C.c_double), _lib.ptr(d, C.c_double), _lib.ptr(dq, C.c_double)))
+        return y, d, dq
 
     def debug_read(self, name, n):
         out = np.empty(int(n), dtype=np.float32)

@@ -8,6 +8,7 @@
 //   step_trace --full   the whole cross product, every step written out (12 MB: compare two trees' outputs, or their checksums)
 //   step_trace --quantiles   the steps of a --quantiles 6 net over 3 actions (18 outputs), every datatype-regime cell that has them, written
 //                       out (neither golden holds them: tests/test_quantile.py reads the head's line)
+//   step_trace --dueling     likewise the steps of a --dueling net over 3 actions (4 outputs), with apply_update's tail (tests/test_dueling.py)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -58,7 +59,7 @@ hipError_t launch_kernel(int id, const StepArgs& a, const LaunchTune& t, hipStre
   fprintf(g_out, " v=%d hidx=%d\n", t.variant, t.host_idx != nullptr);
   return hipSuccess;
 }
-hipError_t launch_head(const StepArgs& a, const HeadArgs& h, hipStream_t s, bool q_system_scope, const BootArgs*, const QuantArgs*) {
+hipError_t launch_head(const StepArgs& a, const HeadArgs& h, hipStream_t s, bool q_system_scope, const BootArgs*, const QuantArgs*, const DuelArgs*) {
   fprintf(g_out, "  %s %2d %-11s", sname(s), K_HEAD, "head"); step_fields(a);
   fprintf(g_out, " train=%d nstep=%d q=%s sys=%d\n", h.train, h.nstep, nm(h.q).c_str(), (int)q_system_scope);
   return hipSuccess;
@@ -86,6 +87,9 @@ template <> hipError_t launch_grad_sqnorm<float>(const float* g, int64_t n, doub
 }
 template <> hipError_t launch_grad_scale<float>(float* g, int64_t n, const double* part, double bsz, double max_norm, double* rec, hipStream_t s) {
   fprintf(g_out, "  %s %2d %-11s g=%s n=%lld bsz=%g max_norm=%g rec=%s\n", sname(s), K_UPDATE, "clip_scale", nm(g).c_str(), (long long)n, bsz, max_norm, nm(rec).c_str()); return hipSuccess;
+}
+hipError_t launch_dueling_mask(void* w5, bool f64, int rows, int H, hipStream_t s) {
+  fprintf(g_out, "  %s %2d %-11s w5=%s f64=%d rows=%d H=%d\n", sname(s), K_UPDATE, "duel_mask", nm(w5).c_str(), (int)f64, rows, H); return hipSuccess;
 }
 hipError_t launch_target_blend(TargetBlendArgs a, hipStream_t s) {
   fprintf(g_out, "  %s %2d %-11s tau=%g\n", sname(s), K_TARGET, "blend", (double)a.tau); return hipSuccess;
@@ -125,7 +129,9 @@ static const char* O_NAMES[] = {"", " bt_xcd=0", " conv1w_bf16=0", " conv1w_bf16
 struct Cfg { int B, dt, fused, dp, clip, tgt, next, adam, keep, opt; };      // dt: 0 float32, 1 float32 + batch_norm, 2 float16
 
 static int g_quantiles = 1;      // --quantiles: every net is a quantile net over 18 / g_quantiles actions
+static bool g_dueling = false;   // --dueling: every net is a dueling net over 3 actions
 static bool refused(const Cfg& c) {
+  if (g_dueling && (c.dt == 1 || c.tgt != T_STD)) return true;            // sdqn_net_set_dueling refuses batch_norm, double_dqn and munchausen
   if (g_quantiles > 1 && (c.dt == 1 || c.tgt != T_STD)) return true;      // sdqn_net_set_quantiles refuses batch_norm, double_dqn and munchausen
   if (c.dp == DP_SERIAL_F32 && c.dt != 2) return true;     // dp_half is a float16 option
   if (c.tgt == T_MUNCH && c.dt == 1) return true;          // sdqn_net_set_munchausen refuses batch_norm
@@ -149,6 +155,7 @@ static void fill(sdqn_net_s* h, const Cfg& c) {
     NAMED(h->wh[0]); NAMED(h->wh[1]); NAMED(h->wht[0]); NAMED(h->wht[1]); NAMED(h->gh); NAMED(h->ovf_flag); NAMED(h->ovf_count);
   }
   if (g_quantiles > 1) { h->cfg.num_actions = h->A = MAX_ACTIONS; h->quant_N = g_quantiles; h->NPW = OFF5 + (int64_t)h->A * NFC; h->NP = h->NPW; }
+  if (g_dueling) h->dueling = true;                                         // (A = 4: V and three advantages)
   h->ev_g4 = (hipEvent_t)0x4000; h->ev_w4 = (hipEvent_t)0x5000;
   h->fused_launches = c.fused != 0; h->keep_grads = c.keep != 0; h->target_tau = 0.01;      // (every applied step ends with its blend line)
   if (c.clip) h->clip_grad_norm = 10.0;
@@ -251,13 +258,22 @@ int main(int argc, char** argv) {
   const bool full = argc > 1 && !strcmp(argv[1], "--full");
   char* text = nullptr; size_t text_len = 0;
   const bool quantiles = argc > 1 && !strcmp(argv[1], "--quantiles");
-  if (!full && !quantiles) g_out = open_memstream(&text, &text_len);
+  if (!full && !quantiles && !(argc > 1 && !strcmp(argv[1], "--dueling"))) g_out = open_memstream(&text, &text_len);
   g_rccl.AllReduce = ar_stub; g_rccl.GroupStart = group_start; g_rccl.GroupEnd = group_end;
   for (int i = 0; i < 512; ++i) g_host_idx[i] = 1000 + 37 * i;
   if (quantiles) {
     g_quantiles = 6;
     for (int dt : {0, 2}) for (int B : {32, 128}) for (int clip = 0; clip < 2; ++clip) train(Cfg{B, dt, 1, DP_NONE, clip, T_STD, 0, 0, 0, O_NONE});
     train(Cfg{32, 0, 1, DP_SERIAL, 0, T_STD, 0, 0, 0, O_NONE});
+    return 0;
+  }
+  if (argc > 1 && !strcmp(argv[1], "--dueling")) {
+    g_dueling = true;
+    for (int dt : {0, 2}) for (int B : {32, 128}) for (int clip = 0; clip < 2; ++clip) train(Cfg{B, dt, 1, DP_NONE, clip, T_STD, 0, 0, 0, O_NONE});
+    for (int dp : {DP_SERIAL, DP_OVERLAP, DP_GRAD_ONLY}) train(Cfg{32, 0, 1, dp, 0, T_STD, 0, 0, 0, O_NONE});
+    train(Cfg{32, 2, 1, DP_SERIAL, 0, T_STD, 0, 0, 0, O_NONE});
+    apply(Cfg{32, 0, 1, DP_GRAD_ONLY, 0, T_STD, 0, 0, 0, O_NONE}, false);
+    apply(Cfg{32, 0, 1, DP_GRAD_ONLY, 1, T_STD, 0, 0, 0, O_NONE}, false);
     return 0;
   }
   static const int BS[] = {32, 33, 127, 128, 256};

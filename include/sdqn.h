@@ -434,6 +434,29 @@ int sdqn_dueling_loss(int A, double clip_error, const float* q_pre_row, const fl
 /* the acting rule on one raw row q[A + 1]: the first maximum of Q(s, .) (a NaN Q(a) is never chosen over a number, a NaN Q(0) stays);
  * q_out (may be NULL) receives the A action values */
 int sdqn_dueling_act(const float* q, int A, int* action, float* q_out);
+/* Noisy networks, --noisy_nets (Fortunato et al. 2018, factorised Gaussian noise; no reference counterpart).  fc4 and fc5 become
+ * W = mu + sigma * (f(e_out) f(e_in)^T), f(x) = sgn(x) sqrt|x|, e of unit normals; the layers have no bias, the convolutions stay as they are.
+ * mu is what sdqn_net_set_weights / _get_weights address (which 0 / 1); sigma starts at sigma0 / sqrt(fan_in) in both nets and is the online
+ * net's own learned parameter: d sigma = dW * (f(e_out) f(e_in)^T), applied by the net's optimizer rule with state of its own and mu's
+ * learning rate and divisor.  Train step t (1, 2, ...) draws xi_t for the online and an independent xi'_t for the target net, used by the
+ * whole step.  The noise is a counter: sdqn_noisy_words / sdqn_noisy_noise restate stream (seed, step, slot 0 online / 1 target, layer 0 fc4 /
+ * 1 fc5, side 0 inputs / 1 outputs) on the host — n 64-bit words, or the n unit normals z with e = f(z); fc4's input index is the weights'
+ * column index.  sdqn_net_update_target also copies sigma.  Forwards: sdqn_net_predict, sdqn_env_eval and the single-environment acting
+ * paths after sdqn_net_noisy_acting(h, 0) read mu alone; sdqn_net_predict_noisy, sdqn_env_collect and the acting paths after
+ * sdqn_net_noisy_acting(h, 1) (default) read the online net's current mu and sigma under the last train step's xi_t (xi_0 before the first).
+ * A noisy step runs the split optimizer tail plus three launches (compose, sigma, compose).  on = 1 is SDQN_ERR_ARG on float16 / float64 /
+ * other geometries, with batch_norm, clip_grad_norm, target_tau, munchausen, advantage_learning, bootstrap_heads > 1, quantiles > 1,
+ * dueling and data parallel (either order).  sdqn_net_get / _set_noisy_sigma: layer 3 (fc4, [512][3136]) or 4 (fc5, [A][512]) of net 0 / 1,
+ * in the layout of the weights.  sdqn_net_debug_read: "noisy_eps" [2][4192] the factors f(z) last composed per net (e_in4 | e_out4 | e_in5 |
+ * e_out5 padded to 32), "noisy_theta" / "noisy_theta_t" the effective flat buffers, "noisy_sigma_grad" (option keep_gradients). */
+int sdqn_net_set_noisy(sdqn_net_t h, int on, double sigma0, uint64_t seed);
+int sdqn_net_get_noisy(sdqn_net_t h, int* on, double* sigma0, uint64_t* seed, int64_t* step);      /* any pointer may be NULL */
+int sdqn_net_noisy_acting(sdqn_net_t h, int collecting);
+int sdqn_net_get_noisy_sigma(sdqn_net_t h, int which_net, int layer, float* buf, int64_t n);
+int sdqn_net_set_noisy_sigma(sdqn_net_t h, int which_net, int layer, const float* buf, int64_t n);
+int sdqn_net_predict_noisy(sdqn_net_t h, const uint8_t* states, float* q_out);
+int sdqn_noisy_words(uint64_t seed, uint64_t step, int slot, int layer, int side, int64_t n, uint64_t* out_words);
+int sdqn_noisy_noise(uint64_t seed, uint64_t step, int slot, int layer, int side, int64_t n, float* out_z);
 /* option "double_dqn" (0 default / 1, any configuration, switchable between steps): Double DQN targets (van Hasselt, Guez and Silver
  * 2016): the online net picks each poststate's action, the target net values it (see sdqn_net_last_q).  The online net's forward on
  * the poststates rides as a third net slot in the step's own forward launches (batch_norm: a forward of its own in front of the step,

@@ -149,6 +149,14 @@ SIGNATURES = {
     "sdqn_dueling_loss": (C.c_int, [C.c_int, C.c_double, _f32p, _f32p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double,
                                     C.c_double, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p]),
     "sdqn_dueling_act": (C.c_int, [_f32p, C.c_int, C.POINTER(C.c_int), _f32p]),
+    "sdqn_net_set_noisy": (C.c_int, [_vp, C.c_int, C.c_double, C.c_uint64]),
+    "sdqn_net_get_noisy": (C.c_int, [_vp, C.POINTER(C.c_int), _f64p, C.POINTER(C.c_uint64), _i64p]),
+    "sdqn_net_noisy_acting": (C.c_int, [_vp, C.c_int]),
+    "sdqn_net_get_noisy_sigma": (C.c_int, [_vp, C.c_int, C.c_int, _f32p, C.c_int64]),
+    "sdqn_net_set_noisy_sigma": (C.c_int, [_vp, C.c_int, C.c_int, _f32p, C.c_int64]),
+    "sdqn_net_predict_noisy": (C.c_int, [_vp, _u8p, _f32p]),
+    "sdqn_noisy_words": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_uint64)]),
+    "sdqn_noisy_noise": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int64, _f32p]),
     "sdqn_net_sync": (C.c_int, [_vp]),
     "sdqn_net_apply_update": (C.c_int, [_vp, C.c_double]),
     "sdqn_net_grad_to_half": (C.c_int, [_vp, C.POINTER(C.c_uint16), C.c_int64]),

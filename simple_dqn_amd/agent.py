@@ -162,7 +162,7 @@ class Agent:
         return self._epsilon.at(self.total_train_steps)
 
     def _acting_mode(self, test):
-        if self._boot:
+        if self._boot or getattr(self.net, "noisy_nets", False):      # --noisy_nets: the noise while collecting, mu while testing
             self.net.set_acting(test)
 
     def play_random(self, random_steps):                              # fill the replay memory with uniform-random play

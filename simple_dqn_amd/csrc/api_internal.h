@@ -19,6 +19,7 @@
 #include "sampler.h"
 #include "sdqn_per.h"
 #include "sdqn_clip.h"
+#include "noisy.h"
 
 using namespace sdqn;
 
@@ -154,6 +155,14 @@ struct sdqn_net_s {
   // A - 1 action values (the game loops: one launch into boot_q).  duel_step: [2][B] the last step's y and delta (tuned path;
   // sdqn_net_debug_read "dueling_step"), allocated by the setter
   bool dueling = false; float* duel_step = nullptr;
+  // --noisy_nets (sdqn_net_set_noisy; noisy.h, sdqn_noisy.hip): fc4 and fc5 are W = mu + sigma * (e_out * e_in); theta / theta_t hold
+  // mu.  nz_sigma: [NP - OFF4] per net, internal layout (the target's aliases the online one without a target net); nz_eff: the effective flat
+  // buffers the step's kernels read; nz_state / nz_state2: sigma's optimizer state; nz_eps: [2][NOISY_EPS_NET] the factor vectors last composed;
+  // nz_gsig: g_sigma of the last step (option keep_gradients).  nz_step: train steps run as a noisy net = the t of the xi_t the effective
+  // buffers hold between steps.  nz_stale: mu or sigma changed outside a train step, the buffers are recomposed before their next use
+  // (noisy_fresh).  nz_collecting: the single-environment acting paths use the effective weights (train phase) or mu (test phase)
+  bool noisy = false, nz_stale = false, nz_collecting = true; double nz_sigma0 = 0.5; uint64_t nz_seed = 0; int64_t nz_step = 0;
+  float *nz_sigma[2] = {nullptr, nullptr}, *nz_eff[2] = {nullptr, nullptr}, *nz_state = nullptr, *nz_state2 = nullptr, *nz_eps = nullptr, *nz_gsig = nullptr;
   int n_step = 1;                          // --n_step (option "n_step"): poststate frame offset of the ring paths, n-step head
   double target_tau = 0.0;                 // --target_tau (sdqn_net_set_target_tau): > 0: every train step is followed by one soft target update
   // --clip_grad_norm (sdqn_net_set_clip_grad_norm): > 0: the flat gradient is scaled to this global L2 norm (of the MEAN
@@ -260,6 +269,7 @@ enum Exchange { XCH_NONE = 0, XCH_F32, XCH_HALF, XCH_GROUPED };   // all-reduce 
 struct TailPlan {
   bool reduce_first = false;
   Exchange exchange = XCH_NONE;
+  bool noisy = false;                      // --noisy_nets: the sigma launch (g_sigma = g * e, the optimizer on sigma) where the mask sits: behind the sums, in front of the apply launch
   bool mask = false;                       // --dueling: fc5's block mask on g, one launch behind the sums / exchange, in front of the clip
   bool clip = false;                       // --clip_grad_norm: the two clip launches in front of the apply launch
   bool ovf = false;                        // the gradient came through the half payload: the apply launch honours the overflow flag
@@ -309,6 +319,10 @@ int step_blend(sdqn_net_s* h);                                     // what every
 int gen_step_done(sdqn_net_s* h);                                  // generic path: a train step was enqueued ([clip + deferred update,] counter, step_blend)
 // the actions a transition may hold (--bootstrap_heads / --quantiles: A is K / N times that; --dueling: one more, the V row)
 inline int game_actions(const sdqn_net_s* h) { return h->dueling ? h->A - 1 : h->A / (h->boot_K * h->quant_N); }
+// --noisy_nets: the effective buffers as of xi_{nz_step}, recomposed when stale (nothing on a plain net); the acting weights of the phase
+int noisy_fresh(sdqn_net_s* h);
+int noisy_compose(sdqn_net_s* h, int64_t step, int nets);
+inline bool noisy_acting(const sdqn_net_s* h) { return h->noisy && h->nz_collecting; }
 inline bool clip_on(const sdqn_net_s* h) { return h->clip_grad_norm > 0.0; }
 int clip_gradient(sdqn_net_s* h, double bsz);                      // --clip_grad_norm: the two launches on g between update modes 1 and 2 (nothing when off)
 StepPlan step_plan(const sdqn_net_s* h);
@@ -328,8 +342,9 @@ UpdateForm update_form(const sdqn_net_s* h);
 int run_train(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd, const PrepArgs* next = nullptr);
 int read_cost(sdqn_net_s* h, float* cost_out);                      // either path; ends with per_check_all
 int read_mean_cost(sdqn_net_s* h, int n_steps, float* mean_cost);
-int predict_forward_tuned(sdqn_net_s* h, const uint8_t* states, const HeadArgs& hd, int B = 0);   // B = 0: the net's batch
-int predict_forward(sdqn_net_s* h, const uint8_t* states, int rows, const void** q, int* q_f64);
+// noisy (a --noisy_nets net): the forward reads the effective weights (the caller has run noisy_fresh), else mu
+int predict_forward_tuned(sdqn_net_s* h, const uint8_t* states, const HeadArgs& hd, int B = 0, bool noisy = false);   // B = 0: the net's batch
+int predict_forward(sdqn_net_s* h, const uint8_t* states, int rows, const void** q, int* q_f64, bool noisy = false);
 StepArgs ring_step_args(sdqn_net_s* h, const sdqn_replay_s* r);
 int run_ring_step(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* host_idx, const HeadArgs& hd, const PrepArgs* next = nullptr);
 int check_replay_geometry(const sdqn_net_s* h, const sdqn_replay_s* r);

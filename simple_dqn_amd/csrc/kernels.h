@@ -222,5 +222,25 @@ struct TargetBlendArgs {
   int64_t flat_first;         // (filled in by launch_target_blend) first element of the element-wise part
 };
 hipError_t launch_target_blend(TargetBlendArgs a, hipStream_t s);
+// ---- --noisy_nets: factorised noise on fc4 and fc5 (sdqn_noisy.hip; the noise itself: noisy.h) ---------------------------------------------
+struct NoisyArgs {              // noisy_compose: eff = [conv of mu | mu + sigma * (e_out * e_in) on fc4, fc5] for net slots 0 .. nets - 1
+  const float* mu[2];           // flat parameters (theta, theta-)
+  const float* sigma[2];        // [NP - OFF4] the fc4 | fc5 range, internal layout
+  float* eff[2];                // [NP] effective flat buffers (what the step's kernels read as StepArgs::theta)
+  float* eps;                   // [2][NOISY_EPS_NET] the factor vectors of the composed nets, left by workgroup 0 of each
+  uint64_t seed, step;          // the counter: (seed, step, net slot, layer, side, index)
+  int64_t NP;
+  int A, nets;
+};
+struct NoisyTailArgs {          // noisy_tail: g_sigma = g * (e_out * e_in) on the fc range of g, then the optimizer rule on sigma
+  const float* g;               // the flat gradient sums (update mode 1)
+  float* sigma; float* state; float* state2;      // [n] the online net's sigma and its optimizer state (state2: Adam / Adadelta)
+  const float* eps;             // [NOISY_EPS_NET] the online net's factor vectors of this step
+  float* gsig;                  // nullptr, or [n]: g_sigma is kept (option keep_gradients)
+  int64_t n;                    // NP - OFF4
+  UpdateArgs u;                 // the optimizer's constants, bsz = the apply launch's divisor
+};
+hipError_t launch_noisy_compose(const NoisyArgs& a, hipStream_t s);
+hipError_t launch_noisy_tail(const NoisyTailArgs& a, hipStream_t s);
 
 }  // namespace sdqn

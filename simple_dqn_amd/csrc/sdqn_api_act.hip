@@ -86,11 +86,12 @@ int predict_state_enqueue(sdqn_net_s* h, sdqn_statebuf_s* sb) {
   volatile uint32_t* qh = reinterpret_cast<volatile uint32_t*>(h->q_host + h->q_slot * Q_SLOT_FLOATS);
   for (int k = 0; k < h->A; ++k) qh[k] = Q_SENTINEL;
   h->act_last = false;
+  if (noisy_acting(h)) { int rcn = noisy_fresh(h); if (rcn) return rcn; }      // --noisy_nets, train phase: the effective weights (test phase: mu)
   if (h->act_on && !h->prof_on) {                                // one launch: conv1 .. fc5 (sdqn_act.hip); 8 stripe partials come back
     { int rcj = join_comm(h); if (rcj) return rcj; }            // (data parallel, overlapped form: W4's update runs on the second stream)
     for (int sp = 1; sp < 8; ++sp) for (int k = 0; k < h->A; ++k) qh[sp * ACT_Q_STRIDE + k] = Q_SENTINEL;
     ActArgs aa; memset(&aa, 0, sizeof aa);
-    aa.state = statebuf_window(sb); aa.theta = h->theta; aa.scratch = h->act_scratch; aa.ctl = h->act_ctl;
+    aa.state = statebuf_window(sb); aa.theta = noisy_acting(h) ? h->nz_eff[0] : h->theta; aa.scratch = h->act_scratch; aa.ctl = h->act_ctl;
     aa.q = h->q_host_dev + h->q_slot * Q_SLOT_FLOATS; aa.A = h->A; aa.seq = h->act_seq++;
     if (h->act_inject) {            // every ticket counter of this launch's control block far beyond the item count: all workgroups leave at once
       h->act_inject = false;
@@ -105,7 +106,7 @@ int predict_state_enqueue(sdqn_net_s* h, sdqn_statebuf_s* sb) {
   const bool direct = !h->bn;                                    // (--batch_norm: the plain head + a copy, as before)
   if (direct) hd.q = h->q_host_dev + h->q_slot * Q_SLOT_FLOATS;
   h->head_q_system = direct;
-  const int rc = predict_forward_tuned(h, statebuf_window(sb), hd, 1);      // batch of one, read in place
+  const int rc = predict_forward_tuned(h, statebuf_window(sb), hd, 1, noisy_acting(h));      // batch of one, read in place
   h->head_q_system = false;
   if (rc) return rc;
   if (!direct) HIPCHK(hipMemcpyAsync(h->q_host + h->q_slot * Q_SLOT_FLOATS, h->q, (size_t)h->A * 4, hipMemcpyDeviceToHost, g_stream));

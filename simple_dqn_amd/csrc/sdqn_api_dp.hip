@@ -38,6 +38,7 @@ extern "C" int sdqn_dp_init(sdqn_net_t h, const char* rccl_path, const char id[1
   ARGCHK(h && id && nranks >= 1 && rank >= 0 && rank < nranks, "bad arguments");
   if (h->gen) { set_error("data parallel is implemented for the 84x84x4 float32 / float16 configurations"); return SDQN_ERR_STATE; }
   if (h->comm) { set_error("data parallel already initialised"); return SDQN_ERR_STATE; }
+  ARGCHK(!h->noisy, "data parallel cannot be combined with noisy_nets: sigma's gradient is not exchanged (DESIGN.md §33)");
   int rc = rccl_load(rccl_path); if (rc) return rc;
   Id128 u; memcpy(u.b, id, 128);
   NCCLCHK(g_rccl.CommInitRank(&h->comm, nranks, u, rank));

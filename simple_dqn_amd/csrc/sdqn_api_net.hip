@@ -272,6 +272,7 @@ extern "C" int sdqn_net_set_weights(sdqn_net_t h, int which, int layer, const fl
     HIPCHK(launch_refresh16(zz ? h->theta_t : h->theta, h->wh[zz], h->wht[zz], g_stream));
     HIPCHK(hipStreamSynchronize(g_stream));
   }
+  if (h->noisy && which <= 1) h->nz_stale = true;    // --noisy_nets: mu changed, the effective buffers are recomposed before their next use
   if (h->w1p[0] && which <= 1 && layer == 0) {   // conv1's bf16 planes follow W1
     const int zz = (which == 1 && h->theta_t != h->theta) ? 1 : 0;
     HIPCHK(launch_w1_planes(zz ? h->theta_t : h->theta, h->w1p[zz], g_stream));
@@ -356,6 +357,10 @@ static int target_copy(sdqn_net_s* h) {
       HIPCHK(hipMemcpyAsync(h->wh[1], h->wh[0], (size_t)OFF5 * 2, hipMemcpyDeviceToDevice, g_stream));
       HIPCHK(hipMemcpyAsync(h->wht[1], h->wht[0], (size_t)OFF5 * 2, hipMemcpyDeviceToDevice, g_stream));
     }
+    if (h->noisy) {                               // --noisy_nets: the target's sigma follows; its noise stays its own (net slot 1)
+      HIPCHK(hipMemcpyAsync(h->nz_sigma[1], h->nz_sigma[0], (size_t)(h->NP - OFF4) * 4, hipMemcpyDeviceToDevice, g_stream));
+      h->nz_stale = true;
+    }
   }
   return SDQN_OK;
 }
@@ -412,6 +417,7 @@ int gen_step_done(sdqn_net_s* h) {
 extern "C" int sdqn_net_set_clip_grad_norm(sdqn_net_t h, double max_norm) {
   ARGCHK(h, "NULL handle");
   ARGCHK(max_norm >= 0.0 && max_norm < INFINITY, "clip_grad_norm %g: must be a finite value >= 0 (0 = off)", max_norm);     // (false for a NaN)
+  ARGCHK(!(max_norm > 0.0 && h->noisy), "clip_grad_norm cannot be combined with noisy_nets: the norm would have to include sigma's gradient");
   if (h->gen) GENCHK(h->gen->set_clip(max_norm > 0.0));
   else if (max_norm > 0.0 && !h->clip_buf) { int r_ = dalloc(h, (void**)&h->clip_buf, (size_t)CLIP_WORDS * 8); if (r_) return r_; }
   h->clip_grad_norm = max_norm;
@@ -433,12 +439,14 @@ extern "C" int sdqn_net_last_grad_norm(sdqn_net_t h, double* norm, double* scale
 extern "C" int sdqn_net_soft_update(sdqn_net_t h, double tau) {
   ARGCHK(h, "NULL handle");
   ARGCHK(tau_in_range(tau), "soft target update: tau %g outside (0, 1]", tau);
+  ARGCHK(!h->noisy || tau == 1.0, "target_tau cannot be combined with noisy_nets: the blend would have to cover sigma");
   if (!h->gen) { int rc = join_comm(h); if (rc) return rc; }
   return target_blend(h, tau);
 }
 extern "C" int sdqn_net_set_target_tau(sdqn_net_t h, double tau) {
   ARGCHK(h, "NULL handle");
   ARGCHK(tau == 0.0 || tau_in_range(tau), "target_tau %g outside [0, 1]", tau);
+  ARGCHK(!(tau > 0.0 && h->noisy), "target_tau cannot be combined with noisy_nets: the blend would have to cover sigma");
   h->target_tau = tau;
   return SDQN_OK;
 }
@@ -449,6 +457,7 @@ extern "C" int sdqn_net_get_target_tau(sdqn_net_t h, double* tau) { ARGCHK(h && 
 extern "C" int sdqn_net_apply_update(sdqn_net_t h, double bsz) {
   ARGCHK(h && bsz > 0, "bad arguments");
   if (h->gen) { set_error("data parallel (grad_only / apply_update) is implemented for the 84x84x4 float32 / float16 configurations"); return SDQN_ERR_STATE; }
+  ARGCHK(!h->noisy, "data parallel (apply_update) cannot be combined with noisy_nets: sigma's gradient is not exchanged");
   { int rc = join_comm(h); if (rc) return rc; }
   h->spec_pending = false;
   TailPlan t;                              // the step's optimizer tail from "clip" on, with the caller's divisor
@@ -559,6 +568,7 @@ extern "C" int sdqn_net_set_munchausen(sdqn_net_t h, int on, double alpha, doubl
     ARGCHK(h->boot_K == 1, "munchausen cannot be combined with bootstrap_heads %d", h->boot_K);
     ARGCHK(h->quant_N == 1, "munchausen cannot be combined with quantiles %d", h->quant_N);
     ARGCHK(!h->dueling, "munchausen cannot be combined with dueling");
+    ARGCHK(!h->noisy, "munchausen cannot be combined with noisy_nets");
     ARGCHK(!(h->al_alpha > 0.0), "munchausen cannot be combined with advantage_learning: both targets want q slot 2 for a head of their own");
     ARGCHK(h->cfg.batch_norm == 0.0, "munchausen cannot be combined with batch_norm: inference-mode statistics for its third forward are not defined");
     ARGCHK(h->gen || !h->double_dqn, "munchausen cannot be combined with double_dqn: the Munchausen target has no argmax for the online net to choose");
@@ -590,6 +600,7 @@ extern "C" int sdqn_net_set_advantage_learning(sdqn_net_t h, double alpha, int p
     ARGCHK(h->boot_K == 1, "advantage_learning cannot be combined with bootstrap_heads %d", h->boot_K);
     ARGCHK(h->quant_N == 1, "advantage_learning cannot be combined with quantiles %d", h->quant_N);
     ARGCHK(!h->dueling, "advantage_learning cannot be combined with dueling");
+    ARGCHK(!h->noisy, "advantage_learning cannot be combined with noisy_nets");
     ARGCHK(h->cfg.batch_norm == 0.0, "advantage_learning cannot be combined with batch_norm: inference-mode statistics for its third forward are not defined");
     ARGCHK(!(persistent && h->n_step > 1), "persistent_advantage cannot be combined with n_step %d: it repeats the action in the NEXT state", h->n_step);
   }
@@ -623,6 +634,7 @@ extern "C" int sdqn_net_set_bootstrap(sdqn_net_t h, int K, double P, uint64_t se
     ARGCHK(!(h->al_alpha > 0.0), "bootstrap_heads %d cannot be combined with advantage_learning", K);
     ARGCHK(h->quant_N == 1, "bootstrap_heads %d cannot be combined with quantiles %d", K, h->quant_N);
     ARGCHK(!h->dueling, "bootstrap_heads %d cannot be combined with dueling", K);
+    ARGCHK(!h->noisy, "bootstrap_heads %d cannot be combined with noisy_nets", K);
   }
   if (h->gen) h->gen->set_bootstrap(K, thresh, bootstrap_mask_seed(seed));
   h->boot_K = K; h->boot_P = P; h->boot_seed = seed; h->boot_thresh = thresh; h->boot_episode = 0;
@@ -674,6 +686,7 @@ extern "C" int sdqn_net_set_quantiles(sdqn_net_t h, int N) {
     ARGCHK(!(h->al_alpha > 0.0), "quantiles %d cannot be combined with advantage_learning", N);
     ARGCHK(h->boot_K == 1, "quantiles %d cannot be combined with bootstrap_heads %d", N, h->boot_K);
     ARGCHK(!h->dueling, "quantiles %d cannot be combined with dueling", N);
+    ARGCHK(!h->noisy, "quantiles %d cannot be combined with noisy_nets", N);
     if (!h->gen && !h->quant_targets) { int r_ = dalloc(h, (void**)&h->quant_targets, (size_t)h->B * MAX_ACTIONS * sizeof(float)); if (r_) return r_; }
   }
   if (h->gen) GENCHK(h->gen->set_quantiles(N));
@@ -730,6 +743,7 @@ extern "C" int sdqn_net_set_dueling(sdqn_net_t h, int on) {
     ARGCHK(!(h->al_alpha > 0.0), "dueling cannot be combined with advantage_learning");
     ARGCHK(h->boot_K == 1, "dueling cannot be combined with bootstrap_heads %d", h->boot_K);
     ARGCHK(h->quant_N == 1, "dueling cannot be combined with quantiles %d", h->quant_N);
+    ARGCHK(!h->noisy, "dueling cannot be combined with noisy_nets");
     if (!h->gen && !h->duel_step) { int r_ = dalloc(h, (void**)&h->duel_step, (size_t)2 * h->B * sizeof(float)); if (r_) return r_; }
   }
   if (h->gen) GENCHK(h->gen->set_dueling(on != 0));
@@ -786,6 +800,104 @@ extern "C" int sdqn_dueling_act(const float* q, int A, int* action, float* q_out
   return SDQN_OK;
 }
 
+// ---- --noisy_nets: factorised Gaussian noise on fc4 and fc5 (sdqn.h; noisy.h, sdqn_noisy.hip) -------------------------------
+static void noisy_sigma_init(const sdqn_net_s* h, std::vector<float>& v) {
+  v.resize((size_t)(h->NP - OFF4));
+  const float s4 = (float)(h->nz_sigma0 / sqrt((double)NIN4)), s5 = (float)(h->nz_sigma0 / sqrt((double)NFC));      // sigma_0 / sqrt(fan_in)
+  for (size_t i = 0; i < v.size(); ++i) v[i] = i < (size_t)NW4 ? s4 : s5;
+}
+extern "C" int sdqn_net_set_noisy(sdqn_net_t h, int on, double sigma0, uint64_t seed) {
+  ARGCHK(h, "NULL handle");
+  if (!on) { h->noisy = false; h->spec_pending = false; return SDQN_OK; }      // (sigma and its optimizer state stay where they are)
+  ARGCHK(!h->gen, "noisy_nets is implemented for the 84x84x4 float32 configuration (not datatype float64 or other geometries: the generic path)");
+  ARGCHK(h->cfg.datatype == 0, "noisy_nets cannot be combined with datatype float16");
+  ARGCHK(!h->bn, "noisy_nets cannot be combined with batch_norm");
+  ARGCHK(!clip_on(h), "noisy_nets cannot be combined with clip_grad_norm: the norm would have to include sigma's gradient");
+  ARGCHK(!(h->target_tau > 0.0), "noisy_nets cannot be combined with target_tau: the blend would have to cover sigma");
+  ARGCHK(!h->munchausen, "noisy_nets cannot be combined with munchausen");
+  ARGCHK(!(h->al_alpha > 0.0), "noisy_nets cannot be combined with advantage_learning");
+  ARGCHK(h->boot_K == 1, "noisy_nets cannot be combined with bootstrap_heads %d", h->boot_K);
+  ARGCHK(h->quant_N == 1, "noisy_nets cannot be combined with quantiles %d", h->quant_N);
+  ARGCHK(!h->dueling, "noisy_nets cannot be combined with dueling");
+  ARGCHK(!h->comm && !h->grad_only, "noisy_nets cannot be combined with data parallel: sigma's gradient is not exchanged");
+  ARGCHK(sigma0 >= 0.0 && sigma0 < INFINITY, "noisy_sigma %g: must be a finite value >= 0", sigma0);     // (false for a NaN)
+  const size_t nf = (size_t)(h->NP - OFF4);
+  if (!h->nz_eff[0]) {
+    const bool tgt = h->theta_t != h->theta;
+    int r_ = dalloc(h, (void**)&h->nz_eff[0], (size_t)h->NP * 4); if (r_) return r_;
+    r_ = dalloc(h, (void**)&h->nz_sigma[0], nf * 4); if (r_) return r_;
+    if (tgt) { r_ = dalloc(h, (void**)&h->nz_eff[1], (size_t)h->NP * 4); if (r_) return r_; r_ = dalloc(h, (void**)&h->nz_sigma[1], nf * 4); if (r_) return r_; }
+    else { h->nz_eff[1] = h->nz_eff[0]; h->nz_sigma[1] = h->nz_sigma[0]; }
+    r_ = dalloc(h, (void**)&h->nz_state, nf * 4); if (r_) return r_;
+    if (h->cfg.optimizer != 0) { r_ = dalloc(h, (void**)&h->nz_state2, nf * 4); if (r_) return r_; }
+    r_ = dalloc(h, (void**)&h->nz_eps, (size_t)2 * NOISY_EPS_NET * 4); if (r_) return r_;
+    r_ = dalloc(h, (void**)&h->nz_gsig, nf * 4); if (r_) return r_;
+  }
+  h->nz_sigma0 = sigma0; h->nz_seed = seed; h->nz_step = 0;
+  std::vector<float> v; noisy_sigma_init(h, v);
+  { int rc_ = join_comm(h); if (rc_) return rc_; } HIPCHK(hipStreamSynchronize(g_stream));
+  HIPCHK(hipMemcpy(h->nz_sigma[0], v.data(), nf * 4, hipMemcpyHostToDevice));
+  if (h->nz_sigma[1] != h->nz_sigma[0]) HIPCHK(hipMemcpy(h->nz_sigma[1], v.data(), nf * 4, hipMemcpyHostToDevice));
+  HIPCHK(hipMemset(h->nz_state, 0, nf * 4));
+  if (h->nz_state2) HIPCHK(hipMemset(h->nz_state2, 0, nf * 4));
+  h->noisy = true; h->nz_stale = true; h->spec_pending = false;
+  return SDQN_OK;
+}
+extern "C" int sdqn_net_get_noisy(sdqn_net_t h, int* on, double* sigma0, uint64_t* seed, int64_t* step) {
+  ARGCHK(h, "NULL handle");
+  if (on) *on = h->noisy ? 1 : 0; if (sigma0) *sigma0 = h->nz_sigma0; if (seed) *seed = h->nz_seed; if (step) *step = h->nz_step;
+  return SDQN_OK;
+}
+// the single-environment acting paths: collecting != 0 reads the effective weights (train phase), 0 reads mu (test phase)
+extern "C" int sdqn_net_noisy_acting(sdqn_net_t h, int collecting) {
+  ARGCHK(h, "NULL handle");
+  if (h->nz_collecting != (collecting != 0)) h->spec_pending = false;        // a forward enqueued ahead read the other weights
+  h->nz_collecting = collecting != 0;
+  return SDQN_OK;
+}
+// sigma of fc4 (layer 3, [512][3136]) or fc5 (layer 4, [A][512]) of the online (0) or target (1) net, in the layout of the weights
+static int noisy_sigma_span(sdqn_net_s* h, int which_net, int layer, int64_t n, float** base, int64_t* rows, int64_t* cols) {
+  ARGCHK(h->noisy, "the network is not a noisy net (sdqn_net_set_noisy)");
+  ARGCHK((which_net == 0 || which_net == 1) && (layer == 3 || layer == 4), "sigma: net 0 (online) or 1 (target), layer 3 (fc4) or 4 (fc5); got net %d, layer %d", which_net, layer);
+  int64_t off; layer_dims(layer, h->A, *rows, *cols, off);
+  ARGCHK(n == *rows * *cols, "sigma of layer %d holds %lld values, got %lld", layer, (long long)(*rows * *cols), (long long)n);
+  *base = h->nz_sigma[which_net] + (off - OFF4);
+  return SDQN_OK;
+}
+extern "C" int sdqn_net_get_noisy_sigma(sdqn_net_t h, int which_net, int layer, float* buf, int64_t n) {
+  ARGCHK(h && buf, "NULL argument");
+  float* base; int64_t rows, cols; int rc = noisy_sigma_span(h, which_net, layer, n, &base, &rows, &cols); if (rc) return rc;
+  std::vector<float> tmp((size_t)n);
+  { int rc_ = join_comm(h); if (rc_) return rc_; } HIPCHK(hipStreamSynchronize(g_stream));
+  HIPCHK(hipMemcpy(tmp.data(), base, (size_t)n * 4, hipMemcpyDeviceToHost));
+  for (int64_t r = 0; r < rows; ++r) for (int64_t c = 0; c < cols; ++c) buf[r * cols + c] = tmp[(size_t)neon_to_internal(layer, r, c)];
+  return SDQN_OK;
+}
+extern "C" int sdqn_net_set_noisy_sigma(sdqn_net_t h, int which_net, int layer, const float* buf, int64_t n) {
+  ARGCHK(h && buf, "NULL argument");
+  float* base; int64_t rows, cols; int rc = noisy_sigma_span(h, which_net, layer, n, &base, &rows, &cols); if (rc) return rc;
+  std::vector<float> tmp((size_t)n);
+  for (int64_t r = 0; r < rows; ++r) for (int64_t c = 0; c < cols; ++c) tmp[(size_t)neon_to_internal(layer, r, c)] = buf[r * cols + c];
+  { int rc_ = join_comm(h); if (rc_) return rc_; } HIPCHK(hipStreamSynchronize(g_stream));
+  HIPCHK(hipMemcpy(base, tmp.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+  h->nz_stale = true; h->spec_pending = false;
+  return SDQN_OK;
+}
+// the host restatement of the noise (no device): the n 64-bit words / the n unit normals z of stream (seed, step, slot, layer, side); e = f(z)
+static bool noisy_stream_ok(int slot, int layer, int side, int64_t n) { return (slot == 0 || slot == 1) && (layer == 0 || layer == 1) && (side == 0 || side == 1) && n >= 0; }
+extern "C" int sdqn_noisy_words(uint64_t seed, uint64_t step, int slot, int layer, int side, int64_t n, uint64_t* out_words) {
+  ARGCHK(out_words && noisy_stream_ok(slot, layer, side, n), "noise stream: slot 0 / 1, layer 0 (fc4) / 1 (fc5), side 0 (inputs) / 1 (outputs), n >= 0");
+  const uint64_t key = noisy_key(seed, step, slot, layer, side);
+  for (int64_t i = 0; i < n; ++i) out_words[i] = noisy_word(key, (uint64_t)i);
+  return SDQN_OK;
+}
+extern "C" int sdqn_noisy_noise(uint64_t seed, uint64_t step, int slot, int layer, int side, int64_t n, float* out_z) {
+  ARGCHK(out_z && noisy_stream_ok(slot, layer, side, n), "noise stream: slot 0 / 1, layer 0 (fc4) / 1 (fc5), side 0 (inputs) / 1 (outputs), n >= 0");
+  const uint64_t key = noisy_key(seed, step, slot, layer, side);
+  for (int64_t i = 0; i < n; ++i) out_z[i] = noisy_normal(noisy_word(key, (uint64_t)i));
+  return SDQN_OK;
+}
+
 extern "C" int sdqn_net_set_option(sdqn_net_t h, const char* name, int value) {
   ARGCHK(h && name, "NULL argument");
   if (!strcmp(name, "double_dqn") && value) ARGCHK(h->boot_K == 1, "double_dqn cannot be combined with bootstrap_heads %d", h->boot_K);
@@ -822,7 +934,7 @@ extern "C" int sdqn_net_set_option(sdqn_net_t h, const char* name, int value) {
     h->double_dqn = value != 0;
   }
   else if (!strcmp(name, "keep_gradients")) h->keep_grads = value != 0;
-  else if (!strcmp(name, "grad_only")) h->grad_only = value != 0;
+  else if (!strcmp(name, "grad_only")) { ARGCHK(!(value && h->noisy), "grad_only (data parallel) cannot be combined with noisy_nets: sigma's gradient is not exchanged"); h->grad_only = value != 0; }
   else if (!strcmp(name, "h16_wgrad_mfma")) h->h16_wgrad_mfma = value != 0;
   else if (!strcmp(name, "c1w_in_wgrads")) { if (value < 0 || value > 2) { set_error("bad c1w_in_wgrads (0..2)"); return SDQN_ERR_ARG; } h->c1w_in_wgrads = value; }
   else if (!strcmp(name, "dp_half")) h->dp_half = value != 0;              // fp16 mode: half (1, default) or fp32 (0) all-reduce payload
@@ -913,7 +1025,11 @@ extern "C" int sdqn_net_debug_read(sdqn_net_t h, const char* name, float* out, i
     {"d3", h->d3, (int64_t)B * PIX3 * K3}, {"d2p", h->d2p, (int64_t)B * PD2 * PD2 * K2}, {"d1", h->d1, (int64_t)B * PIX1 * K1}, {"q", h->q, (int64_t)2 * B * h->A},
     {"dq", h->dq, (int64_t)B * h->A}, {"g", h->g, h->NP}, {"theta", h->theta, h->NP}, {"cost_terms", h->cost_terms, B},
     {"quantile_targets", h->quant_targets, h->quant_targets ? (int64_t)B * h->quant_N : 0},
-    {"dueling_step", h->duel_step, h->duel_step ? (int64_t)2 * B : 0}};
+    {"dueling_step", h->duel_step, h->duel_step ? (int64_t)2 * B : 0},
+    // --noisy_nets: the factor vectors last composed [2][NOISY_EPS_NET]; the effective buffers (online / target); g_sigma (option keep_gradients)
+    {"noisy_eps", h->nz_eps, h->nz_eps ? (int64_t)2 * NOISY_EPS_NET : 0}, {"noisy_theta", h->nz_eff[0], h->nz_eff[0] ? h->NP : 0},
+    {"noisy_theta_t", h->nz_eff[1], h->nz_eff[1] ? h->NP : 0}, {"noisy_sigma_grad", h->nz_gsig, h->nz_gsig ? h->NP - OFF4 : 0}};
+  if (!strncmp(name, "noisy_", 6)) { int rcn = noisy_fresh(h); if (rcn) return rcn; }
   for (auto& e : tab) if (!strcmp(e.n, name)) {
     ARGCHK(n <= e.len, "buffer %s holds %lld floats", name, (long long)e.len);
     { int rc_ = join_comm(h); if (rc_) return rc_; } HIPCHK(hipStreamSynchronize(g_stream));

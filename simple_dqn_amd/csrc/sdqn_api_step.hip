@@ -168,7 +168,8 @@ static UpdateForm update_form_of(const sdqn_net_s* h, StepStructure structure) {
   if (h->comm) return UPD_DP_SERIAL;
   if (h->grad_only) return UPD_GRAD_ONLY;
   // --dueling masks g between its sums and their application: the split tail a clipped step runs, with or without the clip's own launches
-  return (clip_on(h) || h->dueling) ? UPD_CLIP : UPD_SINGLE;
+  // --noisy_nets forms g_sigma from g between the same two launches
+  return (clip_on(h) || h->dueling || h->noisy) ? UPD_CLIP : UPD_SINGLE;
 }
 UpdateForm update_form(const sdqn_net_s* h) { return update_form_of(h, step_structure(h)); }
 // --clip_grad_norm: g holds the complete gradient sums (all layers [+ the BatchNorm beta | gamma block]); bsz is the divisor the
@@ -279,6 +280,7 @@ StepPlan step_plan(const sdqn_net_s* h) {
   t.ovf = t.exchange == XCH_HALF;
   t.clip = clip_on(h) && (p.update == UPD_CLIP || p.update == UPD_DP_SERIAL);      // the all-reduced gradient, every rank alike
   t.mask = h->dueling && p.update != UPD_GRAD_ONLY;                                // likewise, in every applying form (fc5 is never applied on the side stream)
+  t.noisy = h->noisy && p.update == UPD_CLIP;                                      // --noisy_nets (single GPU only: sdqn_net_set_noisy): the sigma launch; run_train composes around the step
   t.apply_mode = p.update == UPD_SINGLE ? 0 : p.update == UPD_GRAD_ONLY ? -1 : 2;
   t.divisor = (double)h->B * (double)(h->comm ? h->nranks : 1);
   t.skip_fc4 = p.side_fc4 ? 1 : p.fuse_rms;
@@ -322,6 +324,13 @@ int run_update_tail(sdqn_net_s* h, UpdateArgs u, const TailPlan& t, const PrepAr
   }
   if (t.ovf) { u.ovf_flag = h->ovf_flag; u.ovf_count = h->ovf_count; u.ovf_dynamic = h->dp_half_scale_log2 < 0 ? 1 : 0; }
   if (t.mask) LAUNCH(K_UPDATE, launch_dueling_mask(h->g + OFF5, false, h->A, NFC, g_stream));      // --dueling: the clip measures, the optimizer reads the masked g
+  if (t.noisy) {                           // --noisy_nets: sigma moves by the same rule, divisor and learning rate as mu, on g * e of this step's xi
+    NoisyTailArgs nt; memset(&nt, 0, sizeof nt);
+    nt.g = h->g; nt.sigma = h->nz_sigma[0]; nt.state = h->nz_state; nt.state2 = h->nz_state2; nt.eps = h->nz_eps;
+    nt.gsig = h->keep_grads ? h->nz_gsig : nullptr; nt.n = h->NP - OFF4;
+    nt.u = u; nt.u.bsz = (float)t.divisor; nt.u.next.B = 0;
+    LAUNCH(K_UPDATE, launch_noisy_tail(nt, g_stream));
+  }
   if (t.clip) { int rc = clip_gradient(h, t.divisor); if (rc) return rc; }
   u.mode = t.apply_mode; u.bsz = (float)t.divisor;
   if (next) u.next = *next;
@@ -340,8 +349,32 @@ static const int BWD_SEQ[4][12] = {
   /* STEP_H16_BT     */ {K_FC4_DGRAD, K_CONV3_DGRAD, K_CONV2_DGRAD, K_WGRADS, K_BWD1, BWD_END},
   /* STEP_DP_OVERLAP */ {BWD_BN + 3, K_FC4_DGRAD, BWD_BN + 2, K_BWD3, BWD_SIDE_FC4, BWD_BN + 1, K_BWD2, BWD_BN + 0, K_BWD1, BWD_END},
   /* STEP_UNFUSED    */ {BWD_BN + 3, K_FC4_DGRAD, BWD_BN + 2, K_FC4_WGRAD, K_CONV3_WGRAD, K_CONV3_DGRAD, BWD_BN + 1, K_CONV2_WGRAD, K_CONV2_DGRAD, BWD_BN + 0, K_CONV1_WGRAD, BWD_END}};
-int run_train(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd0, const PrepArgs* next) {
+// --noisy_nets: one launch writes the effective buffers of net slots 0 .. nets - 1 under xi_step
+int noisy_compose(sdqn_net_s* h, int64_t step, int nets) {
+  NoisyArgs n; memset(&n, 0, sizeof n);
+  n.mu[0] = h->theta; n.mu[1] = h->theta_t; n.sigma[0] = h->nz_sigma[0]; n.sigma[1] = h->nz_sigma[1]; n.eff[0] = h->nz_eff[0]; n.eff[1] = h->nz_eff[1];
+  n.eps = h->nz_eps; n.seed = h->nz_seed; n.step = (uint64_t)step; n.NP = h->NP; n.A = h->A;
+  n.nets = (nets > 1 && h->theta_t != h->theta) ? 2 : 1;
+  LAUNCH(K_UPDATE, launch_noisy_compose(n, g_stream));
+  return SDQN_OK;
+}
+int noisy_fresh(sdqn_net_s* h) {
+  if (!h->noisy || !h->nz_stale) return SDQN_OK;
+  { int rc = join_comm(h); if (rc) return rc; }
+  h->nz_stale = false;
+  return noisy_compose(h, h->nz_step, 2);
+}
+int run_train(sdqn_net_s* h, const StepArgs& a0, const HeadArgs& hd0, const PrepArgs* next) {
   const StepPlan plan = step_plan(h);
+  // --noisy_nets: step t = nz_step + 1 draws xi_t (online) and xi'_t (target); both forwards, the Double DQN slot and the backward
+  // read the effective buffers, the optimizer tail moves mu (theta) and sigma, and the online net's fc slices are composed again from the
+  // updated parameters under the same xi_t: what the acting paths read until the next step
+  StepArgs a = a0;
+  if (plan.tail.noisy) {
+    int rcn = noisy_compose(h, h->nz_step + 1, 2); if (rcn) return rcn;
+    h->nz_stale = false;
+    a.theta[0] = h->nz_eff[0]; a.theta[1] = h->nz_eff[1];      // (without a target net the two alias, as theta and theta_t do)
+  }
   HeadArgs hd = hd0;
   if (plan.head_train) hd.train = plan.head_train;
   if (plan.head_train == HEAD_MUNCHAUSEN) { hd.mu_alpha = h->mu_alpha; hd.mu_tau = h->mu_tau; hd.mu_clip = h->mu_clip; }
@@ -355,6 +388,8 @@ int run_train(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd0, const PrepA
     else if (h->bn) LAUNCH(K_BN, launch_bn_backward(bn_args(h, a, *s - BWD_BN, 1), g_stream));
   }
   rc = run_update_tail(h, make_update_args(h, a), plan.tail, next); if (rc) return rc;
+  // (the whole online buffer: the apply launch has moved the conv slices too, and the acting forward reads them from here)
+  if (plan.tail.noisy) { h->nz_step += 1; rc = noisy_compose(h, h->nz_step, 1); if (rc) return rc; }
   h->train_iterations += 1;                                                   // deepqnetwork.py:168
   h->spec_pending = false;                 // the online parameters move: a forward enqueued before this step no longer is "predict now"
   return plan.update == UPD_GRAD_ONLY ? SDQN_OK : step_blend(h);      // --target_tau: one blend behind every APPLIED step
@@ -380,17 +415,18 @@ int read_mean_cost(sdqn_net_s* h, int n_steps, float* mean_cost) {
   return per_check_all();
 }
 // The predict forward (what sdqn_net_predict launches) on states already on the device, tuned path: the net's full batch, or B states.
-int predict_forward_tuned(sdqn_net_s* h, const uint8_t* states, const HeadArgs& hd, int B) {
+int predict_forward_tuned(sdqn_net_s* h, const uint8_t* states, const HeadArgs& hd, int B, bool noisy) {
   StepArgs a = step_args(h); a.nz = 1; a.from_ring = 0; a.src = states;
+  if (noisy && h->noisy) a.theta[0] = h->nz_eff[0];       // --noisy_nets: the collecting-mode forward (the caller has run noisy_fresh)
   if (B) a.B = B;
   return run_forward(h, a, hd);
 }
 // ... on either path: `rows` states are wanted (the tuned forward runs its full batch, the generic one these rows); *q: where the Q-values
 // [rows][A] will lie, *q_f64: as doubles (a float64 network)
-int predict_forward(sdqn_net_s* h, const uint8_t* states, int rows, const void** q, int* q_f64) {
+int predict_forward(sdqn_net_s* h, const uint8_t* states, int rows, const void** q, int* q_f64, bool noisy) {
   if (h->gen) { GENCHK(h->gen->forward_dev(states, rows)); *q = h->gen->q_dev(); *q_f64 = h->gen->is_f64() ? 1 : 0; return SDQN_OK; }
   *q = h->q; *q_f64 = 0;
-  return predict_forward_tuned(h, states, head_args(h, HEAD_PREDICT));
+  return predict_forward_tuned(h, states, head_args(h, HEAD_PREDICT), 0, noisy);
 }
 
 extern "C" int sdqn_net_predict_f64(sdqn_net_t h, const uint8_t* states, double* q_out) {
@@ -401,14 +437,24 @@ extern "C" int sdqn_net_predict_f64(sdqn_net_t h, const uint8_t* states, double*
   for (size_t i = 0; i < tmp.size(); ++i) q_out[i] = (double)tmp[i];
   return SDQN_OK;
 }
-extern "C" int sdqn_net_predict(sdqn_net_t h, const uint8_t* states, float* q_out) {
-  ARGCHK(h && states && q_out, "NULL argument");
-  if (h->gen) { GENCHK(h->gen->predict_host(states, h->B, q_out, false)); return SDQN_OK; }
+static int predict_host(sdqn_net_s* h, const uint8_t* states, float* q_out, bool noisy) {
   HIPCHK(hipMemcpyAsync(h->st_states, states, (size_t)h->B * STATE, hipMemcpyHostToDevice, g_stream));
-  int rc = predict_forward_tuned(h, h->st_states, head_args(h, HEAD_PREDICT)); if (rc) return rc;
+  int rc = predict_forward_tuned(h, h->st_states, head_args(h, HEAD_PREDICT), 0, noisy); if (rc) return rc;
   rc = fetch_small(h, h->q, (size_t)h->B * h->A * 4); if (rc) return rc;
   memcpy(q_out, h->h_f, (size_t)h->B * h->A * 4);                             // (B, A): deepqnetwork.py:186 qvalues.T
   return SDQN_OK;
+}
+extern "C" int sdqn_net_predict(sdqn_net_t h, const uint8_t* states, float* q_out) {
+  ARGCHK(h && states && q_out, "NULL argument");
+  if (h->gen) { GENCHK(h->gen->predict_host(states, h->B, q_out, false)); return SDQN_OK; }
+  return predict_host(h, states, q_out, false);                               // (--noisy_nets: mu alone, a score is deterministic)
+}
+// --noisy_nets: the collecting-mode Q-values — the online net's current parameters under the last train step's noise (xi_0 before the first)
+extern "C" int sdqn_net_predict_noisy(sdqn_net_t h, const uint8_t* states, float* q_out) {
+  ARGCHK(h && states && q_out, "NULL argument");
+  ARGCHK(h->noisy, "the network is not a noisy net (sdqn_net_set_noisy)");
+  { int rc = noisy_fresh(h); if (rc) return rc; }
+  return predict_host(h, states, q_out, true);
 }
 
 // the one-launch forward's 8 stripe partials [8][ACT_Q_STRIDE] -> Q-values, added in stripe order; false if a stripe never arrived
@@ -428,10 +474,11 @@ extern "C" int sdqn_net_predict_one(sdqn_net_t h, const uint8_t* state, float* q
   ARGCHK(h && state && q_out, "NULL argument");
   if (h->gen) { GENCHK(h->gen->predict_host(state, 1, q_out, false)); return SDQN_OK; }
   HIPCHK(hipMemcpyAsync(h->st_states, state, (size_t)STATE, hipMemcpyHostToDevice, g_stream));
+  if (noisy_acting(h)) { int rcn = noisy_fresh(h); if (rcn) return rcn; }      // --noisy_nets, train phase: the effective weights
   if (h->act_on && !h->prof_on) {            // the one-launch forward (sdqn_act.hip): the same kernel predict_state runs, the same numbers
     { int rcj = join_comm(h); if (rcj) return rcj; }
     ActArgs aa; memset(&aa, 0, sizeof aa);
-    aa.state = h->st_states; aa.theta = h->theta; aa.scratch = h->act_scratch; aa.ctl = h->act_ctl;
+    aa.state = h->st_states; aa.theta = noisy_acting(h) ? h->nz_eff[0] : h->theta; aa.scratch = h->act_scratch; aa.ctl = h->act_ctl;
     aa.q = h->act_q; aa.A = h->A; aa.seq = h->act_seq++;
     HIPCHK(hipMemsetAsync(h->act_q, 0xFF, (size_t)Q_SLOT_FLOATS * 4, g_stream));          // (an abandoned launch leaves NaNs, checked below)
     LAUNCH(K_ACT, launch_act(aa, false, g_stream));
@@ -440,7 +487,7 @@ extern "C" int sdqn_net_predict_one(sdqn_net_t h, const uint8_t* state, float* q
     h->act_on = false; h->act_fallbacks += 1;
     fprintf(stderr, "simple_dqn_amd: the one-launch acting forward did not complete; using the five-launch forward from now on\n");
   }
-  int rc = predict_forward_tuned(h, h->st_states, head_args(h, HEAD_PREDICT), 1); if (rc) return rc;   // same buffers, batch of one
+  int rc = predict_forward_tuned(h, h->st_states, head_args(h, HEAD_PREDICT), 1, noisy_acting(h)); if (rc) return rc;   // same buffers, batch of one
   rc = fetch_small(h, h->q, (size_t)h->A * 4); if (rc) return rc;
   memcpy(q_out, h->h_f, (size_t)h->A * 4);
   return SDQN_OK;

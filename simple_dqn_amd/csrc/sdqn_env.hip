@@ -540,7 +540,8 @@ static int env_collect(sdqn_net_t h, sdqn_env_t e, sdqn_replay_t r, int N, int64
       double eps = epsilon_start + (double)t * epsilon_step;
       eps = eps < 0.0 ? 0.0 : (eps > 1.0 ? 1.0 : eps);
       a.q = nullptr;
-      if (eps < 1.0) { rc = predict_forward(h, cur, N, &a.q, &a.q_f64); if (rc) return rc; rc = env_select<G>(h, a, 0); if (rc) return rc; }
+      // (--noisy_nets: collecting reads the effective weights — the current parameters under the last train step's noise; evaluating reads mu)
+      if (eps < 1.0) { rc = noisy_fresh(h); if (rc) return rc; rc = predict_forward(h, cur, N, &a.q, &a.q_f64, true); if (rc) return rc; rc = env_select<G>(h, a, 0); if (rc) return rc; }
       a.thresh = (uint64_t)ceil(ldexp(eps, 53));
       a.t = t; a.src = cur; a.dst = h->col_win + (size_t)((T + 1) & 1) * g.half;
       c.pos = p;

@@ -103,6 +103,52 @@ def check_dueling(args, num_actions=None):
     return True
 
 
+def check_noisy(args):
+    """--noisy_nets / --noisy_sigma: float32 on 84 x 84 x 4 and none of --batch_norm, --clip_grad_norm, --target_tau,
+    --munchausen, --advantage_learning, --bootstrap_heads > 1, --quantiles > 1, --dueling.  Raises ValueError naming the flag; touches no
+    device.  Returns (on, sigma0)."""
+    sigma0 = float(getattr(args, "noisy_sigma", 0.5) if getattr(args, "noisy_sigma", 0.5) is not None else 0.5)
+    if not bool(getattr(args, "noisy_nets", False)):
+        return False, sigma0
+    if not (sigma0 >= 0.0 and sigma0 < float("inf")):
+        raise ValueError("--noisy_sigma %r: must be a finite value >= 0" % (sigma0,))
+    follow = " (DESIGN.md §33 lists it as a follow-up)"
+    dt = str(getattr(args, "datatype", "float32"))
+    if dt != "float32":
+        raise ValueError("--noisy_nets cannot be combined with --datatype %s%s" % (dt, follow))
+    geom = (int(getattr(args, "history_length", 4)), int(getattr(args, "screen_height", 84)), int(getattr(args, "screen_width", 84)))
+    if geom != (4, 84, 84):
+        raise ValueError("--noisy_nets needs 84 x 84 screens with --history_length 4, not --screen_height %d --screen_width %d --history_length %d%s"
+                         % (geom[1], geom[2], geom[0], follow))
+    for flag in ("batch_norm", "munchausen", "dueling"):
+        if getattr(args, flag, False):
+            raise ValueError("--noisy_nets cannot be combined with --%s%s" % (flag, follow))
+    for flag in ("clip_grad_norm", "target_tau", "advantage_learning"):
+        if float(getattr(args, flag, 0.0) or 0.0) > 0.0:
+            raise ValueError("--noisy_nets cannot be combined with --%s %g%s" % (flag, float(getattr(args, flag)), follow))
+    for flag in ("bootstrap_heads", "quantiles"):
+        v = getattr(args, flag, 1)
+        if (1 if v is None else int(v)) > 1:
+            raise ValueError("--noisy_nets cannot be combined with --%s %d%s" % (flag, int(v), follow))
+    return True, sigma0
+
+
+def noisy_words(seed, step, slot, layer, side, n):
+    """--noisy_nets: the n 64-bit words of noise stream (seed, step, slot, layer, side), restated on the host (csrc/noisy.h; no device)"""
+    out = np.empty(int(n), np.uint64)
+    lib = _lib.load()
+    _lib.check(lib.sdqn_noisy_words(int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), int(slot), int(layer), int(side), out.size, _lib.ptr(out, C.c_uint64)))
+    return out
+
+
+def noisy_noise(seed, step, slot, layer, side, n):
+    """--noisy_nets: the n unit normals z of that stream (float32); the factor is f(z) = sgn(z) sqrt|z|"""
+    out = np.empty(int(n), np.float32)
+    lib = _lib.load()
+    _lib.check(lib.sdqn_noisy_noise(int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), int(slot), int(layer), int(side), out.size, _lib.ptr(out, C.c_float)))
+    return out
+
+
 def check_advantage_learning(args):
     """--advantage_learning alpha / --persistent_advantage: alpha in [0, 1) (0: off), the persistent form only with
     alpha > 0 and one-step targets, and alpha > 0 with none of --double_dqn, --munchausen, --bootstrap_heads K > 1, --batch_norm.  Raises
@@ -135,6 +181,7 @@ class DeepQNetwork:
     def __init__(self, num_actions, args):
         # Bootstrapped DQN: K Q-heads over one torso are a library net with K x num_actions outputs, row k A + a = head k, action a
         al_alpha, al_persistent = check_advantage_learning(args)
+        self.noisy_nets, self.noisy_sigma = check_noisy(args)
         self.bootstrap_heads, self.bootstrap_mask_probability = check_bootstrap(args, num_actions)
         # quantile-regression DQN: N quantiles per action are a library net with N x num_actions outputs, row j A + a = quantile j, action a
         self.quantiles = check_quantiles(args, num_actions)
@@ -239,6 +286,10 @@ class DeepQNetwork:
             _lib.check(self._lib.sdqn_net_set_quantiles(h, self.quantiles))
         if self.dueling:                                       # (off: the library is not told anything)
             _lib.check(self._lib.sdqn_net_set_dueling(h, 1))
+        # noisy networks: fc4 and fc5 are mu + sigma * noise; the weights (get_weights, the .npz keys) are mu
+        self.noisy_seed = int(getattr(args, "random_seed", 0) or 0) & 0xFFFFFFFFFFFFFFFF
+        if self.noisy_nets:                                    # (off: the library is not told anything)
+            _lib.check(self._lib.sdqn_net_set_noisy(h, 1, self.noisy_sigma, self.noisy_seed))
         self._mt_buf = (C.c_uint32 * _lib.MT_WORDS)()
         self._act_out = C.c_int(); self._act_greedy = self._lib.sdqn_net_act_greedy
         self._env_r, self._env_t = C.c_int(), C.c_int(); self._act_step_env = self._lib.sdqn_net_act_step_env
@@ -332,6 +383,8 @@ class DeepQNetwork:
         self._boot_vote = bool(test)
         if self.bootstrap_heads > 1:
             _lib.check(self._lib.sdqn_net_bootstrap_acting(self._h, int(self._boot_vote), 0))
+        if self.noisy_nets:                                     # --noisy_nets: mu alone while testing, the last step's noise while collecting
+            _lib.check(self._lib.sdqn_net_noisy_acting(self._h, 0 if test else 1))
 
     def next_episode(self, reset=False):
         """a fresh episode starts: the episode number, which picks the Q-head to follow, advances (reset=True: returns to 0)"""
@@ -452,6 +505,60 @@ class DeepQNetwork:
         if self.bootstrap_heads == 1:
             return q
         return q.reshape(self.batch_size, self.bootstrap_heads, self.num_actions).mean(axis=1, dtype=self._np)     # the head-mean [B][A]
+
+    def predict_noisy(self, states):
+        """--noisy_nets: the collecting-mode Q-values [B][A] — the online net's current mu and sigma under the last train step's noise
+        (the noise of step 0 before the first); predict() reads mu alone."""
+        assert self.noisy_nets, "predict_noisy needs --noisy_nets"
+        assert states.shape == ((self.batch_size, self.history_length,) + self.screen_dim)
+        st = np.ascontiguousarray(states, dtype=np.uint8)
+        q = np.empty((self.batch_size, self._net_actions), dtype=np.float32)
+        _lib.check(self._lib.sdqn_net_predict_noisy(self._h, _lib.ptr(st, C.c_uint8), _lib.ptr(q, C.c_float)))
+        return q
+
+    def get_noisy_sigma(self, which=0):
+        """--noisy_nets: [sigma of fc4 (512, 3136), sigma of fc5 (A, 512)] of the online (0) or target (1) net, laid out as the weights"""
+        out = []
+        for layer in (3, 4):
+            w = np.empty(self._shapes[layer], dtype=np.float32)
+            _lib.check(self._lib.sdqn_net_get_noisy_sigma(self._h, int(which), layer, _lib.ptr(w, C.c_float), w.size))
+            out.append(w)
+        return out
+
+    def set_noisy_sigma(self, sigmas, which=0):
+        """--noisy_nets: set both sigmas of one net between steps (the next forward that reads them sees them)"""
+        for layer, w in zip((3, 4), sigmas):
+            w = np.ascontiguousarray(w, dtype=np.float32)
+            assert w.shape == self._shapes[layer], (w.shape, layer)
+            _lib.check(self._lib.sdqn_net_set_noisy_sigma(self._h, int(which), layer, _lib.ptr(w, C.c_float), w.size))
+
+    def noisy_step(self):
+        """--noisy_nets: t of the noise xi_t the acting paths read now = train steps this net has run"""
+        t = C.c_int64()
+        _lib.check(self._lib.sdqn_net_get_noisy(self._h, None, None, None, C.byref(t)))
+        return t.value
+
+    def noisy_eps(self):
+        """--noisy_nets: the factor vectors f(z) last composed on the device, per net slot: [{"in4", "out4", "in5", "out5"}, ...]"""
+        (o4, i4), (o5, i5) = self._shapes[3], self._shapes[4]      # fc4 (512, 3136), fc5 (A, 512); a net's block: in4 | out4 | in5 | out5 padded to 32
+        n_net = i4 + o4 + i5 + 32
+        raw = self.debug_read("noisy_eps", 2 * n_net)
+        out = []
+        for z in range(2):
+            v = raw[z * n_net:(z + 1) * n_net]
+            out.append(dict(in4=v[:i4].copy(), out4=v[i4:i4 + o4].copy(), in5=v[i4 + o4:i4 + o4 + i5].copy(), out5=v[i4 + o4 + i5:i4 + o4 + i5 + o5].copy()))
+        return out
+
+    def noisy_fc(self, name):
+        """--noisy_nets: the fc4 / fc5 slices of a debug buffer in the weights' layout [(512, 3136), (A, 512)]: "noisy_theta",
+        "noisy_theta_t" (the effective weights) or "noisy_sigma_grad" (option keep_gradients)"""
+        size = lambda shp: int(np.prod(shp))
+        nconv, n4, n5 = sum(size(s) for s in self._shapes[:3]), size(self._shapes[3]), size(self._shapes[4])
+        units, maps = self._shapes[3][0], self._shapes[2][1]        # 512 hidden units; conv3's 64 feature maps of 49 pixels
+        skip = 0 if name == "noisy_sigma_grad" else nconv
+        raw = self.debug_read(name, skip + n4 + n5)[skip:]
+        w4 = raw[:n4].reshape(-1, maps, units).transpose(2, 1, 0).reshape(self._shapes[3])        # internal [pix][f][unit] -> [unit][f 49 + pix]
+        return [np.ascontiguousarray(w4), raw[n4:].reshape(self._shapes[4]).copy()]
 
     def predict_heads(self, states):
         """--bootstrap_heads: the Q-values of every Q-head, [B][K][A] (K = 1: predict() with an axis of one)"""
@@ -582,6 +689,9 @@ class DeepQNetwork:
             return                                                 # (online model only, like model.load_params: the target
                                                                    #  net follows at the next update_target_network, agent.py:105)
         with np.load(load_path) as f:
+            has_sigma = any(k in f for k in ("NS3", "NS4", "NSt3", "NSt4"))
+            if has_sigma and not self.noisy_nets:
+                raise ValueError("%s holds noisy-net sigmas (keys NS3 / NS4): load it into a network created with --noisy_nets" % (load_path,))
             for which, key in ((0, "W"), (1, "Wt"), (2, "S"), (4, "S2")):
                 for i in range(5):
                     name = "%s%d" % (key, i)
@@ -596,6 +706,12 @@ class DeepQNetwork:
                     for l in range(4):
                         if "%s_bn%d" % (key, l) in f:
                             self.set_bn(l, *f["%s_bn%d" % (key, l)], which=which, running=True)
+            # --noisy_nets: sigma of both nets ("NS3" / "NS4", "NSt3" / "NSt4"; its optimizer state does not travel).  A file without the
+            # keys leaves the init sigma; a file with them is a noisy net's: a plain net has refused it by name above
+            if has_sigma:
+                for which, key in ((0, "NS"), (1, "NSt")):
+                    if key + "3" in f and key + "4" in f:
+                        self.set_noisy_sigma([f[key + "3"], f[key + "4"]], which)
             if "train_iterations" in f:
                 self.train_iterations = int(f["train_iterations"])
 
@@ -618,6 +734,10 @@ class DeepQNetwork:
             for which, key in ((0, "run"), (1, "run_t")):
                 for l in range(4):
                     d["%s_bn%d" % (key, l)] = np.stack(self.get_bn(l, which, running=True))
+        if self.noisy_nets:
+            for which, key in ((0, "NS"), (1, "NSt")):
+                s4, s5 = self.get_noisy_sigma(which)
+                d[key + "3"], d[key + "4"] = s4, s5
         d["train_iterations"] = np.int64(self.train_iterations)
         with open(save_path, "wb") as f:
             np.savez(f, **d)

@@ -50,6 +50,8 @@ _OPTIONS = {
         ("--advantage_learning", float, 0.0, dict(help="Advantage learning (Bellemare et al. 2016): subtract this fraction, in [0, 1), of the target net's action gap max_a Q(s, a) - Q(s, a_taken) from the target (0: off; the paper uses 0.9).")),
         ("--persistent_advantage", _flag, False, dict(help="Persistent advantage learning: on non-terminal transitions take the larger of the advantage-learning target and the one with the poststate's gap of the same action (needs --advantage_learning > 0).")),
         ("--dueling", _flag, False, dict(help="Dueling architecture (Wang et al. 2016): a value stream over one half of fc4's units and an advantage stream over the other, Q = V + Adv - mean(Adv); the network gets actions + 1 <= 18 outputs.")),
+        ("--noisy_nets", _flag, False, dict(help="Noisy networks (Fortunato et al. 2018): factorised Gaussian noise on the two fully connected layers, W = mu + sigma * noise with learned sigma; one noise sample per net per train step, collecting acts under the last step's noise, testing on mu alone. Use with --exploration_rate_start 0 --exploration_rate_end 0.")),
+        ("--noisy_sigma", float, 0.5, dict(help="Noisy networks: sigma starts at this value / sqrt(fan_in).")),
         ("--quantiles", int, 1, dict(help="Quantile-regression DQN: this many quantile estimates per action (quantiles x actions <= 18), trained with the quantile Huber loss at threshold --clip_error; acting takes the mean over the quantiles (1: off).")),
         ("--bootstrap_heads", int, 1, dict(help="Bootstrapped DQN: this many Q-heads over one shared torso (heads x actions <= 18); acting follows one head per episode while training, the heads' majority vote while testing (1: off).")),
         ("--bootstrap_mask_probability", float, 1.0, dict(help="Bootstrapped DQN: probability that a Q-head trains on a transition, in (0, 1]; the mask is a fixed function of the replay slot.")),
@@ -207,8 +209,15 @@ def check_dueling(args, num_actions=None):
     return check(args, num_actions)
 
 
+def check_noisy(args):
+    """--noisy_nets / --noisy_sigma: what they cannot be combined with, refused before anything touches the device"""
+    from .deepqnetwork import check_noisy as check
+    return check(args)
+
+
 def run(args):
     train_envs = check_train_envs(args)
+    check_noisy(args)
     check_dueling(args)
     check_bootstrap(args)
     check_quantiles(args)

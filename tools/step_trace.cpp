@@ -91,6 +91,12 @@ template <> hipError_t launch_grad_scale<float>(float* g, int64_t n, const doubl
 hipError_t launch_dueling_mask(void* w5, bool f64, int rows, int H, hipStream_t s) {
   fprintf(g_out, "  %s %2d %-11s w5=%s f64=%d rows=%d H=%d\n", sname(s), K_UPDATE, "duel_mask", nm(w5).c_str(), (int)f64, rows, H); return hipSuccess;
 }
+hipError_t launch_noisy_compose(const NoisyArgs& a, hipStream_t s) {
+  fprintf(g_out, "  %s %2d %-11s eff=%s step=%llu nets=%d\n", sname(s), K_UPDATE, "nz_compose", nm(a.eff[0]).c_str(), (unsigned long long)a.step, a.nets); return hipSuccess;
+}
+hipError_t launch_noisy_tail(const NoisyTailArgs& a, hipStream_t s) {
+  fprintf(g_out, "  %s %2d %-11s g=%s sigma=%s bsz=%g opt=%d keep=%d\n", sname(s), K_UPDATE, "nz_sigma", nm(a.g).c_str(), nm(a.sigma).c_str(), (double)a.u.bsz, a.u.opt, a.gsig != nullptr); return hipSuccess;
+}
 hipError_t launch_target_blend(TargetBlendArgs a, hipStream_t s) {
   fprintf(g_out, "  %s %2d %-11s tau=%g\n", sname(s), K_TARGET, "blend", (double)a.tau); return hipSuccess;
 }

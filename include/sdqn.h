@@ -457,6 +457,23 @@ int sdqn_net_set_noisy_sigma(sdqn_net_t h, int which_net, int layer, const float
 int sdqn_net_predict_noisy(sdqn_net_t h, const uint8_t* states, float* q_out);
 int sdqn_noisy_words(uint64_t seed, uint64_t step, int slot, int layer, int side, int64_t n, uint64_t* out_words);
 int sdqn_noisy_noise(uint64_t seed, uint64_t step, int slot, int layer, int side, int64_t n, float* out_z);
+/* Random-shift augmentation, --random_shift P (DrQ: Kostrikov, Yarats and Fergus 2020; no reference counterpart).  P in 0..8,
+ * 0 (default) off: nothing changes.  P > 0: every train step that samples from a replay memory — sdqn_net_train_many, _train_many_deferred,
+ * _train_replay, prioritized or not, any datatype and geometry — trains on shifted states: sample n and state s (0 prestate, 1 poststate)
+ * draw (dy, dx) in [-P, P]^2, and output pixel (y, x) of every frame of the state is input pixel (clamp(y + dy, 0, H - 1), clamp(x + dx, 0,
+ * W - 1)): replicate-padding by P, then a crop.  The bytes stay exact; every forward of the step (online, target, the Double DQN slot, the
+ * Munchausen / advantage-learning forward on the prestates) reads the same shifted state.  One launch in front of the step writes the 2 B
+ * shifted states into the memory's device minibatch (what sdqn_replay_gather fills: a pending minibatch there is overwritten), and the step
+ * reads it in place, as sdqn_net_train_host does with states_in_place.  The draws are a counter: splitmix64 keyed by (seed, t, n, s), t = 0,
+ * 1, ... the shifted steps this handle has enqueued since the setter (which returns t to 0); sdqn_random_shift_draw restates them on the host
+ * (no device).  Sampling, indexes, weights and priorities are what they are with P = 0; sdqn_net_train_host / _returns (the caller's own
+ * states), predict, acting, sdqn_env_eval and sdqn_env_collect are never shifted.  SDQN_ERR_ARG: P outside 0..8, P > 0 with batch_norm or with
+ * P >= min(screen_height, screen_width).  sdqn_net_last_shifts: out [B][2][2] = (dy, dx) per sample and state as the last step's launch
+ * drew them (waits for the device; SDQN_ERR_ARG before the first shifted step). */
+int sdqn_net_set_random_shift(sdqn_net_t h, int P, uint64_t seed);
+int sdqn_net_get_random_shift(sdqn_net_t h, int* P, int64_t* step_counter);      /* any pointer may be NULL */
+int sdqn_random_shift_draw(uint64_t seed, uint64_t step, int64_t n, int s, int P, int* dy, int* dx);
+int sdqn_net_last_shifts(sdqn_net_t h, int8_t* out);
 /* option "double_dqn" (0 default / 1, any configuration, switchable between steps): Double DQN targets (van Hasselt, Guez and Silver
  * 2016): the online net picks each poststate's action, the target net values it (see sdqn_net_last_q).  The online net's forward on
  * the poststates rides as a third net slot in the step's own forward launches (batch_norm: a forward of its own in front of the step,

@@ -157,6 +157,10 @@ SIGNATURES = {
     "sdqn_net_predict_noisy": (C.c_int, [_vp, _u8p, _f32p]),
     "sdqn_noisy_words": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int64, C.POINTER(C.c_uint64)]),
     "sdqn_noisy_noise": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int64, _f32p]),
+    "sdqn_net_set_random_shift": (C.c_int, [_vp, C.c_int, C.c_uint64]),
+    "sdqn_net_get_random_shift": (C.c_int, [_vp, C.POINTER(C.c_int), _i64p]),
+    "sdqn_random_shift_draw": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "sdqn_net_last_shifts": (C.c_int, [_vp, C.POINTER(C.c_int8)]),
     "sdqn_net_sync": (C.c_int, [_vp]),
     "sdqn_net_apply_update": (C.c_int, [_vp, C.c_double]),
     "sdqn_net_grad_to_half": (C.c_int, [_vp, C.POINTER(C.c_uint16), C.c_int64]),

@@ -20,6 +20,7 @@
 #include "sdqn_per.h"
 #include "sdqn_clip.h"
 #include "noisy.h"
+#include "shift.h"
 
 using namespace sdqn;
 
@@ -163,6 +164,11 @@ struct sdqn_net_s {
   // (noisy_fresh).  nz_collecting: the single-environment acting paths use the effective weights (train phase) or mu (test phase)
   bool noisy = false, nz_stale = false, nz_collecting = true; double nz_sigma0 = 0.5; uint64_t nz_seed = 0; int64_t nz_step = 0;
   float *nz_sigma[2] = {nullptr, nullptr}, *nz_eff[2] = {nullptr, nullptr}, *nz_state = nullptr, *nz_state2 = nullptr, *nz_eps = nullptr, *nz_gsig = nullptr;
+  // --random_shift (sdqn_net_set_random_shift; shift.h, sdqn_shift.hip): shift_P > 0: every train step that samples from a replay
+  // memory (sdqn_net_train_many / _deferred / _replay, prioritized or not) first writes the shifted minibatch into the memory's device
+  // minibatch (one launch, shift_minibatch) and runs as the step that reads a device minibatch in place.  shift_step: such steps enqueued =
+  // the t of the next step's draws; shift_out: [B][2][2] the (dy, dx) the last launch drew, allocated by the setter.  0: nothing changes
+  int shift_P = 0; uint64_t shift_seed = 0; int64_t shift_step = 0; int8_t* shift_out = nullptr;
   int n_step = 1;                          // --n_step (option "n_step"): poststate frame offset of the ring paths, n-step head
   double target_tau = 0.0;                 // --target_tau (sdqn_net_set_target_tau): > 0: every train step is followed by one soft target update
   // --clip_grad_norm (sdqn_net_set_clip_grad_norm): > 0: the flat gradient is scaled to this global L2 norm (of the MEAN
@@ -348,6 +354,7 @@ int predict_forward(sdqn_net_s* h, const uint8_t* states, int rows, const void**
 StepArgs ring_step_args(sdqn_net_s* h, const sdqn_replay_s* r);
 int run_ring_step(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* host_idx, const HeadArgs& hd, const PrepArgs* next = nullptr);
 int check_replay_geometry(const sdqn_net_s* h, const sdqn_replay_s* r);
+int shift_minibatch(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* didx);   // --random_shift: the launch (the caller has checked shift_P > 0); didx: the step's indexes as the device reads them
 bool act_sum_partials(const float* part, int A, float* q_out);
 const uint8_t* statebuf_window(sdqn_statebuf_s* s);
 int statebuf_advance(sdqn_statebuf_s* s, uint8_t** host_frame, uint8_t** dev_slot);

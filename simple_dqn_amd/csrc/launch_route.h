@@ -17,7 +17,8 @@ enum KernelId {
   K_BWD2,      // one launch: conv2_dgrad + conv2_wgrad (both depend on conv3_dgrad only) + a share of fc4_wgrad
   K_BWD1,      // one launch: conv1_wgrad + the last share of fc4_wgrad
   K_BN,        // --batch_norm: one BatchNorm layer, forward ([partial +] apply) or backward (partial + apply)
-  K_RESERVED_20, K_RESERVED_21, K_RESERVED_22, K_RESERVED_23,   // ids of retired round-3 launches: the numbers are public (options bt:/xcd:/nw:<id>, profile_read), nothing launches them
+  K_SHIFT,     // --random_shift: the shifted minibatch, one launch in front of the step (sdqn_shift.hip); the id of a retired round-3 launch, reused
+  K_RESERVED_21, K_RESERVED_22, K_RESERVED_23,   // ids of retired round-3 launches: the numbers are public (options bt:/xcd:/nw:<id>, profile_read), nothing launches them
   K_WGRADS,    // round 4 (float16, B >= 128): fc4_wgrad (+ fused RMSProp) || conv3_wgrad || conv2_wgrad in one launch, after the block-tile dgrad chain
   K_ACT,       // round 4: the acting forward (batch of one) as ONE launch (sdqn_act.hip)
   K_COLLECT,   // --train_envs: one lockstep of N games of catch written into the laned ring (sdqn_env.hip; not a launch of the train step)

@@ -114,7 +114,7 @@ static int forward(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd, const L
   { int rc = join_comm(h); if (rc) return rc; }                // conv1..3 of this step overlap the previous step's fc4 all-reduce
   PLANNED_LAUNCH(K_FC4_FWD, f, l);
   BN_FWD(3);
-  const BootArgs boot = {h->boot_K, game_actions(h), h->boot_thresh, bootstrap_mask_seed(h->boot_seed), a.from_ring ? a.idx : nullptr};   // (read when HEAD_BOOTSTRAP)
+  const BootArgs boot = {h->boot_K, game_actions(h), h->boot_thresh, bootstrap_mask_seed(h->boot_seed), a.idx};   // (read when HEAD_BOOTSTRAP; the ring indexes: set by the ring paths alone)
   const QuantArgs quant = {h->quant_N, game_actions(h), h->quant_targets};      // (read when HEAD_QUANTILE)
   const DuelArgs duel = {h->dueling ? 1 : 0, game_actions(h), h->duel_step};      // (read when HEAD_DUELING)
   LAUNCH(K_HEAD, launch_head(f, hd, g_stream, h->head_q_system, &boot, &quant, &duel));      // (head_q_system: the acting path, never with batch_norm)
@@ -615,7 +615,24 @@ StepArgs ring_step_args(sdqn_net_s* h, const sdqn_replay_s* r) {
   StepArgs a = step_args(h); a.from_ring = 1; a.src = r->d_ring; a.idx = h->d_idx;
   return a;
 }
+// --random_shift: the step's 2 B shifted states into r's device minibatch, from the ring at the indexes in didx
+int shift_minibatch(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* didx) {
+  ARGCHK(h->shift_P < r->H && h->shift_P < r->W, "random_shift %d needs screens larger than the shift (replay memory %dx%d)", h->shift_P, r->H, r->W);
+  ShiftArgs s; memset(&s, 0, sizeof s);
+  s.ring = r->d_ring; s.idx = didx; s.pre = r->d_pre; s.post = r->d_post; s.shifts = h->shift_out; s.size = r->size;
+  s.seed = h->shift_seed; s.step = (uint64_t)h->shift_step;
+  s.B = r->B; s.hist = r->hist; s.H = r->H; s.W = r->W; s.P = h->shift_P; s.post_off = r->ns.n > 1 ? r->ns.n : 1;      // (problems.h soff)
+  r->mb_dev_gen++;                                  // (the launch overwrites the device minibatch: gather_args)
+  LAUNCH(K_SHIFT, launch_shift_gather(s, g_stream));
+  h->shift_step += 1;
+  return SDQN_OK;
+}
 int run_ring_step(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* host_idx, const HeadArgs& hd, const PrepArgs* next) {
+  if (h->shift_P > 0) {            // the step that reads a device minibatch in place (sdqn_net_train_host with states_in_place), on the shifted one;
+    int rcs = shift_minibatch(h, r, h->d_idx); if (rcs) return rcs;      // (a, r, t) stay where prep left them
+    StepArgs a = step_args(h); a.from_ring = 0; a.src = r->d_pre; a.idx = h->d_idx;      // (idx: the bootstrap head's masks are keyed by ring index)
+    return run_train(h, a, hd, next);
+  }
   h->host_idx_cur = host_idx;
   const int rc = run_train(h, ring_step_args(h, r), hd, next);
   h->host_idx_cur = nullptr;
@@ -634,6 +651,7 @@ static int gen_train_replay(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* idx_
   int slot; const int64_t* didx; int rc = check_ring_actions(h, r, idx_host); if (rc) return rc;
   rc = replay_push_idx(r, idx_host, &slot, &didx); if (rc) return rc;
   rc = replay_gather_generic(r, didx); if (rc) return rc;
+  if (h->shift_P > 0) { rc = shift_minibatch(h, r, didx); if (rc) return rc; }      // --random_shift: the states again, shifted; (a, r, t) stay
   if (h->boot_K > 1) GENCHK(h->gen->boot_idx(didx));                    // (copied on the stream, in front of the slot's release)
   rc = replay_release_idx_batched(r, slot, false); if (rc) return rc;
   GENCHK(h->gen->train_dev(r->d_pre, r->d_post, r->d_act, r->d_rew, r->d_term, h->epoch));
@@ -732,5 +750,35 @@ extern "C" int sdqn_net_cost_collect(sdqn_net_t h, int64_t ticket, float* mean_c
   uint64_t bits = *w; double sum; memcpy(&sum, &bits, 8);
   *mean_cost = (float)(sum / h->cost_steps[slot]);
   return per_check_all();
+}
+// ---- --random_shift ---------------------------------------------------------------------------------------------------
+extern "C" int sdqn_net_set_random_shift(sdqn_net_t h, int P, uint64_t seed) {
+  ARGCHK(h, "NULL handle");
+  ARGCHK(P >= 0 && P <= SHIFT_MAX_PAD, "random_shift %d out of range [0, %d]", P, SHIFT_MAX_PAD);
+  if (P > 0) {
+    ARGCHK(!h->bn, "random_shift cannot be combined with batch_norm: the shift would change the batch statistics");
+    ARGCHK(P < h->cfg.screen_height && P < h->cfg.screen_width, "random_shift %d needs screens larger than the shift (%dx%d)", P, h->cfg.screen_height, h->cfg.screen_width);
+    if (!h->shift_out) { int rc = dalloc(h, (void**)&h->shift_out, (size_t)h->B * 4); if (rc) return rc; }
+  }
+  h->shift_P = P; h->shift_seed = seed; h->shift_step = 0;
+  return SDQN_OK;
+}
+extern "C" int sdqn_net_get_random_shift(sdqn_net_t h, int* P, int64_t* step_counter) {
+  ARGCHK(h, "NULL handle");
+  if (P) *P = h->shift_P; if (step_counter) *step_counter = h->shift_step;
+  return SDQN_OK;
+}
+extern "C" int sdqn_random_shift_draw(uint64_t seed, uint64_t step, int64_t n, int s, int P, int* dy, int* dx) {
+  ARGCHK(dy && dx, "NULL argument");
+  ARGCHK(P >= 0 && P <= SHIFT_MAX_PAD && n >= 0 && (s == 0 || s == 1), "bad arguments (P %d, n %lld, s %d)", P, (long long)n, s);
+  shift_draw(seed, step, (uint64_t)n, (uint64_t)s, P, *dy, *dx);
+  return SDQN_OK;
+}
+extern "C" int sdqn_net_last_shifts(sdqn_net_t h, int8_t* out) {
+  ARGCHK(h && out, "NULL argument");
+  ARGCHK(h->shift_out && h->shift_step > 0, "no train step has run with random_shift > 0 (sdqn_net_set_random_shift)");
+  HIPCHK(hipMemcpyAsync(out, h->shift_out, (size_t)h->B * 4, hipMemcpyDeviceToHost, g_stream));
+  HIPCHK(hipStreamSynchronize(g_stream));
+  return SDQN_OK;
 }
 extern "C" int sdqn_mt_words(uint64_t* words) { ARGCHK(words, "NULL argument"); *words = mt_words_drawn(); return SDQN_OK; }

@@ -18,7 +18,7 @@ static const char* k_names[K_COUNT] = {
   "fc4_dgrad", "fc4_wgrad", "conv3_dgrad", "conv3_wgrad", "conv2_dgrad", "conv2_wgrad",
   "conv1_wgrad", "update(reduce+fc5wgrad+rmsprop)", "rccl_allreduce", "replay_gather_u8", "prep(idx+meta)",
   "bwd3(conv3_dgrad+conv3_wgrad+fc4_wgrad)", "bwd2(conv2_dgrad+conv2_wgrad+fc4_wgrad)", "bwd1(conv1_wgrad+fc4_wgrad)",
-  "batchnorm(layer fwd/bwd)", "reserved", "reserved", "reserved", "reserved",
+  "batchnorm(layer fwd/bwd)", "shift_gather(random_shift)", "reserved", "reserved", "reserved",
   "wgrads(fc4+conv3+conv2)", "act(conv1..fc5, one state)", "catch_collect(lockstep)", "target_blend(polyak)"};
 const char* kernel_name(int id) { return (id >= 0 && id < K_COUNT) ? k_names[id] : "?"; }
 LaunchEvents& launch_events() { static thread_local LaunchEvents le; return le; }

@@ -443,6 +443,7 @@ static void per_targets(sdqn_net_s* h, sdqn_replay_s* r, PerStepArgs& a) {
 static int per_gen_step(sdqn_net_s* h, sdqn_replay_s* r) {
   PerState* p = r->per;
   int rc = replay_gather_generic(r, p->sidx); if (rc) return rc;
+  if (h->shift_P > 0) { rc = shift_minibatch(h, r, p->sidx); if (rc) return rc; }      // --random_shift: the states again, shifted; (a, r, t) stay
   h->gen->set_per(p->w, p->newp, p->alpha, p->eps);
   const hipError_t e = h->gen->train_dev(r->d_pre, r->d_post, r->d_act, r->d_rew, r->d_term, h->epoch);
   h->gen->set_per(nullptr, nullptr, 0.0, 0.0);

@@ -149,6 +149,30 @@ def noisy_noise(seed, step, slot, layer, side, n):
     return out
 
 
+def check_random_shift(args):
+    """--random_shift P: P in 0..8 (0: off), P < min(screen_height, screen_width), and P > 0 not with --batch_norm.  Raises
+    ValueError naming the flag; touches no device.  Returns P."""
+    P = getattr(args, "random_shift", 0)
+    P = 0 if P is None else int(P)
+    if not 0 <= P <= 8:
+        raise ValueError("--random_shift %d: must be in [0, 8] (0: off)" % P)
+    if P == 0:
+        return 0
+    if getattr(args, "batch_norm", False):
+        raise ValueError("--random_shift cannot be combined with --batch_norm: the shift would change the batch statistics, and that case has no oracle")
+    hw = (int(getattr(args, "screen_height", 84)), int(getattr(args, "screen_width", 84)))
+    if P >= min(hw):
+        raise ValueError("--random_shift %d needs screens larger than the shift (--screen_height %d --screen_width %d)" % ((P,) + hw))
+    return P
+
+
+def random_shift_draw(seed, step, n, s, P):
+    """--random_shift: (dy, dx) of sample n, state s (0 prestate, 1 poststate) of shifted train step `step`, restated on the host (csrc/shift.h; no device)"""
+    dy, dx = C.c_int(), C.c_int()
+    _lib.check(_lib.load().sdqn_random_shift_draw(int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), int(n), int(s), int(P), C.byref(dy), C.byref(dx)))
+    return dy.value, dx.value
+
+
 def check_advantage_learning(args):
     """--advantage_learning alpha / --persistent_advantage: alpha in [0, 1) (0: off), the persistent form only with
     alpha > 0 and one-step targets, and alpha > 0 with none of --double_dqn, --munchausen, --bootstrap_heads K > 1, --batch_norm.  Raises
@@ -182,6 +206,7 @@ class DeepQNetwork:
         # Bootstrapped DQN: K Q-heads over one torso are a library net with K x num_actions outputs, row k A + a = head k, action a
         al_alpha, al_persistent = check_advantage_learning(args)
         self.noisy_nets, self.noisy_sigma = check_noisy(args)
+        random_shift = check_random_shift(args)
         self.bootstrap_heads, self.bootstrap_mask_probability = check_bootstrap(args, num_actions)
         # quantile-regression DQN: N quantiles per action are a library net with N x num_actions outputs, row j A + a = quantile j, action a
         self.quantiles = check_quantiles(args, num_actions)
@@ -290,6 +315,10 @@ class DeepQNetwork:
         self.noisy_seed = int(getattr(args, "random_seed", 0) or 0) & 0xFFFFFFFFFFFFFFFF
         if self.noisy_nets:                                    # (off: the library is not told anything)
             _lib.check(self._lib.sdqn_net_set_noisy(h, 1, self.noisy_sigma, self.noisy_seed))
+        # random-shift augmentation: the train steps that sample from a replay memory read shifted states
+        self.random_shift, self.random_shift_seed = 0, int(getattr(args, "random_seed", 0) or 0) & 0xFFFFFFFFFFFFFFFF
+        if random_shift:                                       # (off: the library is not told anything)
+            self.set_random_shift(random_shift)
         self._mt_buf = (C.c_uint32 * _lib.MT_WORDS)()
         self._act_out = C.c_int(); self._act_greedy = self._lib.sdqn_net_act_greedy
         self._env_r, self._env_t = C.c_int(), C.c_int(); self._act_step_env = self._lib.sdqn_net_act_step_env
@@ -406,6 +435,26 @@ class DeepQNetwork:
         _lib.check(self._lib.sdqn_bootstrap_act(_lib.ptr(q, C.c_float), self.bootstrap_heads, self.num_actions, int(self._boot_vote),
                                                 self.bootstrap_seed, 0, self._boot_episode, C.byref(a)))
         return a.value
+
+    def set_random_shift(self, P, seed=None):
+        """--random_shift: P in 1..8 shifts every state the ring-fed train steps sample (train_from_memory and its kin), 0 switches it off;
+        seed left None keeps its value (--random_seed).  The step counter of the draws returns to 0.  Refused with batch_norm."""
+        seed = self.random_shift_seed if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
+        _lib.check(self._lib.sdqn_net_set_random_shift(self._h, int(P), seed))
+        self.random_shift, self.random_shift_seed = int(P), seed
+
+    def random_shift_steps(self):
+        """--random_shift: shifted train steps enqueued since set_random_shift = the step counter of the next step's draws"""
+        t = C.c_int64()
+        _lib.check(self._lib.sdqn_net_get_random_shift(self._h, None, C.byref(t)))
+        return t.value
+
+    def last_shifts(self):
+        """--random_shift: int8 [B][2][2], the (dy, dx) of every sample's prestate [:, 0] and poststate [:, 1] as the last shifted step's
+        launch drew them.  Waits for the device; raises SdqnError before the first such step."""
+        out = np.empty((self.batch_size, 2, 2), np.int8)
+        _lib.check(self._lib.sdqn_net_last_shifts(self._h, _lib.ptr(out, C.c_int8)))
+        return out
 
     def set_target_tau(self, tau):
         """--target_tau: tau in (0, 1] makes every train step of this net end with one soft target update inside the library; 0: off."""
@@ -814,9 +863,9 @@ class DeepQNetwork:
     def _keep_pending_minibatch(self, mem):
         """A getMinibatch() whose states nobody has looked at yet lives ONLY in the device minibatch.  The generic path (float64, other
         screen geometries) gathers a fused step's states into that very buffer: fetch the pending one to the host first, so that a
-        later net.train(mb) / np.asarray(mb[0]) still sees its own states (the tuned 84x84x4 path gathers inside conv1 and never
-        touches the buffer)."""
-        if getattr(mem, "_mb_pending", False) and self.step_structure()[0] == "generic":
+        later net.train(mb) / np.asarray(mb[0]) still sees its own states.  The tuned 84x84x4 path gathers inside conv1 and never
+        touches the buffer — except with --random_shift > 0, whose launch writes every step's shifted states there."""
+        if getattr(mem, "_mb_pending", False) and (self.random_shift > 0 or self.step_structure()[0] == "generic"):
             mem._materialize()
 
     def train_indexes(self, mem, indexes, want_cost=False):

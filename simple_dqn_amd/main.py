@@ -52,6 +52,7 @@ _OPTIONS = {
         ("--dueling", _flag, False, dict(help="Dueling architecture (Wang et al. 2016): a value stream over one half of fc4's units and an advantage stream over the other, Q = V + Adv - mean(Adv); the network gets actions + 1 <= 18 outputs.")),
         ("--noisy_nets", _flag, False, dict(help="Noisy networks (Fortunato et al. 2018): factorised Gaussian noise on the two fully connected layers, W = mu + sigma * noise with learned sigma; one noise sample per net per train step, collecting acts under the last step's noise, testing on mu alone. Use with --exploration_rate_start 0 --exploration_rate_end 0.")),
         ("--noisy_sigma", float, 0.5, dict(help="Noisy networks: sigma starts at this value / sqrt(fan_in).")),
+        ("--random_shift", int, 0, dict(help="Random-shift augmentation (DrQ, Kostrikov et al. 2020): every sampled state is replicate-padded by this many pixels (0..8) and cropped back at a random offset, prestate and poststate independently (0: off).")),
         ("--quantiles", int, 1, dict(help="Quantile-regression DQN: this many quantile estimates per action (quantiles x actions <= 18), trained with the quantile Huber loss at threshold --clip_error; acting takes the mean over the quantiles (1: off).")),
         ("--bootstrap_heads", int, 1, dict(help="Bootstrapped DQN: this many Q-heads over one shared torso (heads x actions <= 18); acting follows one head per episode while training, the heads' majority vote while testing (1: off).")),
         ("--bootstrap_mask_probability", float, 1.0, dict(help="Bootstrapped DQN: probability that a Q-head trains on a transition, in (0, 1]; the mask is a fixed function of the replay slot.")),
@@ -215,8 +216,15 @@ def check_noisy(args):
     return check(args)
 
 
+def check_random_shift(args):
+    """--random_shift: its range and what it cannot be combined with, refused before anything touches the device"""
+    from .deepqnetwork import check_random_shift as check
+    return check(args)
+
+
 def run(args):
     train_envs = check_train_envs(args)
+    check_random_shift(args)
     check_noisy(args)
     check_dueling(args)
     check_bootstrap(args)

@@ -148,6 +148,15 @@ class ReplayMemory:
             self._mb_pending = False
             self._mb_dirty = False              # host and device copies of the minibatch are identical from here on
 
+    def device_minibatch(self):
+        """Copies (prestates, poststates) of the device minibatch as it stands: what the last gather, or the last --random_shift train
+        step, left there.  Waits for the device.  The fetch goes through the host minibatch buffers, which the arrays of an
+        earlier getMinibatch() alias: copy those first if they are still needed."""
+        _lib.check(self._lib.sdqn_replay_minibatch_to_host(self._h))
+        self._mb_pending = False
+        self._mb_dirty = False
+        return self._raw_mb["mb_pre"].copy(), self._raw_mb["mb_post"].copy()
+
     def _device_minibatch_gen(self):
         g = C.c_uint64()
         _lib.check(self._lib.sdqn_replay_minibatch_gen(self._h, C.byref(g), None))

@@ -361,6 +361,23 @@ int sdqn_net_get_munchausen(sdqn_net_t h, int* on, double* alpha, double* tau, d
  * with option "double_dqn", sdqn_net_set_munchausen, sdqn_net_set_bootstrap K > 1 and batch_norm (either order). */
 int sdqn_net_set_advantage_learning(sdqn_net_t h, double alpha, int persistent);
 int sdqn_net_get_advantage_learning(sdqn_net_t h, double* alpha, int* persistent);     /* any pointer may be NULL */
+/* Conservative Q-learning, --cql_alpha alpha (Kumar, Zhou, Tucker and Levine 2020, CQL(H) in its discrete form; no reference
+ * counterpart).  With q = Q(theta, s) the online net's row of the prestate, a the taken action, y the standard target and w the importance
+ * weight of a prioritized memory (else 1), a train step's loss per sample is w (0.5 delta^2 + alpha (lse(q) - q[a])):
+ *   lse = max q + log sum_k exp(q[k] - max q),   pi[k] = exp(q[k] - lse)                  (double from the stored row, sum in action order)
+ *   dq[k] = w (T)(alpha (pi[k] - 1[k == a])) + 1[k == a] w clip(delta),   cost term = w 0.5 delta^2 + w (T)(alpha (lse - q[a]))
+ * in the network's number type T (option "n_step": R, the done flag and discount^n inside y).  delta, the error clip, the new priority (of
+ * the unclipped delta) and sdqn_net_last_q's maxpostq are the standard step's; every fc5 row carries gradient.  The regulariser reads only
+ * values the step already holds: no forward of its own and no launch more than the standard step, in every regime.  alpha >= 0, finite;
+ * alpha = 0 (default) is off: no launch, no argument changes.  Every datatype, geometry, optimizer and replay memory; usable online and
+ * offline; switchable between steps.  SDQN_ERR_ARG for a negative, NaN or infinite alpha, and for alpha > 0 together with option
+ * "double_dqn", sdqn_net_set_munchausen, sdqn_net_set_advantage_learning, sdqn_net_set_bootstrap K > 1, sdqn_net_set_quantiles N > 1,
+ * sdqn_net_set_dueling, sdqn_net_set_noisy and batch_norm (either order). */
+int sdqn_net_set_cql(sdqn_net_t h, double alpha);
+int sdqn_net_get_cql(sdqn_net_t h, double* alpha);      /* the pointer may be NULL */
+/* the rule on one sample, host side (no device), from its stored row q_row [A] and its target y: clip_error 0 = no clip, weight 1 = no
+ * prioritized replay.  dq_out [A] and *cost_out receive what the train step's head writes for that sample */
+int sdqn_cql_loss(int A, double alpha, double clip_error, const float* q_row, int action, double y, double weight, float* dq_out, float* cost_out);
 /* Bootstrapped DQN, --bootstrap_heads K (Osband, Blundell, Pritzel and Van Roy 2016; no reference counterpart).  The network is
  * created with num_actions = K x A outputs (<= 18); output row k A + a is Q-head k, action a, and actions in transitions are < A.  A train step
  * gives every Q-head its own target y_k = r_c + (terminal ? 0 : discount max_a Q_k(theta-, s')[a]) and sets

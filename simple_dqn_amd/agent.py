@@ -38,8 +38,10 @@ def priority_beta(beta0, beta_steps, train_step):
 
 
 class Agent:
-    def __init__(self, environment, replay_memory, deep_q_network, args, fused=True):
+    def __init__(self, environment, replay_memory, deep_q_network, args, fused=True, offline_chunk=64):
         self.env, self.mem, self.net = environment, replay_memory, deep_q_network
+        # --offline_replay: train_offline hands the library at most this many learns per call
+        self.offline_chunk = max(1, int(offline_chunk))
         # acting state resident on the device when the network can read it there
         on_device = hasattr(deep_q_network, "predict_state")
         self.buf = DeviceStateBuffer(args) if on_device else StateBuffer(args)
@@ -224,6 +226,41 @@ class Agent:
                     self._learn(epoch)
                 self._vec_due -= self.train_frequency
             self.total_train_steps += N
+
+    # ---- --offline_replay: training from a fixed memory -------------------------------------------------------
+    def _offline_refresh_due(self, t):
+        """the target net is refreshed before learn t (= total_train_steps): with --target_tau only the reference's very first copy"""
+        if not self.target_steps:
+            return False
+        return t == 0 if self.target_tau > 0 else t % self.target_steps == 0
+
+    def train_offline(self, train_steps, epoch=0):
+        """train_steps learns (each train_repeat gradient steps) from the memory as it stands: no environment step, no exploration.  Before
+        learn t = total_train_steps the target net is refreshed where _offline_refresh_due says so; total_train_steps += 1 after every learn.
+        Consecutive learns with no refresh between them go to the library as ONE call of k <= offline_chunk learns; a prioritized memory's
+        beta is set once per call, from total_train_steps at its start."""
+        if not self.mem.can_sample():
+            raise ValueError("offline training needs more than batch_size = %d transitions in the replay memory, it holds %d"
+                             % (self.mem.batch_size, self.mem.count))
+        left = int(train_steps)
+        while left > 0:
+            t = self.total_train_steps
+            if self._offline_refresh_due(t):
+                self.net.update_target_network()
+            k = 1
+            while k < min(left, self.offline_chunk) and not self._offline_refresh_due(t + k):
+                k += 1
+            if self._per:
+                self.mem.set_priority_beta(priority_beta(self._beta0, self._beta_steps, t))
+            if self.fused:
+                if hasattr(self.net, "set_epoch"):
+                    self.net.set_epoch(epoch)
+                self.net.train_from_memory(self.mem, k * self.train_repeat)
+            else:
+                for _ in range(k * self.train_repeat):
+                    self.net.train(self.mem.getMinibatch(), epoch)
+            self.total_train_steps += k
+            left -= k
 
     def test(self, test_steps, epoch=0):
         self._acting_mode(True)

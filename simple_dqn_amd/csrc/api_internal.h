@@ -139,6 +139,9 @@ struct sdqn_net_s {
   // --advantage_learning / --persistent_advantage (sdqn_net_set_advantage_learning): al_alpha > 0: the same forward in front
   // of every train step, and the step's forward ends with the advantage-learning head (HEAD_ADVANTAGE); 0: off, nothing changes
   double al_alpha = 0.0; bool al_persistent = false;
+  // --cql_alpha (sdqn_net_set_cql; cql.h): cql_alpha > 0: the step's forward ends with the conservative Q-learning head (HEAD_CQL),
+  // which adds alpha (logsumexp_k Q(theta, s)[k] - Q(theta, s)[a]) to the loss; no forward of its own, no launch more; 0: off, nothing changes
+  double cql_alpha = 0.0;
   // --bootstrap_heads (sdqn_net_set_bootstrap; bootstrap.h): the net's A outputs are boot_K Q-heads of A / boot_K actions.  boot_K > 1:
   // train steps end their forward with the bootstrap head (HEAD_BOOTSTRAP), the acting paths reduce a Q row to the game's actions.
   // boot_q: [B][A / boot_K] acting rows of the game loops (select launch), allocated on first use.  boot_vote / boot_episode: the single-

@@ -58,6 +58,9 @@ struct GenericNet {
   // refused (hipErrorInvalidValue) with double_dqn, munchausen and bootstrap heads, and they with it
   virtual hipError_t set_advantage_learning(bool on, double alpha, bool persistent) = 0;
   virtual bool advantage_learning_on() const = 0;
+  // --cql_alpha (cql.h): alpha > 0 arms the CQL branch of the TD head (no forward of its own); refused (hipErrorInvalidValue)
+  // with double_dqn, munchausen, advantage learning, bootstrap heads, quantiles and dueling, and they with it
+  virtual hipError_t set_cql(double alpha) = 0;
   // --prioritized_replay (sdqn_per.hip): w != nullptr makes the following train steps weight the taken action's row by w[n] and write the
   // new priority (|delta| + eps)^alpha into newp[n]; nullptr: the standard step
   virtual void set_per(const float* w, float* newp, double alpha, double eps) = 0;

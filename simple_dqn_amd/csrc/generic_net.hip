@@ -16,6 +16,7 @@
 #include "problems.h"          // MetaRec
 #include "launch.h"            // SDQN_LAUNCH: the soft target update has a profile row
 #include "sdqn_clip.h"         // --clip_grad_norm: the two clip launches, float / double
+#include "cql.h"               // --cql_alpha: the CQL branch of the TD head
 #include <vector>
 #include <algorithm>
 #include <math.h>
@@ -174,7 +175,7 @@ __global__ void head_kernel(const T* __restrict__ q_on, const T* __restrict__ q_
                             const T* __restrict__ q_sel, const float* __restrict__ per_w, float* __restrict__ per_p, double per_alpha, double per_eps,
                             int nstep, double gamma_n, const T* __restrict__ q_mu, double mu_alpha, double mu_tau, double mu_clip, const BootArgs boot,
                             double al_alpha, int al_persistent, const QuantArgs quant, T* __restrict__ q_targets, const DuelArgs duel,
-                            T* __restrict__ duel_step) {
+                            T* __restrict__ duel_step, double cql_alpha) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
   if (duel.on) {                                                              // --dueling: dueling.h's rule on this sample's two rows
@@ -258,6 +259,11 @@ __global__ void head_kernel(const T* __restrict__ q_on, const T* __restrict__ q_
   const int at = act[n];
   T d = (T)0;
   const T w = per_w ? (T)per_w[n] : (T)1;                                     // --prioritized_replay: importance weight of the sample
+  if (cql_alpha > 0.0) {                                                      // --cql_alpha: cql.h's rule on this sample's online row and the target y
+    cost_terms[n] = cql_sample<T>(q_on + (int64_t)n * A, A, at, y, cql_alpha, clip, w, dq + (int64_t)n * A, &d);
+    if (per_w) per_p[n] = (float)pow(fabs((double)d) + per_eps, per_alpha);   // unclipped |delta|
+    return;
+  }
   for (int a = 0; a < A; ++a) {
     T e = (a == at) ? q_on[(int64_t)n * A + a] - target : (T)0;               // deltas = preq - targets: 0 off the taken action
     if (a == at) d = e;
@@ -447,7 +453,7 @@ class GenericNetT : public GenericNet {
     hipLaunchKernelGGL(head_kernel<T>, dim3((B + 63) / 64), dim3(64), 0, st, (const T*)q, (const T*)(q + (int64_t)B * A), actions, rew, term,
                        dq, cost_terms, maxq, B, A, cfg.discount_rate, cfg.min_reward, cfg.max_reward, (T)cfg.clip_error, (const T*)(dd ? q_sel : nullptr),
                        per_w, per_p, per_alpha, per_eps, nstep, gamma_n, (const T*)((munchausen || advantage) ? q_mu : nullptr), mu_alpha, mu_tau, mu_clip, boot,
-                       advantage ? al_alpha : 0.0, al_persistent ? 1 : 0, quant, q_targets, duel, duel_step);
+                       advantage ? al_alpha : 0.0, al_persistent ? 1 : 0, quant, q_targets, duel, duel_step, cql_alpha);
     hipLaunchKernelGGL(cost_kernel<T>, dim3(1), dim3(64), 0, st, (const T*)cost_terms, cost, cost_sum, B);
     // ---- bprop (A8) :162
     GCHK(gemm(ga(dq, 1, A, act[3], 512, 1, g + off[4], A, 512, B)));                                   // gW5 = dq^T @ a4
@@ -579,7 +585,7 @@ class GenericNetT : public GenericNet {
   }
   DuelArgs duel = {0, 0, nullptr}; T* duel_step = nullptr;            // duel_step: [2][B] the last step's y and delta in T (duel.step is the tuned path's float buffer)
   hipError_t set_dueling(bool on) override {
-    if (on && (double_dqn || munchausen || advantage || boot.K > 1 || quant.N > 1 || A < 2)) return hipErrorInvalidValue;
+    if (on && (double_dqn || munchausen || advantage || cql_alpha > 0.0 || boot.K > 1 || quant.N > 1 || A < 2)) return hipErrorInvalidValue;
     if (on && !duel_step) GCHK(dalloc(&duel_step, (int64_t)2 * B));
     duel.on = on ? 1 : 0; duel.A = A - 1;
     return hipSuccess;
@@ -607,25 +613,31 @@ class GenericNetT : public GenericNet {
   int nstep = 1; double gamma_n = 0.0;
   bool double_dqn_on() const override { return double_dqn; }
   hipError_t set_double_dqn(bool on) override {
-    if (on && (munchausen || advantage)) return hipErrorInvalidValue;
+    if (on && (munchausen || advantage || cql_alpha > 0.0)) return hipErrorInvalidValue;
     if (on && !q_sel) GCHK(dalloc(&q_sel, (int64_t)B * A));
     double_dqn = on;
     return hipSuccess;
   }
   hipError_t set_munchausen(bool on, double alpha, double tau, double clip) override {
-    if (on && (double_dqn || advantage)) return hipErrorInvalidValue;
+    if (on && (double_dqn || advantage || cql_alpha > 0.0)) return hipErrorInvalidValue;
     if (on && !q_mu) GCHK(dalloc(&q_mu, (int64_t)B * A));
     munchausen = on; mu_alpha = alpha; mu_tau = tau; mu_clip = clip;
     return hipSuccess;
   }
   bool munchausen_on() const override { return munchausen; }
   hipError_t set_advantage_learning(bool on, double alpha, bool persistent) override {
-    if (on && (double_dqn || munchausen || boot.K > 1 || quant.N > 1 || duel.on || !(alpha > 0.0 && alpha < 1.0))) return hipErrorInvalidValue;
+    if (on && (double_dqn || munchausen || cql_alpha > 0.0 || boot.K > 1 || quant.N > 1 || duel.on || !(alpha > 0.0 && alpha < 1.0))) return hipErrorInvalidValue;
     if (on && !q_mu) GCHK(dalloc(&q_mu, (int64_t)B * A));
     advantage = on; al_alpha = on ? alpha : 0.0; al_persistent = on && persistent;
     return hipSuccess;
   }
   bool advantage_learning_on() const override { return advantage; }
+  double cql_alpha = 0.0;                                       // --cql_alpha: > 0 arms the CQL branch of the TD head; no forward of its own
+  hipError_t set_cql(double alpha) override {
+    if (alpha > 0.0 && (double_dqn || munchausen || advantage || boot.K > 1 || quant.N > 1 || duel.on || !(alpha < INFINITY))) return hipErrorInvalidValue;
+    cql_alpha = alpha > 0.0 ? alpha : 0.0;
+    return hipSuccess;
+  }
   hipError_t update_target() override {
     if (theta_t != theta) return hipMemcpyAsync(theta_t, theta, (size_t)NP * sizeof(T), hipMemcpyDeviceToDevice, st);
     return hipSuccess;

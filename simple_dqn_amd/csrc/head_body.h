@@ -1,6 +1,6 @@
 // head_body.h — what the option heads' kernels share, as device functions (HIP only): munchausen_head_kernel (sdqn_munchausen.hip),
-// bootstrap_head_kernel (sdqn_bootstrap.hip), advantage_head_kernel (sdqn_advantage.hip), quantile_head_kernel (sdqn_quantile.hip) and
-// dueling_head_kernel (sdqn_dueling.hip) are these pieces around the few lines of their own rule.  The statements and the floating-point operation order are
+// bootstrap_head_kernel (sdqn_bootstrap.hip), advantage_head_kernel (sdqn_advantage.hip), quantile_head_kernel (sdqn_quantile.hip),
+// dueling_head_kernel (sdqn_dueling.hip) and cql_head_kernel (sdqn_cql.hip) are these pieces around the few lines of their own rule.  The statements and the floating-point operation order are
 // head_kernel's (sdqn_kernels.hip) for a train step without batch_norm, nz = 2: one 512-thread workgroup per sample; the fc4 slab reduce +
 // ReLU and the fc5 of slots 0 (online net, prestates) and 1 (target net, poststates) are the same loads, the same prod[][] transpose and the
 // same single butterfly per row, so Q(pre), Q(post), a4 and d4 are what the standard head of a net with a.A outputs leaves.  head_kernel

@@ -31,7 +31,9 @@ struct HeadArgs {
   // in the 24 bytes a retired option's fields left: every later field keeps its offset (see StepArgs::reserved_)
   // --advantage_learning, read when train == HEAD_ADVANTAGE: the gap scale alpha in (0, 1) and the persistent (PAL) switch.  The two
   // options are refused together (sdqn_net_set_advantage_learning), so they share mu_alpha's and mu_tau's bytes: no field moves
-  union { double mu_alpha; double al_alpha; };
+  // --cql_alpha, read when train == HEAD_CQL: the regulariser's scale alpha > 0.  Refused together with both (sdqn_net_set_cql): the
+  // same bytes once more
+  union { double mu_alpha; double al_alpha; double cql_alpha; };
   union { double mu_tau; int al_persistent; };
   double mu_clip;
   // --prioritized_replay (sdqn_per.hip): per_w != nullptr selects the PER head — dq = w clip(delta), cost term 0.5 w delta^2, and
@@ -95,6 +97,7 @@ struct UpdateArgs {
 // The kernel-argument layouts are part of the tuned kernels (StepArgs::reserved_, problems.h): frozen where a retired field became reserved bytes
 static_assert(sizeof(HeadArgs) == 160 && offsetof(HeadArgs, train) == 84 && offsetof(HeadArgs, mu_alpha) == 88 && offsetof(HeadArgs, mu_clip) == 104 &&
               offsetof(HeadArgs, al_alpha) == offsetof(HeadArgs, mu_alpha) && offsetof(HeadArgs, al_persistent) == offsetof(HeadArgs, mu_tau) &&
+              offsetof(HeadArgs, cql_alpha) == offsetof(HeadArgs, mu_alpha) &&
               offsetof(HeadArgs, per_w) == 112 && offsetof(HeadArgs, per_eps) == 136 &&
               offsetof(HeadArgs, nstep) == 144 && offsetof(HeadArgs, gamma_n) == 152, "HeadArgs layout");
 static_assert(sizeof(PrepArgs) == 344 && offsetof(PrepArgs, idx_in_valid) == 52 && offsetof(PrepArgs, idx_in) == 56 && offsetof(PrepArgs, ns) == 312, "PrepArgs layout");
@@ -178,6 +181,7 @@ hipError_t launch_quantile_mean(const void* q, void* out, bool f64, int M, int N
 hipError_t launch_head_munchausen(const StepArgs& a, const HeadArgs& h, hipStream_t s);     // sdqn_munchausen.hip: what launch_head runs for HEAD_MUNCHAUSEN
 hipError_t launch_head_bootstrap(const StepArgs& a, const HeadArgs& h, const BootArgs& b, hipStream_t s);     // sdqn_bootstrap.hip: what launch_head runs for HEAD_BOOTSTRAP
 hipError_t launch_head_advantage(const StepArgs& a, const HeadArgs& h, hipStream_t s);      // sdqn_advantage.hip: what launch_head runs for HEAD_ADVANTAGE
+hipError_t launch_head_cql(const StepArgs& a, const HeadArgs& h, hipStream_t s);            // sdqn_cql.hip: what launch_head runs for HEAD_CQL
 // sdqn_bootstrap.hip: [N][K A] Q rows -> [N][A] acting rows (float or double); vote = 0: the slice of Q-head k(e, episodes_e), the int64 episode
 // counter of copy e at recs + e stride + offset; vote = 1: the vote counts
 hipError_t launch_bootstrap_select(const void* q, void* out, bool f64, int N, int K, int A, int vote, uint64_t head_seed,

@@ -35,9 +35,10 @@ enum HeadMode {
   HEAD_ADVANTAGE,       // train step with advantage-learning targets (--advantage_learning; advantage_head_kernel, sdqn_advantage.hip)
   HEAD_QUANTILE,        // train step of an N-quantile net (--quantiles N > 1; quantile_head_kernel, sdqn_quantile.hip, its QuantArgs beside HeadArgs;
                         // HeadArgs::clip_error is the Huber threshold kappa there)
-  HEAD_DUELING          // train step of a dueling net (--dueling; dueling_head_kernel, sdqn_dueling.hip, its DuelArgs beside HeadArgs)
+  HEAD_DUELING,         // train step of a dueling net (--dueling; dueling_head_kernel, sdqn_dueling.hip, its DuelArgs beside HeadArgs)
+  HEAD_CQL              // train step with the conservative Q-learning regulariser (--cql_alpha; cql_head_kernel, sdqn_cql.hip)
 };
-static_assert(HEAD_TRAIN == 1 && HEAD_DOUBLE == 2 && HEAD_MUNCHAUSEN == 3 && HEAD_BOOTSTRAP == 4 && HEAD_ADVANTAGE == 5 && HEAD_QUANTILE == 6 && HEAD_DUELING == 7, "head modes are public numbers");
+static_assert(HEAD_TRAIN == 1 && HEAD_DOUBLE == 2 && HEAD_MUNCHAUSEN == 3 && HEAD_BOOTSTRAP == 4 && HEAD_ADVANTAGE == 5 && HEAD_QUANTILE == 6 && HEAD_DUELING == 7 && HEAD_CQL == 8, "head modes are public numbers");
 static_assert(K_BN == 19 && K_WGRADS == 24 && K_ACT == 25 && K_COLLECT == 26 && K_TARGET == 27 && K_COUNT == 28, "kernel ids are public numbers");
 
 // LaunchTune::variant — the launch variants the step's orchestration asks for (sdqn_api_step.hip decides, resolve_route tests); bit 0 is unused

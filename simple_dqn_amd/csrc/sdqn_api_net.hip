@@ -1,5 +1,6 @@
 // sdqn_api_net.hip — DeepQNetwork handles: create / destroy, weights, profiler, options, small read-backs (deepqnetwork.py:16-105,188-192)
 #include "api_internal.h"
+#include "cql.h"
 
 // One step structure per (B regime, datatype, batch-norm, data-parallel form): DESIGN.md 12.  The step structures that were built, tested
 // bit-identical and measured SLOWER in rounds 1-4 (hoist, f4w_early, fuse_upd, head_f4d, two_streams, fwd_rb, bwd_order, rb:<id>, bt_x,
@@ -570,6 +571,7 @@ extern "C" int sdqn_net_set_munchausen(sdqn_net_t h, int on, double alpha, doubl
     ARGCHK(!h->dueling, "munchausen cannot be combined with dueling");
     ARGCHK(!h->noisy, "munchausen cannot be combined with noisy_nets");
     ARGCHK(!(h->al_alpha > 0.0), "munchausen cannot be combined with advantage_learning: both targets want q slot 2 for a head of their own");
+    ARGCHK(!(h->cql_alpha > 0.0), "munchausen cannot be combined with cql_alpha");
     ARGCHK(h->cfg.batch_norm == 0.0, "munchausen cannot be combined with batch_norm: inference-mode statistics for its third forward are not defined");
     ARGCHK(h->gen || !h->double_dqn, "munchausen cannot be combined with double_dqn: the Munchausen target has no argmax for the online net to choose");
   }
@@ -601,6 +603,7 @@ extern "C" int sdqn_net_set_advantage_learning(sdqn_net_t h, double alpha, int p
     ARGCHK(h->quant_N == 1, "advantage_learning cannot be combined with quantiles %d", h->quant_N);
     ARGCHK(!h->dueling, "advantage_learning cannot be combined with dueling");
     ARGCHK(!h->noisy, "advantage_learning cannot be combined with noisy_nets");
+    ARGCHK(!(h->cql_alpha > 0.0), "advantage_learning cannot be combined with cql_alpha");
     ARGCHK(h->cfg.batch_norm == 0.0, "advantage_learning cannot be combined with batch_norm: inference-mode statistics for its third forward are not defined");
     ARGCHK(!(persistent && h->n_step > 1), "persistent_advantage cannot be combined with n_step %d: it repeats the action in the NEXT state", h->n_step);
   }
@@ -612,6 +615,41 @@ extern "C" int sdqn_net_set_advantage_learning(sdqn_net_t h, double alpha, int p
 extern "C" int sdqn_net_get_advantage_learning(sdqn_net_t h, double* alpha, int* persistent) {
   ARGCHK(h, "NULL handle");
   if (alpha) *alpha = h->al_alpha; if (persistent) *persistent = h->al_persistent ? 1 : 0;
+  return SDQN_OK;
+}
+
+// ---- --cql_alpha: the conservative Q-learning regulariser (sdqn.h; cql.h) ---------------------------------------------------
+extern "C" int sdqn_net_set_cql(sdqn_net_t h, double alpha) {
+  ARGCHK(h, "NULL handle");
+  ARGCHK(alpha >= 0.0 && alpha < INFINITY, "cql_alpha %g: must be a finite value >= 0", alpha);          // (a NaN fails the comparison)
+  if (alpha > 0.0) {
+    const bool dd = h->gen ? h->gen->double_dqn_on() : h->double_dqn, mu = h->gen ? h->gen->munchausen_on() : h->munchausen;
+    ARGCHK(!dd, "cql_alpha cannot be combined with double_dqn: the shared head body carries no third slot");
+    ARGCHK(!mu, "cql_alpha cannot be combined with munchausen");
+    ARGCHK(!(h->al_alpha > 0.0), "cql_alpha cannot be combined with advantage_learning");
+    ARGCHK(h->boot_K == 1, "cql_alpha cannot be combined with bootstrap_heads %d", h->boot_K);
+    ARGCHK(h->quant_N == 1, "cql_alpha cannot be combined with quantiles %d", h->quant_N);
+    ARGCHK(!h->dueling, "cql_alpha cannot be combined with dueling");
+    ARGCHK(!h->noisy, "cql_alpha cannot be combined with noisy_nets");
+    ARGCHK(h->cfg.batch_norm == 0.0, "cql_alpha cannot be combined with batch_norm");
+  }
+  if (h->gen) GENCHK(h->gen->set_cql(alpha));
+  h->cql_alpha = alpha;
+  return SDQN_OK;
+}
+extern "C" int sdqn_net_get_cql(sdqn_net_t h, double* alpha) {
+  ARGCHK(h, "NULL handle");
+  if (alpha) *alpha = h->cql_alpha;
+  return SDQN_OK;
+}
+// the host restatement of one sample of the CQL head (no device): cql.h's cql_sample on a float row
+extern "C" int sdqn_cql_loss(int A, double alpha, double clip_error, const float* q_row, int action, double y, double weight, float* dq_out, float* cost_out) {
+  ARGCHK(q_row && dq_out && cost_out, "NULL argument");
+  ARGCHK(A >= 1 && A <= MAX_ACTIONS, "%d actions outside [1, %d]", A, MAX_ACTIONS);
+  ARGCHK(action >= 0 && action < A, "action %d out of range [0, %d)", action, A);
+  ARGCHK(alpha >= 0.0 && alpha < INFINITY, "cql_alpha %g: must be a finite value >= 0", alpha);
+  ARGCHK(clip_error >= 0.0, "clip_error %g: must be >= 0", clip_error);
+  *cost_out = cql_sample<float>(q_row, A, action, y, alpha, (float)clip_error, (float)weight, dq_out, nullptr);
   return SDQN_OK;
 }
 
@@ -632,6 +670,7 @@ extern "C" int sdqn_net_set_bootstrap(sdqn_net_t h, int K, double P, uint64_t se
     ARGCHK(!dd, "bootstrap_heads %d cannot be combined with double_dqn", K);
     ARGCHK(!mu, "bootstrap_heads %d cannot be combined with munchausen", K);
     ARGCHK(!(h->al_alpha > 0.0), "bootstrap_heads %d cannot be combined with advantage_learning", K);
+    ARGCHK(!(h->cql_alpha > 0.0), "bootstrap_heads %d cannot be combined with cql_alpha", K);
     ARGCHK(h->quant_N == 1, "bootstrap_heads %d cannot be combined with quantiles %d", K, h->quant_N);
     ARGCHK(!h->dueling, "bootstrap_heads %d cannot be combined with dueling", K);
     ARGCHK(!h->noisy, "bootstrap_heads %d cannot be combined with noisy_nets", K);
@@ -684,6 +723,7 @@ extern "C" int sdqn_net_set_quantiles(sdqn_net_t h, int N) {
     ARGCHK(!dd, "quantiles %d cannot be combined with double_dqn", N);
     ARGCHK(!mu, "quantiles %d cannot be combined with munchausen", N);
     ARGCHK(!(h->al_alpha > 0.0), "quantiles %d cannot be combined with advantage_learning", N);
+    ARGCHK(!(h->cql_alpha > 0.0), "quantiles %d cannot be combined with cql_alpha", N);
     ARGCHK(h->boot_K == 1, "quantiles %d cannot be combined with bootstrap_heads %d", N, h->boot_K);
     ARGCHK(!h->dueling, "quantiles %d cannot be combined with dueling", N);
     ARGCHK(!h->noisy, "quantiles %d cannot be combined with noisy_nets", N);
@@ -741,6 +781,7 @@ extern "C" int sdqn_net_set_dueling(sdqn_net_t h, int on) {
     ARGCHK(!dd, "dueling cannot be combined with double_dqn: the shared head body carries no third slot");
     ARGCHK(!mu, "dueling cannot be combined with munchausen");
     ARGCHK(!(h->al_alpha > 0.0), "dueling cannot be combined with advantage_learning");
+    ARGCHK(!(h->cql_alpha > 0.0), "dueling cannot be combined with cql_alpha");
     ARGCHK(h->boot_K == 1, "dueling cannot be combined with bootstrap_heads %d", h->boot_K);
     ARGCHK(h->quant_N == 1, "dueling cannot be combined with quantiles %d", h->quant_N);
     ARGCHK(!h->noisy, "dueling cannot be combined with noisy_nets");
@@ -816,6 +857,7 @@ extern "C" int sdqn_net_set_noisy(sdqn_net_t h, int on, double sigma0, uint64_t 
   ARGCHK(!(h->target_tau > 0.0), "noisy_nets cannot be combined with target_tau: the blend would have to cover sigma");
   ARGCHK(!h->munchausen, "noisy_nets cannot be combined with munchausen");
   ARGCHK(!(h->al_alpha > 0.0), "noisy_nets cannot be combined with advantage_learning");
+  ARGCHK(!(h->cql_alpha > 0.0), "noisy_nets cannot be combined with cql_alpha");
   ARGCHK(h->boot_K == 1, "noisy_nets cannot be combined with bootstrap_heads %d", h->boot_K);
   ARGCHK(h->quant_N == 1, "noisy_nets cannot be combined with quantiles %d", h->quant_N);
   ARGCHK(!h->dueling, "noisy_nets cannot be combined with dueling");
@@ -904,6 +946,7 @@ extern "C" int sdqn_net_set_option(sdqn_net_t h, const char* name, int value) {
   if (!strcmp(name, "double_dqn") && value) ARGCHK(h->quant_N == 1, "double_dqn cannot be combined with quantiles %d", h->quant_N);
   if (!strcmp(name, "double_dqn") && value) ARGCHK(!h->dueling, "double_dqn cannot be combined with dueling: the shared head body carries no third slot");
   if (!strcmp(name, "double_dqn") && value) ARGCHK(!(h->al_alpha > 0.0), "double_dqn cannot be combined with advantage_learning: q slot 2 is taken by its third forward");
+  if (!strcmp(name, "double_dqn") && value) ARGCHK(!(h->cql_alpha > 0.0), "double_dqn cannot be combined with cql_alpha: the shared head body carries no third slot");
   if (!strcmp(name, "n_step")) {                          // n-step returns: sdqn.h
     ARGCHK(value >= 1 && value <= SDQN_MAX_N_STEP, "n_step %d out of range [1, %d]", value, SDQN_MAX_N_STEP);
     ARGCHK(!(value > 1 && h->al_persistent), "n_step %d cannot be combined with persistent_advantage: it repeats the action in the NEXT state", value);

@@ -218,7 +218,10 @@ StepPlan step_plan(const sdqn_net_s* h) {
   // --bootstrap_heads K > 1 (refused together with double_dqn / munchausen / batch_norm: sdqn_net_set_bootstrap): its own head; K = 1: nothing
   // --quantiles N > 1 (refused together with all of them: sdqn_net_set_quantiles): likewise; N = 1: nothing
   // --dueling (refused together with all of them and with double_dqn: sdqn_net_set_dueling): likewise
-  p.head_train = h->dueling ? HEAD_DUELING : h->quant_N > 1 ? HEAD_QUANTILE : h->boot_K > 1 ? HEAD_BOOTSTRAP : h->munchausen ? HEAD_MUNCHAUSEN : al ? HEAD_ADVANTAGE : ddqn_active(h) ? HEAD_DOUBLE : 0;
+  // --cql_alpha > 0 (refused together with all of them and with double_dqn: sdqn_net_set_cql): likewise, and nothing else — no forward in
+  // front, two slots, the standard step's launches; alpha = 0 is off: nothing below changes
+  const bool cql = h->cql_alpha > 0.0;
+  p.head_train = h->dueling ? HEAD_DUELING : h->quant_N > 1 ? HEAD_QUANTILE : h->boot_K > 1 ? HEAD_BOOTSTRAP : h->munchausen ? HEAD_MUNCHAUSEN : al ? HEAD_ADVANTAGE : cql ? HEAD_CQL : ddqn_active(h) ? HEAD_DOUBLE : 0;
   p.nz = (!h->munchausen && !al && ddqn_active(h) && !h->bn) ? 3 : 2;
   LaunchPlan* l = p.launch;
   plan_forward(h, l);
@@ -379,6 +382,7 @@ int run_train(sdqn_net_s* h, const StepArgs& a0, const HeadArgs& hd0, const Prep
   if (plan.head_train) hd.train = plan.head_train;
   if (plan.head_train == HEAD_MUNCHAUSEN) { hd.mu_alpha = h->mu_alpha; hd.mu_tau = h->mu_tau; hd.mu_clip = h->mu_clip; }
   if (plan.head_train == HEAD_ADVANTAGE) { hd.al_alpha = h->al_alpha; hd.al_persistent = h->al_persistent ? 1 : 0; }
+  if (plan.head_train == HEAD_CQL) hd.cql_alpha = h->cql_alpha;
   if (plan.extra_fwd) { int rc0 = run_extra_forward(h, a, plan.extra_fwd == 1, plan.extra_fwd == 2, plan.launch); if (rc0) return rc0; }
   StepArgs af = a; af.nz = plan.nz;        // the forward's arguments (the backward keeps a: its launches know two slots only)
   int rc = forward(h, af, hd, plan.launch); if (rc) return rc;

@@ -344,6 +344,7 @@ hipError_t launch_head(const StepArgs& a, const HeadArgs& h, hipStream_t s, bool
   if (h.train == HEAD_MUNCHAUSEN) return launch_head_munchausen(a, h, s);        // --munchausen: a kernel of its own (sdqn_munchausen.hip)
   if (h.train == HEAD_BOOTSTRAP) return boot ? launch_head_bootstrap(a, h, *boot, s) : hipErrorInvalidValue;   // --bootstrap_heads: likewise (sdqn_bootstrap.hip)
   if (h.train == HEAD_ADVANTAGE) return launch_head_advantage(a, h, s);          // --advantage_learning: likewise (sdqn_advantage.hip)
+  if (h.train == HEAD_CQL) return launch_head_cql(a, h, s);                      // --cql_alpha: likewise (sdqn_cql.hip)
   if (a.nz > 2 && (h.train != HEAD_DOUBLE || a.bn)) return hipErrorInvalidValue;   // (a third slot needs the Double DQN head's LDS)
   const int bucket = a.bn ? 3 : (a.A <= 4 ? 0 : (a.A <= 8 ? 1 : 2));
   const bool qsys = q_system_scope && !a.bn && !h.train;                         // acting path: Q-values straight into mapped host memory

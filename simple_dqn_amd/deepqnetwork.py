@@ -201,10 +201,44 @@ def check_advantage_learning(args):
     return alpha, pal
 
 
+def check_cql(args):
+    """--cql_alpha ALPHA: a finite value >= 0 (0: off), and ALPHA > 0 with none of --double_dqn, --munchausen,
+    --advantage_learning > 0, --bootstrap_heads > 1, --quantiles > 1, --dueling, --noisy_nets, --batch_norm.  Raises ValueError naming the
+    flag; touches no device.  Returns alpha."""
+    alpha = getattr(args, "cql_alpha", 0.0)
+    alpha = 0.0 if alpha is None else float(alpha)
+    if not 0.0 <= alpha < float("inf"):                       # (a NaN fails both comparisons)
+        raise ValueError("--cql_alpha %g: must be a finite value >= 0 (0: off)" % alpha)
+    if alpha == 0.0:
+        return alpha
+    follow = " (DESIGN.md §35 lists it as a follow-up)"
+    for flag in ("double_dqn", "munchausen", "dueling", "noisy_nets", "batch_norm"):
+        if getattr(args, flag, False):
+            raise ValueError("--cql_alpha cannot be combined with --%s%s" % (flag, follow))
+    if float(getattr(args, "advantage_learning", 0.0) or 0.0) > 0.0:
+        raise ValueError("--cql_alpha cannot be combined with --advantage_learning %g%s" % (float(args.advantage_learning), follow))
+    for flag in ("bootstrap_heads", "quantiles"):
+        v = getattr(args, flag, 1)
+        if (1 if v is None else int(v)) > 1:
+            raise ValueError("--cql_alpha cannot be combined with --%s %d%s" % (flag, int(v), follow))
+    return alpha
+
+
+def cql_loss(q_row, action, y, alpha, clip_error=1.0, weight=1.0):
+    """--cql_alpha: (dq row, cost term) of one sample from its stored float32 row q = Q(theta, s) and its target y, restated on the host
+    (csrc/cql.h; no device)"""
+    q = np.ascontiguousarray(q_row, dtype=np.float32).reshape(-1)
+    dq, cost = np.empty(q.size, np.float32), C.c_float()
+    _lib.check(_lib.load().sdqn_cql_loss(q.size, float(alpha), float(clip_error), _lib.ptr(q, C.c_float), int(action), float(y), float(weight),
+                                         _lib.ptr(dq, C.c_float), C.byref(cost)))
+    return dq, np.float32(cost.value)
+
+
 class DeepQNetwork:
     def __init__(self, num_actions, args):
         # Bootstrapped DQN (DESIGN.md §27): K Q-heads over one torso are a library net with K x num_actions outputs, row k A + a = head k, action a
         al_alpha, al_persistent = check_advantage_learning(args)
+        cql_alpha = check_cql(args)
         self.noisy_nets, self.noisy_sigma = check_noisy(args)
         random_shift = check_random_shift(args)
         self.bootstrap_heads, self.bootstrap_mask_probability = check_bootstrap(args, num_actions)
@@ -303,6 +337,10 @@ class DeepQNetwork:
         self.advantage_learning, self.persistent_advantage = 0.0, False
         if al_alpha > 0.0:                                     # (alpha = 0: the library is not told anything)
             self.set_advantage_learning(al_alpha, al_persistent)
+        # conservative Q-learning: alpha x (logsumexp_k Q(s, k) - Q(s, a_taken)) added to the loss, from the step's own Q-values
+        self.cql_alpha = 0.0
+        if cql_alpha > 0.0:                                    # (alpha = 0: the library is not told anything)
+            self.set_cql(cql_alpha)
         self.bootstrap_seed = int(getattr(args, "random_seed", 0) or 0) & 0xFFFFFFFFFFFFFFFF
         self._boot_vote, self._boot_episode = False, 0
         if self.bootstrap_heads > 1:                           # (K = 1: the library is not told anything)
@@ -405,6 +443,13 @@ class DeepQNetwork:
         persistent = (self.persistent_advantage if persistent is None else bool(persistent)) and alpha != 0.0
         _lib.check(self._lib.sdqn_net_set_advantage_learning(self._h, alpha, 1 if persistent else 0))
         self.advantage_learning, self.persistent_advantage = alpha, persistent
+
+    def set_cql(self, alpha):
+        """--cql_alpha: set the regulariser's scale between steps (a finite value >= 0; 0 switches the option off).  Refused with double_dqn,
+        munchausen, advantage_learning, bootstrap_heads > 1, quantiles > 1, dueling, noisy_nets and batch_norm."""
+        alpha = float(alpha)
+        _lib.check(self._lib.sdqn_net_set_cql(self._h, alpha))
+        self.cql_alpha = alpha
 
     # ---- --bootstrap_heads: the acting rule of the single-environment paths (the game loops carry theirs: evaluate votes, collect follows heads)
     def set_acting(self, test):

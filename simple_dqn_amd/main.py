@@ -34,6 +34,8 @@ _OPTIONS = {
         ("--priority_beta_steps", int, 1000000, dict(help="Training steps over which the importance-sampling exponent anneals from --priority_beta to 1.")),
         ("--priority_epsilon", float, 1e-6),
         ("--n_step", int, 1, dict(help="n-step returns (1..16): bootstrap from the state n steps later, rewards summed with the discount (1: one-step targets).")),
+        ("--save_replay", str, None, dict(help="Write the replay memory to this file when the run ends: a dataset for --offline_replay.")),
+        ("--offline_replay", str, None, dict(help="Offline training: load the replay memory from this file (written by --save_replay with the same --replay_size, screen size and --history_length), collect nothing, and count --train_steps in learns; the test phase plays the game as ever.")),
     ],
     "Deep Q-learning network": [
         ("--learning_rate", float, 0.00025), ("--discount_rate", float, 0.99), ("--batch_size", int, 32),
@@ -49,6 +51,7 @@ _OPTIONS = {
         ("--munchausen_clip", float, -1.0, dict(help="Munchausen DQN: lower clip of tau * ln pi(a|s), <= 0.")),
         ("--advantage_learning", float, 0.0, dict(help="Advantage learning (Bellemare et al. 2016): subtract this fraction, in [0, 1), of the target net's action gap max_a Q(s, a) - Q(s, a_taken) from the target (0: off; the paper uses 0.9).")),
         ("--persistent_advantage", _flag, False, dict(help="Persistent advantage learning: on non-terminal transitions take the larger of the advantage-learning target and the one with the poststate's gap of the same action (needs --advantage_learning > 0).")),
+        ("--cql_alpha", float, 0.0, dict(help="Conservative Q-learning (Kumar et al. 2020, CQL(H)): add this multiple of logsumexp_a Q(s, a) - Q(s, a_taken) to the loss, which holds down the values of actions the data never took (0: off; offline training commonly uses 1).")),
         ("--dueling", _flag, False, dict(help="Dueling architecture (Wang et al. 2016): a value stream over one half of fc4's units and an advantage stream over the other, Q = V + Adv - mean(Adv); the network gets actions + 1 <= 18 outputs.")),
         ("--noisy_nets", _flag, False, dict(help="Noisy networks (Fortunato et al. 2018): factorised Gaussian noise on the two fully connected layers, W = mu + sigma * noise with learned sigma; one noise sample per net per train step, collecting acts under the last step's noise, testing on mu alone. Use with --exploration_rate_start 0 --exploration_rate_end 0.")),
         ("--noisy_sigma", float, 0.5, dict(help="Noisy networks: sigma starts at this value / sqrt(fan_in).")),
@@ -192,6 +195,42 @@ def check_advantage_learning(args):
     return check(args)
 
 
+def check_cql(args):
+    """--cql_alpha: its range and what it cannot be combined with, refused before anything touches the device"""
+    from .deepqnetwork import check_cql as check
+    return check(args)
+
+
+def check_offline(args):
+    """--save_replay / --offline_replay: what they cannot be combined with, refused before anything touches the device.  Returns
+    (save_replay, offline_replay)."""
+    save, offline = getattr(args, "save_replay", None) or None, getattr(args, "offline_replay", None) or None
+    train_envs = int(getattr(args, "train_envs", 0) or 0)
+    if save and train_envs > 0:
+        raise ValueError("--save_replay cannot be combined with --train_envs %d: laned memories have no checkpoint" % train_envs)
+    if offline:
+        if train_envs > 0:
+            raise ValueError("--offline_replay cannot be combined with --train_envs %d: offline training collects nothing, and laned "
+                             "memories have no checkpoint" % train_envs)
+        if int(getattr(args, "play_games", 0) or 0):
+            raise ValueError("--offline_replay cannot be combined with --play_games %d: playing trains nothing" % int(args.play_games))
+        if save:
+            raise ValueError("--offline_replay cannot be combined with --save_replay: the memory would be written back as it was read")
+    return save, offline
+
+
+def check_offline_file(args, path):
+    """--offline_replay FILE against --replay_size, --screen_height / --screen_width and --history_length: a ValueError naming both values
+    where they differ.  Reads the file's header only.  Returns ReplayMemory.peek's dictionary."""
+    from .replay_memory import ReplayMemory
+    head = ReplayMemory.peek(path)
+    for key, flag, want in (("size", "--replay_size", args.replay_size), ("H", "--screen_height", args.screen_height),
+                            ("W", "--screen_width", args.screen_width), ("hist", "--history_length", args.history_length)):
+        if int(head[key]) != int(want):
+            raise ValueError("--offline_replay %s was written with %s %d, this run has %s %d" % (path, flag, head[key], flag, want))
+    return head
+
+
 def check_bootstrap(args, num_actions=None):
     """--bootstrap_heads: its ranges and what it cannot be combined with, refused before anything touches the device"""
     from .deepqnetwork import check_bootstrap as check
@@ -232,6 +271,10 @@ def run(args):
     check_target_tau(args)
     check_munchausen(args)
     check_advantage_learning(args)
+    check_cql(args)
+    save_replay, offline_replay = check_offline(args)
+    if offline_replay:
+        check_offline_file(args, offline_replay)                     # (the header only: a mismatch is refused before the memory is allocated)
     check_clip_grad_norm(args)
     check_dynamics(args)
     check_freeway_ticks(args)
@@ -273,8 +316,13 @@ def run(args):
                                  "hold the whole game)" % (agent.history_length, mem.current, agent.random_starts))
             logger.info("visualising ring indexes %d..%d: %d states of the game played" % (indexes[0], indexes[-1], len(indexes)))
             visualize(net, mem, args.visualization_filters, args.visualization_file, indexes=indexes)
+        if save_replay:                                              # --save_replay: the games just played
+            mem.save(save_replay)
         return stats
-    if args.random_steps:                                            # :130-137
+    if offline_replay:                                               # --offline_replay: the dataset is the memory; no random phase
+        mem.load(offline_replay)
+        logger.info("offline training on %s: %d transitions" % (offline_replay, mem.count))
+    if args.random_steps and not offline_replay:                     # :130-137
         env.setMode('train')
         stats.reset()
         if train_envs:
@@ -287,7 +335,9 @@ def run(args):
         if args.train_steps:
             env.setMode('train')
             stats.reset()
-            if train_envs:
+            if offline_replay:
+                agent.train_offline(args.train_steps, epoch)
+            elif train_envs:
                 agent.train_vectorised(args.train_steps, epoch)
                 stats.record_evaluation(*agent.vectorised_tallies())
             else:
@@ -306,6 +356,9 @@ def run(args):
             else:
                 agent.test(args.test_steps, epoch)
             stats.write(epoch + 1, "test")
+    if save_replay:                                                  # --save_replay: the memory as the run leaves it
+        mem.save(save_replay)
+        logger.info("replay memory written to %s: %d transitions" % (save_replay, mem.count))
     stats.close()
     return stats
 

@@ -355,6 +355,18 @@ class ReplayMemory:
             self.actions[:count].tofile(f); self.rewards[:count].tofile(f)
             self.terminals[:count].view(np.uint8).tofile(f); self.screens[:count].tofile(f)
 
+    @classmethod
+    def peek(cls, path):
+        """The header of a file written by save(), without loading it (no memory, no device): a dictionary with size, count, current, H, W
+        and hist.  ValueError for a file that is no checkpoint."""
+        with open(path, "rb") as f:
+            if f.read(len(cls._MAGIC)) != cls._MAGIC:
+                raise ValueError("%s is not a replay-memory checkpoint" % path)
+            head = np.fromfile(f, dtype=np.int64, count=6)
+        if head.size != 6:
+            raise ValueError("%s: the replay-memory checkpoint ends inside its header" % path)
+        return dict(zip(("size", "count", "current", "H", "W", "hist"), (int(v) for v in head)))
+
     def load(self, path):
         """Restores a ring written by save() into THIS memory (same size and geometry) and refreshes the HBM mirror."""
         if self.lanes[0]:

@@ -150,7 +150,10 @@ class Statistics:
         now = time.process_time()
         total_time, epoch_time = now - self.start_time, max(now - t.began, 1e-9)
         rate = t.num_steps / epoch_time
-        t.close_open_game()
+        if t.num_steps or t.num_games or t.game_rewards:
+            t.close_open_game()
+        else:                                                           # a phase without an environment step (--offline_replay's train phase):
+            t.min_game_reward = t.max_game_reward = 0                   # zero games, and no extremes of games that were never played
         if self.validation_states is None and self.mem.count > self.mem.batch_size:
             self.validation_states = self.mem.getMinibatch()[0]         # fixed held-out states for the meanq column
         if self.csv_name:

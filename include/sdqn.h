@@ -378,6 +378,14 @@ int sdqn_net_get_cql(sdqn_net_t h, double* alpha);      /* the pointer may be NU
 /* the rule on one sample, host side (no device), from its stored row q_row [A] and its target y: clip_error 0 = no clip, weight 1 = no
  * prioritized replay.  dq_out [A] and *cost_out receive what the train step's head writes for that sample */
 int sdqn_cql_loss(int A, double alpha, double clip_error, const float* q_row, int action, double y, double weight, float* dq_out, float* cost_out);
+/* Which training options combine (csrc/option_table.h), host side (no device).  The options that take part are numbered from 0:
+ * sdqn_option_name(id) is the name the refusals print ("double_dqn", "munchausen", "advantage_learning", "cql_alpha", "bootstrap_heads",
+ * "quantiles", "dueling", "noisy_nets", "batch_norm", "clip_grad_norm", "target_tau"), NULL past the end.  sdqn_option_conflict returns 1
+ * when switching option `setting` on is refused while option `other` is on — msg [cap] (may be NULL) then receives the words the setter's
+ * SDQN_ERR_ARG leaves in sdqn_last_error, the two values printed where an option prints one — 0 when the two combine (msg is emptied), and
+ * SDQN_ERR_ARG for an id past the end.  The relation is symmetric and no option is refused with itself. */
+const char* sdqn_option_name(int id);
+int sdqn_option_conflict(int setting, int other, int setting_value, int other_value, char* msg /*[cap], nullable*/, int cap);
 /* Bootstrapped DQN, --bootstrap_heads K (Osband, Blundell, Pritzel and Van Roy 2016; no reference counterpart).  The network is
  * created with num_actions = K x A outputs (<= 18); output row k A + a is Q-head k, action a, and actions in transitions are < A.  A train step
  * gives every Q-head its own target y_k = r_c + (terminal ? 0 : discount max_a Q_k(theta-, s')[a]) and sets

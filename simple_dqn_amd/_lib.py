@@ -135,6 +135,8 @@ SIGNATURES = {
     "sdqn_net_set_cql": (C.c_int, [_vp, C.c_double]),
     "sdqn_net_get_cql": (C.c_int, [_vp, _f64p]),
     "sdqn_cql_loss": (C.c_int, [C.c_int, C.c_double, C.c_double, _f32p, C.c_int, C.c_double, C.c_double, _f32p, _f32p]),
+    "sdqn_option_name": (C.c_char_p, [C.c_int]),
+    "sdqn_option_conflict": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int]),
     "sdqn_net_set_bootstrap": (C.c_int, [_vp, C.c_int, C.c_double, C.c_uint64]),
     "sdqn_net_get_bootstrap": (C.c_int, [_vp, C.POINTER(C.c_int), _f64p, C.POINTER(C.c_uint64)]),
     "sdqn_net_bootstrap_acting": (C.c_int, [_vp, C.c_int, C.c_int]),

@@ -21,6 +21,7 @@
 #include "sdqn_clip.h"
 #include "noisy.h"
 #include "shift.h"
+#include "option_table.h"
 
 using namespace sdqn;
 
@@ -333,6 +334,17 @@ int noisy_fresh(sdqn_net_s* h);
 int noisy_compose(sdqn_net_s* h, int64_t step, int nets);
 inline bool noisy_acting(const sdqn_net_s* h) { return h->noisy && h->nz_collecting; }
 inline bool clip_on(const sdqn_net_s* h) { return h->clip_grad_norm > 0.0; }
+// The options of option_table.h that are on, as a mask of option_bit(OptionId); values (may be NULL): [OPT_COUNT], the values the messages
+// print.  The one place that knows where each switch lives (the generic path keeps double_dqn and munchausen in its own object).
+inline unsigned active_options(const sdqn_net_s* h, int* values = nullptr) {
+  const bool on[OPT_COUNT] = {
+    h->gen ? h->gen->double_dqn_on() : h->double_dqn, h->gen ? h->gen->munchausen_on() : h->munchausen, h->al_alpha > 0.0, h->cql_alpha > 0.0,
+    h->boot_K > 1, h->quant_N > 1, h->dueling, h->noisy, h->cfg.batch_norm != 0.0, clip_on(h), h->target_tau > 0.0};
+  unsigned mask = 0;
+  for (int id = 0; id < OPT_COUNT; ++id) { if (on[id]) mask |= option_bit(id); if (values) values[id] = 0; }
+  if (values) { values[OPT_BOOTSTRAP_HEADS] = h->boot_K; values[OPT_QUANTILES] = h->quant_N; }
+  return mask;
+}
 int clip_gradient(sdqn_net_s* h, double bsz);                      // --clip_grad_norm: the two launches on g between update modes 1 and 2 (nothing when off)
 StepPlan step_plan(const sdqn_net_s* h);
 int run_update_tail(sdqn_net_s* h, UpdateArgs u, const TailPlan& t, const PrepArgs* next = nullptr);

@@ -9,6 +9,22 @@
 static const char* const RETIRED_OPTIONS[] = {"hoist", "two_streams", "fuse_dbg", "fwd_rb", "head_f4d", "fuse_upd", "f4w_early", "bt_planes", "bt_x", "bwd_order", nullptr};
 #define RETIRED_OPTION_REFUSED(NAME) do { set_error("option %s belonged to an experiment that was measured slower than the default step and has been removed from " \
                                                     "the library (tools/exp/README.md; tools/exp/experiments_r04.patch)", NAME); return SDQN_ERR_ARG; } while (0)
+// Switching option `setting` on (value: what its message prints, where it prints one): SDQN_ERR_ARG and the message when an option that
+// option_table.h pairs it with is on.  Every setter asks before it allocates or changes anything, so a refused call leaves the handle as it was.
+static int refuse_conflicts(const sdqn_net_s* h, int setting, int value = 0) {
+  int values[OPT_COUNT]; char msg[256];
+  const unsigned active = active_options(h, values);
+  ARGCHK(option_conflict(setting, value, active, values, msg, sizeof msg) < 0, "%s", msg);
+  return SDQN_OK;
+}
+#define REFUSE_CONFLICTS(...) do { int rc_ = refuse_conflicts(__VA_ARGS__); if (rc_) return rc_; } while (0)
+// ---- the option table without a device (option_table.h; tests/test_option_table.py) --------------------------------------------------------
+extern "C" const char* sdqn_option_name(int id) { return option_id_ok(id) ? OPTIONS[id].name : nullptr; }
+extern "C" int sdqn_option_conflict(int setting, int other, int setting_value, int other_value, char* msg, int cap) {
+  ARGCHK(option_id_ok(setting) && option_id_ok(other), "option ids %d, %d outside [0, %d)", setting, other, (int)OPT_COUNT);
+  int values[OPT_COUNT] = {0}; values[other] = other_value;
+  return option_conflict(setting, setting_value, option_bit(other), values, msg, cap) == other ? 1 : 0;
+}
 // ---- network -------------------------------------------------------------------------------------------
 
 int dalloc(sdqn_net_s* h, void** p, size_t bytes, bool zero) {
@@ -418,7 +434,7 @@ int gen_step_done(sdqn_net_s* h) {
 extern "C" int sdqn_net_set_clip_grad_norm(sdqn_net_t h, double max_norm) {
   ARGCHK(h, "NULL handle");
   ARGCHK(max_norm >= 0.0 && max_norm < INFINITY, "clip_grad_norm %g: must be a finite value >= 0 (0 = off)", max_norm);     // (false for a NaN)
-  ARGCHK(!(max_norm > 0.0 && h->noisy), "clip_grad_norm cannot be combined with noisy_nets: the norm would have to include sigma's gradient");
+  if (max_norm > 0.0) REFUSE_CONFLICTS(h, OPT_CLIP_GRAD_NORM);
   if (h->gen) GENCHK(h->gen->set_clip(max_norm > 0.0));
   else if (max_norm > 0.0 && !h->clip_buf) { int r_ = dalloc(h, (void**)&h->clip_buf, (size_t)CLIP_WORDS * 8); if (r_) return r_; }
   h->clip_grad_norm = max_norm;
@@ -440,14 +456,14 @@ extern "C" int sdqn_net_last_grad_norm(sdqn_net_t h, double* norm, double* scale
 extern "C" int sdqn_net_soft_update(sdqn_net_t h, double tau) {
   ARGCHK(h, "NULL handle");
   ARGCHK(tau_in_range(tau), "soft target update: tau %g outside (0, 1]", tau);
-  ARGCHK(!h->noisy || tau == 1.0, "target_tau cannot be combined with noisy_nets: the blend would have to cover sigma");
+  if (tau != 1.0) REFUSE_CONFLICTS(h, OPT_TARGET_TAU);                   // (tau = 1 is the hard copy)
   if (!h->gen) { int rc = join_comm(h); if (rc) return rc; }
   return target_blend(h, tau);
 }
 extern "C" int sdqn_net_set_target_tau(sdqn_net_t h, double tau) {
   ARGCHK(h, "NULL handle");
   ARGCHK(tau == 0.0 || tau_in_range(tau), "target_tau %g outside [0, 1]", tau);
-  ARGCHK(!(tau > 0.0 && h->noisy), "target_tau cannot be combined with noisy_nets: the blend would have to cover sigma");
+  if (tau > 0.0) REFUSE_CONFLICTS(h, OPT_TARGET_TAU);
   h->target_tau = tau;
   return SDQN_OK;
 }
@@ -565,21 +581,9 @@ extern "C" int sdqn_net_set_munchausen(sdqn_net_t h, int on, double alpha, doubl
   ARGCHK(tau > 0.0 && tau < INFINITY, "munchausen_tau %g: must be > 0", tau);
   ARGCHK(alpha >= 0.0 && alpha <= 1.0, "munchausen_alpha %g outside [0, 1]", alpha);
   ARGCHK(clip <= 0.0 && clip > -INFINITY, "munchausen_clip %g: must be <= 0", clip);
-  if (on) {
-    ARGCHK(h->boot_K == 1, "munchausen cannot be combined with bootstrap_heads %d", h->boot_K);
-    ARGCHK(h->quant_N == 1, "munchausen cannot be combined with quantiles %d", h->quant_N);
-    ARGCHK(!h->dueling, "munchausen cannot be combined with dueling");
-    ARGCHK(!h->noisy, "munchausen cannot be combined with noisy_nets");
-    ARGCHK(!(h->al_alpha > 0.0), "munchausen cannot be combined with advantage_learning: both targets want q slot 2 for a head of their own");
-    ARGCHK(!(h->cql_alpha > 0.0), "munchausen cannot be combined with cql_alpha");
-    ARGCHK(h->cfg.batch_norm == 0.0, "munchausen cannot be combined with batch_norm: inference-mode statistics for its third forward are not defined");
-    ARGCHK(h->gen || !h->double_dqn, "munchausen cannot be combined with double_dqn: the Munchausen target has no argmax for the online net to choose");
-  }
-  if (h->gen) {
-    const hipError_t ge = h->gen->set_munchausen(on != 0, alpha, tau, clip);
-    ARGCHK(ge != hipErrorInvalidValue, "munchausen cannot be combined with double_dqn: the Munchausen target has no argmax for the online net to choose");
-    GENCHK(ge);
-  } else if (on) { int r_ = ensure_slots3(h); if (r_) return r_; }
+  if (on) REFUSE_CONFLICTS(h, OPT_MUNCHAUSEN);
+  if (h->gen) GENCHK(h->gen->set_munchausen(on != 0, alpha, tau, clip));
+  else if (on) { int r_ = ensure_slots3(h); if (r_) return r_; }
   h->munchausen = on != 0; h->mu_alpha = alpha; h->mu_tau = tau; h->mu_clip = clip;
   return SDQN_OK;
 }
@@ -596,16 +600,8 @@ extern "C" int sdqn_net_set_advantage_learning(sdqn_net_t h, double alpha, int p
   ARGCHK(persistent == 0 || persistent == 1, "persistent_advantage must be 0 or 1");
   ARGCHK(!(persistent && alpha == 0.0), "persistent_advantage needs advantage_learning > 0");
   if (alpha > 0.0) {
-    const bool dd = h->gen ? h->gen->double_dqn_on() : h->double_dqn, mu = h->gen ? h->gen->munchausen_on() : h->munchausen;
-    ARGCHK(!dd, "advantage_learning cannot be combined with double_dqn: q slot 2 is taken by its third forward");
-    ARGCHK(!mu, "advantage_learning cannot be combined with munchausen: both targets want q slot 2 for a head of their own");
-    ARGCHK(h->boot_K == 1, "advantage_learning cannot be combined with bootstrap_heads %d", h->boot_K);
-    ARGCHK(h->quant_N == 1, "advantage_learning cannot be combined with quantiles %d", h->quant_N);
-    ARGCHK(!h->dueling, "advantage_learning cannot be combined with dueling");
-    ARGCHK(!h->noisy, "advantage_learning cannot be combined with noisy_nets");
-    ARGCHK(!(h->cql_alpha > 0.0), "advantage_learning cannot be combined with cql_alpha");
-    ARGCHK(h->cfg.batch_norm == 0.0, "advantage_learning cannot be combined with batch_norm: inference-mode statistics for its third forward are not defined");
-    ARGCHK(!(persistent && h->n_step > 1), "persistent_advantage cannot be combined with n_step %d: it repeats the action in the NEXT state", h->n_step);
+    REFUSE_CONFLICTS(h, OPT_ADVANTAGE_LEARNING);
+    ARGCHK(!(persistent && h->n_step > 1),"persistent_advantage cannot be combined with n_step %d: it repeats the action in the NEXT state", h->n_step);
   }
   if (h->gen) GENCHK(h->gen->set_advantage_learning(alpha > 0.0, alpha, persistent != 0));
   else if (alpha > 0.0) { int r_ = ensure_slots3(h); if (r_) return r_; }
@@ -622,17 +618,7 @@ extern "C" int sdqn_net_get_advantage_learning(sdqn_net_t h, double* alpha, int*
 extern "C" int sdqn_net_set_cql(sdqn_net_t h, double alpha) {
   ARGCHK(h, "NULL handle");
   ARGCHK(alpha >= 0.0 && alpha < INFINITY, "cql_alpha %g: must be a finite value >= 0", alpha);          // (a NaN fails the comparison)
-  if (alpha > 0.0) {
-    const bool dd = h->gen ? h->gen->double_dqn_on() : h->double_dqn, mu = h->gen ? h->gen->munchausen_on() : h->munchausen;
-    ARGCHK(!dd, "cql_alpha cannot be combined with double_dqn: the shared head body carries no third slot");
-    ARGCHK(!mu, "cql_alpha cannot be combined with munchausen");
-    ARGCHK(!(h->al_alpha > 0.0), "cql_alpha cannot be combined with advantage_learning");
-    ARGCHK(h->boot_K == 1, "cql_alpha cannot be combined with bootstrap_heads %d", h->boot_K);
-    ARGCHK(h->quant_N == 1, "cql_alpha cannot be combined with quantiles %d", h->quant_N);
-    ARGCHK(!h->dueling, "cql_alpha cannot be combined with dueling");
-    ARGCHK(!h->noisy, "cql_alpha cannot be combined with noisy_nets");
-    ARGCHK(h->cfg.batch_norm == 0.0, "cql_alpha cannot be combined with batch_norm");
-  }
+  if (alpha > 0.0) REFUSE_CONFLICTS(h, OPT_CQL_ALPHA);
   if (h->gen) GENCHK(h->gen->set_cql(alpha));
   h->cql_alpha = alpha;
   return SDQN_OK;
@@ -664,17 +650,7 @@ extern "C" int sdqn_net_set_bootstrap(sdqn_net_t h, int K, double P, uint64_t se
   ARGCHK(K >= 1 && K <= MAX_ACTIONS, "bootstrap_heads %d outside [1, %d]", K, MAX_ACTIONS);
   ARGCHK(h->A % K == 0, "bootstrap_heads %d does not divide the network's %d outputs (create it with bootstrap_heads x num_actions <= %d)", K, h->A, MAX_ACTIONS);
   uint64_t thresh; { int rc_ = boot_thresh_of(P, &thresh); if (rc_) return rc_; }
-  if (K > 1) {
-    ARGCHK(h->cfg.batch_norm == 0.0, "bootstrap_heads %d cannot be combined with batch_norm", K);
-    const bool dd = h->gen ? h->gen->double_dqn_on() : h->double_dqn, mu = h->gen ? h->gen->munchausen_on() : h->munchausen;
-    ARGCHK(!dd, "bootstrap_heads %d cannot be combined with double_dqn", K);
-    ARGCHK(!mu, "bootstrap_heads %d cannot be combined with munchausen", K);
-    ARGCHK(!(h->al_alpha > 0.0), "bootstrap_heads %d cannot be combined with advantage_learning", K);
-    ARGCHK(!(h->cql_alpha > 0.0), "bootstrap_heads %d cannot be combined with cql_alpha", K);
-    ARGCHK(h->quant_N == 1, "bootstrap_heads %d cannot be combined with quantiles %d", K, h->quant_N);
-    ARGCHK(!h->dueling, "bootstrap_heads %d cannot be combined with dueling", K);
-    ARGCHK(!h->noisy, "bootstrap_heads %d cannot be combined with noisy_nets", K);
-  }
+  if (K > 1) REFUSE_CONFLICTS(h, OPT_BOOTSTRAP_HEADS, K);
   if (h->gen) h->gen->set_bootstrap(K, thresh, bootstrap_mask_seed(seed));
   h->boot_K = K; h->boot_P = P; h->boot_seed = seed; h->boot_thresh = thresh; h->boot_episode = 0;
   return SDQN_OK;
@@ -718,15 +694,7 @@ extern "C" int sdqn_net_set_quantiles(sdqn_net_t h, int N) {
   ARGCHK(h->A % N == 0, "quantiles %d does not divide the network's %d outputs (create it with quantiles x num_actions <= %d)", N, h->A, MAX_ACTIONS);
   if (N > 1) {
     ARGCHK(h->cfg.clip_error > 0.0, "quantiles %d needs clip_error > 0 (clip_error %g): it is the Huber threshold of the quantile loss", N, h->cfg.clip_error);
-    ARGCHK(h->cfg.batch_norm == 0.0, "quantiles %d cannot be combined with batch_norm", N);
-    const bool dd = h->gen ? h->gen->double_dqn_on() : h->double_dqn, mu = h->gen ? h->gen->munchausen_on() : h->munchausen;
-    ARGCHK(!dd, "quantiles %d cannot be combined with double_dqn", N);
-    ARGCHK(!mu, "quantiles %d cannot be combined with munchausen", N);
-    ARGCHK(!(h->al_alpha > 0.0), "quantiles %d cannot be combined with advantage_learning", N);
-    ARGCHK(!(h->cql_alpha > 0.0), "quantiles %d cannot be combined with cql_alpha", N);
-    ARGCHK(h->boot_K == 1, "quantiles %d cannot be combined with bootstrap_heads %d", N, h->boot_K);
-    ARGCHK(!h->dueling, "quantiles %d cannot be combined with dueling", N);
-    ARGCHK(!h->noisy, "quantiles %d cannot be combined with noisy_nets", N);
+    REFUSE_CONFLICTS(h, OPT_QUANTILES, N);
     if (!h->gen && !h->quant_targets) { int r_ = dalloc(h, (void**)&h->quant_targets, (size_t)h->B * MAX_ACTIONS * sizeof(float)); if (r_) return r_; }
   }
   if (h->gen) GENCHK(h->gen->set_quantiles(N));
@@ -776,15 +744,7 @@ extern "C" int sdqn_net_set_dueling(sdqn_net_t h, int on) {
   ARGCHK(h, "NULL handle");
   if (on) {
     ARGCHK(h->A >= 2, "dueling needs a network with actions + 1 >= 2 outputs, this one has %d", h->A);
-    ARGCHK(h->cfg.batch_norm == 0.0, "dueling cannot be combined with batch_norm");
-    const bool dd = h->gen ? h->gen->double_dqn_on() : h->double_dqn, mu = h->gen ? h->gen->munchausen_on() : h->munchausen;
-    ARGCHK(!dd, "dueling cannot be combined with double_dqn: the shared head body carries no third slot");
-    ARGCHK(!mu, "dueling cannot be combined with munchausen");
-    ARGCHK(!(h->al_alpha > 0.0), "dueling cannot be combined with advantage_learning");
-    ARGCHK(!(h->cql_alpha > 0.0), "dueling cannot be combined with cql_alpha");
-    ARGCHK(h->boot_K == 1, "dueling cannot be combined with bootstrap_heads %d", h->boot_K);
-    ARGCHK(h->quant_N == 1, "dueling cannot be combined with quantiles %d", h->quant_N);
-    ARGCHK(!h->noisy, "dueling cannot be combined with noisy_nets");
+    REFUSE_CONFLICTS(h, OPT_DUELING);
     if (!h->gen && !h->duel_step) { int r_ = dalloc(h, (void**)&h->duel_step, (size_t)2 * h->B * sizeof(float)); if (r_) return r_; }
   }
   if (h->gen) GENCHK(h->gen->set_dueling(on != 0));
@@ -852,15 +812,7 @@ extern "C" int sdqn_net_set_noisy(sdqn_net_t h, int on, double sigma0, uint64_t 
   if (!on) { h->noisy = false; h->spec_pending = false; return SDQN_OK; }      // (sigma and its optimizer state stay where they are)
   ARGCHK(!h->gen, "noisy_nets is implemented for the 84x84x4 float32 configuration (not datatype float64 or other geometries: the generic path)");
   ARGCHK(h->cfg.datatype == 0, "noisy_nets cannot be combined with datatype float16");
-  ARGCHK(!h->bn, "noisy_nets cannot be combined with batch_norm");
-  ARGCHK(!clip_on(h), "noisy_nets cannot be combined with clip_grad_norm: the norm would have to include sigma's gradient");
-  ARGCHK(!(h->target_tau > 0.0), "noisy_nets cannot be combined with target_tau: the blend would have to cover sigma");
-  ARGCHK(!h->munchausen, "noisy_nets cannot be combined with munchausen");
-  ARGCHK(!(h->al_alpha > 0.0), "noisy_nets cannot be combined with advantage_learning");
-  ARGCHK(!(h->cql_alpha > 0.0), "noisy_nets cannot be combined with cql_alpha");
-  ARGCHK(h->boot_K == 1, "noisy_nets cannot be combined with bootstrap_heads %d", h->boot_K);
-  ARGCHK(h->quant_N == 1, "noisy_nets cannot be combined with quantiles %d", h->quant_N);
-  ARGCHK(!h->dueling, "noisy_nets cannot be combined with dueling");
+  REFUSE_CONFLICTS(h, OPT_NOISY_NETS);
   ARGCHK(!h->comm && !h->grad_only, "noisy_nets cannot be combined with data parallel: sigma's gradient is not exchanged");
   ARGCHK(sigma0 >= 0.0 && sigma0 < INFINITY, "noisy_sigma %g: must be a finite value >= 0", sigma0);     // (false for a NaN)
   const size_t nf = (size_t)(h->NP - OFF4);
@@ -942,11 +894,7 @@ extern "C" int sdqn_noisy_noise(uint64_t seed, uint64_t step, int slot, int laye
 
 extern "C" int sdqn_net_set_option(sdqn_net_t h, const char* name, int value) {
   ARGCHK(h && name, "NULL argument");
-  if (!strcmp(name, "double_dqn") && value) ARGCHK(h->boot_K == 1, "double_dqn cannot be combined with bootstrap_heads %d", h->boot_K);
-  if (!strcmp(name, "double_dqn") && value) ARGCHK(h->quant_N == 1, "double_dqn cannot be combined with quantiles %d", h->quant_N);
-  if (!strcmp(name, "double_dqn") && value) ARGCHK(!h->dueling, "double_dqn cannot be combined with dueling: the shared head body carries no third slot");
-  if (!strcmp(name, "double_dqn") && value) ARGCHK(!(h->al_alpha > 0.0), "double_dqn cannot be combined with advantage_learning: q slot 2 is taken by its third forward");
-  if (!strcmp(name, "double_dqn") && value) ARGCHK(!(h->cql_alpha > 0.0), "double_dqn cannot be combined with cql_alpha: the shared head body carries no third slot");
+  if (!strcmp(name, "double_dqn") && value) REFUSE_CONFLICTS(h, OPT_DOUBLE_DQN);
   if (!strcmp(name, "n_step")) {                          // n-step returns: sdqn.h
     ARGCHK(value >= 1 && value <= SDQN_MAX_N_STEP, "n_step %d out of range [1, %d]", value, SDQN_MAX_N_STEP);
     ARGCHK(!(value > 1 && h->al_persistent), "n_step %d cannot be combined with persistent_advantage: it repeats the action in the NEXT state", value);
@@ -958,7 +906,6 @@ extern "C" int sdqn_net_set_option(sdqn_net_t h, const char* name, int value) {
     if (!strcmp(name, "dp_overlap") && value < 0) return SDQN_OK;      // (auto: nothing to overlap without a communicator)
     if (!strcmp(name, "double_dqn")) {
       ARGCHK(value == 0 || value == 1, "double_dqn must be 0 or 1");
-      ARGCHK(!(value && h->gen->munchausen_on()), "double_dqn cannot be combined with munchausen: the Munchausen target has no argmax for the online net to choose");
       GENCHK(h->gen->set_double_dqn(value != 0));
       return SDQN_OK;
     }
@@ -972,7 +919,6 @@ extern "C" int sdqn_net_set_option(sdqn_net_t h, const char* name, int value) {
   if (retired) { if (value) RETIRED_OPTION_REFUSED(name); return SDQN_OK; }
   if (!strcmp(name, "double_dqn")) {                      // Double DQN targets (van Hasselt et al. 2016): sdqn.h
     ARGCHK(value == 0 || value == 1, "double_dqn must be 0 or 1");
-    ARGCHK(!(value && h->munchausen), "double_dqn cannot be combined with munchausen: the Munchausen target has no argmax for the online net to choose");
     if (value) { int r_ = ensure_slots3(h); if (r_) return r_; }
     h->double_dqn = value != 0;
   }

@@ -211,18 +211,13 @@ StepPlan step_plan(const sdqn_net_s* h) {
   StepPlan p;
   p.structure = step_structure(h); p.update = update_form_of(h, p.structure);
   p.fuse_rms = plan_fuse_rms(h, p.update); p.side_fc4 = p.structure == STEP_DP_OVERLAP;
-  // the forward: --munchausen (refused together with double_dqn / batch_norm: sdqn_net_set_munchausen) | --double_dqn (comment at ddqn_active)
-  // | --advantage_learning (refused together with all of them: sdqn_net_set_advantage_learning; alpha = 0 is off: nothing below changes)
-  const bool al = h->al_alpha > 0.0;
-  p.extra_fwd = (h->munchausen || al) ? 1 : (ddqn_active(h) && h->bn) ? 2 : 0;
-  // --bootstrap_heads K > 1 (refused together with double_dqn / munchausen / batch_norm: sdqn_net_set_bootstrap): its own head; K = 1: nothing
-  // --quantiles N > 1 (refused together with all of them: sdqn_net_set_quantiles): likewise; N = 1: nothing
-  // --dueling (refused together with all of them and with double_dqn: sdqn_net_set_dueling): likewise
-  // --cql_alpha > 0 (refused together with all of them and with double_dqn: sdqn_net_set_cql): likewise, and nothing else — no forward in
-  // front, two slots, the standard step's launches; alpha = 0 is off: nothing below changes
-  const bool cql = h->cql_alpha > 0.0;
-  p.head_train = h->dueling ? HEAD_DUELING : h->quant_N > 1 ? HEAD_QUANTILE : h->boot_K > 1 ? HEAD_BOOTSTRAP : h->munchausen ? HEAD_MUNCHAUSEN : al ? HEAD_ADVANTAGE : cql ? HEAD_CQL : ddqn_active(h) ? HEAD_DOUBLE : 0;
-  p.nz = (!h->munchausen && !al && ddqn_active(h) && !h->bn) ? 3 : 2;
+  // the head of the one option that is on (option_table.h lets no two of them through); Double DQN's only with a target net (ddqn_active)
+  const int head = option_head(active_options(h));
+  p.head_train = head == HEAD_DOUBLE && !ddqn_active(h) ? 0 : head;
+  // --munchausen / --advantage_learning: the target net on the prestates in front of the step | --double_dqn: its own forward with
+  // --batch_norm, else a third slot of the step's (comment at ddqn_active)
+  p.extra_fwd = (p.head_train == HEAD_MUNCHAUSEN || p.head_train == HEAD_ADVANTAGE) ? 1 : (p.head_train == HEAD_DOUBLE && h->bn) ? 2 : 0;
+  p.nz = (p.head_train == HEAD_DOUBLE && !h->bn) ? 3 : 2;
   LaunchPlan* l = p.launch;
   plan_forward(h, l);
   // The backward.  conv1's weight gradient on packed-bf16 MFMA (sdqn_kernels_r3.hip) in every launch structure (same bits); B < 128 only: in the

@@ -30,6 +30,68 @@ def layer_shapes(num_actions, history_length=4, screen_height=84, screen_width=8
 MAX_ACTIONS = 18                                          # outputs of the library's head kernels (csrc/problems.h)
 
 
+# ---- which flags combine ---------------------------------------------------------------------------------------------
+# One row per refusal: (the flag the message names first, the flag it names second, the message; a % conversion in it takes the second
+# flag's value).  A pair is refused whichever of its flags is checked first; where both have words of their own (--bootstrap_heads /
+# --advantage_learning) there are two rows and each flag's check speaks its own.  The rows between the library's options are its table
+# (csrc/option_table.h; tests/test_option_table.py holds the two to each other) restated here, because these refusals come before the
+# library is loaded; --prioritized_replay, --random_shift, --persistent_advantage / --n_step and --noisy_nets' datatype and geometry
+# are this layer's alone.
+def _row(first, second, tail="", value=""):
+    return first, second, "--%s cannot be combined with --%s%s%s" % (first, second, value and " " + value, tail)
+
+
+def _follow(section):
+    return " (DESIGN.md §%d lists it as a follow-up)" % section
+
+
+_NO_BN_THIRD_FORWARD = ": inference-mode statistics for its third forward are not defined"
+CONFLICTS = (
+    [_row("bootstrap_heads", f, _follow(27)) for f in ("double_dqn", "prioritized_replay", "munchausen", "batch_norm", "advantage_learning")]
+    + [_row("quantiles", f, _follow(29)) for f in ("double_dqn", "prioritized_replay", "munchausen", "batch_norm", "advantage_learning")]
+    + [_row("quantiles", "bootstrap_heads", _follow(29), "%d")]
+    + [_row("dueling", f, _follow(32)) for f in ("double_dqn", "munchausen", "batch_norm", "advantage_learning")]
+    + [_row("dueling", f, _follow(32), "%d") for f in ("bootstrap_heads", "quantiles")]
+    + [_row("noisy_nets", "datatype", _follow(33), "%s"),
+       ("noisy_nets", "geometry", "--noisy_nets needs 84 x 84 screens with --history_length 4, not --screen_height %d --screen_width %d "
+                                  "--history_length %d" + _follow(33))]
+    + [_row("noisy_nets", f, _follow(33)) for f in ("batch_norm", "munchausen", "dueling")]
+    + [_row("noisy_nets", f, _follow(33), "%g") for f in ("clip_grad_norm", "target_tau", "advantage_learning")]
+    + [_row("noisy_nets", f, _follow(33), "%d") for f in ("bootstrap_heads", "quantiles")]
+    + [_row("random_shift", "batch_norm", ": the shift would change the batch statistics, and that case has no oracle"),
+       _row("persistent_advantage", "n_step", " (--advantage_learning alone can): it repeats the action in the NEXT state", "%d"),
+       _row("advantage_learning", "double_dqn", ": q slot 2 is taken by its third forward" + _follow(28)),
+       _row("advantage_learning", "munchausen", ": both targets want q slot 2 for a head of their own"),
+       _row("advantage_learning", "bootstrap_heads", _follow(28), "%d"),
+       _row("advantage_learning", "batch_norm", _NO_BN_THIRD_FORWARD)]
+    + [_row("cql_alpha", f, _follow(35)) for f in ("double_dqn", "munchausen", "dueling", "noisy_nets", "batch_norm")]
+    + [_row("cql_alpha", "advantage_learning", _follow(35), "%g")]
+    + [_row("cql_alpha", f, _follow(35), "%d") for f in ("bootstrap_heads", "quantiles")]
+    + [_row("munchausen", "double_dqn", ": the Munchausen target has no argmax for the online net to choose"),
+       _row("munchausen", "batch_norm", _NO_BN_THIRD_FORWARD)])
+_OFF_AT = {"bootstrap_heads": 1, "quantiles": 1, "n_step": 1, "random_shift": 0, "datatype": "float32",     # a number: on above this value
+           "advantage_learning": 0.0, "cql_alpha": 0.0, "clip_grad_norm": 0.0, "target_tau": 0.0}            # every other flag: a switch
+
+
+def flag_setting(args, flag):
+    """(whether `flag` is on in args, its value as the messages print it); a missing or None attribute is the flag's off value"""
+    if flag == "geometry":
+        geom = tuple(int(getattr(args, k, d)) for k, d in (("screen_height", 84), ("screen_width", 84), ("history_length", 4)))
+        return geom != (84, 84, 4), geom
+    off = _OFF_AT.get(flag, False)
+    v = type(off)(getattr(args, flag, off) or off)
+    return (v != off if isinstance(off, (bool, str)) else v > off), v
+
+
+def refuse_conflicts(args, flag):
+    """The "cannot be combined" part of every check_* function: ValueError in the words of the first row of CONFLICTS that pairs `flag`
+    with another flag when both are on, rows that name `flag` first taken first.  Touches no device."""
+    for first, second, message in sorted((r for r in CONFLICTS if flag in r[:2]), key=lambda r: r[0] != flag):
+        (on1, _), (on2, value) = flag_setting(args, first), flag_setting(args, second)
+        if on1 and on2:
+            raise ValueError(message % value if "%" in message else message)
+
+
 def check_bootstrap(args, num_actions=None):
     """--bootstrap_heads K / --bootstrap_mask_probability P: K >= 1, K x num_actions <= 18 (when num_actions is known),
     P in (0, 1], and K > 1 with none of --double_dqn, --prioritized_replay, --munchausen, --batch_norm.  Raises ValueError; touches no
@@ -44,10 +106,7 @@ def check_bootstrap(args, num_actions=None):
     if K > 1 and num_actions is not None and K * int(num_actions) > MAX_ACTIONS:      # (K = 1: the library's own range check, as ever)
         raise ValueError("--bootstrap_heads %d x %d actions = %d outputs: the network has at most %d"
                          % (K, int(num_actions), K * int(num_actions), MAX_ACTIONS))
-    if K > 1:
-        for flag in ("double_dqn", "prioritized_replay", "munchausen", "batch_norm", "advantage_learning"):
-            if getattr(args, flag, False):
-                raise ValueError("--bootstrap_heads cannot be combined with --%s (DESIGN.md §27 lists it as a follow-up)" % flag)
+    refuse_conflicts(args, "bootstrap_heads")
     return K, P
 
 
@@ -68,14 +127,7 @@ def check_quantiles(args, num_actions=None):
     if not float(kappa or 0.0) > 0.0:
         raise ValueError("--quantiles %d needs --clip_error > 0 (got %s): it is the Huber threshold of the quantile loss; the pure "
                          "pinball loss is not offered" % (N, kappa))
-    for flag in ("double_dqn", "prioritized_replay", "munchausen", "batch_norm"):
-        if getattr(args, flag, False):
-            raise ValueError("--quantiles cannot be combined with --%s (DESIGN.md §29 lists it as a follow-up)" % flag)
-    if float(getattr(args, "advantage_learning", 0.0) or 0.0) > 0.0:
-        raise ValueError("--quantiles cannot be combined with --advantage_learning (DESIGN.md §29 lists it as a follow-up)")
-    K = getattr(args, "bootstrap_heads", 1)
-    if (1 if K is None else int(K)) > 1:
-        raise ValueError("--quantiles cannot be combined with --bootstrap_heads %d (DESIGN.md §29 lists it as a follow-up)" % int(K))
+    refuse_conflicts(args, "quantiles")
     return N
 
 
@@ -89,17 +141,7 @@ def check_dueling(args, num_actions=None):
                          % (int(num_actions), int(num_actions) + 1, MAX_ACTIONS))
     if num_actions is not None and int(num_actions) < 1:
         raise ValueError("--dueling needs at least one action, got %d" % int(num_actions))
-    for flag in ("double_dqn", "munchausen", "batch_norm"):
-        if getattr(args, flag, False):
-            raise ValueError("--dueling cannot be combined with --%s (DESIGN.md §32 lists it as a follow-up)" % flag)
-    if float(getattr(args, "advantage_learning", 0.0) or 0.0) > 0.0:
-        raise ValueError("--dueling cannot be combined with --advantage_learning (DESIGN.md §32 lists it as a follow-up)")
-    K = getattr(args, "bootstrap_heads", 1)
-    if (1 if K is None else int(K)) > 1:
-        raise ValueError("--dueling cannot be combined with --bootstrap_heads %d (DESIGN.md §32 lists it as a follow-up)" % int(K))
-    N = getattr(args, "quantiles", 1)
-    if (1 if N is None else int(N)) > 1:
-        raise ValueError("--dueling cannot be combined with --quantiles %d (DESIGN.md §32 lists it as a follow-up)" % int(N))
+    refuse_conflicts(args, "dueling")
     return True
 
 
@@ -112,24 +154,7 @@ def check_noisy(args):
         return False, sigma0
     if not (sigma0 >= 0.0 and sigma0 < float("inf")):
         raise ValueError("--noisy_sigma %r: must be a finite value >= 0" % (sigma0,))
-    follow = " (DESIGN.md §33 lists it as a follow-up)"
-    dt = str(getattr(args, "datatype", "float32"))
-    if dt != "float32":
-        raise ValueError("--noisy_nets cannot be combined with --datatype %s%s" % (dt, follow))
-    geom = (int(getattr(args, "history_length", 4)), int(getattr(args, "screen_height", 84)), int(getattr(args, "screen_width", 84)))
-    if geom != (4, 84, 84):
-        raise ValueError("--noisy_nets needs 84 x 84 screens with --history_length 4, not --screen_height %d --screen_width %d --history_length %d%s"
-                         % (geom[1], geom[2], geom[0], follow))
-    for flag in ("batch_norm", "munchausen", "dueling"):
-        if getattr(args, flag, False):
-            raise ValueError("--noisy_nets cannot be combined with --%s%s" % (flag, follow))
-    for flag in ("clip_grad_norm", "target_tau", "advantage_learning"):
-        if float(getattr(args, flag, 0.0) or 0.0) > 0.0:
-            raise ValueError("--noisy_nets cannot be combined with --%s %g%s" % (flag, float(getattr(args, flag)), follow))
-    for flag in ("bootstrap_heads", "quantiles"):
-        v = getattr(args, flag, 1)
-        if (1 if v is None else int(v)) > 1:
-            raise ValueError("--noisy_nets cannot be combined with --%s %d%s" % (flag, int(v), follow))
+    refuse_conflicts(args, "noisy_nets")
     return True, sigma0
 
 
@@ -158,8 +183,7 @@ def check_random_shift(args):
         raise ValueError("--random_shift %d: must be in [0, 8] (0: off)" % P)
     if P == 0:
         return 0
-    if getattr(args, "batch_norm", False):
-        raise ValueError("--random_shift cannot be combined with --batch_norm: the shift would change the batch statistics, and that case has no oracle")
+    refuse_conflicts(args, "random_shift")
     hw = (int(getattr(args, "screen_height", 84)), int(getattr(args, "screen_width", 84)))
     if P >= min(hw):
         raise ValueError("--random_shift %d needs screens larger than the shift (--screen_height %d --screen_width %d)" % ((P,) + hw))
@@ -186,18 +210,8 @@ def check_advantage_learning(args):
         raise ValueError("--persistent_advantage needs --advantage_learning > 0: it is a form of the same gap correction")
     if alpha == 0.0:
         return alpha, pal
-    if pal and int(getattr(args, "n_step", 1) or 1) > 1:
-        raise ValueError("--persistent_advantage cannot be combined with --n_step %d (--advantage_learning alone can): it repeats the "
-                         "action in the NEXT state" % int(args.n_step))
-    if getattr(args, "double_dqn", False):
-        raise ValueError("--advantage_learning cannot be combined with --double_dqn: q slot 2 is taken by its third forward (DESIGN.md §28 lists it as a follow-up)")
-    if getattr(args, "munchausen", False):
-        raise ValueError("--advantage_learning cannot be combined with --munchausen: both targets want q slot 2 for a head of their own")
-    K = getattr(args, "bootstrap_heads", 1)
-    if (1 if K is None else int(K)) > 1:
-        raise ValueError("--advantage_learning cannot be combined with --bootstrap_heads %d (DESIGN.md §28 lists it as a follow-up)" % int(K))
-    if getattr(args, "batch_norm", False):
-        raise ValueError("--advantage_learning cannot be combined with --batch_norm: inference-mode statistics for its third forward are not defined")
+    refuse_conflicts(args, "persistent_advantage")
+    refuse_conflicts(args, "advantage_learning")
     return alpha, pal
 
 
@@ -211,16 +225,7 @@ def check_cql(args):
         raise ValueError("--cql_alpha %g: must be a finite value >= 0 (0: off)" % alpha)
     if alpha == 0.0:
         return alpha
-    follow = " (DESIGN.md §35 lists it as a follow-up)"
-    for flag in ("double_dqn", "munchausen", "dueling", "noisy_nets", "batch_norm"):
-        if getattr(args, flag, False):
-            raise ValueError("--cql_alpha cannot be combined with --%s%s" % (flag, follow))
-    if float(getattr(args, "advantage_learning", 0.0) or 0.0) > 0.0:
-        raise ValueError("--cql_alpha cannot be combined with --advantage_learning %g%s" % (float(args.advantage_learning), follow))
-    for flag in ("bootstrap_heads", "quantiles"):
-        v = getattr(args, flag, 1)
-        if (1 if v is None else int(v)) > 1:
-            raise ValueError("--cql_alpha cannot be combined with --%s %d%s" % (flag, int(v), follow))
+    refuse_conflicts(args, "cql_alpha")
     return alpha
 
 

@@ -6,6 +6,10 @@ import logging
 import random
 import sys
 
+# the checks of the options that DeepQNetwork refuses on its own as well: the same functions, refused here before anything touches the device
+from .deepqnetwork import (check_advantage_learning, check_bootstrap, check_cql, check_dueling, check_noisy, check_quantiles,  # noqa: F401
+                           check_random_shift, refuse_conflicts)
+
 
 def _flag(text):
     return text.lower() in ("yes", "true", "t", "1")
@@ -181,24 +185,8 @@ def check_munchausen(args):
         raise ValueError("--munchausen_alpha %g: must be in [0, 1]" % alpha)
     if not (clip <= 0.0 and clip > -float("inf")):
         raise ValueError("--munchausen_clip %g: must be <= 0" % clip)
-    if on and getattr(args, "double_dqn", False):
-        raise ValueError("--munchausen cannot be combined with --double_dqn: the Munchausen target has no argmax for the online net to choose")
-    if on and getattr(args, "batch_norm", False):
-        raise ValueError("--munchausen cannot be combined with --batch_norm: inference-mode statistics for its third forward are not defined")
+    refuse_conflicts(args, "munchausen")
     return on
-
-
-def check_advantage_learning(args):
-    """--advantage_learning / --persistent_advantage: their ranges and what they cannot be combined with, refused before anything touches
-    the device"""
-    from .deepqnetwork import check_advantage_learning as check
-    return check(args)
-
-
-def check_cql(args):
-    """--cql_alpha: its range and what it cannot be combined with, refused before anything touches the device"""
-    from .deepqnetwork import check_cql as check
-    return check(args)
 
 
 def check_offline(args):
@@ -229,36 +217,6 @@ def check_offline_file(args, path):
         if int(head[key]) != int(want):
             raise ValueError("--offline_replay %s was written with %s %d, this run has %s %d" % (path, flag, head[key], flag, want))
     return head
-
-
-def check_bootstrap(args, num_actions=None):
-    """--bootstrap_heads: its ranges and what it cannot be combined with, refused before anything touches the device"""
-    from .deepqnetwork import check_bootstrap as check
-    return check(args, num_actions)
-
-
-def check_quantiles(args, num_actions=None):
-    """--quantiles: its range and what it cannot be combined with, refused before anything touches the device"""
-    from .deepqnetwork import check_quantiles as check
-    return check(args, num_actions)
-
-
-def check_dueling(args, num_actions=None):
-    """--dueling: what it cannot be combined with, refused before anything touches the device"""
-    from .deepqnetwork import check_dueling as check
-    return check(args, num_actions)
-
-
-def check_noisy(args):
-    """--noisy_nets / --noisy_sigma: what they cannot be combined with, refused before anything touches the device"""
-    from .deepqnetwork import check_noisy as check
-    return check(args)
-
-
-def check_random_shift(args):
-    """--random_shift: its range and what it cannot be combined with, refused before anything touches the device"""
-    from .deepqnetwork import check_random_shift as check
-    return check(args)
 
 
 def run(args):

@@ -499,6 +499,31 @@ int sdqn_net_set_random_shift(sdqn_net_t h, int P, uint64_t seed);
 int sdqn_net_get_random_shift(sdqn_net_t h, int* P, int64_t* step_counter);      /* any pointer may be NULL */
 int sdqn_random_shift_draw(uint64_t seed, uint64_t step, int64_t n, int s, int P, int* dy, int* dx);
 int sdqn_net_last_shifts(sdqn_net_t h, int8_t* out);
+/* Dormant-neuron recycling, --redo_interval N / --redo_threshold T (ReDo: Sokar, Agarwal, Castro and Evci 2023; no reference
+ * counterpart).  The four ReLU layers conv1, conv2, conv3, fc4 have 32, 64, 64, 512 units = 672 scores [s_1 | s_2 | s_3 | s_4].  The score of
+ * unit j of layer l is m_l[j] / mean_k m_l[k] (0 when the mean is 0), m_l[j] = the mean of |activation| over the rows of the online net's
+ * prestate half of the LAST TRAIN STEP, summed in fp64 in a fixed order (no atomics: the same activations give the same bits); a unit is
+ * dormant when its score <= T (T in [0, 1), 0: exactly silent units only).  One recycle EVENT e = 1, 2, ... on the online net: the incoming
+ * weights of every dormant unit become fresh draws of the initialiser, (u 2^-23 - 1) sqrt(3 / fan_in) in float with u the top 24 bits of one
+ * splitmix64 word keyed by (seed, e, flat internal index) (sdqn_redo_draw restates it); every weight of the next layer that multiplies the
+ * unit becomes +0.0 (fc5: that column of all rows; zeroing wins over a draw); the optimizer state(s) of all those entries return to +0.0.
+ * The target net, every other weight and the gradient buffer are untouched; the half copies / conv1's bf16 planes follow.
+ * sdqn_net_set_redo: interval N > 0: an event follows every applied train step t (sdqn_net_train_iterations) with t % N == 0, on the
+ * library stream, inside multi-step calls too, without any wait; 0 (default): nothing runs and nothing is allocated.  SDQN_ERR_ARG: N < 0,
+ * T outside [0, 1), N > 0 on a batch_norm or noisy net, on the generic path (float64, other geometries) or with data parallel on more than
+ * one rank (sdqn_net_set_noisy and sdqn_dp_init refuse the other way round).  sdqn_net_redo_now: one event now; sdqn_net_redo_scores: out
+ * [672], recycles nothing, usable with interval 0 — both SDQN_ERR_ARG before the first train step or once a forward of its own (predict,
+ * act) has overwritten that step's activations.  sdqn_net_redo_last: out [6] = the last event's number (0: none yet), the train step it
+ * followed and the four dormant counts, as the device left them.  sdqn_redo_apply_host (no device): the same rules on host arrays in the
+ * internal layouts, theta / state / state2 (state, state2, counts may be NULL) of 1 683 456 + 512 A floats, in place. */
+int sdqn_net_set_redo(sdqn_net_t h, int interval, double tau, uint64_t seed);
+int sdqn_net_get_redo(sdqn_net_t h, int* interval, double* tau, uint64_t* seed);      /* any pointer may be NULL */
+int sdqn_net_redo_now(sdqn_net_t h);
+int sdqn_net_redo_scores(sdqn_net_t h, float* out);
+int sdqn_net_redo_last(sdqn_net_t h, int64_t* out);
+int sdqn_redo_apply_host(const float* scores, double tau, uint64_t seed, uint64_t event, int A, float* theta, float* state, float* state2,
+                         int64_t* counts);
+int sdqn_redo_draw(uint64_t seed, uint64_t event, int64_t index, int layer, uint64_t* word, float* value);      /* layer 1..4; either may be NULL */
 /* option "double_dqn" (0 default / 1, any configuration, switchable between steps): Double DQN targets (van Hasselt, Guez and Silver
  * 2016): the online net picks each poststate's action, the target net values it (see sdqn_net_last_q).  The online net's forward on
  * the poststates rides as a third net slot in the step's own forward launches (batch_norm: a forward of its own in front of the step,

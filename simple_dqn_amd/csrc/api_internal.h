@@ -21,6 +21,7 @@
 #include "sdqn_clip.h"
 #include "noisy.h"
 #include "shift.h"
+#include "redo.h"
 #include "option_table.h"
 
 using namespace sdqn;
@@ -173,6 +174,13 @@ struct sdqn_net_s {
   // minibatch (one launch, shift_minibatch) and runs as the step that reads a device minibatch in place.  shift_step: such steps enqueued =
   // the t of the next step's draws; shift_out: [B][2][2] the (dy, dx) the last launch drew, allocated by the setter.  0: nothing changes
   int shift_P = 0; uint64_t shift_seed = 0; int64_t shift_step = 0; int8_t* shift_out = nullptr;
+  // --redo_interval (sdqn_net_set_redo; redo.h, sdqn_redo.hip): redo_interval > 0: every applied train step t (train_iterations) with
+  // t % redo_interval == 0 is followed by one recycle event on the library stream (redo_step_done).  redo_partial / redo_scores / redo_info:
+  // the score reduction's partial sums, the 672 scores and the last event's record {event, step, four dormant counts}, allocated on first use
+  // (the setter with interval > 0, or the first sdqn_net_redo_scores).  redo_events: events enqueued = the number of the last one.
+  // redo_acts_live: slot 0 of a1..a4 holds the online net's prestate activations of the last train step (a forward of its own overwrites them)
+  int redo_interval = 0; double redo_tau = 0.1; uint64_t redo_seed = 0; int64_t redo_events = 0; bool redo_acts_live = false;
+  double* redo_partial = nullptr; float* redo_scores = nullptr; int64_t* redo_info = nullptr;
   int n_step = 1;                          // --n_step (option "n_step"): poststate frame offset of the ring paths, n-step head
   double target_tau = 0.0;                 // --target_tau (sdqn_net_set_target_tau): > 0: every train step is followed by one soft target update
   // --clip_grad_norm (sdqn_net_set_clip_grad_norm): > 0: the flat gradient is scaled to this global L2 norm (of the MEAN
@@ -369,6 +377,10 @@ int predict_forward(sdqn_net_s* h, const uint8_t* states, int rows, const void**
 StepArgs ring_step_args(sdqn_net_s* h, const sdqn_replay_s* r);
 int run_ring_step(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* host_idx, const HeadArgs& hd, const PrepArgs* next = nullptr);
 int check_replay_geometry(const sdqn_net_s* h, const sdqn_replay_s* r);
+// --redo_interval (sdqn_api_redo.hip): what every applied train step of the tuned path ends with — nothing unless the step's number is a multiple
+// of the interval (sdqn_net_set_noisy and sdqn_dp_init ask redo_on for their side of the refusals)
+int redo_step_done(sdqn_net_s* h);
+inline bool redo_on(const sdqn_net_s* h) { return h->redo_interval > 0; }
 int shift_minibatch(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* didx);   // --random_shift: the launch (the caller has checked shift_P > 0); didx: the step's indexes as the device reads them
 bool act_sum_partials(const float* part, int A, float* q_out);
 const uint8_t* statebuf_window(sdqn_statebuf_s* s);

@@ -39,6 +39,7 @@ extern "C" int sdqn_dp_init(sdqn_net_t h, const char* rccl_path, const char id[1
   if (h->gen) { set_error("data parallel is implemented for the 84x84x4 float32 / float16 configurations"); return SDQN_ERR_STATE; }
   if (h->comm) { set_error("data parallel already initialised"); return SDQN_ERR_STATE; }
   ARGCHK(!h->noisy, "data parallel cannot be combined with noisy_nets: sigma's gradient is not exchanged (DESIGN.md §33)");
+  ARGCHK(!(redo_on(h) && nranks > 1), "data parallel with %d ranks cannot be combined with redo_interval %d: the ranks' activations differ (DESIGN.md §37)", nranks, h->redo_interval);
   int rc = rccl_load(rccl_path); if (rc) return rc;
   Id128 u; memcpy(u.b, id, 128);
   NCCLCHK(g_rccl.CommInitRank(&h->comm, nranks, u, rank));

@@ -1,0 +1,105 @@
+// sdqn_api_redo.hip — dormant-neuron recycling (--redo_interval): the host side.  The rules are redo.h's, the kernels sdqn_redo.hip's.
+//   scores   two launches (partial sums, scores) over slot 0 of a1..a4 (h_a1..h_a3 on a float16 net): the online net's prestate activations
+//            as the last train step left them
+//   event    scores, then one apply launch on theta / state / state2 and the event's record, then the derived copies of the online weights
+//            that sdqn_net_set_weights(which = 0) would have rebuilt: wh / wht (float16) or conv1's bf16 planes (float32)
+// Everything is enqueued on the library stream; nothing here waits for the device but the two read-outs.
+#include "api_internal.h"
+
+static int redo_buffers(sdqn_net_s* h) {
+  if (h->redo_scores) return SDQN_OK;
+  int rc = dalloc(h, (void**)&h->redo_partial, (size_t)redo_partial_doubles(h->B) * 8); if (rc) return rc;
+  rc = dalloc(h, (void**)&h->redo_scores, (size_t)REDO_UNITS * 4); if (rc) return rc;
+  return dalloc(h, (void**)&h->redo_info, 6 * 8);
+}
+// what the feature cannot run on, in the words both sides of each refusal use (sdqn_net_set_noisy, sdqn_dp_init)
+static int redo_refusals(const sdqn_net_s* h, const char* flag) {
+  ARGCHK(!h->gen, "%s is implemented for the 84x84x4 float32 / float16 configurations (not datatype float64 or other geometries: the generic path)", flag);
+  ARGCHK(!h->bn, "%s cannot be combined with batch_norm: the stored planes are not what the next layer reads", flag);
+  ARGCHK(!h->noisy, "%s cannot be combined with noisy_nets: sigma would have to be recycled too", flag);
+  ARGCHK(!(h->comm && h->nranks > 1), "%s cannot be combined with data parallel on %d ranks: the ranks' activations differ", flag, h->nranks);
+  return SDQN_OK;
+}
+static int redo_scores_enqueue(sdqn_net_s* h) {
+  ARGCHK(h->train_iterations > 0, "no train step has run: there are no activations to score");
+  ARGCHK(h->redo_acts_live, "a forward of its own (predict, act) has overwritten the last train step's activations: score them before it, or run a train step");
+  int rc = redo_buffers(h); if (rc) return rc;
+  RedoScoreArgs s; memset(&s, 0, sizeof s);
+  const bool half = h->cfg.datatype == 1;
+  s.a[0] = half ? (const void*)h->h_a1 : (const void*)h->a1; s.a[1] = half ? (const void*)h->h_a2 : (const void*)h->a2;
+  s.a[2] = half ? (const void*)h->h_a3 : (const void*)h->a3; s.a[3] = h->a4;
+  s.half123 = half ? 1 : 0; s.B = h->B; s.partial = h->redo_partial; s.scores = h->redo_scores;
+  LAUNCH(K_UPDATE, launch_redo_scores(s, 0, g_stream));
+  LAUNCH(K_UPDATE, launch_redo_scores(s, 1, g_stream));
+  return SDQN_OK;
+}
+static int redo_event(sdqn_net_s* h) {
+  { int rc = join_comm(h); if (rc) return rc; }            // (a single rank's overlapped form may still be applying fc4 on the side stream)
+  int rc = redo_scores_enqueue(h); if (rc) return rc;
+  RedoApplyArgs a; memset(&a, 0, sizeof a);
+  a.scores = h->redo_scores; a.theta = h->theta; a.state = h->state; a.state2 = h->state2; a.n = h->NPW;
+  a.tau = h->redo_tau; a.seed = h->redo_seed; a.event = (uint64_t)(h->redo_events + 1); a.step = h->train_iterations; a.info = h->redo_info;
+  LAUNCH(K_UPDATE, launch_redo_apply(a, g_stream));
+  h->redo_events += 1;
+  h->spec_pending = false;                 // the online parameters moved under a speculative acting forward
+  if (h->cfg.datatype == 1) HIPCHK(launch_refresh16(h->theta, h->wh[0], h->wht[0], g_stream));
+  if (h->w1p[0]) HIPCHK(launch_w1_planes(h->theta, h->w1p[0], g_stream));
+  return SDQN_OK;
+}
+int redo_step_done(sdqn_net_s* h) {
+  if (!redo_on(h) || h->train_iterations % h->redo_interval != 0) return SDQN_OK;
+  return redo_event(h);
+}
+
+extern "C" int sdqn_net_set_redo(sdqn_net_t h, int interval, double tau, uint64_t seed) {
+  ARGCHK(h, "NULL handle");
+  ARGCHK(interval >= 0, "redo_interval %d: must be >= 0 (0: off)", interval);
+  ARGCHK(tau >= 0.0 && tau < 1.0, "redo_threshold %g: must be in [0, 1)", tau);      // (false for a NaN)
+  if (interval > 0) {
+    int rc = redo_refusals(h, "redo_interval"); if (rc) return rc;
+    rc = redo_buffers(h); if (rc) return rc;
+  }
+  h->redo_interval = interval; h->redo_tau = tau; h->redo_seed = seed;
+  return SDQN_OK;
+}
+extern "C" int sdqn_net_get_redo(sdqn_net_t h, int* interval, double* tau, uint64_t* seed) {
+  ARGCHK(h, "NULL handle");
+  if (interval) *interval = h->redo_interval; if (tau) *tau = h->redo_tau; if (seed) *seed = h->redo_seed;
+  return SDQN_OK;
+}
+extern "C" int sdqn_net_redo_now(sdqn_net_t h) {
+  ARGCHK(h, "NULL handle");
+  int rc = redo_refusals(h, "redo_now"); if (rc) return rc;
+  return redo_event(h);
+}
+extern "C" int sdqn_net_redo_scores(sdqn_net_t h, float* out) {
+  ARGCHK(h && out, "NULL argument");
+  int rc = redo_refusals(h, "redo_scores"); if (rc) return rc;
+  rc = redo_scores_enqueue(h); if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(out, h->redo_scores, (size_t)REDO_UNITS * 4, hipMemcpyDeviceToHost, g_stream));
+  HIPCHK(hipStreamSynchronize(g_stream));
+  return per_check_all();
+}
+extern "C" int sdqn_net_redo_last(sdqn_net_t h, int64_t* out) {
+  ARGCHK(h && out, "NULL argument");
+  if (h->redo_events == 0) { for (int i = 0; i < 6; ++i) out[i] = 0; return SDQN_OK; }      // (no event yet: event number 0)
+  HIPCHK(hipMemcpyAsync(out, h->redo_info, 6 * 8, hipMemcpyDeviceToHost, g_stream));
+  HIPCHK(hipStreamSynchronize(g_stream));
+  return per_check_all();
+}
+// ---- the host restatement (no device) ---------------------------------------------------------------------------------------------------
+extern "C" int sdqn_redo_apply_host(const float* scores, double tau, uint64_t seed, uint64_t event, int A, float* theta, float* state, float* state2,
+                                    int64_t* counts) {
+  ARGCHK(scores && theta, "NULL argument");
+  ARGCHK(A >= 1 && A <= MAX_ACTIONS, "num_actions must be in 1..%d (got %d)", MAX_ACTIONS, A);
+  ARGCHK(tau >= 0.0 && tau < 1.0, "redo_threshold %g: must be in [0, 1)", tau);
+  redo_apply_host(scores, tau, seed, event, REDO_OFF5 + (int64_t)A * NFC, theta, state, state2, counts);
+  return SDQN_OK;
+}
+extern "C" int sdqn_redo_draw(uint64_t seed, uint64_t event, int64_t index, int layer, uint64_t* word, float* value) {
+  ARGCHK(index >= 0 && layer >= 1 && layer <= REDO_LAYERS, "bad arguments (index %lld, layer %d of 1..4)", (long long)index, layer);
+  const uint64_t key = redo_key(seed, event);
+  if (word) *word = redo_word(key, (uint64_t)index);
+  if (value) *value = redo_draw(key, (uint64_t)index, layer);
+  return SDQN_OK;
+}

@@ -122,6 +122,7 @@ static int forward(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd, const L
 }
 int run_forward(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd) {
   LaunchPlan l[K_FC4_FWD + 1]; plan_forward(h, l);
+  h->redo_acts_live = false;               // (a forward of its own writes slot 0 of a1..a4: no longer the last train step's activations)
   return forward(h, a, hd, l);
 }
 UpdateArgs make_update_args(sdqn_net_s* h, const StepArgs& a) {
@@ -391,7 +392,10 @@ int run_train(sdqn_net_s* h, const StepArgs& a0, const HeadArgs& hd0, const Prep
   if (plan.tail.noisy) { h->nz_step += 1; rc = noisy_compose(h, h->nz_step, 1); if (rc) return rc; }
   h->train_iterations += 1;                                                   // deepqnetwork.py:168
   h->spec_pending = false;                 // the online parameters move: a forward enqueued before this step no longer is "predict now"
-  return plan.update == UPD_GRAD_ONLY ? SDQN_OK : step_blend(h);      // --target_tau: one blend behind every APPLIED step
+  h->redo_acts_live = true;
+  if (plan.update == UPD_GRAD_ONLY) return SDQN_OK;
+  rc = step_blend(h); if (rc) return rc;                                      // --target_tau: one blend behind every APPLIED step
+  return redo_on(h) ? redo_step_done(h) : SDQN_OK;                            // --redo_interval: one recycle event behind every interval-th
 }
 // small read-backs: `bytes` of device memory into the pinned scratch h->h_f, waited for
 static int fetch_small(sdqn_net_s* h, const void* src, size_t bytes) {

@@ -197,6 +197,61 @@ def random_shift_draw(seed, step, n, s, P):
     return dy.value, dx.value
 
 
+REDO_UNITS = (32, 64, 64, 512)                            # ReLU units of conv1, conv2, conv3, fc4 (csrc/redo.h)
+
+
+def check_redo(args):
+    """--redo_interval N / --redo_threshold T / --log_dormant: N >= 0 (0: off), T in [0, 1), and recycling or the dormancy
+    read-out with none of --batch_norm, --noisy_nets, --datatype float64 or screens other than 84 x 84 x 4 (the generic path).  Raises
+    ValueError naming the flag; touches no device.  Returns (N, T, log_dormant)."""
+    n = getattr(args, "redo_interval", 0)
+    n = 0 if n is None else int(n)
+    tau = getattr(args, "redo_threshold", 0.1)
+    tau = 0.1 if tau is None else float(tau)
+    log = bool(getattr(args, "log_dormant", False))
+    if n < 0:
+        raise ValueError("--redo_interval %d: must be >= 0 (0: off)" % n)
+    if not 0.0 <= tau < 1.0:                                  # (a NaN fails both comparisons)
+        raise ValueError("--redo_threshold %g: must be in [0, 1)" % tau)
+    for on, flag in ((n > 0, "--redo_interval %d" % n), (log, "--log_dormant")):
+        if not on:
+            continue
+        if bool(getattr(args, "batch_norm", False)):
+            raise ValueError("%s cannot be combined with --batch_norm: the stored planes are not what the next layer reads" % flag)
+        if bool(getattr(args, "noisy_nets", False)):
+            raise ValueError("%s cannot be combined with --noisy_nets: sigma would have to be recycled too" % flag)
+        if str(getattr(args, "datatype", "float32")) == "float64":
+            raise ValueError("%s cannot be combined with --datatype float64: the generic path keeps no activations to score" % flag)
+        generic, geom = flag_setting(args, "geometry")
+        if generic:
+            raise ValueError("%s needs 84 x 84 screens with --history_length 4, not --screen_height %d --screen_width %d --history_length %d"
+                             % ((flag,) + geom))
+    return n, tau, log
+
+
+def redo_draw(seed, event, index, layer):
+    """--redo_interval: (the splitmix64 word, the float32 draw) of flat internal index `index` in layer 1..4 at recycle event `event`,
+    restated on the host (csrc/redo.h; no device)"""
+    w, v = C.c_uint64(), C.c_float()
+    _lib.check(_lib.load().sdqn_redo_draw(int(seed) & 0xFFFFFFFFFFFFFFFF, int(event), int(index), int(layer), C.byref(w), C.byref(v)))
+    return w.value, np.float32(v.value)
+
+
+def redo_apply_host(scores, tau, seed, event, num_outputs, theta, state=None, state2=None):
+    """--redo_interval: one recycle event on host arrays in the library's internal layouts (flat float32 buffers of 1 683 456 + 512 x
+    num_outputs values, changed in place; csrc/redo.h, no device).  Returns the four dormant counts."""
+    sc = np.ascontiguousarray(scores, dtype=np.float32).reshape(-1)
+    assert sc.size == sum(REDO_UNITS)
+    n = 1683456 + 512 * int(num_outputs)
+    for b in (theta, state, state2):
+        assert b is None or (b.dtype == np.float32 and b.flags.c_contiguous and b.flags.writeable and b.size == n)
+    counts = np.zeros(4, np.int64)
+    _lib.check(_lib.load().sdqn_redo_apply_host(_lib.ptr(sc, C.c_float), float(tau), int(seed) & 0xFFFFFFFFFFFFFFFF, int(event), int(num_outputs),
+                                                _lib.ptr(theta, C.c_float), None if state is None else _lib.ptr(state, C.c_float),
+                                                None if state2 is None else _lib.ptr(state2, C.c_float), _lib.ptr(counts, C.c_int64)))
+    return counts
+
+
 def check_advantage_learning(args):
     """--advantage_learning alpha / --persistent_advantage: alpha in [0, 1) (0: off), the persistent form only with
     alpha > 0 and one-step targets, and alpha > 0 with none of --double_dqn, --munchausen, --bootstrap_heads K > 1, --batch_norm.  Raises
@@ -246,6 +301,7 @@ class DeepQNetwork:
         cql_alpha = check_cql(args)
         self.noisy_nets, self.noisy_sigma = check_noisy(args)
         random_shift = check_random_shift(args)
+        redo_interval, redo_threshold, self.log_dormant = check_redo(args)
         self.bootstrap_heads, self.bootstrap_mask_probability = check_bootstrap(args, num_actions)
         # quantile-regression DQN: N quantiles per action are a library net with N x num_actions outputs, row j A + a = quantile j, action a
         self.quantiles = check_quantiles(args, num_actions)
@@ -362,6 +418,12 @@ class DeepQNetwork:
         self.random_shift, self.random_shift_seed = 0, int(getattr(args, "random_seed", 0) or 0) & 0xFFFFFFFFFFFFFFFF
         if random_shift:                                       # (off: the library is not told anything)
             self.set_random_shift(random_shift)
+        # dormant-neuron recycling: every redo_interval-th train step ends with one recycle event inside the library
+        self.redo_interval, self.redo_threshold = 0, redo_threshold
+        self.redo_seed = int(getattr(args, "random_seed", 0) or 0) & 0xFFFFFFFFFFFFFFFF
+        self._dormant_logged = None
+        if redo_interval:                                      # (off: the library is not told anything)
+            self.set_redo(redo_interval, redo_threshold)
         self._mt_buf = (C.c_uint32 * _lib.MT_WORDS)()
         self._act_out = C.c_int(); self._act_greedy = self._lib.sdqn_net_act_greedy
         self._env_r, self._env_t = C.c_int(), C.c_int(); self._act_step_env = self._lib.sdqn_net_act_step_env
@@ -506,6 +568,55 @@ class DeepQNetwork:
         _lib.check(self._lib.sdqn_net_last_shifts(self._h, _lib.ptr(out, C.c_int8)))
         return out
 
+    def set_redo(self, interval, threshold=None, seed=None):
+        """--redo_interval / --redo_threshold: interval N > 0 makes every N-th train step of this net end with one recycle event inside the
+        library (units whose score <= threshold get fresh incoming weights and zeroed outgoing ones), 0 switches it off; threshold and seed
+        left None keep their values (--redo_threshold, --random_seed).  Refused on batch_norm, noisy, float64 / other-geometry and
+        multi-rank data-parallel nets."""
+        tau = self.redo_threshold if threshold is None else float(threshold)
+        seed = self.redo_seed if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
+        _lib.check(self._lib.sdqn_net_set_redo(self._h, int(interval), tau, seed))
+        self.redo_interval, self.redo_threshold, self.redo_seed = int(interval), tau, seed
+
+    def redo_now(self):
+        """One recycle event now, from the last train step's activations.  Raises SdqnError before any train step, or once a forward of
+        its own (predict, acting) has overwritten them."""
+        _lib.check(self._lib.sdqn_net_redo_now(self._h))
+
+    def dormant_scores(self):
+        """{"conv1": [32], "conv2": [64], "conv3": [64], "fc4": [512]} float32: every ReLU unit's mean |activation| over the online net's
+        prestate half of the last train step, divided by its layer's mean (0 where the layer is silent).  Recycles nothing; usable with
+        redo_interval 0.  Waits for the device; raises SdqnError where redo_now does."""
+        out = np.empty(sum(REDO_UNITS), np.float32)
+        _lib.check(self._lib.sdqn_net_redo_scores(self._h, _lib.ptr(out, C.c_float)))
+        edges = np.cumsum((0,) + REDO_UNITS)
+        return {name: out[edges[l]:edges[l + 1]].copy() for l, name in enumerate(("conv1", "conv2", "conv3", "fc4"))}
+
+    def dormant_fraction(self, tau=None):
+        """The fraction of each of the four layers' units whose score is <= tau (None: the net's redo_threshold), from dormant_scores()"""
+        tau = self.redo_threshold if tau is None else float(tau)
+        return tuple(float(np.mean(v.astype(np.float64) <= tau)) for v in self.dormant_scores().values())
+
+    def last_redo(self):
+        """{"event": the last recycle event's number (0: none yet), "step": the train step it followed, "dormant": its four counts}, as the
+        device left them.  Waits for the device."""
+        out = np.zeros(6, np.int64)
+        _lib.check(self._lib.sdqn_net_redo_last(self._h, _lib.ptr(out, C.c_int64)))
+        return {"event": int(out[0]), "step": int(out[1]), "dormant": tuple(int(c) for c in out[2:])}
+
+    def _note_trained(self):
+        """What every train entry point ends with.  --log_dormant: the four dormant fractions of the step just enqueued are measured now
+        (two launches and a wait), while its activations are still in place; Statistics writes the last ones of a phase."""
+        if self.log_dormant:
+            self._dormant_logged = self.dormant_fraction()
+
+    def logged_dormant(self):
+        """The four values of the CSV columns dormant_1..4: with --log_dormant the fractions measured after the last train call, else
+        (--redo_interval alone) the last recycle event's dormant counts over the layers' units; zeros before either exists."""
+        if self.log_dormant:
+            return self._dormant_logged or (0.0,) * 4
+        return tuple(c / float(n) for c, n in zip(self.last_redo()["dormant"], REDO_UNITS))
+
     def set_target_tau(self, tau):
         """--target_tau: tau in (0, 1] makes every train step of this net end with one soft target update inside the library; 0: off."""
         _lib.check(self._lib.sdqn_net_set_target_tau(self._h, float(tau)))
@@ -586,6 +697,7 @@ class DeepQNetwork:
             _lib.check(self._lib.sdqn_net_train_host(self._h, pre_p, _lib.ptr(act, C.c_uint8), _lib.ptr(rew, C.c_int64), post_p,
                                                      _lib.ptr(term, C.c_uint8), C.byref(cost) if want else None))
         self.train_iterations += 1                                 # :168
+        self._note_trained()
         if self.callback:
             self.callback.on_train(cost.value)                     # :171-172
 
@@ -880,6 +992,7 @@ class DeepQNetwork:
                 for _ in range(int(n_steps)):
                     _lib.check(self._lib.sdqn_net_train_many(self._h, mem._h, mt, 1, C.byref(cost)))
                     self.train_iterations += 1
+                    self._note_trained()
                     self.callback.on_train(cost.value)
                     total += cost.value
             finally:
@@ -893,6 +1006,7 @@ class DeepQNetwork:
             finally:
                 resync()
             self.train_iterations += 1
+            self._note_trained()
             tk = ticket.value
 
             def collect(tk=tk):
@@ -906,6 +1020,8 @@ class DeepQNetwork:
         finally:
             resync()
         self.train_iterations += n_steps
+        if n_steps:
+            self._note_trained()
         if self.callback and n_steps:
             self.callback.on_train(cost.value)
         return cost.value if want else None
@@ -925,6 +1041,7 @@ class DeepQNetwork:
         cost = C.c_float()
         _lib.check(self._lib.sdqn_net_train_replay(self._h, mem._h, _lib.ptr(idx, C.c_int64), C.byref(cost) if want_cost else None))
         self.train_iterations += 1
+        self._note_trained()
         return cost.value if want_cost else None
 
     def visualize(self, states=None, mem=None, indexes=None, max_fm=4, timing=None):

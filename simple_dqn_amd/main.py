@@ -8,7 +8,7 @@ import sys
 
 # the checks of the options that DeepQNetwork refuses on its own as well: the same functions, refused here before anything touches the device
 from .deepqnetwork import (check_advantage_learning, check_bootstrap, check_cql, check_dueling, check_noisy, check_quantiles,  # noqa: F401
-                           check_random_shift, refuse_conflicts)
+                           check_random_shift, check_redo, refuse_conflicts)
 
 
 def _flag(text):
@@ -60,6 +60,9 @@ _OPTIONS = {
         ("--noisy_nets", _flag, False, dict(help="Noisy networks (Fortunato et al. 2018): factorised Gaussian noise on the two fully connected layers, W = mu + sigma * noise with learned sigma; one noise sample per net per train step, collecting acts under the last step's noise, testing on mu alone. Use with --exploration_rate_start 0 --exploration_rate_end 0.")),
         ("--noisy_sigma", float, 0.5, dict(help="Noisy networks: sigma starts at this value / sqrt(fan_in).")),
         ("--random_shift", int, 0, dict(help="Random-shift augmentation (DrQ, Kostrikov et al. 2020): every sampled state is replicate-padded by this many pixels (0..8) and cropped back at a random offset, prestate and poststate independently (0: off).")),
+        ("--redo_interval", int, 0, dict(help="Dormant-neuron recycling (ReDo, Sokar et al. 2023): after every this many train steps, the ReLU units whose normalised mean activation on the step's minibatch is at most --redo_threshold get fresh incoming weights and zeroed outgoing ones, and their optimizer state is reset (0: off).")),
+        ("--redo_threshold", float, 0.1, dict(help="Dormant-neuron recycling: a unit is dormant when its mean |activation| divided by its layer's mean is at most this, in [0, 1) (0: exactly silent units only).")),
+        ("--log_dormant", _flag, False, dict(help="Measure the dormant fraction of the four ReLU layers after every train call and write it to the CSV columns dormant_1..4 (with --redo_interval alone the columns hold the last recycle event's fractions).")),
         ("--quantiles", int, 1, dict(help="Quantile-regression DQN: this many quantile estimates per action (quantiles x actions <= 18), trained with the quantile Huber loss at threshold --clip_error; acting takes the mean over the quantiles (1: off).")),
         ("--bootstrap_heads", int, 1, dict(help="Bootstrapped DQN: this many Q-heads over one shared torso (heads x actions <= 18); acting follows one head per episode while training, the heads' majority vote while testing (1: off).")),
         ("--bootstrap_mask_probability", float, 1.0, dict(help="Bootstrapped DQN: probability that a Q-head trains on a transition, in (0, 1]; the mask is a fixed function of the replay slot.")),
@@ -222,6 +225,7 @@ def check_offline_file(args, path):
 def run(args):
     train_envs = check_train_envs(args)
     check_random_shift(args)
+    check_redo(args)
     check_noisy(args)
     check_dueling(args)
     check_bootstrap(args)

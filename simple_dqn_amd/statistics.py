@@ -20,6 +20,7 @@ logger = logging.getLogger(__name__)
 COLUMNS = ("epoch", "phase", "steps", "nr_games", "average_reward", "min_game_reward", "max_game_reward",
            "last_exploration_rate", "total_train_steps", "replay_memory_count", "meanq", "meancost",
            "weight_updates", "total_time", "epoch_time", "steps_per_second")
+DORMANT_COLUMNS = ("dormant_1", "dormant_2", "dormant_3", "dormant_4")      # only with --redo_interval / --log_dormant
 
 
 class _PhaseTally:
@@ -50,14 +51,14 @@ class _PhaseTally:
 
 
 class _CsvSink:
-    def __init__(self, path):
+    def __init__(self, path, columns=COLUMNS):
         self.path = path
         self.fh = self.writer = None
         if path:
             logger.info("Results are written to %s" % path)
             self.fh = open(path, "w", newline="")
             self.writer = csv.writer(self.fh)
-            self.row(COLUMNS)
+            self.row(columns)
 
     def row(self, values):
         if self.writer:
@@ -78,7 +79,9 @@ class Statistics:
         self.agent, self.net, self.mem, self.env = agent, net, mem, env
         agent.callback = net.callback = self                            # both producers report here
         self.csv_name = args.csv_file
-        self._csv = _CsvSink(self.csv_name)
+        # the dormancy columns exist only when asked for, so that every other run's CSV keeps its 16-column header
+        self._dormant = bool(getattr(args, "redo_interval", 0) or getattr(args, "log_dormant", False))
+        self._csv = _CsvSink(self.csv_name, COLUMNS + DORMANT_COLUMNS if self._dormant else COLUMNS)
         self.start_time = time.process_time()
         self.validation_states = None
         self.reset()
@@ -159,7 +162,8 @@ class Statistics:
         if self.csv_name:
             self._csv.row((epoch, phase, t.num_steps, t.num_games, t.average_reward, t.min_game_reward, t.max_game_reward,
                            t.last_exploration_rate, self.agent.total_train_steps, self.mem.count, self._mean_max_q(),
-                           t.average_cost, self.net.train_iterations, total_time, epoch_time, rate))
+                           t.average_cost, self.net.train_iterations, total_time, epoch_time, rate)
+                          + (tuple(self.net.logged_dormant()) if self._dormant else ()))
         logger.info("  num_games: %d, average_reward: %f, min_game_reward: %d, max_game_reward: %d" %
                     (t.num_games, t.average_reward, t.min_game_reward, t.max_game_reward))
         logger.info("  last_exploration_rate: %f, epoch_time: %ds, steps_per_second: %d" %

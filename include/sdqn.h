@@ -524,6 +524,31 @@ int sdqn_net_redo_last(sdqn_net_t h, int64_t* out);
 int sdqn_redo_apply_host(const float* scores, double tau, uint64_t seed, uint64_t event, int A, float* theta, float* state, float* state2,
                          int64_t* counts);
 int sdqn_redo_draw(uint64_t seed, uint64_t event, int64_t index, int layer, uint64_t* word, float* value);      /* layer 1..4; either may be NULL */
+/* Periodic resets with shrink-and-perturb, --reset_interval N / --reset_layers L / --shrink_perturb ALPHA (Nikishin et al. 2022, Ash and
+ * Adams 2020, D'Oro et al. 2023; no reference counterpart).  One reset EVENT e = 1, 2, ... walks the flat weight buffers once:
+ * the last L of the five layers conv1, conv2, conv3, fc4, fc5 have factor 0, the others factor ALPHA.  Factor 1: the entry is not written, in
+ * any buffer.  Factor 0: theta[i] = phi_i (the old value is not read).  Otherwise theta[i] = fmaf(a, theta[i], b * phi_i) with a =
+ * (float)ALPHA, b = (float)(1.0 - ALPHA), the product rounded once.  The target net takes the same formula with the same phi_i; the optimizer
+ * state(s) become +0.0 wherever the factor is below 1; the gradient buffer, the replay memory and the step counter are untouched.  phi_i =
+ * (u 2^-23 - 1) sqrt(3 / fan_in) in float, fan_in 256, 512, 576, 3136, 512, u the top 24 bits of one splitmix64 word keyed by (seed, e, flat
+ * internal index) under a domain constant of its own: under one seed it is never the word sdqn_redo_draw gives for the same (e, index)
+ * (sdqn_reset_draw restates it).  The half copies / conv1's bf16 planes of both nets and a dueling net's fc5 mask follow.
+ * sdqn_net_set_reset: interval N > 0: an event follows every applied train step t (sdqn_net_train_iterations) with t % N == 0, behind the
+ * soft target update and the recycle event of sdqn_net_set_redo, on the library stream, inside multi-step calls too, without any wait; 0
+ * (default): nothing runs and nothing is allocated.  SDQN_ERR_ARG: N < 0, L outside 0..5, ALPHA outside [0, 1], N > 0 with L = 0 and ALPHA
+ * = 1 (nothing to do), N > 0 on a batch_norm or noisy net, on the generic path (float64, other geometries) or with data parallel on more
+ * than one rank (sdqn_net_set_noisy and sdqn_dp_init refuse the other way round).  sdqn_net_reset_now: one event now, numbered like the
+ * others, with the L and ALPHA last set.  sdqn_net_reset_last: out [2] = the last event's number (0: none yet) and the train step it
+ * followed, as the device left them; the only call here that waits.  sdqn_reset_apply_host (no device): the same event on host arrays in the
+ * internal layouts, 1 683 456 + 512 A floats each, in place, A = fc5's rows; theta_t NULL or == theta: one net; state may be NULL; state2 is
+ * read for optimizer 1 (adam) and 2 (adadelta) only. */
+int sdqn_net_set_reset(sdqn_net_t h, int interval, int layers, double alpha, uint64_t seed);
+int sdqn_net_get_reset(sdqn_net_t h, int* interval, int* layers, double* alpha, uint64_t* seed);      /* any pointer may be NULL */
+int sdqn_net_reset_now(sdqn_net_t h);
+int sdqn_net_reset_last(sdqn_net_t h, int64_t* out);
+int sdqn_reset_apply_host(int layers, double alpha, uint64_t seed, uint64_t event, int A, int optimizer, float* theta, float* theta_t,
+                          float* state, float* state2);
+int sdqn_reset_draw(uint64_t seed, uint64_t event, int64_t index, int layer, uint64_t* word, float* value);      /* layer 1..5; either may be NULL */
 /* option "double_dqn" (0 default / 1, any configuration, switchable between steps): Double DQN targets (van Hasselt, Guez and Silver
  * 2016): the online net picks each poststate's action, the target net values it (see sdqn_net_last_q).  The online net's forward on
  * the poststates rides as a third net slot in the step's own forward launches (batch_norm: a forward of its own in front of the step,

@@ -173,6 +173,12 @@ SIGNATURES = {
     "sdqn_net_redo_last": (C.c_int, [_vp, _i64p]),
     "sdqn_redo_apply_host": (C.c_int, [_f32p, C.c_double, C.c_uint64, C.c_uint64, C.c_int, _f32p, _f32p, _f32p, _i64p]),
     "sdqn_redo_draw": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
+    "sdqn_net_set_reset": (C.c_int, [_vp, C.c_int, C.c_int, C.c_double, C.c_uint64]),
+    "sdqn_net_get_reset": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), _f64p, C.POINTER(C.c_uint64)]),
+    "sdqn_net_reset_now": (C.c_int, [_vp]),
+    "sdqn_net_reset_last": (C.c_int, [_vp, _i64p]),
+    "sdqn_reset_apply_host": (C.c_int, [C.c_int, C.c_double, C.c_uint64, C.c_uint64, C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p]),
+    "sdqn_reset_draw": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
     "sdqn_net_sync": (C.c_int, [_vp]),
     "sdqn_net_apply_update": (C.c_int, [_vp, C.c_double]),
     "sdqn_net_grad_to_half": (C.c_int, [_vp, C.POINTER(C.c_uint16), C.c_int64]),

@@ -22,6 +22,7 @@
 #include "noisy.h"
 #include "shift.h"
 #include "redo.h"
+#include "reset.h"
 #include "option_table.h"
 
 using namespace sdqn;
@@ -181,6 +182,11 @@ struct sdqn_net_s {
   // redo_acts_live: slot 0 of a1..a4 holds the online net's prestate activations of the last train step (a forward of its own overwrites them)
   int redo_interval = 0; double redo_tau = 0.1; uint64_t redo_seed = 0; int64_t redo_events = 0; bool redo_acts_live = false;
   double* redo_partial = nullptr; float* redo_scores = nullptr; int64_t* redo_info = nullptr;
+  // --reset_interval (sdqn_net_set_reset; reset.h, sdqn_reset.hip): reset_interval > 0: every applied train step t with
+  // t % reset_interval == 0 is followed by one reset event on the library stream (reset_step_done, behind redo_step_done): the last
+  // reset_layers layers redrawn, the others shrunk by reset_alpha and perturbed, both nets, the optimizer state cleared.  reset_info: the last
+  // event's record {event, step}, allocated by the setter or the first sdqn_net_reset_now.  reset_events: events enqueued = the last one's number
+  int reset_interval = 0, reset_layers = 2; double reset_alpha = 1.0; uint64_t reset_seed = 0; int64_t reset_events = 0; int64_t* reset_info = nullptr;
   int n_step = 1;                          // --n_step (option "n_step"): poststate frame offset of the ring paths, n-step head
   double target_tau = 0.0;                 // --target_tau (sdqn_net_set_target_tau): > 0: every train step is followed by one soft target update
   // --clip_grad_norm (sdqn_net_set_clip_grad_norm): > 0: the flat gradient is scaled to this global L2 norm (of the MEAN
@@ -381,6 +387,9 @@ int check_replay_geometry(const sdqn_net_s* h, const sdqn_replay_s* r);
 // of the interval (sdqn_net_set_noisy and sdqn_dp_init ask redo_on for their side of the refusals)
 int redo_step_done(sdqn_net_s* h);
 inline bool redo_on(const sdqn_net_s* h) { return h->redo_interval > 0; }
+// --reset_interval (sdqn_api_reset.hip): the same hook, one place later — nothing unless the step's number is a multiple of the interval
+int reset_step_done(sdqn_net_s* h);
+inline bool reset_on(const sdqn_net_s* h) { return h->reset_interval > 0; }
 int shift_minibatch(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* didx);   // --random_shift: the launch (the caller has checked shift_P > 0); didx: the step's indexes as the device reads them
 bool act_sum_partials(const float* part, int A, float* q_out);
 const uint8_t* statebuf_window(sdqn_statebuf_s* s);

@@ -815,6 +815,7 @@ extern "C" int sdqn_net_set_noisy(sdqn_net_t h, int on, double sigma0, uint64_t 
   REFUSE_CONFLICTS(h, OPT_NOISY_NETS);
   ARGCHK(!h->comm && !h->grad_only, "noisy_nets cannot be combined with data parallel: sigma's gradient is not exchanged");
   ARGCHK(!redo_on(h), "noisy_nets cannot be combined with redo_interval %d: sigma would have to be recycled too", h->redo_interval);
+  ARGCHK(!reset_on(h), "noisy_nets cannot be combined with reset_interval %d: sigma would have to be reset too", h->reset_interval);
   ARGCHK(sigma0 >= 0.0 && sigma0 < INFINITY, "noisy_sigma %g: must be a finite value >= 0", sigma0);     // (false for a NaN)
   const size_t nf = (size_t)(h->NP - OFF4);
   if (!h->nz_eff[0]) {

@@ -395,7 +395,8 @@ int run_train(sdqn_net_s* h, const StepArgs& a0, const HeadArgs& hd0, const Prep
   h->redo_acts_live = true;
   if (plan.update == UPD_GRAD_ONLY) return SDQN_OK;
   rc = step_blend(h); if (rc) return rc;                                      // --target_tau: one blend behind every APPLIED step
-  return redo_on(h) ? redo_step_done(h) : SDQN_OK;                            // --redo_interval: one recycle event behind every interval-th
+  if (redo_on(h)) { rc = redo_step_done(h); if (rc) return rc; }              // --redo_interval: one recycle event behind every interval-th
+  return reset_on(h) ? reset_step_done(h) : SDQN_OK;                          // --reset_interval: then one reset event behind every interval-th
 }
 // small read-backs: `bytes` of device memory into the pinned scratch h->h_f, waited for
 static int fetch_small(sdqn_net_s* h, const void* src, size_t bytes) {

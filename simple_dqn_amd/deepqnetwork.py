@@ -252,6 +252,61 @@ def redo_apply_host(scores, tau, seed, event, num_outputs, theta, state=None, st
     return counts
 
 
+RESET_LAYER_NAMES = ("conv1", "conv2", "conv3", "fc4", "fc5")
+
+
+def check_reset(args):
+    """--reset_interval N / --reset_layers L / --shrink_perturb ALPHA: N >= 0 (0: off), L in 0..5, ALPHA in [0, 1]; N > 0
+    with something to do (not L = 0 with ALPHA = 1) and with none of --batch_norm, --noisy_nets, --datatype float64 or screens other than
+    84 x 84 x 4 (the generic path).  Raises ValueError naming both flags; touches no device.  Returns (N, L, ALPHA)."""
+    n = getattr(args, "reset_interval", 0)
+    n = 0 if n is None else int(n)
+    layers = getattr(args, "reset_layers", 2)
+    layers = 2 if layers is None else int(layers)
+    alpha = getattr(args, "shrink_perturb", 1.0)
+    alpha = 1.0 if alpha is None else float(alpha)
+    if n < 0:
+        raise ValueError("--reset_interval %d: must be >= 0 (0: off)" % n)
+    if not 0 <= layers <= 5:
+        raise ValueError("--reset_layers %d: must be in 0..5" % layers)
+    if not 0.0 <= alpha <= 1.0:                                # (a NaN fails both comparisons)
+        raise ValueError("--shrink_perturb %g: must be in [0, 1]" % alpha)
+    if n > 0:
+        flag = "--reset_interval %d" % n
+        if layers == 0 and alpha == 1.0:
+            raise ValueError("%s with --reset_layers 0 --shrink_perturb 1 would reset nothing" % flag)
+        if bool(getattr(args, "batch_norm", False)):
+            raise ValueError("%s cannot be combined with --batch_norm: the running statistics would have to be reset too" % flag)
+        if bool(getattr(args, "noisy_nets", False)):
+            raise ValueError("%s cannot be combined with --noisy_nets: sigma would have to be reset too" % flag)
+        if str(getattr(args, "datatype", "float32")) == "float64":
+            raise ValueError("%s cannot be combined with --datatype float64: the generic path has no reset pass" % flag)
+        generic, geom = flag_setting(args, "geometry")
+        if generic:
+            raise ValueError("%s needs 84 x 84 screens with --history_length 4, not --screen_height %d --screen_width %d --history_length %d"
+                             % ((flag,) + geom))
+    return n, layers, alpha
+
+
+def reset_draw(seed, event, index, layer):
+    """--reset_interval: (the splitmix64 word, the float32 draw) of flat internal index `index` in layer 1..5 at reset event `event`,
+    restated on the host (csrc/reset.h; no device)"""
+    w, v = C.c_uint64(), C.c_float()
+    _lib.check(_lib.load().sdqn_reset_draw(int(seed) & 0xFFFFFFFFFFFFFFFF, int(event), int(index), int(layer), C.byref(w), C.byref(v)))
+    return w.value, np.float32(v.value)
+
+
+def reset_apply_host(layers, alpha, seed, event, num_outputs, optimizer, theta, theta_t=None, state=None, state2=None):
+    """--reset_interval: one reset event on host arrays in the library's internal layouts (flat float32 buffers of 1 683 456 + 512 x
+    num_outputs values, changed in place; csrc/reset.h, no device).  theta_t None or theta itself: a net without a target net."""
+    n = 1683456 + 512 * int(num_outputs)
+    for b in (theta, theta_t, state, state2):
+        assert b is None or (b.dtype == np.float32 and b.flags.c_contiguous and b.flags.writeable and b.size == n)
+    p = lambda b: None if b is None else _lib.ptr(b, C.c_float)
+    _lib.check(_lib.load().sdqn_reset_apply_host(int(layers), float(alpha), int(seed) & 0xFFFFFFFFFFFFFFFF, int(event), int(num_outputs),
+                                                 ("rmsprop", "adam", "adadelta").index(optimizer), p(theta), p(theta_t), p(state), p(state2)))
+
+
 def check_advantage_learning(args):
     """--advantage_learning alpha / --persistent_advantage: alpha in [0, 1) (0: off), the persistent form only with
     alpha > 0 and one-step targets, and alpha > 0 with none of --double_dqn, --munchausen, --bootstrap_heads K > 1, --batch_norm.  Raises
@@ -302,6 +357,7 @@ class DeepQNetwork:
         self.noisy_nets, self.noisy_sigma = check_noisy(args)
         random_shift = check_random_shift(args)
         redo_interval, redo_threshold, self.log_dormant = check_redo(args)
+        reset_interval, reset_layers, shrink_perturb = check_reset(args)
         self.bootstrap_heads, self.bootstrap_mask_probability = check_bootstrap(args, num_actions)
         # quantile-regression DQN: N quantiles per action are a library net with N x num_actions outputs, row j A + a = quantile j, action a
         self.quantiles = check_quantiles(args, num_actions)
@@ -424,6 +480,11 @@ class DeepQNetwork:
         self._dormant_logged = None
         if redo_interval:                                      # (off: the library is not told anything)
             self.set_redo(redo_interval, redo_threshold)
+        # periodic resets with shrink-and-perturb: every reset_interval-th train step ends with one reset event inside the library
+        self.reset_interval, self.reset_layers, self.shrink_perturb = 0, reset_layers, shrink_perturb
+        self.reset_seed = int(getattr(args, "random_seed", 0) or 0) & 0xFFFFFFFFFFFFFFFF
+        if reset_interval:                                     # (off: the library is not told anything)
+            self.set_reset(reset_interval, reset_layers, shrink_perturb)
         self._mt_buf = (C.c_uint32 * _lib.MT_WORDS)()
         self._act_out = C.c_int(); self._act_greedy = self._lib.sdqn_net_act_greedy
         self._env_r, self._env_t = C.c_int(), C.c_int(); self._act_step_env = self._lib.sdqn_net_act_step_env
@@ -603,6 +664,34 @@ class DeepQNetwork:
         out = np.zeros(6, np.int64)
         _lib.check(self._lib.sdqn_net_redo_last(self._h, _lib.ptr(out, C.c_int64)))
         return {"event": int(out[0]), "step": int(out[1]), "dormant": tuple(int(c) for c in out[2:])}
+
+    def set_reset(self, interval, layers=None, alpha=None, seed=None):
+        """--reset_interval / --reset_layers / --shrink_perturb: interval N > 0 makes every N-th train step of this net end with one reset
+        event inside the library (the last `layers` of conv1, conv2, conv3, fc4, fc5 redrawn from the initialiser, the others theta <-
+        alpha theta + (1 - alpha) phi, both nets with the same phi, the optimizer state cleared there), 0 switches it off; layers, alpha and
+        seed left None keep their values (--reset_layers, --shrink_perturb, --random_seed).  With interval 0 the values are what reset_now()
+        uses.  Refused on batch_norm, noisy, float64 / other-geometry and multi-rank data-parallel nets."""
+        layers = self.reset_layers if layers is None else int(layers)
+        alpha = self.shrink_perturb if alpha is None else float(alpha)
+        seed = self.reset_seed if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF
+        _lib.check(self._lib.sdqn_net_set_reset(self._h, int(interval), layers, alpha, seed))
+        self.reset_interval, self.reset_layers, self.shrink_perturb, self.reset_seed = int(interval), layers, alpha, seed
+
+    def get_reset(self):
+        """(interval, layers, alpha, seed) as the library holds them"""
+        n, l, a, s = C.c_int(), C.c_int(), C.c_double(), C.c_uint64()
+        _lib.check(self._lib.sdqn_net_get_reset(self._h, C.byref(n), C.byref(l), C.byref(a), C.byref(s)))
+        return n.value, l.value, a.value, s.value
+
+    def reset_now(self):
+        """One reset event now, outside the schedule and numbered like the scheduled ones.  Enqueued; does not wait."""
+        _lib.check(self._lib.sdqn_net_reset_now(self._h))
+
+    def last_reset(self):
+        """(the last reset event's number, 0: none yet; the train step it followed), as the device left them.  Waits for the device."""
+        out = np.zeros(2, np.int64)
+        _lib.check(self._lib.sdqn_net_reset_last(self._h, _lib.ptr(out, C.c_int64)))
+        return int(out[0]), int(out[1])
 
     def _note_trained(self):
         """What every train entry point ends with.  --log_dormant: the four dormant fractions of the step just enqueued are measured now

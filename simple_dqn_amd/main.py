@@ -8,7 +8,7 @@ import sys
 
 # the checks of the options that DeepQNetwork refuses on its own as well: the same functions, refused here before anything touches the device
 from .deepqnetwork import (check_advantage_learning, check_bootstrap, check_cql, check_dueling, check_noisy, check_quantiles,  # noqa: F401
-                           check_random_shift, check_redo, refuse_conflicts)
+                           check_random_shift, check_redo, check_reset, refuse_conflicts)
 
 
 def _flag(text):
@@ -63,6 +63,9 @@ _OPTIONS = {
         ("--redo_interval", int, 0, dict(help="Dormant-neuron recycling (ReDo, Sokar et al. 2023): after every this many train steps, the ReLU units whose normalised mean activation on the step's minibatch is at most --redo_threshold get fresh incoming weights and zeroed outgoing ones, and their optimizer state is reset (0: off).")),
         ("--redo_threshold", float, 0.1, dict(help="Dormant-neuron recycling: a unit is dormant when its mean |activation| divided by its layer's mean is at most this, in [0, 1) (0: exactly silent units only).")),
         ("--log_dormant", _flag, False, dict(help="Measure the dormant fraction of the four ReLU layers after every train call and write it to the CSV columns dormant_1..4 (with --redo_interval alone the columns hold the last recycle event's fractions).")),
+        ("--reset_interval", int, 0, dict(help="Periodic resets against the primacy bias (Nikishin et al. 2022): after every this many train steps the last --reset_layers layers of both nets are re-initialised, the others are shrunk by --shrink_perturb and perturbed, and the optimizer state is cleared there; the replay memory is kept (0: off).")),
+        ("--reset_layers", int, 2, dict(help="Periodic resets: how many of the last layers (of conv1, conv2, conv3, fc4, fc5) are re-initialised in full, 0..5 (default 2: fc4 and fc5).")),
+        ("--shrink_perturb", float, 1.0, dict(help="Periodic resets: the layers that are not re-initialised become ALPHA x weights + (1 - ALPHA) x a fresh draw of the initialiser (Ash & Adams 2020), ALPHA in [0, 1]; 1 (default) keeps them bit for bit, BBF uses 0.5.")),
         ("--quantiles", int, 1, dict(help="Quantile-regression DQN: this many quantile estimates per action (quantiles x actions <= 18), trained with the quantile Huber loss at threshold --clip_error; acting takes the mean over the quantiles (1: off).")),
         ("--bootstrap_heads", int, 1, dict(help="Bootstrapped DQN: this many Q-heads over one shared torso (heads x actions <= 18); acting follows one head per episode while training, the heads' majority vote while testing (1: off).")),
         ("--bootstrap_mask_probability", float, 1.0, dict(help="Bootstrapped DQN: probability that a Q-head trains on a transition, in (0, 1]; the mask is a fixed function of the replay slot.")),
@@ -226,6 +229,7 @@ def run(args):
     train_envs = check_train_envs(args)
     check_random_shift(args)
     check_redo(args)
+    check_reset(args)
     check_noisy(args)
     check_dueling(args)
     check_bootstrap(args)

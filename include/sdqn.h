@@ -549,6 +549,31 @@ int sdqn_net_reset_last(sdqn_net_t h, int64_t* out);
 int sdqn_reset_apply_host(int layers, double alpha, uint64_t seed, uint64_t event, int A, int optimizer, float* theta, float* theta_t,
                           float* state, float* state2);
 int sdqn_reset_draw(uint64_t seed, uint64_t event, int64_t index, int layer, uint64_t* word, float* value);      /* layer 1..5; either may be NULL */
+/* Decoupled weight decay and L2-init regularisation, --weight_decay WD / --l2_init LAMBDA (Loshchilov and Hutter 2019; Kumar, Marklund and Van
+ * Roy 2023; no reference counterpart).  The rule on each of the 1 683 456 + 512 A weights of the online net, after every applied
+ * train step, in front of the soft target update, the recycle event and the reset event:
+ *     v = theta[e];  WD > 0: v = v * kf;  LAMBDA > 0: v = v + cf * (anchor[e] - v);  theta[e] = v
+ * with kf = (float)(1.0 - lr WD), cf = (float)(lr LAMBDA), lr the net's learning_rate, every float operation rounded on its own.  A coefficient
+ * of 0 skips its line.  The optimizer state is not touched; the half copies / conv1's bf16 planes follow in the same launch.  With target_tau
+ * in (0, 1) and a target net ONE launch regularises theta and blends theta- toward the new theta (bit for bit the two launches it replaces).
+ * sdqn_net_set_regularizer: SDQN_ERR_ARG for WD < 0, LAMBDA < 0, lr WD >= 1, lr LAMBDA > 1 (NaN included) and for a coefficient > 0 on a
+ * batch_norm or noisy net, on the generic path (float64, other geometries) or with data parallel on more than one rank (sdqn_net_set_noisy and
+ * sdqn_dp_init refuse the other way round).  When LAMBDA goes from 0 to > 0 the anchor (a device copy of the online weights) is allocated if
+ * need be and taken, in stream order; sdqn_net_anchor_now takes it again (and allocates it on a net that has none); events of
+ * sdqn_net_set_redo / sdqn_net_set_reset do not move it, and it is not part of the weights a caller saves.  Both 0 (default): nothing runs,
+ * nothing is allocated.  sdqn_net_regularize_now: one launch of the rule now with the coefficients set, outside a step, the target net
+ * untouched; sdqn_net_regularize_with: the same with the coefficients given (LAMBDA > 0 needs an anchor).  sdqn_net_get_anchor: layer 0..4 of
+ * the anchor in sdqn_net_get_weights' layout; waits.  sdqn_net_weight_norms: out [10] = per layer conv1..fc5 the fp64 sum of theta^2, then
+ * of (theta - anchor)^2 (NaN without an anchor), reduced in a fixed order: the same weights give the same bits; two launches and a wait, never
+ * part of a step.  sdqn_regularize_apply_host (no device): the rule on n host values in place; anchor is read for LAMBDA > 0 only. */
+int sdqn_net_set_regularizer(sdqn_net_t h, double wd, double lambda);
+int sdqn_net_get_regularizer(sdqn_net_t h, double* wd, double* lambda);      /* either pointer may be NULL */
+int sdqn_net_regularize_now(sdqn_net_t h);
+int sdqn_net_regularize_with(sdqn_net_t h, double wd, double lambda);
+int sdqn_net_anchor_now(sdqn_net_t h);
+int sdqn_net_get_anchor(sdqn_net_t h, int layer, float* buf, int64_t n);
+int sdqn_net_weight_norms(sdqn_net_t h, double* out);
+int sdqn_regularize_apply_host(double wd, double lambda, double lr, int64_t n, float* theta, const float* anchor);
 /* option "double_dqn" (0 default / 1, any configuration, switchable between steps): Double DQN targets (van Hasselt, Guez and Silver
  * 2016): the online net picks each poststate's action, the target net values it (see sdqn_net_last_q).  The online net's forward on
  * the poststates rides as a third net slot in the step's own forward launches (batch_norm: a forward of its own in front of the step,

@@ -179,6 +179,14 @@ SIGNATURES = {
     "sdqn_net_reset_last": (C.c_int, [_vp, _i64p]),
     "sdqn_reset_apply_host": (C.c_int, [C.c_int, C.c_double, C.c_uint64, C.c_uint64, C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p]),
     "sdqn_reset_draw": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int64, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
+    "sdqn_net_set_regularizer": (C.c_int, [_vp, C.c_double, C.c_double]),
+    "sdqn_net_get_regularizer": (C.c_int, [_vp, _f64p, _f64p]),
+    "sdqn_net_regularize_now": (C.c_int, [_vp]),
+    "sdqn_net_regularize_with": (C.c_int, [_vp, C.c_double, C.c_double]),
+    "sdqn_net_anchor_now": (C.c_int, [_vp]),
+    "sdqn_net_get_anchor": (C.c_int, [_vp, C.c_int, _f32p, C.c_int64]),
+    "sdqn_net_weight_norms": (C.c_int, [_vp, _f64p]),
+    "sdqn_regularize_apply_host": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_int64, _f32p, _f32p]),
     "sdqn_net_sync": (C.c_int, [_vp]),
     "sdqn_net_apply_update": (C.c_int, [_vp, C.c_double]),
     "sdqn_net_grad_to_half": (C.c_int, [_vp, C.POINTER(C.c_uint16), C.c_int64]),

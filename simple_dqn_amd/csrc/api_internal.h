@@ -23,6 +23,7 @@
 #include "shift.h"
 #include "redo.h"
 #include "reset.h"
+#include "regularize.h"
 #include "option_table.h"
 
 using namespace sdqn;
@@ -187,6 +188,11 @@ struct sdqn_net_s {
   // reset_layers layers redrawn, the others shrunk by reset_alpha and perturbed, both nets, the optimizer state cleared.  reset_info: the last
   // event's record {event, step}, allocated by the setter or the first sdqn_net_reset_now.  reset_events: events enqueued = the last one's number
   int reset_interval = 0, reset_layers = 2; double reset_alpha = 1.0; uint64_t reset_seed = 0; int64_t reset_events = 0; int64_t* reset_info = nullptr;
+  // --weight_decay / --l2_init (sdqn_net_set_regularizer; regularize.h, sdqn_regularize.hip): either > 0: every applied train step is
+  // followed by one regulariser launch on the online weights, in front of the soft target update (with --target_tau the two are ONE launch:
+  // regularize_step_done).  reg_anchor: [NPW] the weights L2-init pulls toward, allocated and taken when reg_lambda first leaves 0
+  // (sdqn_net_anchor_now takes it again); reg_norms: weight_norms' partials and results, allocated by the first read-out.  Both 0: nothing runs
+  double reg_wd = 0.0, reg_lambda = 0.0; float* reg_anchor = nullptr; double* reg_norms = nullptr;
   int n_step = 1;                          // --n_step (option "n_step"): poststate frame offset of the ring paths, n-step head
   double target_tau = 0.0;                 // --target_tau (sdqn_net_set_target_tau): > 0: every train step is followed by one soft target update
   // --clip_grad_norm (sdqn_net_set_clip_grad_norm): > 0: the flat gradient is scaled to this global L2 norm (of the MEAN
@@ -390,6 +396,10 @@ inline bool redo_on(const sdqn_net_s* h) { return h->redo_interval > 0; }
 // --reset_interval (sdqn_api_reset.hip): the same hook, one place later — nothing unless the step's number is a multiple of the interval
 int reset_step_done(sdqn_net_s* h);
 inline bool reset_on(const sdqn_net_s* h) { return h->reset_interval > 0; }
+// --weight_decay / --l2_init (sdqn_api_regularize.hip): the hook in front of step_blend.  *blended: the launch was the fused form and has
+// done this step's soft target update too (the caller then skips step_blend)
+int regularize_step_done(sdqn_net_s* h, bool* blended);
+inline bool regularizer_on(const sdqn_net_s* h) { return h->reg_wd > 0.0 || h->reg_lambda > 0.0; }
 int shift_minibatch(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* didx);   // --random_shift: the launch (the caller has checked shift_P > 0); didx: the step's indexes as the device reads them
 bool act_sum_partials(const float* part, int A, float* q_out);
 const uint8_t* statebuf_window(sdqn_statebuf_s* s);

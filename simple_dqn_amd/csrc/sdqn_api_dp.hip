@@ -41,6 +41,7 @@ extern "C" int sdqn_dp_init(sdqn_net_t h, const char* rccl_path, const char id[1
   ARGCHK(!h->noisy, "data parallel cannot be combined with noisy_nets: sigma's gradient is not exchanged (DESIGN.md §33)");
   ARGCHK(!(redo_on(h) && nranks > 1), "data parallel with %d ranks cannot be combined with redo_interval %d: the ranks' activations differ (DESIGN.md §37)", nranks, h->redo_interval);
   ARGCHK(!(reset_on(h) && nranks > 1), "data parallel with %d ranks cannot be combined with reset_interval %d: every rank would have to run the same event (DESIGN.md §38)", nranks, h->reset_interval);
+  ARGCHK(!(regularizer_on(h) && nranks > 1), "data parallel with %d ranks cannot be combined with weight_decay %g / l2_init %g: every rank would have to hold the same anchor and run the rule behind the overlapped fc4 update (DESIGN.md §39)", nranks, h->reg_wd, h->reg_lambda);
   int rc = rccl_load(rccl_path); if (rc) return rc;
   Id128 u; memcpy(u.b, id, 128);
   NCCLCHK(g_rccl.CommInitRank(&h->comm, nranks, u, rank));

@@ -481,8 +481,10 @@ extern "C" int sdqn_net_apply_update(sdqn_net_t h, double bsz) {
   t.mask = h->dueling; t.clip = clip_on(h); t.apply_mode = 2; t.divisor = bsz;
   t.ovf = h->half_payload_pending;         // the gradient came back through the half payload: same overflow rule as the RCCL path
   h->half_payload_pending = false;
-  const int rc = run_update_tail(h, make_update_args(h, step_args(h)), t);
-  return rc ? rc : step_blend(h);
+  int rc = run_update_tail(h, make_update_args(h, step_args(h)), t); if (rc) return rc;
+  bool blended = false;                    // an applied step: the regulariser runs wherever step_blend does
+  if (regularizer_on(h)) { rc = regularize_step_done(h, &blended); if (rc) return rc; }
+  return blended ? SDQN_OK : step_blend(h);
 }
 // float16 data parallel without a communicator: the two passes that bracket ncclAllReduce(ncclFloat16) in run_train, callable
 // on their own so that the exchange can be done by the caller (tests: gloo across two processes sharing one GPU).
@@ -816,6 +818,7 @@ extern "C" int sdqn_net_set_noisy(sdqn_net_t h, int on, double sigma0, uint64_t 
   ARGCHK(!h->comm && !h->grad_only, "noisy_nets cannot be combined with data parallel: sigma's gradient is not exchanged");
   ARGCHK(!redo_on(h), "noisy_nets cannot be combined with redo_interval %d: sigma would have to be recycled too", h->redo_interval);
   ARGCHK(!reset_on(h), "noisy_nets cannot be combined with reset_interval %d: sigma would have to be reset too", h->reset_interval);
+  ARGCHK(!regularizer_on(h), "noisy_nets cannot be combined with weight_decay %g / l2_init %g: sigma would have to be regularised too", h->reg_wd, h->reg_lambda);
   ARGCHK(sigma0 >= 0.0 && sigma0 < INFINITY, "noisy_sigma %g: must be a finite value >= 0", sigma0);     // (false for a NaN)
   const size_t nf = (size_t)(h->NP - OFF4);
   if (!h->nz_eff[0]) {

@@ -307,6 +307,49 @@ def reset_apply_host(layers, alpha, seed, event, num_outputs, optimizer, theta, 
                                                  ("rmsprop", "adam", "adadelta").index(optimizer), p(theta), p(theta_t), p(state), p(state2)))
 
 
+def check_regularizer(args):
+    """--weight_decay WD / --l2_init LAMBDA / --log_weight_norms: WD >= 0 and LAMBDA >= 0 (0: off), learning_rate x WD < 1,
+    learning_rate x LAMBDA <= 1, and any of the three with none of --batch_norm, --noisy_nets, --datatype float64 or screens other than
+    84 x 84 x 4 (the generic path).  Raises ValueError naming the flag; touches no device.  Returns (WD, LAMBDA, log_weight_norms)."""
+    wd = getattr(args, "weight_decay", 0.0)
+    wd = 0.0 if wd is None else float(wd)
+    lam = getattr(args, "l2_init", 0.0)
+    lam = 0.0 if lam is None else float(lam)
+    log = bool(getattr(args, "log_weight_norms", False))
+    lr = float(getattr(args, "learning_rate", 0.00025))
+    if not wd >= 0.0:                                         # (a NaN fails every comparison)
+        raise ValueError("--weight_decay %g: must be >= 0 (0: off)" % wd)
+    if not lam >= 0.0:
+        raise ValueError("--l2_init %g: must be >= 0 (0: off)" % lam)
+    if not lr * wd < 1.0:
+        raise ValueError("--weight_decay %g: --learning_rate x --weight_decay = %g must be below 1" % (wd, lr * wd))
+    if not lr * lam <= 1.0:
+        raise ValueError("--l2_init %g: --learning_rate x --l2_init = %g must be at most 1" % (lam, lr * lam))
+    for on, flag in ((wd > 0.0, "--weight_decay %g" % wd), (lam > 0.0, "--l2_init %g" % lam), (log, "--log_weight_norms")):
+        if not on:
+            continue
+        if bool(getattr(args, "batch_norm", False)):
+            raise ValueError("%s cannot be combined with --batch_norm: its block of the flat buffer is not weights" % flag)
+        if bool(getattr(args, "noisy_nets", False)):
+            raise ValueError("%s cannot be combined with --noisy_nets: sigma would have to be regularised too" % flag)
+        if str(getattr(args, "datatype", "float32")) == "float64":
+            raise ValueError("%s cannot be combined with --datatype float64: the generic path has no regulariser pass" % flag)
+        generic, geom = flag_setting(args, "geometry")
+        if generic:
+            raise ValueError("%s needs 84 x 84 screens with --history_length 4, not --screen_height %d --screen_width %d --history_length %d"
+                             % ((flag,) + geom))
+    return wd, lam, log
+
+
+def regularize_apply_host(weight_decay, l2_init, learning_rate, theta, anchor=None):
+    """--weight_decay / --l2_init: the rule on a host array of float32 weights, changed in place (csrc/regularize.h, no device); anchor: the
+    same number of float32 values, read when l2_init > 0 only."""
+    assert theta.dtype == np.float32 and theta.flags.c_contiguous and theta.flags.writeable
+    assert anchor is None or (anchor.dtype == np.float32 and anchor.flags.c_contiguous and anchor.size == theta.size)
+    _lib.check(_lib.load().sdqn_regularize_apply_host(float(weight_decay), float(l2_init), float(learning_rate), int(theta.size),
+                                                      _lib.ptr(theta, C.c_float), None if anchor is None else _lib.ptr(anchor, C.c_float)))
+
+
 def check_advantage_learning(args):
     """--advantage_learning alpha / --persistent_advantage: alpha in [0, 1) (0: off), the persistent form only with
     alpha > 0 and one-step targets, and alpha > 0 with none of --double_dqn, --munchausen, --bootstrap_heads K > 1, --batch_norm.  Raises
@@ -358,6 +401,7 @@ class DeepQNetwork:
         random_shift = check_random_shift(args)
         redo_interval, redo_threshold, self.log_dormant = check_redo(args)
         reset_interval, reset_layers, shrink_perturb = check_reset(args)
+        weight_decay, l2_init, self.log_weight_norms = check_regularizer(args)
         self.bootstrap_heads, self.bootstrap_mask_probability = check_bootstrap(args, num_actions)
         # quantile-regression DQN: N quantiles per action are a library net with N x num_actions outputs, row j A + a = quantile j, action a
         self.quantiles = check_quantiles(args, num_actions)
@@ -499,6 +543,12 @@ class DeepQNetwork:
                 fan_in = shp[0] if i < 3 else shp[1]
                 k = np.sqrt(3.0 / fan_in)
                 self.set_layer(i, rng.uniform(-k, k, size=shp).astype(self._np), which)
+        # decoupled weight decay and L2-init: every train step ends with one regulariser launch inside the library.  Set behind
+        # the initialiser: the anchor of --l2_init is the weights as they are when the coefficient leaves 0
+        self.weight_decay, self.l2_init = 0.0, 0.0
+        self._weight_norms_logged = None
+        if weight_decay or l2_init:                            # (off: the library is not told anything)
+            self.set_regularizer(weight_decay, l2_init)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -692,6 +742,56 @@ class DeepQNetwork:
         out = np.zeros(2, np.int64)
         _lib.check(self._lib.sdqn_net_reset_last(self._h, _lib.ptr(out, C.c_int64)))
         return int(out[0]), int(out[1])
+
+    def set_regularizer(self, weight_decay=None, l2_init=None):
+        """--weight_decay / --l2_init: either > 0 makes every applied train step of this net end with one launch of the rule
+        v <- v (1 - lr WD); v <- v + lr LAMBDA (anchor - v) on the online weights, in front of the soft target update (with --target_tau the
+        same launch blends the target net).  The anchor is taken when l2_init leaves 0 (anchor_now() takes it again).  None keeps a value."""
+        wd = self.weight_decay if weight_decay is None else float(weight_decay)
+        lam = self.l2_init if l2_init is None else float(l2_init)
+        _lib.check(self._lib.sdqn_net_set_regularizer(self._h, wd, lam))
+        self.weight_decay, self.l2_init = wd, lam
+
+    def last_regularizer(self):
+        """(weight_decay, l2_init) as the library holds them"""
+        wd, lam = C.c_double(), C.c_double()
+        _lib.check(self._lib.sdqn_net_get_regularizer(self._h, C.byref(wd), C.byref(lam)))
+        return wd.value, lam.value
+
+    def regularize_now(self, weight_decay=None, l2_init=None):
+        """One launch of the rule now, outside a train step, with the net's coefficients or the ones given (l2_init > 0 needs an anchor).
+        The target net is not touched.  Enqueued; does not wait."""
+        if weight_decay is None and l2_init is None:
+            _lib.check(self._lib.sdqn_net_regularize_now(self._h))
+        else:
+            _lib.check(self._lib.sdqn_net_regularize_with(self._h, float(weight_decay or 0.0), float(l2_init or 0.0)))
+
+    def anchor_now(self):
+        """The anchor of --l2_init becomes the online weights as they are now (allocated if the net has none yet).  Enqueued."""
+        _lib.check(self._lib.sdqn_net_anchor_now(self._h))
+
+    def get_anchor(self):
+        """The anchor's five layers in the shapes get_weights uses.  Waits for the device."""
+        out = []
+        for layer, shp in enumerate(self._shapes):
+            w = np.empty(shp, np.float32)
+            _lib.check(self._lib.sdqn_net_get_anchor(self._h, layer, _lib.ptr(w, C.c_float), w.size))
+            out.append(w)
+        return out
+
+    def weight_norms(self, squared=False):
+        """(norms, distances): per layer conv1..fc5 the L2 norm of the online weights and their L2 distance from the anchor (nan without one),
+        two float64 arrays of 5; squared=True returns the device's fp64 sums of squares themselves.  Three launches and a wait."""
+        out = np.zeros(10, np.float64)
+        _lib.check(self._lib.sdqn_net_weight_norms(self._h, _lib.ptr(out, C.c_double)))
+        if not squared:
+            out = np.sqrt(out)
+        return out[:5].copy(), out[5:].copy()
+
+    def logged_weight_norms(self):
+        """The ten values of the CSV columns wnorm_1..5 and winit_1..5 (--log_weight_norms), measured now"""
+        norms, dists = self.weight_norms()
+        return tuple(float(x) for x in norms) + tuple(float(x) for x in dists)
 
     def _note_trained(self):
         """What every train entry point ends with.  --log_dormant: the four dormant fractions of the step just enqueued are measured now
@@ -977,7 +1077,13 @@ class DeepQNetwork:
         return self._play(self._lib.sdqn_env_collect, head, n, steps, trace)
 
     def load_weights(self, load_path):                             # :188-189
-        """Own .npz snapshots, or a Neon pickle (the reference's `model.load_params`, best effort: neon_compat.py)."""
+        """Own .npz snapshots, or a Neon pickle (the reference's `model.load_params`, best effort: neon_compat.py).  The anchor of --l2_init is
+        not part of a snapshot: a net that loads weights anchors at what it loaded."""
+        self._load_weights(load_path)
+        if getattr(self, "l2_init", 0.0) > 0.0:
+            self.anchor_now()
+
+    def _load_weights(self, load_path):
         if not str(load_path).endswith(".npz"):
             from .neon_compat import read_neon_pickle
             ws, states, A = read_neon_pickle(load_path)

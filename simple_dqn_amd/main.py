@@ -8,7 +8,7 @@ import sys
 
 # the checks of the options that DeepQNetwork refuses on its own as well: the same functions, refused here before anything touches the device
 from .deepqnetwork import (check_advantage_learning, check_bootstrap, check_cql, check_dueling, check_noisy, check_quantiles,  # noqa: F401
-                           check_random_shift, check_redo, check_reset, refuse_conflicts)
+                           check_random_shift, check_redo, check_regularizer, check_reset, refuse_conflicts)
 
 
 def _flag(text):
@@ -66,6 +66,9 @@ _OPTIONS = {
         ("--reset_interval", int, 0, dict(help="Periodic resets against the primacy bias (Nikishin et al. 2022): after every this many train steps the last --reset_layers layers of both nets are re-initialised, the others are shrunk by --shrink_perturb and perturbed, and the optimizer state is cleared there; the replay memory is kept (0: off).")),
         ("--reset_layers", int, 2, dict(help="Periodic resets: how many of the last layers (of conv1, conv2, conv3, fc4, fc5) are re-initialised in full, 0..5 (default 2: fc4 and fc5).")),
         ("--shrink_perturb", float, 1.0, dict(help="Periodic resets: the layers that are not re-initialised become ALPHA x weights + (1 - ALPHA) x a fresh draw of the initialiser (Ash & Adams 2020), ALPHA in [0, 1]; 1 (default) keeps them bit for bit, BBF uses 0.5.")),
+        ("--weight_decay", float, 0.0, dict(help="Decoupled weight decay (AdamW, Loshchilov & Hutter 2019; BBF and SR-SPR use 0.1): after every train step each weight of the online net is multiplied by 1 - learning_rate x WD, for all three optimizers (0: off).")),
+        ("--l2_init", float, 0.0, dict(help="L2-init regularisation (Kumar, Marklund & Van Roy 2023): after every train step each weight of the online net moves by learning_rate x LAMBDA of the way back toward its value at initialisation (or at --load_weights) (0: off).")),
+        ("--log_weight_norms", _flag, False, dict(help="Measure the L2 norm of each layer's weights and their L2 distance from the --l2_init anchor when a CSV row is written: columns wnorm_1..5 and winit_1..5 (winit is nan without --l2_init).")),
         ("--quantiles", int, 1, dict(help="Quantile-regression DQN: this many quantile estimates per action (quantiles x actions <= 18), trained with the quantile Huber loss at threshold --clip_error; acting takes the mean over the quantiles (1: off).")),
         ("--bootstrap_heads", int, 1, dict(help="Bootstrapped DQN: this many Q-heads over one shared torso (heads x actions <= 18); acting follows one head per episode while training, the heads' majority vote while testing (1: off).")),
         ("--bootstrap_mask_probability", float, 1.0, dict(help="Bootstrapped DQN: probability that a Q-head trains on a transition, in (0, 1]; the mask is a fixed function of the replay slot.")),
@@ -230,6 +233,7 @@ def run(args):
     check_random_shift(args)
     check_redo(args)
     check_reset(args)
+    check_regularizer(args)
     check_noisy(args)
     check_dueling(args)
     check_bootstrap(args)

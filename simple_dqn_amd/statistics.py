@@ -21,6 +21,8 @@ COLUMNS = ("epoch", "phase", "steps", "nr_games", "average_reward", "min_game_re
            "last_exploration_rate", "total_train_steps", "replay_memory_count", "meanq", "meancost",
            "weight_updates", "total_time", "epoch_time", "steps_per_second")
 DORMANT_COLUMNS = ("dormant_1", "dormant_2", "dormant_3", "dormant_4")      # only with --redo_interval / --log_dormant
+# only with --log_weight_norms: the L2 norm of each layer's weights and their L2 distance from the L2-init anchor
+WEIGHT_NORM_COLUMNS = tuple("wnorm_%d" % l for l in range(1, 6)) + tuple("winit_%d" % l for l in range(1, 6))
 
 
 class _PhaseTally:
@@ -81,7 +83,8 @@ class Statistics:
         self.csv_name = args.csv_file
         # the dormancy columns exist only when asked for, so that every other run's CSV keeps its 16-column header
         self._dormant = bool(getattr(args, "redo_interval", 0) or getattr(args, "log_dormant", False))
-        self._csv = _CsvSink(self.csv_name, COLUMNS + DORMANT_COLUMNS if self._dormant else COLUMNS)
+        self._weight_norms = bool(getattr(args, "log_weight_norms", False))
+        self._csv = _CsvSink(self.csv_name, COLUMNS + (DORMANT_COLUMNS if self._dormant else ()) + (WEIGHT_NORM_COLUMNS if self._weight_norms else ()))
         self.start_time = time.process_time()
         self.validation_states = None
         self.reset()
@@ -163,7 +166,8 @@ class Statistics:
             self._csv.row((epoch, phase, t.num_steps, t.num_games, t.average_reward, t.min_game_reward, t.max_game_reward,
                            t.last_exploration_rate, self.agent.total_train_steps, self.mem.count, self._mean_max_q(),
                            t.average_cost, self.net.train_iterations, total_time, epoch_time, rate)
-                          + (tuple(self.net.logged_dormant()) if self._dormant else ()))
+                          + (tuple(self.net.logged_dormant()) if self._dormant else ())
+                          + (tuple(self.net.logged_weight_norms()) if self._weight_norms else ()))
         logger.info("  num_games: %d, average_reward: %f, min_game_reward: %d, max_game_reward: %d" %
                     (t.num_games, t.average_reward, t.min_game_reward, t.max_game_reward))
         logger.info("  last_exploration_rate: %f, epoch_time: %ds, steps_per_second: %d" %

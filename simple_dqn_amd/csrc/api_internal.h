@@ -177,20 +177,20 @@ struct sdqn_net_s {
   // the t of the next step's draws; shift_out: [B][2][2] the (dy, dx) the last launch drew, allocated by the setter.  0: nothing changes
   int shift_P = 0; uint64_t shift_seed = 0; int64_t shift_step = 0; int8_t* shift_out = nullptr;
   // --redo_interval (sdqn_net_set_redo; redo.h, sdqn_redo.hip): redo_interval > 0: every applied train step t (train_iterations) with
-  // t % redo_interval == 0 is followed by one recycle event on the library stream (redo_step_done).  redo_partial / redo_scores / redo_info:
+  // t % redo_interval == 0 is followed by one recycle event on the library stream (step_applied).  redo_partial / redo_scores / redo_info:
   // the score reduction's partial sums, the 672 scores and the last event's record {event, step, four dormant counts}, allocated on first use
   // (the setter with interval > 0, or the first sdqn_net_redo_scores).  redo_events: events enqueued = the number of the last one.
   // redo_acts_live: slot 0 of a1..a4 holds the online net's prestate activations of the last train step (a forward of its own overwrites them)
   int redo_interval = 0; double redo_tau = 0.1; uint64_t redo_seed = 0; int64_t redo_events = 0; bool redo_acts_live = false;
   double* redo_partial = nullptr; float* redo_scores = nullptr; int64_t* redo_info = nullptr;
   // --reset_interval (sdqn_net_set_reset; reset.h, sdqn_reset.hip): reset_interval > 0: every applied train step t with
-  // t % reset_interval == 0 is followed by one reset event on the library stream (reset_step_done, behind redo_step_done): the last
+  // t % reset_interval == 0 is followed by one reset event on the library stream (step_applied, behind the recycle event): the last
   // reset_layers layers redrawn, the others shrunk by reset_alpha and perturbed, both nets, the optimizer state cleared.  reset_info: the last
   // event's record {event, step}, allocated by the setter or the first sdqn_net_reset_now.  reset_events: events enqueued = the last one's number
   int reset_interval = 0, reset_layers = 2; double reset_alpha = 1.0; uint64_t reset_seed = 0; int64_t reset_events = 0; int64_t* reset_info = nullptr;
   // --weight_decay / --l2_init (sdqn_net_set_regularizer; regularize.h, sdqn_regularize.hip): either > 0: every applied train step is
   // followed by one regulariser launch on the online weights, in front of the soft target update (with --target_tau the two are ONE launch:
-  // regularize_step_done).  reg_anchor: [NPW] the weights L2-init pulls toward, allocated and taken when reg_lambda first leaves 0
+  // step_applied).  reg_anchor: [NPW] the weights L2-init pulls toward, allocated and taken when reg_lambda first leaves 0
   // (sdqn_net_anchor_now takes it again); reg_norms: weight_norms' partials and results, allocated by the first read-out.  Both 0: nothing runs
   double reg_wd = 0.0, reg_lambda = 0.0; float* reg_anchor = nullptr; double* reg_norms = nullptr;
   int n_step = 1;                          // --n_step (option "n_step"): poststate frame offset of the ring paths, n-step head
@@ -345,7 +345,7 @@ int gen_set(sdqn_net_s* h, int which, int layer, const void* w, int64_t n, bool 
 int gen_get(sdqn_net_s* h, int which, int layer, void* w, int64_t n, bool f64);
 int ensure_slots3(sdqn_net_s* h);                                  // room for a third net slot in a1..a4, slab4, q (first use of --double_dqn / --munchausen / --advantage_learning)
 int target_blend(sdqn_net_s* h, double tau);                       // one soft target update now (tau in (0, 1]; the caller has joined g_comm)
-int step_blend(sdqn_net_s* h);                                     // what every applied train step ends with: the blend of --target_tau, or nothing
+int step_blend(sdqn_net_s* h);                                     // the blend of --target_tau behind an applied train step, or nothing
 int gen_step_done(sdqn_net_s* h);                                  // generic path: a train step was enqueued ([clip + deferred update,] counter, step_blend)
 // the actions a transition may hold (--bootstrap_heads / --quantiles: A is K / N times that; --dueling: one more, the V row)
 inline int game_actions(const sdqn_net_s* h) { return h->dueling ? h->A - 1 : h->A / (h->boot_K * h->quant_N); }
@@ -389,17 +389,20 @@ int predict_forward(sdqn_net_s* h, const uint8_t* states, int rows, const void**
 StepArgs ring_step_args(sdqn_net_s* h, const sdqn_replay_s* r);
 int run_ring_step(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* host_idx, const HeadArgs& hd, const PrepArgs* next = nullptr);
 int check_replay_geometry(const sdqn_net_s* h, const sdqn_replay_s* r);
-// --redo_interval (sdqn_api_redo.hip): what every applied train step of the tuned path ends with — nothing unless the step's number is a multiple
-// of the interval (sdqn_net_set_noisy and sdqn_dp_init ask redo_on for their side of the refusals)
-int redo_step_done(sdqn_net_s* h);
+// What follows an applied train step of the tuned path (sdqn_api_net.hip: step_applied, the one place that knows the order) and its parts:
+// one regulariser launch (fuse: it blends the target net too), one ReDo event, one reset event — each as its *_now entry point runs it
+int step_applied(sdqn_net_s* h, bool interval_events);
+int regularize_launch(sdqn_net_s* h, double wd, double lambda, bool fuse);      // sdqn_api_regularize.hip
+int redo_event(sdqn_net_s* h);                                                  // sdqn_api_redo.hip
+int reset_event(sdqn_net_s* h);                                                 // sdqn_api_reset.hip
 inline bool redo_on(const sdqn_net_s* h) { return h->redo_interval > 0; }
-// --reset_interval (sdqn_api_reset.hip): the same hook, one place later — nothing unless the step's number is a multiple of the interval
-int reset_step_done(sdqn_net_s* h);
 inline bool reset_on(const sdqn_net_s* h) { return h->reset_interval > 0; }
-// --weight_decay / --l2_init (sdqn_api_regularize.hip): the hook in front of step_blend.  *blended: the launch was the fused form and has
-// done this step's soft target update too (the caller then skips step_blend)
-int regularize_step_done(sdqn_net_s* h, bool* blended);
 inline bool regularizer_on(const sdqn_net_s* h) { return h->reg_wd > 0.0 || h->reg_lambda > 0.0; }
+// theta (net_slot 0) or theta- (1) was written in [first, last) of the flat buffer: what is derived from it is rebuilt on the library stream
+int refresh_derived(sdqn_net_s* h, int net_slot, int64_t first, int64_t last);
+// option_table.h's feature rows against this handle: `flag` of `feature` refuses the net | a feature that is on refuses `property`
+int refuse_feature(const sdqn_net_s* h, int feature, const char* flag);
+int refuse_beside_features(const sdqn_net_s* h, int property, int ranks);
 int shift_minibatch(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* didx);   // --random_shift: the launch (the caller has checked shift_P > 0); didx: the step's indexes as the device reads them
 bool act_sum_partials(const float* part, int A, float* q_out);
 const uint8_t* statebuf_window(sdqn_statebuf_s* s);

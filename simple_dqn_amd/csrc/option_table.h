@@ -78,4 +78,40 @@ inline int option_conflict(int setting, int setting_value, unsigned active_mask,
   return -1;
 }
 
+// ---- the features that move the weights behind an applied step (--redo_interval, --reset_interval, --weight_decay / --l2_init) -----------
+// They refuse properties of the NET, not other options, so they have rows of their own: the label the feature's value prints with (one
+// int, or two doubles), why it cannot run beside each property, its DESIGN section.  feature_refusal words the refusal from the feature's
+// side (its setters and *_now calls), feature_refuses from the property's (sdqn_net_set_noisy, sdqn_dp_init); no reason is written twice.
+enum FeatureId { FEAT_REDO = 0, FEAT_RESET, FEAT_REGULARIZER, FEAT_COUNT };
+enum NetProperty { NET_BATCH_NORM = 0, NET_NOISY_NETS, NET_DATA_PARALLEL, NET_PROPERTIES };
+struct FeatureRow { const char* label; const char* reason[NET_PROPERTIES]; int section; };
+constexpr FeatureRow FEATURES[FEAT_COUNT] = {
+  {"redo_interval %d", {"the stored planes are not what the next layer reads", "sigma would have to be recycled too", "the ranks' activations differ"}, 37},
+  {"reset_interval %d", {"the running statistics would have to be reset too", "sigma would have to be reset too", "every rank would have to run the same event"}, 38},
+  {"weight_decay %g / l2_init %g", {"its block of the flat buffer is not weights", "sigma would have to be regularised too",
+                                    "every rank would have to hold the same anchor and run the rule behind the overlapped fc4 update"}, 39},
+};
+// `flag` (a feature's option or entry point) on a net with these properties (ranks: of its communicator, 1 without one): true and the
+// message in buf when the feature refuses the net
+inline bool feature_refusal(int feature, const char* flag, bool generic, bool batch_norm, bool noisy, int ranks, char* buf, size_t cap) {
+  const char* const* why = FEATURES[feature].reason;
+  if (generic) snprintf(buf, cap, "%s is implemented for the 84x84x4 float32 / float16 configurations (not datatype float64 or other geometries: the generic path)", flag);
+  else if (batch_norm) snprintf(buf, cap, "%s cannot be combined with batch_norm: %s", flag, why[NET_BATCH_NORM]);
+  else if (noisy) snprintf(buf, cap, "%s cannot be combined with noisy_nets: %s", flag, why[NET_NOISY_NETS]);
+  else if (ranks > 1) snprintf(buf, cap, "%s cannot be combined with data parallel on %d ranks: %s", flag, ranks, why[NET_DATA_PARALLEL]);
+  else return false;
+  return true;
+}
+// the reverse question: the net is about to get `property` (NET_NOISY_NETS, or NET_DATA_PARALLEL on `ranks` ranks) while `feature` is on
+// with values v (v[1]: the regulariser's second): true and the message in buf when the feature refuses it
+inline bool feature_refuses(int feature, int property, int ranks, const double* v, char* buf, size_t cap) {
+  if (property == NET_DATA_PARALLEL && ranks <= 1) return false;
+  const FeatureRow& f = FEATURES[feature];
+  char label[96];
+  if (feature == FEAT_REGULARIZER) snprintf(label, sizeof label, f.label, v[0], v[1]); else snprintf(label, sizeof label, f.label, (int)v[0]);
+  if (property == NET_NOISY_NETS) snprintf(buf, cap, "noisy_nets cannot be combined with %s: %s", label, f.reason[property]);
+  else snprintf(buf, cap, "data parallel with %d ranks cannot be combined with %s: %s (DESIGN.md §%d)", ranks, label, f.reason[property], f.section);
+  return true;
+}
+
 }  // namespace sdqn

@@ -39,10 +39,8 @@ extern "C" int sdqn_dp_init(sdqn_net_t h, const char* rccl_path, const char id[1
   if (h->gen) { set_error("data parallel is implemented for the 84x84x4 float32 / float16 configurations"); return SDQN_ERR_STATE; }
   if (h->comm) { set_error("data parallel already initialised"); return SDQN_ERR_STATE; }
   ARGCHK(!h->noisy, "data parallel cannot be combined with noisy_nets: sigma's gradient is not exchanged (DESIGN.md §33)");
-  ARGCHK(!(redo_on(h) && nranks > 1), "data parallel with %d ranks cannot be combined with redo_interval %d: the ranks' activations differ (DESIGN.md §37)", nranks, h->redo_interval);
-  ARGCHK(!(reset_on(h) && nranks > 1), "data parallel with %d ranks cannot be combined with reset_interval %d: every rank would have to run the same event (DESIGN.md §38)", nranks, h->reset_interval);
-  ARGCHK(!(regularizer_on(h) && nranks > 1), "data parallel with %d ranks cannot be combined with weight_decay %g / l2_init %g: every rank would have to hold the same anchor and run the rule behind the overlapped fc4 update (DESIGN.md §39)", nranks, h->reg_wd, h->reg_lambda);
-  int rc = rccl_load(rccl_path); if (rc) return rc;
+  int rc = refuse_beside_features(h, NET_DATA_PARALLEL, nranks); if (rc) return rc;
+  rc = rccl_load(rccl_path); if (rc) return rc;
   Id128 u; memcpy(u.b, id, 128);
   NCCLCHK(g_rccl.CommInitRank(&h->comm, nranks, u, rank));
   h->rank = rank; h->nranks = nranks;
@@ -69,14 +67,7 @@ extern "C" int sdqn_dp_init(sdqn_net_t h, const char* rccl_path, const char id[1
     if (h->theta_t != h->theta) NCCLCHK(g_rccl.Broadcast(h->theta_t, h->theta_t, (size_t)h->NP, 7, 0, h->comm, g_stream));
     NCCLCHK(g_rccl.Broadcast(h->state, h->state, (size_t)h->NP, 7, 0, h->comm, g_stream));
     if (h->state2) NCCLCHK(g_rccl.Broadcast(h->state2, h->state2, (size_t)h->NP, 7, 0, h->comm, g_stream));
-    if (h->w1p[0]) {
-      HIPCHK(launch_w1_planes(h->theta, h->w1p[0], g_stream));
-      if (h->w1p[1] != h->w1p[0]) HIPCHK(launch_w1_planes(h->theta_t, h->w1p[1], g_stream));
-    }
-    if (h->cfg.datatype == 1) {
-      HIPCHK(launch_refresh16(h->theta, h->wh[0], h->wht[0], g_stream));
-      if (h->theta_t != h->theta) HIPCHK(launch_refresh16(h->theta_t, h->wh[1], h->wht[1], g_stream));
-    }
+    for (int zz = 0; zz < (h->theta_t != h->theta ? 2 : 1); ++zz) { rc = refresh_derived(h, zz, 0, h->NPW); if (rc) return rc; }
     HIPCHK(hipStreamSynchronize(g_stream));
     h->spec_pending = false;               // rank 0's parameters replaced ours: a forward enqueued before the sync is not "predict now"
   }

@@ -18,6 +18,20 @@ static int refuse_conflicts(const sdqn_net_s* h, int setting, int value = 0) {
   return SDQN_OK;
 }
 #define REFUSE_CONFLICTS(...) do { int rc_ = refuse_conflicts(__VA_ARGS__); if (rc_) return rc_; } while (0)
+// option_table.h's feature rows (what moves the weights behind a step refuses properties of the net): asked from the feature's side ...
+int refuse_feature(const sdqn_net_s* h, int feature, const char* flag) {
+  char msg[320];
+  ARGCHK(!feature_refusal(feature, flag, h->gen != nullptr, h->bn, h->noisy, h->comm ? h->nranks : 1, msg, sizeof msg), "%s", msg);
+  return SDQN_OK;
+}
+// ... and from the property's: the first feature that is on and refuses it
+int refuse_beside_features(const sdqn_net_s* h, int property, int ranks) {
+  const bool on[FEAT_COUNT] = {redo_on(h), reset_on(h), regularizer_on(h)};
+  const double values[FEAT_COUNT][2] = {{(double)h->redo_interval, 0.0}, {(double)h->reset_interval, 0.0}, {h->reg_wd, h->reg_lambda}};
+  char msg[320];
+  for (int f = 0; f < FEAT_COUNT; ++f) ARGCHK(!(on[f] && feature_refuses(f, property, ranks, values[f], msg, sizeof msg)), "%s", msg);
+  return SDQN_OK;
+}
 // ---- the option table without a device (option_table.h; tests/test_option_table.py) --------------------------------------------------------
 extern "C" const char* sdqn_option_name(int id) { return option_id_ok(id) ? OPTIONS[id].name : nullptr; }
 extern "C" int sdqn_option_conflict(int setting, int other, int setting_value, int other_value, char* msg, int cap) {
@@ -280,21 +294,10 @@ extern "C" int sdqn_net_set_weights(sdqn_net_t h, int which, int layer, const fl
   for (int64_t r = 0; r < rows; ++r) for (int64_t c = 0; c < cols; ++c) tmp[(size_t)neon_to_internal(layer, r, c)] = w[r * cols + c];
   { int rc_ = join_comm(h); if (rc_) return rc_; } HIPCHK(hipStreamSynchronize(g_stream));
   HIPCHK(hipMemcpy(which_buf(h, which) + off, tmp.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-  if (h->dueling && layer == 4 && which <= 1) {  // --dueling: whatever the caller's W5 holds outside the two streams' blocks becomes +0.0
-    HIPCHK(launch_dueling_mask(which_buf(h, which) + OFF5, false, h->A, NFC, g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-  }
-  if (h->cfg.datatype == 1 && which <= 1) {      // fp16 mode: the half copies follow the master weights
-    const int zz = (which == 1 && h->theta_t != h->theta) ? 1 : 0;
-    HIPCHK(launch_refresh16(zz ? h->theta_t : h->theta, h->wh[zz], h->wht[zz], g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-  }
-  if (h->noisy && which <= 1) h->nz_stale = true;    // --noisy_nets: mu changed, the effective buffers are recomposed before their next use
-  if (h->w1p[0] && which <= 1 && layer == 0) {   // conv1's bf16 planes follow W1
-    const int zz = (which == 1 && h->theta_t != h->theta) ? 1 : 0;
-    HIPCHK(launch_w1_planes(zz ? h->theta_t : h->theta, h->w1p[zz], g_stream));
-    HIPCHK(hipStreamSynchronize(g_stream));
-  }
+  if (which > 1) return SDQN_OK;
+  if (h->noisy) h->nz_stale = true;        // --noisy_nets: mu changed, the effective buffers are recomposed before their next use
+  { int rc_ = refresh_derived(h, (which == 1 && h->theta_t != h->theta) ? 1 : 0, off, off + n); if (rc_) return rc_; }
+  HIPCHK(hipStreamSynchronize(g_stream));
   return SDQN_OK;
 }
 extern "C" int sdqn_net_get_weights(sdqn_net_t h, int which, int layer, float* w, int64_t n) {
@@ -418,6 +421,29 @@ int step_blend(sdqn_net_s* h) {
   if (!h->gen) { int rc = join_comm(h); if (rc) return rc; }
   return target_blend(h, h->target_tau);
 }
+// What follows an APPLIED train step of the tuned path, and the only code that knows the order: regulariser -> blend -> ReDo -> reset
+// (DESIGN.md §36).  With --target_tau in (0, 1) and a target net the regulariser's launch blends theta- as well (fuse) and step_blend is
+// skipped; tau = 1 is the hard update's copies (target_blend), not blend1's arithmetic, and stays a launch of its own.
+// interval_events: run_train's steps count toward --redo_interval / --reset_interval.  sdqn_net_apply_update passes false: it is the
+// second half of a step whose number the grad_only half has counted, a caller may apply once, twice or never per such half, and ReDo
+// scores the activations of ONE rank's forward — so no event has ever been scheduled there, and a grad_only + apply_update flow fires none.
+int step_applied(sdqn_net_s* h, bool interval_events) {
+  const bool fuse = regularizer_on(h) && h->target_tau > 0.0 && h->target_tau < 1.0 && h->theta_t != h->theta;
+  int rc = regularizer_on(h) ? regularize_launch(h, h->reg_wd, h->reg_lambda, fuse) : SDQN_OK; if (rc) return rc;
+  if (!fuse) { rc = step_blend(h); if (rc) return rc; }
+  if (!interval_events) return SDQN_OK;
+  if (redo_on(h) && h->train_iterations % h->redo_interval == 0) { rc = redo_event(h); if (rc) return rc; }
+  return reset_on(h) && h->train_iterations % h->reset_interval == 0 ? reset_event(h) : SDQN_OK;
+}
+// theta (net_slot 0) or theta- (1) was written in [first, last) of the flat buffer: fc5's block mask of a dueling net, the float16 copies
+// wh / wht (they hold the OFF5 values in front of fc5), conv1's bf16 planes — each where the range reaches it, on the library stream
+int refresh_derived(sdqn_net_s* h, int net_slot, int64_t first, int64_t last) {
+  float* th = net_slot ? h->theta_t : h->theta;
+  if (h->dueling && last > OFF5) HIPCHK(launch_dueling_mask(th + OFF5, false, h->A, NFC, g_stream));
+  if (h->cfg.datatype == 1 && first < OFF5) HIPCHK(launch_refresh16(th, h->wh[net_slot], h->wht[net_slot], g_stream));
+  if (h->w1p[net_slot] && first < OFF2) HIPCHK(launch_w1_planes(th, h->w1p[net_slot], g_stream));
+  return SDQN_OK;
+}
 // generic path: train_dev has enqueued the step.  With --clip_grad_norm it stopped behind the gradient (GenericNet::set_clip): the two
 // clip launches and the deferred optimizer launch follow here, in the profile's update slot
 int gen_step_done(sdqn_net_s* h) {
@@ -482,9 +508,7 @@ extern "C" int sdqn_net_apply_update(sdqn_net_t h, double bsz) {
   t.ovf = h->half_payload_pending;         // the gradient came back through the half payload: same overflow rule as the RCCL path
   h->half_payload_pending = false;
   int rc = run_update_tail(h, make_update_args(h, step_args(h)), t); if (rc) return rc;
-  bool blended = false;                    // an applied step: the regulariser runs wherever step_blend does
-  if (regularizer_on(h)) { rc = regularize_step_done(h, &blended); if (rc) return rc; }
-  return blended ? SDQN_OK : step_blend(h);
+  return step_applied(h, false);
 }
 // float16 data parallel without a communicator: the two passes that bracket ncclAllReduce(ncclFloat16) in run_train, callable
 // on their own so that the exchange can be done by the caller (tests: gloo across two processes sharing one GPU).
@@ -816,9 +840,7 @@ extern "C" int sdqn_net_set_noisy(sdqn_net_t h, int on, double sigma0, uint64_t 
   ARGCHK(h->cfg.datatype == 0, "noisy_nets cannot be combined with datatype float16");
   REFUSE_CONFLICTS(h, OPT_NOISY_NETS);
   ARGCHK(!h->comm && !h->grad_only, "noisy_nets cannot be combined with data parallel: sigma's gradient is not exchanged");
-  ARGCHK(!redo_on(h), "noisy_nets cannot be combined with redo_interval %d: sigma would have to be recycled too", h->redo_interval);
-  ARGCHK(!reset_on(h), "noisy_nets cannot be combined with reset_interval %d: sigma would have to be reset too", h->reset_interval);
-  ARGCHK(!regularizer_on(h), "noisy_nets cannot be combined with weight_decay %g / l2_init %g: sigma would have to be regularised too", h->reg_wd, h->reg_lambda);
+  { int rc_ = refuse_beside_features(h, NET_NOISY_NETS, 1); if (rc_) return rc_; }
   ARGCHK(sigma0 >= 0.0 && sigma0 < INFINITY, "noisy_sigma %g: must be a finite value >= 0", sigma0);     // (false for a NaN)
   const size_t nf = (size_t)(h->NP - OFF4);
   if (!h->nz_eff[0]) {

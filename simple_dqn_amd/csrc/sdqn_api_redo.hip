@@ -2,7 +2,7 @@
 //   scores   two launches (partial sums, scores) over slot 0 of a1..a4 (h_a1..h_a3 on a float16 net): the online net's prestate activations
 //            as the last train step left them
 //   event    scores, then one apply launch on theta / state / state2 and the event's record, then the derived copies of the online weights
-//            that sdqn_net_set_weights(which = 0) would have rebuilt: wh / wht (float16) or conv1's bf16 planes (float32)
+//            in front of fc5 (refresh_derived)
 // Everything is enqueued on the library stream; nothing here waits for the device but the two read-outs.
 #include "api_internal.h"
 
@@ -11,14 +11,6 @@ static int redo_buffers(sdqn_net_s* h) {
   int rc = dalloc(h, (void**)&h->redo_partial, (size_t)redo_partial_doubles(h->B) * 8); if (rc) return rc;
   rc = dalloc(h, (void**)&h->redo_scores, (size_t)REDO_UNITS * 4); if (rc) return rc;
   return dalloc(h, (void**)&h->redo_info, 6 * 8);
-}
-// what the feature cannot run on, in the words both sides of each refusal use (sdqn_net_set_noisy, sdqn_dp_init)
-static int redo_refusals(const sdqn_net_s* h, const char* flag) {
-  ARGCHK(!h->gen, "%s is implemented for the 84x84x4 float32 / float16 configurations (not datatype float64 or other geometries: the generic path)", flag);
-  ARGCHK(!h->bn, "%s cannot be combined with batch_norm: the stored planes are not what the next layer reads", flag);
-  ARGCHK(!h->noisy, "%s cannot be combined with noisy_nets: sigma would have to be recycled too", flag);
-  ARGCHK(!(h->comm && h->nranks > 1), "%s cannot be combined with data parallel on %d ranks: the ranks' activations differ", flag, h->nranks);
-  return SDQN_OK;
 }
 static int redo_scores_enqueue(sdqn_net_s* h) {
   ARGCHK(h->train_iterations > 0, "no train step has run: there are no activations to score");
@@ -33,7 +25,7 @@ static int redo_scores_enqueue(sdqn_net_s* h) {
   LAUNCH(K_UPDATE, launch_redo_scores(s, 1, g_stream));
   return SDQN_OK;
 }
-static int redo_event(sdqn_net_s* h) {
+int redo_event(sdqn_net_s* h) {
   { int rc = join_comm(h); if (rc) return rc; }            // (a single rank's overlapped form may still be applying fc4 on the side stream)
   int rc = redo_scores_enqueue(h); if (rc) return rc;
   RedoApplyArgs a; memset(&a, 0, sizeof a);
@@ -42,13 +34,7 @@ static int redo_event(sdqn_net_s* h) {
   LAUNCH(K_UPDATE, launch_redo_apply(a, g_stream));
   h->redo_events += 1;
   h->spec_pending = false;                 // the online parameters moved under a speculative acting forward
-  if (h->cfg.datatype == 1) HIPCHK(launch_refresh16(h->theta, h->wh[0], h->wht[0], g_stream));
-  if (h->w1p[0]) HIPCHK(launch_w1_planes(h->theta, h->w1p[0], g_stream));
-  return SDQN_OK;
-}
-int redo_step_done(sdqn_net_s* h) {
-  if (!redo_on(h) || h->train_iterations % h->redo_interval != 0) return SDQN_OK;
-  return redo_event(h);
+  return refresh_derived(h, 0, 0, OFF5);   // (fc5 gets +0.0 only: its mask has nothing to do)
 }
 
 extern "C" int sdqn_net_set_redo(sdqn_net_t h, int interval, double tau, uint64_t seed) {
@@ -56,7 +42,7 @@ extern "C" int sdqn_net_set_redo(sdqn_net_t h, int interval, double tau, uint64_
   ARGCHK(interval >= 0, "redo_interval %d: must be >= 0 (0: off)", interval);
   ARGCHK(tau >= 0.0 && tau < 1.0, "redo_threshold %g: must be in [0, 1)", tau);      // (false for a NaN)
   if (interval > 0) {
-    int rc = redo_refusals(h, "redo_interval"); if (rc) return rc;
+    int rc = refuse_feature(h, FEAT_REDO, "redo_interval"); if (rc) return rc;
     rc = redo_buffers(h); if (rc) return rc;
   }
   h->redo_interval = interval; h->redo_tau = tau; h->redo_seed = seed;
@@ -69,12 +55,12 @@ extern "C" int sdqn_net_get_redo(sdqn_net_t h, int* interval, double* tau, uint6
 }
 extern "C" int sdqn_net_redo_now(sdqn_net_t h) {
   ARGCHK(h, "NULL handle");
-  int rc = redo_refusals(h, "redo_now"); if (rc) return rc;
+  int rc = refuse_feature(h, FEAT_REDO, "redo_now"); if (rc) return rc;
   return redo_event(h);
 }
 extern "C" int sdqn_net_redo_scores(sdqn_net_t h, float* out) {
   ARGCHK(h && out, "NULL argument");
-  int rc = redo_refusals(h, "redo_scores"); if (rc) return rc;
+  int rc = refuse_feature(h, FEAT_REDO, "redo_scores"); if (rc) return rc;
   rc = redo_scores_enqueue(h); if (rc) return rc;
   HIPCHK(hipMemcpyAsync(out, h->redo_scores, (size_t)REDO_UNITS * 4, hipMemcpyDeviceToHost, g_stream));
   HIPCHK(hipStreamSynchronize(g_stream));

@@ -1,20 +1,12 @@
 // sdqn_api_regularize.hip — decoupled weight decay and L2-init regularisation (--weight_decay, --l2_init): the host side.  The rule
 // is regularize.h's, the kernels sdqn_regularize.hip's.
-//   step     regularize_step_done, in front of step_blend: one launch on the online weights and their derived copies; with --target_tau in (0, 1)
-//            and a target net the SAME launch blends theta- and writes the target's derived copies (the caller skips step_blend)
+//   step     regularize_launch from step_applied: one launch on the online weights and their derived copies; with --target_tau in (0, 1)
+//            and a target net the SAME launch blends theta- and writes the target's derived copies (fuse)
 //   now      the same launch outside a step, never fused
 //   norms    the read-out: two launches and one 80-byte copy, waited for
 // Everything is enqueued on the library stream; nothing here waits for the device but the read-outs.
 #include "api_internal.h"
 
-// what the feature cannot run on, in the words both sides of each refusal use (sdqn_net_set_noisy, sdqn_dp_init)
-static int regularize_refusals(const sdqn_net_s* h, const char* flag) {
-  ARGCHK(!h->gen, "%s is implemented for the 84x84x4 float32 / float16 configurations (not datatype float64 or other geometries: the generic path)", flag);
-  ARGCHK(!h->bn, "%s cannot be combined with batch_norm: its block of the flat buffer is not weights", flag);
-  ARGCHK(!h->noisy, "%s cannot be combined with noisy_nets: sigma would have to be regularised too", flag);
-  ARGCHK(!(h->comm && h->nranks > 1), "%s cannot be combined with data parallel on %d ranks: every rank would have to hold the same anchor", flag, h->nranks);
-  return SDQN_OK;
-}
 static int regularize_range_check(double wd, double lambda, double lr) {
   const int e = reg_range_error(wd, lambda, lr);
   ARGCHK(e != 1, "weight_decay %g: must be >= 0 (0: off)", wd);
@@ -31,7 +23,7 @@ static int anchor_take(sdqn_net_s* h) {
   return SDQN_OK;
 }
 // one launch of the rule with (wd, lambda); fuse: blend the target net toward the new weights with h->target_tau in the same launch
-static int regularize_launch(sdqn_net_s* h, double wd, double lambda, bool fuse) {
+int regularize_launch(sdqn_net_s* h, double wd, double lambda, bool fuse) {
   { int rc = join_comm(h); if (rc) return rc; }            // (a single rank's overlapped form may still be applying fc4 on the side stream)
   RegularizeArgs a; memset(&a, 0, sizeof a);
   a.theta = h->theta; a.anchor = h->reg_anchor; a.n = h->NPW; a.rule = reg_rule(wd, lambda, h->cfg.learning_rate);
@@ -46,22 +38,13 @@ static int regularize_launch(sdqn_net_s* h, double wd, double lambda, bool fuse)
   h->spec_pending = false;                 // the online parameters moved under a speculative acting forward
   return SDQN_OK;
 }
-int regularize_step_done(sdqn_net_s* h, bool* blended) {
-  *blended = false;
-  if (!regularizer_on(h)) return SDQN_OK;
-  // tau = 1 is the hard update's copies (target_blend), not blend1's arithmetic: it stays a launch of its own
-  const bool fuse = h->target_tau > 0.0 && h->target_tau < 1.0 && h->theta_t != h->theta;
-  const int rc = regularize_launch(h, h->reg_wd, h->reg_lambda, fuse);
-  if (!rc) *blended = fuse;
-  return rc;
-}
 
 extern "C" int sdqn_net_set_regularizer(sdqn_net_t h, double wd, double lambda) {
   ARGCHK(h, "NULL handle");
   int rc = regularize_range_check(wd, lambda, h->cfg.learning_rate); if (rc) return rc;
-  if (wd > 0.0) { rc = regularize_refusals(h, "weight_decay"); if (rc) return rc; }
+  if (wd > 0.0) { rc = refuse_feature(h, FEAT_REGULARIZER, "weight_decay"); if (rc) return rc; }
   if (lambda > 0.0) {
-    rc = regularize_refusals(h, "l2_init"); if (rc) return rc;
+    rc = refuse_feature(h, FEAT_REGULARIZER, "l2_init"); if (rc) return rc;
     if (!(h->reg_lambda > 0.0)) { rc = anchor_take(h); if (rc) return rc; }      // 0 -> on: the anchor is the weights as they are now
   }
   h->reg_wd = wd; h->reg_lambda = lambda;
@@ -74,7 +57,7 @@ extern "C" int sdqn_net_get_regularizer(sdqn_net_t h, double* wd, double* lambda
 }
 extern "C" int sdqn_net_regularize_with(sdqn_net_t h, double wd, double lambda) {
   ARGCHK(h, "NULL handle");
-  int rc = regularize_refusals(h, "regularize_now"); if (rc) return rc;
+  int rc = refuse_feature(h, FEAT_REGULARIZER, "regularize_now"); if (rc) return rc;
   rc = regularize_range_check(wd, lambda, h->cfg.learning_rate); if (rc) return rc;
   ARGCHK(!(lambda > 0.0) || h->reg_anchor, "l2_init %g: this network has no anchor yet (sdqn_net_set_regularizer with l2_init > 0, or sdqn_net_anchor_now)", lambda);
   if (!(wd > 0.0) && !(lambda > 0.0)) return SDQN_OK;      // both lines skipped: no launch
@@ -86,12 +69,12 @@ extern "C" int sdqn_net_regularize_now(sdqn_net_t h) {
 }
 extern "C" int sdqn_net_anchor_now(sdqn_net_t h) {
   ARGCHK(h, "NULL handle");
-  int rc = regularize_refusals(h, "anchor_now"); if (rc) return rc;
+  int rc = refuse_feature(h, FEAT_REGULARIZER, "anchor_now"); if (rc) return rc;
   return anchor_take(h);
 }
 extern "C" int sdqn_net_get_anchor(sdqn_net_t h, int layer, float* buf, int64_t n) {
   ARGCHK(h && buf, "NULL argument");
-  int rc = regularize_refusals(h, "get_anchor"); if (rc) return rc;
+  int rc = refuse_feature(h, FEAT_REGULARIZER, "get_anchor"); if (rc) return rc;
   ARGCHK(h->reg_anchor, "this network has no anchor (l2_init was never set above 0 and sdqn_net_anchor_now never called)");
   ARGCHK(layer >= 0 && layer < 5, "layer %d: must be in 0..4", layer);
   int64_t rows, cols, off; layer_dims(layer, h->A, rows, cols, off);
@@ -104,7 +87,7 @@ extern "C" int sdqn_net_get_anchor(sdqn_net_t h, int layer, float* buf, int64_t 
 }
 extern "C" int sdqn_net_weight_norms(sdqn_net_t h, double* out) {
   ARGCHK(h && out, "NULL argument");
-  int rc = regularize_refusals(h, "weight_norms"); if (rc) return rc;
+  int rc = refuse_feature(h, FEAT_REGULARIZER, "weight_norms"); if (rc) return rc;
   rc = join_comm(h); if (rc) return rc;
   if (!h->reg_norms) { rc = dalloc(h, (void**)&h->reg_norms, (size_t)REG_NORM_DOUBLES * 8); if (rc) return rc; }
   WeightNormArgs a; a.theta = h->theta; a.anchor = h->reg_anchor; a.n = h->NPW; a.buf = h->reg_norms;

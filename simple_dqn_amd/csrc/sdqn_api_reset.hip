@@ -1,24 +1,16 @@
 // sdqn_api_reset.hip — periodic resets with shrink-and-perturb (--reset_interval): the host side.  The rules are reset.h's, the
 // kernel sdqn_reset.hip's.
-//   event    one apply launch on theta / theta_t / state / state2 and the event's record, then what sdqn_net_set_weights would have redone for
-//            both nets: the fc5 block mask of a dueling net, the half copies wh / wht (float16) or conv1's bf16 planes (float32)
+//   event    one apply launch on theta / theta_t / state / state2 and the event's record, then both nets' derived copies from the first
+//            entry the rule writes (refresh_derived)
 // Everything is enqueued on the library stream; nothing here waits for the device but sdqn_net_reset_last.
 #include "api_internal.h"
 
-// what the feature cannot run on, in the words both sides of each refusal use (sdqn_net_set_noisy, sdqn_dp_init)
-static int reset_refusals(const sdqn_net_s* h, const char* flag) {
-  ARGCHK(!h->gen, "%s is implemented for the 84x84x4 float32 / float16 configurations (not datatype float64 or other geometries: the generic path)", flag);
-  ARGCHK(!h->bn, "%s cannot be combined with batch_norm: the running statistics would have to be reset too", flag);
-  ARGCHK(!h->noisy, "%s cannot be combined with noisy_nets: sigma would have to be reset too", flag);
-  ARGCHK(!(h->comm && h->nranks > 1), "%s cannot be combined with data parallel on %d ranks: every rank would have to run the same event", flag, h->nranks);
-  return SDQN_OK;
-}
 static int reset_rule_check(int layers, double alpha) {
   ARGCHK(layers >= 0 && layers <= RESET_LAYERS, "reset_layers %d: must be in 0..%d", layers, RESET_LAYERS);
   ARGCHK(alpha >= 0.0 && alpha <= 1.0, "shrink_perturb %g: must be in [0, 1]", alpha);      // (false for a NaN)
   return SDQN_OK;
 }
-static int reset_event(sdqn_net_s* h) {
+int reset_event(sdqn_net_s* h) {
   ARGCHK(!reset_noop(h->reset_layers, h->reset_alpha), "reset_layers 0 with shrink_perturb 1 resets nothing");
   { int rc = join_comm(h); if (rc) return rc; }            // (a single rank's overlapped form may still be applying fc4 on the side stream)
   if (!h->reset_info) { int rc = dalloc(h, (void**)&h->reset_info, 2 * 8); if (rc) return rc; }
@@ -30,18 +22,10 @@ static int reset_event(sdqn_net_s* h) {
   LAUNCH(K_UPDATE, launch_reset_apply(a, g_stream));
   h->reset_events += 1;
   h->spec_pending = false;                 // the online parameters moved under a speculative acting forward
-  const int64_t first = reset_first(h->reset_layers, h->reset_alpha);
-  for (int zz = 0; zz < (tgt ? 2 : 1); ++zz) {
-    float* th = zz ? h->theta_t : h->theta;
-    if (h->dueling) HIPCHK(launch_dueling_mask(th + OFF5, false, h->A, NFC, g_stream));      // fc5 is in every event's tail
-    if (h->cfg.datatype == 1 && first < OFF5) HIPCHK(launch_refresh16(th, h->wh[zz], h->wht[zz], g_stream));
-    if (h->w1p[0] && first < OFF2) HIPCHK(launch_w1_planes(th, h->w1p[zz], g_stream));
+  for (int zz = 0; zz < (tgt ? 2 : 1); ++zz) {      // (fc5 is in every event's tail)
+    int rc = refresh_derived(h, zz, reset_first(h->reset_layers, h->reset_alpha), h->NPW); if (rc) return rc;
   }
   return SDQN_OK;
-}
-int reset_step_done(sdqn_net_s* h) {
-  if (!reset_on(h) || h->train_iterations % h->reset_interval != 0) return SDQN_OK;
-  return reset_event(h);
 }
 
 extern "C" int sdqn_net_set_reset(sdqn_net_t h, int interval, int layers, double alpha, uint64_t seed) {
@@ -50,7 +34,7 @@ extern "C" int sdqn_net_set_reset(sdqn_net_t h, int interval, int layers, double
   int rc = reset_rule_check(layers, alpha); if (rc) return rc;
   if (interval > 0) {
     ARGCHK(!reset_noop(layers, alpha), "reset_interval %d with reset_layers 0 and shrink_perturb 1 would reset nothing", interval);
-    rc = reset_refusals(h, "reset_interval"); if (rc) return rc;
+    rc = refuse_feature(h, FEAT_RESET, "reset_interval"); if (rc) return rc;
     if (!h->reset_info) { rc = dalloc(h, (void**)&h->reset_info, 2 * 8); if (rc) return rc; }
   }
   h->reset_interval = interval; h->reset_layers = layers; h->reset_alpha = alpha; h->reset_seed = seed;
@@ -63,7 +47,7 @@ extern "C" int sdqn_net_get_reset(sdqn_net_t h, int* interval, int* layers, doub
 }
 extern "C" int sdqn_net_reset_now(sdqn_net_t h) {
   ARGCHK(h, "NULL handle");
-  int rc = reset_refusals(h, "reset_now"); if (rc) return rc;
+  int rc = refuse_feature(h, FEAT_RESET, "reset_now"); if (rc) return rc;
   return reset_event(h);
 }
 extern "C" int sdqn_net_reset_last(sdqn_net_t h, int64_t* out) {

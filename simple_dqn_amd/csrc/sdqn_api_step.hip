@@ -394,11 +394,7 @@ int run_train(sdqn_net_s* h, const StepArgs& a0, const HeadArgs& hd0, const Prep
   h->spec_pending = false;                 // the online parameters move: a forward enqueued before this step no longer is "predict now"
   h->redo_acts_live = true;
   if (plan.update == UPD_GRAD_ONLY) return SDQN_OK;
-  bool blended = false;                                                       // --weight_decay / --l2_init: the regulariser in front of the blend
-  if (regularizer_on(h)) { rc = regularize_step_done(h, &blended); if (rc) return rc; }      // (with --target_tau ONE launch does both)
-  if (!blended) { rc = step_blend(h); if (rc) return rc; }                    // --target_tau: one blend behind every APPLIED step
-  if (redo_on(h)) { rc = redo_step_done(h); if (rc) return rc; }              // --redo_interval: one recycle event behind every interval-th
-  return reset_on(h) ? reset_step_done(h) : SDQN_OK;                          // --reset_interval: then one reset event behind every interval-th
+  return step_applied(h, true);            // the regulariser, the blend of --target_tau, the interval events
 }
 // small read-backs: `bytes` of device memory into the pinned scratch h->h_f, waited for
 static int fetch_small(sdqn_net_s* h, const void* src, size_t bytes) {

@@ -197,6 +197,22 @@ def random_shift_draw(seed, step, n, s, P):
     return dy.value, dx.value
 
 
+def refuse_net_properties(args, flag, batch_norm, noisy_nets, float64):
+    """What --redo_interval, --reset_interval and --weight_decay / --l2_init (and their read-outs) share: `flag`, as its message prints it,
+    with none of --batch_norm, --noisy_nets, --datatype float64 or screens other than 84 x 84 x 4; the three reasons are the feature's
+    (csrc/option_table.h: FEATURES words the first two for the library).  Raises ValueError; touches no device."""
+    if bool(getattr(args, "batch_norm", False)):
+        raise ValueError("%s cannot be combined with --batch_norm: %s" % (flag, batch_norm))
+    if bool(getattr(args, "noisy_nets", False)):
+        raise ValueError("%s cannot be combined with --noisy_nets: %s" % (flag, noisy_nets))
+    if str(getattr(args, "datatype", "float32")) == "float64":
+        raise ValueError("%s cannot be combined with --datatype float64: %s" % (flag, float64))
+    generic, geom = flag_setting(args, "geometry")
+    if generic:
+        raise ValueError("%s needs 84 x 84 screens with --history_length 4, not --screen_height %d --screen_width %d --history_length %d"
+                         % ((flag,) + geom))
+
+
 REDO_UNITS = (32, 64, 64, 512)                            # ReLU units of conv1, conv2, conv3, fc4 (csrc/redo.h)
 
 
@@ -214,18 +230,9 @@ def check_redo(args):
     if not 0.0 <= tau < 1.0:                                  # (a NaN fails both comparisons)
         raise ValueError("--redo_threshold %g: must be in [0, 1)" % tau)
     for on, flag in ((n > 0, "--redo_interval %d" % n), (log, "--log_dormant")):
-        if not on:
-            continue
-        if bool(getattr(args, "batch_norm", False)):
-            raise ValueError("%s cannot be combined with --batch_norm: the stored planes are not what the next layer reads" % flag)
-        if bool(getattr(args, "noisy_nets", False)):
-            raise ValueError("%s cannot be combined with --noisy_nets: sigma would have to be recycled too" % flag)
-        if str(getattr(args, "datatype", "float32")) == "float64":
-            raise ValueError("%s cannot be combined with --datatype float64: the generic path keeps no activations to score" % flag)
-        generic, geom = flag_setting(args, "geometry")
-        if generic:
-            raise ValueError("%s needs 84 x 84 screens with --history_length 4, not --screen_height %d --screen_width %d --history_length %d"
-                             % ((flag,) + geom))
+        if on:
+            refuse_net_properties(args, flag, "the stored planes are not what the next layer reads", "sigma would have to be recycled too",
+                                  "the generic path keeps no activations to score")
     return n, tau, log
 
 
@@ -275,16 +282,8 @@ def check_reset(args):
         flag = "--reset_interval %d" % n
         if layers == 0 and alpha == 1.0:
             raise ValueError("%s with --reset_layers 0 --shrink_perturb 1 would reset nothing" % flag)
-        if bool(getattr(args, "batch_norm", False)):
-            raise ValueError("%s cannot be combined with --batch_norm: the running statistics would have to be reset too" % flag)
-        if bool(getattr(args, "noisy_nets", False)):
-            raise ValueError("%s cannot be combined with --noisy_nets: sigma would have to be reset too" % flag)
-        if str(getattr(args, "datatype", "float32")) == "float64":
-            raise ValueError("%s cannot be combined with --datatype float64: the generic path has no reset pass" % flag)
-        generic, geom = flag_setting(args, "geometry")
-        if generic:
-            raise ValueError("%s needs 84 x 84 screens with --history_length 4, not --screen_height %d --screen_width %d --history_length %d"
-                             % ((flag,) + geom))
+        refuse_net_properties(args, flag, "the running statistics would have to be reset too", "sigma would have to be reset too",
+                              "the generic path has no reset pass")
     return n, layers, alpha
 
 
@@ -326,18 +325,9 @@ def check_regularizer(args):
     if not lr * lam <= 1.0:
         raise ValueError("--l2_init %g: --learning_rate x --l2_init = %g must be at most 1" % (lam, lr * lam))
     for on, flag in ((wd > 0.0, "--weight_decay %g" % wd), (lam > 0.0, "--l2_init %g" % lam), (log, "--log_weight_norms")):
-        if not on:
-            continue
-        if bool(getattr(args, "batch_norm", False)):
-            raise ValueError("%s cannot be combined with --batch_norm: its block of the flat buffer is not weights" % flag)
-        if bool(getattr(args, "noisy_nets", False)):
-            raise ValueError("%s cannot be combined with --noisy_nets: sigma would have to be regularised too" % flag)
-        if str(getattr(args, "datatype", "float32")) == "float64":
-            raise ValueError("%s cannot be combined with --datatype float64: the generic path has no regulariser pass" % flag)
-        generic, geom = flag_setting(args, "geometry")
-        if generic:
-            raise ValueError("%s needs 84 x 84 screens with --history_length 4, not --screen_height %d --screen_width %d --history_length %d"
-                             % ((flag,) + geom))
+        if on:
+            refuse_net_properties(args, flag, "its block of the flat buffer is not weights", "sigma would have to be regularised too",
+                                  "the generic path has no regulariser pass")
     return wd, lam, log
 
 
@@ -502,7 +492,8 @@ class DeepQNetwork:
         self.cql_alpha = 0.0
         if cql_alpha > 0.0:                                    # (alpha = 0: the library is not told anything)
             self.set_cql(cql_alpha)
-        self.bootstrap_seed = int(getattr(args, "random_seed", 0) or 0) & 0xFFFFFFFFFFFFFFFF
+        seed = int(getattr(args, "random_seed", 0) or 0) & 0xFFFFFFFFFFFFFFFF        # what every seeded option starts from
+        self.bootstrap_seed = self.noisy_seed = self.random_shift_seed = self.redo_seed = self.reset_seed = seed
         self._boot_vote, self._boot_episode = False, 0
         if self.bootstrap_heads > 1:                           # (K = 1: the library is not told anything)
             _lib.check(self._lib.sdqn_net_set_bootstrap(h, self.bootstrap_heads, self.bootstrap_mask_probability, self.bootstrap_seed))
@@ -511,22 +502,19 @@ class DeepQNetwork:
         if self.dueling:                                       # (off: the library is not told anything)
             _lib.check(self._lib.sdqn_net_set_dueling(h, 1))
         # noisy networks: fc4 and fc5 are mu + sigma * noise; the weights (get_weights, the .npz keys) are mu
-        self.noisy_seed = int(getattr(args, "random_seed", 0) or 0) & 0xFFFFFFFFFFFFFFFF
         if self.noisy_nets:                                    # (off: the library is not told anything)
             _lib.check(self._lib.sdqn_net_set_noisy(h, 1, self.noisy_sigma, self.noisy_seed))
         # random-shift augmentation: the train steps that sample from a replay memory read shifted states
-        self.random_shift, self.random_shift_seed = 0, int(getattr(args, "random_seed", 0) or 0) & 0xFFFFFFFFFFFFFFFF
+        self.random_shift = 0
         if random_shift:                                       # (off: the library is not told anything)
             self.set_random_shift(random_shift)
         # dormant-neuron recycling: every redo_interval-th train step ends with one recycle event inside the library
         self.redo_interval, self.redo_threshold = 0, redo_threshold
-        self.redo_seed = int(getattr(args, "random_seed", 0) or 0) & 0xFFFFFFFFFFFFFFFF
         self._dormant_logged = None
         if redo_interval:                                      # (off: the library is not told anything)
             self.set_redo(redo_interval, redo_threshold)
         # periodic resets with shrink-and-perturb: every reset_interval-th train step ends with one reset event inside the library
         self.reset_interval, self.reset_layers, self.shrink_perturb = 0, reset_layers, shrink_perturb
-        self.reset_seed = int(getattr(args, "random_seed", 0) or 0) & 0xFFFFFFFFFFFFFFFF
         if reset_interval:                                     # (off: the library is not told anything)
             self.set_reset(reset_interval, reset_layers, shrink_perturb)
         self._mt_buf = (C.c_uint32 * _lib.MT_WORDS)()

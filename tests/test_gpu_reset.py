@@ -215,6 +215,36 @@ def test_schedule_inside_a_multi_step_call_and_its_place_behind_redo():
             assert np.array_equal(bits(a[l]), bits(b[l])), (which, l)
 
 
+@pytest.mark.parametrize("datatype,optimizer", [("float32", "rmsprop"), ("float16", "adadelta")], ids=["float32", "float16"])
+def test_everything_behind_a_step_equals_the_same_calls_by_hand(datatype, optimizer):
+    """the order behind an applied step — regulariser, soft target update, ReDo, reset — and the derived copies each of them leaves: a net
+    with all four on against one with all off that makes the same calls by hand, on a dueling net with a target net"""
+    wd, lam, tau = 0.1, 0.01, 0.01
+    kw = dict(num_outputs=A + 1, dueling=True, random_seed=9, dormant=True, learning_rate=0.01)
+    P, Q = make_net(datatype, optimizer, **kw), make_net(datatype, optimizer, **kw)
+    P.set_regularizer(wd, lam); P.set_target_tau(tau); P.set_redo(1, 0.1); P.set_reset(1, 2, 1.0)
+    Q.anchor_now(); Q.set_redo(0, 0.1); Q.set_reset(0, 2, 1.0)     # the same rules and seeds, nothing scheduled
+    mem = ring()
+    random.seed(3)
+    P.train_from_memory(mem, 2)
+    random.seed(3)
+    for t in (1, 2):
+        Q.train_from_memory(mem, 1)
+        Q.regularize_now(wd, lam)
+        Q.soft_update_target_network(tau)
+        Q.redo_now()
+        Q.reset_now()
+    assert P.last_redo() == Q.last_redo() and P.last_redo()["event"] == 2 and P.last_redo()["step"] == 2
+    assert P.last_reset() == Q.last_reset() == (2, 2)
+    p, q = snapshot(P), snapshot(Q)
+    assert sorted(p) == ([0, 1, 2] if optimizer == "rmsprop" else [0, 1, 2, 4])
+    for w in sorted(p):
+        assert np.array_equal(bits(p[w]), bits(q[w])), w
+    assert (p[0] != p[1]).any()                                    # (the target net is a net of its own: the blend had something to do)
+    states = random_minibatch(B, A, 5)[0]
+    assert np.array_equal(bits(P.predict(states)), bits(Q.predict(states)))
+
+
 # ---- off means off ------------------------------------------------------------------------------------------------------------------------
 def _profiled_step(net, mem):
     net.profile(True, -1); net.profile_reset()

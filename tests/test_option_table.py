@@ -107,6 +107,28 @@ def test_library_words_are_the_recorded_ones():
     assert {(g["second"], g["first"]) for g in golden} == settable
 
 
+def test_feature_reasons_are_the_library_ones():
+    """--redo_interval, --reset_interval and --weight_decay / --l2_init refuse properties of the net, so they are rows of their own
+    (csrc/option_table.h: FEATURES): the reason deepqnetwork.py gives beside --batch_norm and --noisy_nets is the one in the library's line of
+    the recorded trace (tests/golden/step_trace_events.txt)"""
+    import argparse
+    from simple_dqn_amd import deepqnetwork as D
+    trace = open(os.path.join(HERE, "golden", "step_trace_events.txt")).read().splitlines()
+    cases = ((D.check_redo, dict(redo_interval=5), "redo_interval"), (D.check_reset, dict(reset_interval=5), "reset_interval"),
+             (D.check_regularizer, dict(weight_decay=0.1), "weight_decay"), (D.check_regularizer, dict(l2_init=0.01), "l2_init"))
+    for check, on, flag in cases:
+        for prop in ("batch_norm", "noisy_nets"):
+            try:
+                check(argparse.Namespace(**dict(on, **{prop: True})))
+                said = None
+            except ValueError as e:
+                said = str(e)
+            assert said is not None and said.startswith("--%s " % flag) and " cannot be combined with --%s: " % prop in said, (flag, prop, said)
+            lines = [l for l in trace if l.startswith("  ERROR %s cannot be combined with %s: " % (flag, prop))]
+            assert len(lines) == 1, (flag, prop)
+            assert said.split(": ", 1)[1] == lines[0].split(": ", 1)[1], (flag, prop)
+
+
 def test_symbols_in_signatures_header_and_library():
     import simple_dqn_amd as sd
     from simple_dqn_amd import _lib

@@ -1,6 +1,7 @@
 // step_trace — what the host orchestration of a step sends outward (sdqn_api_step.hip: run_train, predict_forward_tuned; sdqn_api_net.hip:
 // sdqn_net_apply_update), printed one line per launch / event / all-reduce, in order, on the host and without a device.  Links the host-only
-// objects of those two translation units and answers everything they call with the recording stubs below; whatever else they name stays
+// objects of those two translation units (and of the ReDo / reset / regulariser / data-parallel ones where the tree has them as files of
+// their own) and answers everything they call with the recording stubs below; whatever else they name stays
 // unresolved and is never called.  Two trees orchestrate alike iff their outputs are equal: the acceptance check of a refactoring of the
 // step's host side (tests/test_step_trace.py holds the tree to tests/golden/step_trace.txt).  Build and use: tools/step_trace.sh.
 //   step_trace          the thinned grid (the golden): every launch structure and optimizer tail, the other axes off their default one at a
@@ -9,6 +10,9 @@
 //   step_trace --quantiles   the steps of a --quantiles 6 net over 3 actions (18 outputs), every datatype-regime cell that has them, written
 //                       out (neither golden holds them: tests/test_quantile.py reads the head's line)
 //   step_trace --dueling     likewise the steps of a --dueling net over 3 actions (4 outputs), with apply_update's tail (tests/test_dueling.py)
+//   step_trace --events      what follows an applied step — the regulariser, the blend of --target_tau, the ReDo and reset events, the derived
+//                       copies each rebuilds — written out, then every refusal of the three features in both directions
+//                       (tests/golden/step_trace_events.txt; needs sdqn_api_redo / _reset / _regularize / _dp, or whatever holds their code)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -39,7 +43,7 @@ hipStream_t g_stream = (hipStream_t)0x1000, g_side = (hipStream_t)0x2000, g_comm
 hipEvent_t g_ev[5];
 int g_dev = 0;
 std::vector<sdqn_replay_s*> g_replays;
-Rccl g_rccl;
+__attribute__((weak)) Rccl g_rccl;      // (sdqn_api_dp.hip has the definition where --events links it)
 static const char* sname(hipStream_t s) { return s == g_stream ? "main" : s == g_comm ? "comm" : s == g_side ? "side" : "?"; }
 void set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); fprintf(g_out, "  ERROR "); vfprintf(g_out, fmt, ap); fprintf(g_out, "\n"); va_end(ap); }
 
@@ -100,6 +104,34 @@ hipError_t launch_noisy_tail(const NoisyTailArgs& a, hipStream_t s) {
 hipError_t launch_target_blend(TargetBlendArgs a, hipStream_t s) {
   fprintf(g_out, "  %s %2d %-11s tau=%g\n", sname(s), K_TARGET, "blend", (double)a.tau); return hipSuccess;
 }
+// (--events) the launches behind an applied step
+hipError_t launch_redo_scores(const RedoScoreArgs& a, int stage, hipStream_t s) {
+  fprintf(g_out, "  %s %2d %-11s stage=%d a=%s,%s,%s,%s half123=%d B=%d partial=%s scores=%s\n", sname(s), K_UPDATE, "redo_scores", stage, nm(a.a[0]).c_str(), nm(a.a[1]).c_str(),
+         nm(a.a[2]).c_str(), nm(a.a[3]).c_str(), a.half123, a.B, nm(a.partial).c_str(), nm(a.scores).c_str()); return hipSuccess;
+}
+hipError_t launch_redo_apply(const RedoApplyArgs& a, hipStream_t s) {
+  fprintf(g_out, "  %s %2d %-11s scores=%s theta=%s state=%s state2=%s n=%lld tau=%g seed=%llu event=%llu step=%lld info=%s\n", sname(s), K_UPDATE, "redo_apply", nm(a.scores).c_str(),
+         nm(a.theta).c_str(), nm(a.state).c_str(), nm(a.state2).c_str(), (long long)a.n, a.tau, (unsigned long long)a.seed, (unsigned long long)a.event, (long long)a.step, nm(a.info).c_str());
+  return hipSuccess;
+}
+hipError_t launch_reset_apply(const ResetApplyArgs& a, hipStream_t s) {
+  fprintf(g_out, "  %s %2d %-11s theta=%s theta_t=%s state=%s state2=%s n=%lld layers=%d alpha=%g seed=%llu event=%llu step=%lld info=%s\n", sname(s), K_UPDATE, "reset_apply",
+         nm(a.theta).c_str(), nm(a.theta_t).c_str(), nm(a.state).c_str(), nm(a.state2).c_str(), (long long)a.n, a.layers, a.alpha, (unsigned long long)a.seed, (unsigned long long)a.event,
+         (long long)a.step, nm(a.info).c_str());
+  return hipSuccess;
+}
+hipError_t launch_regularize(RegularizeArgs a, hipStream_t s) {
+  fprintf(g_out, "  %s %2d %-11s theta=%s anchor=%s n=%lld kf=%.9g cf=%.9g wd_on=%d l2_on=%d wh=%s wht=%s w1p=%s | theta_t=%s tau=%g wh_t=%s wht_t=%s w1p_t=%s\n", sname(s), K_UPDATE,
+         "regularize", nm(a.theta).c_str(), nm(a.anchor).c_str(), (long long)a.n, (double)a.rule.kf, (double)a.rule.cf, (int)a.rule.wd_on, (int)a.rule.l2_on, nm(a.wh).c_str(),
+         nm(a.wht).c_str(), nm(a.w1p).c_str(), nm(a.theta_t).c_str(), (double)a.tau, nm(a.wh_t).c_str(), nm(a.wht_t).c_str(), nm(a.w1p_t).c_str());
+  return hipSuccess;
+}
+hipError_t launch_refresh16(const float* theta, half_t* wh, half_t* wht, hipStream_t s) {
+  fprintf(g_out, "  %s %2d %-11s theta=%s wh=%s wht=%s\n", sname(s), K_UPDATE, "refresh16", nm(theta).c_str(), nm(wh).c_str(), nm(wht).c_str()); return hipSuccess;
+}
+hipError_t launch_w1_planes(const float* theta, unsigned short* w1p, hipStream_t s) {
+  fprintf(g_out, "  %s %2d %-11s theta=%s w1p=%s\n", sname(s), K_UPDATE, "w1_planes", nm(theta).c_str(), nm(w1p).c_str()); return hipSuccess;
+}
 }  // namespace sdqn
 
 // ---- the HIP runtime entry points the orchestration uses, and the collective library ----------------------------------------------------
@@ -112,6 +144,16 @@ hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) { fprintf(g_out, "  %s   
 hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) { fprintf(g_out, "  %s    wait        %s\n", sname(s), ename(e)); return hipSuccess; }
 hipError_t hipMemcpyAsync(void* dst, const void* src, size_t n, hipMemcpyKind kind, hipStream_t s) {
   fprintf(g_out, "  %s    copy        dst=%s src=%s bytes=%zu kind=%d\n", sname(s), nm(dst).c_str(), nm(src).c_str(), n, (int)kind); return hipSuccess;
+}
+// (--events) dalloc's two calls: a named dummy, one line each
+static const char* const ALLOC_NAMES[] = {"alloc1", "alloc2", "alloc3", "alloc4", "alloc5", "alloc6", "alloc7", "alloc8"};
+static int g_allocs = 0;
+hipError_t hipMalloc(void** p, size_t bytes) {
+  *p = dummy<char>(ALLOC_NAMES[g_allocs < 8 ? g_allocs : 7]); ++g_allocs;
+  fprintf(g_out, "  -       malloc      %s bytes=%zu\n", nm(*p).c_str(), bytes); return hipSuccess;
+}
+hipError_t hipMemsetAsync(void* dst, int value, size_t bytes, hipStream_t s) {
+  fprintf(g_out, "  %s    memset      dst=%s value=%d bytes=%zu\n", sname(s), nm(dst).c_str(), value, bytes); return hipSuccess;
 }
 void** __hipRegisterFatBinary(const void*) { static void* handle; return &handle; }
 void __hipUnregisterFatBinary(void**) {}
@@ -144,7 +186,7 @@ static bool refused(const Cfg& c) {
   return false;
 }
 static void fill(sdqn_net_s* h, const Cfg& c) {
-  g_names.clear();
+  g_names.clear(); g_allocs = 0;
   memset(&h->cfg, 0, sizeof h->cfg);
   h->cfg.batch_size = c.B; h->cfg.num_actions = 4; h->cfg.target_enabled = 1; h->cfg.optimizer = c.adam; h->cfg.datatype = c.dt == 2;
   h->cfg.discount_rate = 0.99; h->cfg.clip_error = 1.0; h->cfg.min_reward = -1.0; h->cfg.max_reward = 1.0; h->cfg.learning_rate = 0.00025;
@@ -259,12 +301,161 @@ static void print_thin(char* text) {
   printf("== steps: the lines each sends out, in order\n%s\n", steps.c_str());
 }
 
+// ---- --events: what follows an applied step, and the refusals of the three features that move the weights there ---------------------------
+// reg: 0 off | 1 weight_decay | 2 weight_decay and l2_init; redo / reset: the interval (0: off); iters: train_iterations in front of the step
+struct Ev { int dt, B, target, dueling, dp, reg; double tau; int redo, reset, layers; double alpha; int64_t iters; };
+static void fill_events(sdqn_net_s* h, const Ev& e) {
+  fill(h, Cfg{e.B, e.dt, 1, e.dp == DP_OVERLAP ? DP_NONE : e.dp, 0, T_STD, 0, 0, 0, O_NONE});
+  NAMED(h->state2);
+  if (e.dt == 2) h->w1p[0] = h->w1p[1] = nullptr;                             // (as sdqn_net_create leaves a float16 net)
+  if (!e.target) { h->cfg.target_enabled = 0; h->theta_t = h->theta; h->w1p[1] = h->w1p[0]; h->wh[1] = h->wh[0]; h->wht[1] = h->wht[0]; }
+  h->dueling = e.dueling != 0;
+  if (e.dp == DP_OVERLAP) { NAMED(h->comm); NAMED(h->comm2); h->nranks = 1; h->rank = 0; h->dp_overlap = true; }      // one rank, the overlapped form
+  h->target_tau = e.tau;
+  if (e.reg) { h->reg_wd = 0.1; if (e.reg == 2) { h->reg_lambda = 0.01; NAMED(h->reg_anchor); } }
+  h->redo_interval = e.redo; h->redo_tau = 0.1; h->redo_seed = 7;
+  h->reset_interval = e.reset; h->reset_layers = e.layers; h->reset_alpha = e.alpha; h->reset_seed = 9;
+  h->train_iterations = e.iters;
+}
+static void header_events(const char* what, const Ev& e) {
+  fprintf(g_out, "%s B=%d %s target_net=%d dueling=%d dp=%s weight_decay=%g l2_init=%g target_tau=%g redo_interval=%d reset_interval=%d reset_layers=%d shrink_perturb=%g train_iterations=%lld\n",
+          what, e.B, e.dt == 0 ? "float32" : "float16", e.target, e.dueling, DP_NAMES[e.dp], e.reg ? 0.1 : 0.0, e.reg == 2 ? 0.01 : 0.0, e.tau, e.redo, e.reset, e.layers, e.alpha,
+          (long long)e.iters);
+}
+static void footer_events(int rc, const sdqn_net_s* h) {
+  footer(rc, h);
+  fprintf(g_out, "  -> redo_events=%lld reset_events=%lld redo_acts_live=%d nz_stale=%d\n", (long long)h->redo_events, (long long)h->reset_events, (int)h->redo_acts_live, (int)h->nz_stale);
+}
+static void train_events(const Ev& e) {
+  sdqn_net_s* h = new sdqn_net_s(); g_h = h;
+  fill_events(h, e);
+  header_events("train", e);
+  h->spec_pending = true;
+  StepArgs a = step_args(h);
+  a.from_ring = 1; a.src = dummy<const uint8_t>("ring"); a.idx = h->d_idx; h->host_idx_cur = g_host_idx;
+  footer_events(run_train(h, a, head_args(h, HEAD_TRAIN), nullptr), h);
+  delete h; g_h = nullptr;
+}
+static void apply_events(const Ev& e) {
+  sdqn_net_s* h = new sdqn_net_s(); g_h = h;
+  fill_events(h, e);
+  header_events("apply_update", e);
+  h->spec_pending = true;
+  footer_events(sdqn_net_apply_update(h, 2.0 * e.B), h);
+  delete h; g_h = nullptr;
+}
+// the features, alone and together; (interval 3, train_iterations 2): due at this step, (3, 3): not due.  reset_first: (layers 2, alpha 1) fc4,
+// between conv2's and fc5's offsets; (1, 1) fc5's; (4, 1) conv2's exactly; (5, .) and alpha < 1: 0
+static Ev feature(int f, int dt, int B, int target, int dueling, int dp) {
+  Ev e{dt, B, target, dueling, dp, 0, 0.0, 0, 0, 2, 1.0, 2};
+  switch (f) {
+    case 0: e.reg = 1; break;
+    case 1: e.reg = 2; break;
+    case 2: e.tau = 0.01; break;
+    case 3: e.tau = 1.0; break;
+    case 4: e.reg = 2; e.tau = 0.01; break;
+    case 5: e.reg = 2; e.tau = 1.0; break;
+    case 6: e.redo = 3; break;
+    case 7: e.redo = 3; e.iters = 3; break;
+    case 8: e.reset = 3; break;
+    case 9: e.reset = 3; e.iters = 3; break;
+    case 10: e.reset = 3; e.layers = 1; break;
+    case 11: e.reset = 3; e.layers = 5; break;
+    case 12: e.reset = 3; e.layers = 4; break;
+    case 13: e.reset = 3; e.layers = 1; e.alpha = 0.5; break;
+    case 14: e.reg = 2; e.tau = 0.01; e.redo = 1; e.reset = 1; break;
+    case 15: e.reg = 2; e.tau = 0.01; e.redo = 3; e.reset = 3; e.iters = 3; break;
+    default: e.reg = 2; e.tau = 1.0; e.redo = 1; e.reset = 1; break;
+  }
+  return e;
+}
+constexpr int EVENT_CASES = 17;
+// a refusal: the call's words (set_error's stub has printed them) and its return value
+enum Bad { BAD_GEN, BAD_BN, BAD_NOISY, BAD_RANKS, BAD_COUNT };
+static const char* BAD_NAMES[] = {"the generic path", "batch_norm", "noisy_nets", "two ranks"};
+static sdqn_net_s* plain_handle() {
+  sdqn_net_s* h = new sdqn_net_s(); g_h = h;
+  fill_events(h, Ev{0, 32, 1, 0, DP_NONE, 0, 0.0, 0, 0, 2, 1.0, 2});
+  h->redo_acts_live = true;
+  return h;
+}
+static sdqn_net_s* bad_handle(int bad) {
+  sdqn_net_s* h = plain_handle();
+  if (bad == BAD_GEN) h->gen = reinterpret_cast<decltype(h->gen)>(SPAN / 2);      // (asked for, never dereferenced)
+  if (bad == BAD_BN) h->bn = true;
+  if (bad == BAD_NOISY) h->noisy = true;
+  if (bad == BAD_RANKS) { NAMED(h->comm); h->nranks = 2; }
+  return h;
+}
+static void drop(sdqn_net_s* h) { h->gen = nullptr; delete h; g_h = nullptr; }
+#define CALL(h, expr) do { fprintf(g_out, "%s\n", #expr); const int rc_ = (expr); fprintf(g_out, "  -> rc=%d redo_interval=%d reset_interval=%d weight_decay=%g l2_init=%g noisy=%d comm=%s\n", rc_, \
+  (h)->redo_interval, (h)->reset_interval, (h)->reg_wd, (h)->reg_lambda, (int)(h)->noisy, nm((h)->comm).c_str()); } while (0)
+static void refusals() {
+  static float fbuf[2048]; static double dbuf[16]; static char id[128];
+  for (int bad = 0; bad < BAD_COUNT; ++bad) {
+    fprintf(g_out, "== on a handle with %s\n", BAD_NAMES[bad]);
+    sdqn_net_s* h = bad_handle(bad);
+    CALL(h, sdqn_net_set_redo(h, 5, 0.1, 7));
+    CALL(h, sdqn_net_redo_now(h));
+    CALL(h, sdqn_net_redo_scores(h, fbuf));
+    CALL(h, sdqn_net_set_reset(h, 5, 2, 1.0, 9));
+    CALL(h, sdqn_net_reset_now(h));
+    CALL(h, sdqn_net_set_regularizer(h, 0.1, 0.0));
+    CALL(h, sdqn_net_set_regularizer(h, 0.0, 0.01));
+    CALL(h, sdqn_net_regularize_now(h));
+    CALL(h, sdqn_net_regularize_with(h, 0.1, 0.01));
+    CALL(h, sdqn_net_anchor_now(h));
+    CALL(h, sdqn_net_get_anchor(h, 0, fbuf, 2048));
+    CALL(h, sdqn_net_weight_norms(h, dbuf));
+    drop(h);
+  }
+  for (int f = 0; f < 5; ++f) {
+    static const char* ON[] = {"redo_interval 5", "reset_interval 5", "weight_decay 0.1", "l2_init 0.01", "weight_decay 0.1 and l2_init 0.01"};
+    fprintf(g_out, "== on a handle with %s\n", ON[f]);
+    for (int call = 0; call < 2; ++call) {
+      sdqn_net_s* h = plain_handle();
+      if (f == 0) h->redo_interval = 5;
+      if (f == 1) h->reset_interval = 5;
+      if (f == 2 || f == 4) h->reg_wd = 0.1;
+      if (f == 3 || f == 4) h->reg_lambda = 0.01;
+      if (call == 0) CALL(h, sdqn_net_set_noisy(h, 1, 0.5, 0));
+      else CALL(h, sdqn_dp_init(h, nullptr, id, 0, 2));
+      drop(h);
+    }
+  }
+  // and what the setters do where nothing refuses them (dalloc's lines, the anchor's copy)
+  fprintf(g_out, "== on a plain handle\n");
+  sdqn_net_s* h = plain_handle();
+  CALL(h, sdqn_net_set_redo(h, 5, 0.1, 7));
+  CALL(h, sdqn_net_set_reset(h, 5, 2, 1.0, 9));
+  CALL(h, sdqn_net_set_regularizer(h, 0.1, 0.01));
+  CALL(h, sdqn_net_anchor_now(h));
+  CALL(h, sdqn_net_regularize_now(h));
+  CALL(h, sdqn_net_regularize_with(h, 0.0, 0.0));
+  h->train_iterations = 4;
+  CALL(h, sdqn_net_redo_now(h));
+  CALL(h, sdqn_net_reset_now(h));
+  CALL(h, sdqn_net_set_reset(h, 0, 0, 1.0, 9));
+  CALL(h, sdqn_net_reset_now(h));
+  drop(h);
+}
+static void events() {
+  for (int dt : {0, 2}) for (int B : {32, 128}) for (int f = 0; f < EVENT_CASES; ++f)
+    if (B == 32 || f == 4 || f == 6 || f == 8 || f == 14 || f == 16) train_events(feature(f, dt, B, 1, 0, DP_NONE));
+  for (int dt : {0, 2}) for (int shape = 1; shape < 4; ++shape) for (int f : {4, 6, 8, 10, 11, 14, 16}) train_events(feature(f, dt, 32, !(shape & 1), shape >> 1, DP_NONE));
+  for (int dt : {0, 2}) train_events(feature(14, dt, 32, 1, 1, DP_GRAD_ONLY));           // a grad_only step applies nothing: nothing follows it
+  for (int f : {1, 4, 6, 8, 14}) train_events(feature(f, 0, 32, 1, 0, DP_OVERLAP));      // join_comm in front of each event
+  train_events(feature(14, 2, 32, 1, 1, DP_OVERLAP));
+  for (int dt : {0, 2}) for (int shape = 0; shape < 4; ++shape) for (int f : {0, 2, 3, 4, 5, 6, 8, 14, 16}) apply_events(feature(f, dt, 32, !(shape & 1), shape >> 1, DP_GRAD_ONLY));
+  refusals();
+}
+
 int main(int argc, char** argv) {
   setvbuf(stdout, nullptr, _IOFBF, 1 << 20);
   const bool full = argc > 1 && !strcmp(argv[1], "--full");
   char* text = nullptr; size_t text_len = 0;
   const bool quantiles = argc > 1 && !strcmp(argv[1], "--quantiles");
-  if (!full && !quantiles && !(argc > 1 && !strcmp(argv[1], "--dueling"))) g_out = open_memstream(&text, &text_len);
+  if (!full && !quantiles && !(argc > 1 && (!strcmp(argv[1], "--dueling") || !strcmp(argv[1], "--events")))) g_out = open_memstream(&text, &text_len);
   g_rccl.AllReduce = ar_stub; g_rccl.GroupStart = group_start; g_rccl.GroupEnd = group_end;
   for (int i = 0; i < 512; ++i) g_host_idx[i] = 1000 + 37 * i;
   if (quantiles) {
@@ -273,6 +464,7 @@ int main(int argc, char** argv) {
     train(Cfg{32, 0, 1, DP_SERIAL, 0, T_STD, 0, 0, 0, O_NONE});
     return 0;
   }
+  if (argc > 1 && !strcmp(argv[1], "--events")) { events(); return 0; }
   if (argc > 1 && !strcmp(argv[1], "--dueling")) {
     g_dueling = true;
     for (int dt : {0, 2}) for (int B : {32, 128}) for (int clip = 0; clip < 2; ++clip) train(Cfg{B, dt, 1, DP_NONE, clip, T_STD, 0, 0, 0, O_NONE});

@@ -54,12 +54,11 @@ struct GenericNet {
   // --munchausen: Munchausen DQN targets; one more forward (target net, prestates) and the soft-value branch of the TD head
   virtual hipError_t set_munchausen(bool on, double alpha, double tau, double clip) = 0;
   virtual bool munchausen_on() const = 0;
-  // --advantage_learning / --persistent_advantage: the same extra forward as --munchausen and the AL / PAL branch of the TD head;
-  // refused (hipErrorInvalidValue) with double_dqn, munchausen and bootstrap heads, and they with it
+  // --advantage_learning / --persistent_advantage: the same extra forward as --munchausen and the AL / PAL branch of the TD head.
+  // These setters allocate and assign: which options combine, and their ranges, is the caller's to refuse (option_table.h; sdqn_api_net.hip)
   virtual hipError_t set_advantage_learning(bool on, double alpha, bool persistent) = 0;
   virtual bool advantage_learning_on() const = 0;
-  // --cql_alpha (cql.h): alpha > 0 arms the CQL branch of the TD head (no forward of its own); refused (hipErrorInvalidValue)
-  // with double_dqn, munchausen, advantage learning, bootstrap heads, quantiles and dueling, and they with it
+  // --cql_alpha (cql.h): alpha > 0 arms the CQL branch of the TD head (no forward of its own)
   virtual hipError_t set_cql(double alpha) = 0;
   // --prioritized_replay (sdqn_per.hip): w != nullptr makes the following train steps weight the taken action's row by w[n] and write the
   // new priority (|delta| + eps)^alpha into newp[n]; nullptr: the standard step

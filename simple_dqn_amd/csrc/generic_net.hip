@@ -16,7 +16,10 @@
 #include "problems.h"          // MetaRec
 #include "launch.h"            // SDQN_LAUNCH: the soft target update has a profile row
 #include "sdqn_clip.h"         // --clip_grad_norm: the two clip launches, float / double
-#include "cql.h"               // --cql_alpha: the CQL branch of the TD head
+#include "td_rule.h"           // the TD head's rules, one header each
+#include "munchausen.h"
+#include "advantage.h"
+#include "cql.h"
 #include <vector>
 #include <algorithm>
 #include <math.h>
@@ -157,125 +160,65 @@ __global__ void __launch_bounds__(256) reduce_slabs_kernel(const T* __restrict__
   }
 }
 
-// --munchausen: lse(q) = v + tau log(sum_a exp((q[a] - v) / tau)), v = max_a q[a]; double, sum in action order
-template <typename T>
-__device__ inline double soft_value(const T* __restrict__ q, int A, double tau) {
-  double v = (double)q[0];
-  for (int a = 1; a < A; ++a) { const double x = (double)q[a]; v = x > v ? x : v; }
-  double s = 0.0;
-  for (int a = 0; a < A; ++a) s += exp(((double)q[a] - v) / tau);
-  return v + tau * log(s);
-}
-
 // ---- TD target, error, cost, clip (deepqnetwork.py:133-159) ----------------------------------------------------------------------
+// One thread per sample.  The arithmetic of every rule lives in its header: td_rule.h (standard, Double DQN, PER),
+// munchausen.h, advantage.h, bootstrap.h, quantile.h, dueling.h, cql.h; this kernel picks the rows and the rule.
+template <typename T> struct GenHead {
+  const T *q_on, *q_tg;                         // [N][A] Q(theta, s), Q(theta-, s')
+  const T *q_sel, *q_mu;                        // --double_dqn: Q(theta, s') or nullptr; --munchausen / --advantage_learning: Q(theta-, s) or nullptr
+  const uint8_t *act, *term; const int64_t* rew;
+  T *dq, *cost_terms, *maxq;
+  T *q_targets, *duel_step;                     // --quantiles: [N][quant.N] targets; --dueling: [2][N] y, delta (either may be nullptr)
+  const float* per_w; float* per_p; double per_alpha, per_eps;     // --prioritized_replay: weights or nullptr, new priorities
+  int N, A, nstep; T clip;
+  double discount, gamma_n, minr, maxr;
+  int munchausen; double mu_alpha, mu_tau, mu_clip;
+  double al_alpha; int al_persistent;           // --advantage_learning: alpha > 0 arms it
+  double cql_alpha;
+  BootArgs boot; QuantArgs quant; DuelArgs duel;
+};
 template <typename T>
-__global__ void head_kernel(const T* __restrict__ q_on, const T* __restrict__ q_tg, const uint8_t* __restrict__ act,
-                            const int64_t* __restrict__ rew, const uint8_t* __restrict__ term, T* __restrict__ dq,
-                            T* __restrict__ cost_terms, T* __restrict__ maxq, int N, int A, double discount, double minr, double maxr, T clip,
-                            const T* __restrict__ q_sel, const float* __restrict__ per_w, float* __restrict__ per_p, double per_alpha, double per_eps,
-                            int nstep, double gamma_n, const T* __restrict__ q_mu, double mu_alpha, double mu_tau, double mu_clip, const BootArgs boot,
-                            double al_alpha, int al_persistent, const QuantArgs quant, T* __restrict__ q_targets, const DuelArgs duel,
-                            T* __restrict__ duel_step, double cql_alpha) {
+__global__ void head_kernel(const GenHead<T> h) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= N) return;
-  if (duel.on) {                                                              // --dueling: dueling.h's rule on this sample's two rows
-    const int GA = duel.A, at = act[n] < GA ? act[n] : GA - 1;
-    double r, gam = discount;
-    if (nstep > 1) { r = __builtin_bit_cast(double, rew[n]); gam = gamma_n; }
-    else { r = (double)rew[n]; r = r < minr ? minr : (r > maxr ? maxr : r); }
-    cost_terms[n] = dueling_sample<T>(q_on + (int64_t)n * A, q_tg + (int64_t)n * A, GA, at, r, term[n], gam, clip, per_w != nullptr,
-                                        per_w ? (T)per_w[n] : (T)1, per_alpha, per_eps, dq + (int64_t)n * A, duel_step ? duel_step + n : nullptr,
-                                        duel_step ? duel_step + N + n : nullptr, maxq + n, per_p ? per_p + n : nullptr);
+  if (n >= h.N) return;
+  const int A = h.A, term = h.term[n], per = h.per_w != nullptr;
+  const int GA = h.duel.on ? h.duel.A : (h.quant.N > 1 ? h.quant.A : (h.boot.K > 1 ? h.boot.A : A));      // the game's actions
+  const int at = h.act[n] < GA ? h.act[n] : GA - 1;                             // memory safety only: the host rejects out-of-range actions before launching
+  double r, gam; td_reward(h.rew[n], h.nstep, h.discount, h.gamma_n, h.minr, h.maxr, &r, &gam);
+  const T* q_on = h.q_on + (int64_t)n * A; const T* q_tg = h.q_tg + (int64_t)n * A;
+  T* dq = h.dq + (int64_t)n * A;
+  const T w = per ? (T)h.per_w[n] : (T)1;                                       // the importance weight of the sample
+  if (h.duel.on) {                                                              // --dueling
+    h.cost_terms[n] = dueling_sample<T>(q_on, q_tg, GA, at, r, term, gam, h.clip, per, w, h.per_alpha, h.per_eps, dq, h.duel_step ? h.duel_step + n : nullptr,
+                                        h.duel_step ? h.duel_step + h.N + n : nullptr, h.maxq + n, h.per_p ? h.per_p + n : nullptr);
     return;
   }
-  if (quant.N > 1) {                                                          // --quantiles: quantile.h's rule on this sample's two rows; clip is kappa
-    const int GA = quant.A, at = act[n] < GA ? act[n] : GA - 1;
-    double r, gam = discount;
-    if (nstep > 1) { r = __builtin_bit_cast(double, rew[n]); gam = gamma_n; }
-    else { r = (double)rew[n]; r = r < minr ? minr : (r > maxr ? maxr : r); }
-    cost_terms[n] = quantile_sample<T>(q_on + (int64_t)n * A, q_tg + (int64_t)n * A, quant.N, GA, at, r, term[n], gam, clip, dq + (int64_t)n * A,
-                                         q_targets ? q_targets + (int64_t)n * quant.N : nullptr, maxq + n);
+  if (h.quant.N > 1) {                                                          // --quantiles; clip is kappa
+    h.cost_terms[n] = quantile_sample<T>(q_on, q_tg, h.quant.N, GA, at, r, term, gam, h.clip, dq, h.q_targets ? h.q_targets + (int64_t)n * h.quant.N : nullptr, h.maxq + n);
     return;
   }
-  if (boot.K > 1) {                                                           // --bootstrap_heads: one target per Q-head, masked, all over K
-    const int K = boot.K, GA = boot.A, at = act[n] < GA ? act[n] : GA - 1;
-    double r, gam = discount;
-    if (nstep > 1) { r = __builtin_bit_cast(double, rew[n]); gam = gamma_n; }
-    else { r = (double)rew[n]; r = r < minr ? minr : (r > maxr ? maxr : r); }
-    const int64_t i = boot.idx ? boot.idx[n] : 0;
-    double msum = 0.0; T cost = (T)0;
-    for (int k = 0; k < K; ++k) {
-      const T* qp = q_tg + (int64_t)n * A + k * GA;
-      T m = qp[0];
-      for (int a = 1; a < GA; ++a) { const T v = qp[a]; m = v > m ? v : m; }
-      msum += (double)m;
-      const double y = term[n] ? r : r + gam * (double)m;
-      const T d = q_on[(int64_t)n * A + k * GA + at] - (T)y;
-      T e = d;
-      if (clip != (T)0) e = e < -clip ? -clip : (e > clip ? clip : e);
-      const int live = bootstrap_mask_bit(boot.mask_seed, boot.thresh, i, k);
-      if (live) cost += (T)0.5 * (d * d);
-      for (int a = 0; a < GA; ++a) dq[(int64_t)n * A + k * GA + a] = (live && a == at) ? e / (T)K : (T)0;
-    }
-    cost_terms[n] = cost / (T)K;
-    maxq[n] = (T)(msum / (double)K);
+  if (h.boot.K > 1) {                                                           // --bootstrap_heads
+    h.cost_terms[n] = bootstrap_sample<T, CompareOps<T>>(q_on, q_tg, h.boot.K, GA, at, r, term, gam, h.clip, h.boot.mask_seed, h.boot.thresh,
+                                                         h.boot.idx ? h.boot.idx[n] : 0, dq, nullptr, h.maxq + n);
     return;
   }
-  T m = q_tg[(int64_t)n * A];
-  double bonus = 0.0, V = 0.0;
-  const bool al = q_mu && al_alpha > 0.0;                                     // --advantage_learning: q_mu is qbar of the prestates, the maximum stays the standard one
-  if (q_mu && !al) {                                                                 // --munchausen: soft value of s', scaled log-policy bonus of (s, a)
-    V = soft_value(q_tg + (int64_t)n * A, A, mu_tau);
-    const double lp = (double)q_mu[(int64_t)n * A + act[n]] - soft_value(q_mu + (int64_t)n * A, A, mu_tau);     // tau ln pi(a|s) <= 0
-    bonus = mu_alpha * (lp < mu_clip ? mu_clip : (lp > 0.0 ? 0.0 : lp));
-    m = (T)V;
-  } else if (q_sel) {                                                                // --double_dqn: target net's Q at the online net's argmax
-    int best = 0; T bv = q_sel[(int64_t)n * A];
-    for (int a = 1; a < A; ++a) { const T v = q_sel[(int64_t)n * A + a]; if (v > bv) { bv = v; best = a; } }   // first maximum
-    m = q_tg[(int64_t)n * A + best];
-  } else
-  for (int a = 1; a < A; ++a) { const T v = q_tg[(int64_t)n * A + a]; m = v > m ? v : m; }     // be.max(postq, axis=0) :124
-  maxq[n] = m;
-  double r, gam = discount;
-  if (nstep > 1) { r = __builtin_bit_cast(double, rew[n]); gam = gamma_n; }   // --n_step: the return R (clipped per step), gamma^n
-  else {
-    r = (double)rew[n];
-    r = r < minr ? minr : (r > maxr ? maxr : r);                              // np.clip(rewards, min_reward, max_reward) :136
+  double y;
+  if (h.munchausen) {                                                           // --munchausen: y from the soft value V, maxq holds V's rounded copy
+    double V; y = munchausen_target<T>(h.q_mu + (int64_t)n * A, q_tg, A, at, r, term, gam, h.mu_alpha, h.mu_tau, h.mu_clip, &V);
+    h.maxq[n] = (T)V;
+  } else {                                                                      // the standard target, Double DQN's with q_sel
+    const T m = td_post_value<T>(q_tg, h.q_sel ? h.q_sel + (int64_t)n * A : nullptr, A);
+    h.maxq[n] = m;
+    y = td_target(r, term, gam, (double)m);
+    if (h.al_alpha > 0.0)                                                       // --advantage_learning: the maximum stays the standard one
+      y = advantage_target<T>(y, h.q_mu + (int64_t)n * A, q_tg, A, at, (double)m, h.al_alpha, h.al_persistent, term);
   }
-  double y = term[n] ? r : r + gam * (double)m;                               // :139-143, python float arithmetic
-  if (q_mu && !al) { const double rm = r + bonus; y = term[n] ? rm : rm + gam * V; }   // y = r_c + m + gamma V, V in double (maxq holds its rounded copy)
-  if (al) {                                                                   // y_AL = y - alpha gap(qbar(s), a), on terminal transitions too
-    const T* qp = q_mu + (int64_t)n * A;
-    double v = (double)qp[0];
-    for (int a = 1; a < A; ++a) { const double x = (double)qp[a]; v = x > v ? x : v; }
-    const double ystd = y;
-    y = ystd - al_alpha * (v - (double)qp[act[n]]);
-    if (al_persistent && !term[n]) {                                          // PAL: or the gap of repeating a in s', whichever target is larger
-      const double yp = ystd - al_alpha * ((double)m - (double)q_tg[(int64_t)n * A + act[n]]);
-      y = yp > y ? yp : y;
-    }
-  }
-  const T target = (T)y;                                                      // stored into the backend dtype
-  const int at = act[n];
-  T d = (T)0;
-  const T w = per_w ? (T)per_w[n] : (T)1;                                     // --prioritized_replay: importance weight of the sample
-  if (cql_alpha > 0.0) {                                                      // --cql_alpha: cql.h's rule on this sample's online row and the target y
-    cost_terms[n] = cql_sample<T>(q_on + (int64_t)n * A, A, at, y, cql_alpha, clip, w, dq + (int64_t)n * A, &d);
-    if (per_w) per_p[n] = (float)pow(fabs((double)d) + per_eps, per_alpha);   // unclipped |delta|
+  if (h.cql_alpha > 0.0) {                                                      // --cql_alpha
+    T d; h.cost_terms[n] = cql_sample<T>(q_on, A, at, y, h.cql_alpha, h.clip, w, dq, &d);
+    if (per) h.per_p[n] = (float)pow(fabs((double)d) + h.per_eps, h.per_alpha);   // unclipped |delta|
     return;
   }
-  for (int a = 0; a < A; ++a) {
-    T e = (a == at) ? q_on[(int64_t)n * A + a] - target : (T)0;               // deltas = preq - targets: 0 off the taken action
-    if (a == at) d = e;
-    if (clip != (T)0) e = e < -clip ? -clip : (e > clip ? clip : e);          // :158-159
-    if (per_w && a == at) e = w * e;                                          // clip, then weight
-    dq[(int64_t)n * A + a] = e;
-  }
-  if (per_w) {
-    cost_terms[n] = w * ((T)0.5 * (d * d));
-    per_p[n] = (float)pow(fabs((double)d) + per_eps, per_alpha);              // unclipped |delta|
-  } else
-  cost_terms[n] = (T)0.5 * (d * d);                                           // SumSquared before the clip (A7) :154
+  h.cost_terms[n] = td_sample<T>(q_on, A, at, y, h.clip, per, w, h.per_alpha, h.per_eps, dq, per ? h.per_p + n : nullptr);
 }
 template <typename T>
 __global__ void cost_kernel(const T* __restrict__ cost_terms, T* __restrict__ cost, double* __restrict__ cost_sum, int N) {
@@ -344,7 +287,7 @@ class GenericNetT : public GenericNet {
   bool double_dqn = false; T* q_sel = nullptr;          // --double_dqn: Q of the online net on the poststates [B][A]
   bool munchausen = false; T* q_mu = nullptr;           // --munchausen: Q of the target net on the prestates [B][A]
   double mu_alpha = 0.0, mu_tau = 1.0, mu_clip = 0.0;
-  bool advantage = false, al_persistent = false; double al_alpha = 0.0;      // --advantage_learning: shares forward(3, ..) and q_mu with --munchausen (refused together)
+  bool advantage = false, al_persistent = false; double al_alpha = 0.0;      // --advantage_learning: shares forward(3, ..) and q_mu with --munchausen (option_table.h refuses them together)
   uint8_t* st_states = nullptr; uint8_t* st_small = nullptr;
   std::vector<void*> allocs; std::vector<uint8_t> small_host;
 
@@ -450,10 +393,16 @@ class GenericNetT : public GenericNet {
     if (dd) GCHK(forward(2, post, B));                                         // --double_dqn: online net on the poststates
     if (munchausen || advantage) GCHK(forward(3, pre, B));                     // --munchausen / --advantage_learning: target net on the prestates (always, also when theta- aliases theta)
     GCHK(forward(0, pre, B));                                                  // online net on the prestates, tensors kept :128-130
-    hipLaunchKernelGGL(head_kernel<T>, dim3((B + 63) / 64), dim3(64), 0, st, (const T*)q, (const T*)(q + (int64_t)B * A), actions, rew, term,
-                       dq, cost_terms, maxq, B, A, cfg.discount_rate, cfg.min_reward, cfg.max_reward, (T)cfg.clip_error, (const T*)(dd ? q_sel : nullptr),
-                       per_w, per_p, per_alpha, per_eps, nstep, gamma_n, (const T*)((munchausen || advantage) ? q_mu : nullptr), mu_alpha, mu_tau, mu_clip, boot,
-                       advantage ? al_alpha : 0.0, al_persistent ? 1 : 0, quant, q_targets, duel, duel_step, cql_alpha);
+    GenHead<T> hd;
+    hd.q_on = q; hd.q_tg = q + (int64_t)B * A; hd.q_sel = dd ? q_sel : nullptr; hd.q_mu = (munchausen || advantage) ? q_mu : nullptr;
+    hd.act = actions; hd.term = term; hd.rew = rew; hd.dq = dq; hd.cost_terms = cost_terms; hd.maxq = maxq; hd.q_targets = q_targets; hd.duel_step = duel_step;
+    hd.per_w = per_w; hd.per_p = per_p; hd.per_alpha = per_alpha; hd.per_eps = per_eps;
+    hd.N = B; hd.A = A; hd.nstep = nstep; hd.clip = (T)cfg.clip_error;
+    hd.discount = cfg.discount_rate; hd.gamma_n = gamma_n; hd.minr = cfg.min_reward; hd.maxr = cfg.max_reward;
+    hd.munchausen = munchausen ? 1 : 0; hd.mu_alpha = mu_alpha; hd.mu_tau = mu_tau; hd.mu_clip = mu_clip;
+    hd.al_alpha = advantage ? al_alpha : 0.0; hd.al_persistent = al_persistent ? 1 : 0; hd.cql_alpha = cql_alpha;
+    hd.boot = boot; hd.quant = quant; hd.duel = duel;
+    hipLaunchKernelGGL(head_kernel<T>, dim3((B + 63) / 64), dim3(64), 0, st, hd);
     hipLaunchKernelGGL(cost_kernel<T>, dim3(1), dim3(64), 0, st, (const T*)cost_terms, cost, cost_sum, B);
     // ---- bprop (A8) :162
     GCHK(gemm(ga(dq, 1, A, act[3], 512, 1, g + off[4], A, 512, B)));                                   // gW5 = dq^T @ a4
@@ -585,7 +534,6 @@ class GenericNetT : public GenericNet {
   }
   DuelArgs duel = {0, 0, nullptr}; T* duel_step = nullptr;            // duel_step: [2][B] the last step's y and delta in T (duel.step is the tuned path's float buffer)
   hipError_t set_dueling(bool on) override {
-    if (on && (double_dqn || munchausen || advantage || cql_alpha > 0.0 || boot.K > 1 || quant.N > 1 || A < 2)) return hipErrorInvalidValue;
     if (on && !duel_step) GCHK(dalloc(&duel_step, (int64_t)2 * B));
     duel.on = on ? 1 : 0; duel.A = A - 1;
     return hipSuccess;
@@ -613,20 +561,17 @@ class GenericNetT : public GenericNet {
   int nstep = 1; double gamma_n = 0.0;
   bool double_dqn_on() const override { return double_dqn; }
   hipError_t set_double_dqn(bool on) override {
-    if (on && (munchausen || advantage || cql_alpha > 0.0)) return hipErrorInvalidValue;
     if (on && !q_sel) GCHK(dalloc(&q_sel, (int64_t)B * A));
     double_dqn = on;
     return hipSuccess;
   }
   hipError_t set_munchausen(bool on, double alpha, double tau, double clip) override {
-    if (on && (double_dqn || advantage || cql_alpha > 0.0)) return hipErrorInvalidValue;
     if (on && !q_mu) GCHK(dalloc(&q_mu, (int64_t)B * A));
     munchausen = on; mu_alpha = alpha; mu_tau = tau; mu_clip = clip;
     return hipSuccess;
   }
   bool munchausen_on() const override { return munchausen; }
   hipError_t set_advantage_learning(bool on, double alpha, bool persistent) override {
-    if (on && (double_dqn || munchausen || cql_alpha > 0.0 || boot.K > 1 || quant.N > 1 || duel.on || !(alpha > 0.0 && alpha < 1.0))) return hipErrorInvalidValue;
     if (on && !q_mu) GCHK(dalloc(&q_mu, (int64_t)B * A));
     advantage = on; al_alpha = on ? alpha : 0.0; al_persistent = on && persistent;
     return hipSuccess;
@@ -634,7 +579,6 @@ class GenericNetT : public GenericNet {
   bool advantage_learning_on() const override { return advantage; }
   double cql_alpha = 0.0;                                       // --cql_alpha: > 0 arms the CQL branch of the TD head; no forward of its own
   hipError_t set_cql(double alpha) override {
-    if (alpha > 0.0 && (double_dqn || munchausen || advantage || boot.K > 1 || quant.N > 1 || duel.on || !(alpha < INFINITY))) return hipErrorInvalidValue;
     cql_alpha = alpha > 0.0 ? alpha : 0.0;
     return hipSuccess;
   }

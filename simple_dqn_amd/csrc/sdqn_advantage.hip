@@ -1,24 +1,15 @@
-// sdqn_advantage.hip — the head of an advantage-learning train step, --advantage_learning / --persistent_advantage (Bellemare, Ostrovski,
-// Guez, Thomas, Munos 2016, "Increasing the Action Gap").  With qbar(s) = Q(theta-, s), alpha = HeadArgs::al_alpha:
-//     gap(q, a) = max_k q[k] - q[a]                                                     (>= 0, exactly 0 when a is a maximiser)
-//     y_std[n]  = r_c[n] + (terminal ? 0 : gamma max_a qbar(s'_n)[a])                    (--n_step: R, done, gamma^n in their places)
-//     y_AL[n]   = y_std[n] - alpha gap(qbar(s_n), a_n)                                   (on terminal transitions too)
-//     y_PAL[n]  = terminal ? y_AL[n] : max(y_AL[n], y_std[n] - alpha gap(qbar(s'_n), a_n))          (HeadArgs::al_persistent)
-// all in double from the stored fp32 Q-values, as head_kernel computes its y.  maxq[n] receives max_a qbar(s'_n)[a], as the standard head's.
+// sdqn_advantage.hip — the head of an advantage-learning train step, --advantage_learning / --persistent_advantage.  The rule
+// is advantage.h's, with alpha = HeadArgs::al_alpha; thread 0 applies it to the stored fp32 rows, as head_kernel computes its y, and takes
+// max_a qbar(s'_n)[a] with fmaxf (td_rule.h: FminmaxOps).
 // Everything in front of y and behind it is head_body.h.  qbar(s_n) is NOT computed here: a forward of the target weights on the prestates
 // runs in front of the step and leaves it in q slot 2 (sdqn_api_step.hip: run_extra_forward); thread 0 reads row n of it.  The PAL choice
 // is a run-time branch in thread 0: one kernel per (bucket, PER, NSTEP).
 #include "head_body.h"
+#include "td_rule.h"
+#include "advantage.h"
 
 namespace sdqn {
 namespace {
-
-// max_k q[k] - q[act] of one Q row, double: every term is a stored value, so the gap of a maximiser is exactly +0
-__device__ __forceinline__ double action_gap(const float* q, int A, int act) {
-  double v = (double)q[0];
-  for (int k = 1; k < A; ++k) { const double x = (double)q[k]; v = x > v ? x : v; }
-  return v - (double)q[act];
-}
 
 template <int AMAX, bool PER, bool NSTEP>
 __global__ void __launch_bounds__(512) advantage_head_kernel(const StepArgs a, const HeadArgs h) {
@@ -39,14 +30,10 @@ __global__ void __launch_bounds__(512) advantage_head_kernel(const StepArgs a, c
   if (j == 0) {
     const float* qpre = h.q + ((int64_t)2 * a.B + n) * A;                                         // qbar(s_n): q slot 2, left by the extra forward
     float m = sh_q[1][0];
-    for (int k = 1; k < A; ++k) m = fmaxf(m, sh_q[1][k]);                                         // max_a qbar(s'_n)[a]
+    for (int k = 1; k < A; ++k) m = FminmaxOps::max(m, sh_q[1][k]);                                        // max_a qbar(s'_n)[a]
     double rr, gam; head_reward<NSTEP>(h, m_rew, rr, gam);
     const double ystd = m_term ? rr : rr + gam * (double)m;
-    double y = ystd - h.al_alpha * action_gap(qpre, A, m_act);                                    // the gap correction applies on terminal transitions too
-    if (h.al_persistent && !m_term) {                                                             // PAL: the better of leaving a_n now and repeating it in s'_n
-      const double yp = ystd - h.al_alpha * ((double)m - (double)sh_q[1][m_act]);
-      y = yp > y ? yp : y;
-    }
+    const double y = advantage_target<float>(ystd, qpre, sh_q[1], A, m_act, (double)m, h.al_alpha, h.al_persistent, m_term);
     const float dc = head_delta<PER>(h, n, sh_q[0][m_act], y, m_w);
     h.maxq[n] = m;
     sh_dc = dc; sh_act = m_act;

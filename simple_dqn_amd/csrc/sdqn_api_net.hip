@@ -600,6 +600,20 @@ int ensure_slots3(sdqn_net_s* h) {
   h->slots3 = true;
   return SDQN_OK;
 }
+// a test's view of what a tuned step left on the device: k float spans joined, copied, synchronised and widened to double (out: may be NULL)
+struct FloatSpan { const float* dev; size_t n; double* out; };
+static int read_spans(sdqn_net_s* h, const FloatSpan* spans, int k) {
+  { int rc_ = join_comm(h); if (rc_) return rc_; }
+  size_t total = 0;
+  for (int i = 0; i < k; ++i) total += spans[i].n;
+  std::vector<float> buf(total);
+  size_t at = 0;
+  for (int i = 0; i < k; ++i) { HIPCHK(hipMemcpyAsync(buf.data() + at, spans[i].dev, spans[i].n * 4, hipMemcpyDeviceToHost, g_stream)); at += spans[i].n; }
+  HIPCHK(hipStreamSynchronize(g_stream));
+  at = 0;
+  for (int i = 0; i < k; ++i) { if (spans[i].out) for (size_t j = 0; j < spans[i].n; ++j) spans[i].out[j] = (double)buf[at + j]; at += spans[i].n; }
+  return SDQN_OK;
+}
 // ---- --munchausen: Munchausen DQN targets (sdqn.h) -------------------------------------------------------------------------
 extern "C" int sdqn_net_set_munchausen(sdqn_net_t h, int on, double alpha, double tau, double clip) {
   ARGCHK(h, "NULL handle");
@@ -732,15 +746,8 @@ extern "C" int sdqn_net_last_quantile_step(sdqn_net_t h, double* targets, double
   ARGCHK(h, "NULL handle");
   ARGCHK(h->quant_N > 1, "the network has no quantiles (sdqn_net_set_quantiles)");
   if (h->gen) { GENCHK(h->gen->last_quantile_step(targets, dq)); return SDQN_OK; }
-  { int rc_ = join_comm(h); if (rc_) return rc_; }
-  const size_t nt = (size_t)h->B * h->quant_N, nd = (size_t)h->B * h->A;
-  std::vector<float> buf(nt + nd);
-  HIPCHK(hipMemcpyAsync(buf.data(), h->quant_targets, nt * 4, hipMemcpyDeviceToHost, g_stream));
-  HIPCHK(hipMemcpyAsync(buf.data() + nt, h->dq, nd * 4, hipMemcpyDeviceToHost, g_stream));
-  HIPCHK(hipStreamSynchronize(g_stream));
-  if (targets) for (size_t i = 0; i < nt; ++i) targets[i] = (double)buf[i];
-  if (dq) for (size_t i = 0; i < nd; ++i) dq[i] = (double)buf[nt + i];
-  return SDQN_OK;
+  const FloatSpan spans[2] = {{h->quant_targets, (size_t)h->B * h->quant_N, targets}, {h->dq, (size_t)h->B * h->A, dq}};
+  return read_spans(h, spans, 2);
 }
 extern "C" int sdqn_net_get_quantiles(sdqn_net_t h, int* N) {
   ARGCHK(h, "NULL handle");
@@ -794,16 +801,9 @@ extern "C" int sdqn_net_last_dueling_step(sdqn_net_t h, double* y, double* delta
   ARGCHK(h, "NULL handle");
   ARGCHK(h->dueling, "the network is not a dueling net (sdqn_net_set_dueling)");
   if (h->gen) { GENCHK(h->gen->last_dueling_step(y, delta, dq)); return SDQN_OK; }
-  { int rc_ = join_comm(h); if (rc_) return rc_; }
-  const size_t nb = (size_t)h->B, nd = (size_t)h->B * h->A;
-  std::vector<float> buf(2 * nb + nd);
-  HIPCHK(hipMemcpyAsync(buf.data(), h->duel_step, 2 * nb * 4, hipMemcpyDeviceToHost, g_stream));
-  HIPCHK(hipMemcpyAsync(buf.data() + 2 * nb, h->dq, nd * 4, hipMemcpyDeviceToHost, g_stream));
-  HIPCHK(hipStreamSynchronize(g_stream));
-  if (y) for (size_t i = 0; i < nb; ++i) y[i] = (double)buf[i];
-  if (delta) for (size_t i = 0; i < nb; ++i) delta[i] = (double)buf[nb + i];
-  if (dq) for (size_t i = 0; i < nd; ++i) dq[i] = (double)buf[2 * nb + i];
-  return SDQN_OK;
+  const size_t nb = (size_t)h->B;
+  const FloatSpan spans[3] = {{h->duel_step, nb, y}, {h->duel_step + nb, nb, delta}, {h->dq, nb * h->A, dq}};
+  return read_spans(h, spans, 3);
 }
 // the host restatement of one sample of the dueling head (no device): dueling.h's dueling_sample on float rows
 extern "C" int sdqn_dueling_loss(int A, double clip_error, const float* q_pre_row, const float* q_post_row, int action, double reward, int terminal,

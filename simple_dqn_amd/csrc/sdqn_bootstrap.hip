@@ -1,13 +1,8 @@
-// sdqn_bootstrap.hip — Bootstrapped DQN, --bootstrap_heads K (Osband, Blundell, Pritzel, Van Roy 2016): the head of a train
-// step and the acting rule's select launch.  The net has A' = K A outputs, row k A + a = Q-head k, action a.  For sample n, ring slot i_n:
-//     y_k    = r_c + (terminal ? 0 : gamma max_a Q_k(theta-, s')[a])          (double from the stored fp32 Q, as head_kernel's y;
-//                                                                               --n_step: R, done, gamma^n in their places)
-//     d_k    = Q_k(theta, s)[a_n] - (float)y_k,  dc_k = clip(d_k)
-//     dq[n][k A + a_n] = m_k(i_n) dc_k / K, zero elsewhere;  cost term = (sum_k m_k 0.5 d_k^2) / K, sum in head order
+// sdqn_bootstrap.hip — Bootstrapped DQN, --bootstrap_heads K: the head of a train step and the acting rule's select launch.
+// The net has A' = K A outputs; the rule (targets, masks m_k, dq row, cost term, maxq) is bootstrap.h's bootstrap_sample, and
 //     d4     = 1[a4 > 0] sum_k W5[k A + a_n] dq_k  over the rows with m_k = 1, in head order
-//     maxq[n] = (float)((sum_k max_a Q_k(theta-, s')[a]) / K)
-// m_k: bootstrap.h.  The front end over the A' rows and the fc5 dgrad are head_body.h.  Thread 0 computes the K targets; the dq row
-// replaces the (dead) target-net row in LDS and reaches the other threads with a bit mask of its live rows.  K, A, the mask threshold and
+// The front end over the A' rows and the fc5 dgrad are head_body.h.  Thread 0 runs the rule with fmaxf / fminf (td_rule.h: FminmaxOps); the
+// dq row replaces the (dead) target-net row in LDS and reaches the other threads with a bit mask of its live rows.  K, A, the mask threshold and
 // seed and the index pointer are a third kernel argument (BootArgs), StepArgs and HeadArgs keep their layout.
 #include "head_body.h"
 
@@ -31,24 +26,10 @@ __global__ void __launch_bounds__(512) bootstrap_head_kernel(const StepArgs a, c
   m_act = m_act < b.A ? m_act : b.A - 1;               // memory safety only: the host rejects out-of-range actions before launching
   head_front_q<AMAX>(a, h, n, j, f, prod, sh_q);
   if (j == 0) {
-    const int act = m_act, term = m_term, K = b.K, GA = b.A;
     double rr, gam; head_reward<NSTEP>(h, m_rew, rr, gam);
-    const float fK = (float)K;
-    double msum = 0.0; float cost = 0.0f; int rows = 0;
-    for (int k = 0; k < K; ++k) {
-      float* qp = sh_q[1] + k * GA;                    // Q-head k's slice of the target net's poststate row
-      float m = qp[0];
-      for (int c = 1; c < GA; ++c) m = fmaxf(m, qp[c]);
-      msum += (double)m;
-      const double y = term ? rr : rr + gam * (double)m;
-      const float d = sh_q[0][k * GA + act] - (float)y;
-      const float dc = head_clip(h, d);
-      const int live = bootstrap_mask_bit(b.mask_seed, b.thresh, m_idx, k);
-      if (live) { cost += 0.5f * (d * d); rows |= 1 << (k * GA + act); }
-      for (int c = 0; c < GA; ++c) qp[c] = (live && c == act) ? dc / fK : 0.0f;   // the slice is dead: it becomes the dq row's
-    }
-    h.cost_terms[n] = cost / fK;
-    h.maxq[n] = (float)(msum / (double)K);
+    int rows;                                          // dq = sh_q[1]: each Q-head's slice of the target row is dead once its maximum is taken
+    h.cost_terms[n] = bootstrap_sample<float, FminmaxOps>(sh_q[0], sh_q[1], b.K, b.A, m_act, rr, m_term, gam, h.clip_error, b.mask_seed, b.thresh,
+                                                          m_idx, sh_q[1], &rows, &h.maxq[n]);
     sh_rows = rows;
   }
   __syncthreads();

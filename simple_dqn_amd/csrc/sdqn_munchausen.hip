@@ -1,26 +1,13 @@
-// sdqn_munchausen.hip — the head of a Munchausen DQN train step, --munchausen (Vieillard, Pietquin, Geist 2020).
-// With qbar(s) = Q(theta-, s), tau / alpha / l0 = HeadArgs::mu_tau / mu_alpha / mu_clip and pi = softmax(qbar / tau):
-//     lse(q) = v + tau log(sum_a exp((q[a] - v) / tau)),  v = max_a q[a]                 (sum in action order)
-//     V[n]   = lse(qbar(s'_n))                                                           (the soft value of the poststate)
-//     m[n]   = alpha clip(qbar(s_n)[a_n] - lse(qbar(s_n)), l0, 0)                         (= alpha clip(tau ln pi(a_n | s_n)))
-//     y[n]   = (r_c[n] + m[n]) + (terminal ? 0 : gamma V[n])                             (--n_step: R, done, gamma^n in their places)
-// all in double from the stored fp32 Q-values, as head_kernel computes its y.  maxq[n] receives (float)V[n].
+// sdqn_munchausen.hip — the head of a Munchausen DQN train step, --munchausen.  The rule is munchausen.h's, with tau / alpha /
+// l0 = HeadArgs::mu_tau / mu_alpha / mu_clip; thread 0 applies it to the stored fp32 rows, as head_kernel computes its y.
 // Everything in front of y and behind it is head_body.h.  qbar(s_n) is NOT computed here: a forward of the target weights on the
 // prestates runs in front of the step and leaves it in q slot 2 (sdqn_api_step.hip: run_extra_forward); thread 0 reads row n of it
 // the way the batch_norm Double DQN head reads its slot 2.
 #include "head_body.h"
+#include "munchausen.h"
 
 namespace sdqn {
 namespace {
-
-// lse of one Q row, double.  A = 1: exp(0) = 1, log(1) = +0, so lse == q[0] exactly
-__device__ __forceinline__ double soft_value(const float* q, int A, double tau) {
-  double v = (double)q[0];
-  for (int k = 1; k < A; ++k) { const double x = (double)q[k]; v = x > v ? x : v; }
-  double s = 0.0;
-  for (int k = 0; k < A; ++k) s += exp(((double)q[k] - v) / tau);         // every term in (0, 1], the maximum's is 1: never inf, s >= 1
-  return v + tau * log(s);
-}
 
 template <int AMAX, bool PER, bool NSTEP>
 __global__ void __launch_bounds__(512) munchausen_head_kernel(const StepArgs a, const HeadArgs h) {
@@ -40,12 +27,8 @@ __global__ void __launch_bounds__(512) munchausen_head_kernel(const StepArgs a, 
   head_front_q<AMAX>(a, h, n, j, f, prod, sh_q);
   if (j == 0) {
     const float* qpre = h.q + ((int64_t)2 * a.B + n) * A;                                         // qbar(s_n): q slot 2, left by the extra forward
-    const double V = soft_value(sh_q[1], A, h.mu_tau);
-    const double lp = (double)qpre[m_act] - soft_value(qpre, A, h.mu_tau);                        // tau ln pi(a_n | s_n) <= 0
-    const double bonus = h.mu_alpha * (lp < h.mu_clip ? h.mu_clip : (lp > 0.0 ? 0.0 : lp));
     double rr, gam; head_reward<NSTEP>(h, m_rew, rr, gam);
-    const double rm = rr + bonus;                                                                 // the bonus is added on terminal transitions too
-    const double y = m_term ? rm : rm + gam * V;
+    double V; const double y = munchausen_target<float>(qpre, sh_q[1], A, m_act, rr, m_term, gam, h.mu_alpha, h.mu_tau, h.mu_clip, &V);
     const float dc = head_delta<PER>(h, n, sh_q[0][m_act], y, m_w);
     h.maxq[n] = (float)V;
     sh_dc = dc; sh_act = m_act;

@@ -25,6 +25,7 @@
 #include "reset.h"
 #include "regularize.h"
 #include "option_table.h"
+#include "train_options.h"
 
 using namespace sdqn;
 
@@ -134,35 +135,22 @@ struct sdqn_net_s {
          *h_d2p = nullptr, *h_d2 = nullptr, *h_d1 = nullptr, *wh[2] = {nullptr, nullptr}, *wht[2] = {nullptr, nullptr};
   float *d3p = nullptr, *d2p = nullptr, *d1 = nullptr, *slab1 = nullptr, *slab2 = nullptr, *slab3 = nullptr;
   float *q = nullptr, *maxq = nullptr, *dq = nullptr, *cost_terms = nullptr, *cost_out = nullptr; double* cost_accum = nullptr;
-  // --double_dqn (option "double_dqn"): the forward launches carry a third net slot (problems.h: wslot); a1..a3, slab4, a4, q (and
-  // h_a1..h_a3) are re-allocated with room for it when the option is first switched on
-  bool double_dqn = false, slots3 = false;
-  // --munchausen (sdqn_net_set_munchausen): Munchausen DQN targets; every train step is preceded by a forward of the target
-  // net on the prestates (q slot 2: the slots3 re-allocation) and ends its forward with the Munchausen head (HEAD_MUNCHAUSEN)
-  bool munchausen = false; double mu_alpha = 0.9, mu_tau = 0.03, mu_clip = -1.0;
-  // --advantage_learning / --persistent_advantage (sdqn_net_set_advantage_learning): al_alpha > 0: the same forward in front
-  // of every train step, and the step's forward ends with the advantage-learning head (HEAD_ADVANTAGE); 0: off, nothing changes
-  double al_alpha = 0.0; bool al_persistent = false;
-  // --cql_alpha (sdqn_net_set_cql; cql.h): cql_alpha > 0: the step's forward ends with the conservative Q-learning head (HEAD_CQL),
-  // which adds alpha (logsumexp_k Q(theta, s)[k] - Q(theta, s)[a]) to the loss; no forward of its own, no launch more; 0: off, nothing changes
-  double cql_alpha = 0.0;
-  // --bootstrap_heads (sdqn_net_set_bootstrap; bootstrap.h): the net's A outputs are boot_K Q-heads of A / boot_K actions.  boot_K > 1:
-  // train steps end their forward with the bootstrap head (HEAD_BOOTSTRAP), the acting paths reduce a Q row to the game's actions.
-  // boot_q: [B][A / boot_K] acting rows of the game loops (select launch), allocated on first use.  boot_vote / boot_episode: the single-
-  // environment acting paths (sdqn_net_act_greedy) — majority vote (testing) or the Q-head of copy 0's episode boot_episode (collecting)
-  int boot_K = 1; double boot_P = 1.0; uint64_t boot_seed = 0, boot_thresh = 1ull << 53; void* boot_q = nullptr;
-  int boot_vote = 0; int64_t boot_episode = 0;
-  // --quantiles (sdqn_net_set_quantiles; quantile.h): the net's A outputs are quant_N quantiles of A / quant_N actions.  quant_N > 1:
-  // train steps end their forward with the quantile head (HEAD_QUANTILE), the acting paths reduce a Q row to its mean over the
-  // quantiles (the game loops: one launch into boot_q, which the two options — refused together — share).  quant_targets: [B][quant_N]
-  // the last step's targets (tuned path; sdqn_net_debug_read "quantile_targets"), allocated by the setter
-  int quant_N = 1; float* quant_targets = nullptr;
-  // --dueling (sdqn_net_set_dueling; dueling.h): the net's A outputs are V and A - 1 advantages over the two halves of fc4's
-  // units; fc5's entries outside the two blocks are +0.0 in theta and theta_t (masked where weights are set) and in g before it is clipped
-  // or applied (TailPlan::mask).  Train steps end their forward with the dueling head (HEAD_DUELING), the acting paths reduce a row to its
-  // A - 1 action values (the game loops: one launch into boot_q).  duel_step: [2][B] the last step's y and delta (tuned path;
-  // sdqn_net_debug_read "dueling_step"), allocated by the setter
-  bool dueling = false; float* duel_step = nullptr;
+  // The target options' state (train_options.h): written by the API setters alone, read by both train paths — the generic net
+  // holds a pointer to this member.  What each option adds to a tuned step:
+  //   double_dqn: the forward launches carry a third net slot (problems.h: wslot)             munchausen / al_alpha > 0 (§22, §28): a forward
+  //   of the target net on the prestates in front of every train step (q slot 2) and a head of their own           cql_alpha > 0 (§35), boot_K > 1
+  //   (§27), quant_N > 1 (§29), dueling (§32): a head of their own, no launch more; the net's A outputs are K Q-heads / N quantiles of
+  //   game_actions(h) actions, or V and A - 1 advantages (fc5's entries outside the two blocks are +0.0 in theta, theta_t and g: TailPlan::mask)
+  TrainOptions opt;
+  // slots3: a1..a3, slab4, a4, q (and h_a1..h_a3) have room for the third net slot (ensure_slots3: first use of double_dqn / munchausen / al_alpha)
+  bool slots3 = false;
+  // boot_q: [B][game actions] acting rows of the game loops (one select / mean / dueling launch; the three options are refused together), allocated on
+  // first use.  boot_vote / boot_episode: the single-environment acting paths (sdqn_net_act_greedy) — majority vote (testing) or the Q-head of copy 0's
+  // episode boot_episode (collecting)
+  void* boot_q = nullptr; int boot_vote = 0; int64_t boot_episode = 0;
+  // the last tuned step's read-outs, allocated by the setters: quant_targets [B][quant_N] (sdqn_net_debug_read "quantile_targets"), duel_step [2][B]
+  // y and delta ("dueling_step")
+  float* quant_targets = nullptr; float* duel_step = nullptr;
   // --noisy_nets (sdqn_net_set_noisy; noisy.h, sdqn_noisy.hip): fc4 and fc5 are W = mu + sigma * (e_out * e_in); theta / theta_t hold
   // mu.  nz_sigma: [NP - OFF4] per net, internal layout (the target's aliases the online one without a target net); nz_eff: the effective flat
   // buffers the step's kernels read; nz_state / nz_state2: sigma's optimizer state; nz_eps: [2][NOISY_EPS_NET] the factor vectors last composed;
@@ -193,7 +181,6 @@ struct sdqn_net_s {
   // step_applied).  reg_anchor: [NPW] the weights L2-init pulls toward, allocated and taken when reg_lambda first leaves 0
   // (sdqn_net_anchor_now takes it again); reg_norms: weight_norms' partials and results, allocated by the first read-out.  Both 0: nothing runs
   double reg_wd = 0.0, reg_lambda = 0.0; float* reg_anchor = nullptr; double* reg_norms = nullptr;
-  int n_step = 1;                          // --n_step (option "n_step"): poststate frame offset of the ring paths, n-step head
   double target_tau = 0.0;                 // --target_tau (sdqn_net_set_target_tau): > 0: every train step is followed by one soft target update
   // --clip_grad_norm (sdqn_net_set_clip_grad_norm): > 0: the flat gradient is scaled to this global L2 norm (of the MEAN
   // gradient) between its reduction and its application.  clip_buf: [CLIP_GRID] partials | {norm, scale} of the last clipped step,
@@ -348,21 +335,21 @@ int target_blend(sdqn_net_s* h, double tau);                       // one soft t
 int step_blend(sdqn_net_s* h);                                     // the blend of --target_tau behind an applied train step, or nothing
 int gen_step_done(sdqn_net_s* h);                                  // generic path: a train step was enqueued ([clip + deferred update,] counter, step_blend)
 // the actions a transition may hold (--bootstrap_heads / --quantiles: A is K / N times that; --dueling: one more, the V row)
-inline int game_actions(const sdqn_net_s* h) { return h->dueling ? h->A - 1 : h->A / (h->boot_K * h->quant_N); }
+inline int game_actions(const sdqn_net_s* h) { return game_actions(h->opt, h->A); }
 // --noisy_nets: the effective buffers as of xi_{nz_step}, recomposed when stale (nothing on a plain net); the acting weights of the phase
 int noisy_fresh(sdqn_net_s* h);
 int noisy_compose(sdqn_net_s* h, int64_t step, int nets);
 inline bool noisy_acting(const sdqn_net_s* h) { return h->noisy && h->nz_collecting; }
 inline bool clip_on(const sdqn_net_s* h) { return h->clip_grad_norm > 0.0; }
 // The options of option_table.h that are on, as a mask of option_bit(OptionId); values (may be NULL): [OPT_COUNT], the values the messages
-// print.  The one place that knows where each switch lives (the generic path keeps double_dqn and munchausen in its own object).
+// print
 inline unsigned active_options(const sdqn_net_s* h, int* values = nullptr) {
-  const bool on[OPT_COUNT] = {
-    h->gen ? h->gen->double_dqn_on() : h->double_dqn, h->gen ? h->gen->munchausen_on() : h->munchausen, h->al_alpha > 0.0, h->cql_alpha > 0.0,
-    h->boot_K > 1, h->quant_N > 1, h->dueling, h->noisy, h->cfg.batch_norm != 0.0, clip_on(h), h->target_tau > 0.0};
+  const TrainOptions& o = h->opt;
+  const bool on[OPT_COUNT] = {o.double_dqn, o.munchausen, advantage_on(o), cql_on(o), bootstrap_on(o), quantiles_on(o), o.dueling,
+                              h->noisy, h->cfg.batch_norm != 0.0, clip_on(h), h->target_tau > 0.0};
   unsigned mask = 0;
   for (int id = 0; id < OPT_COUNT; ++id) { if (on[id]) mask |= option_bit(id); if (values) values[id] = 0; }
-  if (values) { values[OPT_BOOTSTRAP_HEADS] = h->boot_K; values[OPT_QUANTILES] = h->quant_N; }
+  if (values) { values[OPT_BOOTSTRAP_HEADS] = o.boot_K; values[OPT_QUANTILES] = o.quant_N; }
   return mask;
 }
 int clip_gradient(sdqn_net_s* h, double bsz);                      // --clip_grad_norm: the two launches on g between update modes 1 and 2 (nothing when off)

@@ -13,6 +13,7 @@
 #include "bootstrap.h"         // BootArgs
 #include "quantile.h"          // QuantArgs
 #include "dueling.h"           // DuelArgs
+#include "train_options.h"
 
 namespace sdqn {
 
@@ -49,35 +50,23 @@ struct GenericNet {
   // launch, none without a target net
   virtual hipError_t soft_update(double tau) = 0;
   virtual bool has_target() const = 0;
-  virtual bool double_dqn_on() const = 0;
-  virtual hipError_t set_double_dqn(bool on) = 0;                        // --double_dqn (allocates the online-on-poststates Q on first use)
-  // --munchausen: Munchausen DQN targets; one more forward (target net, prestates) and the soft-value branch of the TD head
-  virtual hipError_t set_munchausen(bool on, double alpha, double tau, double clip) = 0;
-  virtual bool munchausen_on() const = 0;
-  // --advantage_learning / --persistent_advantage: the same extra forward as --munchausen and the AL / PAL branch of the TD head.
-  // These setters allocate and assign: which options combine, and their ranges, is the caller's to refuse (option_table.h; sdqn_api_net.hip)
-  virtual hipError_t set_advantage_learning(bool on, double alpha, bool persistent) = 0;
-  virtual bool advantage_learning_on() const = 0;
-  // --cql_alpha (cql.h): alpha > 0 arms the CQL branch of the TD head (no forward of its own)
-  virtual hipError_t set_cql(double alpha) = 0;
+  // The target options (train_options.h) are the handle's: the net reads the TrainOptions it was made with where it builds its head's
+  // arguments and decides on its extra forwards, and keeps no copy.  prepare(next) allocates what a step under `next` needs that the net
+  // does not have yet (the Q rows of --double_dqn's and --munchausen / --advantage_learning's extra forwards, the read-outs of
+  // --quantiles and --dueling) and commits nothing: the API setter assigns `next` when it has succeeded (sdqn_api_net.hip) — the
+  // counterpart of ensure_slots3 / dalloc on the tuned path.  Which options combine, and their ranges, is the setter's to refuse
+  virtual hipError_t prepare(const TrainOptions& next) = 0;
   // --prioritized_replay (sdqn_per.hip): w != nullptr makes the following train steps weight the taken action's row by w[n] and write the
   // new priority (|delta| + eps)^alpha into newp[n]; nullptr: the standard step
   virtual void set_per(const float* w, float* newp, double alpha, double eps) = 0;
-  // --bootstrap_heads (bootstrap.h): K > 1 arms the K-head branch of the TD head (the net has K x game-A outputs); boot_idx
-  // names the [B] ring indexes of the NEXT step's samples (device-readable; copied on the stream) or, nullptr, none (tuple path, P = 1)
-  virtual void set_bootstrap(int K, uint64_t thresh, uint64_t mask_seed) = 0;
+  // --bootstrap_heads (bootstrap.h): boot_idx names the [B] ring indexes of the NEXT step's samples (device-readable; copied
+  // on the stream) or, nullptr, none (tuple path, P = 1; also what sdqn_net_set_bootstrap leaves)
   virtual hipError_t boot_idx(const int64_t* idx) = 0;
-  // --quantiles (quantile.h): N > 1 arms the quantile branch of the TD head (the net has N x game-A outputs; clip_error is kappa)
-  virtual hipError_t set_quantiles(int N) = 0;
-  virtual hipError_t last_quantile_step(double* targets, double* dq) = 0;      // the last train step's [B][N] targets and [B][A] dq row, as doubles
-  // --dueling (dueling.h): arms the dueling branch of the TD head (the net has game-A + 1 outputs) and fc5's block mask on g
-  // in front of the clip / the optimizer; dueling_mask_weights applies the mask to W5 of theta (0) or theta_t (1)
-  virtual hipError_t set_dueling(bool on) = 0;
+  // --quantiles (quantile.h) / --dueling (dueling.h): what the last train step's head left, as doubles;
+  // dueling_mask_weights applies fc5's block mask to W5 of theta (0) or theta_t (1)
+  virtual hipError_t last_quantile_step(double* targets, double* dq) = 0;      // [B][N] targets, [B][A] dq row
   virtual hipError_t dueling_mask_weights(int which) = 0;
   virtual hipError_t last_dueling_step(double* y, double* delta, double* dq) = 0;
-  // --n_step: n > 1 makes the train steps read rew as the n-step returns (float64 bits) and term as the done flags, and
-  // bootstrap with gamma_n; n = 1: the standard step
-  virtual void set_nstep(int n, double gamma_n) = 0;
   // --clip_grad_norm (sdqn_clip.h): set_clip(true) makes train_dev / train_host / train_dev_host_meta stop behind the
   // gradient — the caller then enqueues clip_sqnorm, clip_scale (divisor bsz, max norm G) and apply_deferred (the step's optimizer
   // launch), one launch each; clip_record reads {norm, scale} of the last clip_scale (synchronises)
@@ -89,8 +78,8 @@ struct GenericNet {
   virtual size_t state_bytes() const = 0;                                // hist * H * W
 };
 
-// nullptr + *err on failure (bad geometry, out of memory)
-GenericNet* make_generic_net(const sdqn_net_cfg& c, hipStream_t stream, std::string* err);
+// nullptr + *err on failure (bad geometry, out of memory); opt: the handle's options, which outlive the net
+GenericNet* make_generic_net(const sdqn_net_cfg& c, const TrainOptions* opt, hipStream_t stream, std::string* err);
 
 // the standalone replay gather for any geometry (replay_memory.py:71-78): pre[k] = frames idx-hist .. idx-1, post[k] = idx-hist+1 .. idx
 struct GatherGenericArgs {

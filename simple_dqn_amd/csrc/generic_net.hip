@@ -284,10 +284,11 @@ class GenericNetT : public GenericNet {
   T* col[4] = {nullptr}; T* act[4] = {nullptr}; T* dact[3] = {nullptr};
   T *q = nullptr, *dq = nullptr, *d4 = nullptr, *dcol = nullptr, *cost_terms = nullptr, *cost = nullptr, *maxq = nullptr, *slab = nullptr;
   double* cost_sum = nullptr; int64_t slab_cap = 0;
-  bool double_dqn = false; T* q_sel = nullptr;          // --double_dqn: Q of the online net on the poststates [B][A]
-  bool munchausen = false; T* q_mu = nullptr;           // --munchausen: Q of the target net on the prestates [B][A]
-  double mu_alpha = 0.0, mu_tau = 1.0, mu_clip = 0.0;
-  bool advantage = false, al_persistent = false; double al_alpha = 0.0;      // --advantage_learning: shares forward(3, ..) and q_mu with --munchausen (option_table.h refuses them together)
+  const TrainOptions* opt = nullptr;                    // the handle's target options (train_options.h): read per step, never copied
+  T* q_sel = nullptr;                                   // --double_dqn: Q of the online net on the poststates [B][A]
+  T* q_mu = nullptr;                                    // --munchausen / --advantage_learning: Q of the target net on the prestates [B][A] (option_table.h refuses the two together)
+  T* q_targets = nullptr;                               // --quantiles: [B][N] the last step's targets in T (QuantArgs::targets is the tuned path's float buffer)
+  T* duel_step = nullptr;                               // --dueling: [2][B] the last step's y and delta in T (DuelArgs::step is the tuned path's float buffer)
   uint8_t* st_states = nullptr; uint8_t* st_small = nullptr;
   std::vector<void*> allocs; std::vector<uint8_t> small_host;
 
@@ -389,19 +390,23 @@ class GenericNetT : public GenericNet {
 
   hipError_t train_dev(const uint8_t* pre, const uint8_t* post, const uint8_t* actions, const int64_t* rew, const uint8_t* term, int epoch) override {
     GCHK(forward(1, post, B));                                                 // target net on the poststates :119-125
-    const bool dd = double_dqn && theta_t != theta;                            // (no target net: Double DQN is standard DQN)
+    const TrainOptions& o = *opt;
+    const bool dd = o.double_dqn && theta_t != theta;                          // (no target net: Double DQN is standard DQN)
+    const bool mu = prestate_target_forward(o);
     if (dd) GCHK(forward(2, post, B));                                         // --double_dqn: online net on the poststates
-    if (munchausen || advantage) GCHK(forward(3, pre, B));                     // --munchausen / --advantage_learning: target net on the prestates (always, also when theta- aliases theta)
+    if (mu) GCHK(forward(3, pre, B));                                          // --munchausen / --advantage_learning: target net on the prestates (always, also when theta- aliases theta)
     GCHK(forward(0, pre, B));                                                  // online net on the prestates, tensors kept :128-130
     GenHead<T> hd;
-    hd.q_on = q; hd.q_tg = q + (int64_t)B * A; hd.q_sel = dd ? q_sel : nullptr; hd.q_mu = (munchausen || advantage) ? q_mu : nullptr;
+    hd.q_on = q; hd.q_tg = q + (int64_t)B * A; hd.q_sel = dd ? q_sel : nullptr; hd.q_mu = mu ? q_mu : nullptr;
     hd.act = actions; hd.term = term; hd.rew = rew; hd.dq = dq; hd.cost_terms = cost_terms; hd.maxq = maxq; hd.q_targets = q_targets; hd.duel_step = duel_step;
     hd.per_w = per_w; hd.per_p = per_p; hd.per_alpha = per_alpha; hd.per_eps = per_eps;
-    hd.N = B; hd.A = A; hd.nstep = nstep; hd.clip = (T)cfg.clip_error;
-    hd.discount = cfg.discount_rate; hd.gamma_n = gamma_n; hd.minr = cfg.min_reward; hd.maxr = cfg.max_reward;
-    hd.munchausen = munchausen ? 1 : 0; hd.mu_alpha = mu_alpha; hd.mu_tau = mu_tau; hd.mu_clip = mu_clip;
-    hd.al_alpha = advantage ? al_alpha : 0.0; hd.al_persistent = al_persistent ? 1 : 0; hd.cql_alpha = cql_alpha;
-    hd.boot = boot; hd.quant = quant; hd.duel = duel;
+    hd.N = B; hd.A = A; hd.nstep = o.n_step; hd.clip = (T)cfg.clip_error;
+    hd.discount = cfg.discount_rate; hd.gamma_n = o.gamma_n; hd.minr = cfg.min_reward; hd.maxr = cfg.max_reward;
+    hd.munchausen = o.munchausen ? 1 : 0; hd.mu_alpha = o.mu_alpha; hd.mu_tau = o.mu_tau; hd.mu_clip = o.mu_clip;
+    hd.al_alpha = o.al_alpha; hd.al_persistent = o.al_persistent ? 1 : 0; hd.cql_alpha = o.cql_alpha;
+    const int GA = game_actions(o, A);                                         // (each block is read only while its option is on)
+    hd.boot = {o.boot_K, GA, o.boot_thresh, bootstrap_mask_seed(o.boot_seed), boot_idx_cur};
+    hd.quant = {o.quant_N, GA, nullptr}; hd.duel = {o.dueling ? 1 : 0, GA, nullptr};
     hipLaunchKernelGGL(head_kernel<T>, dim3((B + 63) / 64), dim3(64), 0, st, hd);
     hipLaunchKernelGGL(cost_kernel<T>, dim3(1), dim3(64), 0, st, (const T*)cost_terms, cost, cost_sum, B);
     // ---- bprop (A8) :162
@@ -421,7 +426,7 @@ class GenericNetT : public GenericNet {
         hipLaunchKernelGGL(col2im_kernel<T>, dim3(grid_for(total)), dim3(256), 0, st, (const T*)dcol, (const T*)act[l - 1], dact[l - 1], total, c);
       }
     }
-    if (duel.on) GCHK(launch_dueling_mask(g + off[4], sizeof(T) == 8, A, 512, st));                  // --dueling: the clip and the optimizer see the masked g
+    if (o.dueling) GCHK(launch_dueling_mask(g + off[4], sizeof(T) == 8, A, 512, st));                  // --dueling: the clip and the optimizer see the masked g
     // ---- optimizer :165
     OptArgs<T> u; u.w = theta; u.s1 = s1; u.s2 = s2; u.g = g; u.n = NP; u.opt = cfg.optimizer;
     u.bsz = (T)B; u.rho = (T)cfg.decay_rate; u.omr = (T)(1.0 - cfg.decay_rate); u.lr = (T)cfg.learning_rate; u.eps = (T)cfg.epsilon;
@@ -517,25 +522,19 @@ class GenericNetT : public GenericNet {
   }
   void set_per(const float* w, float* newp, double alpha, double eps) override { per_w = w; per_p = newp; per_alpha = alpha; per_eps = eps; }
   const float* per_w = nullptr; float* per_p = nullptr; double per_alpha = 0.0, per_eps = 0.0;
-  void set_nstep(int n, double g) override { nstep = n; gamma_n = g; }
-  BootArgs boot = {1, 0, 1ull << 53, 0, nullptr}; int64_t* boot_idx_buf = nullptr;
-  void set_bootstrap(int K, uint64_t thresh, uint64_t mask_seed) override { boot.K = K; boot.A = A / K; boot.thresh = thresh; boot.mask_seed = mask_seed; boot.idx = nullptr; }
-  QuantArgs quant = {1, 0, nullptr}; T* q_targets = nullptr;          // q_targets: [B][N] the last step's targets in T (quant.targets is the tuned path's float buffer)
-  hipError_t set_quantiles(int N) override {
-    if (N > 1 && !q_targets) GCHK(dalloc(&q_targets, (int64_t)B * A));
-    quant.N = N; quant.A = A / N;
+  // what a step under `next` needs and the net does not have yet; nothing is committed (generic_net.h)
+  hipError_t prepare(const TrainOptions& next) override {
+    if (next.double_dqn && !q_sel) GCHK(dalloc(&q_sel, (int64_t)B * A));
+    if (prestate_target_forward(next) && !q_mu) GCHK(dalloc(&q_mu, (int64_t)B * A));
+    if (quantiles_on(next) && !q_targets) GCHK(dalloc(&q_targets, (int64_t)B * A));
+    if (next.dueling && !duel_step) GCHK(dalloc(&duel_step, (int64_t)2 * B));
     return hipSuccess;
   }
+  const int64_t* boot_idx_cur = nullptr; int64_t* boot_idx_buf = nullptr;      // --bootstrap_heads: the next step's ring indexes (boot_idx) / their device copy
   hipError_t last_quantile_step(double* targets, double* dq_host) override {
-    if (quant.N < 2 || !q_targets) return hipErrorInvalidValue;
-    if (targets) GCHK(fetch(q_targets, (int64_t)B * quant.N, targets, true));
+    if (!quantiles_on(*opt) || !q_targets) return hipErrorInvalidValue;
+    if (targets) GCHK(fetch(q_targets, (int64_t)B * opt->quant_N, targets, true));
     if (dq_host) GCHK(fetch(dq, (int64_t)B * A, dq_host, true));
-    return hipSuccess;
-  }
-  DuelArgs duel = {0, 0, nullptr}; T* duel_step = nullptr;            // duel_step: [2][B] the last step's y and delta in T (duel.step is the tuned path's float buffer)
-  hipError_t set_dueling(bool on) override {
-    if (on && !duel_step) GCHK(dalloc(&duel_step, (int64_t)2 * B));
-    duel.on = on ? 1 : 0; duel.A = A - 1;
     return hipSuccess;
   }
   hipError_t dueling_mask_weights(int which) override {
@@ -544,42 +543,18 @@ class GenericNetT : public GenericNet {
     return launch_dueling_mask(w + off[4], sizeof(T) == 8, A, 512, st);
   }
   hipError_t last_dueling_step(double* y, double* delta, double* dq_host) override {
-    if (!duel.on || !duel_step) return hipErrorInvalidValue;
+    if (!opt->dueling || !duel_step) return hipErrorInvalidValue;
     if (y) GCHK(fetch(duel_step, B, y, true));
     if (delta) GCHK(fetch(duel_step + B, B, delta, true));
     if (dq_host) GCHK(fetch(dq, (int64_t)B * A, dq_host, true));
     return hipSuccess;
   }
   hipError_t boot_idx(const int64_t* idx) override {
-    boot.idx = nullptr;
+    boot_idx_cur = nullptr;
     if (!idx) return hipSuccess;
     if (!boot_idx_buf) GCHK(dalloc(&boot_idx_buf, (int64_t)B));
     GCHK(hipMemcpyAsync(boot_idx_buf, idx, (size_t)B * sizeof(int64_t), hipMemcpyDefault, st));
-    boot.idx = boot_idx_buf;
-    return hipSuccess;
-  }
-  int nstep = 1; double gamma_n = 0.0;
-  bool double_dqn_on() const override { return double_dqn; }
-  hipError_t set_double_dqn(bool on) override {
-    if (on && !q_sel) GCHK(dalloc(&q_sel, (int64_t)B * A));
-    double_dqn = on;
-    return hipSuccess;
-  }
-  hipError_t set_munchausen(bool on, double alpha, double tau, double clip) override {
-    if (on && !q_mu) GCHK(dalloc(&q_mu, (int64_t)B * A));
-    munchausen = on; mu_alpha = alpha; mu_tau = tau; mu_clip = clip;
-    return hipSuccess;
-  }
-  bool munchausen_on() const override { return munchausen; }
-  hipError_t set_advantage_learning(bool on, double alpha, bool persistent) override {
-    if (on && !q_mu) GCHK(dalloc(&q_mu, (int64_t)B * A));
-    advantage = on; al_alpha = on ? alpha : 0.0; al_persistent = on && persistent;
-    return hipSuccess;
-  }
-  bool advantage_learning_on() const override { return advantage; }
-  double cql_alpha = 0.0;                                       // --cql_alpha: > 0 arms the CQL branch of the TD head; no forward of its own
-  hipError_t set_cql(double alpha) override {
-    cql_alpha = alpha > 0.0 ? alpha : 0.0;
+    boot_idx_cur = boot_idx_buf;
     return hipSuccess;
   }
   hipError_t update_target() override {
@@ -595,9 +570,9 @@ class GenericNetT : public GenericNet {
 };
 
 template <typename T>
-GenericNet* make_t(const sdqn_net_cfg& c, hipStream_t s, std::string* err) {
+GenericNet* make_t(const sdqn_net_cfg& c, const TrainOptions* opt, hipStream_t s, std::string* err) {
   GenericNetT<T>* n = new GenericNetT<T>();
-  n->cfg = c; n->st = s; n->B = c.batch_size; n->A = c.num_actions; n->hist = c.history_length; n->H = c.screen_height; n->W = c.screen_width;
+  n->cfg = c; n->opt = opt; n->st = s; n->B = c.batch_size; n->A = c.num_actions; n->hist = c.history_length; n->H = c.screen_height; n->W = c.screen_width;
   hipError_t e = n->init(err);
   if (e != hipSuccess) { if (err->empty()) *err = std::string("generic network: ") + hipGetErrorString(e); delete n; return nullptr; }
   return n;
@@ -621,10 +596,10 @@ __global__ void __launch_bounds__(256) gather_generic_kernel(const GatherGeneric
 
 }  // namespace
 
-GenericNet* make_generic_net(const sdqn_net_cfg& c, hipStream_t s, std::string* err) {
+GenericNet* make_generic_net(const sdqn_net_cfg& c, const TrainOptions* opt, hipStream_t s, std::string* err) {
   err->clear();
-  if (c.datatype == 2) return make_t<double>(c, s, err);
-  return make_t<float>(c, s, err);
+  if (c.datatype == 2) return make_t<double>(c, opt, s, err);
+  return make_t<float>(c, opt, s, err);
 }
 
 hipError_t launch_gather_generic(const GatherGenericArgs& g, hipStream_t s) {

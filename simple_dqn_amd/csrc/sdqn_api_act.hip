@@ -170,13 +170,13 @@ extern "C" int sdqn_net_act_greedy(sdqn_net_t h, sdqn_statebuf_t sb, int* action
   int best = 0;
   for (int k = 1; k < A; ++k) if (q[k] > q[best] || (q[k] != q[k] && q[best] == q[best])) best = k;   // np.argmax: the first maximum, a NaN counts as one
   *action = best;
-  if (h->boot_K > 1) {                     // --bootstrap_heads: the vote while testing, the episode's Q-head (copy 0) while collecting
+  if (h->opt.boot_K > 1) {                     // --bootstrap_heads: the vote while testing, the episode's Q-head (copy 0) while collecting
     int votes[MAX_ACTIONS]; const int GA = game_actions(h);
-    if (h->boot_vote) *action = bootstrap_vote(q, h->boot_K, GA, votes);
-    else *action = bootstrap_vote(q + bootstrap_head_of(bootstrap_head_seed(h->boot_seed), h->boot_K, 0, (uint64_t)h->boot_episode) * GA, 1, GA, votes);
+    if (h->boot_vote) *action = bootstrap_vote(q, h->opt.boot_K, GA, votes);
+    else *action = bootstrap_vote(q + bootstrap_head_of(bootstrap_head_seed(h->opt.boot_seed), h->opt.boot_K, 0, (uint64_t)h->boot_episode) * GA, 1, GA, votes);
   }
-  if (h->quant_N > 1) *action = quantile_act(q, h->quant_N, game_actions(h));     // --quantiles: the first maximum of the quantile means
-  if (h->dueling) *action = dueling_act(q, game_actions(h));                      // --dueling: the first maximum of V + Adv - mean(Adv)
+  if (h->opt.quant_N > 1) *action = quantile_act(q, h->opt.quant_N, game_actions(h));     // --quantiles: the first maximum of the quantile means
+  if (h->opt.dueling) *action = dueling_act(q, game_actions(h));                      // --dueling: the first maximum of V + Adv - mean(Adv)
   if (q_out) memcpy(q_out, q, (size_t)A * 4);
   return SDQN_OK;
 }

@@ -11,6 +11,7 @@ static const char* const RETIRED_OPTIONS[] = {"hoist", "two_streams", "fuse_dbg"
                                                     "the library (tools/exp/README.md; tools/exp/experiments_r04.patch)", NAME); return SDQN_ERR_ARG; } while (0)
 // Switching option `setting` on (value: what its message prints, where it prints one): SDQN_ERR_ARG and the message when an option that
 // option_table.h pairs it with is on.  Every setter asks before it allocates or changes anything, so a refused call leaves the handle as it was.
+// The setters of the target options (train_options.h) share one shape: check the ranges, edit a copy of h->opt, REFUSE_CONFLICTS, commit_options.
 static int refuse_conflicts(const sdqn_net_s* h, int setting, int value = 0) {
   int values[OPT_COUNT]; char msg[256];
   const unsigned active = active_options(h, values);
@@ -83,7 +84,7 @@ extern "C" int sdqn_net_create(sdqn_net_t* out, const sdqn_net_cfg* c) {
   h->cfg = *c; h->B = c->batch_size; h->A = c->num_actions; h->NPW = OFF5 + (int64_t)h->A * NFC;
   if (c->datatype == 2 || !tuned_geom) {            // main.py:27-28,34,53: same layer stack, other sizes / float64 arithmetic
     std::string err;
-    h->gen = make_generic_net(*c, g_stream, &err);
+    h->gen = make_generic_net(*c, &h->opt, g_stream, &err);
     if (!h->gen) { set_error("%s", err.c_str()); delete h; return SDQN_ERR_HIP; }
     h->NP = h->NPW = h->gen->param_count();
     memset(h->prof_ms, 0, sizeof h->prof_ms); memset(h->prof_n, 0, sizeof h->prof_n);
@@ -247,7 +248,7 @@ int gen_set(sdqn_net_s* h, int which, int layer, const void* w, int64_t n, bool 
   ARGCHK(which != 4 || h->cfg.optimizer != 0, "this optimizer has no second state");
   ARGCHK(n == h->gen->layer_size(layer), "layer %d holds %lld values, got %lld", layer, (long long)h->gen->layer_size(layer), (long long)n);
   GENCHK(h->gen->set_param(which, layer, w, f64));
-  if (h->dueling && layer == 4 && which <= 1) GENCHK(h->gen->dueling_mask_weights(which));      // --dueling: as sdqn_net_set_weights
+  if (h->opt.dueling && layer == 4 && which <= 1) GENCHK(h->gen->dueling_mask_weights(which));      // --dueling: as sdqn_net_set_weights
   return SDQN_OK;
 }
 int gen_get(sdqn_net_s* h, int which, int layer, void* w, int64_t n, bool f64) {
@@ -439,7 +440,7 @@ int step_applied(sdqn_net_s* h, bool interval_events) {
 // wh / wht (they hold the OFF5 values in front of fc5), conv1's bf16 planes — each where the range reaches it, on the library stream
 int refresh_derived(sdqn_net_s* h, int net_slot, int64_t first, int64_t last) {
   float* th = net_slot ? h->theta_t : h->theta;
-  if (h->dueling && last > OFF5) HIPCHK(launch_dueling_mask(th + OFF5, false, h->A, NFC, g_stream));
+  if (h->opt.dueling && last > OFF5) HIPCHK(launch_dueling_mask(th + OFF5, false, h->A, NFC, g_stream));
   if (h->cfg.datatype == 1 && first < OFF5) HIPCHK(launch_refresh16(th, h->wh[net_slot], h->wht[net_slot], g_stream));
   if (h->w1p[net_slot] && first < OFF2) HIPCHK(launch_w1_planes(th, h->w1p[net_slot], g_stream));
   return SDQN_OK;
@@ -504,7 +505,7 @@ extern "C" int sdqn_net_apply_update(sdqn_net_t h, double bsz) {
   { int rc = join_comm(h); if (rc) return rc; }
   h->spec_pending = false;
   TailPlan t;                              // the step's optimizer tail from "clip" on, with the caller's divisor
-  t.mask = h->dueling; t.clip = clip_on(h); t.apply_mode = 2; t.divisor = bsz;
+  t.mask = h->opt.dueling; t.clip = clip_on(h); t.apply_mode = 2; t.divisor = bsz;
   t.ovf = h->half_payload_pending;         // the gradient came back through the half payload: same overflow rule as the RCCL path
   h->half_payload_pending = false;
   int rc = run_update_tail(h, make_update_args(h, step_args(h)), t); if (rc) return rc;
@@ -614,6 +615,18 @@ static int read_spans(sdqn_net_s* h, const FloatSpan* spans, int k) {
   for (int i = 0; i < k; ++i) { if (spans[i].out) for (size_t j = 0; j < spans[i].n; ++j) spans[i].out[j] = (double)buf[at + j]; at += spans[i].n; }
   return SDQN_OK;
 }
+// The last two steps of every target-option setter: allocate what a step under `next` needs and the net does not have yet — the generic net's
+// prepare, or on the tuned path the third net slot and the heads' read-outs — and only then commit it (a failure leaves h->opt as it was)
+static int commit_options(sdqn_net_s* h, const TrainOptions& next) {
+  if (h->gen) GENCHK(h->gen->prepare(next));
+  else {
+    if (next.double_dqn || prestate_target_forward(next)) { int r_ = ensure_slots3(h); if (r_) return r_; }
+    if (quantiles_on(next) && !h->quant_targets) { int r_ = dalloc(h, (void**)&h->quant_targets, (size_t)h->B * MAX_ACTIONS * sizeof(float)); if (r_) return r_; }
+    if (next.dueling && !h->duel_step) { int r_ = dalloc(h, (void**)&h->duel_step, (size_t)2 * h->B * sizeof(float)); if (r_) return r_; }
+  }
+  h->opt = next;
+  return SDQN_OK;
+}
 // ---- --munchausen: Munchausen DQN targets (sdqn.h) -------------------------------------------------------------------------
 extern "C" int sdqn_net_set_munchausen(sdqn_net_t h, int on, double alpha, double tau, double clip) {
   ARGCHK(h, "NULL handle");
@@ -621,15 +634,14 @@ extern "C" int sdqn_net_set_munchausen(sdqn_net_t h, int on, double alpha, doubl
   ARGCHK(tau > 0.0 && tau < INFINITY, "munchausen_tau %g: must be > 0", tau);
   ARGCHK(alpha >= 0.0 && alpha <= 1.0, "munchausen_alpha %g outside [0, 1]", alpha);
   ARGCHK(clip <= 0.0 && clip > -INFINITY, "munchausen_clip %g: must be <= 0", clip);
+  TrainOptions next = h->opt;
+  next.munchausen = on != 0; next.mu_alpha = alpha; next.mu_tau = tau; next.mu_clip = clip;
   if (on) REFUSE_CONFLICTS(h, OPT_MUNCHAUSEN);
-  if (h->gen) GENCHK(h->gen->set_munchausen(on != 0, alpha, tau, clip));
-  else if (on) { int r_ = ensure_slots3(h); if (r_) return r_; }
-  h->munchausen = on != 0; h->mu_alpha = alpha; h->mu_tau = tau; h->mu_clip = clip;
-  return SDQN_OK;
+  return commit_options(h, next);
 }
 extern "C" int sdqn_net_get_munchausen(sdqn_net_t h, int* on, double* alpha, double* tau, double* clip) {
   ARGCHK(h, "NULL handle");
-  if (on) *on = h->munchausen ? 1 : 0; if (alpha) *alpha = h->mu_alpha; if (tau) *tau = h->mu_tau; if (clip) *clip = h->mu_clip;
+  if (on) *on = h->opt.munchausen ? 1 : 0; if (alpha) *alpha = h->opt.mu_alpha; if (tau) *tau = h->opt.mu_tau; if (clip) *clip = h->opt.mu_clip;
   return SDQN_OK;
 }
 
@@ -639,18 +651,17 @@ extern "C" int sdqn_net_set_advantage_learning(sdqn_net_t h, double alpha, int p
   ARGCHK(alpha >= 0.0 && alpha < 1.0, "advantage_learning %g outside [0, 1)", alpha);                    // (a NaN fails the comparison)
   ARGCHK(persistent == 0 || persistent == 1, "persistent_advantage must be 0 or 1");
   ARGCHK(!(persistent && alpha == 0.0), "persistent_advantage needs advantage_learning > 0");
-  if (alpha > 0.0) {
+  TrainOptions next = h->opt;
+  next.al_alpha = alpha; next.al_persistent = persistent != 0;
+  if (advantage_on(next)) {
     REFUSE_CONFLICTS(h, OPT_ADVANTAGE_LEARNING);
-    ARGCHK(!(persistent && h->n_step > 1),"persistent_advantage cannot be combined with n_step %d: it repeats the action in the NEXT state", h->n_step);
+    ARGCHK(!(next.al_persistent && next.n_step > 1),"persistent_advantage cannot be combined with n_step %d: it repeats the action in the NEXT state", next.n_step);
   }
-  if (h->gen) GENCHK(h->gen->set_advantage_learning(alpha > 0.0, alpha, persistent != 0));
-  else if (alpha > 0.0) { int r_ = ensure_slots3(h); if (r_) return r_; }
-  h->al_alpha = alpha; h->al_persistent = persistent != 0;
-  return SDQN_OK;
+  return commit_options(h, next);
 }
 extern "C" int sdqn_net_get_advantage_learning(sdqn_net_t h, double* alpha, int* persistent) {
   ARGCHK(h, "NULL handle");
-  if (alpha) *alpha = h->al_alpha; if (persistent) *persistent = h->al_persistent ? 1 : 0;
+  if (alpha) *alpha = h->opt.al_alpha; if (persistent) *persistent = h->opt.al_persistent ? 1 : 0;
   return SDQN_OK;
 }
 
@@ -658,14 +669,14 @@ extern "C" int sdqn_net_get_advantage_learning(sdqn_net_t h, double* alpha, int*
 extern "C" int sdqn_net_set_cql(sdqn_net_t h, double alpha) {
   ARGCHK(h, "NULL handle");
   ARGCHK(alpha >= 0.0 && alpha < INFINITY, "cql_alpha %g: must be a finite value >= 0", alpha);          // (a NaN fails the comparison)
-  if (alpha > 0.0) REFUSE_CONFLICTS(h, OPT_CQL_ALPHA);
-  if (h->gen) GENCHK(h->gen->set_cql(alpha));
-  h->cql_alpha = alpha;
-  return SDQN_OK;
+  TrainOptions next = h->opt;
+  next.cql_alpha = alpha;
+  if (cql_on(next)) REFUSE_CONFLICTS(h, OPT_CQL_ALPHA);
+  return commit_options(h, next);
 }
 extern "C" int sdqn_net_get_cql(sdqn_net_t h, double* alpha) {
   ARGCHK(h, "NULL handle");
-  if (alpha) *alpha = h->cql_alpha;
+  if (alpha) *alpha = h->opt.cql_alpha;
   return SDQN_OK;
 }
 // the host restatement of one sample of the CQL head (no device): cql.h's cql_sample on a float row
@@ -689,15 +700,18 @@ extern "C" int sdqn_net_set_bootstrap(sdqn_net_t h, int K, double P, uint64_t se
   ARGCHK(h, "NULL handle");
   ARGCHK(K >= 1 && K <= MAX_ACTIONS, "bootstrap_heads %d outside [1, %d]", K, MAX_ACTIONS);
   ARGCHK(h->A % K == 0, "bootstrap_heads %d does not divide the network's %d outputs (create it with bootstrap_heads x num_actions <= %d)", K, h->A, MAX_ACTIONS);
-  uint64_t thresh; { int rc_ = boot_thresh_of(P, &thresh); if (rc_) return rc_; }
-  if (K > 1) REFUSE_CONFLICTS(h, OPT_BOOTSTRAP_HEADS, K);
-  if (h->gen) h->gen->set_bootstrap(K, thresh, bootstrap_mask_seed(seed));
-  h->boot_K = K; h->boot_P = P; h->boot_seed = seed; h->boot_thresh = thresh; h->boot_episode = 0;
+  TrainOptions next = h->opt;
+  { int rc_ = boot_thresh_of(P, &next.boot_thresh); if (rc_) return rc_; }
+  next.boot_K = K; next.boot_P = P; next.boot_seed = seed;
+  if (bootstrap_on(next)) REFUSE_CONFLICTS(h, OPT_BOOTSTRAP_HEADS, K);
+  { int rc_ = commit_options(h, next); if (rc_) return rc_; }
+  h->boot_episode = 0;
+  if (h->gen) GENCHK(h->gen->boot_idx(nullptr));           // (the indexes a ring step left name samples of the old setting)
   return SDQN_OK;
 }
 extern "C" int sdqn_net_get_bootstrap(sdqn_net_t h, int* K, double* P, uint64_t* seed) {
   ARGCHK(h, "NULL handle");
-  if (K) *K = h->boot_K; if (P) *P = h->boot_P; if (seed) *seed = h->boot_seed;
+  if (K) *K = h->opt.boot_K; if (P) *P = h->opt.boot_P; if (seed) *seed = h->opt.boot_seed;
   return SDQN_OK;
 }
 extern "C" int sdqn_net_bootstrap_acting(sdqn_net_t h, int vote, int new_episode) {
@@ -732,26 +746,25 @@ extern "C" int sdqn_net_set_quantiles(sdqn_net_t h, int N) {
   ARGCHK(h, "NULL handle");
   ARGCHK(N >= 1 && N <= MAX_ACTIONS, "quantiles %d outside [1, %d]", N, MAX_ACTIONS);
   ARGCHK(h->A % N == 0, "quantiles %d does not divide the network's %d outputs (create it with quantiles x num_actions <= %d)", N, h->A, MAX_ACTIONS);
-  if (N > 1) {
+  TrainOptions next = h->opt;
+  next.quant_N = N;
+  if (quantiles_on(next)) {
     ARGCHK(h->cfg.clip_error > 0.0, "quantiles %d needs clip_error > 0 (clip_error %g): it is the Huber threshold of the quantile loss", N, h->cfg.clip_error);
     REFUSE_CONFLICTS(h, OPT_QUANTILES, N);
-    if (!h->gen && !h->quant_targets) { int r_ = dalloc(h, (void**)&h->quant_targets, (size_t)h->B * MAX_ACTIONS * sizeof(float)); if (r_) return r_; }
   }
-  if (h->gen) GENCHK(h->gen->set_quantiles(N));
-  h->quant_N = N;
-  return SDQN_OK;
+  return commit_options(h, next);
 }
 // what the last train step's quantile head left: its N targets per sample and its dq rows, widened to double (every path; a test's view)
 extern "C" int sdqn_net_last_quantile_step(sdqn_net_t h, double* targets, double* dq) {
   ARGCHK(h, "NULL handle");
-  ARGCHK(h->quant_N > 1, "the network has no quantiles (sdqn_net_set_quantiles)");
+  ARGCHK(quantiles_on(h->opt), "the network has no quantiles (sdqn_net_set_quantiles)");
   if (h->gen) { GENCHK(h->gen->last_quantile_step(targets, dq)); return SDQN_OK; }
-  const FloatSpan spans[2] = {{h->quant_targets, (size_t)h->B * h->quant_N, targets}, {h->dq, (size_t)h->B * h->A, dq}};
+  const FloatSpan spans[2] = {{h->quant_targets, (size_t)h->B * h->opt.quant_N, targets}, {h->dq, (size_t)h->B * h->A, dq}};
   return read_spans(h, spans, 2);
 }
 extern "C" int sdqn_net_get_quantiles(sdqn_net_t h, int* N) {
   ARGCHK(h, "NULL handle");
-  if (N) *N = h->quant_N;
+  if (N) *N = h->opt.quant_N;
   return SDQN_OK;
 }
 // the host restatement of one sample of the quantile head (no device): quantile.h's quantile_sample on float rows
@@ -775,13 +788,13 @@ extern "C" int sdqn_quantile_act(const float* q, int N, int A, int* action) {
 // ---- --dueling: the dueling architecture (sdqn.h; dueling.h) ----------------------------------------------------------------
 extern "C" int sdqn_net_set_dueling(sdqn_net_t h, int on) {
   ARGCHK(h, "NULL handle");
+  TrainOptions next = h->opt;
+  next.dueling = on != 0;
   if (on) {
     ARGCHK(h->A >= 2, "dueling needs a network with actions + 1 >= 2 outputs, this one has %d", h->A);
     REFUSE_CONFLICTS(h, OPT_DUELING);
-    if (!h->gen && !h->duel_step) { int r_ = dalloc(h, (void**)&h->duel_step, (size_t)2 * h->B * sizeof(float)); if (r_) return r_; }
   }
-  if (h->gen) GENCHK(h->gen->set_dueling(on != 0));
-  h->dueling = on != 0;
+  { int rc_ = commit_options(h, next); if (rc_) return rc_; }
   if (!on) return SDQN_OK;
   // the weights as they stand (the online net's and the target's) take the block mask now; sdqn_net_set_weights repeats it on whatever it is handed
   if (h->gen) { GENCHK(h->gen->dueling_mask_weights(0)); GENCHK(h->gen->dueling_mask_weights(1)); return SDQN_OK; }
@@ -793,13 +806,13 @@ extern "C" int sdqn_net_set_dueling(sdqn_net_t h, int on) {
 }
 extern "C" int sdqn_net_get_dueling(sdqn_net_t h, int* on) {
   ARGCHK(h, "NULL handle");
-  if (on) *on = h->dueling ? 1 : 0;
+  if (on) *on = h->opt.dueling ? 1 : 0;
   return SDQN_OK;
 }
 // what the last train step's dueling head left: y, delta and the dq rows, widened to double (every path; a test's view)
 extern "C" int sdqn_net_last_dueling_step(sdqn_net_t h, double* y, double* delta, double* dq) {
   ARGCHK(h, "NULL handle");
-  ARGCHK(h->dueling, "the network is not a dueling net (sdqn_net_set_dueling)");
+  ARGCHK(h->opt.dueling, "the network is not a dueling net (sdqn_net_set_dueling)");
   if (h->gen) { GENCHK(h->gen->last_dueling_step(y, delta, dq)); return SDQN_OK; }
   const size_t nb = (size_t)h->B;
   const FloatSpan spans[3] = {{h->duel_step, nb, y}, {h->duel_step + nb, nb, delta}, {h->dq, nb * h->A, dq}};
@@ -921,21 +934,23 @@ extern "C" int sdqn_noisy_noise(uint64_t seed, uint64_t step, int slot, int laye
 
 extern "C" int sdqn_net_set_option(sdqn_net_t h, const char* name, int value) {
   ARGCHK(h && name, "NULL argument");
-  if (!strcmp(name, "double_dqn") && value) REFUSE_CONFLICTS(h, OPT_DOUBLE_DQN);
+  // the two target options that are set by name (train_options.h), on either path
+  if (!strcmp(name, "double_dqn")) {                      // Double DQN targets (van Hasselt et al. 2016): sdqn.h
+    if (value) REFUSE_CONFLICTS(h, OPT_DOUBLE_DQN);         // (in front of the range check, the one setter where it is: the order its two messages always had)
+    ARGCHK(value == 0 || value == 1, "double_dqn must be 0 or 1");
+    TrainOptions next = h->opt;
+    next.double_dqn = value != 0;
+    return commit_options(h, next);
+  }
   if (!strcmp(name, "n_step")) {                          // n-step returns: sdqn.h
     ARGCHK(value >= 1 && value <= SDQN_MAX_N_STEP, "n_step %d out of range [1, %d]", value, SDQN_MAX_N_STEP);
-    ARGCHK(!(value > 1 && h->al_persistent), "n_step %d cannot be combined with persistent_advantage: it repeats the action in the NEXT state", value);
-    h->n_step = value;
-    if (h->gen) h->gen->set_nstep(value, nstep_gamma_n(value, h->cfg.discount_rate));
-    return SDQN_OK;
+    ARGCHK(!(value > 1 && h->opt.al_persistent), "n_step %d cannot be combined with persistent_advantage: it repeats the action in the NEXT state", value);
+    TrainOptions next = h->opt;
+    next.n_step = value; next.gamma_n = nstep_gamma_n(value, h->cfg.discount_rate);
+    return commit_options(h, next);
   }
   if (h->gen) {                                   // the generic path has no tuning knobs; the ones that change semantics are refused
     if (!strcmp(name, "dp_overlap") && value < 0) return SDQN_OK;      // (auto: nothing to overlap without a communicator)
-    if (!strcmp(name, "double_dqn")) {
-      ARGCHK(value == 0 || value == 1, "double_dqn must be 0 or 1");
-      GENCHK(h->gen->set_double_dqn(value != 0));
-      return SDQN_OK;
-    }
     if (!strcmp(name, "grad_only") || !strcmp(name, "dp_overlap") || !strcmp(name, "keep_gradients")) {
       ARGCHK(value == 0 || !strcmp(name, "keep_gradients"), "option %s is implemented for the 84x84x4 float32 / float16 configurations", name);
     }
@@ -944,12 +959,7 @@ extern "C" int sdqn_net_set_option(sdqn_net_t h, const char* name, int value) {
   bool retired = !strncmp(name, "rb:", 3) || !strncmp(name, "btx:", 4);            // (switching one of them OFF stays a no-op, as before)
   for (int i = 0; RETIRED_OPTIONS[i]; ++i) retired = retired || !strcmp(name, RETIRED_OPTIONS[i]);
   if (retired) { if (value) RETIRED_OPTION_REFUSED(name); return SDQN_OK; }
-  if (!strcmp(name, "double_dqn")) {                      // Double DQN targets (van Hasselt et al. 2016): sdqn.h
-    ARGCHK(value == 0 || value == 1, "double_dqn must be 0 or 1");
-    if (value) { int r_ = ensure_slots3(h); if (r_) return r_; }
-    h->double_dqn = value != 0;
-  }
-  else if (!strcmp(name, "keep_gradients")) h->keep_grads = value != 0;
+  if (!strcmp(name, "keep_gradients")) h->keep_grads = value != 0;
   else if (!strcmp(name, "grad_only")) { ARGCHK(!(value && h->noisy), "grad_only (data parallel) cannot be combined with noisy_nets: sigma's gradient is not exchanged"); h->grad_only = value != 0; }
   else if (!strcmp(name, "h16_wgrad_mfma")) h->h16_wgrad_mfma = value != 0;
   else if (!strcmp(name, "c1w_in_wgrads")) { if (value < 0 || value > 2) { set_error("bad c1w_in_wgrads (0..2)"); return SDQN_ERR_ARG; } h->c1w_in_wgrads = value; }
@@ -1040,7 +1050,7 @@ extern "C" int sdqn_net_debug_read(sdqn_net_t h, const char* name, float* out, i
     {"a4", h->a4, (int64_t)2 * B * NFC}, {"d4", h->d4, (int64_t)B * NFC}, {"d3p", h->d3p, (int64_t)B * PD3 * PD3 * K3},
     {"d3", h->d3, (int64_t)B * PIX3 * K3}, {"d2p", h->d2p, (int64_t)B * PD2 * PD2 * K2}, {"d1", h->d1, (int64_t)B * PIX1 * K1}, {"q", h->q, (int64_t)2 * B * h->A},
     {"dq", h->dq, (int64_t)B * h->A}, {"g", h->g, h->NP}, {"theta", h->theta, h->NP}, {"cost_terms", h->cost_terms, B},
-    {"quantile_targets", h->quant_targets, h->quant_targets ? (int64_t)B * h->quant_N : 0},
+    {"quantile_targets", h->quant_targets, h->quant_targets ? (int64_t)B * h->opt.quant_N : 0},
     {"dueling_step", h->duel_step, h->duel_step ? (int64_t)2 * B : 0},
     // --noisy_nets: the factor vectors last composed [2][NOISY_EPS_NET]; the effective buffers (online / target); g_sigma (option keep_gradients)
     {"noisy_eps", h->nz_eps, h->nz_eps ? (int64_t)2 * NOISY_EPS_NET : 0}, {"noisy_theta", h->nz_eff[0], h->nz_eff[0] ? h->NP : 0},
@@ -1060,9 +1070,9 @@ namespace sdqn { hipError_t set_timing_buffer(unsigned long long* p); }
 // experiment-only build (make timing): run ONE kernel id of the step with phase stamps; returns [blocks][8] cycles
 extern "C" int sdqn_debug_time_kernel(sdqn_net_t h, sdqn_replay_t r, const int64_t* idx_host, int kernel, unsigned long long* out, int max_blocks) {
   ARGCHK(h && r && idx_host && out, "NULL");
-  ARGCHK(kernel != K_HEAD || h->boot_K == 1, "bootstrap_heads %d: this hook launches the standard head, not the step's bootstrap head", h->boot_K);
-  ARGCHK(kernel != K_HEAD || h->quant_N == 1, "quantiles %d: this hook launches the standard head, not the step's quantile head", h->quant_N);
-  ARGCHK(kernel != K_HEAD || !h->dueling, "dueling: this hook launches the standard head, not the step's dueling head");
+  ARGCHK(kernel != K_HEAD || h->opt.boot_K == 1, "bootstrap_heads %d: this hook launches the standard head, not the step's bootstrap head", h->opt.boot_K);
+  ARGCHK(kernel != K_HEAD || h->opt.quant_N == 1, "quantiles %d: this hook launches the standard head, not the step's quantile head", h->opt.quant_N);
+  ARGCHK(kernel != K_HEAD || !h->opt.dueling, "dueling: this hook launches the standard head, not the step's dueling head");
   unsigned long long* d = nullptr;
   HIPCHK(hipMalloc((void**)&d, (size_t)max_blocks * 64));
   HIPCHK(hipMemset(d, 0, (size_t)max_blocks * 64));

@@ -31,14 +31,14 @@ StepArgs step_args(sdqn_net_s* h) {
   a.theta_w = h->theta; a.state = h->state; a.bsz = (float)h->B;
   a.rho = (float)h->cfg.decay_rate; a.one_minus_rho = (float)(1.0 - h->cfg.decay_rate);
   a.lr = (float)h->cfg.learning_rate; a.eps = (float)h->cfg.epsilon;
-  a.post_off = h->n_step;                  // ring paths: poststate = state(i + n - 1) (problems.h soff)
+  a.post_off = h->opt.n_step;                  // ring paths: poststate = state(i + n - 1) (problems.h soff)
   return a;
 }
 double nstep_gamma_n(int n, double gamma) { double g = 1.0; for (int k = 0; k < n; ++k) g = g * gamma; return g; }
 int nstep_match(const sdqn_net_s* h, const sdqn_replay_s* r) {
   const int rn = r->ns.n > 1 ? r->ns.n : 1;
-  if (rn == 1 && h->n_step == 1) return SDQN_OK;
-  ARGCHK(rn == h->n_step, "replay memory n_step %d != network n_step %d", rn, h->n_step);
+  if (rn == 1 && h->opt.n_step == 1) return SDQN_OK;
+  ARGCHK(rn == h->opt.n_step, "replay memory n_step %d != network n_step %d", rn, h->opt.n_step);
   ARGCHK(r->ns.gamma == h->cfg.discount_rate, "replay memory n-step discount %.17g != network discount_rate %.17g", r->ns.gamma, h->cfg.discount_rate);
   ARGCHK(r->ns.min_reward == h->cfg.min_reward && r->ns.max_reward == h->cfg.max_reward,
          "replay memory n-step reward clip [%g, %g] != network [%g, %g]", r->ns.min_reward, r->ns.max_reward, h->cfg.min_reward, h->cfg.max_reward);
@@ -50,7 +50,7 @@ HeadArgs head_args(sdqn_net_s* h, int train) {
   hd.q = h->q; hd.maxq = h->maxq; hd.dq = h->dq; hd.cost_terms = h->cost_terms;
   hd.discount = h->cfg.discount_rate; hd.min_reward = h->cfg.min_reward; hd.max_reward = h->cfg.max_reward;
   hd.clip_error = (float)h->cfg.clip_error; hd.train = train;
-  if (h->n_step > 1) { hd.nstep = h->n_step; hd.gamma_n = nstep_gamma_n(h->n_step, h->cfg.discount_rate); }
+  if (h->opt.n_step > 1) { hd.nstep = h->opt.n_step; hd.gamma_n = h->opt.gamma_n; }      // (gamma_n is the n_step setter's: whoever fills a TrainOptions by hand with n_step > 1 sets it too, nstep_gamma_n)
   return hd;
 }
 // Overlapped data parallel: the previous step's fc4 all-reduce + update may still be running on g_comm.  Everything
@@ -114,9 +114,9 @@ static int forward(sdqn_net_s* h, const StepArgs& a, const HeadArgs& hd, const L
   { int rc = join_comm(h); if (rc) return rc; }                // conv1..3 of this step overlap the previous step's fc4 all-reduce
   PLANNED_LAUNCH(K_FC4_FWD, f, l);
   BN_FWD(3);
-  const BootArgs boot = {h->boot_K, game_actions(h), h->boot_thresh, bootstrap_mask_seed(h->boot_seed), a.idx};   // (read when HEAD_BOOTSTRAP; the ring indexes: set by the ring paths alone)
-  const QuantArgs quant = {h->quant_N, game_actions(h), h->quant_targets};      // (read when HEAD_QUANTILE)
-  const DuelArgs duel = {h->dueling ? 1 : 0, game_actions(h), h->duel_step};      // (read when HEAD_DUELING)
+  const BootArgs boot = {h->opt.boot_K, game_actions(h), h->opt.boot_thresh, bootstrap_mask_seed(h->opt.boot_seed), a.idx};   // (read when HEAD_BOOTSTRAP; the ring indexes: set by the ring paths alone)
+  const QuantArgs quant = {h->opt.quant_N, game_actions(h), h->quant_targets};      // (read when HEAD_QUANTILE)
+  const DuelArgs duel = {h->opt.dueling ? 1 : 0, game_actions(h), h->duel_step};      // (read when HEAD_DUELING)
   LAUNCH(K_HEAD, launch_head(f, hd, g_stream, h->head_q_system, &boot, &quant, &duel));      // (head_q_system: the acting path, never with batch_norm)
   return SDQN_OK;
 }
@@ -170,7 +170,7 @@ static UpdateForm update_form_of(const sdqn_net_s* h, StepStructure structure) {
   if (h->grad_only) return UPD_GRAD_ONLY;
   // --dueling masks g between its sums and their application: the split tail a clipped step runs, with or without the clip's own launches
   // --noisy_nets forms g_sigma from g between the same two launches
-  return (clip_on(h) || h->dueling || h->noisy) ? UPD_CLIP : UPD_SINGLE;
+  return (clip_on(h) || h->opt.dueling || h->noisy) ? UPD_CLIP : UPD_SINGLE;
 }
 UpdateForm update_form(const sdqn_net_s* h) { return update_form_of(h, step_structure(h)); }
 // --clip_grad_norm: g holds the complete gradient sums (all layers [+ the BatchNorm beta | gamma block]); bsz is the divisor the
@@ -194,7 +194,7 @@ extern "C" int sdqn_net_step_structure(sdqn_net_t h, int* structure, int* update
 // the online slot's training-mode BatchNorm pass updates the running statistics that an inference-mode third slot of the same launch
 // would read, so there it is a forward of its own in front of the step (run_extra_forward: online weights, poststates, running
 // statistics as they stand before the step).  Without a target net (theta- aliases theta) Double DQN is standard DQN: nothing changes.
-bool ddqn_active(const sdqn_net_s* h) { return h->double_dqn && h->theta_t != h->theta; }
+bool ddqn_active(const sdqn_net_s* h) { return h->opt.double_dqn && h->theta_t != h->theta; }
 // A forward of its own in front of the step: the predict forward (nz = 1) of weight slot `wz` (0 online, 1 target: the net's theta and
 // its wh / wht / w1p copies move to slot-0 position) on state slot `sz` (0 prestates; 1 poststates: post_off frames further in the ring,
 // replay_memory.py:71-72, or the second half of the [2][B][STATE] staging), its Q-values left in q slot 2.  It uses slot 0 of the
@@ -278,7 +278,7 @@ StepPlan step_plan(const sdqn_net_s* h) {
   else if (p.update == UPD_DP_SERIAL) t.exchange = (h->cfg.datatype == 1 && h->dp_half && h->gh) ? XCH_HALF : XCH_F32;
   t.ovf = t.exchange == XCH_HALF;
   t.clip = clip_on(h) && (p.update == UPD_CLIP || p.update == UPD_DP_SERIAL);      // the all-reduced gradient, every rank alike
-  t.mask = h->dueling && p.update != UPD_GRAD_ONLY;                                // likewise, in every applying form (fc5 is never applied on the side stream)
+  t.mask = h->opt.dueling && p.update != UPD_GRAD_ONLY;                                // likewise, in every applying form (fc5 is never applied on the side stream)
   t.noisy = h->noisy && p.update == UPD_CLIP;                                      // --noisy_nets (single GPU only: sdqn_net_set_noisy): the sigma launch; run_train composes around the step
   t.apply_mode = p.update == UPD_SINGLE ? 0 : p.update == UPD_GRAD_ONLY ? -1 : 2;
   t.divisor = (double)h->B * (double)(h->comm ? h->nranks : 1);
@@ -376,9 +376,9 @@ int run_train(sdqn_net_s* h, const StepArgs& a0, const HeadArgs& hd0, const Prep
   }
   HeadArgs hd = hd0;
   if (plan.head_train) hd.train = plan.head_train;
-  if (plan.head_train == HEAD_MUNCHAUSEN) { hd.mu_alpha = h->mu_alpha; hd.mu_tau = h->mu_tau; hd.mu_clip = h->mu_clip; }
-  if (plan.head_train == HEAD_ADVANTAGE) { hd.al_alpha = h->al_alpha; hd.al_persistent = h->al_persistent ? 1 : 0; }
-  if (plan.head_train == HEAD_CQL) hd.cql_alpha = h->cql_alpha;
+  if (plan.head_train == HEAD_MUNCHAUSEN) { hd.mu_alpha = h->opt.mu_alpha; hd.mu_tau = h->opt.mu_tau; hd.mu_clip = h->opt.mu_clip; }
+  if (plan.head_train == HEAD_ADVANTAGE) { hd.al_alpha = h->opt.al_alpha; hd.al_persistent = h->opt.al_persistent ? 1 : 0; }
+  if (plan.head_train == HEAD_CQL) hd.cql_alpha = h->opt.cql_alpha;
   if (plan.extra_fwd) { int rc0 = run_extra_forward(h, a, plan.extra_fwd == 1, plan.extra_fwd == 2, plan.launch); if (rc0) return rc0; }
   StepArgs af = a; af.nz = plan.nz;        // the forward's arguments (the backward keeps a: its launches know two slots only)
   int rc = forward(h, af, hd, plan.launch); if (rc) return rc;
@@ -507,18 +507,18 @@ static int train_host_tuple(sdqn_net_t h, const uint8_t* pre, const uint8_t* act
     r->mb_clean_declared = false; r->mb_clean_on_device = false;          // one-shot, whoever it was meant for
   }
   ARGCHK(h && pre && actions && rewards && post && terminals, "NULL argument");
-  if (returns) ARGCHK(h->n_step > 1, "sdqn_net_train_host_returns needs option n_step > 1 (network n_step %d)", h->n_step);
-  else ARGCHK(h->n_step == 1, "network n_step %d: integer rewards are refused, train with returns (sdqn_net_train_host_returns)", h->n_step);
+  if (returns) ARGCHK(h->opt.n_step > 1, "sdqn_net_train_host_returns needs option n_step > 1 (network n_step %d)", h->opt.n_step);
+  else ARGCHK(h->opt.n_step == 1, "network n_step %d: integer rewards are refused, train with returns (sdqn_net_train_host_returns)", h->opt.n_step);
   for (int i = 0; i < h->B; ++i) ARGCHK(actions[i] < game_actions(h), "action %d out of range at %d", (int)actions[i], i);
-  ARGCHK(h->boot_K == 1 || h->boot_P >= 1.0, "%s: bootstrap_mask_probability %g < 1 needs the ring index of every sample — train from the replay memory "
+  ARGCHK(h->opt.boot_K == 1 || h->opt.boot_P >= 1.0, "%s: bootstrap_mask_probability %g < 1 needs the ring index of every sample — train from the replay memory "
          "(sdqn_net_train_many / sdqn_net_train_replay); the tuple path serves bootstrap_heads %d with probability 1 only",
-         returns ? "sdqn_net_train_host_returns" : "sdqn_net_train_host", h->boot_P, h->boot_K);
+         returns ? "sdqn_net_train_host_returns" : "sdqn_net_train_host", h->opt.boot_P, h->opt.boot_K);
   const bool ours = owner != nullptr;
   if (ours) { int rcn = nstep_match(h, owner); if (rcn) return rcn; rcn = check_replay_geometry(h, owner); if (rcn) return rcn; }
-  ARGCHK(h->boot_K == 1 || !per_owns_minibatch(owner), "bootstrap_heads %d cannot be combined with prioritized_replay", h->boot_K);
-  ARGCHK(h->quant_N == 1 || !per_owns_minibatch(owner), "quantiles %d cannot be combined with prioritized_replay", h->quant_N);
+  ARGCHK(h->opt.boot_K == 1 || !per_owns_minibatch(owner), "bootstrap_heads %d cannot be combined with prioritized_replay", h->opt.boot_K);
+  ARGCHK(h->opt.quant_N == 1 || !per_owns_minibatch(owner), "quantiles %d cannot be combined with prioritized_replay", h->opt.quant_N);
   if (h->gen) {
-    if (h->boot_K > 1) GENCHK(h->gen->boot_idx(nullptr));
+    if (h->opt.boot_K > 1) GENCHK(h->gen->boot_idx(nullptr));
     const bool per = per_owns_minibatch(owner);                 // prioritized memory: weighted step + priority write-back
     if (per) per_gen_arm(h, owner);
     const hipError_t ge = reuse ? h->gen->train_dev_host_meta(owner->d_pre, owner->d_post, actions, rewards, terminals, h->epoch)
@@ -654,7 +654,7 @@ static int gen_train_replay(sdqn_net_s* h, sdqn_replay_s* r, const int64_t* idx_
   rc = replay_push_idx(r, idx_host, &slot, &didx); if (rc) return rc;
   rc = replay_gather_generic(r, didx); if (rc) return rc;
   if (h->shift_P > 0) { rc = shift_minibatch(h, r, didx); if (rc) return rc; }      // --random_shift: the states again, shifted; (a, r, t) stay
-  if (h->boot_K > 1) GENCHK(h->gen->boot_idx(didx));                    // (copied on the stream, in front of the slot's release)
+  if (h->opt.boot_K > 1) GENCHK(h->gen->boot_idx(didx));                    // (copied on the stream, in front of the slot's release)
   rc = replay_release_idx_batched(r, slot, false); if (rc) return rc;
   GENCHK(h->gen->train_dev(r->d_pre, r->d_post, r->d_act, r->d_rew, r->d_term, h->epoch));
   return gen_step_done(h);
@@ -669,8 +669,8 @@ int check_replay_geometry(const sdqn_net_s* h, const sdqn_replay_s* r) {
 // what the entry points that train from a replay memory ask first: its batch size, n-step settings and geometry are the network's
 static int check_replay_fits(const sdqn_net_s* h, const sdqn_replay_s* r) {
   ARGCHK(r->B == h->B, "replay batch_size %d != network batch_size %d", r->B, h->B);
-  ARGCHK(h->boot_K == 1 || !r->per, "bootstrap_heads %d cannot be combined with prioritized_replay", h->boot_K);
-  ARGCHK(h->quant_N == 1 || !r->per, "quantiles %d cannot be combined with prioritized_replay", h->quant_N);
+  ARGCHK(h->opt.boot_K == 1 || !r->per, "bootstrap_heads %d cannot be combined with prioritized_replay", h->opt.boot_K);
+  ARGCHK(h->opt.quant_N == 1 || !r->per, "quantiles %d cannot be combined with prioritized_replay", h->opt.quant_N);
   const int rc = nstep_match(h, r);
   return rc ? rc : check_replay_geometry(h, r);
 }

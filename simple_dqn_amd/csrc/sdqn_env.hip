@@ -380,7 +380,7 @@ static int env_check(sdqn_net_t h, sdqn_env_t e, int N, double epsilon, const En
   g.hist = h->gen ? h->cfg.history_length : C0; g.H = h->gen ? h->cfg.screen_height : H0; g.W = h->gen ? h->cfg.screen_width : W0;
   g.state = (size_t)g.hist * g.H * g.W; g.half = (size_t)h->B * g.state;
   ARGCHK(e->H == g.H && e->W == g.W, "the environment's screen (%d x %d) and the network's (%d x %d) differ", e->H, e->W, g.H, g.W);
-  ARGCHK(h->A == h->boot_K * h->quant_N * G::ACTIONS + (h->dueling ? 1 : 0), "the network has %d actions, %s has %d", game_actions(h), G::NAME, G::ACTIONS);
+  ARGCHK(h->A == net_outputs(h->opt, G::ACTIONS), "the network has %d actions, %s has %d", game_actions(h), G::NAME, G::ACTIONS);
   ARGCHK(N >= 1 && N <= h->B, "num_envs %d out of range [1, batch_size %d]", N, h->B);
   ARGCHK(epsilon >= 0.0 && epsilon <= 1.0, "epsilon %g out of range [0, 1]", epsilon);
   ARGCHK(!o.trace() || (o.tr_actions && o.tr_rewards && o.tr_terminals && o.tr_q), "the trace buffers come together: all four or none");
@@ -416,17 +416,17 @@ struct EnvTrace {
 // K = 1: nothing is launched, the kernel reads the forward's rows.
 template <class G>
 static int env_select(sdqn_net_t h, EvalArgs& a, int vote) {
-  if (h->boot_K == 1 && h->quant_N == 1 && !h->dueling) return SDQN_OK;
+  if (output_multiplier(h->opt) == 1 && !h->opt.dueling) return SDQN_OK;
   if (!h->boot_q) { int rc = dalloc(h, &h->boot_q, (size_t)h->B * MAX_ACTIONS * sizeof(double)); if (rc) return rc; }
   // counted like the game kernel it feeds: collect's lockstep under K_COLLECT, eval's not at all
-#define BOOT_SELECT launch_bootstrap_select(a.q, h->boot_q, a.q_f64 != 0, a.N, h->boot_K, a.A, vote, bootstrap_head_seed(h->boot_seed), a.envs, \
+#define BOOT_SELECT launch_bootstrap_select(a.q, h->boot_q, a.q_f64 != 0, a.N, h->opt.boot_K, a.A, vote, bootstrap_head_seed(h->opt.boot_seed), a.envs, \
                                             sizeof(EvalRec<G>), offsetof(EvalRec<G>, episodes), g_stream)
   // --quantiles N > 1 (refused together with bootstrap heads): the mean over the quantiles, collecting and evaluating alike
-#define QUANT_MEAN launch_quantile_mean(a.q, h->boot_q, a.q_f64 != 0, a.N, h->quant_N, a.A, g_stream)
+#define QUANT_MEAN launch_quantile_mean(a.q, h->boot_q, a.q_f64 != 0, a.N, h->opt.quant_N, a.A, g_stream)
   // --dueling (refused together with both): Q = V + Adv - mean(Adv), collecting and evaluating alike
 #define DUEL_Q launch_dueling_q(a.q, h->boot_q, a.q_f64 != 0, a.N, a.A, g_stream)
-  if (h->dueling) { if (vote) HIPCHK(DUEL_Q); else LAUNCH(K_COLLECT, DUEL_Q); }
-  else if (h->quant_N > 1) { if (vote) HIPCHK(QUANT_MEAN); else LAUNCH(K_COLLECT, QUANT_MEAN); }
+  if (h->opt.dueling) { if (vote) HIPCHK(DUEL_Q); else LAUNCH(K_COLLECT, DUEL_Q); }
+  else if (h->opt.quant_N > 1) { if (vote) HIPCHK(QUANT_MEAN); else LAUNCH(K_COLLECT, QUANT_MEAN); }
 #undef DUEL_Q
   else if (vote) HIPCHK(BOOT_SELECT); else LAUNCH(K_COLLECT, BOOT_SELECT);
 #undef QUANT_MEAN

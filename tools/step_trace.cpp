@@ -202,13 +202,13 @@ static void fill(sdqn_net_s* h, const Cfg& c) {
     NAMED(h->h_a1); NAMED(h->h_a2); NAMED(h->h_a3); NAMED(h->h_d4); NAMED(h->h_d3p); NAMED(h->h_d3); NAMED(h->h_d2p); NAMED(h->h_d2); NAMED(h->h_d1);
     NAMED(h->wh[0]); NAMED(h->wh[1]); NAMED(h->wht[0]); NAMED(h->wht[1]); NAMED(h->gh); NAMED(h->ovf_flag); NAMED(h->ovf_count);
   }
-  if (g_quantiles > 1) { h->cfg.num_actions = h->A = MAX_ACTIONS; h->quant_N = g_quantiles; h->NPW = OFF5 + (int64_t)h->A * NFC; h->NP = h->NPW; }
-  if (g_dueling) h->dueling = true;                                         // (A = 4: V and three advantages)
+  if (g_quantiles > 1) { h->cfg.num_actions = h->A = MAX_ACTIONS; h->opt.quant_N = g_quantiles; h->NPW = OFF5 + (int64_t)h->A * NFC; h->NP = h->NPW; }
+  if (g_dueling) h->opt.dueling = true;                                         // (A = 4: V and three advantages)
   h->ev_g4 = (hipEvent_t)0x4000; h->ev_w4 = (hipEvent_t)0x5000;
   h->fused_launches = c.fused != 0; h->keep_grads = c.keep != 0; h->target_tau = 0.01;      // (every applied step ends with its blend line)
   if (c.clip) h->clip_grad_norm = 10.0;
-  if (c.tgt == T_DDQN) h->double_dqn = h->slots3 = true;
-  if (c.tgt == T_MUNCH) h->munchausen = h->slots3 = true;
+  if (c.tgt == T_DDQN) h->opt.double_dqn = h->slots3 = true;
+  if (c.tgt == T_MUNCH) h->opt.munchausen = h->slots3 = true;
   if (c.dp == DP_GRAD_ONLY) h->grad_only = true;
   if (c.dp == DP_SERIAL || c.dp == DP_SERIAL_F32 || c.dp == DP_OVERLAP) { NAMED(h->comm); h->nranks = 2; h->rank = 1; }
   if (c.dp == DP_SERIAL_F32) h->dp_half = 0;
@@ -309,7 +309,7 @@ static void fill_events(sdqn_net_s* h, const Ev& e) {
   NAMED(h->state2);
   if (e.dt == 2) h->w1p[0] = h->w1p[1] = nullptr;                             // (as sdqn_net_create leaves a float16 net)
   if (!e.target) { h->cfg.target_enabled = 0; h->theta_t = h->theta; h->w1p[1] = h->w1p[0]; h->wh[1] = h->wh[0]; h->wht[1] = h->wht[0]; }
-  h->dueling = e.dueling != 0;
+  h->opt.dueling = e.dueling != 0;
   if (e.dp == DP_OVERLAP) { NAMED(h->comm); NAMED(h->comm2); h->nranks = 1; h->rank = 0; h->dp_overlap = true; }      // one rank, the overlapped form
   h->target_tau = e.tau;
   if (e.reg) { h->reg_wd = 0.1; if (e.reg == 2) { h->reg_lambda = 0.01; NAMED(h->reg_anchor); } }

@@ -9,14 +9,14 @@
 // receives max_a qbar(s'_n)[a], as the standard head's.
 #pragma once
 #include <stdint.h>
-#include "env_catch.h"
+#include "hd.h"
 
 namespace sdqn {
 
 // max_k q[k] - q[act] of one Q row: every term is a stored value, so the gap of a maximiser is exactly +0.  The maximum is taken in double
 // with a comparison on both paths
 template <typename T>
-CATCH_HD double action_gap(const T* q, int A, int act) {
+SDQN_HD double action_gap(const T* q, int A, int act) {
   double v = (double)q[0];
   for (int k = 1; k < A; ++k) { const double x = (double)q[k]; v = x > v ? x : v; }
   return v - (double)q[act];
@@ -25,7 +25,7 @@ CATCH_HD double action_gap(const T* q, int A, int act) {
 // fmaxf on floats, the generic head with comparisons in T: td_rule.h), q_post is the row qbar(s'): the gap of the poststate is
 // m_post - q_post[act], so PAL reads the same maximum its y_std did
 template <typename T>
-CATCH_HD double advantage_target(double y_std, const T* q_pre, const T* q_post, int A, int act, double m_post, double alpha, int persistent,
+SDQN_HD double advantage_target(double y_std, const T* q_pre, const T* q_post, int A, int act, double m_post, double alpha, int persistent,
                                  int terminal) {
   double y = y_std - alpha * action_gap(q_pre, A, act);
   if (persistent && !terminal) {                       // PAL: the better of leaving act now and repeating it in s'

@@ -382,6 +382,14 @@ int step_applied(sdqn_net_s* h, bool interval_events);
 int regularize_launch(sdqn_net_s* h, double wd, double lambda, bool fuse);      // sdqn_api_regularize.hip
 int redo_event(sdqn_net_s* h);                                                  // sdqn_api_redo.hip
 int reset_event(sdqn_net_s* h);                                                 // sdqn_api_reset.hip
+// sdqn_redo_draw / sdqn_reset_draw: word `index` under an event's key and the initialiser's draw of it in `layer` of 1..layers
+inline int keyed_init_draw(uint64_t key, int64_t index, int layer, int layers, uint64_t* word, float* value) {
+  ARGCHK(index >= 0 && layer >= 1 && layer <= layers, "bad arguments (index %lld, layer %d of 1..%d)", (long long)index, layer, layers);
+  const uint64_t w = stream_keyed(key, (uint64_t)index);
+  if (word) *word = w;
+  if (value) *value = init_draw(w, layer);
+  return SDQN_OK;
+}
 inline bool redo_on(const sdqn_net_s* h) { return h->redo_interval > 0; }
 inline bool reset_on(const sdqn_net_s* h) { return h->reset_interval > 0; }
 inline bool regularizer_on(const sdqn_net_s* h) { return h->reg_wd > 0.0 || h->reg_lambda > 0.0; }

@@ -6,36 +6,36 @@
 //     maxq[n] = (T)((sum_k max_a Q_k(theta-, s')[a]) / K)                                                              (bootstrap_sample)
 //   mask   m_k(i) = 1 iff the 53-bit draw hash(mask_seed, ring index i, k) >> 11 lies below ceil(ldexp(P, 53)); P = 1: all ones, no hash
 //   acting k(e, ep) = hash(head_seed, copy e, episode number ep) mod K
-// with hash(s, a, b) three steps of the project's splitmix64 (env_catch.h: catch_next), the operands folded in between the steps, and
-// mask_seed / head_seed streams 0 / 1 of the seed given to sdqn_net_set_bootstrap (catch_stream_seed).  Nothing is stored: a transition
+// with hash(s, a, b) three steps of the project's generator (stream.h: stream_next), the operands folded in between the steps, and
+// mask_seed / head_seed streams 0 / 1 of the seed given to sdqn_net_set_bootstrap (stream_seed).  Nothing is stored: a transition
 // keeps its mask for as long as it sits in its ring slot, a copy keeps its Q-head for as long as its episode counter stands.
 #pragma once
 #include <stdint.h>
-#include "env_catch.h"
+#include "stream.h"
 #include "td_rule.h"
 
 namespace sdqn {
 
-CATCH_HD uint64_t bootstrap_hash(uint64_t seed, uint64_t a, uint64_t b) {
+SDQN_HD uint64_t bootstrap_hash(uint64_t seed, uint64_t a, uint64_t b) {
   uint64_t s = seed;
-  s = catch_next(s) ^ a;
-  s = catch_next(s) ^ b;
-  return catch_next(s);
+  s = stream_next(s) ^ a;
+  s = stream_next(s) ^ b;
+  return stream_next(s);
 }
-CATCH_HD uint64_t bootstrap_mask_seed(uint64_t seed) { return catch_stream_seed(seed, 0, 0); }
-CATCH_HD uint64_t bootstrap_head_seed(uint64_t seed) { return catch_stream_seed(seed, 0, 1); }
+SDQN_HD uint64_t bootstrap_mask_seed(uint64_t seed) { return stream_seed(seed, 0, 0); }
+SDQN_HD uint64_t bootstrap_head_seed(uint64_t seed) { return stream_seed(seed, 0, 1); }
 // thresh = ceil(ldexp(P, 53)); P = 1 gives 2^53, above every 53-bit draw
-CATCH_HD int bootstrap_mask_bit(uint64_t mask_seed, uint64_t thresh, int64_t index, int k) {
+SDQN_HD int bootstrap_mask_bit(uint64_t mask_seed, uint64_t thresh, int64_t index, int k) {
   if (thresh >= (1ull << 53)) return 1;
   return (bootstrap_hash(mask_seed, (uint64_t)index, (uint64_t)k) >> 11) < thresh ? 1 : 0;
 }
-CATCH_HD int bootstrap_head_of(uint64_t head_seed, int K, uint64_t copy, uint64_t episode) {
+SDQN_HD int bootstrap_head_of(uint64_t head_seed, int K, uint64_t copy, uint64_t episode) {
   return K <= 1 ? 0 : (int)(bootstrap_hash(head_seed, copy, episode) % (uint64_t)K);
 }
 // majority vote of the K per-head greedy actions (first maximum, a NaN counts as one: sdqn_net_act_greedy's rule); votes[A] receives the
 // counts, the winner is the lowest action with the most votes.  q: one raw row [K A]
 template <typename T>
-CATCH_HD int bootstrap_vote(const T* q, int K, int A, int* votes) {
+SDQN_HD int bootstrap_vote(const T* q, int K, int A, int* votes) {
   for (int a = 0; a < A; ++a) votes[a] = 0;
   for (int k = 0; k < K; ++k) {
     const T* r = q + k * A; int best = 0;
@@ -54,7 +54,7 @@ CATCH_HD int bootstrap_vote(const T* q, int K, int A, int* votes) {
 // LDS row.  *rows (may be nullptr) receives the bit mask of the dq rows that can be non-zero (K A <= 32 there), *maxq the mean of the K
 // maxima; returns the cost term.
 template <typename T, typename Ops>
-CATCH_HD T bootstrap_sample(const T* q_pre, const T* q_post, int K, int A, int act, double r, int terminal, double gam, T clip,
+SDQN_HD T bootstrap_sample(const T* q_pre, const T* q_post, int K, int A, int act, double r, int terminal, double gam, T clip,
                             uint64_t mask_seed, uint64_t thresh, int64_t index, T* dq, int* rows, T* maxq) {
   const T fK = (T)K;
   double msum = 0.0; T cost = (T)0;

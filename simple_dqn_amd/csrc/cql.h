@@ -10,12 +10,12 @@
 #pragma once
 #include <stdint.h>
 #include <math.h>
-#include "env_catch.h"
+#include "hd.h"
 
 namespace sdqn {
 
 template <typename T>
-CATCH_HD double cql_lse(const T* q, int A) {
+SDQN_HD double cql_lse(const T* q, int A) {
   double m = (double)q[0];
   for (int k = 1; k < A; ++k) { const double x = (double)q[k]; m = x > m ? x : m; }
   double s = 0.0;
@@ -23,18 +23,18 @@ CATCH_HD double cql_lse(const T* q, int A) {
   return m + log(s);
 }
 template <typename T>
-CATCH_HD T cql_grad(const T* q, int k, int act, double lse, double alpha) {
+SDQN_HD T cql_grad(const T* q, int k, int act, double lse, double alpha) {
   return (T)(alpha * (exp((double)q[k] - lse) - (k == act ? 1.0 : 0.0)));
 }
 template <typename T>
-CATCH_HD T cql_cost(const T* q, int act, double lse, double alpha) { return (T)(alpha * (lse - (double)q[act])); }
+SDQN_HD T cql_cost(const T* q, int act, double lse, double alpha) { return (T)(alpha * (lse - (double)q[act])); }
 
 // The whole rule on one sample, sequentially (the generic path's head branch and the host restatement sdqn_cql_loss; the tuned head computes
 // the same operations, one action per lane).  y: the standard target, in double; clip: clip_error (0: none); w: the importance weight of a
 // prioritized memory, else 1 (a product with 1 is exact: one text serves both).  The error is clipped first, then weighted.  dq[A] receives
 // the row, *delta_out (may be nullptr) the unclipped error; returns the cost term.
 template <typename T>
-CATCH_HD T cql_sample(const T* q, int A, int act, double y, double alpha, T clip, T w, T* dq, T* delta_out) {
+SDQN_HD T cql_sample(const T* q, int A, int act, double y, double alpha, T clip, T w, T* dq, T* delta_out) {
   const double lse = cql_lse(q, A);
   const T d = q[act] - (T)y;
   T dc = d;

@@ -13,18 +13,18 @@
 #pragma once
 #include <stdint.h>
 #include <math.h>
-#include "env_catch.h"
+#include "hd.h"
 
 namespace sdqn {
 
 template <typename T>
-CATCH_HD T dueling_q(const T* row, int A, int a) {
+SDQN_HD T dueling_q(const T* row, int A, int a) {
   double s = 0.0;
   for (int b = 0; b < A; ++b) s += (double)row[1 + b];
   return (T)(((double)row[0] + (double)row[1 + a]) - s / (double)A);
 }
 template <typename T>
-CATCH_HD int dueling_greedy(const T* row, int A, T* q_best) {
+SDQN_HD int dueling_greedy(const T* row, int A, T* q_best) {
   double s = 0.0;                                      // dueling_q's operations, the mean taken once
   for (int b = 0; b < A; ++b) s += (double)row[1 + b];
   const double mean = s / (double)A;
@@ -35,12 +35,12 @@ CATCH_HD int dueling_greedy(const T* row, int A, T* q_best) {
 }
 // the acting rule on one raw row [A + 1]: the greedy action above
 template <typename T>
-CATCH_HD int dueling_act(const T* row, int A) { T v; return dueling_greedy(row, A, &v); }
+SDQN_HD int dueling_act(const T* row, int A) { T v; return dueling_greedy(row, A, &v); }
 // fc5's block mask: 1 where entry (row, j) of the [A + 1][H] matrix belongs to the net, 0 where it is held at +0.0
-CATCH_HD int dueling_mask(int row, int j, int H) { return row == 0 ? (j < H / 2) : (j >= H / 2); }
+SDQN_HD int dueling_mask(int row, int j, int H) { return row == 0 ? (j < H / 2) : (j >= H / 2); }
 // the gradient into the A + 1 rows from c = dLoss / dQ(s, a_n)
 template <typename T>
-CATCH_HD void dueling_dq(T c, int A, int act, T* dq) {
+SDQN_HD void dueling_dq(T c, int A, int act, T* dq) {
   const T on = (T)(1.0 - 1.0 / (double)A), off = (T)(-1.0 / (double)A);
   dq[0] = c;
   for (int b = 0; b < A; ++b) dq[1 + b] = c * (b == act ? on : off);
@@ -52,7 +52,7 @@ CATCH_HD void dueling_dq(T c, int A, int act, T* dq) {
 // (|delta| + per_eps)^per_alpha of the unclipped error.  dq[A + 1] receives the row; returns the cost term; *y_out = (T)y,
 // *delta_out = delta, *maxq = max_a Q(theta-, s', a).
 template <typename T>
-CATCH_HD T dueling_sample(const T* q_pre, const T* q_post, int A, int act, double r, int terminal, double gam, T clip, int per, T w,
+SDQN_HD T dueling_sample(const T* q_pre, const T* q_post, int A, int act, double r, int terminal, double gam, T clip, int per, T w,
                           double per_alpha, double per_eps, T* dq, T* y_out, T* delta_out, T* maxq, float* prio) {
   T m; dueling_greedy(q_post, A, &m);
   *maxq = m;

@@ -1,6 +1,6 @@
 // env_breakout.h — the game "breakout" (DESIGN.md §20): ONE definition in plain integer C++, compiled for the host (sdqn_env_* entry
 // points, the host mirrors of the fused act step) and for the device (the breakout_* kernels of sdqn_env.hip), like env_catch.h, whose
-// generator (catch_mix / catch_next / catch_stream_seed) and epsilon-greedy rule it shares.  No floating point, no library state.
+// generator (stream.h, drawn from with catch_next) and epsilon-greedy rule it shares.  No floating point, no library state.
 //
 //   court   12 x 12 cells of ch = H / 12 by cw = W / 12 pixels (integer division); pixels outside 12 ch x 12 cw stay 0
 //   state   ball (row, col, dx, dy), dx, dy in {-1, +1}; paddle left edge p (3 cells wide on row 11, 0 <= p <= 9); balls lost in this
@@ -29,21 +29,21 @@ struct BreakoutState {         // == sdqn_env_state_breakout (include/sdqn.h), 4
   uint64_t bricks, rng;
 };
 
-CATCH_HD bool breakout_brick_row(int r) { return r >= 1 && r <= BREAKOUT_BRICK_ROWS; }
-CATCH_HD uint64_t breakout_brick_bit(int r, int c) { return 1ull << (BREAKOUT_CELLS * (r - 1) + c); }
+SDQN_HD bool breakout_brick_row(int r) { return r >= 1 && r <= BREAKOUT_BRICK_ROWS; }
+SDQN_HD uint64_t breakout_brick_bit(int r, int c) { return 1ull << (BREAKOUT_CELLS * (r - 1) + c); }
 
-CATCH_HD void breakout_spawn(BreakoutState& s) {
+SDQN_HD void breakout_spawn(BreakoutState& s) {
   const uint64_t d = catch_next(s.rng);
   s.row = BREAKOUT_SPAWN_ROW; s.col = (int32_t)(d % BREAKOUT_CELLS); s.dx = ((d / BREAKOUT_CELLS) & 1) ? 1 : -1; s.dy = 1;
 }
-CATCH_HD void breakout_restart(BreakoutState& s) {      // new episode; the generator goes on (no reseed)
+SDQN_HD void breakout_restart(BreakoutState& s) {      // new episode; the generator goes on (no reseed)
   s.balls = 0; s.terminal = 0; s.paddle = 4; s.pad = 0; s.bricks = BREAKOUT_WALL;
   breakout_spawn(s);
 }
-CATCH_HD void breakout_init(BreakoutState& s, uint64_t seed) { s.rng = seed; breakout_restart(s); }
+SDQN_HD void breakout_init(BreakoutState& s, uint64_t seed) { s.rng = seed; breakout_restart(s); }
 
 // returns the reward (1: a brick broke); lost = 1 when the ball passed the paddle
-CATCH_HD int breakout_step(BreakoutState& s, int action, int balls_per_episode, int& lost) {
+SDQN_HD int breakout_step(BreakoutState& s, int action, int balls_per_episode, int& lost) {
   lost = 0;
   if (action == 1 && s.paddle > 0) s.paddle -= 1;
   if (action == 2 && s.paddle < BREAKOUT_CELLS - BREAKOUT_PADDLE) s.paddle += 1;
@@ -83,14 +83,14 @@ CATCH_HD int breakout_step(BreakoutState& s, int action, int balls_per_episode, 
 
 // what the renderer needs of a state, small enough to ride in kernel arguments
 struct BreakoutView { int32_t row, col, paddle; uint64_t bricks; };
-CATCH_HD BreakoutView breakout_view(const BreakoutState& s) {
+SDQN_HD BreakoutView breakout_view(const BreakoutState& s) {
   BreakoutView v; v.row = s.row; v.col = s.col; v.paddle = s.paddle; v.bricks = s.bricks; return v;
 }
 
 // Where a renderer stands: pixel (y, x), the cell column cx of x and x's offset rx inside that cell (cx >= 12: right of the court).  The
 // device makes one per 16-byte chunk (ONE division, first / W, by the caller; cx by four comparisons) and walks it byte by byte.
 struct BreakoutCursor { int32_t y, x, cx, rx; };
-CATCH_HD BreakoutCursor breakout_cursor(int y, int x, int cw) {
+SDQN_HD BreakoutCursor breakout_cursor(int y, int x, int cw) {
   int cx = 0;                                            // floor(x / cw), capped at 12, by bisection over the 13 cell boundaries
   if (x >= 8 * cw) cx = 8;
   if (x >= (cx + 4) * cw) cx += 4;
@@ -99,12 +99,12 @@ CATCH_HD BreakoutCursor breakout_cursor(int y, int x, int cw) {
   if (cx > BREAKOUT_CELLS) cx = BREAKOUT_CELLS;
   BreakoutCursor c; c.y = y; c.x = x; c.cx = cx; c.rx = x - cx * cw; return c;
 }
-CATCH_HD void breakout_advance(BreakoutCursor& c, int W, int cw) {
+SDQN_HD void breakout_advance(BreakoutCursor& c, int W, int cw) {
   if (++c.x == W) { c.x = 0; c.cx = 0; c.rx = 0; ++c.y; return; }
   if (++c.rx == cw && c.cx < BREAKOUT_CELLS) { c.rx = 0; ++c.cx; }
 }
 // one pixel, by comparisons only (the device calls this per byte): rows as range tests on y, columns through the cursor's cell column
-CATCH_HD uint8_t breakout_pixel(const BreakoutView& v, const BreakoutCursor& c, int ch) {
+SDQN_HD uint8_t breakout_pixel(const BreakoutView& v, const BreakoutCursor& c, int ch) {
   if ((unsigned)c.cx >= (unsigned)BREAKOUT_CELLS) return 0;
   if (c.cx == v.col && (unsigned)(c.y - v.row * ch) < (unsigned)ch) return (uint8_t)BREAKOUT_BALL_PIXEL;
   if (c.y >= ch && c.y < (BREAKOUT_BRICK_ROWS + 1) * ch) {
@@ -116,7 +116,7 @@ CATCH_HD uint8_t breakout_pixel(const BreakoutView& v, const BreakoutCursor& c, 
   return 0;
 }
 // the whole frame on the host: the same rectangles, filled
-CATCH_HD void breakout_render(const BreakoutView& v, uint8_t* out, int H, int W) {
+SDQN_HD void breakout_render(const BreakoutView& v, uint8_t* out, int H, int W) {
   const int ch = H / BREAKOUT_CELLS, cw = W / BREAKOUT_CELLS;
   for (int i = 0; i < H * W; ++i) out[i] = 0;
   for (int r = 1; r <= BREAKOUT_BRICK_ROWS; ++r)
@@ -127,7 +127,7 @@ CATCH_HD void breakout_render(const BreakoutView& v, uint8_t* out, int H, int W)
 }
 
 // every field in range, no brick bit above bit 35, the ball on rows 0 .. 10 and in no brick cell
-CATCH_HD bool breakout_state_valid(const BreakoutState& s) {
+SDQN_HD bool breakout_state_valid(const BreakoutState& s) {
   if (s.row < 0 || s.row > BREAKOUT_CELLS - 2 || s.col < 0 || s.col >= BREAKOUT_CELLS) return false;
   if ((s.dx != 1 && s.dx != -1) || (s.dy != 1 && s.dy != -1)) return false;
   if (s.paddle < 0 || s.paddle > BREAKOUT_CELLS - BREAKOUT_PADDLE || s.balls < 0 || (s.terminal != 0 && s.terminal != 1) || s.pad != 0) return false;
@@ -143,19 +143,19 @@ struct BreakoutGame {
   typedef BreakoutCursor Cursor;
   static constexpr int ACTIONS = BREAKOUT_ACTIONS, CELLS = BREAKOUT_CELLS, VIEW_WORDS = 5;
   static constexpr const char* NAME = "breakout";
-  CATCH_HD static void init(State& s, uint64_t seed) { breakout_init(s, seed); }
-  CATCH_HD static void restart(State& s) { breakout_restart(s); }
-  CATCH_HD static int step(State& s, int action, int bpe, int& lost) { return breakout_step(s, action, bpe, lost); }   // caught = bricks broken, missed = balls lost
-  CATCH_HD static View view(const State& s) { return breakout_view(s); }
-  CATCH_HD static bool valid(const State& s) { return breakout_state_valid(s); }
-  CATCH_HD static void render(const View& v, uint8_t* out, int H, int W) { breakout_render(v, out, H, W); }
-  CATCH_HD static void pack(const View& v, int* w) { w[0] = v.row; w[1] = v.col; w[2] = v.paddle; w[3] = (int)(uint32_t)v.bricks; w[4] = (int)(uint32_t)(v.bricks >> 32); }
-  CATCH_HD static View unpack(const int* w) {
+  SDQN_HD static void init(State& s, uint64_t seed) { breakout_init(s, seed); }
+  SDQN_HD static void restart(State& s) { breakout_restart(s); }
+  SDQN_HD static int step(State& s, int action, int bpe, int& lost) { return breakout_step(s, action, bpe, lost); }   // caught = bricks broken, missed = balls lost
+  SDQN_HD static View view(const State& s) { return breakout_view(s); }
+  SDQN_HD static bool valid(const State& s) { return breakout_state_valid(s); }
+  SDQN_HD static void render(const View& v, uint8_t* out, int H, int W) { breakout_render(v, out, H, W); }
+  SDQN_HD static void pack(const View& v, int* w) { w[0] = v.row; w[1] = v.col; w[2] = v.paddle; w[3] = (int)(uint32_t)v.bricks; w[4] = (int)(uint32_t)(v.bricks >> 32); }
+  SDQN_HD static View unpack(const int* w) {
     View v; v.row = w[0]; v.col = w[1]; v.paddle = w[2]; v.bricks = (uint64_t)(uint32_t)w[3] | ((uint64_t)(uint32_t)w[4] << 32); return v;
   }
-  CATCH_HD static Cursor cursor(int y, int x, int ch, int cw) { (void)ch; return breakout_cursor(y, x, cw); }
-  CATCH_HD static void advance(Cursor& c, int W, int ch, int cw) { (void)ch; breakout_advance(c, W, cw); }
-  CATCH_HD static uint8_t pixel(const View& v, const Cursor& c, int ch, int cw) { (void)cw; return breakout_pixel(v, c, ch); }
+  SDQN_HD static Cursor cursor(int y, int x, int ch, int cw) { (void)ch; return breakout_cursor(y, x, cw); }
+  SDQN_HD static void advance(Cursor& c, int W, int ch, int cw) { (void)ch; breakout_advance(c, W, cw); }
+  SDQN_HD static uint8_t pixel(const View& v, const Cursor& c, int ch, int cw) { (void)cw; return breakout_pixel(v, c, ch); }
 };
 
 }  // namespace sdqn

@@ -5,7 +5,7 @@
 //   frame_skip k   1 <= k <= 8: one agent step is up to k game ticks with the same chosen action; the rewards add up (|R| <= k);
 //                  a tick that sets terminal ends the agent step
 //   thresh_p       ceil(p 2^53) for repeat_action_probability p in [0, 1): before every tick ONE draw u of the copy's sticky generator
-//                  (splitmix64, stream 2 of catch_stream_seed); (u >> 11) < thresh_p: the tick executes `prev`, the action the last tick
+//                  (splitmix64, stream 2 of stream_seed); (u >> 11) < thresh_p: the tick executes `prev`, the action the last tick
 //                  executed, instead of the chosen one.  thresh_p == 0 draws nothing: the generator never moves
 //   prev           0 ("stay") after init and after every restart
 // Only the state after the last tick is rendered; callers record the CHOSEN action.
@@ -15,11 +15,11 @@
 namespace sdqn {
 
 constexpr int DYNAMICS_MAX_SKIP = 8;
-constexpr uint64_t DYNAMICS_STICKY_STREAM = 2;       // catch_stream_seed(seed, e, 2): the sticky generator of copy e
+constexpr uint64_t DYNAMICS_STICKY_STREAM = 2;       // stream_seed(seed, e, 2): the sticky generator of copy e
 
 // one agent step; returns the summed reward R; caught / lost: ticks with a positive reward / that lost a ball (the tallies' per-tick rule)
 template <class G>
-CATCH_HD int dynamics_step(typename G::State& s, int32_t& prev, uint64_t& sticky_rng, int action, int bpe, int frame_skip, uint64_t thresh_p,
+SDQN_HD int dynamics_step(typename G::State& s, int32_t& prev, uint64_t& sticky_rng, int action, int bpe, int frame_skip, uint64_t thresh_p,
                            int& caught, int& lost) {
   int R = 0;
   caught = 0; lost = 0;
@@ -40,6 +40,6 @@ CATCH_HD int dynamics_step(typename G::State& s, int32_t& prev, uint64_t& sticky
 }
 // a new episode: the game's own restart, and the emulator's reset to no-op
 template <class G>
-CATCH_HD void dynamics_restart(typename G::State& s, int32_t& prev) { G::restart(s); prev = 0; }
+SDQN_HD void dynamics_restart(typename G::State& s, int32_t& prev) { G::restart(s); prev = 0; }
 
 }  // namespace sdqn

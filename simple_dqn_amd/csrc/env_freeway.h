@@ -1,6 +1,6 @@
 // env_freeway.h — the game "freeway" (DESIGN.md §25): ONE definition in plain integer C++, compiled for the host (sdqn_env_* entry
 // points, the host mirrors of the fused act step) and for the device (the freeway_* kernels of sdqn_env.hip), like env_catch.h, whose
-// generator (catch_mix / catch_next / catch_stream_seed) and epsilon-greedy rule it shares.  No floating point, no library state.
+// generator (stream.h, drawn from with catch_next) and epsilon-greedy rule it shares.  No floating point, no library state.
 //
 //   court   12 x 12 cells of ch = H / 12 by cw = W / 12 pixels (integer division); pixels outside 12 ch x 12 cw stay 0
 //   state   the chicken's row (0 .. 11; its column is always 6); game ticks played in this episode; crossings made in it; terminal flag;
@@ -31,16 +31,16 @@ struct FreewayState {          // == sdqn_env_state_freeway (include/sdqn.h), 56
   uint64_t cars, timers, periods, rng;
 };
 
-CATCH_HD bool freeway_lane(int r) { return r >= FREEWAY_FIRST_LANE && r <= FREEWAY_LAST_LANE; }
-CATCH_HD int freeway_nibble(uint64_t w, int r) { return (int)((w >> (4 * (r - FREEWAY_FIRST_LANE))) & 15); }
-CATCH_HD uint64_t freeway_with_nibble(uint64_t w, int r, int v) {
+SDQN_HD bool freeway_lane(int r) { return r >= FREEWAY_FIRST_LANE && r <= FREEWAY_LAST_LANE; }
+SDQN_HD int freeway_nibble(uint64_t w, int r) { return (int)((w >> (4 * (r - FREEWAY_FIRST_LANE))) & 15); }
+SDQN_HD uint64_t freeway_with_nibble(uint64_t w, int r, int v) {
   const int sh = 4 * (r - FREEWAY_FIRST_LANE);
   return (w & ~(15ull << sh)) | ((uint64_t)v << sh);
 }
 // whether the car of traffic row `row` stands on the chicken's column (false on rows 0 and 11, which have no car)
-CATCH_HD bool freeway_car_at_chicken(uint64_t cars, int row) { return freeway_lane(row) && freeway_nibble(cars, row) == FREEWAY_COLUMN; }
+SDQN_HD bool freeway_car_at_chicken(uint64_t cars, int row) { return freeway_lane(row) && freeway_nibble(cars, row) == FREEWAY_COLUMN; }
 
-CATCH_HD void freeway_shuffle(FreewayState& s) {
+SDQN_HD void freeway_shuffle(FreewayState& s) {
   uint64_t d = catch_next(s.rng);
   uint64_t cars = 0, periods = 0;
   for (int r = FREEWAY_FIRST_LANE; r <= FREEWAY_LAST_LANE; ++r) {
@@ -51,14 +51,14 @@ CATCH_HD void freeway_shuffle(FreewayState& s) {
   }
   s.cars = cars; s.periods = periods; s.timers = periods;
 }
-CATCH_HD void freeway_restart(FreewayState& s) {       // new episode; the generator goes on (no reseed)
+SDQN_HD void freeway_restart(FreewayState& s) {       // new episode; the generator goes on (no reseed)
   s.row = FREEWAY_START_ROW; s.ticks = 0; s.crossings = 0; s.terminal = 0; s.pad0 = 0; s.pad1 = 0;
   freeway_shuffle(s);
 }
-CATCH_HD void freeway_init(FreewayState& s, uint64_t seed) { s.rng = seed; freeway_restart(s); }
+SDQN_HD void freeway_init(FreewayState& s, uint64_t seed) { s.rng = seed; freeway_restart(s); }
 
 // returns the reward (1: a crossing); lost = 1 when the chicken was hit
-CATCH_HD int freeway_step(FreewayState& s, int action, int episode_ticks, int& lost) {
+SDQN_HD int freeway_step(FreewayState& s, int action, int episode_ticks, int& lost) {
   lost = 0;
   int reward = 0;
   if (action == 1 && s.row > 0) s.row -= 1;
@@ -90,10 +90,10 @@ CATCH_HD int freeway_step(FreewayState& s, int action, int episode_ticks, int& l
 
 // what the renderer needs of a state, small enough to ride in kernel arguments
 struct FreewayView { int32_t row; uint64_t cars; };
-CATCH_HD FreewayView freeway_view(const FreewayState& s) { FreewayView v; v.row = s.row; v.cars = s.cars & FREEWAY_LANE_BITS; return v; }
+SDQN_HD FreewayView freeway_view(const FreewayState& s) { FreewayView v; v.row = s.row; v.cars = s.cars & FREEWAY_LANE_BITS; return v; }
 
 // floor(x / c), capped at 12, by bisection over the 13 cell boundaries (four comparisons, no division)
-CATCH_HD int freeway_cell(int x, int c) {
+SDQN_HD int freeway_cell(int x, int c) {
   int k = 0;
   if (x >= 8 * c) k = 8;
   if (x >= (k + 4) * c) k += 4;
@@ -105,13 +105,13 @@ CATCH_HD int freeway_cell(int x, int c) {
 // (cx, cy >= 12: right of / below the court).  The device makes one per 16-byte chunk (ONE division, first / W, by the caller; cx and cy by
 // four comparisons each: the range tests on y that find a pixel's traffic row) and walks it byte by byte.
 struct FreewayCursor { int32_t y, x, cx, rx, cy, ry; };
-CATCH_HD FreewayCursor freeway_cursor(int y, int x, int ch, int cw) {
+SDQN_HD FreewayCursor freeway_cursor(int y, int x, int ch, int cw) {
   FreewayCursor c; c.y = y; c.x = x;
   c.cx = freeway_cell(x, cw); c.rx = x - c.cx * cw;
   c.cy = freeway_cell(y, ch); c.ry = y - c.cy * ch;
   return c;
 }
-CATCH_HD void freeway_advance(FreewayCursor& c, int W, int ch, int cw) {
+SDQN_HD void freeway_advance(FreewayCursor& c, int W, int ch, int cw) {
   if (++c.x == W) {
     c.x = 0; c.cx = 0; c.rx = 0; ++c.y;
     if (++c.ry == ch && c.cy < FREEWAY_CELLS) { c.ry = 0; ++c.cy; }
@@ -120,7 +120,7 @@ CATCH_HD void freeway_advance(FreewayCursor& c, int W, int ch, int cw) {
   if (++c.rx == cw && c.cx < FREEWAY_CELLS) { c.rx = 0; ++c.cx; }
 }
 // one pixel, by comparisons and shifts only (the device calls this per byte)
-CATCH_HD uint8_t freeway_pixel(const FreewayView& v, const FreewayCursor& c) {
+SDQN_HD uint8_t freeway_pixel(const FreewayView& v, const FreewayCursor& c) {
   if ((unsigned)c.cx >= (unsigned)FREEWAY_CELLS || (unsigned)c.cy >= (unsigned)FREEWAY_CELLS) return 0;
   if (c.cy == v.row && c.cx == FREEWAY_COLUMN) return (uint8_t)FREEWAY_CHICKEN_PIXEL;
   if ((unsigned)(c.cy - FREEWAY_FIRST_LANE) <= (unsigned)(FREEWAY_LAST_LANE - FREEWAY_FIRST_LANE) &&
@@ -129,7 +129,7 @@ CATCH_HD uint8_t freeway_pixel(const FreewayView& v, const FreewayCursor& c) {
   return 0;
 }
 // the whole frame on the host: the same rectangles, filled
-CATCH_HD void freeway_render(const FreewayView& v, uint8_t* out, int H, int W) {
+SDQN_HD void freeway_render(const FreewayView& v, uint8_t* out, int H, int W) {
   const int ch = H / FREEWAY_CELLS, cw = W / FREEWAY_CELLS;
   for (int i = 0; i < H * W; ++i) out[i] = 0;
   for (int r = FREEWAY_FIRST_LANE; r <= FREEWAY_LAST_LANE; ++r)
@@ -139,7 +139,7 @@ CATCH_HD void freeway_render(const FreewayView& v, uint8_t* out, int H, int W) {
 
 // every field in range, every nibble in range (column <= 11, 1 <= timer <= period <= 5), no bit above the ten nibbles, the padding
 // zero, the chicken in no car's cell.  `ticks` has no upper bound: the episode length is the handle's, not the state's
-CATCH_HD bool freeway_state_valid(const FreewayState& s) {
+SDQN_HD bool freeway_state_valid(const FreewayState& s) {
   if (s.row < 0 || s.row >= FREEWAY_CELLS || s.ticks < 0 || s.crossings < 0 || (s.terminal != 0 && s.terminal != 1)) return false;
   if (s.pad0 != 0 || s.pad1 != 0) return false;
   if ((s.cars | s.timers | s.periods) & ~FREEWAY_LANE_BITS) return false;
@@ -157,17 +157,17 @@ struct FreewayGame {
   typedef FreewayCursor Cursor;
   static constexpr int ACTIONS = FREEWAY_ACTIONS, CELLS = FREEWAY_CELLS, VIEW_WORDS = 3;
   static constexpr const char* NAME = "freeway";
-  CATCH_HD static void init(State& s, uint64_t seed) { freeway_init(s, seed); }
-  CATCH_HD static void restart(State& s) { freeway_restart(s); }
-  CATCH_HD static int step(State& s, int action, int episode_ticks, int& lost) { return freeway_step(s, action, episode_ticks, lost); }   // caught = crossings, missed = hits
-  CATCH_HD static View view(const State& s) { return freeway_view(s); }
-  CATCH_HD static bool valid(const State& s) { return freeway_state_valid(s); }
-  CATCH_HD static void render(const View& v, uint8_t* out, int H, int W) { freeway_render(v, out, H, W); }
-  CATCH_HD static void pack(const View& v, int* w) { w[0] = v.row; w[1] = (int)(uint32_t)v.cars; w[2] = (int)(uint32_t)(v.cars >> 32); }
-  CATCH_HD static View unpack(const int* w) { View v; v.row = w[0]; v.cars = (uint64_t)(uint32_t)w[1] | ((uint64_t)(uint32_t)w[2] << 32); return v; }
-  CATCH_HD static Cursor cursor(int y, int x, int ch, int cw) { return freeway_cursor(y, x, ch, cw); }
-  CATCH_HD static void advance(Cursor& c, int W, int ch, int cw) { freeway_advance(c, W, ch, cw); }
-  CATCH_HD static uint8_t pixel(const View& v, const Cursor& c, int ch, int cw) { (void)ch; (void)cw; return freeway_pixel(v, c); }
+  SDQN_HD static void init(State& s, uint64_t seed) { freeway_init(s, seed); }
+  SDQN_HD static void restart(State& s) { freeway_restart(s); }
+  SDQN_HD static int step(State& s, int action, int episode_ticks, int& lost) { return freeway_step(s, action, episode_ticks, lost); }   // caught = crossings, missed = hits
+  SDQN_HD static View view(const State& s) { return freeway_view(s); }
+  SDQN_HD static bool valid(const State& s) { return freeway_state_valid(s); }
+  SDQN_HD static void render(const View& v, uint8_t* out, int H, int W) { freeway_render(v, out, H, W); }
+  SDQN_HD static void pack(const View& v, int* w) { w[0] = v.row; w[1] = (int)(uint32_t)v.cars; w[2] = (int)(uint32_t)(v.cars >> 32); }
+  SDQN_HD static View unpack(const int* w) { View v; v.row = w[0]; v.cars = (uint64_t)(uint32_t)w[1] | ((uint64_t)(uint32_t)w[2] << 32); return v; }
+  SDQN_HD static Cursor cursor(int y, int x, int ch, int cw) { return freeway_cursor(y, x, ch, cw); }
+  SDQN_HD static void advance(Cursor& c, int W, int ch, int cw) { freeway_advance(c, W, ch, cw); }
+  SDQN_HD static uint8_t pixel(const View& v, const Cursor& c, int ch, int cw) { (void)ch; (void)cw; return freeway_pixel(v, c); }
 };
 
 }  // namespace sdqn

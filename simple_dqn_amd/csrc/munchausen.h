@@ -10,14 +10,14 @@
 #pragma once
 #include <stdint.h>
 #include <math.h>
-#include "env_catch.h"
+#include "hd.h"
 
 namespace sdqn {
 
 // lse of one Q row.  Every term of the sum lies in (0, 1] and the maximum's is 1: never inf, s >= 1.  A = 1: exp(0) = 1, log(1) = +0, so
 // lse == q[0] exactly.  The maximum is taken in double with a comparison on both paths
 template <typename T>
-CATCH_HD double soft_value(const T* q, int A, double tau) {
+SDQN_HD double soft_value(const T* q, int A, double tau) {
   double v = (double)q[0];
   for (int k = 1; k < A; ++k) { const double x = (double)q[k]; v = x > v ? x : v; }
   double s = 0.0;
@@ -27,14 +27,14 @@ CATCH_HD double soft_value(const T* q, int A, double tau) {
 // alpha clip(tau ln pi(act | s), l0, 0) from qbar(s): the log-policy term is <= 0 up to rounding and exactly 0 for a unique maximiser far
 // above the rest
 template <typename T>
-CATCH_HD double munchausen_bonus(const T* q_pre, int A, int act, double alpha, double tau, double l0) {
+SDQN_HD double munchausen_bonus(const T* q_pre, int A, int act, double alpha, double tau, double l0) {
   const double lp = (double)q_pre[act] - soft_value(q_pre, A, tau);
   return alpha * (lp < l0 ? l0 : (lp > 0.0 ? 0.0 : lp));
 }
 // the target y of one sample from the rows qbar(s) and qbar(s'); r: the clipped reward or the n-step return; gam: the discount or
 // discount^n.  *V receives the soft value of the poststate
 template <typename T>
-CATCH_HD double munchausen_target(const T* q_pre, const T* q_post, int A, int act, double r, int terminal, double gam, double alpha, double tau,
+SDQN_HD double munchausen_target(const T* q_pre, const T* q_post, int A, int act, double r, int terminal, double gam, double alpha, double tau,
                                   double l0, double* V) {
   *V = soft_value(q_post, A, tau);
   const double rm = r + munchausen_bonus(q_pre, A, act, alpha, tau, l0);      // the bonus is added on terminal transitions too

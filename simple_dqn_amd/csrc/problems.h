@@ -22,27 +22,15 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <math.h>
-
-#if defined(__HIPCC__)
-#define SDQN_HD __host__ __device__ inline
-#else
-#define SDQN_HD inline
-#endif
+#include "hd.h"
+#include "net_layout.h"      // K1..K3, CRS1..3, PIX1..3, NFC, NIN4, NW1..4, OFF1..OFF5: the layers and the flat buffer
 
 namespace sdqn {
 
 constexpr int H0 = 84, W0 = 84, C0 = 4;
 constexpr int FRAME = H0 * W0;          // 7056 B
 constexpr int STATE = C0 * FRAME;       // 28224 B
-constexpr int ST1 = 4, P1 = 20, Q1 = 20, K1 = 32;   // conv 8x8 s4   deepqnetwork.py:83
-constexpr int ST2 = 2, P2 = 9, Q2 = 9, K2 = 64;     // conv 4x4 s2   :85
-constexpr int P3 = 7, Q3 = 7, K3 = 64;              // conv 3x3 s1   :87
-constexpr int PIX1 = P1 * Q1, PIX2 = P2 * Q2, PIX3 = P3 * Q3;
-constexpr int CRS1 = 256, CRS2 = 512, CRS3 = 576;
-constexpr int NFC = 512, NIN4 = PIX3 * K3;          // Affine 512    :89
 constexpr int PD3 = 11, PD2 = 11;                   // padded delta planes
-constexpr int NW1 = CRS1 * K1, NW2 = CRS2 * K2, NW3 = CRS3 * K3, NW4 = NIN4 * NFC;
-constexpr int OFF1 = 0, OFF2 = OFF1 + NW1, OFF3 = OFF2 + NW2, OFF4 = OFF3 + NW3, OFF5 = OFF4 + NW4;
 constexpr int MAX_ACTIONS = 18;
 // --batch_norm: BatchNorm after conv1..3 and fc4 (features per layer), parameter block appended to the flat buffers:
 // [beta_l | gamma_l] per layer at BN_OFF(l), then the running statistics [gmean_l | gvar_l] at BN_PARAMS + BN_OFF(l)

@@ -8,28 +8,28 @@
 //   acting      : Q(s, a) = (sum_j theta_j[a]) / N as a sum of T in quantile order           (quantile_action_value)
 #pragma once
 #include <stdint.h>
-#include "env_catch.h"
+#include "hd.h"
 
 namespace sdqn {
 
 template <typename T>
-CATCH_HD T quantile_tau(int j, int N) { return (T)((double)(2 * j + 1) / (double)(2 * N)); }
+SDQN_HD T quantile_tau(int j, int N) { return (T)((double)(2 * j + 1) / (double)(2 * N)); }
 
 template <typename T>
-CATCH_HD double quantile_mean(const T* q, int N, int A, int a) {
+SDQN_HD double quantile_mean(const T* q, int N, int A, int a) {
   double s = 0.0;
   for (int j = 0; j < N; ++j) s += (double)q[j * A + a];
   return s / (double)N;
 }
 template <typename T>
-CATCH_HD int quantile_greedy(const T* q, int N, int A, double* m_best) {
+SDQN_HD int quantile_greedy(const T* q, int N, int A, double* m_best) {
   int best = 0; double bv = quantile_mean(q, N, A, 0);
   for (int a = 1; a < A; ++a) { const double v = quantile_mean(q, N, A, a); if (v > bv) { bv = v; best = a; } }
   *m_best = bv;
   return best;
 }
 template <typename T>
-CATCH_HD void quantile_pair(T delta, T tau, T kappa, T* g, T* rho) {
+SDQN_HD void quantile_pair(T delta, T tau, T kappa, T* g, T* rho) {
   const T w = delta > (T)0 ? (T)1 - tau : tau;
   const T ad = delta < (T)0 ? -delta : delta;
   const T dc = delta < -kappa ? -kappa : (delta > kappa ? kappa : delta);
@@ -38,14 +38,14 @@ CATCH_HD void quantile_pair(T delta, T tau, T kappa, T* g, T* rho) {
   *rho = (w * L) / kappa;
 }
 template <typename T>
-CATCH_HD T quantile_action_value(const T* q, int N, int A, int a) {
+SDQN_HD T quantile_action_value(const T* q, int N, int A, int a) {
   T s = (T)0;
   for (int j = 0; j < N; ++j) s += q[j * A + a];
   return s / (T)N;
 }
 // the acting rule on one raw row q[N A]: the first maximum of the action values, a NaN counts as one (sdqn_net_act_greedy's rule)
 template <typename T>
-CATCH_HD int quantile_act(const T* q, int N, int A) {
+SDQN_HD int quantile_act(const T* q, int N, int A) {
   int best = 0; T bv = quantile_action_value(q, N, A, 0);
   for (int a = 1; a < A; ++a) { const T v = quantile_action_value(q, N, A, a); if (v > bv || (v != v && bv == bv)) { bv = v; best = a; } }
   return best;
@@ -55,7 +55,7 @@ CATCH_HD int quantile_act(const T* q, int N, int A) {
 // spreads the same operations over threads, in the same order per result).  r: the clipped reward or the n-step return; gam: the discount
 // or discount^n.  dq[N A] receives the row, targets[N] (may be null) the targets in T; returns the cost term, *maxq = (T) m(a*).
 template <typename T>
-CATCH_HD T quantile_sample(const T* q_pre, const T* q_post, int N, int A, int act, double r, int terminal, double gam, T kappa,
+SDQN_HD T quantile_sample(const T* q_pre, const T* q_post, int N, int A, int act, double r, int terminal, double gam, T kappa,
                            T* dq, T* targets, T* maxq) {
   double mb; const int as = quantile_greedy(q_post, N, A, &mb);
   *maxq = (T)mb;

@@ -922,13 +922,13 @@ static bool noisy_stream_ok(int slot, int layer, int side, int64_t n) { return (
 extern "C" int sdqn_noisy_words(uint64_t seed, uint64_t step, int slot, int layer, int side, int64_t n, uint64_t* out_words) {
   ARGCHK(out_words && noisy_stream_ok(slot, layer, side, n), "noise stream: slot 0 / 1, layer 0 (fc4) / 1 (fc5), side 0 (inputs) / 1 (outputs), n >= 0");
   const uint64_t key = noisy_key(seed, step, slot, layer, side);
-  for (int64_t i = 0; i < n; ++i) out_words[i] = noisy_word(key, (uint64_t)i);
+  for (int64_t i = 0; i < n; ++i) out_words[i] = stream_keyed(key, (uint64_t)i);
   return SDQN_OK;
 }
 extern "C" int sdqn_noisy_noise(uint64_t seed, uint64_t step, int slot, int layer, int side, int64_t n, float* out_z) {
   ARGCHK(out_z && noisy_stream_ok(slot, layer, side, n), "noise stream: slot 0 / 1, layer 0 (fc4) / 1 (fc5), side 0 (inputs) / 1 (outputs), n >= 0");
   const uint64_t key = noisy_key(seed, step, slot, layer, side);
-  for (int64_t i = 0; i < n; ++i) out_z[i] = noisy_normal(noisy_word(key, (uint64_t)i));
+  for (int64_t i = 0; i < n; ++i) out_z[i] = noisy_normal(stream_keyed(key, (uint64_t)i));
   return SDQN_OK;
 }
 

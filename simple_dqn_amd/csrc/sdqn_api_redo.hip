@@ -9,7 +9,7 @@
 static int redo_buffers(sdqn_net_s* h) {
   if (h->redo_scores) return SDQN_OK;
   int rc = dalloc(h, (void**)&h->redo_partial, (size_t)redo_partial_doubles(h->B) * 8); if (rc) return rc;
-  rc = dalloc(h, (void**)&h->redo_scores, (size_t)REDO_UNITS * 4); if (rc) return rc;
+  rc = dalloc(h, (void**)&h->redo_scores, (size_t)RELU_UNITS * 4); if (rc) return rc;
   return dalloc(h, (void**)&h->redo_info, 6 * 8);
 }
 static int redo_scores_enqueue(sdqn_net_s* h) {
@@ -62,7 +62,7 @@ extern "C" int sdqn_net_redo_scores(sdqn_net_t h, float* out) {
   ARGCHK(h && out, "NULL argument");
   int rc = refuse_feature(h, FEAT_REDO, "redo_scores"); if (rc) return rc;
   rc = redo_scores_enqueue(h); if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(out, h->redo_scores, (size_t)REDO_UNITS * 4, hipMemcpyDeviceToHost, g_stream));
+  HIPCHK(hipMemcpyAsync(out, h->redo_scores, (size_t)RELU_UNITS * 4, hipMemcpyDeviceToHost, g_stream));
   HIPCHK(hipStreamSynchronize(g_stream));
   return per_check_all();
 }
@@ -79,13 +79,9 @@ extern "C" int sdqn_redo_apply_host(const float* scores, double tau, uint64_t se
   ARGCHK(scores && theta, "NULL argument");
   ARGCHK(A >= 1 && A <= MAX_ACTIONS, "num_actions must be in 1..%d (got %d)", MAX_ACTIONS, A);
   ARGCHK(tau >= 0.0 && tau < 1.0, "redo_threshold %g: must be in [0, 1)", tau);
-  redo_apply_host(scores, tau, seed, event, REDO_OFF5 + (int64_t)A * NFC, theta, state, state2, counts);
+  redo_apply_host(scores, tau, seed, event, OFF5 + (int64_t)A * NFC, theta, state, state2, counts);
   return SDQN_OK;
 }
 extern "C" int sdqn_redo_draw(uint64_t seed, uint64_t event, int64_t index, int layer, uint64_t* word, float* value) {
-  ARGCHK(index >= 0 && layer >= 1 && layer <= REDO_LAYERS, "bad arguments (index %lld, layer %d of 1..4)", (long long)index, layer);
-  const uint64_t key = redo_key(seed, event);
-  if (word) *word = redo_word(key, (uint64_t)index);
-  if (value) *value = redo_draw(key, (uint64_t)index, layer);
-  return SDQN_OK;
+  return keyed_init_draw(redo_key(seed, event), index, layer, REDO_LAYERS, word, value);
 }

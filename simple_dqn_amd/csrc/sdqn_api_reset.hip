@@ -65,13 +65,9 @@ extern "C" int sdqn_reset_apply_host(int layers, double alpha, uint64_t seed, ui
   ARGCHK(optimizer >= 0 && optimizer <= 2, "optimizer %d: 0 rmsprop, 1 adam, 2 adadelta", optimizer);
   int rc = reset_rule_check(layers, alpha); if (rc) return rc;
   ARGCHK(optimizer == 0 || state2, "optimizer %d keeps a second state: state2 is NULL", optimizer);
-  reset_apply_host(layers, alpha, seed, event, REDO_OFF5 + (int64_t)A * NFC, theta, theta_t, state, optimizer == 0 ? nullptr : state2);
+  reset_apply_host(layers, alpha, seed, event, OFF5 + (int64_t)A * NFC, theta, theta_t, state, optimizer == 0 ? nullptr : state2);
   return SDQN_OK;
 }
 extern "C" int sdqn_reset_draw(uint64_t seed, uint64_t event, int64_t index, int layer, uint64_t* word, float* value) {
-  ARGCHK(index >= 0 && layer >= 1 && layer <= RESET_LAYERS, "bad arguments (index %lld, layer %d of 1..5)", (long long)index, layer);
-  const uint64_t key = reset_key(seed, event);
-  if (word) *word = redo_word(key, (uint64_t)index);
-  if (value) *value = reset_draw(key, (uint64_t)index, layer);
-  return SDQN_OK;
+  return keyed_init_draw(reset_key(seed, event), index, layer, RESET_LAYERS, word, value);
 }

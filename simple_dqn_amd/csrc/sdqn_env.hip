@@ -21,7 +21,7 @@ struct sdqn_env_s {
   double p = 0.0;                          // its integer form ceil(p 2^53)
   uint64_t thresh_p = 0;
   int32_t prev = 0;                        // the action the last tick executed (0 after create / restart)
-  uint64_t sticky_rng = 0;                 // the sticky generator: catch_stream_seed(seed, 0, 2) at create
+  uint64_t sticky_rng = 0;                 // the sticky generator: stream_seed(seed, 0, 2) at create
   std::vector<uint8_t> frame;              // the host-rendered frame of the state (valid while frame_ok)
   bool frame_ok = false;
   template <class G> typename G::State& st();
@@ -125,9 +125,9 @@ __device__ __forceinline__ void env_lockstep(const EvalArgs& a, const CollectArg
     EvalRec<G> r = envs[e];
     int restart = 0;
     if (a.init) {
-      G::init(r.s, catch_stream_seed(a.seed, (uint64_t)e, 0));
-      r.act_rng = catch_stream_seed(a.seed, (uint64_t)e, 1);
-      r.sticky_rng = catch_stream_seed(a.seed, (uint64_t)e, DYNAMICS_STICKY_STREAM); r.prev = 0; r.pad_ = 0;
+      G::init(r.s, stream_seed(a.seed, (uint64_t)e, 0));
+      r.act_rng = stream_seed(a.seed, (uint64_t)e, 1);
+      r.sticky_rng = stream_seed(a.seed, (uint64_t)e, DYNAMICS_STICKY_STREAM); r.prev = 0; r.pad_ = 0;
       r.steps = r.reward = r.caught = r.missed = r.episodes = 0;
       restart = 1;
     } else {
@@ -238,7 +238,7 @@ extern "C" int sdqn_env_create(sdqn_env_t* out, const char* name, int H, int W, 
   sdqn_env_s* e = new sdqn_env_s();
   e->game = game;
   e->H = H; e->W = W; e->bpe = balls_per_episode; e->frame.assign((size_t)H * W, 0);
-  e->sticky_rng = catch_stream_seed(seed, 0, DYNAMICS_STICKY_STREAM);
+  e->sticky_rng = stream_seed(seed, 0, DYNAMICS_STICKY_STREAM);
   GAME_CALL(e, env_init, e, seed);
   *out = e; return SDQN_OK;
 }

@@ -12,7 +12,7 @@
 namespace sdqn {
 namespace {
 
-static_assert(K3 == 64 && PIX3 == 49 && NIN4 == NOISY_IN4 && NFC == NOISY_OUT4 && NFC == NOISY_IN5 && NFC == 512, "noisy.h restates the fc4 / fc5 geometry");
+static_assert(K3 == 64 && PIX3 == 49, "noisy_fc4_input");
 static_assert(MAX_ACTIONS <= NOISY_OUT5_PAD && OFF4 % 4 == 0 && OFF5 % 4 == 0 && NOISY_EPS_OUT4 % 4 == 0 && NOISY_EPS_IN5 % 4 == 0, "16-byte pieces");
 constexpr int NOISY_THREADS = 256, NOISY_GRID = 512;
 

@@ -16,8 +16,6 @@
 
 namespace sdqn {
 
-static_assert(REDO_OFF2 == OFF2 && REDO_OFF3 == OFF3 && REDO_OFF4 == OFF4 && REDO_OFF5 == OFF5, "redo.h restates the flat buffer's layer boundaries");
-static_assert(redo_n(0) == K1 && redo_n(1) == K2 && redo_n(2) == K3 && redo_n(3) == NFC, "units per layer");
 static_assert(redo_pix(0) == PIX1 && redo_pix(1) == PIX2 && redo_pix(2) == PIX3, "rows per sample");
 
 namespace {
@@ -66,8 +64,8 @@ __global__ void __launch_bounds__(256) redo_partial_kernel(const RedoScoreArgs a
   __shared__ double sh[8 * 256];
   int b = blockIdx.x, l = 0;
   double* out = a.partial;
-  while (l < REDO_LAYERS - 1 && b >= redo_blocks(l, a.B)) { b -= redo_blocks(l, a.B); out += (int64_t)redo_blocks(l, a.B) * redo_n(l); ++l; }
-  out += (int64_t)b * redo_n(l);
+  while (l < REDO_LAYERS - 1 && b >= redo_blocks(l, a.B)) { b -= redo_blocks(l, a.B); out += (int64_t)redo_blocks(l, a.B) * relu_units(l); ++l; }
+  out += (int64_t)b * relu_units(l);
   const int64_t rows = (int64_t)a.B * redo_pix(l);
   if (l == 3) { partial_cols<float, NFC>(static_cast<const float*>(a.a[3]), rows, b, redo_chunk(3), out, sh); return; }
   if (a.half123) {
@@ -82,9 +80,9 @@ static_assert(K2 == K3, "conv2 and conv3 share an instantiation");
 
 __global__ void __launch_bounds__(512) redo_finish_kernel(const RedoScoreArgs a) {
   __shared__ double sh[512];
-  const int l = blockIdx.x, n = redo_n(l), j = threadIdx.x, nb = redo_blocks(l, a.B);
+  const int l = blockIdx.x, n = relu_units(l), j = threadIdx.x, nb = redo_blocks(l, a.B);
   const double* part = a.partial;
-  for (int k = 0; k < l; ++k) part += (int64_t)redo_blocks(k, a.B) * redo_n(k);
+  for (int k = 0; k < l; ++k) part += (int64_t)redo_blocks(k, a.B) * relu_units(k);
   double m = 0.0;
   if (j < n) {
     for (int b = 0; b < nb; ++b) m = m + part[(int64_t)b * n + j];
@@ -97,17 +95,17 @@ __global__ void __launch_bounds__(512) redo_finish_kernel(const RedoScoreArgs a)
     __syncthreads();
   }
   const double mean = sh[0] / (double)n;
-  if (j < n) a.scores[redo_soff(l) + j] = mean > 0.0 ? (float)(m / mean) : 0.0f;
+  if (j < n) a.scores[relu_off(l) + j] = mean > 0.0 ? (float)(m / mean) : 0.0f;
 }
 
 __global__ void __launch_bounds__(256) redo_apply_kernel(const RedoApplyArgs a) {
-  __shared__ float sc[REDO_UNITS];
-  for (int k = threadIdx.x; k < REDO_UNITS; k += 256) sc[k] = a.scores[k];
+  __shared__ float sc[RELU_UNITS];
+  for (int k = threadIdx.x; k < RELU_UNITS; k += 256) sc[k] = a.scores[k];
   __syncthreads();
   if (blockIdx.x == 0 && threadIdx.x < REDO_LAYERS) {
     const int l = threadIdx.x;
     int64_t c = 0;
-    for (int k = redo_soff(l); k < redo_soff(l + 1); ++k) c += redo_dormant(sc[k], a.tau) ? 1 : 0;
+    for (int k = relu_off(l); k < relu_off(l + 1); ++k) c += redo_dormant(sc[k], a.tau) ? 1 : 0;
     a.info[2 + l] = c;
     if (l == 0) { a.info[0] = (int64_t)a.event; a.info[1] = a.step; }
   }
@@ -147,7 +145,7 @@ hipError_t launch_redo_scores(const RedoScoreArgs& a, int stage, hipStream_t s) 
   return hipGetLastError();
 }
 hipError_t launch_redo_apply(const RedoApplyArgs& a, hipStream_t s) {
-  if (a.n < REDO_OFF5 || (a.n & 3) || !a.scores || !a.theta || !a.state || !a.info) return hipErrorInvalidValue;
+  if (a.n < OFF5 || (a.n & 3) || !a.scores || !a.theta || !a.state || !a.info) return hipErrorInvalidValue;
   int64_t blocks = ((a.n >> 2) + 255) / 256;
   if (blocks > 2048) blocks = 2048;
   SDQN_LAUNCH(redo_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a);

@@ -24,7 +24,6 @@ constexpr int TK = 64, TN = 32;                        // tile: k rows x n colum
 constexpr int TROW = TK + 2;                           // LDS row of the transposed tile (uint16; 132 B: 4-byte aligned, off the bank stride)
 static_assert(CRS1 % TK == 0 && CRS2 % TK == 0 && CRS3 % TK == 0 && NIN4 % TK == 0, "every layer is whole tiles along k");
 static_assert(K1 % TN == 0 && K2 % TN == 0 && K3 % TN == 0 && NFC % TN == 0, "every layer is whole tiles along n");
-static_assert(OFF2 == REDO_OFF2 && OFF3 == REDO_OFF3 && OFF4 == REDO_OFF4 && OFF5 == REDO_OFF5, "regularize.h counts the weights with redo.h's boundaries");
 static_assert(OFF2 % 4 == 0 && OFF5 % 4 == 0 && NFC % 4 == 0, "the element-wise part is whole float4s");
 constexpr int TILES1 = (CRS1 / TK) * (K1 / TN), TILES2 = (CRS2 / TK) * (K2 / TN), TILES3 = (CRS3 / TK) * (K3 / TN), TILES4 = (NIN4 / TK) * (NFC / TN);
 

@@ -14,7 +14,6 @@
 
 namespace sdqn {
 
-static_assert(REDO_OFF2 == OFF2 && REDO_OFF3 == OFF3 && REDO_OFF4 == OFF4 && REDO_OFF5 == OFF5, "redo.h restates the flat buffer's layer boundaries");
 static_assert((OFF2 & 3) == 0 && (OFF3 & 3) == 0 && (OFF4 & 3) == 0 && (OFF5 & 3) == 0 && (NFC & 3) == 0, "a 16-byte piece lies in one layer");
 
 namespace {
@@ -31,7 +30,7 @@ __global__ void __launch_bounds__(256) reset_apply_kernel(const ResetApplyArgs a
   const reset_f4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
   for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < n4; p += (int64_t)gridDim.x * 256) {
     const int64_t i0 = first + p * 4;                                  // i0 + 3 < n
-    const int L = reset_layer(i0), act = reset_action(r, L);
+    const int L = layer_of(i0), act = reset_action(r, L);
     if (!act) continue;
     reset_f4 w = zero, wt = zero;
     if (act == 2) {
@@ -54,9 +53,9 @@ __global__ void __launch_bounds__(256) reset_apply_kernel(const ResetApplyArgs a
 }  // namespace
 
 hipError_t launch_reset_apply(const ResetApplyArgs& a, hipStream_t s) {
-  if (a.n < REDO_OFF5 + NFC || (a.n & 3) || !a.theta || !a.state || !a.info) return hipErrorInvalidValue;
+  if (a.n < OFF5 + NFC || (a.n & 3) || !a.theta || !a.state || !a.info) return hipErrorInvalidValue;
   if (a.layers < 0 || a.layers > RESET_LAYERS || !(a.alpha >= 0.0 && a.alpha <= 1.0) || reset_noop(a.layers, a.alpha)) return hipErrorInvalidValue;
-  const int64_t first = reset_first(a.layers, a.alpha);                // <= REDO_OFF5 < n: at least fc5 is in the tail
+  const int64_t first = reset_first(a.layers, a.alpha);                // <= OFF5 < n: at least fc5 is in the tail
   if (first < 0 || first >= a.n || (first & 3)) return hipErrorInvalidValue;
   int64_t blocks = (((a.n - first) >> 2) + 255) / 256;
   if (blocks > 2048) blocks = 2048;

@@ -4,28 +4,27 @@
 //
 //   shift   sample n of train step t, state s (0 prestate, 1 poststate) draws (dy, dx) in [-P, P]^2; output pixel (y, x) of every frame of
 //           that state is input pixel (clamp(y + dy, 0, H - 1), clamp(x + dx, 0, W - 1)): replicate-padding by P, crop at (P + dy, P + dx)
-//   stream  splitmix64 (env_catch.h: catch_mix / catch_next) started at
-//             k  = catch_mix(seed + 0x9E3779B97F4A7C15 * (t + 1))
-//             s0 = catch_mix(k + 0xD1B54A32D192ED03 * (2 n + s + 1))
-//           all sums and products modulo 2^64; the first output z0 gives dy = (int)(z0 % (2P + 1)) - P, the second z1 gives dx likewise
+//   stream  the project's generator (stream.h) started at
+//             k  = stream_keyed(seed, t)          = mix(seed + G (t + 1))
+//             s0 = stream_seed(k, n, s)           = mix(k + STREAM_MUL (2 n + s + 1))
+//           the first output z0 gives dy = (int)(z0 % (2P + 1)) - P, the second z1 gives dx likewise
 #pragma once
-#include "env_catch.h"
+#include "stream.h"
 
 namespace sdqn {
 
 constexpr int SHIFT_MAX_PAD = 8;
 
-CATCH_HD uint64_t shift_stream(uint64_t seed, uint64_t step, uint64_t n, uint64_t s) {
-  const uint64_t k = catch_mix(seed + 0x9E3779B97F4A7C15ull * (step + 1));
-  return catch_mix(k + 0xD1B54A32D192ED03ull * (2 * n + s + 1));
+SDQN_HD uint64_t shift_stream(uint64_t seed, uint64_t step, uint64_t n, uint64_t s) {
+  return stream_seed(stream_keyed(seed, step), n, s);
 }
-CATCH_HD void shift_draw(uint64_t seed, uint64_t step, uint64_t n, uint64_t s, int P, int& dy, int& dx) {
+SDQN_HD void shift_draw(uint64_t seed, uint64_t step, uint64_t n, uint64_t s, int P, int& dy, int& dx) {
   uint64_t g = shift_stream(seed, step, n, s);
   const uint64_t m = (uint64_t)(2 * P + 1);
-  dy = (int)(catch_next(g) % m) - P;
-  dx = (int)(catch_next(g) % m) - P;
+  dy = (int)(stream_next(g) % m) - P;
+  dx = (int)(stream_next(g) % m) - P;
 }
-CATCH_HD int shift_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+SDQN_HD int shift_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 // sdqn_shift.hip: one launch writes the B shifted prestates and the B shifted poststates of the step into pre | post
 struct ShiftArgs {

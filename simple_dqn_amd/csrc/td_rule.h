@@ -9,7 +9,7 @@
 #pragma once
 #include <stdint.h>
 #include <math.h>
-#include "env_catch.h"
+#include "hd.h"
 
 namespace sdqn {
 
@@ -18,17 +18,17 @@ namespace sdqn {
 // skipped, a NaN error becomes -clip).  A rule that needs either takes the variant as a template parameter; neither is the other's fallback.
 template <typename T>
 struct CompareOps {
-  static CATCH_HD T max(T m, T v) { return v > m ? v : m; }
-  static CATCH_HD T clip(T e, T c) { return e < -c ? -c : (e > c ? c : e); }
+  static SDQN_HD T max(T m, T v) { return v > m ? v : m; }
+  static SDQN_HD T clip(T e, T c) { return e < -c ? -c : (e > c ? c : e); }
 };
 struct FminmaxOps {
-  static CATCH_HD float max(float m, float v) { return fmaxf(m, v); }
-  static CATCH_HD float clip(float e, float c) { return fminf(fmaxf(e, -c), c); }
+  static SDQN_HD float max(float m, float v) { return fmaxf(m, v); }
+  static SDQN_HD float clip(float e, float c) { return fminf(fmaxf(e, -c), c); }
 };
 
 // the reward and the discount of a target: the clipped reward and gamma, or (--n_step) the return R, which `rew` holds as a double's bits
 // (clipped per step), and gamma^n.  The generic path's counterpart of head_body.h's head_reward
-CATCH_HD void td_reward(int64_t rew, int nstep, double discount, double gamma_n, double minr, double maxr, double* r, double* gam) {
+SDQN_HD void td_reward(int64_t rew, int nstep, double discount, double gamma_n, double minr, double maxr, double* r, double* gam) {
   if (nstep > 1) { *r = __builtin_bit_cast(double, rew); *gam = gamma_n; return; }
   const double x = (double)rew;
   *r = x < minr ? minr : (x > maxr ? maxr : x);                                // np.clip(rewards, min_reward, max_reward) :136
@@ -37,7 +37,7 @@ CATCH_HD void td_reward(int64_t rew, int nstep, double discount, double gamma_n,
 
 // be.max(postq, axis=0) :124, or with q_sel = Q(theta, s') the target net's Q at the online net's first maximum
 template <typename T>
-CATCH_HD T td_post_value(const T* q_post, const T* q_sel, int A) {
+SDQN_HD T td_post_value(const T* q_post, const T* q_sel, int A) {
   if (q_sel) {
     int best = 0; T bv = q_sel[0];
     for (int a = 1; a < A; ++a) { const T v = q_sel[a]; if (v > bv) { bv = v; best = a; } }
@@ -47,12 +47,12 @@ CATCH_HD T td_post_value(const T* q_post, const T* q_sel, int A) {
   for (int a = 1; a < A; ++a) m = CompareOps<T>::max(m, q_post[a]);
   return m;
 }
-CATCH_HD double td_target(double r, int terminal, double gam, double m) { return terminal ? r : r + gam * m; }     // :139-143, python float arithmetic
+SDQN_HD double td_target(double r, int terminal, double gam, double m) { return terminal ? r : r + gam * m; }     // :139-143, python float arithmetic
 
 // everything behind the target y: dq[A] receives the row, *prio (with per != 0) the new priority; returns the cost term.  w: the importance
 // weight of a prioritized memory (per != 0), else unused
 template <typename T>
-CATCH_HD T td_sample(const T* q_pre, int A, int act, double y, T clip, int per, T w, double per_alpha, double per_eps, T* dq, float* prio) {
+SDQN_HD T td_sample(const T* q_pre, int A, int act, double y, T clip, int per, T w, double per_alpha, double per_eps, T* dq, float* prio) {
   const T target = (T)y;                                                       // stored into the backend dtype
   T d = (T)0;
   for (int a = 0; a < A; ++a) {

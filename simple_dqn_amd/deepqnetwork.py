@@ -28,6 +28,21 @@ def layer_shapes(num_actions, history_length=4, screen_height=84, screen_width=8
 
 
 MAX_ACTIONS = 18                                          # outputs of the library's head kernels (csrc/problems.h)
+# the tuned net's geometry as csrc/net_layout.h states it: the ReLU units of conv1, conv2, conv3, fc4 (RELU_UNITS there is their sum) and
+# the flat buffer's length in front of fc5 (OFF5)
+REDO_UNITS = tuple(s[1] for s in layer_shapes(1)[:3]) + (layer_shapes(1)[3][0],)
+FLAT_OFF5 = sum(r * c for r, c in layer_shapes(1)[:4])
+
+
+def _flat_size(num_outputs):
+    rows, cols = layer_shapes(int(num_outputs))[4]
+    return FLAT_OFF5 + rows * cols
+
+
+def _keyed_draw(fn, seed, event, index, layer):
+    w, v = C.c_uint64(), C.c_float()
+    _lib.check(fn(int(seed) & 0xFFFFFFFFFFFFFFFF, int(event), int(index), int(layer), C.byref(w), C.byref(v)))
+    return w.value, np.float32(v.value)
 
 
 # ---- which flags combine ---------------------------------------------------------------------------------------------
@@ -213,9 +228,6 @@ def refuse_net_properties(args, flag, batch_norm, noisy_nets, float64):
                          % ((flag,) + geom))
 
 
-REDO_UNITS = (32, 64, 64, 512)                            # ReLU units of conv1, conv2, conv3, fc4 (csrc/redo.h)
-
-
 def check_redo(args):
     """--redo_interval N / --redo_threshold T / --log_dormant: N >= 0 (0: off), T in [0, 1), and recycling or the dormancy
     read-out with none of --batch_norm, --noisy_nets, --datatype float64 or screens other than 84 x 84 x 4 (the generic path).  Raises
@@ -239,9 +251,7 @@ def check_redo(args):
 def redo_draw(seed, event, index, layer):
     """--redo_interval: (the splitmix64 word, the float32 draw) of flat internal index `index` in layer 1..4 at recycle event `event`,
     restated on the host (csrc/redo.h; no device)"""
-    w, v = C.c_uint64(), C.c_float()
-    _lib.check(_lib.load().sdqn_redo_draw(int(seed) & 0xFFFFFFFFFFFFFFFF, int(event), int(index), int(layer), C.byref(w), C.byref(v)))
-    return w.value, np.float32(v.value)
+    return _keyed_draw(_lib.load().sdqn_redo_draw, seed, event, index, layer)
 
 
 def redo_apply_host(scores, tau, seed, event, num_outputs, theta, state=None, state2=None):
@@ -249,7 +259,7 @@ def redo_apply_host(scores, tau, seed, event, num_outputs, theta, state=None, st
     num_outputs values, changed in place; csrc/redo.h, no device).  Returns the four dormant counts."""
     sc = np.ascontiguousarray(scores, dtype=np.float32).reshape(-1)
     assert sc.size == sum(REDO_UNITS)
-    n = 1683456 + 512 * int(num_outputs)
+    n = _flat_size(num_outputs)
     for b in (theta, state, state2):
         assert b is None or (b.dtype == np.float32 and b.flags.c_contiguous and b.flags.writeable and b.size == n)
     counts = np.zeros(4, np.int64)
@@ -290,15 +300,13 @@ def check_reset(args):
 def reset_draw(seed, event, index, layer):
     """--reset_interval: (the splitmix64 word, the float32 draw) of flat internal index `index` in layer 1..5 at reset event `event`,
     restated on the host (csrc/reset.h; no device)"""
-    w, v = C.c_uint64(), C.c_float()
-    _lib.check(_lib.load().sdqn_reset_draw(int(seed) & 0xFFFFFFFFFFFFFFFF, int(event), int(index), int(layer), C.byref(w), C.byref(v)))
-    return w.value, np.float32(v.value)
+    return _keyed_draw(_lib.load().sdqn_reset_draw, seed, event, index, layer)
 
 
 def reset_apply_host(layers, alpha, seed, event, num_outputs, optimizer, theta, theta_t=None, state=None, state2=None):
     """--reset_interval: one reset event on host arrays in the library's internal layouts (flat float32 buffers of 1 683 456 + 512 x
     num_outputs values, changed in place; csrc/reset.h, no device).  theta_t None or theta itself: a net without a target net."""
-    n = 1683456 + 512 * int(num_outputs)
+    n = _flat_size(num_outputs)
     for b in (theta, theta_t, state, state2):
         assert b is None or (b.dtype == np.float32 and b.flags.c_contiguous and b.flags.writeable and b.size == n)
     p = lambda b: None if b is None else _lib.ptr(b, C.c_float)
